@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- LM iterations/sec of the MI355X-native bundle-adjustment path on synthetic sequences.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 2|3|4|5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 2|3|4|5] [--no-cpu-baseline] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 needs nothing else: when the script is not already running under torch.distributed.run (WORLD_SIZE unset)
 it starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a
@@ -15,7 +15,7 @@ synchronisation, MAX over ranks.  N > 1: launched by `python -m torch.distribute
 is sharded by frame range over the ranks (strong scaling), one RCCL all-reduce of the reduced system per damped solve.
 
 Default workload = BASELINE.json's metric configuration: 8 cameras / 40 markers / 500 frames (configs[2], SURVEY "config 3").
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  `--dump-outputs DIR` also writes what the last timed solve returned to its caller (rank 0, see dump_outputs()).
 """
 import argparse
 import json
@@ -99,6 +99,27 @@ def run_steps(problem, x0, steps, params_factory):
         done += rep["iterations"]
         trials += rep["trial_points"]
     return done, trials, x, rep
+
+
+DUMP_REPORT_FIELDS = ("iterations", "stop_code", "initial_err", "final_err", "final_mu", "trial_points")
+
+
+def dump_outputs(out_dir, x, rep):
+    """--dump-outputs: the arrays the last solve of the timed region handed back to its caller -- the full parameter vector and the scalars of its report
+    (solve_seconds, a timing, and the one-entry trace left out) -- as DIR/<name>.npy in float64.  The inputs are the seeded synthetic workload, so two builds
+    given the same flags can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), np.asarray(x, dtype=np.float64))
+    for k in DUMP_REPORT_FIELDS:
+        np.save(os.path.join(out_dir, k + ".npy"), np.array([rep[k]], dtype=np.float64))
+
+
+def positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return v
 
 
 def kernel_source_hash():
@@ -669,7 +690,7 @@ def plumbing_only(args, world, rank, dist):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--steps", type=positive_int, default=1000, help="LM iterations in the timed region (exactly this many)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", type=int, default=3, choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -688,6 +709,8 @@ def main():
     ap.add_argument("--no-scaling-workloads", action="store_true", help="N > 1: skip the extra measurements of configs 4 and 5 (scaling_workloads)")
     ap.add_argument("--no-other-workloads", action="store_true", help="N = 1: skip the extra measurements of configs 4 and 5 (other_workloads)")
     ap.add_argument("--no-direct", action="store_true", help="skip the comparison leg through the direct solver (profiling runs: only the chosen solver's kernels in the trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed solve returned (the parameter vector x "
+                    "and its report's scalars: %s) as DIR/<name>.npy, float64" % ", ".join(DUMP_REPORT_FIELDS))
     ap.add_argument("--plumbing-only", action="store_true", help="launcher / rendezvous / JSON relay only, no GPU work (CPU test of the N-rank plumbing)")
     args = ap.parse_args()
 
@@ -759,7 +782,7 @@ def main():
     pcg0 = problem.pcg_iterations()[1]
     barrier()
     t0 = time.perf_counter()
-    done, trials, _, _ = run_steps(problem, x0, args.steps, params)
+    done, trials, x_last, rep_last = run_steps(problem, x0, args.steps, params)
     aar.lib().aar_device_synchronize()
     dt = time.perf_counter() - t0
     if dist is not None:
@@ -768,6 +791,8 @@ def main():
         dt = float(t[0])
         dist.barrier()
     assert done == args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_last, rep_last)
     pcg_total = problem.pcg_iterations()[1] - pcg0
 
     # ---- full solve for the accuracy half of the metric ----

@@ -10,6 +10,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -146,3 +148,42 @@ def test_committed_bench_lines_keep_the_contract():
     # the N > 1 line's extra workloads, as measured behind a single-rank communicator
     sw = json.load(open(os.path.join(ROOT, "profiles", "r06_bench_cfg3_single_rank_rccl.json")))["scaling_workloads"]
     assert sw["4"]["solver_resolved"] == "spcg" and sw["5"]["solver_resolved"] == "pcg" and sw["5"]["value"] > 500 and sw["4"]["amdahl"]["bound_at"]["8"] > 1.5
+
+
+def test_steps_below_one_are_refused():
+    # --steps is the number of timed LM iterations: zero or a negative count has no timed region and is refused before any GPU work
+    for steps in ("0", "-3"):
+        out = run(["--steps", steps, "--plumbing-only"])
+        assert out.returncode != 0 and "--steps" in out.stderr and not out.stdout.strip()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_timed_solve(tmp_path):
+    # --dump-outputs DIR: what the last solve of the timed region returned -- x and the scalars of its report, float64 -- after exactly --steps steps
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "automatic-ar_amd"))
+    import aar
+    flags = ["--gpus", "1", "--workload", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-kernel-profile", "--no-amdahl",
+             "--no-other-workloads", "--no-direct", "--dump-outputs", str(tmp_path)]
+    out = run(flags)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
+    assert rec["steps"] == 20
+    names = sorted(f for f in os.listdir(str(tmp_path)))
+    assert names == sorted(["x.npy", "iterations.npy", "stop_code.npy", "initial_err.npy", "final_err.npy", "final_mu.npy", "trial_points.npy"])
+    x = np.load(str(tmp_path / "x.npy"))
+    ds = aar.synth(2)
+    assert x.dtype == np.float64 and x.shape == (ds.full_len,) and np.all(np.isfinite(x))
+    it = np.load(str(tmp_path / "iterations.npy"))
+    assert it.dtype == np.float64 and it.shape == (1,) and 1 <= it[0] <= 20
+    # the solve ran from the workload's initial guess and lowered the error; with the same flags the inputs are the same, so a second run's last solve
+    # starts from the same error and takes the same number of steps
+    e0, e1 = float(np.load(str(tmp_path / "initial_err.npy"))[0]), float(np.load(str(tmp_path / "final_err.npy"))[0])
+    assert e1 < e0
+    again = tmp_path / "again"
+    flags[-1] = str(again)
+    out = run(flags)
+    assert out.returncode == 0, out.stderr[-3000:]
+    np.testing.assert_allclose(np.load(str(again / "initial_err.npy")), e0, rtol=1e-9)
+    assert np.array_equal(np.load(str(again / "iterations.npy")), it)
+    np.testing.assert_allclose(np.load(str(again / "x.npy")), x, rtol=0, atol=1e-6)

@@ -2,7 +2,10 @@
 against the REAL ucoslam::SparseLevMarq<double> of libs/sparselevmarq.h compiled into oracle/_ref/libref_lm.so, on the toy problems of
 tests/tools/toy_problems.h: a caller's own residual / Jacobian functions, solve(z, f, J), solve(z, f) with the solver's central differences, a stop function,
 and init + step by step.  Per-step trace (error, damping, accepted) and final vector must agree to 1e-9 -- rejected tries (mu grows inside a step), the
-exits of libs/sparselevmarq.h:458-461 and the stop-function quirk (prevErr stays the initial error) included.  CPU only: no kernel runs."""
+exits of libs/sparselevmarq.h:458-461 and the stop-function quirk (prevErr stays the initial error) included.  CPU only: no kernel runs.
+
+The real solver's traces are stored in tests/golden/g3_host_levmarq_ref.npz (tests/golden/make_ref_vectors.py), so the comparison runs wherever the suite
+runs; where oracle/_ref/libref_lm.so is built, the live reference must still produce the stored traces."""
 import ctypes as C
 import os
 import subprocess
@@ -25,9 +28,12 @@ def tool(tmp_path_factory):
     return exe
 
 
-def ref_toy(problem, mode, max_iters, min_error, min_step, min_avg, tau, der_eps, stop_after, steps):
-    if not os.path.exists(ol.REF_SO):
-        pytest.skip("oracle/_ref/libref_lm.so not built (needs /root/reference)")
+REF_TRACES = os.path.join(ROOT, "tests", "golden", "g3_host_levmarq_ref.npz")
+REF_KEYS = ("err", "mu", "acc", "final_err", "z")
+
+
+def ref_toy_live(problem, mode, max_iters, min_error, min_step, min_avg, tau, der_eps, stop_after, steps):
+    """One toy case through the real solver (oracle/_ref/libref_lm.so)."""
     L = ol.ref()
     L.ref_lm_toy.restype = C.c_double
     cap = 256
@@ -39,6 +45,18 @@ def ref_toy(problem, mode, max_iters, min_error, min_step, min_avg, tau, der_eps
                       C.c_double(der_eps), C.c_int(stop_after), C.c_int(steps), err.ctypes.data_as(dp), mu.ctypes.data_as(dp), acc.ctypes.data_as(ip), C.c_int32(cap),
                       C.byref(n), z.ctypes.data_as(dp))
     return dict(err=err[:n.value], mu=mu[:n.value], acc=acc[:n.value], final_err=fe, z=z)
+
+
+def ref_toy(case, args):
+    """The real solver's trace of CASES[case] as stored; checked against the live solver where oracle/_ref is built."""
+    g = np.load(REF_TRACES)
+    r = {k: g["case%d_%s" % (case, k)] for k in REF_KEYS}
+    r["final_err"] = float(r["final_err"][0])
+    assert tuple(g["case%d_args" % case]) == tuple(float(a) for a in args), "tests/golden/g3_host_levmarq_ref.npz is stale: rerun tests/golden/make_ref_vectors.py"
+    if ol.have_ref():
+        live = ref_toy_live(*args)
+        assert np.array_equal(live["acc"], r["acc"]) and all(close(live[k], r[k]) for k in ("err", "mu", "final_err", "z")), "the live reference solver no longer gives the stored trace"
+    return r
 
 
 def host_toy(tool, *args):
@@ -78,7 +96,7 @@ CASES = [
 
 @pytest.mark.parametrize("name,args", CASES, ids=[c[0] for c in CASES])
 def test_host_loop_equals_the_reference_solver(tool, name, args):
-    r = ref_toy(*args)
+    r = ref_toy(CASES.index((name, args)), args)
     h = host_toy(tool, *args)
     assert len(h["err"]) == len(r["err"]) and len(r["err"]) > 0, (len(h["err"]), len(r["err"]))
     assert close(h["err"], r["err"]), np.abs(h["err"] - r["err"]).max()

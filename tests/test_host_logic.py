@@ -346,7 +346,9 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
                          os.path.join(ROOT, "tests", "tools", "asan_host_main.cpp")] + host + ["-o", exe], capture_output=True, text=True)
     assert cc.returncode == 0, cc.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
+    work = tmp_path / "files"
+    work.mkdir()
+    run = subprocess.run([exe, str(work)], capture_output=True, text=True, env=env, timeout=300)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr and "LeakSanitizer" not in run.stderr
     assert "obs " in run.stdout and "subseqs" in run.stdout

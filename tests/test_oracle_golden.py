@@ -1,14 +1,16 @@
 """The CPU checker against the golden vectors (and against the live reference solver where it is built).
 
 Pins oracle/ba_oracle.cpp -- the restated LM loop, J^T J product and sparse LDL^T -- to outputs of the REAL
-ucoslam::SparseLevMarq<double> / Eigen::SimplicialLDLT (tests/golden/make_golden.py).  CPU only.
+ucoslam::SparseLevMarq<double> / Eigen::SimplicialLDLT (tests/golden/make_golden.py, tests/golden/make_ref_vectors.py).  CPU only.
 """
+import os
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
 import oracle_lib as ol
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 
 G1 = ["g1_cfg2", "g1_cfg3_cut", "g1_cfg2_far", "g1_cfg2_retry"]
 
@@ -159,12 +161,19 @@ def test_huber_weight_restatement():
     assert (w < 1).any() and (w == 1).any()
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref (real reference solver) not built here")
 def test_port_equals_live_reference_solver():
+    # the real solver's result of this very call is stored (tests/golden/make_ref_vectors.py); where oracle/_ref is built, the live solver must still give it
     ds, _ = load_golden("g1_cfg3_cut")
+    g = np.load(os.path.join(GOLDEN, "g1_cfg3_cut_ref_threads2.npz"))
+    r2 = {"iterations": int(g["iterations"][0]), "final_err": float(g["final_err"][0])}
+    x2 = g["x"]
     o = ol.Oracle(ds)
+    if ol.have_ref():
+        xl, rl = o.ref_lm_solve(ds.x_full, threads=2)
+        assert rl["iterations"] == r2["iterations"]
+        np.testing.assert_allclose(rl["final_err"], r2["final_err"], rtol=1e-10)
+        np.testing.assert_allclose(xl, x2, atol=1e-9)
     x1, r1 = o.lm_solve(ds.x_full, threads=2)
-    x2, r2 = o.ref_lm_solve(ds.x_full, threads=2)
     assert r1["iterations"] == r2["iterations"]
     np.testing.assert_allclose(r1["final_err"], r2["final_err"], rtol=1e-10)
     np.testing.assert_allclose(x1, x2, atol=1e-9)
