@@ -35,6 +35,7 @@ SYMBOLS = [
     "aar_comm_get_stats", "aar_lm_set_step_callback", "aar_lm_set_stop_function", "aar_problem_extract_z", "aar_problem_merge_z",
     "aar_solution_read_ex", "aar_cam_configs_read_ex", "aar_set_stage_timers", "aar_problem_pcg_iterations",
     "aar_solver_default_options", "aar_problem_create_ex", "aar_problem_get_solver_stats", "aar_problem_set_test_hook",
+    "aar_problem_covariance", "aar_covariance_write_yaml",
 ]
 NUM_KERNELS = 17
 SOLVER_DIRECT, SOLVER_PCG, SOLVER_SPCG, SOLVER_AUTO = 0, 1, 2, 3
@@ -96,6 +97,11 @@ class CSolverStats(C.Structure):
                 ("total_iterations", C.c_int64), ("solves", C.c_int64), ("fallbacks", C.c_int64), ("pcg_eta", C.c_double),
                 ("pcg_max_it", C.c_int32), ("env_overrides", C.c_int32), ("same_xcd_solves", C.c_int64), ("pcg_eta_loose", C.c_double),
                 ("pcg_eta_switch", C.c_double), ("pcg_abs_tol", C.c_double)]
+
+
+class CCovarianceReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("sum_sq", C.c_double),
+                ("sigma2", C.c_double), ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("frames_written", C.c_int32)]
 
 
 class CLmParams(C.Structure):
@@ -196,6 +202,8 @@ def lib():
     L.aar_eval_residuals.argtypes = [C.c_void_p, dp, dp, dp]
     L.aar_eval_normal_equations.argtypes = [C.c_void_p, dp, dp, dp, dp]
     L.aar_eval_damped_step.argtypes = [C.c_void_p, dp, C.c_double, dp]
+    L.aar_problem_covariance.argtypes = [C.c_void_p, dp, dp, dp, dp, C.POINTER(CCovarianceReport)]
+    L.aar_covariance_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.c_double]
     L.aar_lm_default_params.argtypes = [C.POINTER(CLmParams)]
     L.aar_lm_default_params.restype = None
     L.aar_lm_init.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams)]
@@ -605,6 +613,21 @@ class LocalGroup:
             self.handle = C.c_void_p()
 
 
+class Covariance:
+    """What Problem.covariance returns (see there)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def covariance_write_yaml(path, ds, entity_diag_flat, sigma2, frames=None):
+    """aar_covariance_write_yaml: entity_diag_flat / frames as Problem.covariance returns them (a problem created from ds, its optimize flags)"""
+    c = ds.as_c()
+    d = np.ascontiguousarray(entity_diag_flat, dtype=np.float64)
+    fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.float64).reshape(-1)
+    _check(lib().aar_covariance_write_yaml(path.encode(), C.byref(c), _dptr(d), _dptr(fr) if fr is not None else None, float(sigma2)))
+
+
 class Problem:
     """aar_problem: the bundle-adjustment problem resident on one GPU."""
 
@@ -625,6 +648,8 @@ class Problem:
         d.with_huber = int(with_huber)
         d.device_id = device
         d.comm = comm.handle if comm is not None else None
+        self.optimize = (bool(d.optimize_cam_poses), bool(d.optimize_marker_poses), bool(d.optimize_object_poses))
+        self.intrinsics = bool(intrinsics)
         self.handle = C.c_void_p()
         if all(v is None for v in (solver, deterministic, pcg_eta, pcg_max_it, pcg_eta_loose, pcg_eta_switch, pcg_abs_tol)):
             _check(lib().aar_problem_create(C.byref(d), C.byref(self.handle)))
@@ -694,6 +719,37 @@ class Problem:
         delta = np.zeros(self.num_vars)
         _check(lib().aar_eval_damped_step(self.handle, _dptr(x), mu, _dptr(delta)))
         return delta
+
+    def entity_block_sizes(self):
+        """sizes of the z-order diagonal blocks of the non-frame unknowns: 6 per camera / marker, 9 per intrinsics entity"""
+        oc, om, _ = self.optimize
+        return [6] * ((self.ds.num_cams - 1) if oc else 0) + [6] * ((self.ds.num_markers - 1) if om else 0) + \
+            [9] * (self.ds.num_cams if self.intrinsics else 0)
+
+    def covariance(self, x_full, dense=False, frames=True):
+        """aar_problem_covariance: (J^T J)^-1 at x_full, UNSCALED (times .sigma2 for the covariance), z ordering, NaN where a parameter has no
+        unknown or is unobserved.  Returns a Covariance: sigma2, sum_sq, num_residuals, num_vars, min_pivot, max_pivot, frames_written,
+        entity_diag (list of 6x6 / 9x9 blocks in z order), entity_cov (Pe x Pe, dense=True only), frames ([F][6][6] or None; on a sharded
+        problem only this rank's frames are filled, the others NaN)."""
+        x = self._x(x_full)
+        sizes = self.entity_block_sizes()
+        pe = sum(sizes)
+        diag = np.full(sum(b * b for b in sizes), np.nan)
+        ecov = np.full((pe, pe), np.nan) if dense else None
+        want_fr = frames and self.optimize[2]
+        fr = np.full((self.ds.num_frames, 36), np.nan) if want_fr else None
+        rep = CCovarianceReport()
+        rep.struct_size = C.sizeof(CCovarianceReport)
+        _check(lib().aar_problem_covariance(self.handle, _dptr(x), _dptr(ecov) if dense else None, _dptr(diag),
+                                            _dptr(fr) if want_fr else None, C.byref(rep)))
+        blocks, o = [], 0
+        for b in sizes:
+            blocks.append(diag[o:o + b * b].reshape(b, b))
+            o += b * b
+        return Covariance(sigma2=rep.sigma2, sum_sq=rep.sum_sq, num_residuals=rep.num_residuals, num_vars=rep.num_vars,
+                          min_pivot=rep.min_pivot, max_pivot=rep.max_pivot, frames_written=rep.frames_written,
+                          entity_diag=blocks, entity_diag_flat=diag, entity_cov=ecov,
+                          frames=fr.reshape(-1, 6, 6) if want_fr else None)
 
     def reproj_stats(self, x_full):
         x = self._x(x_full)

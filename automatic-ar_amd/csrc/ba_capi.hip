@@ -247,6 +247,9 @@ struct aar_problem {
     size_t ev_used = 0;
     double k_seconds[KID_COUNT] = {0};
     int64_t k_launches[KID_COUNT] = {0};
+    // aar_problem_covariance: workspace, allocated on the first call (cov_kernels.hip)
+    double *cov_ws = nullptr;
+    int32_t *cov_iws = nullptr;
 };
 
 namespace {
@@ -1853,6 +1856,153 @@ int aar_eval_damped_step(aar_problem *pb, const double *x_full, double mu, doubl
     extract_z(L, x1.data(), z1.data());
     for (int64_t i = 0; i < L.z_len(); i++) delta[i] = z1[i] - z0[i];
     return AAR_OK;
+}
+
+// (J^T J)^-1 at x_full: the DIRECT chain's blocks at mu = 0, the reduced system factored by the k_ldl_* chain (one padding tile more than the
+// LM path uses, so that every real tile's factor stays in Dfac), S^-1 and the frame marginals by cov_kernels.hip.  DESIGN.md section 13.
+int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity_cov, double *entity_diag, double *frame_cov,
+                           aar_covariance_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_problem_covariance: null argument");
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_covariance: report->struct_size not set");
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const PoseLayout &L = pb->L;
+    const int cur = pb->cur, np = P.n_pad, n2 = P.n_pad + CHOL_NB, nT2 = P.nT + 1, NB = CHOL_NB;
+    int rc = upload_z(pb, x_full, cur);
+    if (rc) return rc;
+    if ((rc = zero_block_set(pb, cur))) return rc;
+    // whatever the LM state was, it is gone: the blocks of `cur` are rebuilt and eliminated below
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    pb->vinv_mu = pb->schur_mu = -1;
+    pb->s_reduced = pb->trial_reduced = false;
+    pb->spec_chol_blk = -1;
+    if (pb->panels_blk == cur) pb->panels_blk = -1;
+    P.want_w64 = 1;   // (the frame kernel reads the fp64 W blocks whatever the problem's solver)
+    rc = eval_blocks(pb, cur, -1.0, -1);
+    P.want_w64 = 0;
+    if (rc) return rc;
+    // Schur complement at mu = 0 and this rank's sum r^2 behind g0: they travel in the DIRECT chain's all-reduce
+    launch_frame_inv(P, cur, 0.0, pb->stream);
+    launch_schur(P, cur, 1.0, pb->stream, 0, 0, nullptr, false);
+    launch_reduce_scalars(P, P.F, false, 0ull, pb->stream, P.blk[cur].tail);
+    pb->launches += 3;
+    if (pb->comm && (rc = allreduce_system(pb, cur, 1))) return rc;
+    // workspace: staged system with its factor pieces | L | X = L^-1 | S^-1 | 1/D | frame blocks; masks and flags
+    const size_t fr = (size_t)std::max(P.F, 1) * 36;
+    const size_t o_S2 = 0, o_D = o_S2 + (size_t)n2 * n2 + 2 * (size_t)n2 + 8, o_Li = o_D + (size_t)nT2 * NB * NB, o_Lp = o_Li + (size_t)nT2 * (NB / 16) * 256,
+                 o_zf = o_Lp + (size_t)nT2 * n2 * NB, o_ds = o_zf + n2, o_Lc = o_ds + n2, o_X = o_Lc + (size_t)np * np, o_Si = o_X + (size_t)np * np,
+                 o_Dv = o_Si + (size_t)np * np, o_fr = o_Dv + np, o_db = o_fr + fr, total = o_db + 36 * (size_t)std::max(P.A, 1);
+    if (!pb->cov_ws) {
+        if ((rc = dev_alloc(pb, &pb->cov_ws, total))) return rc;
+        if ((rc = dev_alloc(pb, &pb->cov_iws, (size_t)np + nT2 + 1 + 4))) return rc;
+    }
+    double *ws = pb->cov_ws;
+    int32_t *rowmask = pb->cov_iws, *bsf = rowmask + np, *flg = bsf + nT2 + 1;
+    // the reduced system's diagonal and the summed sum r^2 on the host: entities no observation touches have an exactly zero diagonal
+    HIP_TRY(hipMemcpy2DAsync(pb->d_diag, sizeof(double), P.blk[cur].S, (size_t)(np + 1) * sizeof(double), sizeof(double), np, hipMemcpyDeviceToDevice, pb->stream));
+    std::vector<double> diag(np);
+    double sum_sq = 0;
+    HIP_TRY(hipStreamSynchronize(pb->stream));
+    if ((rc = copy_d2h(pb, diag.data(), pb->d_diag, np * sizeof(double))) || (rc = copy_d2h(pb, &sum_sq, P.blk[cur].tail, sizeof(double)))) return rc;
+    auto par_col = [&](int a, int i) -> int64_t {   // z column of device parameter (a, i), or -1 (as aar_eval_normal_equations)
+        if (a < L.C) { const int s = L.cam_slot(a); return (s < 0 || !L.oc) ? -1 : L.z_cam0() + 6LL * s + i; }
+        if (a < L.C + L.M) { const int s = L.mk_slot(a - L.C); return (s < 0 || !L.om) ? -1 : L.z_mk0() + 6LL * s + i; }
+        return i < 4 ? L.z_intr0() + 9LL * (a - L.C - L.M) + i : -1;
+    };
+    std::vector<int32_t> mask(np, 1);
+    for (int a = 0; a < P.A; a++) {
+        bool seen = false;
+        for (int i = 0; i < 6; i++) seen |= par_col(a, i) >= 0 && diag[6 * a + i] != 0.0;
+        for (int i = 0; i < 6; i++) mask[6 * a + i] = (seen && par_col(a, i) >= 0) ? 0 : 1;
+    }
+    if ((rc = copy_h2d(pb, rowmask, mask.data(), np * sizeof(int32_t)))) return rc;
+    // factor the staged system with the LM path's own chain: a copy of the problem description pointed at the workspace
+    double *S2 = ws + o_S2;
+    launch_cov_stage(P.blk[cur].S, np, S2, n2, rowmask, pb->stream);
+    HIP_TRY(hipMemsetAsync(S2 + (size_t)n2 * n2, 0, (2 * (size_t)n2 + 8) * sizeof(double), pb->stream));
+    HIP_TRY(hipMemsetAsync(bsf, 0, (nT2 + 1 + 4) * sizeof(int32_t), pb->stream));
+    DeviceProblem Q = P;
+    Q.n_pad = n2; Q.nT = nT2;
+    Q.blk[cur].S = S2; Q.blk[cur].rhs = S2 + (size_t)n2 * n2; Q.blk[cur].g0 = Q.blk[cur].rhs + n2; Q.blk[cur].tail = Q.blk[cur].g0 + n2;
+    Q.Dfac = ws + o_D; Q.Linv16 = ws + o_Li; Q.Lp = ws + o_Lp; Q.zf = ws + o_zf; Q.delta_s = ws + o_ds; Q.bs_flags = bsf; Q.bs_epoch = 0; Q.flags = flg;
+    (void)launch_chol(Q, cur, 0.0, pb->stream, -1);
+    launch_cov_inverse(S2, Q.Dfac, Q.Lp, np, n2, nT2, P.tune.fused_panel, ws + o_Lc, ws + o_Dv, ws + o_X, ws + o_Si, pb->stream);
+    const bool frames = frame_cov && L.of && P.F > 0;
+    if (frames) launch_cov_frames(P, cur, ws + o_Si, rowmask, ws + o_fr, pb->stream);
+    if (entity_diag && !entity_cov) launch_cov_diag_blocks(ws + o_Si, np, P.A, ws + o_db, pb->stream);
+    pb->launches += 4 + 3 * nT2 + np / 32;
+    if ((rc = check_async("covariance kernels"))) return rc;
+    HIP_TRY(hipStreamSynchronize(pb->stream));
+    HIP_TRY(hipMemsetAsync(P.flags, 0, 4 * sizeof(int32_t), pb->stream));   // (k_frame_inv flags the frames without observations)
+    std::vector<double> dinv(np);
+    if ((rc = copy_d2h(pb, dinv.data(), ws + o_Dv, np * sizeof(double)))) return rc;
+    double dmin = INFINITY, dmax = -INFINITY;
+    for (int r = 0; r < np; r++) {
+        if (mask[r]) continue;
+        const double d = 1.0 / dinv[r];
+        if (!(d > 0.0) || !std::isfinite(d)) {
+            const int a = r / 6;
+            if (a < L.C) return set_error(AAR_ERR_NUMERIC, "covariance: non-positive pivot %g at parameter %d of camera index %d", d, r % 6, a);
+            if (a < L.C + L.M) return set_error(AAR_ERR_NUMERIC, "covariance: non-positive pivot %g at parameter %d of marker index %d", d, r % 6, a - L.C);
+            return set_error(AAR_ERR_NUMERIC, "covariance: non-positive pivot %g at intrinsic %d of camera index %d", d, r % 6, a - L.C - L.M);
+        }
+        dmin = std::min(dmin, d);
+        dmax = std::max(dmax, d);
+    }
+    const int64_t Pz = L.z_len(), Fz = L.of ? 6LL * L.F : 0, Pe = Pz - Fz;
+    if (entity_cov || entity_diag) {
+        // the whole of S^-1 for a dense output; the entities' 6x6 diagonal blocks alone otherwise (an intrinsics entity's 9x9 block is its 4x4
+        // inside one 6x6 block: NaN elsewhere)
+        std::vector<double> Si((size_t)np * np), db;
+        if (entity_cov) {
+            if ((rc = copy_d2h(pb, Si.data(), ws + o_Si, Si.size() * sizeof(double)))) return rc;
+        } else {
+            db.resize(36 * (size_t)std::max(P.A, 1));
+            if ((rc = copy_d2h(pb, db.data(), ws + o_db, db.size() * sizeof(double)))) return rc;
+        }
+        std::vector<int> zdev((size_t)std::max<int64_t>(Pe, 1), -1);   // entity z column -> device row (-1: NaN)
+        for (int a = 0; a < P.A; a++)
+            for (int i = 0; i < 6; i++) {
+                const int64_t zc = par_col(a, i);
+                if (zc < 0 || mask[6 * a + i]) continue;
+                zdev[(size_t)((L.of && zc >= L.z_fr0()) ? zc - Fz : zc)] = 6 * a + i;
+            }
+        auto val = [&](int64_t i, int64_t j) -> double {
+            const int r = zdev[i], c = zdev[j];
+            if (r < 0 || c < 0) return NAN;
+            if (!entity_cov) return r / 6 == c / 6 ? db[(size_t)(r / 6) * 36 + (r % 6) * 6 + c % 6] : NAN;   // (only diagonal blocks are asked for)
+            return r >= c ? Si[(size_t)r * np + c] : Si[(size_t)c * np + r];
+        };
+        if (entity_cov)
+            for (int64_t i = 0; i < Pe; i++)
+                for (int64_t j = 0; j < Pe; j++) entity_cov[i * Pe + j] = val(i, j);
+        if (entity_diag) {   // z order: 6 x 6 per camera / marker, 9 x 9 per intrinsics entity
+            int64_t z = 0, o = 0;
+            while (z < Pe) {
+                const int b = (L.oi && z >= Pe - 9LL * L.C) ? 9 : 6;
+                for (int i = 0; i < b; i++)
+                    for (int j = 0; j < b; j++) entity_diag[o + i * b + j] = val(z + i, z + j);
+                z += b;
+                o += (int64_t)b * b;
+            }
+        }
+    }
+    if (frames && (rc = copy_d2h(pb, frame_cov + 36 * (size_t)pb->f_begin, ws + o_fr, (size_t)P.F * 36 * sizeof(double)))) return rc;
+    if (report) {
+        aar_covariance_report r;
+        memset(&r, 0, sizeof r);
+        r.struct_size = report->struct_size;
+        r.num_residuals = 8 * pb->N_global;
+        r.num_vars = Pz;
+        r.sum_sq = sum_sq;
+        r.sigma2 = r.num_residuals > Pz ? sum_sq / (double)(r.num_residuals - Pz) : NAN;
+        r.min_pivot = dmin;
+        r.max_pivot = dmax;
+        r.frames_written = frames ? P.F : 0;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return check_async("covariance");
 }
 
 // SparseLevMarq::init, libs/sparselevmarq.h:238-249.  The residual of the start point comes out of the same pass that

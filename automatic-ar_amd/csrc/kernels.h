@@ -271,6 +271,17 @@ int residual_blocks(const DeviceProblem &P);   // entries of err_part written by
 void launch_track(const DeviceProblem &P, int which, int max_iters, double min_error, double min_step, double min_avg, double tau,
                   int32_t *iters_out, double *err_out, hipStream_t st);
 
+// covariance (cov_kernels.hip): S (stride n_pad) -> S2 (stride n2 >= n_pad, zero beyond n_pad), rows with rowmask set -> identity
+void launch_cov_stage(const double *S, int n_pad, double *S2, int n2, const int32_t *rowmask, hipStream_t st);
+// the LDL^T factor launch_chol left for S2 (nT2 tiles, fused_m = the panel rule it ran with) -> Sinv = S^-1, lower 32 x 32 tiles of the first
+// n_pad rows; Lc, X: [n_pad][n_pad] scratch, Dinv: [n_pad] = 1 / D
+void launch_cov_inverse(const double *S2, const double *Dfac, const double *Lp, int n_pad, int n2, int nT2, int fused_m, double *Lc, double *Dinv,
+                        double *X, double *Sinv, hipStream_t st);
+// out[a][36] = the 6x6 diagonal block of entity a in Sinv
+void launch_cov_diag_blocks(const double *Sinv, int n_pad, int A, double *out, hipStream_t st);
+// out[f][36] = (J^T J)^-1 block of local frame f from Vinv of block set `which` (mu = 0), its W blocks and Sinv
+void launch_cov_frames(const DeviceProblem &P, int which, const double *Sinv, const int32_t *rowmask, double *out, hipStream_t st);
+
 // The error flags of a rank (bits 0..3) as one double that survives a SUM all-reduce over up to 4095 ranks: bit b set on k ranks adds k 4096^b.
 // Every rank decodes the same value, so every rank takes the same branch (a rank that failed alone would otherwise leave the
 // others waiting in their next collective).

@@ -26,7 +26,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance]" << endl;
     cout << "       " << a0 << " --synth <config 1..5> <out_folder>   (write a synthetic data set in the reference's file formats)" << endl;
     return -1;
 }
@@ -66,6 +66,7 @@ int main(int argc, char *argv[]) {
     const string folder_path = argv[1];
     const double marker_size = stod(argv[2]);
     bool use_subseqs = false, with_huber = false, set_threshold = false, from_initial = false, tracking_only = false;
+    bool covariance = false;   // not an option of the reference: -covariance also writes final.covariance.yaml (aar_problem_covariance)
     double threshold = 2.0;
     set<int> excluded_cams;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
@@ -79,6 +80,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-tracking-only") { tracking_only = true; arg_flag = NONE; }   // names the files only, as in the reference (:54-57,76-77)
         else if (a == "-thresh") { set_threshold = true; arg_flag = Threshold; }
         else if (a == "-solver") arg_flag = Solver;
+        else if (a == "-covariance") { covariance = true; arg_flag = NONE; }
         else if (arg_flag == Solver) {
             solver = a == "spcg" ? AAR_SOLVER_SPCG : a == "pcg" ? AAR_SOLVER_PCG : a == "auto" ? AAR_SOLVER_AUTO : a == "direct" ? AAR_SOLVER_DIRECT : -1;
             if (solver < 0) return print_usage(argv[0]);
@@ -167,6 +169,18 @@ int main(int argc, char *argv[]) {
     const chrono::duration<double> d = chrono::system_clock::now() - start;
     mcm.write_solution_file(final_path);
     mcm.write_text_solution_file(final_path + ".yaml");
+    if (covariance) {
+        const string cov_path = folder_path + "/final.covariance.yaml";
+        try {
+            const aar::MultiCamMapper::Covariance cv = mcm.compute_covariance(true);
+            if (!mcm.write_covariance_file(cov_path, cv)) throw runtime_error(aar_last_error());
+            cout << "covariance: sigma2 " << cv.sigma2 << " (" << cv.report.num_residuals << " residuals, " << cv.report.num_vars << " unknowns), written to "
+                 << cov_path << endl;
+        } catch (const exception &e) {
+            cerr << "covariance failed: " << e.what() << endl;
+            return 3;
+        }
+    }
     const aar_lm_report &r = mcm.last_report;
     {
         const aar_solver_stats st = mcm.solver_stats();

@@ -304,6 +304,45 @@ aar_solver_stats MultiCamMapper::solver_stats() {
     return st;
 }
 
+MultiCamMapper::Covariance MultiCamMapper::compute_covariance(bool frames) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::compute_covariance: no data set");
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    const int C = data_->num_cams, M = data_->num_markers, F = data_->num_frames;
+    const size_t n_diag = 36 * (size_t)((config_.optimize_cam_poses ? C - 1 : 0) + (config_.optimize_marker_poses ? M - 1 : 0)) +
+                          (config_.optimize_cam_intrinsics ? 81 * (size_t)C : 0);
+    Covariance cv;
+    cv.entity_diag.assign(std::max<size_t>(n_diag, 1), NAN);
+    frames = frames && config_.optimize_object_poses;
+    if (frames) cv.frame_cov.assign(36 * (size_t)F, NAN);
+    cv.report.struct_size = (uint32_t)sizeof cv.report;
+    std::vector<double> x = problem_vector();
+    if (aar_problem_covariance(problem_, x.data(), nullptr, cv.entity_diag.data(), frames ? cv.frame_cov.data() : nullptr, &cv.report))
+        throw std::runtime_error(aar_last_error());
+    cv.sigma2 = cv.report.sigma2;
+    auto scaled = [&](const double *b) { Mat66 m; for (int k = 0; k < 36; k++) m[k] = b ? cv.sigma2 * b[k] : NAN; return m; };
+    const size_t mk0 = config_.optimize_cam_poses ? 36 * (size_t)(C - 1) : 0;
+    for (int c = 0; c < C; c++) {
+        const int s = c == data_->root_cam ? -1 : (c < data_->root_cam ? c : c - 1);
+        cv.cams[data_->cam_ids[c]] = scaled((s < 0 || !config_.optimize_cam_poses) ? nullptr : cv.entity_diag.data() + 36 * (size_t)s);
+    }
+    for (int m = 0; m < M; m++) {
+        const int s = m == data_->root_marker ? -1 : (m < data_->root_marker ? m : m - 1);
+        cv.markers[data_->marker_ids[m]] = scaled((s < 0 || !config_.optimize_marker_poses) ? nullptr : cv.entity_diag.data() + mk0 + 36 * (size_t)s);
+    }
+    if (frames)
+        for (int f = 0; f < F; f++) cv.objects[data_->frame_ids[f]] = scaled(cv.frame_cov.data() + 36 * (size_t)f);
+    return cv;
+}
+
+bool MultiCamMapper::write_covariance_file(const std::string &path, const Covariance &cov) {
+    if (!data_) return false;
+    // (the writer reads the group flags from the data set: the mapper's Config is what the covariance was computed for)
+    aar_dataset d = *data_;
+    d.optimize_cam_poses = config_.optimize_cam_poses;
+    d.optimize_marker_poses = config_.optimize_marker_poses;
+    return aar_covariance_write_yaml(path.c_str(), &d, cov.entity_diag.data(), cov.frame_cov.empty() ? nullptr : cov.frame_cov.data(), cov.sigma2) == AAR_OK;
+}
+
 void MultiCamMapper::error_function(const eVector &input, eVector &error) {
     if (probed(detail::EVAL_ERROR_FUNCTION)) return;
     if (!data_) throw std::runtime_error("MultiCamMapper::error_function: no data set");

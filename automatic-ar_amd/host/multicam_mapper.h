@@ -442,6 +442,20 @@ class MultiCamMapper {
     const SolverOptions &get_solver_options() const { return solver_options_; }
     aar_solver_stats solver_stats();      // what the problem runs with (AUTO resolved) and what its inner solver has done; builds the problem if need be
 
+    // EXTENSION, no counterpart in the reference: the marginal covariance of the current solution (aar_problem_covariance at io_vec's poses,
+    // for the current Config).  Blocks are 6x6 row-major over (rx ry rz tx ty tz), SCALED by sigma2, keyed by id as the transforms are;
+    // roots, fixed groups and unobserved entities hold NaN.  entity_diag / frame_cov keep the unscaled output of the C call
+    // (aar_covariance_write_yaml takes them).  Throws std::runtime_error on failure.
+    typedef std::array<double, 36> Mat66;
+    struct Covariance {
+        double sigma2 = 0;
+        aar_covariance_report report{};
+        std::map<int, Mat66> cams, markers, objects;   // objects: only when frames were asked for and object poses are optimised
+        std::vector<double> entity_diag, frame_cov;
+    };
+    Covariance compute_covariance(bool frames = true);
+    bool write_covariance_file(const std::string &path, const Covariance &cov);   // YAML, aar_covariance_write_yaml
+
     const aar_dataset *dataset() const { return data_; }
 
    private:

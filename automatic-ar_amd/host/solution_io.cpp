@@ -62,6 +62,26 @@ void yaml_transform(FILE *f, const char *id_key, int id, const Rigid &T) {
 
 }  // namespace
 
+namespace {
+// fs_double, with the YAML spellings of the non-finite values (.nan, .inf, -.inf)
+std::string fs_double_nf(double v) {
+    if (std::isnan(v)) return ".nan";
+    if (std::isinf(v)) return v > 0 ? ".inf" : "-.inf";
+    return fs_double(v);
+}
+void yaml_cov_block(FILE *f, const char *id_key, int id, const double *blk, double sigma2) {
+    double sr = 0, st = 0;   // 1-sigma: square root of the mean variance of the three rotation / translation components
+    for (int i = 0; i < 3; i++) { sr += blk[i * 7] * sigma2; st += blk[(i + 3) * 7] * sigma2; }
+    fprintf(f, "   - { %s:%d, sigma_rot: %s, sigma_trans: %s,\n       covariance: !!opencv-matrix { rows:6, cols:6, dt:d, data:[ ", id_key, id,
+            fs_double_nf(std::sqrt(sr / 3.0)).c_str(), fs_double_nf(std::sqrt(st / 3.0)).c_str());
+    for (int k = 0; k < 36; k++) {
+        fprintf(f, "%s%s", fs_double_nf(blk[k] * sigma2).c_str(), k == 35 ? " " : ", ");
+        if (k % 6 == 5 && k != 35) fprintf(f, "\n       ");
+    }
+    fprintf(f, "] } }\n");
+}
+}  // namespace
+
 extern "C" {
 
 int aar_solution_write(const char *path, const aar_dataset *d) {
@@ -249,6 +269,37 @@ int aar_solution_write_yaml(const char *path, const aar_dataset *d) {
     }
     fprintf(f, "root_marker_to_root_cam:\n");
     for (int i = 0; i < L.F; i++) yaml_transform(f, "frame_id", d->frame_ids[i], pose_to_rigid(d->x_full + L.full_fr0() + 6LL * i));
+    const bool good = !ferror(f);
+    fclose(f);
+    return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
+}
+
+
+int aar_covariance_write_yaml(const char *path, const aar_dataset *d, const double *entity_diag, const double *frame_cov, double sigma2) {
+    if (!path || !d || !entity_diag) return set_error(AAR_ERR_INVALID, "aar_covariance_write_yaml: null argument");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    PoseLayout L;
+    L.C = d->num_cams; L.M = d->num_markers; L.F = d->num_frames; L.rc = d->root_cam; L.rm = d->root_marker;
+    L.oc = d->optimize_cam_poses != 0; L.om = d->optimize_marker_poses != 0;
+    std::vector<double> nan_blk(36, NAN);
+    const double *cams = entity_diag, *mks = entity_diag + (L.oc ? 36LL * (L.C - 1) : 0);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "sigma2: %s\n", fs_double_nf(sigma2).c_str());
+    fprintf(f, "cameras:\n");
+    for (int c = 0; c < L.C; c++) {
+        const int s = L.cam_slot(c);
+        yaml_cov_block(f, "cam_id", d->cam_ids[c], (s < 0 || !L.oc) ? nan_blk.data() : cams + 36LL * s, sigma2);
+    }
+    fprintf(f, "markers:\n");
+    for (int m = 0; m < L.M; m++) {
+        const int s = L.mk_slot(m);
+        yaml_cov_block(f, "marker_id", d->marker_ids[m], (s < 0 || !L.om) ? nan_blk.data() : mks + 36LL * s, sigma2);
+    }
+    if (frame_cov) {
+        fprintf(f, "object_poses:\n");
+        for (int i = 0; i < L.F; i++) yaml_cov_block(f, "frame_id", d->frame_ids[i], frame_cov + 36LL * i, sigma2);
+    }
     const bool good = !ferror(f);
     fclose(f);
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);

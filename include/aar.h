@@ -355,6 +355,35 @@ int aar_eval_normal_equations(aar_problem *, const double *x_full, double *JtJ, 
  * (libs/sparselevmarq.h:384-400), in z ordering. */
 int aar_eval_damped_step(aar_problem *, const double *x_full, double mu, double *delta);
 
+/* Covariance of a solved problem (no counterpart in the reference).  (J^T J)^-1 at x_full, UNSCALED -- multiply
+ * by sigma2 for the a-posteriori covariance -- in the reference's z ordering for the problem's Config.  Whatever the problem's solver,
+ * the normal equations are built with its residual mode and Huber weights, the frames are eliminated at mu = 0 and the reduced system
+ * S is factored by the direct chain's LDL^T; S^-1 and the frame marginals V_f^-1 + V_f^-1 W_f^T S^-1 W_f V_f^-1 are formed on the device.
+ * Entries of parameters without a z column (roots, non-optimised groups, the five distortion entries of an intrinsics block) and of
+ * entities no observation touches are NaN; a frame without observations gets a NaN block.  Any other non-positive pivot of S is
+ * AAR_ERR_NUMERIC, naming the entity.  With a communicator S travels in the direct chain's all-reduce, every rank holds the same entity
+ * blocks and writes the frame blocks of its own frame range.  Leaves the problem as aar_eval_damped_step does (no LM state).
+ *   entity_cov:  Pe x Pe row-major, Pe = num_vars minus the frame-pose unknowns; may be NULL
+ *   entity_diag: the diagonal blocks only, z order: 6 x 6 per camera / marker, 9 x 9 per intrinsics entity; may be NULL
+ *   frame_cov:   [num_frames][36]: this rank's frames (the others untouched); may be NULL
+ *   report:      caller sets struct_size = sizeof(aar_covariance_report); at most that many bytes are filled; may be NULL */
+typedef struct aar_covariance_report {
+    uint32_t struct_size;
+    int64_t num_residuals;                    /* 8 N over all ranks                                                      */
+    int64_t num_vars;                         /* P = aar_problem_num_vars                                                */
+    double sum_sq;                            /* at x_full, all ranks                                                    */
+    double sigma2;                            /* sum_sq / (num_residuals - num_vars): the a-posteriori variance factor   */
+    double min_pivot, max_pivot;              /* of D in the LDL^T of S over the rows that carry an unknown (a conditioning hint) */
+    int32_t frames_written;                   /* frame blocks this rank wrote                                            */
+} aar_covariance_report;
+int aar_problem_covariance(aar_problem *, const double *x_full, double *entity_cov, double *entity_diag, double *frame_cov,
+                           aar_covariance_report *report);
+/* YAML (the cv::FileStorage dialect of aar_solution_write_yaml) of a covariance: per camera id and marker id the 6x6 block
+ * sigma2 * entity_diag (rx ry rz tx ty tz) and its 1-sigma rotation (rad) and translation (m) standard deviations; blocks
+ * without unknowns (roots, fixed groups, unobserved) as .nan.  entity_diag as aar_problem_covariance writes it for a problem
+ * created from `d` (its optimize flags); frame_cov (may be NULL) adds the object poses.  Host code. */
+int aar_covariance_write_yaml(const char *path, const aar_dataset *d, const double *entity_diag, const double *frame_cov, double sigma2);
+
 /* ucoslam::SparseLevMarq<T>::Params (libs/sparselevmarq.h:30-50) with the values
  * MultiCamMapper::init installs (libs/multicam_mapper.cpp:326-330). */
 typedef struct aar_lm_params {
