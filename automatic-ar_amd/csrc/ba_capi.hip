@@ -17,6 +17,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <numeric>
 #include <condition_variable>
 #include <mutex>
@@ -34,6 +35,22 @@ using namespace aar;
         hipError_t _e = (expr);                                                                        \
         if (_e != hipSuccess) return set_error(AAR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
+
+// kernels.h: the one record of the dynamic LDS each kernel may use on each device
+void aar::raise_dynamic_lds(const void *kernel, size_t bytes) {
+    constexpr size_t FLOOR = 48 * 1024;   // what every launcher asks for without an opt-in
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> granted;
+    if (bytes <= FLOOR) return;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    const auto key = std::make_pair(dev, kernel);
+    const auto it = granted.find(key);
+    if (it != granted.end() && it->second >= bytes) return;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) granted[key] = bytes;
+    else (void)hipGetLastError();   // (not recorded: the launch that asks for it fails and reports its own error)
+}
 
 // ------------------------------------------------------------------------------------------------
 // RCCL, resolved at run time so that libaar.so loads on machines without it (and shares whichever
@@ -1587,8 +1604,7 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
     UP(chunk_start, chunk_start); UP(ent_fixed, ent_fixed); UP(up_start, up_start); UP(up_ent, up_ent);
     UP(sw_ent, sw_ent); UP(sw_begin, sw_begin); UP(sw_end, sw_end); UP(pair_rec, pair_rec);
     if (P.use_pcg) {   // balanced work items: at most `chunk` incidences of one entity each, 1 .. 8 items per entity (PCG_MAX_ITEMS)
-        hipDeviceProp_t prop;
-        const int cus = (hipGetDeviceProperties(&prop, pb->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 64;
+        const int cus = P.n_cus;
         int64_t longest = 0;
         for (int a = 0; a < A; a++) longest = std::max<int64_t>(longest, pair_base[a + 1] - pair_base[a]);
         int64_t chunk = std::max<int64_t>(256, (total_pairs + 2LL * cus - 1) / (2LL * cus));
@@ -1637,8 +1653,7 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
             if (w32 && P.pcg_fused && !P.deterministic && P.pcg_eta >= PCG_W32_MIN_ETA)   // (a caller who asks for residuals below 1e-4 gets fp64 blocks throughout)
                 for (int w = 0; w < 2; w++) AL(blk[w].Wf, (size_t)P.total_slots * 36 + 4);
         }
-        hipDeviceProp_t prop;
-        P.pcg_grid = (hipGetDeviceProperties(&prop, pb->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 64;   // one workgroup per CU: all resident
+        P.pcg_grid = P.n_cus;   // one workgroup per CU: all resident
         // small problems: fewer workgroups make the two grid-wide hand-overs of an iteration cheaper than the passes get slower
         // (measured, LM it/s at config 3: 64 / 128 / 256 workgroups 4174 / 4201 / 3883; config 2: 32 best; config 5: 256 best)
         const int64_t want = std::max<int64_t>(32, ((int64_t)F + 3) / 4);
@@ -1652,12 +1667,9 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
             if (hipHostGetDevicePointer((void **)&P.pcgd_host, pb->h_pcg, 0) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipHostGetDevicePointer failed"));
         }
         if (const char *t = getenv("AAR_PCG_GRID")) P.pcg_grid = std::max(1, atoi(t));
-        // the kernels' grid-wide hand-overs need every workgroup resident: never more than the occupancy query admits (the override included)
-        {
-            hipDeviceProp_t prop2;
-            const int cus2 = (hipGetDeviceProperties(&prop2, pb->device) == hipSuccess && prop2.multiProcessorCount > 0) ? prop2.multiProcessorCount : 64;
-            P.pcg_grid = std::min(P.pcg_grid, pcg_max_grid(A, cus2));
-        }
+        // the kernels' grid-wide hand-overs need every workgroup resident: never more than the occupancy query admits (the override included),
+        // asked at the footprint they are launched with (P.pcg_coarse is final: cut above where its tables do not fit)
+        P.pcg_grid = std::min(P.pcg_grid, pcg_max_grid(A, P.pcg_coarse != 0, P.n_cus));
     }
     if (P.use_spcg) {
         AL(spcg_ws, spcg_ws_doubles(P.n_pad)); AL(spcg_iters, 8); AL(spcg_done, 2);

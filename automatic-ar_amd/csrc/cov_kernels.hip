@@ -244,10 +244,8 @@ void launch_cov_inverse(const double *S2, const double *Dfac, const double *Lp, 
 void launch_cov_frames(const DeviceProblem &P, int which, const double *Sinv, const int32_t *rowmask, double *out, hipStream_t st) {
     if (P.F == 0) return;
     const size_t lds = ((size_t)std::max(P.max_kf, 1) * 37) * sizeof(double);
-    static size_t granted = 48 * 1024;
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_cov_frames), lds, granted);
-    hipLaunchKernelGGL(k_cov_frames, dim3((unsigned)P.F), dim3(64), lds, st, P.fslot_start, P.fslot_ent, P.blk[which].W, P.blk[which].Vinv, Sinv, rowmask,
-                       P.n_pad, P.F, out);
+    launch_lds(k_cov_frames, dim3((unsigned)P.F), dim3(64), lds, st, P.fslot_start, P.fslot_ent, P.blk[which].W, P.blk[which].Vinv, Sinv, rowmask,
+               P.n_pad, P.F, out);
 }
 
 }  // namespace aar

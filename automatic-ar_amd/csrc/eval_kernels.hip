@@ -1305,54 +1305,29 @@ template <int B, int CPL>
 static void launch_passA_t(const DeviceProblem &P, const PassAArgs &a, const PassBArgs *pbargs, hipStream_t st) {
     size_t lds = P.tune.passA_wrench ? passA_wrench_lds_bytes(P.max_kf, P.intr != 0) : passA_lds_bytes(P.max_kf, B);
     if (pbargs) lds = std::max(lds, (size_t)(B / 64) * 2048 * sizeof(double));   // pass B's wave-sum scratch, when its chunks ride along
-    static size_t granted = 48 * 1024, granted_ab = 48 * 1024;
     HookScope _h(P, KID_PASSA);
+    const int nb = (P.n_chunks + B / 64 - 1) / (B / 64);   // pass B's workgroups, when its chunks ride along
     if (P.intr && pbargs) {
-        static size_t granted_abi = 48 * 1024;
-        const int nb = (P.n_chunks + B / 64 - 1) / (B / 64);
-        if (P.tune.passA_wrench) {
-            static size_t granted_abiw = 48 * 1024;
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_passAB_intr<B, CPL, true>), lds, granted_abiw);
-            hipLaunchKernelGGL((k_passAB_intr<B, CPL, true>), dim3(P.F + 2 * nb), dim3(B), lds, st, a, *pbargs, nb);
-        } else {
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_passAB_intr<B, CPL, false>), lds, granted_abi);
-            hipLaunchKernelGGL((k_passAB_intr<B, CPL, false>), dim3(P.F + 2 * nb), dim3(B), lds, st, a, *pbargs, nb);
-        }
+        if (P.tune.passA_wrench) launch_lds(k_passAB_intr<B, CPL, true>, dim3(P.F + 2 * nb), dim3(B), lds, st, a, *pbargs, nb);
+        else launch_lds(k_passAB_intr<B, CPL, false>, dim3(P.F + 2 * nb), dim3(B), lds, st, a, *pbargs, nb);
     } else if (P.intr) {
-        static size_t granted_i = 48 * 1024;
-        if (P.tune.passA_wrench) {
-            static size_t granted_iw = 48 * 1024;
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_passA_intr<B, CPL, true>), lds, granted_iw);
-            hipLaunchKernelGGL((k_passA_intr<B, CPL, true>), dim3(P.F), dim3(B), lds, st, a);
-        } else {
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_passA_intr<B, CPL, false>), lds, granted_i);
-            hipLaunchKernelGGL((k_passA_intr<B, CPL, false>), dim3(P.F), dim3(B), lds, st, a);
-        }
+        if (P.tune.passA_wrench) launch_lds(k_passA_intr<B, CPL, true>, dim3(P.F), dim3(B), lds, st, a);
+        else launch_lds(k_passA_intr<B, CPL, false>, dim3(P.F), dim3(B), lds, st, a);
     } else if (pbargs && P.tune.passA_wrench && !P.tune.passB_wrench_merged &&
-               (P.tune.passAB_occ2 >= 0 ? P.tune.passAB_occ2 != 0 : P.F + (P.n_chunks + B / 64 - 1) / (B / 64) > P.n_cus * 4 / (B / 64))) {
+               (P.tune.passAB_occ2 >= 0 ? P.tune.passAB_occ2 != 0 : P.F + nb > P.n_cus * 4 / (B / 64))) {
         // more workgroups than the chip holds at one wavefront per SIMD (388 registers): at two the frames of a long sequence run in one round instead of two
         // (config 4, 2000 frames: 36.3 -> 32.6 us; config 3's 500 frames fit anyway and keep the unrolled pass B)
-        static size_t granted_o2 = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_passAB_o2<B, CPL>), lds, granted_o2);
-        hipLaunchKernelGGL((k_passAB_o2<B, CPL>), dim3(P.F + (P.n_chunks + B / 64 - 1) / (B / 64)), dim3(B), lds, st, a, *pbargs);
+        launch_lds(k_passAB_o2<B, CPL>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
     } else if (pbargs && P.tune.passA_wrench && !P.tune.passB_wrench_merged) {   // (the default: pass A in wrench form, pass B's chunks in row form)
-        static size_t granted_abr = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_passAB<B, CPL, true, false>), lds, granted_abr);
-        hipLaunchKernelGGL((k_passAB<B, CPL, true, false>), dim3(P.F + (P.n_chunks + B / 64 - 1) / (B / 64)), dim3(B), lds, st, a, *pbargs);
+        launch_lds(k_passAB<B, CPL, true, false>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
     } else if (pbargs && P.tune.passA_wrench) {
-        static size_t granted_abw = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_passAB<B, CPL, true>), lds, granted_abw);
-        hipLaunchKernelGGL((k_passAB<B, CPL, true>), dim3(P.F + (P.n_chunks + B / 64 - 1) / (B / 64)), dim3(B), lds, st, a, *pbargs);
+        launch_lds(k_passAB<B, CPL, true>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
     } else if (pbargs) {
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_passAB<B, CPL, false>), lds, granted_ab);
-        hipLaunchKernelGGL((k_passAB<B, CPL, false>), dim3(P.F + (P.n_chunks + B / 64 - 1) / (B / 64)), dim3(B), lds, st, a, *pbargs);
+        launch_lds(k_passAB<B, CPL, false>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
     } else if (P.tune.passA_wrench) {
-        static size_t granted_w = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_passA<B, CPL, true>), lds, granted_w);
-        hipLaunchKernelGGL((k_passA<B, CPL, true>), dim3(P.F), dim3(B), lds, st, a);
+        launch_lds(k_passA<B, CPL, true>, dim3(P.F), dim3(B), lds, st, a);
     } else {
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_passA<B, CPL, false>), lds, granted);
-        hipLaunchKernelGGL((k_passA<B, CPL, false>), dim3(P.F), dim3(B), lds, st, a);
+        launch_lds(k_passA<B, CPL, false>, dim3(P.F), dim3(B), lds, st, a);
     }
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility>
 
 namespace aar {
 
@@ -199,12 +200,15 @@ struct DeviceProblem {
     LaunchHook hook;
 };
 
-// opt in to more than the default dynamic LDS per workgroup (gfx950: 160 KiB per CU); remembered per kernel
-inline void allow_dynamic_lds(const void *kernel, size_t bytes, size_t &granted) {
-    if (bytes > granted) {
-        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        granted = bytes;
-    }
+// Opt `kernel` in to `bytes` of dynamic LDS per workgroup on the current device (gfx950: up to 160 KiB per CU).  One process-wide,
+// mutex-guarded table per (device, kernel) holds what was granted: the attribute is only ever raised (from 48 KiB), so no problem or
+// thread lowers it under another's live launches (ba_capi.hip).
+void raise_dynamic_lds(const void *kernel, size_t bytes);
+// every launch with dynamic LDS: the opt-in, then the launch with the same arguments
+template <typename... Params, typename... Args>
+inline void launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args &&...args) {
+    raise_dynamic_lds(reinterpret_cast<const void *>(kernel), lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, std::forward<Args>(args)...);
 }
 
 // camera matrices: the constant table, or -- intrinsics being optimised -- the rows of the intrinsics entities of pose buffer `which`
@@ -248,7 +252,7 @@ bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, i
 void launch_backsub(const DeviceProblem &P, int cur, int trial, hipStream_t st);   // z[trial] = z[cur] + delta, lin_part
 void launch_pcg(const DeviceProblem &P, int which, double mu, hipStream_t st);     // AAR_SOLVER=pcg: delta_s by PCG through the frame blocks (needs Vinv, hf for mu)
 size_t pcg_lds_bytes(int A, bool coarse = false);   // coarse: with the tables of k_pcgf's coarse space
-int pcg_max_grid(int A, int cus);   // largest co-resident grid of the persistent PCG kernels
+int pcg_max_grid(int A, bool coarse, int cus);   // largest co-resident grid of the persistent PCG kernels at the dynamic LDS they are launched with
 // solver spcg: delta_s by CG on the explicit reduced system S of block set `which` (the Schur complement for mu must have been taken; S is not modified)
 bool launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial = -1);   // trial >= 0: launch_backsub(which, trial) may ride (true: it did)
 int spcg_resident_per_cu(int nT, bool coarse);             // occupancy query: wavefronts of k_spcg<nT> one CU holds (0: unknown)

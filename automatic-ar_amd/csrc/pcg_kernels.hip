@@ -72,7 +72,7 @@ __device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomi
 // false: the grid is not whole -- this workgroup waited 2^26 polls for the others, or somebody else already has (device flag 4) -- and every
 // workgroup LEAVES the kernel at its next hop instead of spinning through the remaining ones (up to two per CG iteration): the launch ends within
 // one time-out, the host reports AAR_ERR_NUMERIC ("chain timed out").  Co-residency itself is not assumed blindly: the grid is clamped to what the
-// occupancy query admits (pcg_max_grid).
+// occupancy query admits at the launched dynamic LDS (pcg_max_grid).
 // The arrivals form a two-level tree, so that no address sees more than PCG_NY agent-scope operations per hop (256 increments of ONE address serialise at
 // the memory side, ~60 ns each: the 15 us a hop used to cost at config 5; 256 pollers of one address are no better): workgroup wg arrives at counter wg % PCG_NY;
 // the last arrival of a group arrives at the second level; the last arrival there raises every group's own flag, which is all a group's workgroups poll.
@@ -1587,37 +1587,23 @@ __global__ void __launch_bounds__(PCG_THREADS) k_pcgd_iter_f(const PcgDistArgs d
 size_t pcg_lds_bytes(int A, bool coarse) { return ((size_t)10 * 6 * A + (PCGF32_THREADS / 64) * 27 + 8 + (coarse ? (size_t)12 * A + 144 + 72 + (PCGF32_THREADS / 64) * 144 : 0)) * sizeof(double); }   // x | r | p | Mi [6 n] | yacc [n] (k_pcgf) | red | coarse space: zd [12 A] | Ews | einv | scratch
 
 // the largest grid of the persistent PCG kernels that is resident as a whole (their hand-overs wait for every workgroup): what the occupancy query
-// admits per CU for the kernel with the larger footprint, times the CUs
-int pcg_max_grid(int A, int cus) {
-    const size_t lds = pcg_lds_bytes(A);
-    static size_t g1 = 48 * 1024, g2 = 48 * 1024;
-    static size_t g3 = 48 * 1024, g4 = 48 * 1024;
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_pcg), lds, g1);
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgd_iter), lds, g2);
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<false>), lds, g3);
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<true>), lds, g4);
-    int n1 = 0, n2 = 0, n3 = 0, n4 = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n3, k_pcgf<false>, PCG_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); n3 = 1; }
-    {
-        static size_t g6 = 48 * 1024;
-        int n6 = 0;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<false, 2>), lds, g6);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n6, k_pcgf<false, 2>, PCG_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); n6 = 1; }
-        n3 = std::min(n3, n6);
+// admits per CU for the kernel with the larger footprint, times the CUs.  Asked at the largest dynamic LDS launch_pcg / launch_pcgd_iter request
+// for this problem (coarse: with the coarse space's tables).
+int pcg_max_grid(int A, bool coarse, int cus) {
+    const size_t lds = pcg_lds_bytes(A, coarse);
+    const struct { const void *kernel; int threads; } kernels[] = {
+        {reinterpret_cast<const void *>(k_pcgf<false>), PCG_THREADS},      {reinterpret_cast<const void *>(k_pcgf<false, 2>), PCG_THREADS},
+        {reinterpret_cast<const void *>(k_pcgf<true>), PCGF32_THREADS},    {reinterpret_cast<const void *>(k_pcgf<true, 1>), PCGF32_THREADS},
+        {reinterpret_cast<const void *>(k_pcg), PCG_THREADS},              {reinterpret_cast<const void *>(k_pcgd_iter), PCG_THREADS},
+    };
+    int n = 1 << 30;
+    for (const auto &k : kernels) {
+        raise_dynamic_lds(k.kernel, lds);
+        int nk = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nk, k.kernel, k.threads, lds) != hipSuccess) { (void)hipGetLastError(); nk = 1; }
+        n = std::min(n, nk);
     }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n4, k_pcgf<true>, PCGF32_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); n4 = 1; }
-    {
-        static size_t g5 = 48 * 1024;
-        int n5 = 0;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<true, 1>), lds, g5);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n5, k_pcgf<true, 1>, PCGF32_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); n5 = 1; }
-        n4 = std::min(n4, n5);
-    }
-    n3 = std::min(n3, n4);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, k_pcg, PCG_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); n1 = 1; }
-    n1 = std::min(n1, n3);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, k_pcgd_iter, PCG_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); n2 = 1; }
-    return std::max(1, std::min(n1, n2)) * cus;
+    return std::max(1, n) * cus;
 }
 
 void launch_pcg(const DeviceProblem &P, int which, double mu, hipStream_t st) {
@@ -1631,7 +1617,6 @@ void launch_pcg(const DeviceProblem &P, int which, double mu, hipStream_t st) {
     a.counter = P.pcg_counter; a.hop = P.pcg_hop; a.parity = P.pcg_parity & 1; P.pcg_parity++;
     a.x_out = P.delta_s; a.iters_out = P.pcg_counter + 2; a.flags = P.flags;
     const size_t lds = pcg_lds_bytes(P.A, P.pcg_coarse != 0);
-    static size_t granted = 48 * 1024, granted_f = 48 * 1024, granted_f32 = 48 * 1024;
     a.Wf = nullptr;
     HookScope _h(P, KID_PCG);
     if (P.pcg_fused && !P.deterministic) {   // one pass over W and one hand-over per iteration; its atomics take the sums in any order
@@ -1644,31 +1629,17 @@ void launch_pcg(const DeviceProblem &P, int which, double mu, hipStream_t st) {
         a.eg = P.pcg_yg + (size_t)3 * PCG_NYV * P.n_pad + (size_t)28 * P.A;
         // fp32 blocks (kernels.h, Blocks::Wf): allocated -- and written by pass A INSTEAD of the fp64 blocks -- only where the forcing term is far above what
         // that rounding can show (ba_capi.hip, PCG_W32_MIN_ETA; AAR_PCG_W32=0: never): the allocation is the one place that decides
-        if (b.Wf) {
-            a.Wf = b.Wf;
-            static size_t granted_f32r = 48 * 1024;
-            if (P.pcg_resident) {
-                allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<true, 1>), lds, granted_f32r);
-                hipLaunchKernelGGL((k_pcgf<true, 1>), dim3(P.pcg_grid), dim3(PCGF32_THREADS), lds, st, a, P.pcg_yg, P.pcg_yg + (size_t)3 * PCG_NYV * P.n_pad);
-                return;
-            }
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<true>), lds, granted_f32);
-            hipLaunchKernelGGL(k_pcgf<true>, dim3(P.pcg_grid), dim3(PCGF32_THREADS), lds, st, a, P.pcg_yg, P.pcg_yg + (size_t)3 * PCG_NYV * P.n_pad);
-            return;
-        }
-        if (P.pcg_resident) {   // fp64 blocks, one wavefront per SIMD (512 registers per lane): both rounds of a wavefront's first frame stay in registers (2 x 18 double2 = 144: 256 + 210 in all)
-            static size_t granted_fr = 48 * 1024;
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<false, 2>), lds, granted_fr);
-            hipLaunchKernelGGL((k_pcgf<false, 2>), dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, a, P.pcg_yg, P.pcg_yg + (size_t)3 * PCG_NYV * P.n_pad);
-            return;
-        }
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgf<false>), lds, granted_f);
-        hipLaunchKernelGGL(k_pcgf<false>, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, a, P.pcg_yg, P.pcg_yg + (size_t)3 * PCG_NYV * P.n_pad);
+        double *sg = P.pcg_yg + (size_t)3 * PCG_NYV * P.n_pad;
+        a.Wf = b.Wf;
+        if (b.Wf && P.pcg_resident) launch_lds(k_pcgf<true, 1>, dim3(P.pcg_grid), dim3(PCGF32_THREADS), lds, st, a, P.pcg_yg, sg);
+        else if (b.Wf) launch_lds(k_pcgf<true>, dim3(P.pcg_grid), dim3(PCGF32_THREADS), lds, st, a, P.pcg_yg, sg);
+        // fp64 blocks, one wavefront per SIMD (512 registers per lane): both rounds of a wavefront's first frame stay in registers (2 x 18 double2 = 144: 256 + 210 in all)
+        else if (P.pcg_resident) launch_lds(k_pcgf<false, 2>, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, a, P.pcg_yg, sg);
+        else launch_lds(k_pcgf<false>, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, a, P.pcg_yg, sg);
         return;
     }
     if (b.Wf) { (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.flags), 2, 1, st); return; }   // (k_pcg reads the fp64 blocks, which a block set with Wf does not keep: see pcgf_operator)
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_pcg), lds, granted);
-    hipLaunchKernelGGL(k_pcg, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, a);
+    launch_lds(k_pcg, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, a);
 }
 
 static inline bool pcgd_fused(const DeviceProblem &P) { return P.pcg_fused && !P.deterministic; }
@@ -1704,9 +1675,7 @@ void launch_pcgd_setup(const DeviceProblem &P, int which, double mu, hipStream_t
         (void)hipMemsetAsync(P.pcgd_setup, 0, ((size_t)28 * P.A + 144) * sizeof(double), st);
         (void)hipMemsetAsync(P.pcgd_y, 0, 3 * pcgd_y_stride(P) * sizeof(double), st);
         const size_t lds = ((size_t)27 * P.A + (P.pcg_coarse ? (size_t)12 * P.A + 144 + (PCG_THREADS / 64) * 144 : 0)) * sizeof(double);
-        static size_t granted = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgd_setup_f), lds, granted);
-        hipLaunchKernelGGL(k_pcgd_setup_f, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d);
+        launch_lds(k_pcgd_setup_f, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d);
         return;
     }
     if (P.blk[which].Wf) { (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.flags), 2, 1, st); return; }   // (reads the fp64 blocks: never on a block set that keeps Wf instead)
@@ -1717,26 +1686,17 @@ void launch_pcgd_iter(const DeviceProblem &P, int which, double mu, int k, bool 
     PcgDistArgs d = pcgd_args(P, which, mu);
     d.k = k; d.last = last ? 1 : 0; d.publish_seq = publish_seq;
     const size_t lds = pcg_lds_bytes(P.A, pcgd_fused(P) && P.pcg_coarse != 0);
-    static size_t granted = 48 * 1024, granted_f = 48 * 1024;
     HookScope _h(P, KID_PCG);
     if (pcgd_fused(P)) {
         PcgDistBufs bf;
         const size_t ys = pcgd_y_stride(P), ss = pcgd_state_stride(P);
         bf.state_rd = P.pcgd_state + (size_t)(k % 2) * ss; bf.state_wr = P.pcgd_state + (size_t)((k + 1) % 2) * ss;
         bf.y_rd = P.pcgd_y + (size_t)((k + 2) % 3) * ys; bf.y_wr = P.pcgd_y + (size_t)(k % 3) * ys; bf.y_zero = P.pcgd_y + (size_t)((k + 1) % 3) * ys;
-        if (d.a.Wf) {
-            static size_t granted_f32 = 48 * 1024;
-            allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgd_iter_f<true>), lds, granted_f32);
-            hipLaunchKernelGGL(k_pcgd_iter_f<true>, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d, bf);
-            return;
-        }
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgd_iter_f<false>), lds, granted_f);
-        hipLaunchKernelGGL(k_pcgd_iter_f<false>, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d, bf);
+        launch_lds(d.a.Wf ? k_pcgd_iter_f<true> : k_pcgd_iter_f<false>, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d, bf);
         return;
     }
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_pcgd_iter), lds, granted);
     if (P.blk[which].Wf) { (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.flags), 2, 1, st); return; }
-    hipLaunchKernelGGL(k_pcgd_iter, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d);
+    launch_lds(k_pcgd_iter, dim3(P.pcg_grid), dim3(PCG_THREADS), lds, st, d);
 }
 
 }  // namespace aar

@@ -1585,8 +1585,6 @@ bool launch_schur(const DeviceProblem &P, int which, double sign, hipStream_t st
     const DeviceProblem::Blocks &b = P.blk[which];
     if (P.n_smwork > 0) {   // many shared entities: dense panels + block-of-S-stationary MFMA kernel
         const size_t lds = (size_t)2 * SM_ROWS * SM_PS * sizeof(double);
-        static size_t granted = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_schur_mfma), lds, granted);
         const ReduceArgs red = reduce_args(P, ride_n_err, false, ride_scal ? 0ull : ride_seq, ride_scal);
         const int extra = (ride_seq || ride_scal) ? 1 : 0;
         HookScope _h(P, KID_SCHUR);
@@ -1594,35 +1592,25 @@ bool launch_schur(const DeviceProblem &P, int which, double sign, hipStream_t st
             hipLaunchKernelGGL(k_schur_fill, dim3((unsigned)(((int64_t)P.total_slots * 6 + (int64_t)P.F * 6 + 255) / 256) + extra), dim3(256), 0, st, P.slot_frame, P.slot_dense,
                                b.W, b.Vinv, b.gf, P.total_slots, P.F, P.Ad, P.Wd, P.Yd, extra, red);
         const int extra_m = panels_ready ? extra : 0;
-        hipLaunchKernelGGL(k_schur_mfma, dim3(P.n_smwork + extra_m), dim3(512), lds, st, P.sm_ga, P.sm_gb, P.sm_fb, P.sm_fe, P.sm_frames, P.dense_ent, P.Wd, P.Yd, P.Ad, P.n_pad, sign,
-                           b.S, b.rhs, extra_m, red);
+        launch_lds(k_schur_mfma, dim3(P.n_smwork + extra_m), dim3(512), lds, st, P.sm_ga, P.sm_gb, P.sm_fb, P.sm_fe, P.sm_frames, P.dense_ent, P.Wd, P.Yd, P.Ad, P.n_pad, sign,
+                   b.S, b.rhs, extra_m, red);
         return extra != 0;
     }
     if (P.n_swork == 0) return false;
     if (P.deterministic) {   // one wavefront per work item, records instead of atomics, fixed-order sums; the scalars do not ride
         const size_t lds1 = ((size_t)P.A * 36 + 8 + 48) * sizeof(double);
-        static size_t granted_d = 48 * 1024;
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_schur<0, 1>), lds1, granted_d);
         HookScope _h(P, KID_SCHUR);
-        hipLaunchKernelGGL((k_schur<0, 1>), dim3(P.n_swork), dim3(64), lds1, st, P.sw_ent, P.sw_begin, P.sw_end, P.pair_rec, P.fslot_ent, b.W, b.Vinv, b.hf, P.A, P.n_pad, sign,
-                           b.S, b.rhs, 0, ReduceArgs(), P.sp_part, P.sp_off);
+        launch_lds(k_schur<0, 1>, dim3(P.n_swork), dim3(64), lds1, st, P.sw_ent, P.sw_begin, P.sw_end, P.pair_rec, P.fslot_ent, b.W, b.Vinv, b.hf, P.A, P.n_pad, sign,
+                   b.S, b.rhs, 0, ReduceArgs(), P.sp_part, P.sp_off);
         hipLaunchKernelGGL(k_schur_reduce, dim3(P.A), dim3(256), 0, st, P.se_start, P.se_items, P.sp_off, P.sp_part, P.n_pad, sign, b.S, b.rhs);
         return false;
     }
     const size_t lds = ((size_t)P.A * 36 + 8 + 4 * 48) * sizeof(double);
-    static size_t granted0 = 48 * 1024, granted3 = 48 * 1024;
     const ReduceArgs red = reduce_args(P, ride_n_err, false, ride_scal ? 0ull : ride_seq, ride_scal);
     const int extra = (ride_seq || ride_scal) ? 1 : 0;
     HookScope _h(P, KID_SCHUR);
-    if (P.max_kf > 64) {
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_schur<3>), lds, granted3);
-        hipLaunchKernelGGL(k_schur<3>, dim3(P.n_swork + extra), dim3(256), lds, st, P.sw_ent, P.sw_begin, P.sw_end, P.pair_rec, P.fslot_ent, b.W, b.Vinv, b.hf,
-                           P.A, P.n_pad, sign, b.S, b.rhs, extra, red);
-    } else {
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_schur<0>), lds, granted0);
-        hipLaunchKernelGGL(k_schur<0>, dim3(P.n_swork + extra), dim3(256), lds, st, P.sw_ent, P.sw_begin, P.sw_end, P.pair_rec, P.fslot_ent, b.W, b.Vinv, b.hf,
-                           P.A, P.n_pad, sign, b.S, b.rhs, extra, red);
-    }
+    launch_lds(P.max_kf > 64 ? k_schur<3> : k_schur<0>, dim3(P.n_swork + extra), dim3(256), lds, st, P.sw_ent, P.sw_begin, P.sw_end, P.pair_rec, P.fslot_ent, b.W, b.Vinv, b.hf,
+               P.A, P.n_pad, sign, b.S, b.rhs, extra, red, nullptr, nullptr);   // (no records: the atomic flush)
     return extra != 0;
 }
 
@@ -1642,7 +1630,6 @@ BacksubArgs backsub_args(const DeviceProblem &P, int cur, int trial, int waves_p
 bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial) {
     const DeviceProblem::Blocks &b = P.blk[which];
     const size_t lds_diag = ((size_t)NB * (NB + 2) + 2 * NB * DG_YS + (size_t)NB * (NB / 2 + 2)) * sizeof(double);   // tile | panel | look-ahead half panel
-    static size_t g_diag = 48 * 1024, g_bs = 48 * 1024;
     // block columns with at most this many tiles below the diagonal take the fused panel kernel (0: never); its redundancy grows
     // with the square of the column's height, the two-kernel path's fixed cost does not  (3: +2.6 % on a four-tile system, nothing at 14 tiles)
     const int fused_m = P.tune.fused_panel;
@@ -1654,7 +1641,6 @@ bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, i
     // Look-ahead: where trsm and update are launches of their own (tall block columns), the update is not launched: the next diagonal tile's
     // workgroup applies it to its own tile and starts factoring, riders of that launch do the other tiles (AAR_LDL_LOOKAHEAD=0: off)
     const bool lookahead = P.tune.lookahead != 0;
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_ldl_diag), lds_diag, g_diag);
     bool rode_backsub = false;
     int upd_s = -1;   // the block column whose update the next k_ldl_diag launch carries
     for (int s = 0; s < P.nT; s++) {
@@ -1667,9 +1653,9 @@ bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, i
         BacksubArgs ba = backsub_args(P, which, trial >= 0 ? trial : which, DG_THREADS / 64);
         if (ride || ride2) P.bs_epoch++;
         const int grid = 1 + (ride ? 1 : 0) + (ride2 ? ba.n_frame_blocks + 1 : 0) + (upd_s >= 0 ? ldl_update_riders(P.nT - upd_s - 1) : 0);
-        { HookScope _h(P, KID_LDL_DIAG); hipLaunchKernelGGL(k_ldl_diag, dim3(grid), dim3(DG_THREADS), lds_diag, st, b.S, P.Dfac, P.Linv16, P.n_pad, P.n, s, mu, P.ent_fixed, P.flags,
-                                                         P.nT, b.rhs, b.g0, P.delta_s, P.Lp, P.zf, fused_m, P.bs_flags, P.bs_epoch, ride ? 1 : 0, ride2 ? 1 : 0, ba,
-                                                         upd_s, b.S, b.rhs); }
+        { HookScope _h(P, KID_LDL_DIAG); launch_lds(k_ldl_diag, dim3(grid), dim3(DG_THREADS), lds_diag, st, b.S, P.Dfac, P.Linv16, P.n_pad, P.n, s, mu, P.ent_fixed, P.flags,
+                                                 P.nT, b.rhs, b.g0, P.delta_s, P.Lp, P.zf, fused_m, P.bs_flags, P.bs_epoch, ride ? 1 : 0, ride2 ? 1 : 0, ba,
+                                                 upd_s, b.S, b.rhs); }
         upd_s = -1;
         rode_backsub = ride2;
         if (m > 0 && m <= fused_m) {   // short block column: panel solve and trailing update in one launch
@@ -1684,11 +1670,9 @@ bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, i
     }
     if (P.nT > 1 && !(bs_rides && P.nT <= 3)) {
         const size_t lds = ((size_t)NB * (NB + 2) + 2 * NB + 10 * NB) * sizeof(double);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_ldl_backsolve), lds, g_bs);
         P.bs_epoch++;
         HookScope _h(P, KID_LDL_BACKSOLVE);
-        hipLaunchKernelGGL(k_ldl_backsolve, dim3(P.nT - 1), dim3(1024), lds, st, b.S, b.rhs, P.Dfac, P.delta_s, P.n_pad, P.nT, P.bs_flags, P.bs_epoch, P.flags, P.Lp, P.zf,
-                           fused_m);
+        launch_lds(k_ldl_backsolve, dim3(P.nT - 1), dim3(1024), lds, st, b.S, b.rhs, P.Dfac, P.delta_s, P.n_pad, P.nT, P.bs_flags, P.bs_epoch, P.flags, P.Lp, P.zf, fused_m);
     }
     return rode_backsub;
 }

@@ -614,11 +614,8 @@ static void launch_spcg_pre(const DeviceProblem &P, int which, double mu, hipStr
     a.share = w; w += 80 * ne;
     a.flags = P.flags;
     k.pre_rows = a.rows; k.pre_minv = a.minv; k.pre_z = a.z; k.pre_azt = a.azt; k.pre_share = a.share; k.root_c = a.root_c; k.root_m = a.root_m;
-    static size_t granted = 0;
-    const size_t lds = spcg_pre_lds_bytes(P.n_pad);
-    allow_dynamic_lds(reinterpret_cast<const void *>(k_spcg_pre), lds, granted);
     HookScope _h(P, KID_SPCG_PRE);
-    hipLaunchKernelGGL(k_spcg_pre, dim3((unsigned)ne), dim3(256), lds, st, a);
+    launch_lds(k_spcg_pre, dim3((unsigned)ne), dim3(256), spcg_pre_lds_bytes(P.n_pad), st, a);
 }
 
 bool spcg_fits(int nT) { return nT >= 1 && nT <= SPCG_MAX_NT; }

@@ -265,6 +265,57 @@ def test_problems_with_different_solvers_live_side_by_side_in_one_process():
             p.close()
 
 
+# Each part in a fresh process: the dynamic LDS a kernel may use is process-wide state, and any PCG solve before the side-by-side sequence (the solo runs,
+# earlier tests) would already have raised it.  Problem 1 (A = 160) launches k_pcgf at 104 896 B; problem 2 (A = 200) is created, and its grid sizing opts
+# the kernels in at ITS footprint; problem 1 then launches again before problem 2 does (problem 2's own launch, at 127 936 B, would raise the limit again).
+_PCG_TWO_SIZES_CHILD = """
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import aar
+dss = [aar.synth(5, num_frames=300, num_markers=m) for m in (144, 184)]
+if sys.argv[2] == "alone":
+    out = []
+    for ds in dss:
+        with aar.Problem(ds, solver="pcg") as p:
+            out.append([t["err"] for t in p.lm_solve(ds.x_full)[1]["trace"]])
+else:
+    steps = json.loads(sys.argv[2])
+    ps = [aar.Problem(dss[0], solver="pcg")]
+    ps[0].lm_init(dss[0].x_full)
+    errs = [[ps[0].lm_step()["err"]], []]
+    ps.append(aar.Problem(dss[1], solver="pcg"))
+    ps[1].lm_init(dss[1].x_full)
+    for _ in range(max(steps)):
+        for i in (0, 1):
+            if len(errs[i]) < steps[i]:
+                errs[i].append(ps[i].lm_step()["err"])
+    out = {"errs": errs, "solvers": [p.solver_stats()["solver"] for p in ps]}
+    for p in ps:
+        p.close()
+print(json.dumps(out))
+"""
+
+
+def _pcg_two_sizes_child(mode):
+    import json
+    import subprocess
+    import sys
+    pkg = os.path.dirname(os.path.dirname(os.path.abspath(aar.__file__)))
+    out = subprocess.run([sys.executable, "-c", _PCG_TWO_SIZES_CHILD, pkg, mode], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    return json.loads([l for l in out.stdout.splitlines() if l.startswith(("{", "["))][-1])
+
+
+def test_pcg_problems_of_different_sizes_live_side_by_side_in_one_process():
+    import json
+    alone = _pcg_two_sizes_child("alone")
+    assert len(alone[0]) >= 2 and len(alone[1]) >= 1, alone   # (problem 1 steps again after problem 2's creation)
+    side = _pcg_two_sizes_child(json.dumps([len(t) for t in alone]))
+    assert side["solvers"] == ["pcg", "pcg"]
+    for i in (0, 1):
+        np.testing.assert_allclose(side["errs"][i], alone[i], rtol=1e-4, err_msg=str(i))
+
+
 @pytest.mark.parametrize("cfg", [3, 4, 5])
 def test_inexact_solvers_at_full_size_against_the_direct_path(cfg):
     # configs 3, 4, 5 at FULL size: PCG through the frame blocks (what AUTO picks at config 5) and, where the reduced system fits the wavefronts'
