@@ -36,6 +36,7 @@ SYMBOLS = [
     "aar_solution_read_ex", "aar_cam_configs_read_ex", "aar_set_stage_timers", "aar_problem_pcg_iterations",
     "aar_solver_default_options", "aar_problem_create_ex", "aar_problem_get_solver_stats", "aar_problem_set_test_hook",
     "aar_problem_covariance", "aar_covariance_write_yaml",
+    "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
 ]
 NUM_KERNELS = 17
 SOLVER_DIRECT, SOLVER_PCG, SOLVER_SPCG, SOLVER_AUTO = 0, 1, 2, 3
@@ -102,6 +103,16 @@ class CSolverStats(C.Structure):
 class CCovarianceReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("sum_sq", C.c_double),
                 ("sigma2", C.c_double), ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("frames_written", C.c_int32)]
+
+
+class COutlierRule(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("k_median", C.c_double), ("min_px", C.c_double)]
+
+
+class CResidualReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_detections", C.c_int64), ("num_rejected", C.c_int64), ("num_nonfinite", C.c_int64),
+                ("sum_sq", C.c_double), ("rmse", C.c_double), ("median", C.c_double), ("max", C.c_double), ("threshold", C.c_double),
+                ("cams_emptied", C.c_int32), ("markers_emptied", C.c_int32), ("frames_emptied", C.c_int32)]
 
 
 class CLmParams(C.Structure):
@@ -204,6 +215,10 @@ def lib():
     L.aar_eval_damped_step.argtypes = [C.c_void_p, dp, C.c_double, dp]
     L.aar_problem_covariance.argtypes = [C.c_void_p, dp, dp, dp, dp, C.POINTER(CCovarianceReport)]
     L.aar_covariance_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.c_double]
+    u8p = C.POINTER(C.c_uint8)
+    L.aar_problem_residual_report.argtypes = [C.c_void_p, dp, C.POINTER(COutlierRule), dp, u8p, dp, dp, dp, C.POINTER(CResidualReport)]
+    L.aar_dataset_select_observations.argtypes = [C.POINTER(CDataset), u8p, C.POINTER(C.POINTER(CDataset))]
+    L.aar_residual_report_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, dp, u8p, C.POINTER(CResidualReport)]
     L.aar_lm_default_params.argtypes = [C.POINTER(CLmParams)]
     L.aar_lm_default_params.restype = None
     L.aar_lm_init.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams)]
@@ -258,6 +273,10 @@ def _check(rc):
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _u8ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
 def _np(ptr, n, dtype):
@@ -336,6 +355,24 @@ class Dataset:
         d.optimize_object_poses = int(self.optimize_object_poses)
         d.optimize_cam_intrinsics = int(self.optimize_cam_intrinsics)
         return d
+
+    def select_observations(self, keep):
+        """aar_dataset_select_observations: a copy with the observations where keep is true, in their order; every id, camera, frame,
+        x_full and x_truth kept."""
+        k = np.ascontiguousarray(keep).astype(np.uint8)
+        if k.ndim != 1 or k.shape[0] != self.num_obs:
+            raise ValueError("keep must have one entry per observation (%d), got shape %s" % (self.num_obs, k.shape))
+        c = self.as_c()
+        truth = None
+        if self.x_truth is not None:
+            truth = np.ascontiguousarray(self.x_truth, dtype=np.float64)
+            c.x_truth = _dptr(truth)
+        p = C.POINTER(CDataset)()
+        _check(lib().aar_dataset_select_observations(C.byref(c), _u8ptr(k), C.byref(p)))
+        try:
+            return Dataset(p)
+        finally:
+            lib().aar_dataset_free(p)
 
 
 def synth_desc(config_index, **over):
@@ -628,6 +665,34 @@ def covariance_write_yaml(path, ds, entity_diag_flat, sigma2, frames=None):
     _check(lib().aar_covariance_write_yaml(path.encode(), C.byref(c), _dptr(d), _dptr(fr) if fr is not None else None, float(sigma2)))
 
 
+class ResidualReport:
+    """What Problem.residual_report returns (see there)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _report_c(rep):
+    r = CResidualReport()
+    r.struct_size = C.sizeof(CResidualReport)
+    for name, _ in CResidualReport._fields_[1:]:
+        setattr(r, name, rep[name])
+    return r
+
+
+def residual_report_write_yaml(path, ds, rr, det_err=True):
+    """aar_residual_report_write_yaml: rr as Problem.residual_report returns it for a (single-GPU) problem created from ds; det_err=False
+    leaves the list of rejected detections out"""
+    c = ds.as_c()
+    cs = np.ascontiguousarray(rr.cam_stats, dtype=np.float64)
+    ms = np.ascontiguousarray(rr.marker_stats, dtype=np.float64)
+    e = np.ascontiguousarray(rr.det_err, dtype=np.float64) if det_err else None
+    k = np.ascontiguousarray(rr.keep, dtype=np.uint8) if det_err else None
+    r = _report_c(rr.report)
+    _check(lib().aar_residual_report_write_yaml(path.encode(), C.byref(c), _dptr(cs), _dptr(ms), _dptr(e) if det_err else None,
+                                                _u8ptr(k) if det_err else None, C.byref(r)))
+
+
 class Problem:
     """aar_problem: the bundle-adjustment problem resident on one GPU."""
 
@@ -750,6 +815,31 @@ class Problem:
                           min_pivot=rep.min_pivot, max_pivot=rep.max_pivot, frames_written=rep.frames_written,
                           entity_diag=blocks, entity_diag_flat=diag, entity_cov=ecov,
                           frames=fr.reshape(-1, 6, 6) if want_fr else None)
+
+    def residual_report(self, x_full, k_median=0.0, min_px=0.0, rule=None):
+        """aar_problem_residual_report at x_full.  The rule's threshold is max(min_px, k_median * median) (k_median <= 0: min_px; both <= 0:
+        +inf); rule=False passes no rule at all (the same threshold), rule=None passes one when k_median or min_px is set.  Returns a
+        ResidualReport: det_err, keep ([local_obs], this rank's detections in reference order), cam_stats [C][4], marker_stats [M][4],
+        frame_stats [F][4] ({detections, sum r^2, max e_d, rejected}; on a sharded problem only this rank's frames, the others NaN) and
+        report (a dict of the aar_residual_report fields)."""
+        x = self._x(x_full)
+        n = self.local_obs
+        e = np.zeros(max(n, 1))
+        k = np.zeros(max(n, 1), dtype=np.uint8)
+        cs = np.zeros((self.ds.num_cams, 4))
+        ms = np.zeros((self.ds.num_markers, 4))
+        fs = np.full((max(self.ds.num_frames, 1), 4), np.nan)
+        use = (k_median != 0 or min_px != 0) if rule is None else bool(rule)
+        r = COutlierRule()
+        r.struct_size = C.sizeof(COutlierRule)
+        r.k_median, r.min_px = float(k_median), float(min_px)
+        rep = CResidualReport()
+        rep.struct_size = C.sizeof(CResidualReport)
+        _check(lib().aar_problem_residual_report(self.handle, _dptr(x), C.byref(r) if use else None, _dptr(e), _u8ptr(k), _dptr(cs), _dptr(ms),
+                                                 _dptr(fs), C.byref(rep)))
+        report = {name: getattr(rep, name) for name, _ in CResidualReport._fields_[1:]}
+        return ResidualReport(det_err=e[:n], keep=k[:n].astype(bool), cam_stats=cs, marker_stats=ms, frame_stats=fs[:self.ds.num_frames],
+                              report=report)
 
     def reproj_stats(self, x_full):
         x = self._x(x_full)

@@ -267,6 +267,9 @@ struct aar_problem {
     // aar_problem_covariance: workspace, allocated on the first call (cov_kernels.hip)
     double *cov_ws = nullptr;
     int32_t *cov_iws = nullptr;
+    // aar_problem_residual_report: buffers and the ordering-B runs with their B -> A permutation, built on the first call (resid_kernels.hip)
+    RRWork rr;
+    bool rr_ready = false;
 };
 
 namespace {
@@ -2015,6 +2018,158 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
         memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
     }
     return check_async("covariance");
+}
+
+// Residual report: e_d and the first digit's histogram in one pass over ordering A, an exact radix select of the
+// lower median on the device (RR_PASSES histogram / pick pairs, no host round trip on one GPU; with a communicator every histogram is
+// all-reduced as doubles, so every rank picks the same digits), then keep flags and the run / entity sums in a fixed order.
+namespace {
+int rr_setup(aar_problem *pb) {
+    DeviceProblem &P = pb->P;
+    RRWork &w = pb->rr;
+    const int64_t N = P.N;
+    const int C = P.C, M = P.M;
+    // ordering B as the problem built it (a stable sort of ordering A by camera, marker): rebuilt here from the device's ordering A,
+    // its (camera, marker) runs and their lists per camera / marker
+    std::vector<ObsIdx> a_idx((size_t)N);
+    int rc;
+    if (N && (rc = copy_d2h(pb, a_idx.data(), P.a_idx, (size_t)N * sizeof(ObsIdx)))) return rc;
+    std::vector<int32_t> perm((size_t)N);
+    std::iota(perm.begin(), perm.end(), 0);
+    std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
+        const ObsIdx &p = a_idx[x], &q = a_idx[y];
+        if (p.cam != q.cam) return p.cam < q.cam;
+        if (p.marker != q.marker) return p.marker < q.marker;
+        return p.frame < q.frame;
+    });
+    std::vector<int32_t> run_start, run_mk, cam_run_start(C + 1, 0), mk_run_start(M + 1, 0), mk_runs;
+    for (int64_t i = 0; i < N;) {
+        const ObsIdx &h = a_idx[perm[i]];
+        int64_t e = i;
+        while (e < N && a_idx[perm[e]].cam == h.cam && a_idx[perm[e]].marker == h.marker) e++;
+        cam_run_start[h.cam + 1]++;
+        mk_run_start[h.marker - C + 1]++;
+        run_start.push_back((int32_t)i);
+        run_mk.push_back(h.marker - C);
+        i = e;
+    }
+    const int R = (int)run_start.size();
+    run_start.push_back((int32_t)N);
+    for (int c = 0; c < C; c++) cam_run_start[c + 1] += cam_run_start[c];
+    for (int m = 0; m < M; m++) mk_run_start[m + 1] += mk_run_start[m];
+    mk_runs.resize(R);
+    {
+        std::vector<int32_t> fill(mk_run_start.begin(), mk_run_start.end() - 1);
+        for (int r = 0; r < R; r++) mk_runs[fill[run_mk[r]]++] = r;   // runs are camera-ascending: so is every marker's list
+    }
+    w.R = R;
+    if ((rc = dev_upload(pb, &w.perm, perm)) || (rc = dev_upload(pb, &w.run_start, run_start)) || (rc = dev_upload(pb, &w.cam_run_start, cam_run_start)) ||
+        (rc = dev_upload(pb, &w.mk_run_start, mk_run_start)) || (rc = dev_upload(pb, &w.mk_runs, mk_runs)))
+        return rc;
+    if ((rc = dev_alloc(pb, &w.err, (size_t)N)) || (rc = dev_alloc(pb, &w.ss, (size_t)N)) || (rc = dev_alloc(pb, &w.keep, (size_t)N)) ||
+        (rc = dev_alloc(pb, &w.fstat, 4 * (size_t)P.F)) || (rc = dev_alloc(pb, &w.rstat, 5 * (size_t)R)) || (rc = dev_alloc(pb, &w.rmax, (size_t)R)) ||
+        (rc = dev_alloc(pb, &w.esum, 5 * (size_t)(C + M) + 1)) || (rc = dev_alloc(pb, &w.emax, (size_t)(C + M))) ||
+        (rc = dev_alloc(pb, &w.hist, (size_t)RR_HIST_WORDS)) || (rc = dev_alloc(pb, &w.hd, (size_t)RR_BINS + 2)) || (rc = dev_alloc(pb, &w.sel, 1)))
+        return rc;
+    pb->rr_ready = true;
+    return AAR_OK;
+}
+
+double rr_threshold_host(const aar_outlier_rule *rule, double median) {   // (k_rr_keep's rule, for a problem without detections)
+    if (!rule || (rule->k_median <= 0.0 && rule->min_px <= 0.0)) return INFINITY;
+    if (rule->k_median <= 0.0) return rule->min_px;
+    const double a = rule->k_median * median;
+    return a > rule->min_px ? a : rule->min_px;
+}
+}  // namespace
+
+int aar_problem_residual_report(aar_problem *pb, const double *x_full, const aar_outlier_rule *rule, double *det_err, uint8_t *keep,
+                                double *cam_stats, double *marker_stats, double *frame_stats, aar_residual_report *report) {
+    if (!pb || !x_full || !report) return set_error(AAR_ERR_INVALID, "aar_problem_residual_report: null argument");
+    if (report->struct_size != sizeof(aar_residual_report))
+        return set_error(AAR_ERR_INVALID, "aar_problem_residual_report: report->struct_size %u, expected %zu", report->struct_size, sizeof(aar_residual_report));
+    if (rule && rule->struct_size != sizeof(aar_outlier_rule))
+        return set_error(AAR_ERR_INVALID, "aar_problem_residual_report: rule->struct_size %u, expected %zu", rule->struct_size, sizeof(aar_outlier_rule));
+    if (rule && (std::isnan(rule->k_median) || std::isnan(rule->min_px))) return set_error(AAR_ERR_INVALID, "aar_problem_residual_report: NaN in the rule");
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int C = P.C, M = P.M, cur = pb->cur;
+    aar_residual_report r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = report->struct_size;
+    if (pb->N_global == 0) {   // nothing to select (the same on every rank)
+        if (cam_stats) std::fill(cam_stats, cam_stats + 4 * (size_t)C, 0.0);
+        if (marker_stats) std::fill(marker_stats, marker_stats + 4 * (size_t)M, 0.0);
+        if (frame_stats) std::fill(frame_stats + 4 * (size_t)pb->f_begin, frame_stats + 4 * (size_t)pb->f_end, 0.0);
+        r.rmse = r.median = r.max = NAN;
+        r.threshold = rr_threshold_host(rule, NAN);
+        *report = r;
+        return AAR_OK;
+    }
+    int rc;
+    if (!pb->rr_ready && (rc = rr_setup(pb))) return rc;
+    const RRWork &w = pb->rr;
+    if ((rc = upload_z(pb, x_full, cur))) return rc;
+    // whatever the LM state was, it is gone: z[cur] and its entity rows now hold x_full
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    pb->vinv_mu = pb->schur_mu = -1;
+    pb->s_reduced = pb->trial_reduced = false;
+    pb->spec_chol_blk = -1;
+    if (pb->panels_blk == cur) pb->panels_blk = -1;
+    HIP_TRY(hipMemsetAsync(w.hist, 0, RR_HIST_WORDS * sizeof(uint32_t), pb->stream));
+    launch_unpack(P, cur, pb->stream);
+    launch_rr_errors(P, cur, w, (unsigned long long)((pb->N_global - 1) / 2), pb->stream);
+    for (int pass = 0; pass < RR_PASSES; pass++) {
+        if (pass > 0) launch_rr_select_pass(P, w, pb->stream);
+        if (pb->comm) {
+            launch_rr_to_double(w, pb->stream);
+            if ((rc = allreduce(pb, w.hd, RR_BINS + 2, NCCL_SUM))) return rc;
+        }
+        launch_rr_pick(w, pb->comm != nullptr, pb->stream);
+    }
+    launch_rr_stats(P, w, rule ? 1 : 0, rule ? rule->k_median : 0.0, rule ? rule->min_px : 0.0, pb->stream);
+    pb->launches += 2 + 2 * RR_PASSES + 2 + (w.R > 0 ? 1 : 0) + (pb->comm ? RR_PASSES : 0);
+    if ((rc = check_async("residual report kernels"))) return rc;
+    if (pb->comm && ((rc = allreduce(pb, w.esum, 5 * (size_t)(C + M) + 1, NCCL_SUM)) || (rc = allreduce(pb, w.emax, (size_t)(C + M), NCCL_MAX)))) return rc;
+    HIP_TRY(hipStreamSynchronize(pb->stream));
+    RRSel sel;
+    std::vector<double> esum(5 * (size_t)(C + M) + 1), emax((size_t)(C + M));
+    if ((rc = copy_d2h(pb, &sel, w.sel, sizeof sel)) || (rc = copy_d2h(pb, esum.data(), w.esum, esum.size() * sizeof(double))) ||
+        (rc = copy_d2h(pb, emax.data(), w.emax, emax.size() * sizeof(double))))
+        return rc;
+    if (!sel.done) return set_error(AAR_ERR_HIP, "residual report: the select did not converge (rank %llu left at bit %d)", sel.rank, sel.pshift);
+    if (det_err && P.N && (rc = copy_d2h(pb, det_err, w.err, (size_t)P.N * sizeof(double)))) return rc;
+    if (keep && P.N && (rc = copy_d2h(pb, keep, w.keep, (size_t)P.N))) return rc;
+    if (frame_stats && P.F && (rc = copy_d2h(pb, frame_stats + 4 * (size_t)pb->f_begin, w.fstat, 4 * (size_t)P.F * sizeof(double)))) return rc;
+    double mx = 0.0;
+    int64_t n_nan = 0;
+    for (int e = 0; e < C + M; e++) {
+        const double *q = &esum[5 * (size_t)e];
+        const double emx = q[4] > 0 ? NAN : emax[e];
+        double *out = e < C ? (cam_stats ? cam_stats + 4 * (size_t)e : nullptr) : (marker_stats ? marker_stats + 4 * (size_t)(e - C) : nullptr);
+        if (out) { out[0] = q[0]; out[1] = q[1]; out[2] = emx; out[3] = q[2]; }
+        const bool emptied = q[0] > 0 && q[2] == q[0];
+        if (e < C) {   // every detection belongs to exactly one camera: the totals are the cameras' sums, ascending
+            r.num_detections += (int64_t)q[0];
+            r.num_rejected += (int64_t)q[2];
+            r.num_nonfinite += (int64_t)q[3];
+            n_nan += (int64_t)q[4];
+            r.sum_sq += q[1];
+            mx = std::max(mx, emax[e]);
+            r.cams_emptied += emptied;
+        } else {
+            r.markers_emptied += emptied;
+        }
+    }
+    r.frames_emptied = (int32_t)esum[5 * (size_t)(C + M)];
+    r.rmse = std::sqrt(r.sum_sq / (4.0 * (double)r.num_detections));
+    uint64_t mk = sel.prefix;
+    memcpy(&r.median, &mk, sizeof mk);
+    r.max = n_nan > 0 ? NAN : mx;
+    r.threshold = sel.t;
+    *report = r;
+    return AAR_OK;
 }
 
 // SparseLevMarq::init, libs/sparselevmarq.h:238-249.  The residual of the start point comes out of the same pass that

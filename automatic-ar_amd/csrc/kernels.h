@@ -286,6 +286,36 @@ void launch_cov_diag_blocks(const double *Sinv, int n_pad, int A, double *out, h
 // out[f][36] = (J^T J)^-1 block of local frame f from Vinv of block set `which` (mu = 0), its W blocks and Sinv
 void launch_cov_frames(const DeviceProblem &P, int which, const double *Sinv, const int32_t *rowmask, double *out, hipStream_t st);
 
+// residual report (resid_kernels.hip).  The select's state: the key bits [pshift, 63) picked so far, the rank still
+// wanted inside that bucket, done (prefix = the key), single (one key left in the bucket: the next pass fetches it), t = the threshold
+constexpr int RR_DIGIT_BITS = 11, RR_BINS = 1 << RR_DIGIT_BITS, RR_PASSES = 6;   // 63 key bits = 5 digits of 11 + one of 8
+struct RRSel {
+    unsigned long long prefix, rank;
+    double t;
+    int pshift, done, single, pad;
+};
+// device buffers of the report (allocated by the first call of a problem): per observation of ordering A err, ss (its sum r^2), keep;
+// [F][4] frame stats; ordering B as runs of (camera, marker): perm (B -> A), run_start [R+1]; cam_run_start [C+1] (runs of a camera are
+// contiguous), mk_run_start [M+1] / mk_runs [R] (the runs of a marker, camera-ascending); rstat [R][5], rmax [R]; esum [5 (C+M) + 1],
+// emax [C+M] (k_rr_entities); hist: [RR_BINS] counts | 2 halves of a found key | frames-emptied counter; hd: hist as doubles
+struct RRWork {
+    double *err = nullptr, *ss = nullptr, *fstat = nullptr, *rstat = nullptr, *esum = nullptr, *emax = nullptr, *hd = nullptr;
+    uint8_t *keep = nullptr;
+    int32_t *perm = nullptr, *run_start = nullptr, *cam_run_start = nullptr, *mk_run_start = nullptr, *mk_runs = nullptr;
+    unsigned long long *rmax = nullptr;
+    uint32_t *hist = nullptr;
+    RRSel *sel = nullptr;
+    int R = 0;
+};
+constexpr int RR_HIST_WORDS = RR_BINS + 3;
+// e_d, ss, frame stats [0..2] and the first digit's histogram at z[which] (ent[which] must hold its rows); starts the select for `rank`
+void launch_rr_errors(const DeviceProblem &P, int which, const RRWork &w, unsigned long long rank, hipStream_t st);
+void launch_rr_select_pass(const DeviceProblem &P, const RRWork &w, hipStream_t st);   // the next digit's histogram
+void launch_rr_to_double(const RRWork &w, hipStream_t st);                               // hist -> hd (the all-reduce payload)
+void launch_rr_pick(const RRWork &w, bool reduced, hipStream_t st);                      // reduced: read hd instead of hist
+// threshold, keep flags, rejected per frame, the run and entity sums
+void launch_rr_stats(const DeviceProblem &P, const RRWork &w, int has_rule, double k_median, double min_px, hipStream_t st);
+
 // The error flags of a rank (bits 0..3) as one double that survives a SUM all-reduce over up to 4095 ranks: bit b set on k ranks adds k 4096^b.
 // Every rank decodes the same value, so every rank takes the same branch (a rank that failed alone would otherwise leave the
 // others waiting in their next collective).

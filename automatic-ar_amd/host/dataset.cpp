@@ -82,6 +82,36 @@ void aar_problem_desc_from_dataset(const aar_dataset *d, aar_problem_desc *p) {
     p->comm = nullptr;
 }
 
+int aar_dataset_select_observations(const aar_dataset *d, const uint8_t *keep, aar_dataset **out) {
+    if (!d || !out || (!keep && d->num_obs > 0)) return aar::set_error(AAR_ERR_INVALID, "aar_dataset_select_observations: null argument");
+    int64_t n = 0;
+    for (int64_t o = 0; o < d->num_obs; o++) n += keep[o] != 0;
+    aar_dataset *r = aar::dataset_alloc(d->num_cams, d->num_markers, d->num_frames, n, d->x_truth != nullptr);
+    if (!r) return aar::set_error(AAR_ERR_INVALID, "aar_dataset_select_observations: out of memory");
+    const int C = d->num_cams, M = d->num_markers, F = d->num_frames;
+    r->root_cam = d->root_cam; r->root_marker = d->root_marker;
+    memcpy(r->cam_ids, d->cam_ids, sizeof(int32_t) * C);
+    memcpy(r->marker_ids, d->marker_ids, sizeof(int32_t) * M);
+    if (F) memcpy(r->frame_ids, d->frame_ids, sizeof(int32_t) * F);
+    memcpy(r->image_sizes, d->image_sizes, sizeof(int32_t) * 2 * C);
+    memcpy(r->cam_mats, d->cam_mats, sizeof(double) * 9 * C);
+    memcpy(r->dist_coeffs, d->dist_coeffs, sizeof(double) * 5 * C);
+    r->marker_size = d->marker_size;
+    const int64_t len = aar_dataset_full_len(d);
+    memcpy(r->x_full, d->x_full, sizeof(double) * len);
+    if (d->x_truth) memcpy(r->x_truth, d->x_truth, sizeof(double) * len);
+    r->optimize_cam_poses = d->optimize_cam_poses; r->optimize_marker_poses = d->optimize_marker_poses;
+    r->optimize_object_poses = d->optimize_object_poses; r->optimize_cam_intrinsics = d->optimize_cam_intrinsics;
+    for (int64_t o = 0, k = 0; o < d->num_obs; o++) {
+        if (!keep[o]) continue;
+        r->obs_frame[k] = d->obs_frame[o]; r->obs_cam[k] = d->obs_cam[o]; r->obs_marker[k] = d->obs_marker[o];
+        memcpy(r->obs_uv + 8 * k, d->obs_uv + 8 * o, 8 * sizeof(float));
+        k++;
+    }
+    *out = r;
+    return AAR_OK;
+}
+
 void aar_rodrigues_vec2mat(const double w[3], double R[9]) { aar::rodrigues_vec2mat(w, R); }
 void aar_rodrigues_mat2vec(const double R[9], double w[3]) { aar::rodrigues_mat2vec(R, w); }
 

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <set>
 #include <stdexcept>
 #include <string>
@@ -26,7 +27,12 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]]" << endl;
+    cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
+    cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
+    cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
+    cout << "                            (up to 3 rounds, until a round drops nothing); final.solution keeps the remaining detections" << endl;
+    cout << "       -reject-min-px px    the floor of that threshold in pixels (default 0)" << endl;
     cout << "       " << a0 << " --synth <config 1..5> <out_folder>   (write a synthetic data set in the reference's file formats)" << endl;
     return -1;
 }
@@ -60,6 +66,59 @@ static int synth(int cfg, const string &folder) {
     return rc ? 1 : 0;
 }
 
+// -reject-outliers: report, drop, solve again from that solution -- until a round drops nothing, at most 3 rounds.  final.residuals.yaml
+// then holds the final solution's statistics over the detections it kept; its rejected counts and list cover every detection dropped in
+// any round (with its error in the round that dropped it), against the detections the first solve had.
+static int reject_outliers(aar::MultiCamMapper &mcm, const string &res_path, double k, double min_px) {
+    try {
+        aar_dataset *d0 = nullptr;   // a copy of the detections before any round
+        {
+            const aar_dataset *cur = mcm.dataset();
+            vector<uint8_t> all(std::max<int64_t>(cur->num_obs, 1), 1);
+            if (aar_dataset_select_observations(cur, all.data(), &d0)) throw runtime_error(aar_last_error());
+        }
+        unique_ptr<aar_dataset, void (*)(aar_dataset *)> hold(d0, aar_dataset_free);
+        vector<int64_t> alive(d0->num_obs);   // original index of every detection the mapper still has
+        for (int64_t o = 0; o < d0->num_obs; o++) alive[o] = o;
+        vector<uint8_t> keep0(std::max<int64_t>(d0->num_obs, 1), 1);
+        vector<double> err0(std::max<int64_t>(d0->num_obs, 1), 0.0);
+        for (int round = 1; round <= 3; round++) {
+            aar::MultiCamMapper::ResidualReport rr;
+            const int64_t dropped = mcm.reject_outliers(k, min_px, &rr);
+            const aar_residual_report &r = rr.report;
+            cout << "outlier round " << round << ": median " << r.median << " px, threshold " << r.threshold << " px, " << dropped << " of " << r.num_detections
+                 << " detections rejected" << endl;
+            if (r.cams_emptied || r.markers_emptied || r.frames_emptied)
+                cerr << "warning: the rejected detections were all of " << r.cams_emptied << " camera(s), " << r.markers_emptied << " marker(s) and "
+                     << r.frames_emptied << " frame(s)" << endl;
+            vector<int64_t> next;
+            for (size_t i = 0; i < rr.keep.size(); i++) {
+                if (rr.keep[i]) { next.push_back(alive[i]); continue; }
+                keep0[alive[i]] = 0;
+                err0[alive[i]] = rr.det_err[i];
+            }
+            alive.swap(next);
+            if (dropped == 0) break;
+            mcm.solve();
+        }
+        aar::MultiCamMapper::ResidualReport fin = mcm.residual_report(nullptr);
+        // the rejected counts of the file: every detection dropped in any round, per camera / marker index of the (unchanged) entity lists
+        fin.report.num_rejected = 0;
+        for (int c = 0; c < d0->num_cams; c++) fin.cam_stats[4 * c + 3] = 0;
+        for (int m = 0; m < d0->num_markers; m++) fin.marker_stats[4 * m + 3] = 0;
+        for (int64_t o = 0; o < d0->num_obs; o++)
+            if (!keep0[o]) { fin.report.num_rejected++; fin.cam_stats[4 * d0->obs_cam[o] + 3]++; fin.marker_stats[4 * d0->obs_marker[o] + 3]++; }
+        if (aar_residual_report_write_yaml(res_path.c_str(), d0, fin.cam_stats.data(), fin.marker_stats.data(), err0.data(), keep0.data(), &fin.report))
+            throw runtime_error(aar_last_error());
+        cout << "residuals: " << fin.report.num_detections << " detections kept, " << fin.report.num_rejected << " rejected, RMSE " << fin.report.rmse
+             << " px, written to " << res_path << endl;
+    } catch (const exception &e) {
+        cerr << "outlier rejection failed: " << e.what() << endl;
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc >= 4 && string(argv[1]) == "--synth") return synth(atoi(argv[2]), argv[3]);
     if (argc < 3) return print_usage(argv[0]);
@@ -67,10 +126,12 @@ int main(int argc, char *argv[]) {
     const double marker_size = stod(argv[2]);
     bool use_subseqs = false, with_huber = false, set_threshold = false, from_initial = false, tracking_only = false;
     bool covariance = false;   // not an option of the reference: -covariance also writes final.covariance.yaml (aar_problem_covariance)
+    bool residuals = false;    // nor these: -residuals writes final.residuals.yaml; -reject-outliers k drops detections above max(min_px, k median) and solves again
+    double reject_k = 0.0, reject_min_px = 0.0;
     double threshold = 2.0;
     set<int> excluded_cams;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -81,6 +142,15 @@ int main(int argc, char *argv[]) {
         else if (a == "-thresh") { set_threshold = true; arg_flag = Threshold; }
         else if (a == "-solver") arg_flag = Solver;
         else if (a == "-covariance") { covariance = true; arg_flag = NONE; }
+        else if (a == "-residuals") { residuals = true; arg_flag = NONE; }
+        else if (a == "-reject-outliers") arg_flag = RejectK;
+        else if (a == "-reject-min-px") arg_flag = RejectPx;
+        else if (arg_flag == RejectK || arg_flag == RejectPx) {
+            const double v = stod(a);
+            if (!(v > 0.0) && !(arg_flag == RejectPx && v == 0.0)) return print_usage(argv[0]);
+            (arg_flag == RejectK ? reject_k : reject_min_px) = v;
+            arg_flag = NONE;
+        }
         else if (arg_flag == Solver) {
             solver = a == "spcg" ? AAR_SOLVER_SPCG : a == "pcg" ? AAR_SOLVER_PCG : a == "auto" ? AAR_SOLVER_AUTO : a == "direct" ? AAR_SOLVER_DIRECT : -1;
             if (solver < 0) return print_usage(argv[0]);
@@ -165,6 +235,19 @@ int main(int argc, char *argv[]) {
     } catch (const exception &e) {
         cerr << "solve failed: " << e.what() << endl;
         return 2;
+    }
+    if (reject_k > 0.0 && reject_outliers(mcm, folder_path + "/final.residuals.yaml", reject_k, reject_min_px)) return 4;
+    else if (residuals && reject_k <= 0.0) {
+        const string res_path = folder_path + "/final.residuals.yaml";
+        try {
+            const aar::MultiCamMapper::ResidualReport rr = mcm.residual_report(nullptr);
+            if (!mcm.write_residuals_file(res_path, rr)) throw runtime_error(aar_last_error());
+            cout << "residuals: " << rr.report.num_detections << " detections, RMSE " << rr.report.rmse << " px, median " << rr.report.median << " px, max "
+                 << rr.report.max << " px, written to " << res_path << endl;
+        } catch (const exception &e) {
+            cerr << "residual report failed: " << e.what() << endl;
+            return 4;
+        }
     }
     const chrono::duration<double> d = chrono::system_clock::now() - start;
     mcm.write_solution_file(final_path);

@@ -343,6 +343,53 @@ bool MultiCamMapper::write_covariance_file(const std::string &path, const Covari
     return aar_covariance_write_yaml(path.c_str(), &d, cov.entity_diag.data(), cov.frame_cov.empty() ? nullptr : cov.frame_cov.data(), cov.sigma2) == AAR_OK;
 }
 
+MultiCamMapper::ResidualReport MultiCamMapper::residual_report(const aar_outlier_rule *rule) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::residual_report: no data set");
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    ResidualReport rr;
+    const size_t N = (size_t)data_->num_obs;
+    rr.det_err.assign(std::max<size_t>(N, 1), 0.0);
+    rr.keep.assign(std::max<size_t>(N, 1), 1);
+    rr.cam_stats.assign(4 * (size_t)data_->num_cams, 0.0);
+    rr.marker_stats.assign(4 * (size_t)data_->num_markers, 0.0);
+    rr.frame_stats.assign(4 * (size_t)std::max(data_->num_frames, 1), 0.0);
+    rr.report.struct_size = (uint32_t)sizeof rr.report;
+    std::vector<double> x = problem_vector();
+    if (aar_problem_residual_report(problem_, x.data(), rule, rr.det_err.data(), rr.keep.data(), rr.cam_stats.data(), rr.marker_stats.data(),
+                                    rr.frame_stats.data(), &rr.report))
+        throw std::runtime_error(aar_last_error());
+    rr.det_err.resize(N);
+    rr.keep.resize(N);
+    rr.frame_stats.resize(4 * (size_t)data_->num_frames);
+    return rr;
+}
+
+int64_t MultiCamMapper::reject_outliers(double k_median, double min_px, ResidualReport *out) {
+    aar_outlier_rule rule;
+    rule.struct_size = (uint32_t)sizeof rule;
+    rule.k_median = k_median;
+    rule.min_px = min_px;
+    ResidualReport rr = residual_report(&rule);
+    const int64_t dropped = rr.report.num_rejected;
+    if (dropped > 0) {
+        // data_->x_full (and with intrinsics cam_mats / dist_coeffs) is the current solution: the new data set starts from it
+        aar_dataset *nd = nullptr;
+        if (aar_dataset_select_observations(data_, rr.keep.data(), &nd)) throw std::runtime_error(aar_last_error());
+        drop_problem();
+        aar_dataset_free(data_);
+        data_ = nd;
+        mats2eVec();
+    }
+    if (out) *out = std::move(rr);
+    return dropped;
+}
+
+bool MultiCamMapper::write_residuals_file(const std::string &path, const ResidualReport &rep) {
+    if (!data_ || rep.keep.size() != (size_t)data_->num_obs) return false;   // (the list names the detections of the data set the report was made of)
+    return aar_residual_report_write_yaml(path.c_str(), data_, rep.cam_stats.data(), rep.marker_stats.data(), rep.det_err.data(), rep.keep.data(),
+                                          &rep.report) == AAR_OK;
+}
+
 void MultiCamMapper::error_function(const eVector &input, eVector &error) {
     if (probed(detail::EVAL_ERROR_FUNCTION)) return;
     if (!data_) throw std::runtime_error("MultiCamMapper::error_function: no data set");

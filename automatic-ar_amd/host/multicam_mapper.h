@@ -456,6 +456,20 @@ class MultiCamMapper {
     Covariance compute_covariance(bool frames = true);
     bool write_covariance_file(const std::string &path, const Covariance &cov);   // YAML, aar_covariance_write_yaml
 
+    // EXTENSION, no counterpart in the reference: reprojection errors of the current solution per detection and per camera / marker / frame
+    // (aar_problem_residual_report at io_vec's poses, for the current Config); stats are [index][4] {detections, sum r^2, max, rejected} in
+    // the data set's index order.  rule NULL: nothing is rejected.  Throws std::runtime_error on failure.
+    struct ResidualReport {
+        aar_residual_report report{};
+        std::vector<double> det_err, cam_stats, marker_stats, frame_stats;
+        std::vector<uint8_t> keep;
+    };
+    ResidualReport residual_report(const aar_outlier_rule *rule = nullptr);
+    // drops the detections the rule max(min_px, k_median * median) rejects from the data set and rebuilds the device problem (same Config,
+    // solver options and Huber setting) with the current solution as its start; returns how many were dropped (its report in *out if given)
+    int64_t reject_outliers(double k_median, double min_px = 0.0, ResidualReport *out = nullptr);
+    bool write_residuals_file(const std::string &path, const ResidualReport &rep);   // YAML, aar_residual_report_write_yaml
+
     const aar_dataset *dataset() const { return data_; }
 
    private:

@@ -305,6 +305,37 @@ int aar_covariance_write_yaml(const char *path, const aar_dataset *d, const doub
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
 }
 
+int aar_residual_report_write_yaml(const char *path, const aar_dataset *d, const double *cam_stats, const double *marker_stats, const double *det_err,
+                                   const uint8_t *keep, const aar_residual_report *rep) {
+    if (!path || !d || !cam_stats || !marker_stats || !rep || (!det_err != !keep)) return set_error(AAR_ERR_INVALID, "aar_residual_report_write_yaml: null argument");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "num_detections: %lld\nnum_rejected: %lld\nnum_nonfinite: %lld\n", (long long)rep->num_detections, (long long)rep->num_rejected,
+            (long long)rep->num_nonfinite);
+    fprintf(f, "sum_sq: %s\nrmse: %s\nmedian: %s\nmax: %s\nthreshold: %s\n", fs_double_nf(rep->sum_sq).c_str(), fs_double_nf(rep->rmse).c_str(),
+            fs_double_nf(rep->median).c_str(), fs_double_nf(rep->max).c_str(), fs_double_nf(rep->threshold).c_str());
+    fprintf(f, "cams_emptied: %d\nmarkers_emptied: %d\nframes_emptied: %d\n", rep->cams_emptied, rep->markers_emptied, rep->frames_emptied);
+    auto entity = [&](const char *key, int id, const double *q) {   // q = {detections, sum r^2, max e_d, rejected}
+        fprintf(f, "   - { %s:%d, detections:%lld, rmse: %s, max: %s, rejected:%lld }\n", key, id, (long long)q[0],
+                fs_double_nf(q[0] > 0 ? std::sqrt(q[1] / (4.0 * q[0])) : 0.0).c_str(), fs_double_nf(q[2]).c_str(), (long long)q[3]);
+    };
+    fprintf(f, "cameras:\n");
+    for (int c = 0; c < d->num_cams; c++) entity("cam_id", d->cam_ids[c], cam_stats + 4LL * c);
+    fprintf(f, "markers:\n");
+    for (int m = 0; m < d->num_markers; m++) entity("marker_id", d->marker_ids[m], marker_stats + 4LL * m);
+    if (keep) {
+        fprintf(f, "rejected_detections:\n");
+        for (int64_t o = 0; o < d->num_obs; o++)
+            if (!keep[o])
+                fprintf(f, "   - { frame_id:%d, cam_id:%d, marker_id:%d, error: %s }\n", d->frame_ids[d->obs_frame[o]], d->cam_ids[d->obs_cam[o]],
+                        d->marker_ids[d->obs_marker[o]], fs_double_nf(det_err[o]).c_str());
+    }
+    const bool good = !ferror(f);
+    fclose(f);
+    return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
+}
+
 int aar_detections_write(const char *path, const aar_dataset *d) {
     if (!path || !d) return set_error(AAR_ERR_INVALID, "aar_detections_write: null argument");
     FILE *f = fopen(path, "wb");

@@ -384,6 +384,45 @@ int aar_problem_covariance(aar_problem *, const double *x_full, double *entity_c
  * created from `d` (its optimize flags); frame_cov (may be NULL) adds the object poses.  Host code. */
 int aar_covariance_write_yaml(const char *path, const aar_dataset *d, const double *entity_diag, const double *frame_cov, double sigma2);
 
+/* Residual report and outlier rejection (no counterpart in the reference).  At x_full, for every detection d (one
+ * marker seen by one camera in one frame): e_d = sqrt((sum over its 4 corners of rx^2 + ry^2) / 4) in pixels, summed in fp64 in corner
+ * order, UNWEIGHTED (Huber is ignored), with the corner residuals of the problem's residual mode (the rows aar_eval_residuals gives
+ * without Huber).  median = the exact lower median of e_d over all ranks (element floor((n-1)/2) of the ascending order), max = the
+ * exact maximum; a non-finite e_d sorts above every finite one.  The rule's threshold t = max(min_px, k_median * median) in fp64;
+ * k_median <= 0: t = min_px; both <= 0 or no rule: t = +inf.  A detection is kept iff e_d <= t (so a non-finite e_d never is when a
+ * rule is given).  Per camera, marker and frame four doubles {detections, sum r^2 over its corners, max e_d, rejected}; an entity
+ * without detections gets {0, 0, 0, 0}.  Every output is the same bits from call to call.  With a communicator every rank takes part;
+ * median, max, threshold, the keep flags and every count are bit-identical to one GPU, the camera and marker statistics are the same on
+ * every rank (and agree with one GPU to rounding).  Leaves the problem as aar_eval_damped_step does (no LM state).
+ *   rule:         may be NULL (nothing is rejected but a NaN e_d)
+ *   det_err:      [aar_problem_local_obs] e_d of this rank's detections in reference order; may be NULL
+ *   keep:         [aar_problem_local_obs] 1 = kept; may be NULL
+ *   cam_stats:    [num_cams][4]; marker_stats: [num_markers][4]; may be NULL
+ *   frame_stats:  [num_frames][4]: this rank's frames (the others untouched); may be NULL
+ *   report:       caller sets struct_size = sizeof(aar_residual_report); required */
+typedef struct aar_outlier_rule {
+    uint32_t struct_size;                     /* sizeof(aar_outlier_rule)                                                */
+    double k_median;                          /* t = max(min_px, k_median * median); <= 0: t = min_px                     */
+    double min_px;
+} aar_outlier_rule;
+typedef struct aar_residual_report {
+    uint32_t struct_size;
+    int64_t num_detections, num_rejected, num_nonfinite;   /* all ranks                                                      */
+    double sum_sq, rmse;                      /* unweighted; rmse = sqrt(sum_sq / (4 num_detections)) per corner coordinate pair */
+    double median, max, threshold;            /* threshold = +inf without a rule                                          */
+    int32_t cams_emptied, markers_emptied, frames_emptied;   /* had detections, keep none (frames: all ranks)             */
+} aar_residual_report;
+int aar_problem_residual_report(aar_problem *, const double *x_full, const aar_outlier_rule *rule, double *det_err, uint8_t *keep,
+                                double *cam_stats, double *marker_stats, double *frame_stats, aar_residual_report *report);
+/* A copy of `d` that keeps the observations with keep[o] != 0, in their order (still frame-nondecreasing).  Every id, camera matrix,
+ * x_full, x_truth and the optimize flags are kept; a frame, camera or marker left without detections stays.  Host code. */
+int aar_dataset_select_observations(const aar_dataset *d, const uint8_t *keep, aar_dataset **out);
+/* YAML (the cv::FileStorage dialect of aar_solution_write_yaml) of a residual report: the report's scalars, per camera id and marker id
+ * {detections, rmse, max, rejected} from cam_stats / marker_stats, and the rejected detections as (frame id, camera id, marker id, error)
+ * (det_err / keep of a single-GPU report of a problem created from d; both NULL: no list).  Host code. */
+int aar_residual_report_write_yaml(const char *path, const aar_dataset *d, const double *cam_stats, const double *marker_stats,
+                                   const double *det_err, const uint8_t *keep, const aar_residual_report *report);
+
 /* ucoslam::SparseLevMarq<T>::Params (libs/sparselevmarq.h:30-50) with the values
  * MultiCamMapper::init installs (libs/multicam_mapper.cpp:326-330). */
 typedef struct aar_lm_params {
