@@ -37,8 +37,11 @@ SYMBOLS = [
     "aar_solver_default_options", "aar_problem_create_ex", "aar_problem_get_solver_stats", "aar_problem_set_test_hook",
     "aar_problem_covariance", "aar_covariance_write_yaml",
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
+    "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
 ]
-NUM_KERNELS = 17
+NUM_KERNELS = 18
+PRIOR_CAMERA, PRIOR_MARKER = 0, 1
+PRIOR_KINDS = {"camera": PRIOR_CAMERA, "marker": PRIOR_MARKER}
 SOLVER_DIRECT, SOLVER_PCG, SOLVER_SPCG, SOLVER_AUTO = 0, 1, 2, 3
 TEST_HOOK_SPCG_DROP = 1
 ENV_SOLVER, ENV_DETERMINISTIC, ENV_PCG_ETA, ENV_PCG_MAX_IT = 1, 2, 4, 8
@@ -113,6 +116,64 @@ class CResidualReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_detections", C.c_int64), ("num_rejected", C.c_int64), ("num_nonfinite", C.c_int64),
                 ("sum_sq", C.c_double), ("rmse", C.c_double), ("median", C.c_double), ("max", C.c_double), ("threshold", C.c_double),
                 ("cams_emptied", C.c_int32), ("markers_emptied", C.c_int32), ("frames_emptied", C.c_int32)]
+
+
+class CPosePrior(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("x6", C.c_double * 6), ("info", C.c_double * 36)]
+
+
+class CConstraints(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_fixed_cams", C.c_int32), ("fixed_cams", C.POINTER(C.c_int32)),
+                ("n_fixed_markers", C.c_int32), ("fixed_markers", C.POINTER(C.c_int32)),
+                ("n_priors", C.c_int32), ("priors", C.POINTER(CPosePrior))]
+
+
+class Constraints:
+    """aar_problem_constraints built from Python values (kept alive with the struct).  fixed_cams / fixed_markers: indices; priors: a list of
+    (kind, index, x6, info) with kind "camera" | "marker" (or PRIOR_CAMERA / PRIOR_MARKER), x6 the 6-vector (rvec, t), info the 6x6 information matrix."""
+
+    def __init__(self, fixed_cams=None, fixed_markers=None, priors=None):
+        self._fc = np.ascontiguousarray(list(fixed_cams or []), dtype=np.int32)
+        self._fm = np.ascontiguousarray(list(fixed_markers or []), dtype=np.int32)
+        pr = list(priors or [])
+        self._pr = (CPosePrior * max(len(pr), 1))()
+        for i, (kind, index, x6, info) in enumerate(pr):
+            q = self._pr[i]
+            q.kind = PRIOR_KINDS[kind] if isinstance(kind, str) else int(kind)
+            q.index = int(index)
+            x6 = np.asarray(x6, dtype=np.float64).reshape(6)
+            info = np.asarray(info, dtype=np.float64).reshape(36)
+            for k in range(6):
+                q.x6[k] = float(x6[k])
+            for k in range(36):
+                q.info[k] = float(info[k])
+        c = CConstraints()
+        c.struct_size = C.sizeof(CConstraints)
+        c.n_fixed_cams = len(self._fc)
+        c.fixed_cams = self._fc.ctypes.data_as(C.POINTER(C.c_int32)) if len(self._fc) else None
+        c.n_fixed_markers = len(self._fm)
+        c.fixed_markers = self._fm.ctypes.data_as(C.POINTER(C.c_int32)) if len(self._fm) else None
+        c.n_priors = len(pr)
+        c.priors = C.cast(self._pr, C.POINTER(CPosePrior)) if pr else None
+        self.c = c
+        self.n_priors = len(pr)
+
+    def empty(self):
+        return self.c.n_fixed_cams == 0 and self.c.n_fixed_markers == 0 and self.c.n_priors == 0
+
+
+def constraints_validate(ds, fixed_cams=None, fixed_markers=None, priors=None, optimize=None, struct_size=None):
+    """aar_problem_constraints_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  struct_size overrides
+    the struct's own size (versioning tests)."""
+    cds = ds.as_c()
+    d = CProblemDesc()
+    lib().aar_problem_desc_from_dataset(C.byref(cds), C.byref(d))
+    if optimize is not None:
+        d.optimize_cam_poses, d.optimize_marker_poses, d.optimize_object_poses = [int(b) for b in optimize]
+    k = Constraints(fixed_cams, fixed_markers, priors)
+    if struct_size is not None:
+        k.c.struct_size = int(struct_size)
+    _check(lib().aar_problem_constraints_validate(C.byref(d), C.byref(k.c)))
 
 
 class CLmParams(C.Structure):
@@ -200,6 +261,11 @@ def lib():
     L.aar_problem_desc_from_dataset.restype = None
     L.aar_problem_create.argtypes = [C.POINTER(CProblemDesc), C.POINTER(C.c_void_p)]
     L.aar_problem_create_ex.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CSolverOptions), C.POINTER(C.c_void_p)]
+    L.aar_problem_constraints_validate.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CConstraints)]
+    L.aar_problem_create_constrained.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CSolverOptions), C.POINTER(CConstraints), C.POINTER(C.c_void_p)]
+    L.aar_problem_num_priors.argtypes = [C.c_void_p]
+    L.aar_problem_num_priors.restype = C.c_int32
+    L.aar_problem_eval_priors.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.aar_solver_default_options.argtypes = [C.POINTER(CSolverOptions)]
     L.aar_solver_default_options.restype = None
     L.aar_problem_get_solver_stats.argtypes = [C.c_void_p, C.POINTER(CSolverStats)]
@@ -697,11 +763,14 @@ class Problem:
     """aar_problem: the bundle-adjustment problem resident on one GPU."""
 
     def __init__(self, ds, residual_mode=RES_F32, device=0, comm=None, optimize=None, with_huber=False, intrinsics=False,
-                 solver=None, deterministic=None, pcg_eta=None, pcg_max_it=None, pcg_eta_loose=None, pcg_eta_switch=None, pcg_abs_tol=None):
+                 solver=None, deterministic=None, pcg_eta=None, pcg_max_it=None, pcg_eta_loose=None, pcg_eta_switch=None, pcg_abs_tol=None,
+                 fixed_cams=None, fixed_markers=None, priors=None, constrained=False):
         """intrinsics=True: Config::optimize_cam_intrinsics -- every vector ends with 9 per camera (x_with_intrinsics builds one)
         solver ("direct" | "spcg" | "pcg" | "auto"), deterministic, pcg_eta, pcg_max_it, pcg_eta_loose, pcg_eta_switch: aar_solver_options
         (None = the library's default: solver AUTO -- direct for one tile of unknowns, SPCG wherever it fits, PCG for many entities per frame x many frames -- with
-        one pose-grade forcing term and an absolute tolerance; a forcing SEQUENCE only when pcg_eta_loose is given)"""
+        one pose-grade forcing term and an absolute tolerance; a forcing SEQUENCE only when pcg_eta_loose is given)
+        fixed_cams, fixed_markers (indices), priors (list of (kind, index, x6, info)): aar_problem_constraints, created through
+        aar_problem_create_constrained (also taken, with empty constraints, when constrained=True)"""
         self.ds = ds
         self._cds = ds.as_c()
         d = CProblemDesc()
@@ -716,7 +785,10 @@ class Problem:
         self.optimize = (bool(d.optimize_cam_poses), bool(d.optimize_marker_poses), bool(d.optimize_object_poses))
         self.intrinsics = bool(intrinsics)
         self.handle = C.c_void_p()
-        if all(v is None for v in (solver, deterministic, pcg_eta, pcg_max_it, pcg_eta_loose, pcg_eta_switch, pcg_abs_tol)):
+        self._cons = Constraints(fixed_cams, fixed_markers, priors)
+        self.n_priors = self._cons.n_priors
+        if all(v is None for v in (solver, deterministic, pcg_eta, pcg_max_it, pcg_eta_loose, pcg_eta_switch, pcg_abs_tol)) and \
+                self._cons.empty() and not constrained:
             _check(lib().aar_problem_create(C.byref(d), C.byref(self.handle)))
         else:
             so = CSolverOptions()
@@ -735,7 +807,10 @@ class Problem:
                 so.pcg_eta_switch = float(pcg_eta_switch)
             if pcg_abs_tol is not None:
                 so.pcg_abs_tol = float(pcg_abs_tol)
-            _check(lib().aar_problem_create_ex(C.byref(d), C.byref(so), C.byref(self.handle)))
+            if self._cons.empty() and not constrained:
+                _check(lib().aar_problem_create_ex(C.byref(d), C.byref(so), C.byref(self.handle)))
+            else:
+                _check(lib().aar_problem_create_constrained(C.byref(d), C.byref(so), C.byref(self._cons.c), C.byref(self.handle)))
         self.full_len = lib().aar_problem_full_len(self.handle)
         self.num_vars = lib().aar_problem_num_vars(self.handle)
         self.local_obs = lib().aar_problem_local_obs(self.handle)
@@ -778,6 +853,14 @@ class Problem:
         ss = C.c_double()
         _check(lib().aar_eval_normal_equations(self.handle, _dptr(x), _dptr(H), _dptr(B), C.byref(ss)))
         return H, B, ss.value
+
+    def eval_priors(self, x_full):
+        """aar_problem_eval_priors: (e [n_priors][6], summed cost e^T L e) at x_full"""
+        x = self._x(x_full)
+        e = np.zeros((max(self.n_priors, 1), 6))
+        cost = C.c_double()
+        _check(lib().aar_problem_eval_priors(self.handle, _dptr(x), _dptr(e), C.byref(cost)))
+        return e[:self.n_priors], cost.value
 
     def eval_damped_step(self, x_full, mu):
         x = self._x(x_full)

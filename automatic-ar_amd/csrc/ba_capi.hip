@@ -202,6 +202,8 @@ struct aar_problem {
     double mu_seed = 0;
     // host copies of the index structure (normal-equation assembly for tests)
     std::vector<int32_t> h_fslot_start, h_fslot_ent;
+    std::vector<int32_t> h_ent_fixed;   // [A] the device's ent_fixed
+    std::vector<aar_pose_prior> priors; // the caller's priors (aar_problem_constraints), in their order
     // LM state (SparseLevMarq members, libs/sparselevmarq.h:129-136)
     aar_lm_params prm;
     int cur = 0;                       // pose buffer / block set of curr_z
@@ -572,12 +574,13 @@ int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool s
     {
         StageTimer t(pb, &pb->times.jacobian_normal_eq);
         if (pb->merge_passes && launch_passAB(P, which, mu_pred, zero_blk, pb->stream)) {
+            launch_prior(P, which, true, pb->stream);   // (priors: after pass B, before anything reads S)
             if (spec_schur) launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
-            pb->launches += spec_schur ? 2 : 1;
+            pb->launches += (spec_schur ? 2 : 1) + (P.n_prior ? 1 : 0);
             return check_async("normal-equation kernels");
         }
         launch_passA(P, which, mu_pred, zero_blk, pb->stream);
-        if (spec_schur && pb->overlap && !pb->profiling && !pb->stage_timers) {
+        if (spec_schur && pb->overlap && !pb->profiling && !pb->stage_timers && P.n_prior == 0) {
             HIP_TRY(hipEventRecord(pb->ev_fork, pb->stream));
             HIP_TRY(hipStreamWaitEvent(pb->stream2, pb->ev_fork, 0));
             launch_passB(P, which, pb->stream2);
@@ -586,11 +589,12 @@ int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool s
             HIP_TRY(hipStreamWaitEvent(pb->stream, pb->ev_join, 0));
         } else {
             launch_passB(P, which, pb->stream);
+            launch_prior(P, which, true, pb->stream);
             if (spec_schur) launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
         }
     }
     if (spec_schur) panels_now(pb, which, mu_pred);
-    pb->launches += spec_schur ? 3 : 2;
+    pb->launches += (spec_schur ? 3 : 2) + (P.n_prior ? 1 : 0);
     return check_async("normal-equation kernels");
 }
 
@@ -737,7 +741,8 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
             int rc = zero_block_set(pb, cur);
             if (rc) return rc;
             launch_passB(P, cur, pb->stream);
-            pb->launches += 1;
+            launch_prior(P, cur, true, pb->stream);
+            pb->launches += P.n_prior ? 2 : 1;
             pb->s_reduced = false;
         } else if (pb->schur_mu >= 0) {
             // the speculative Schur complement was taken with another damping than the step now needs (gain < 0.94): take it
@@ -784,7 +789,7 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
         if (rc) return rc;
         pb->trial_points++;
     } else {
-        HIP_TRY(hipMemsetAsync(P.err_part, 0, sizeof(double) * (size_t)std::max(P.F, 1), pb->stream));
+        HIP_TRY(hipMemsetAsync(P.err_part, 0, sizeof(double) * (size_t)std::max(n_err_terms(P), 1), pb->stream));
     }
     // The scalars go to the host BEFORE the speculative Schur complement of the trial point is queued: the host takes its
     // accept / reject decision and queues the next factorisation while that kernel runs, instead of after it.
@@ -792,24 +797,24 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
     int rc = AAR_OK;
     bool rode = false;
     if (P.use_pcg) {   // nothing is eliminated ahead of the next step in this mode: only the step's scalars travel
-        if ((rc = launch_scalars(pb, P.F))) return rc;
+        if ((rc = launch_scalars(pb, n_err_terms(P)))) return rc;
     } else if (evaluate_trial && !pb->comm) {
         StageTimer t(pb, &pb->times.schur);
-        rode = launch_schur(P, tr, 1.0, pb->stream, pb->seq + 1, P.F, nullptr, panels_ok(pb, tr, mu * 0.33));
+        rode = launch_schur(P, tr, 1.0, pb->stream, pb->seq + 1, n_err_terms(P), nullptr, panels_ok(pb, tr, mu * 0.33));
         panels_now(pb, tr, mu * 0.33);
         pb->launches += 1;
         if (rode) pb->seq++;
-        else if ((rc = launch_scalars(pb, P.F))) return rc;   // (nothing rode: a rank without frames launches no Schur kernel)
+        else if ((rc = launch_scalars(pb, n_err_terms(P)))) return rc;   // (nothing rode: a rank without frames launches no Schur kernel)
     } else if (evaluate_trial && pb->fused_comm) {
         // Multi-GPU: this rank's scalars ride in the speculative Schur launch as on one GPU, but into the 8 doubles behind
         // g0 of the trial's block set, and ONE all-reduce then carries the step's scalars AND the next step's S | rhs | g0:
         // an accepted step with the predicted damping (the usual case) costs one collective, not two.
         {
             StageTimer t(pb, &pb->times.schur);
-            rode = launch_schur(P, tr, 1.0, pb->stream, 0, P.F, P.blk[tr].tail, panels_ok(pb, tr, mu * 0.33));
+            rode = launch_schur(P, tr, 1.0, pb->stream, 0, n_err_terms(P), P.blk[tr].tail, panels_ok(pb, tr, mu * 0.33));
             panels_now(pb, tr, mu * 0.33);
             pb->launches += 1;
-            if (!rode) { launch_reduce_scalars(P, P.F, false, 0ull, pb->stream, P.blk[tr].tail); pb->launches += 1; }
+            if (!rode) { launch_reduce_scalars(P, n_err_terms(P), false, 0ull, pb->stream, P.blk[tr].tail); pb->launches += 1; }
         }
         pb->seq++;
         {
@@ -833,7 +838,7 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
             pb->launches += 3 * P.nT;
         }
     } else {
-        if ((rc = launch_scalars(pb, P.F))) return rc;
+        if ((rc = launch_scalars(pb, n_err_terms(P)))) return rc;
         if (evaluate_trial) {
             StageTimer t(pb, &pb->times.schur);
             launch_schur(P, tr, 1.0, pb->stream, 0, 0, nullptr, panels_ok(pb, tr, mu * 0.33));
@@ -1091,6 +1096,101 @@ void aar_solver_default_options(aar_solver_options *o) {
 
 int aar_problem_create(const aar_problem_desc *d, aar_problem **out) { return aar_problem_create_ex(d, nullptr, out); }
 
+// ---- constraints ----
+static int problem_create(const aar_problem_desc *d, const aar_solver_options *opts, const aar_problem_constraints *cons, aar_problem **out);
+namespace {
+// the caller's struct at its own size; fields beyond it count as empty
+aar_problem_constraints constraints_of(const aar_problem_constraints *c) {
+    aar_problem_constraints k;
+    memset(&k, 0, sizeof k);
+    if (c) memcpy(&k, c, std::min<size_t>(c->struct_size, sizeof k));
+    k.struct_size = (uint32_t)sizeof k;
+    return k;
+}
+bool constraints_empty(const aar_problem_constraints &k) { return k.n_fixed_cams == 0 && k.n_fixed_markers == 0 && k.n_priors == 0; }
+// symmetric positive semi-definite: LDL^T without pivoting, a negative pivot or a zero pivot over a non-zero column fails
+bool info_psd(const double *I) {
+    double scale = 0;
+    for (int i = 0; i < 36; i++) scale = std::max(scale, std::fabs(I[i]));
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < i; j++)
+            if (std::fabs(I[6 * i + j] - I[6 * j + i]) > 1e-12 * scale) return false;
+    if (scale == 0) return true;
+    const double tol = 1e-13 * scale;
+    double Lm[36] = {0}, D[6];
+    for (int k = 0; k < 6; k++) {
+        double d = I[6 * k + k];
+        for (int j = 0; j < k; j++) d -= Lm[6 * k + j] * Lm[6 * k + j] * D[j];
+        if (d < -tol) return false;
+        for (int i = k + 1; i < 6; i++) {
+            double v = I[6 * i + k];
+            for (int j = 0; j < k; j++) v -= Lm[6 * i + j] * Lm[6 * k + j] * D[j];
+            if (d <= tol) {
+                if (std::fabs(v) > std::sqrt(tol * scale)) return false;
+                Lm[6 * i + k] = 0;
+            } else {
+                Lm[6 * i + k] = v / d;
+            }
+        }
+        D[k] = d <= tol ? 0.0 : d;
+    }
+    return true;
+}
+}  // namespace
+
+int aar_problem_constraints_validate(const aar_problem_desc *d, const aar_problem_constraints *cons) {
+    if (!d) return set_error(AAR_ERR_INVALID, "aar_problem_constraints_validate: null problem description");
+    if (!cons) return AAR_OK;
+    if (cons->struct_size < sizeof(uint32_t) + sizeof(int32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_constraints.struct_size is not set");
+    const aar_problem_constraints k = constraints_of(cons);
+    const int C = d->num_cams, M = d->num_markers;
+    if (k.n_fixed_cams < 0 || k.n_fixed_markers < 0 || k.n_priors < 0) return set_error(AAR_ERR_INVALID, "aar_problem_constraints: negative count");
+    if ((k.n_fixed_cams && !k.fixed_cams) || (k.n_fixed_markers && !k.fixed_markers) || (k.n_priors && !k.priors))
+        return set_error(AAR_ERR_INVALID, "aar_problem_constraints: null array with a non-zero count");
+    std::vector<uint8_t> fixed((size_t)std::max(C, 0) + std::max(M, 0), 0);
+    for (int c = 0; c < C; c++) fixed[c] = (c == d->root_cam || !d->optimize_cam_poses) ? 1 : 0;
+    for (int m = 0; m < M; m++) fixed[(size_t)C + m] = (m == d->root_marker || !d->optimize_marker_poses) ? 1 : 0;
+    for (int i = 0; i < k.n_fixed_cams; i++) {
+        const int c = k.fixed_cams[i];
+        if (c < 0 || c >= C) return set_error(AAR_ERR_INVALID, "fixed_cams[%d] = %d: camera index out of range [0, %d)", i, c, C);
+        fixed[c] = 1;
+    }
+    for (int i = 0; i < k.n_fixed_markers; i++) {
+        const int m = k.fixed_markers[i];
+        if (m < 0 || m >= M) return set_error(AAR_ERR_INVALID, "fixed_markers[%d] = %d: marker index out of range [0, %d)", i, m, M);
+        fixed[(size_t)C + m] = 1;
+    }
+    std::vector<int32_t> owner(fixed.size(), -1);
+    for (int p = 0; p < k.n_priors; p++) {
+        const aar_pose_prior &q = k.priors[p];
+        const char *what = q.kind == AAR_PRIOR_CAMERA ? "camera" : "marker";
+        if (q.kind != AAR_PRIOR_CAMERA && q.kind != AAR_PRIOR_MARKER) return set_error(AAR_ERR_INVALID, "priors[%d]: kind %d is not AAR_PRIOR_CAMERA or AAR_PRIOR_MARKER", p, q.kind);
+        const int lim = q.kind == AAR_PRIOR_CAMERA ? C : M;
+        if (q.index < 0 || q.index >= lim) return set_error(AAR_ERR_INVALID, "priors[%d]: %s index %d out of range [0, %d)", p, what, q.index, lim);
+        const size_t e = q.kind == AAR_PRIOR_CAMERA ? (size_t)q.index : (size_t)C + q.index;
+        if (owner[e] >= 0) return set_error(AAR_ERR_INVALID, "priors[%d]: %s index %d already has a prior (priors[%d])", p, what, q.index, owner[e]);
+        owner[e] = p;
+        if (fixed[e]) return set_error(AAR_ERR_INVALID, "priors[%d]: %s index %d is fixed (root, non-optimised group or fixed index)", p, what, q.index);
+        for (int i = 0; i < 6; i++)
+            if (!std::isfinite(q.x6[i])) return set_error(AAR_ERR_INVALID, "priors[%d]: x6[%d] is not finite", p, i);
+        for (int i = 0; i < 36; i++)
+            if (!std::isfinite(q.info[i])) return set_error(AAR_ERR_INVALID, "priors[%d]: info[%d] is not finite", p, i);
+        if (!info_psd(q.info)) return set_error(AAR_ERR_INVALID, "priors[%d]: the information matrix is not symmetric positive semi-definite (its Cholesky fails)", p);
+    }
+    return AAR_OK;
+}
+
+int aar_problem_create_constrained(const aar_problem_desc *d, const aar_solver_options *opts, const aar_problem_constraints *cons, aar_problem **out) {
+    if (!d || !out) return set_error(AAR_ERR_INVALID, "aar_problem_create_constrained: null argument");
+    int rc = aar_problem_constraints_validate(d, cons);
+    if (rc) return rc;
+    if (!cons || constraints_empty(constraints_of(cons))) return aar_problem_create_ex(d, opts, out);
+    const aar_problem_constraints k = constraints_of(cons);
+    return problem_create(d, opts, &k, out);
+}
+
+int32_t aar_problem_num_priors(const aar_problem *pb) { return pb ? pb->P.n_prior : 0; }
+
 // AAR_ABORT_BACKTRACE=<file> (diagnostics): the native stack of whoever raises SIGABRT in this process (a runtime library giving up) is appended to the file before the default action
 static int abort_bt_fd = 2;
 static void abort_backtrace(int sig) {
@@ -1102,7 +1202,10 @@ static void abort_backtrace(int sig) {
     raise(sig);
 }
 
-int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *opts, aar_problem **out) {
+int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *opts, aar_problem **out) { return problem_create(d, opts, nullptr, out); }
+
+// cons: validated and not empty, or NULL
+static int problem_create(const aar_problem_desc *d, const aar_solver_options *opts, const aar_problem_constraints *cons, aar_problem **out) {
     { static bool once = false; if (!once && getenv("AAR_ABORT_BACKTRACE")) { once = true; const int fd = open(getenv("AAR_ABORT_BACKTRACE"), O_WRONLY | O_CREAT | O_APPEND, 0644); if (fd >= 0) abort_bt_fd = fd; signal(SIGABRT, abort_backtrace); } }
     if (!d || !out) return set_error(AAR_ERR_INVALID, "aar_problem_create: null argument");
     aar_solver_options so;
@@ -1211,6 +1314,13 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
     P.half_size = (double)((float)d->marker_size / 2.f);
     P.frames_fixed = L.of ? 0 : 1;
     const int A = P.A, F = P.F;
+    // entities the caller fixed that would be free otherwise
+    std::vector<int32_t> held(C + M, 0);
+    bool held_extra = false;
+    if (cons) {
+        for (int i = 0; i < cons->n_fixed_cams; i++) { const int c = cons->fixed_cams[i]; if (c != L.rc && L.oc) { held[c] = 1; held_extra = true; } }
+        for (int i = 0; i < cons->n_fixed_markers; i++) { const int m = cons->fixed_markers[i]; if (m != L.rm && L.om) { held[C + m] = 1; held_extra = true; } }
+    }
 
     int local_rc = AAR_OK;   // rank-local limits: decided collectively below
     // ---- ordering A (reference order) + per-frame slot lists ----
@@ -1287,6 +1397,9 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
         if (const char *t = getenv("AAR_SPCG_COARSE_FROM")) P.spcg_coarse_from = atoi(t);
         if (const char *t = getenv("AAR_PCG_COARSE")) P.pcg_coarse = atoi(t) != 0;
         if (const char *t = getenv("AAR_PCG_COARSE_FROM")) P.pcg_coarse_from = atoi(t);
+        // both coarse spaces are built for groups whose only fixed entity is the root (its slot carries the group's rigid motion): with entities
+        // fixed by the caller they are off
+        if (held_extra) { P.spcg_coarse = 0; P.pcg_coarse = 0; }
         // the coarse operator's pass costs like ~1.5 CG iterations and a kept operator ~0.1 - 0.7 more iterations per solve: keeping it pays on long sequences only
         // (profiles/r06_attempts.txt section 3: +3.7 % at 160 entities x 4 000 frames, +1.4 % at config 5, -1 .. -3 % on 500-frame problems)
         P.pcg_e_every = P.total_slots >= 300000 ? 3 : 1;
@@ -1596,6 +1709,7 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
     std::vector<int32_t> ent_fixed(A, 0);
     for (int c = 0; c < C; c++) ent_fixed[c] = (c == L.rc || !L.oc) ? 1 : 0;
     for (int m = 0; m < M; m++) ent_fixed[C + m] = (m == L.rm || !L.om) ? 1 : 0;
+    for (int e = 0; e < C + M; e++) ent_fixed[e] |= held[e];
     // (intrinsics entities are free, root camera included: fill_io_vec_cam_intrinsics covers ALL cameras, libs/multicam_mapper.cpp:488-498;
     //  their two idle parameters have zero rows and columns and get mu on the diagonal, like the reference's five distortion columns)
     std::vector<double> Kh(d->cam_mats, d->cam_mats + 9 * (size_t)C);
@@ -1684,6 +1798,22 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
     AL(Lp, (size_t)P.nT * P.n_pad * CHOL_NB); AL(zf, P.n_pad);
     AL(err_part, std::max<size_t>((size_t)F, (size_t)((N + 255) / 256)) + 1);
     AL(lin_part, 2 * (size_t)(F + 1)); AL(scal, 8); AL(flags, 4);
+    if (cons && cons->n_priors > 0) {
+        const int np_ = cons->n_priors;
+        std::vector<int32_t> pent(np_);
+        std::vector<double> pdat((size_t)np_ * PRIOR_DAT);
+        for (int p = 0; p < np_; p++) {
+            const aar_pose_prior &q = cons->priors[p];
+            pent[p] = q.kind == AAR_PRIOR_CAMERA ? q.index : C + q.index;
+            memcpy(&pdat[(size_t)p * PRIOR_DAT], q.x6, 6 * sizeof(double));
+            memcpy(&pdat[(size_t)p * PRIOR_DAT + 6], q.info, 36 * sizeof(double));
+        }
+        if ((rc = dev_upload(pb, &P.prior_ent, pent)) || (rc = dev_upload(pb, &P.prior_dat, pdat))) return fail(rc);
+        AL(prior_out, (size_t)np_ * 8 + 1);
+        P.n_prior = np_;
+        P.prior_rank0 = rank == 0 ? 1 : 0;
+        pb->priors.assign(cons->priors, cons->priors + np_);
+    }
 #undef AL
     if ((rc = dev_alloc(pb, &pb->d_diag, P.n_pad))) return fail(rc);
     if (pb->comm && (rc = dev_alloc(pb, &pb->d_frames_all, 6 * (size_t)std::max(Fg, 1)))) return fail(rc);
@@ -1704,6 +1834,7 @@ int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *o
     }
     pb->h_fslot_start = fslot_start;
     pb->h_fslot_ent = fslot_ent;
+    pb->h_ent_fixed = ent_fixed;
     *out = pb;
     return AAR_OK;
 }
@@ -1777,14 +1908,15 @@ int aar_eval_normal_equations(aar_problem *pb, const double *x_full, double *JtJ
     if (rc) return rc;
     const int A = P.A, F = P.F, np = P.n_pad;
     const DeviceProblem::Blocks &bk = P.blk[pb->cur];
-    std::vector<double> U0((size_t)np * np), g0(np), V((size_t)F * 36), gf((size_t)F * 6), W((size_t)P.total_slots * 36), ep(F);
+    std::vector<double> U0((size_t)np * np), g0(np), V((size_t)F * 36), gf((size_t)F * 6), W((size_t)P.total_slots * 36), ep(n_err_terms(P));
     // (copies through the library's page-locked staging, hostcopy.h)
     HIP_TRY(hipStreamSynchronize(pb->stream));
     if ((rc = copy_d2h(pb, U0.data(), bk.S, U0.size() * sizeof(double))) || (rc = copy_d2h(pb, g0.data(), bk.g0, g0.size() * sizeof(double)))) return rc;
     if (F) {
         if ((rc = copy_d2h(pb, V.data(), bk.V, V.size() * sizeof(double))) || (rc = copy_d2h(pb, gf.data(), bk.gf, gf.size() * sizeof(double))) ||
-            (rc = copy_d2h(pb, W.data(), bk.W, W.size() * sizeof(double))) || (rc = copy_d2h(pb, ep.data(), P.err_part, ep.size() * sizeof(double)))) return rc;
+            (rc = copy_d2h(pb, W.data(), bk.W, W.size() * sizeof(double)))) return rc;
     }
+    if (!ep.empty() && (rc = copy_d2h(pb, ep.data(), P.err_part, ep.size() * sizeof(double)))) return rc;   // (the frames' sums, then the priors' cost)
     pb->lm_ready = false;
     // reference column of each device parameter (or -1): roots, non-optimised groups and the two idle parameters of an
     // intrinsics entity have none
@@ -1837,9 +1969,35 @@ int aar_eval_normal_equations(aar_problem *pb, const double *x_full, double *JtJ
     }
     if (sum_sq) {
         double s = 0;
-        for (int f = 0; f < F; f++) s += ep[f];
+        for (double v : ep) s += v;
         *sum_sq = s;
     }
+    return AAR_OK;
+}
+
+int aar_problem_eval_priors(aar_problem *pb, const double *x_full, double *e_out, double *cost) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_problem_eval_priors: null argument");
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    if (P.n_prior == 0) {
+        if (cost) *cost = 0.0;
+        return AAR_OK;
+    }
+    int rc = upload_z(pb, x_full, pb->cur);
+    if (rc) return rc;
+    // the entity rows of `cur` are rewritten: whatever the LM state was, it is gone
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    launch_unpack(P, pb->cur, pb->stream);
+    launch_prior(P, pb->cur, /*add=*/false, pb->stream);
+    pb->launches += 2;
+    if ((rc = check_async("prior kernels"))) return rc;
+    HIP_TRY(hipStreamSynchronize(pb->stream));
+    std::vector<double> h((size_t)P.n_prior * 8 + 1);
+    if ((rc = copy_d2h(pb, h.data(), P.prior_out, h.size() * sizeof(double)))) return rc;
+    if (e_out)
+        for (int p = 0; p < P.n_prior; p++) memcpy(e_out + 6 * (size_t)p, &h[8 * (size_t)p], 6 * sizeof(double));
+    if (cost) *cost = h[(size_t)P.n_prior * 8];
     return AAR_OK;
 }
 
@@ -1900,7 +2058,7 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
     // Schur complement at mu = 0 and this rank's sum r^2 behind g0: they travel in the DIRECT chain's all-reduce
     launch_frame_inv(P, cur, 0.0, pb->stream);
     launch_schur(P, cur, 1.0, pb->stream, 0, 0, nullptr, false);
-    launch_reduce_scalars(P, P.F, false, 0ull, pb->stream, P.blk[cur].tail);
+    launch_reduce_scalars(P, n_err_terms(P), false, 0ull, pb->stream, P.blk[cur].tail);
     pb->launches += 3;
     if (pb->comm && (rc = allreduce_system(pb, cur, 1))) return rc;
     // workspace: staged system with its factor pieces | L | X = L^-1 | S^-1 | 1/D | frame blocks; masks and flags
@@ -1929,7 +2087,8 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
     for (int a = 0; a < P.A; a++) {
         bool seen = false;
         for (int i = 0; i < 6; i++) seen |= par_col(a, i) >= 0 && diag[6 * a + i] != 0.0;
-        for (int i = 0; i < 6; i++) mask[6 * a + i] = (seen && par_col(a, i) >= 0) ? 0 : 1;
+        const bool held = a < L.C + L.M && pb->h_ent_fixed[a];   // (fixed by the caller: as a root)
+        for (int i = 0; i < 6; i++) mask[6 * a + i] = (seen && !held && par_col(a, i) >= 0) ? 0 : 1;
     }
     if ((rc = copy_h2d(pb, rowmask, mask.data(), np * sizeof(int32_t)))) return rc;
     // factor the staged system with the LM path's own chain: a copy of the problem description pointed at the workspace
@@ -2209,7 +2368,7 @@ int aar_lm_init(aar_problem *pb, const double *x_full, const aar_lm_params *prm)
     pb->huber_of_blocks = P.huber;
     pb->mu_seed_valid = false;
     // (single GPU: mu_0 rides to the host with the sum r^2: the first step() then needs no round trip of its own)
-    if ((rc = launch_scalars(pb, P.F, pb->comm ? -1 : 0))) return rc;
+    if ((rc = launch_scalars(pb, n_err_terms(P), pb->comm ? -1 : 0))) return rc;
     // Head start of the first step (single GPU, direct solver): its damping mu_0 = tau * max diag(J^T J) is on the device one kernel before the host
     // can read it, and the frame inverses and the Schur complement need nothing else -- they are queued HERE, with mu_0 read on the device, and
     // run while the record travels to the host and the host queues the factorisation.  (tau changed between init and step: the damped try finds
@@ -2499,7 +2658,7 @@ int aar_get_kernel_times(aar_problem *pb, double seconds[AAR_NUM_KERNELS], int64
 const char *aar_kernel_name(int kid) {
     static const char *names[KID_COUNT] = {"k_unpack", "k_residual", "k_passA", "k_passB", "k_maxdiag", "k_frame_inv", "k_schur",
                                            "k_ldl_diag", "k_ldl_trsm", "k_ldl_update", "k_ldl_backsolve", "k_backsub",
-                                           "k_reduce_scalars", "k_ldl_panel", "k_pcg", "k_spcg", "k_spcg_pre"};
+                                           "k_reduce_scalars", "k_ldl_panel", "k_pcg", "k_spcg", "k_spcg_pre", "k_prior"};
     return (kid >= 0 && kid < KID_COUNT) ? names[kid] : "?";
 }
 

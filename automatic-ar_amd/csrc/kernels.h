@@ -35,7 +35,7 @@ inline int spcg_stride(int n_pad) { return 8 * (n_pad / 6); }   // doubles per h
 
 // Kernel ids for the optional per-launch timing hooks (aar_get_kernel_times)
 enum KernelId { KID_UNPACK = 0, KID_RESIDUAL, KID_PASSA, KID_PASSB, KID_MAXDIAG, KID_FRAME_INV, KID_SCHUR, KID_LDL_DIAG,
-                KID_LDL_TRSM, KID_LDL_UPDATE, KID_LDL_BACKSOLVE, KID_BACKSUB, KID_REDUCE, KID_LDL_PANEL, KID_PCG, KID_SPCG, KID_SPCG_PRE, KID_COUNT };
+                KID_LDL_TRSM, KID_LDL_UPDATE, KID_LDL_BACKSOLVE, KID_BACKSUB, KID_REDUCE, KID_LDL_PANEL, KID_PCG, KID_SPCG, KID_SPCG_PRE, KID_PRIOR, KID_COUNT };
 
 struct LaunchHook {  // called around every kernel launch when profiling is on
     void (*pre)(void *ctx, int kid) = nullptr;
@@ -71,7 +71,7 @@ struct DeviceProblem {
     ObsIdx *b_idx = nullptr;          // ordering B = (camera, marker, frame)
     float *b_uv = nullptr;
     int32_t *chunk_start = nullptr;   // [n_chunks+1] into ordering B; a chunk never spans two (camera, marker) runs
-    int32_t *ent_fixed = nullptr;     // [A] 1 = root or non-optimised group
+    int32_t *ent_fixed = nullptr;     // [A] 1 = root, non-optimised group or fixed by the caller (aar_problem_constraints)
     int frames_fixed = 0;
     // Schur work list: item w handles pairs [sw_begin[w], sw_end[w]) of entity sw_ent[w]
     int32_t *sw_ent = nullptr, *sw_begin = nullptr, *sw_end = nullptr;
@@ -197,6 +197,11 @@ struct DeviceProblem {
     double *host_result = nullptr;        // device pointer to the mapped host record (10 x 8 bytes)
     int32_t *flags = nullptr;             // [4] device error flags (0: non-positive pivot)
     double *r_out = nullptr;              // optional [8N]
+    // pose priors (prior_kernels.hip): every rank holds them, only rank 0 (prior_rank0) adds them into the system
+    int n_prior = 0, prior_rank0 = 1;
+    int32_t *prior_ent = nullptr;         // [n_prior] shared entity
+    double *prior_dat = nullptr;          // [n_prior][PRIOR_DAT] x6 | information matrix
+    double *prior_out = nullptr;          // [n_prior][8] e | cost | 0, then the summed cost
     LaunchHook hook;
 };
 
@@ -271,6 +276,12 @@ void launch_reduce_scalars(const DeviceProblem &P, int n_err, bool fold_shared, 
 // scal / flags -> host record; flags_reduced: the flags are decoded from src[3] (every rank's flags, all-reduced) instead of P.flags
 void launch_publish(const DeviceProblem &P, unsigned long long publish_seq, hipStream_t st, const double *src = nullptr, bool flags_reduced = false);
 int residual_blocks(const DeviceProblem &P);   // entries of err_part written by launch_residual
+// pose priors at ent[which]: e and the costs into prior_out; add (and rank 0): J^T L J into the diagonal blocks of blk[which].S, -J^T L e into
+// its g0, the summed cost into err_part[F].  Runs after pass B is complete and before anything reads S (maximum diagonal, Schur complement)
+constexpr int PRIOR_DAT = 42;
+void launch_prior(const DeviceProblem &P, int which, bool add, hipStream_t st);
+// entries of err_part the step's error sums: the frames' and, with priors on this rank, their cost behind them
+inline int n_err_terms(const DeviceProblem &P) { return P.F + ((P.n_prior > 0 && P.prior_rank0) ? 1 : 0); }
 // track(): every frame's own 6-DoF LM, whole loop on the device; needs ent[which] rows of the shared entities (launch_unpack)
 void launch_track(const DeviceProblem &P, int which, int max_iters, double min_error, double min_step, double min_avg, double tau,
                   int32_t *iters_out, double *err_out, hipStream_t st);

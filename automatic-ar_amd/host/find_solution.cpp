@@ -23,16 +23,23 @@
 #include <vector>
 
 #include "multicam_mapper.h"
+#include "se3.h"
 
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
     cout << "                            (up to 3 rounds, until a round drops nothing); final.solution keeps the remaining detections" << endl;
     cout << "       -reject-min-px px    the floor of that threshold in pixels (default 0)" << endl;
+    cout << "       -fix-cams ids        hold these cameras exactly where the initial solution has them (comma-separated ids)" << endl;
+    cout << "       -fix-markers ids     the same for markers" << endl;
+    cout << "       -prior-solution f    pull every non-root camera and marker of the .solution file f toward its pose there (isotropic" << endl;
+    cout << "                            prior, information diag(1/sigma_rot^2 x3, 1/sigma_t^2 x3)); f must have the same root camera and marker ids" << endl;
+    cout << "       -prior-sigma-deg d   rotation sigma of those priors in degrees (default 1)" << endl;
+    cout << "       -prior-sigma-m m     translation sigma of those priors in metres (default 0.01)" << endl;
     cout << "       " << a0 << " --synth <config 1..5> <out_folder>   (write a synthetic data set in the reference's file formats)" << endl;
     return -1;
 }
@@ -64,6 +71,59 @@ static int synth(int cfg, const string &folder) {
          << " marker-observations=" << d->num_obs << endl;
     aar_dataset_free(d);
     return rc ? 1 : 0;
+}
+
+// comma-separated ids of -fix-cams / -fix-markers; false on anything that is not an integer list
+static bool parse_ids(const string &a, set<int> &out) {
+    size_t p = 0;
+    while (p <= a.size()) {
+        const size_t q = a.find(',', p);
+        const string tok = a.substr(p, q == string::npos ? string::npos : q - p);
+        char *end = nullptr;
+        const long v = strtol(tok.c_str(), &end, 10);
+        if (tok.empty() || *end != '\0') return false;
+        out.insert((int)v);
+        if (q == string::npos) break;
+        p = q + 1;
+    }
+    return true;
+}
+
+// -prior-solution: an isotropic prior on every non-root camera and marker of the file; its roots must be the problem's (the poses are relative to them)
+static int read_pose_priors(const string &path, const aar_dataset *d, double sigma_deg, double sigma_m, vector<aar::MultiCamMapper::PosePrior> &out) {
+    aar_dataset *p = nullptr;
+    if (aar_solution_read(path.c_str(), &p)) {
+        cerr << "cannot read the prior solution " << path << ": " << aar_last_error() << endl;
+        return 1;
+    }
+    std::unique_ptr<aar_dataset, void (*)(aar_dataset *)> hold(p, aar_dataset_free);
+    if (p->cam_ids[p->root_cam] != d->cam_ids[d->root_cam] || p->marker_ids[p->root_marker] != d->marker_ids[d->root_marker]) {
+        cerr << "the prior solution " << path << " has root camera " << p->cam_ids[p->root_cam] << " / marker " << p->marker_ids[p->root_marker]
+             << ", the problem " << d->cam_ids[d->root_cam] << " / " << d->marker_ids[d->root_marker] << endl;
+        return 1;
+    }
+    const double sr = sigma_deg * M_PI / 180.0;
+    aar::MultiCamMapper::Mat66 info{};
+    for (int i = 0; i < 6; i++) info[7 * i] = i < 3 ? 1.0 / (sr * sr) : 1.0 / (sigma_m * sigma_m);
+    auto add = [&](int kind, int id, const double *x6) {
+        const aar::Rigid r = aar::pose_to_rigid(x6);
+        aar::MultiCamMapper::PosePrior q;
+        q.kind = kind;
+        q.id = id;
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) q.T[4 * i + j] = r.R[3 * i + j];
+            q.T[4 * i + 3] = r.t[i];
+        }
+        q.T[15] = 1.0;
+        q.info = info;
+        out.push_back(q);
+    };
+    // x_full: (C-1) cameras | (M-1) markers, ascending index, roots skipped
+    for (int c = 0, k = 0; c < p->num_cams; c++)
+        if (c != p->root_cam) add(AAR_PRIOR_CAMERA, p->cam_ids[c], p->x_full + 6 * (k++));
+    for (int m = 0, k = 0; m < p->num_markers; m++)
+        if (m != p->root_marker) add(AAR_PRIOR_MARKER, p->marker_ids[m], p->x_full + 6 * (size_t)(p->num_cams - 1) + 6 * (k++));
+    return 0;
 }
 
 // -reject-outliers: report, drop, solve again from that solution -- until a round drops nothing, at most 3 rounds.  final.residuals.yaml
@@ -130,8 +190,13 @@ int main(int argc, char *argv[]) {
     double reject_k = 0.0, reject_min_px = 0.0;
     double threshold = 2.0;
     set<int> excluded_cams;
+    // nor these: -fix-cams / -fix-markers hold entities by id, -prior-solution pulls the cameras and markers toward a solution file's poses
+    set<int> fixed_cams, fixed_markers;
+    bool fix_cams = false, fix_markers = false;
+    string prior_path;
+    double prior_sigma_deg = 1.0, prior_sigma_m = 0.01;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -145,6 +210,24 @@ int main(int argc, char *argv[]) {
         else if (a == "-residuals") { residuals = true; arg_flag = NONE; }
         else if (a == "-reject-outliers") arg_flag = RejectK;
         else if (a == "-reject-min-px") arg_flag = RejectPx;
+        else if (a == "-fix-cams") arg_flag = FixCams;
+        else if (a == "-fix-markers") arg_flag = FixMarkers;
+        else if (a == "-prior-solution") arg_flag = PriorPath;
+        else if (a == "-prior-sigma-deg") arg_flag = PriorDeg;
+        else if (a == "-prior-sigma-m") arg_flag = PriorM;
+        else if (arg_flag == FixCams || arg_flag == FixMarkers) {
+            if (!parse_ids(a, arg_flag == FixCams ? fixed_cams : fixed_markers)) return print_usage(argv[0]);
+            (arg_flag == FixCams ? fix_cams : fix_markers) = true;
+            arg_flag = NONE;
+        }
+        else if (arg_flag == PriorPath) { prior_path = a; arg_flag = NONE; }
+        else if (arg_flag == PriorDeg || arg_flag == PriorM) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            (arg_flag == PriorDeg ? prior_sigma_deg : prior_sigma_m) = v;
+            arg_flag = NONE;
+        }
         else if (arg_flag == RejectK || arg_flag == RejectPx) {
             const double v = stod(a);
             if (!(v > 0.0) && !(arg_flag == RejectPx && v == 0.0)) return print_usage(argv[0]);
@@ -229,6 +312,26 @@ int main(int argc, char *argv[]) {
         so.solver = solver;
         mcm.set_solver_options(so);
     }
+    const bool constrained = fix_cams || fix_markers || !prior_path.empty();
+    if (constrained) {
+        if (fix_cams) mcm.set_fixed_cams(fixed_cams);
+        if (fix_markers) mcm.set_fixed_markers(fixed_markers);
+        if (!prior_path.empty()) {
+            vector<aar::MultiCamMapper::PosePrior> priors;
+            if (read_pose_priors(prior_path, mcm.dataset(), prior_sigma_deg, prior_sigma_m, priors)) return 5;
+            mcm.set_pose_priors(priors);
+        }
+        try {
+            const aar::MultiCamMapper::ConstraintIndices k = mcm.constraint_indices();
+            cout << "constraints: " << k.fixed_cams.size() << " fixed camera(s), " << k.fixed_markers.size() << " fixed marker(s), " << k.priors.size()
+                 << " pose prior(s)";
+            if (!prior_path.empty()) cout << " from " << prior_path << " (sigma " << prior_sigma_deg << " deg, " << prior_sigma_m << " m)";
+            cout << endl;
+        } catch (const exception &e) {
+            cerr << "constraints: " << e.what() << endl;
+            return 5;
+        }
+    }
     const auto start = chrono::system_clock::now();
     try {
         mcm.solve();
@@ -273,6 +376,15 @@ int main(int argc, char *argv[]) {
     }
     cout << "LM iterations: " << r.iterations << "  error " << r.initial_err << " -> " << r.final_err << "  (" << r.iterations / r.solve_seconds
          << " LM it/s in the solver loop)" << endl;
+    if (constrained) {
+        try {
+            const double pc = mcm.prior_cost();
+            cout << "final error: reprojection " << r.final_err - pc << " + prior " << pc << endl;
+        } catch (const exception &e) {
+            cerr << "prior cost failed: " << e.what() << endl;
+            return 3;
+        }
+    }
     const int minutes = (int)(d.count() / 60);
     const int seconds = (int)lround(d.count() - minutes * 60);
     cout << "The algorithm took: " << minutes << " minutes " << seconds << " seconds" << endl;

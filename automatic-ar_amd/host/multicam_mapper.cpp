@@ -2,6 +2,7 @@
 // vectors and file I/O happen on the host; residuals, Jacobians and the LM solve are HIP kernels.
 #include "multicam_mapper.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -285,9 +286,62 @@ int MultiCamMapper::ensure_problem() {
     so.pcg_eta_loose = solver_options_.pcg_eta_loose;
     so.pcg_eta_switch = solver_options_.pcg_eta_switch;
     so.pcg_abs_tol = solver_options_.pcg_abs_tol;
-    int rc = aar_problem_create_ex(&d, &so, &problem_);
+    const ConstraintIndices k = constraint_indices();
+    int rc;
+    if (k.empty()) {
+        rc = aar_problem_create_ex(&d, &so, &problem_);
+    } else {
+        aar_problem_constraints c;
+        memset(&c, 0, sizeof c);
+        c.struct_size = (uint32_t)sizeof c;
+        c.n_fixed_cams = (int32_t)k.fixed_cams.size(); c.fixed_cams = k.fixed_cams.data();
+        c.n_fixed_markers = (int32_t)k.fixed_markers.size(); c.fixed_markers = k.fixed_markers.data();
+        c.n_priors = (int32_t)k.priors.size(); c.priors = k.priors.data();
+        rc = aar_problem_create_constrained(&d, &so, &c, &problem_);
+    }
     if (!rc && with_huber_) rc = aar_problem_set_huber_delta(problem_, hubberDelta);
     return rc;
+}
+
+void MultiCamMapper::set_fixed_cams(std::set<int> ids) { fixed_cam_ids_ = std::move(ids); drop_problem(); }
+void MultiCamMapper::set_fixed_markers(std::set<int> ids) { fixed_marker_ids_ = std::move(ids); drop_problem(); }
+void MultiCamMapper::set_pose_priors(std::vector<PosePrior> priors) { pose_priors_ = std::move(priors); drop_problem(); }
+
+MultiCamMapper::ConstraintIndices MultiCamMapper::constraint_indices() const {
+    ConstraintIndices k;
+    if (!data_) return k;
+    auto index_of = [](const int32_t *ids, int n, int id, const char *what) -> int {
+        const int32_t *e = ids + n, *p = std::lower_bound(ids, e, id);   // (ids ascending)
+        if (p == e || *p != id) throw std::invalid_argument(std::string("MultiCamMapper: no ") + what + " with id " + std::to_string(id));
+        return (int)(p - ids);
+    };
+    const int C = data_->num_cams, M = data_->num_markers;
+    std::vector<uint8_t> held(C + M, 0);
+    for (int c = 0; c < C; c++) held[c] = (c == data_->root_cam || !config_.optimize_cam_poses) ? 1 : 0;
+    for (int m = 0; m < M; m++) held[C + m] = (m == data_->root_marker || !config_.optimize_marker_poses) ? 1 : 0;
+    for (int id : fixed_cam_ids_) { const int c = index_of(data_->cam_ids, C, id, "camera"); k.fixed_cams.push_back(c); held[c] = 1; }
+    for (int id : fixed_marker_ids_) { const int m = index_of(data_->marker_ids, M, id, "marker"); k.fixed_markers.push_back(m); held[C + m] = 1; }
+    for (const PosePrior &q : pose_priors_) {
+        aar_pose_prior p;
+        memset(&p, 0, sizeof p);
+        p.kind = q.kind;
+        p.index = q.kind == AAR_PRIOR_CAMERA ? index_of(data_->cam_ids, C, q.id, "camera") : index_of(data_->marker_ids, M, q.id, "marker");
+        if (held[q.kind == AAR_PRIOR_CAMERA ? p.index : C + p.index]) continue;
+        rigid_to_pose(from44(q.T), p.x6);
+        memcpy(p.info, q.info.data(), sizeof p.info);
+        k.priors.push_back(p);
+    }
+    return k;
+}
+
+double MultiCamMapper::prior_cost() {
+    if (!data_) throw std::runtime_error("MultiCamMapper::prior_cost: no data set");
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    if (aar_problem_num_priors(problem_) == 0) return 0.0;
+    std::vector<double> x = problem_vector();
+    double cost = 0;
+    if (aar_problem_eval_priors(problem_, x.data(), nullptr, &cost)) throw std::runtime_error(aar_last_error());
+    return cost;
 }
 
 void MultiCamMapper::set_solver_options(const SolverOptions &o) {

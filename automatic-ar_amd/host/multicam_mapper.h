@@ -470,6 +470,28 @@ class MultiCamMapper {
     int64_t reject_outliers(double k_median, double min_px = 0.0, ResidualReport *out = nullptr);
     bool write_residuals_file(const std::string &path, const ResidualReport &rep);   // YAML, aar_residual_report_write_yaml
 
+    // EXTENSION, no counterpart in the reference: per-entity fixing and pose priors (aar_problem_constraints), by ID.
+    // Fixed cameras / markers stay exactly where they are; a prior pulls a camera / marker toward a 4x4 transform T (the convention of
+    // get_transforms_to_root_cam / _marker) with a 6x6 information matrix over (rx ry rz tx ty tz).  They take effect when the device problem
+    // is (re)built and hold across Config changes and reject_outliers rebuilds; a prior on an entity the Config or the fixed sets hold is
+    // left out.  An unknown id throws std::invalid_argument when the problem is built (constraint_indices).
+    struct PosePrior {
+        int kind = AAR_PRIOR_CAMERA;   // AAR_PRIOR_CAMERA | AAR_PRIOR_MARKER
+        int id = 0;
+        Mat44 T{};
+        Mat66 info{};
+    };
+    void set_fixed_cams(std::set<int> ids);
+    void set_fixed_markers(std::set<int> ids);
+    void set_pose_priors(std::vector<PosePrior> priors);
+    struct ConstraintIndices {   // what the device problem gets: indices, and the priors as x6 in x_full's convention
+        std::vector<int32_t> fixed_cams, fixed_markers;
+        std::vector<aar_pose_prior> priors;
+        bool empty() const { return fixed_cams.empty() && fixed_markers.empty() && priors.empty(); }
+    };
+    ConstraintIndices constraint_indices() const;
+    double prior_cost();   // sum of e^T L e at the current solution (aar_problem_eval_priors); 0 without priors
+
     const aar_dataset *dataset() const { return data_; }
 
    private:
@@ -490,6 +512,8 @@ class MultiCamMapper {
     Config config_;
     SolverOptions solver_options_;
     bool with_huber_ = false;
+    std::set<int> fixed_cam_ids_, fixed_marker_ids_;
+    std::vector<PosePrior> pose_priors_;
 };
 
 }  // namespace aar

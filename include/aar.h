@@ -423,6 +423,52 @@ int aar_dataset_select_observations(const aar_dataset *d, const uint8_t *keep, a
 int aar_residual_report_write_yaml(const char *path, const aar_dataset *d, const double *cam_stats, const double *marker_stats,
                                    const double *det_err, const uint8_t *keep, const aar_residual_report *report);
 
+/* Per-entity fixing and pose priors (no counterpart in the reference).  Cameras and markers are named by INDEX
+ * (problem indices as in aar_problem_desc, not ids).
+ *  Fixed entities: fixed_cams / fixed_markers are held where they are, exactly as the roots are.  The layout of z does not change
+ *    (num_vars, extract_z, merge_z are those of the problem without constraints); a fixed entity's rows of every step are exactly 0 and
+ *    its pose in x_full stays bit-identical.  Naming a root or an entity of a non-optimised group is allowed and changes nothing.
+ *    Intrinsics entities are not affected: fixing camera c's pose leaves its intrinsics free.
+ *  Pose priors: {kind, index, x6, info}.  x6 is the prior pose as the entity's 6-vector in x_full's convention (rvec, t) -- relative to
+ *    the root camera / marker like everything in x_full --, info a symmetric positive semi-definite 6x6 information matrix L (rotation
+ *    rows first).  With R, t the entity's current pose the prior residual is
+ *        phi = log(R_p^T R)^v,   e = [phi ; t - t_p],   cost = e^T L e
+ *    and cost is added to the data's sum r^2 everywhere the solver reads an error (the LM's gain test and stopping rules, aar_lm_report,
+ *    aar_eval_normal_equations' sum_sq).  J^T L J (J = [J_r(phi)^-1 J_r(w) 0; 0 I] over the entity's z entries (w, t)) joins the
+ *    entity's diagonal block of J^T J and -J^T L e joins B, in every entry point that builds the normal equations: the LM,
+ *    aar_eval_normal_equations, aar_eval_damped_step and aar_problem_covariance.  Priors are never Huber-weighted.
+ *  Validation (AAR_ERR_INVALID, the message names the entry): an index out of range, two priors on one entity, a prior on a fixed
+ *    entity (root, non-optimised group or fixed index), an information matrix that is not symmetric or not positive semi-definite
+ *    (a host Cholesky with a negative pivot, or a zero pivot over a non-zero column), a non-finite value.  L = 0 is allowed: it adds
+ *    nothing. */
+enum { AAR_PRIOR_CAMERA = 0, AAR_PRIOR_MARKER = 1 };
+typedef struct aar_pose_prior {
+    int32_t kind;                             /* AAR_PRIOR_CAMERA | AAR_PRIOR_MARKER                                      */
+    int32_t index;                            /* camera / marker index                                                    */
+    double x6[6];                             /* prior pose (rx ry rz tx ty tz), x_full's convention                      */
+    double info[36];                          /* row-major 6x6 information matrix, rotation rows first                    */
+} aar_pose_prior;
+typedef struct aar_problem_constraints {
+    uint32_t struct_size;                     /* sizeof(aar_problem_constraints) of the caller: fields beyond it count as empty */
+    int32_t n_fixed_cams;
+    const int32_t *fixed_cams;                /* [n_fixed_cams] camera indices                                            */
+    int32_t n_fixed_markers;
+    const int32_t *fixed_markers;             /* [n_fixed_markers] marker indices                                         */
+    int32_t n_priors;
+    const aar_pose_prior *priors;             /* [n_priors]                                                               */
+} aar_problem_constraints;
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the offending entry.  NULL constraints are valid. */
+int aar_problem_constraints_validate(const aar_problem_desc *, const aar_problem_constraints *);
+/* aar_problem_create_ex with constraints (validated first).  options may be NULL (AUTO); NULL or empty constraints: exactly
+ * aar_problem_create_ex.  With a communicator every rank passes the same constraints; only rank 0 adds the prior terms (the
+ * all-reduce of the reduced system makes them global). */
+int aar_problem_create_constrained(const aar_problem_desc *, const aar_solver_options *options, const aar_problem_constraints *constraints,
+                                   aar_problem **out);
+int32_t aar_problem_num_priors(const aar_problem *);
+/* The priors at x_full, by the device code the solver runs: e_out [n_priors][6] (may be NULL), cost = sum of e^T L e (may be NULL).
+ * With a communicator every rank gets the same values.  Leaves the problem as aar_eval_damped_step does (no LM state). */
+int aar_problem_eval_priors(aar_problem *, const double *x_full, double *e_out, double *cost);
+
 /* ucoslam::SparseLevMarq<T>::Params (libs/sparselevmarq.h:30-50) with the values
  * MultiCamMapper::init installs (libs/multicam_mapper.cpp:326-330). */
 typedef struct aar_lm_params {
@@ -503,7 +549,7 @@ int aar_problem_pcg_iterations(aar_problem *, int32_t out[2]);
 /* Per-kernel device time: when profiling is on, every kernel launch of this problem is bracketed by two HIP
  * events on the library's own stream (the stream the kernels run on) and the elapsed times are accumulated
  * per kernel.  bench.py's roofline figures come from here.  Switching profiling on resets the accumulators. */
-#define AAR_NUM_KERNELS 17
+#define AAR_NUM_KERNELS 18
 int aar_set_kernel_profiling(aar_problem *, int on);
 int aar_get_kernel_times(aar_problem *, double seconds[AAR_NUM_KERNELS], int64_t launches[AAR_NUM_KERNELS]);
 const char *aar_kernel_name(int kernel_id);
