@@ -14,73 +14,8 @@ from conftest import PKG, load_golden
 pytestmark = pytest.mark.gpu
 
 
-# ---- numpy restatement of the prior (include/aar.h) ----
-def hat(w):
-    return np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-
-
-def rodrigues(w):
-    th = np.linalg.norm(w)
-    if th < 1e-300:
-        return np.eye(3)
-    k = hat(w / th)
-    return np.eye(3) + np.sin(th) * k + (1 - np.cos(th)) * k @ k
-
-
-def so3_log(Q):
-    v = np.array([Q[2, 1] - Q[1, 2], Q[0, 2] - Q[2, 0], Q[1, 0] - Q[0, 1]])
-    s2 = np.linalg.norm(v)
-    th = np.arctan2(0.5 * s2, 0.5 * (np.trace(Q) - 1))
-    return v * (0.5 if s2 == 0 else th / s2)
-
-
-def jl(w):
-    th = np.linalg.norm(w)
-    K = hat(w)
-    if th < 1e-8:
-        return np.eye(3) + 0.5 * K
-    return np.eye(3) + (1 - np.cos(th)) / th ** 2 * K + (th - np.sin(th)) / th ** 3 * K @ K
-
-
-def jr_inv(phi):
-    th = np.linalg.norm(phi)
-    K = hat(phi)
-    k = 1 / 12 if th < 1e-8 else 1 / th ** 2 - (1 + np.cos(th)) / (2 * th * np.sin(th))
-    return np.eye(3) + 0.5 * K + k * K @ K
-
-
-def prior_e(x6, xp):
-    return np.r_[so3_log(rodrigues(xp[:3]).T @ rodrigues(x6[:3])), x6[3:] - xp[3:]]
-
-
-def prior_J(x6, xp):
-    phi = prior_e(x6, xp)[:3]
-    J = np.eye(6)
-    J[:3, :3] = jr_inv(phi) @ jl(x6[:3]).T
-    return J
-
-
-def slot_col(ds, kind, idx):
-    """z / x_full column of a camera or marker's 6-vector (default Config: cameras | markers | frames, roots skipped)"""
-    if kind == "camera":
-        return 6 * (idx - (idx > ds.root_cam))
-    return 6 * (ds.num_cams - 1) + 6 * (idx - (idx > ds.root_marker))
-
-
-def prior_terms(ds, x, priors, P):
-    """dense J_p^T L J_p (P x P), -J_p^T L e, sum e^T L e of the priors at x"""
-    H = np.zeros((P, P))
-    B = np.zeros(P)
-    cost = 0.0
-    for kind, idx, xp, info in priors:
-        c = slot_col(ds, kind, idx)
-        x6 = x[c:c + 6]
-        e = prior_e(x6, xp)
-        J = prior_J(x6, xp)
-        H[c:c + 6, c:c + 6] += J.T @ info @ J
-        B[c:c + 6] -= J.T @ info @ e
-        cost += e @ info @ e
-    return H, B, cost
+# ---- numpy restatement of the prior (include/aar.h): tests/reduced_system.py ----
+from reduced_system import prior_e, prior_terms, rodrigues, slot_col, so3_log  # noqa: E402
 
 
 def free_entities(ds):
