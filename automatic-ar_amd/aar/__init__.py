@@ -38,6 +38,7 @@ SYMBOLS = [
     "aar_problem_covariance", "aar_covariance_write_yaml",
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
+    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system",
 ]
 NUM_KERNELS = 18
 PRIOR_CAMERA, PRIOR_MARKER = 0, 1
@@ -183,6 +184,43 @@ class CLmParams(C.Structure):
     ]
 
 
+class CSmoothParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sigma_rot", C.c_double), ("sigma_trans", C.c_double),
+                ("frame_time", C.POINTER(C.c_double)), ("rel_motion", C.POINTER(C.c_double))]
+
+
+class CSmoothReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("stop_code", C.c_int32), ("rejected_tries", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_data_cost", C.c_double),
+                ("final_prior_cost", C.c_double), ("final_mu", C.c_double), ("seconds", C.c_double)]
+
+
+class SmoothParams:
+    """aar_smooth_params built from Python values (the arrays are kept alive with the struct)"""
+
+    def __init__(self, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, struct_size=None):
+        self._ft = None if frame_time is None else np.ascontiguousarray(frame_time, dtype=np.float64).reshape(-1)
+        self._rm = None if rel_motion is None else np.ascontiguousarray(rel_motion, dtype=np.float64).reshape(-1)
+        c = CSmoothParams()
+        c.struct_size = C.sizeof(CSmoothParams) if struct_size is None else int(struct_size)
+        c.sigma_rot, c.sigma_trans = float(sigma_rot), float(sigma_trans)
+        c.frame_time = None if self._ft is None else self._ft.ctypes.data_as(C.POINTER(C.c_double))
+        c.rel_motion = None if self._rm is None else self._rm.ctypes.data_as(C.POINTER(C.c_double))
+        self.c = c
+
+    def check_lengths(self, num_frames):
+        assert self._ft is None or len(self._ft) == num_frames
+        assert self._rm is None or len(self._rm) == 6 * max(num_frames - 1, 0)
+
+
+def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, struct_size=None):
+    """aar_smooth_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  struct_size overrides the
+    struct's own size (versioning tests)."""
+    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size)
+    sp.check_lengths(num_frames)
+    _check(lib().aar_smooth_params_validate(int(num_frames), C.byref(sp.c)))
+
+
 class CLmIter(C.Structure):
     _fields_ = [("err", C.c_double), ("mu", C.c_double), ("gain", C.c_double), ("delta_norm", C.c_double),
                 ("accepted", C.c_int32), ("tries", C.c_int32)]
@@ -300,6 +338,9 @@ def lib():
     L.aar_kernel_name.argtypes = [C.c_int]
     L.aar_kernel_name.restype = C.c_char_p
     L.aar_track.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(C.c_int32), dp]
+    L.aar_smooth_params_validate.argtypes = [C.c_int32, C.POINTER(CSmoothParams)]
+    L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothReport)]
+    L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_double, dp, dp, dp, dp, dp]
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.aar_local_group_destroy.argtypes = [C.c_void_p]
     L.aar_local_group_destroy.restype = None
@@ -968,6 +1009,33 @@ class Problem:
         _check(lib().aar_track(self.handle, _dptr(x), C.byref(params) if params is not None else None,
                                it.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(err)))
         return x, it, err
+
+    def track_smooth(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None):
+        """aar_track_smooth: every frame's pose with a motion prior between consecutive frames, one joint LM on the device.  Returns
+        (x_full with the smoothed frame poses, report dict, frame_err [F] = E_f, pair_err [F-1] = e_f^T L_f e_f)."""
+        x = np.array(self._x(x_full), dtype=np.float64)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp.check_lengths(F)
+        fe, pe = np.zeros(max(F, 1)), np.zeros(max(F - 1, 1))
+        rep = CSmoothReport()
+        rep.struct_size = C.sizeof(CSmoothReport)
+        _check(lib().aar_track_smooth(self.handle, _dptr(x), C.byref(params) if params is not None else None, C.byref(sp.c),
+                                      _dptr(fe), _dptr(pe), C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothReport._fields_ if k != "struct_size"}
+        return x, report, fe[:F], pe[:max(F - 1, 0)]
+
+    def track_smooth_system(self, x_full, sigma_rot, sigma_trans, mu, frame_time=None, rel_motion=None):
+        """aar_track_smooth_system: (diag [F, 6, 6], off [F-1, 6, 6], rhs [6F], delta [6F], (data cost, prior cost)) of one try at x_full"""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp.check_lengths(F)
+        diag, off = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6))
+        rhs, delta, cost = np.zeros(6 * max(F, 1)), np.zeros(6 * max(F, 1)), np.zeros(2)
+        _check(lib().aar_track_smooth_system(self.handle, _dptr(x), C.byref(sp.c), float(mu), _dptr(diag), _dptr(off), _dptr(rhs),
+                                             _dptr(delta), _dptr(cost)))
+        return diag[:F], off[:max(F - 1, 0)], rhs[:6 * F], delta[:6 * F], (cost[0], cost[1])
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

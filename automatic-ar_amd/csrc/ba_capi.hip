@@ -2625,6 +2625,211 @@ int aar_track(aar_problem *pb, double *x_full, const aar_lm_params *prm, int32_t
     return AAR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Smoothed tracking (smooth_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the caller's struct read up to its struct_size; false: too short to hold the sigmas
+bool smooth_params_read(const aar_smooth_params *sp, aar_smooth_params *out) {
+    memset(out, 0, sizeof *out);
+    if (sp->struct_size < offsetof(aar_smooth_params, sigma_trans) + sizeof(double)) return false;
+    memcpy(out, sp, std::min<size_t>(sp->struct_size, sizeof *out));
+    return true;
+}
+
+struct SmoothCall {
+    double *base = nullptr;
+    SmoothWork w;
+    ~SmoothCall() { if (base) (void)hipFree(base); }
+};
+
+// workspace, lambda and the expected motions on the device; the frame poses of z[cur] (uploaded by the caller) into w.z[0]
+int smooth_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCall &c) {
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const size_t n = smooth_work_doubles(F);
+    HIP_TRY(hipMalloc((void **)&c.base, n * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(c.base, 0, n * sizeof(double), pb->stream));
+    smooth_work_carve(c.w, c.base, F);
+    int rc = AAR_OK;
+    if (F > 1) {
+        std::vector<double> lam(2 * (size_t)(F - 1));
+        for (int f = 0; f + 1 < F; f++) {
+            const double dt = sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0;
+            lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt);
+            lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt);
+        }
+        if ((rc = copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double)))) return rc;
+        if (sp.rel_motion) {
+            if ((rc = copy_h2d(pb, c.w.rel_buf, sp.rel_motion, 6 * (size_t)(F - 1) * sizeof(double)))) return rc;
+            c.w.rel = c.w.rel_buf;
+        }
+    }
+    if (F) HIP_TRY(hipMemcpyAsync(c.w.z[0], P.z[pb->cur] + 6 * (size_t)P.A, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    return AAR_OK;
+}
+
+int smooth_entry(aar_problem *pb, const aar_smooth_params *sp_in, aar_smooth_params *sp, const char *who) {
+    if (!sp_in) return set_error(AAR_ERR_INVALID, "%s: null aar_smooth_params", who);
+    int rc = aar_smooth_params_validate(pb->L.F, sp_in);
+    if (rc) return rc;
+    (void)smooth_params_read(sp_in, sp);
+    if (pb->comm) return set_error(AAR_ERR_UNSUPPORTED, "%s: the motion prior couples frames across shard boundaries; smoothed tracking is single-GPU only", who);
+    return AAR_OK;
+}
+
+}  // namespace
+
+int aar_smooth_params_validate(int32_t num_frames, const aar_smooth_params *sp_in) {
+    if (!sp_in) return set_error(AAR_ERR_INVALID, "aar_smooth_params_validate: null argument");
+    if (num_frames < 0) return set_error(AAR_ERR_INVALID, "aar_smooth_params: num_frames %d is negative", (int)num_frames);
+    aar_smooth_params sp;
+    if (!smooth_params_read(sp_in, &sp))
+        return set_error(AAR_ERR_INVALID, "aar_smooth_params: struct_size %u does not reach sigma_rot / sigma_trans", (unsigned)sp_in->struct_size);
+    if (!(sp.sigma_rot > 0.0) || !std::isfinite(sp.sigma_rot)) return set_error(AAR_ERR_INVALID, "aar_smooth_params: sigma_rot = %g must be positive and finite", sp.sigma_rot);
+    if (!(sp.sigma_trans > 0.0) || !std::isfinite(sp.sigma_trans)) return set_error(AAR_ERR_INVALID, "aar_smooth_params: sigma_trans = %g must be positive and finite", sp.sigma_trans);
+    if (sp.frame_time)
+        for (int f = 0; f < num_frames; f++) {
+            if (!std::isfinite(sp.frame_time[f])) return set_error(AAR_ERR_INVALID, "aar_smooth_params: frame_time[%d] is not finite", f);
+            if (f > 0 && !(sp.frame_time[f] > sp.frame_time[f - 1]))
+                return set_error(AAR_ERR_INVALID, "aar_smooth_params: frame_time[%d] = %g does not ascend from frame_time[%d] = %g", f, sp.frame_time[f], f - 1, sp.frame_time[f - 1]);
+            if (f > 0 && !std::isfinite(sp.frame_time[f] - sp.frame_time[f - 1]))
+                return set_error(AAR_ERR_INVALID, "aar_smooth_params: frame_time[%d] - frame_time[%d] overflows", f, f - 1);
+        }
+    if (sp.rel_motion)
+        for (int f = 0; f + 1 < num_frames; f++)
+            for (int k = 0; k < 6; k++)
+                if (!std::isfinite(sp.rel_motion[6 * (size_t)f + k])) return set_error(AAR_ERR_INVALID, "aar_smooth_params: rel_motion[%d][%d] is not finite", f, k);
+    return AAR_OK;
+}
+
+int aar_track_smooth_system(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double mu, double *diag, double *off, double *rhs,
+                            double *delta, double cost[2]) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system: null argument");
+    if (!(mu >= 0.0) || !std::isfinite(mu)) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system: mu = %g must be finite and not negative", mu);
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_system");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCall c;
+    if ((rc = smooth_prepare(pb, sp, c))) return rc;
+    if (cost) cost[0] = cost[1] = 0.0;
+    if (F == 0) { HIP_TRY(hipStreamSynchronize(pb->stream)); return AAR_OK; }
+    launch_smooth_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
+    double res[8];
+    if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+    if (cost) { cost[0] = res[0]; cost[1] = res[1]; }
+    if (diag && (rc = copy_d2h(pb, diag, c.w.Dg, 36 * (size_t)F * sizeof(double)))) return rc;
+    if (off && F > 1 && (rc = copy_d2h(pb, off, c.w.Of, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    if (rhs && (rc = copy_d2h(pb, rhs, c.w.rhs, 6 * (size_t)F * sizeof(double)))) return rc;
+    if (delta) {
+        pb->launches += launch_smooth_solve(c.w, F, mu, pb->stream);
+        int32_t flag = 0;
+        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+        if ((rc = copy_d2h(pb, delta, c.w.delta, 6 * (size_t)F * sizeof(double)))) return rc;
+        if (flag) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_system: non-positive pivot in the block-tridiagonal solve (mu = %g)", mu);
+    }
+    return check_async("smoothing kernels");
+}
+
+int aar_track_smooth(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, double *frame_err, double *pair_err,
+                     aar_smooth_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    aar_lm_params p;
+    if (prm) p = *prm; else aar_lm_default_params(&p);
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    const int F = P.F;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);  // rows of the fixed cameras / markers (and K with intrinsics)
+    SmoothCall c;
+    if ((rc = smooth_prepare(pb, sp, c))) return rc;
+    const SmoothWork &w = c.w;
+    const double rows = 8.0 * (double)P.N + 6.0 * (double)(F - 1);
+    int cur = 0, iters = 0, rejected = 0, mustExit = 0;
+    double res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double currData = 0.0, currPrior = 0.0, mu = -1.0, v = 2.0;
+    if (F > 0) {
+        // init: the first evaluation also yields the first step's system
+        launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream);
+        pb->launches += 2;
+        if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;
+        currData = res[0]; currPrior = res[1];
+    }
+    double currErr = currData + currPrior, prevErr = currErr;
+    const double initial = currErr;
+    for (int it = 0; it < p.max_iters && !mustExit && rows > 0 && F > 0; it++) {
+        if (it > 0) { launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream); pb->launches += 2; }   // H, b at curr_z (its costs are those already held)
+        if (mu < 0) mu = res[4] * p.tau;   // (first iteration: res still holds the initial evaluation's record)
+        double gain = 0.0;
+        int ntries = 0;
+        bool accepted = false;
+        do {
+            pb->launches += launch_smooth_solve(w, F, mu, pb->stream);
+            launch_smooth_eval(P, pb->cur, w, cur, false, pb->stream);   // z[1 - cur] = z[cur] + delta, its costs, |delta|^2, delta . b
+            pb->launches += 2;
+            if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;   // the try's one read-back
+            const double err = res[0] + res[1];
+            const bool bad_pivot = res[5] != 0.0;
+            const double Lq = 0.5 * (mu * res[2] - res[3]);
+            gain = (err - prevErr) / Lq;
+            if (!bad_pivot && gain > 0 && (err - prevErr) < 0) {
+                const double t = 2 * gain - 1;
+                mu = mu * std::max(0.33, 1.0 - t * t * t);
+                v = 2.0;
+                currErr = err; currData = res[0]; currPrior = res[1];
+                cur = 1 - cur;
+                accepted = true;
+            } else {
+                if (bad_pivot) gain = 0.0;   // a failed factorisation is a rejected try: more damping, and the retry rule below applies
+                mu = mu * v;
+                v = v * 5;
+                rejected++;
+            }
+        } while (gain <= 0 && ntries++ < 5 && !accepted);
+        if (currErr < p.min_error) mustExit = 1;
+        if (std::fabs(prevErr - currErr) <= p.min_step_error_diff || std::fabs((prevErr - currErr) / rows) <= p.min_average_step_error_diff || !accepted)
+            mustExit = 2;
+        if (currErr > prevErr) mustExit = 3;
+        iters++;
+        prevErr = currErr;
+    }
+    if (F) HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, w.z[cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    if (frame_err && F && (rc = copy_d2h(pb, frame_err, w.Ef[cur], (size_t)F * sizeof(double)))) return rc;
+    if (pair_err && F > 1 && (rc = copy_d2h(pb, pair_err, w.Pe[cur], (size_t)(F - 1) * sizeof(double)))) return rc;
+    if ((rc = check_async("smoothing kernels"))) return rc;
+    // only the frame poses move; download_z honours the Config flags, so force "frames on, shared off" for this call
+    PoseLayout keep = pb->L;
+    pb->L.oc = false; pb->L.om = false; pb->L.of = true;
+    rc = download_z(pb, pb->cur, x_full);
+    pb->L = keep;
+    if (rc) return rc;
+    if (report) {
+        aar_smooth_report r;
+        memset(&r, 0, sizeof r);
+        r.struct_size = report->struct_size;
+        r.iterations = iters; r.stop_code = mustExit; r.rejected_tries = rejected;
+        r.initial_cost = initial; r.final_cost = currErr; r.final_data_cost = currData; r.final_prior_cost = currPrior;
+        r.final_mu = mu;
+        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
 int aar_set_kernel_profiling(aar_problem *pb, int on) {
     if (!pb) return set_error(AAR_ERR_INVALID, "aar_set_kernel_profiling: null argument");
     HIP_TRY(hipSetDevice(pb->device));

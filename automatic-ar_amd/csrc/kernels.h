@@ -286,6 +286,27 @@ inline int n_err_terms(const DeviceProblem &P) { return P.F + ((P.n_prior > 0 &&
 void launch_track(const DeviceProblem &P, int which, int max_iters, double min_error, double min_step, double min_avg, double tau,
                   int32_t *iters_out, double *err_out, hipStream_t st);
 
+// smoothed tracking (smooth_kernels.hip): the workspace of one aar_track_smooth call, carved out of one allocation
+constexpr int SMOOTH_TAIL = 256;   // threads of the workgroup that finishes the cyclic reduction: levels with at most this many eliminating nodes run inside it
+struct SmoothWork {
+    double *z[2] = {nullptr, nullptr};     // [F][6] frame poses: the current point and the trial point
+    double *delta = nullptr;               // [F][6] the damped step
+    double *Dg = nullptr, *Of = nullptr;   // [F][36] H_ff, [F][36] H_{f,f+1} (row-major, rows: frame f; the last one unused)
+    double *rhs = nullptr;                 // [F][6] b
+    double *Dw = nullptr, *Uw = nullptr, *bw = nullptr, *Dinv = nullptr, *Ls = nullptr;   // the reduction's working copy and what its back-substitution keeps
+    double *Ef[2] = {nullptr, nullptr}, *Pe[2] = {nullptr, nullptr};   // [F] data cost per frame, prior cost per pair, of the two points
+    double *lin = nullptr;                 // [F][2] |delta_f|^2, delta_f . b_f
+    double *lam = nullptr;                 // [F-1][2] 1 / (sigma_rot^2 dt), 1 / (sigma_trans^2 dt)
+    double *rel_buf = nullptr;             // [F-1][6] storage of the expected relative motions ...
+    const double *rel = nullptr;           // ... = rel_buf when the caller gave any, else NULL
+    double *res = nullptr;                 // [8] the record the host reads: data cost, prior cost, |delta|^2, delta . b, max diag H, pivot flag
+    int32_t *flag = nullptr;               // [1] a non-positive pivot in the last solve
+};
+size_t smooth_work_doubles(int F);
+void smooth_work_carve(SmoothWork &w, double *base, int F);
+void launch_smooth_eval(const DeviceProblem &P, int which, const SmoothWork &w, int cur, bool with_j, hipStream_t st);   // two launches
+int launch_smooth_solve(const SmoothWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
+
 // covariance (cov_kernels.hip): S (stride n_pad) -> S2 (stride n2 >= n_pad, zero beyond n_pad), rows with rowmask set -> identity
 void launch_cov_stage(const double *S, int n_pad, double *S2, int n2, const int32_t *rowmask, hipStream_t st);
 // the LDL^T factor launch_chol left for S2 (nT2 tiles, fused_m = the panel rule it ran with) -> Sinv = S^-1, lower 32 x 32 tiles of the first

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -195,8 +195,13 @@ int main(int argc, char *argv[]) {
     bool fix_cams = false, fix_markers = false;
     string prior_path;
     double prior_sigma_deg = 1.0, prior_sigma_m = 0.01;
+    // nor this: -smooth <sigma_rot> <sigma_trans> (only with -tracking-only) refines every frame with track() after the solve and then smooths the
+    // trajectory with a motion prior between consecutive frames (MultiCamMapper::track_smooth)
+    bool smooth = false;
+    double smooth_sigma[2] = {0.0, 0.0};
+    int smooth_args = 0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, Smooth } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -215,6 +220,14 @@ int main(int argc, char *argv[]) {
         else if (a == "-prior-solution") arg_flag = PriorPath;
         else if (a == "-prior-sigma-deg") arg_flag = PriorDeg;
         else if (a == "-prior-sigma-m") arg_flag = PriorM;
+        else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
+        else if (arg_flag == Smooth) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            smooth_sigma[smooth_args++] = v;
+            if (smooth_args == 2) arg_flag = NONE;
+        }
         else if (arg_flag == FixCams || arg_flag == FixMarkers) {
             if (!parse_ids(a, arg_flag == FixCams ? fixed_cams : fixed_markers)) return print_usage(argv[0]);
             (arg_flag == FixCams ? fix_cams : fix_markers) = true;
@@ -242,6 +255,7 @@ int main(int argc, char *argv[]) {
         else if (arg_flag == ExcludeCams) excluded_cams.insert(stoi(a));
         else if (arg_flag == Threshold) { threshold = stod(a); arg_flag = NONE; }
     }
+    if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     string name = "";
     if (tracking_only) name += "_tracking_only";
     if (use_subseqs) name += "_subseqs";
@@ -350,6 +364,18 @@ int main(int argc, char *argv[]) {
         } catch (const exception &e) {
             cerr << "residual report failed: " << e.what() << endl;
             return 4;
+        }
+    }
+    if (smooth) {
+        try {
+            mcm.track();
+            mcm.track_smooth(smooth_sigma[0], smooth_sigma[1]);
+            const aar_smooth_report &sr = mcm.smooth_report;
+            cout << "smooth: " << sr.iterations << " LM iterations (" << sr.rejected_tries << " rejected tries, exit " << sr.stop_code << "), cost " << sr.initial_cost
+                 << " -> " << sr.final_cost << " (data " << sr.final_data_cost << ", prior " << sr.final_prior_cost << ") in " << sr.seconds << " s" << endl;
+        } catch (const exception &e) {
+            cerr << "smoothing failed: " << e.what() << endl;
+            return 6;
         }
     }
     const chrono::duration<double> d = chrono::system_clock::now() - start;

@@ -531,6 +531,41 @@ double solve_tracking(MultiCamMapper *m, std::vector<double> &z) {
 }
 }  // namespace detail
 
+// Smoothed tracking (aar_track_smooth): track()'s model plus a random-walk motion prior between consecutive frames, one
+// joint LM on the device.  The mapper's frame ids are the prior's time axis, so a hole in the recording is bridged more loosely than one step.
+void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::track_smooth: no data set");
+    mats2eVec();
+    hubberDelta = 10;  // as track()
+    std::vector<double> x;
+    aar_problem *pb = detail::bind_problem(this, x);
+    if (aar_problem_merge_z(pb, io_vec.data(), x.data())) throw std::runtime_error(aar_last_error());
+    aar_lm_params p;
+    aar_lm_default_params(&p);
+    p.max_iters = solver_params.maxIters;
+    p.min_error = solver_params.minError;
+    p.min_step_error_diff = solver_params.min_step_error_diff;
+    p.min_average_step_error_diff = solver_params.min_average_step_error_diff;
+    p.tau = solver_params.tau;
+    const int F = data_->num_frames;
+    std::vector<double> time(F);
+    for (int f = 0; f < F; f++) time[f] = (double)data_->frame_ids[f];
+    aar_smooth_params sp;
+    memset(&sp, 0, sizeof sp);
+    sp.struct_size = sizeof sp;
+    sp.sigma_rot = sigma_rot;
+    sp.sigma_trans = sigma_trans;
+    sp.frame_time = F ? time.data() : nullptr;
+    memset(&smooth_report, 0, sizeof smooth_report);
+    smooth_report.struct_size = sizeof smooth_report;
+    track_errors.assign(F, 0.0);
+    smooth_pair_errors.assign(F > 1 ? F - 1 : 0, 0.0);
+    if (aar_track_smooth(pb, x.data(), &p, &sp, track_errors.data(), smooth_pair_errors.data(), &smooth_report)) throw std::runtime_error(aar_last_error());
+    if (aar_problem_extract_z(pb, x.data(), io_vec.data())) throw std::runtime_error(aar_last_error());   // (only the frame poses have moved)
+    memcpy(data_->x_full, x.data(), sizeof(double) * aar_dataset_full_len(data_));   // ... also when the Config keeps them out of z
+    eVec2Mats(io_vec);
+}
+
 bool MultiCamMapper::write_solution_file(std::string path) {
     if (!data_) return false;
     aar_dataset tmp = *data_;

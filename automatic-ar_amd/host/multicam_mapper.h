@@ -390,6 +390,10 @@ class MultiCamMapper {
 
     void solve();                                               // libs/multicam_mapper.cpp:419-428
     void track();                                               // :430-443, every frame of the data set at once
+    // no counterpart in the reference: track()'s model with a random-walk motion prior between consecutive frames (sigma_rot rad, sigma_trans
+    // metre per sqrt(frame id step)), all frames in one LM on the device (aar_track_smooth); the report lands in smooth_report, E_f in
+    // track_errors and the pairs' prior costs in smooth_pair_errors
+    void track_smooth(double sigma_rot, double sigma_trans);
     void error_function(const eVector &input, eVector &error);  // :731-737
     // :739-801 (private in the reference; public here so that reference-shaped caller code outside the class can bind it).  The
     // Jacobian of the accelerated path is analytic and never leaves the device: called by the solver mirror's probe it names
@@ -420,6 +424,8 @@ class MultiCamMapper {
     aar_lm_report last_report;                    // iterations, errors and timing of the last solve()
     std::vector<int32_t> track_iterations;        // per frame, after track()
     std::vector<double> track_errors;
+    aar_smooth_report smooth_report = {};         // after track_smooth()
+    std::vector<double> smooth_pair_errors;       // [num_frames - 1] e_f^T L_f e_f, after track_smooth()
     int device_id = 0;
     int residual_mode = AAR_RES_F32;
     // How the damped normal equations are solved (aar_solver_options, include/aar.h) -- the counterpart of configuring the reference's solver object

@@ -530,6 +530,45 @@ int aar_problem_merge_z(const aar_problem *, const double *z, double *x_full);
  * iterations / final_err: optional [num_frames] outputs (step() calls made, final sum of squares per frame). */
 int aar_track(aar_problem *, double *x_full, const aar_lm_params *, int32_t *iterations, double *final_err);
 
+/* Smoothed tracking (no counterpart in the reference): aar_track's model with a motion prior between consecutive frames,
+ * solved as ONE Levenberg-Marquardt problem over all 6 num_frames frame unknowns on the device.  Cameras, markers and intrinsics stay at
+ * their x_full values and the optimize_* flags are ignored, exactly as in aar_track.
+ *     E(z) = sum_f E_f(z_f) + sum_{f < F-1} e_f^T L_f e_f
+ *     e_f  = [ log((R_f dR_f)^T R_{f+1})^v ; t_{f+1} - t_f - dt_f ],   L_f = diag(1 / (sigma_rot^2 D_f) x3, 1 / (sigma_trans^2 D_f) x3)
+ *  E_f is aar_track's frame error (double residuals, Huber weights with the problem's current delta when with_huber); the prior is never
+ *  Huber-weighted.  D_f = frame_time[f+1] - frame_time[f] (1 when frame_time is NULL): pass frame ids or time stamps, so that a hole in the
+ *  recording is bridged more loosely than one frame step.  (dR_f, dt_f) = rel_motion[f] as (rvec, t), the expected motion from f to f+1
+ *  (NULL: none, a random walk on the pose); feeding the relative motions of a previous pass gives constant-velocity behaviour.
+ *  The LM is SparseLevMarq's (mu_0 = tau max diag H, the gain test, mu *= v / v *= 5 with at most five retries, exits 1 / 2 / 3 with
+ *  rows = 8 num_obs + 6 (num_frames - 1)); every try solves the block-tridiagonal (H + mu I) delta = b by block cyclic reduction.  A frame
+ *  without detections is carried by its neighbours.  Results are bit-reproducible from call to call.
+ *  Structs are size-versioned: the caller sets struct_size, fields beyond it read as NULL / are not written.
+ *  On a problem with a communicator both calls return AAR_ERR_UNSUPPORTED on every rank (the chain crosses shard boundaries).  Leaves no
+ *  LM state behind (as aar_track). */
+typedef struct aar_smooth_params {
+    uint32_t struct_size;
+    double sigma_rot;            /* rad   per sqrt(unit of frame_time), > 0 finite */
+    double sigma_trans;          /* metre per sqrt(unit of frame_time), > 0 finite */
+    const double *frame_time;    /* [num_frames] strictly ascending, finite; NULL = 0,1,2,... */
+    const double *rel_motion;    /* [num_frames-1][6] expected (rvec, t) from f to f+1; NULL = none */
+} aar_smooth_params;
+typedef struct aar_smooth_report {
+    uint32_t struct_size;
+    int32_t iterations, stop_code, rejected_tries;
+    double initial_cost, final_cost, final_data_cost, final_prior_cost, final_mu, seconds;
+} aar_smooth_report;
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the sigma or the index in frame_time / rel_motion. */
+int aar_smooth_params_validate(int32_t num_frames, const aar_smooth_params *);
+/* x_full in/out (only the frame poses move).  NULL aar_lm_params: the defaults.  frame_err [num_frames]: E_f at the result, pair_err
+ * [num_frames-1]: e_f^T L_f e_f at the result, report: each may be NULL. */
+int aar_track_smooth(aar_problem *, double *x_full, const aar_lm_params *, const aar_smooth_params *, double *frame_err, double *pair_err,
+                     aar_smooth_report *report);
+/* The system of one try at x_full, for checking: diag [num_frames][36] = H_ff, off [num_frames-1][36] = H_{f,f+1} (row-major, rows: frame f),
+ * rhs [6 num_frames] = b, delta [6 num_frames] = the solution of (H + mu I) delta = b by the device's reduction (AAR_ERR_NUMERIC on a
+ * non-positive pivot), cost = {sum_f E_f, sum_f e_f^T L_f e_f}.  Every output may be NULL. */
+int aar_track_smooth_system(aar_problem *, const double *x_full, const aar_smooth_params *, double mu, double *diag, double *off, double *rhs,
+                            double *delta, double cost[2]);
+
 /* per-stage device time of the last aar_lm_solve, seconds, in the reference's verbose-timer vocabulary
  * (libs/sparselevmarq.h:425) extended with the stages that only exist here */
 typedef struct aar_stage_times {
