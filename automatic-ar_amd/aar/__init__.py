@@ -39,7 +39,10 @@ SYMBOLS = [
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system",
+    "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
+    "aar_tracker_reset", "aar_tracker_destroy",
 ]
+TRACKER_MAX_LAG = 15
 NUM_KERNELS = 18
 PRIOR_CAMERA, PRIOR_MARKER = 0, 1
 PRIOR_KINDS = {"camera": PRIOR_CAMERA, "marker": PRIOR_MARKER}
@@ -221,6 +224,41 @@ def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, 
     _check(lib().aar_smooth_params_validate(int(num_frames), C.byref(sp.c)))
 
 
+class CTrackerParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("lag", C.c_int32), ("smooth", C.c_int32), ("sigma_rot", C.c_double), ("sigma_trans", C.c_double),
+                ("with_huber", C.c_int32), ("huber_delta", C.c_float), ("max_obs_per_frame", C.c_int32), ("device_id", C.c_int32)]
+
+
+class CTrackerResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("frame_index", C.c_int64), ("window_frames", C.c_int32), ("iterations", C.c_int32),
+                ("stop_code", C.c_int32), ("rejected_tries", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("final_data_cost", C.c_double), ("final_prior_cost", C.c_double), ("final_mu", C.c_double), ("pose", C.c_double * 6),
+                ("has_lagged", C.c_int32), ("lagged_index", C.c_int64), ("lagged_pose", C.c_double * 6), ("seconds", C.c_double)]
+
+
+def tracker_params(lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None, device=0,
+                   struct_size=None):
+    """aar_tracker_params from Python values (None = the library's default)"""
+    p = CTrackerParams()
+    lib().aar_tracker_default_params(C.byref(p))
+    p.lag, p.smooth, p.sigma_rot, p.sigma_trans = int(lag), int(smooth), float(sigma_rot), float(sigma_trans)
+    p.with_huber, p.device_id = int(bool(with_huber)), int(device)
+    if huber_delta is not None:
+        p.huber_delta = float(huber_delta)
+    if max_obs_per_frame is not None:
+        p.max_obs_per_frame = int(max_obs_per_frame)
+    if struct_size is not None:
+        p.struct_size = int(struct_size)
+    return p
+
+
+def tracker_params_validate(ds, **kw):
+    """aar_tracker_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
+    c = ds.as_c()
+    p = tracker_params(**kw)
+    _check(lib().aar_tracker_params_validate(C.byref(c), C.byref(p)))
+
+
 class CLmIter(C.Structure):
     _fields_ = [("err", C.c_double), ("mu", C.c_double), ("gain", C.c_double), ("delta_norm", C.c_double),
                 ("accepted", C.c_int32), ("tries", C.c_int32)]
@@ -341,6 +379,16 @@ def lib():
     L.aar_smooth_params_validate.argtypes = [C.c_int32, C.POINTER(CSmoothParams)]
     L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothReport)]
     L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_double, dp, dp, dp, dp, dp]
+    L.aar_tracker_default_params.argtypes = [C.POINTER(CTrackerParams)]
+    L.aar_tracker_default_params.restype = None
+    L.aar_tracker_params_validate.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerParams)]
+    L.aar_tracker_create.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerParams), C.POINTER(CLmParams), C.POINTER(C.c_void_p)]
+    L.aar_tracker_push.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), dp,
+                                   C.POINTER(CTrackerResult)]
+    L.aar_tracker_window.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.aar_tracker_reset.argtypes = [C.c_void_p]
+    L.aar_tracker_destroy.argtypes = [C.c_void_p]
+    L.aar_tracker_destroy.restype = None
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.aar_local_group_destroy.argtypes = [C.c_void_p]
     L.aar_local_group_destroy.restype = None
@@ -798,6 +846,67 @@ def residual_report_write_yaml(path, ds, rr, det_err=True):
     r = _report_c(rr.report)
     _check(lib().aar_residual_report_write_yaml(path.encode(), C.byref(c), _dptr(cs), _dptr(ms), _dptr(e) if det_err else None,
                                                 _u8ptr(k) if det_err else None, C.byref(r)))
+
+
+class Tracker:
+    """aar_tracker: the live tracker.  Built from a solution data set (its cameras, markers, cam_mats, marker_size and
+    roots; its frames are ignored) and fed one frame per push."""
+
+    def __init__(self, ds, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
+                 device=0, params=None):
+        """params: aar_lm_params (lm_default_params(...)) or None for the defaults"""
+        self.ds = ds
+        self._cds = ds.as_c()
+        self.prm = tracker_params(lag, smooth, sigma_rot, sigma_trans, with_huber, huber_delta, max_obs_per_frame, device)
+        self.handle = C.c_void_p()
+        _check(lib().aar_tracker_create(C.byref(self._cds), C.byref(self.prm), C.byref(params) if params is not None else None,
+                                        C.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            lib().aar_tracker_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def push(self, frame_time, obs_cam, obs_marker, obs_uv, pose_init=None):
+        """aar_tracker_push: one frame's detections (camera / marker INDICES, undistorted corners [n, 8]).  Returns a dict of the
+        aar_tracker_result fields (pose, lagged_pose as arrays; lagged_pose None until the window is full)."""
+        cam = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+        mk = np.ascontiguousarray(obs_marker, dtype=np.int32).reshape(-1)
+        uv = np.ascontiguousarray(obs_uv, dtype=np.float32).reshape(-1)
+        n = len(cam)
+        assert len(mk) == n and len(uv) == 8 * n
+        init = None if pose_init is None else np.ascontiguousarray(pose_init, dtype=np.float64).reshape(6)
+        r = CTrackerResult()
+        r.struct_size = C.sizeof(CTrackerResult)
+        ip = C.POINTER(C.c_int32)
+        _check(lib().aar_tracker_push(self.handle, float(frame_time), n, cam.ctypes.data_as(ip), mk.ctypes.data_as(ip),
+                                      uv.ctypes.data_as(C.POINTER(C.c_float)), _dptr(init) if init is not None else None, C.byref(r)))
+        out = {k: getattr(r, k) for k, _ in CTrackerResult._fields_ if k not in ("struct_size", "pose", "lagged_pose")}
+        out["pose"] = np.array(r.pose[:])
+        out["lagged_pose"] = np.array(r.lagged_pose[:]) if r.has_lagged else None
+        return out
+
+    def window(self):
+        """aar_tracker_window: dict(n, frame_index [n], poses [n, 6], frame_err [n], pair_err [n] (entry i: the pair that ends at window
+        frame i; entry 0 the anchor pair), anchor_pose [6] or None)"""
+        cap = TRACKER_MAX_LAG + 1
+        n, has = C.c_int32(0), C.c_int32(0)
+        idx = np.zeros(cap, dtype=np.int64)
+        poses, fe, pe, anchor = np.zeros((cap, 6)), np.zeros(cap), np.zeros(cap), np.zeros(6)
+        _check(lib().aar_tracker_window(self.handle, C.byref(n), idx.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(poses), _dptr(fe), _dptr(pe),
+                                        _dptr(anchor), C.byref(has)))
+        w = n.value
+        return dict(n=w, frame_index=idx[:w].copy(), poses=poses[:w].copy(), frame_err=fe[:w].copy(), pair_err=pe[:w].copy(),
+                    anchor_pose=anchor if has.value else None)
+
+    def reset(self):
+        _check(lib().aar_tracker_reset(self.handle))
 
 
 class Problem:

@@ -2929,4 +2929,262 @@ int aar_get_stage_times(aar_problem *pb, aar_stage_times *t) {
     return AAR_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Live tracker (live_kernels.hip): one frame per push, the window's LM in one launch
+// ------------------------------------------------------------------------------------------------
+struct aar_tracker {
+    aar_tracker_params prm;
+    aar_lm_params lm;
+    int C = 0, M = 0, device = 0;
+    hipStream_t stream = nullptr;
+    double *d_ent = nullptr, *d_K = nullptr;
+    double *d_state = nullptr;       // zslot [16][6] | anchor [6] + 2 idle | Ef [16] | Pe [16] | result record
+    char *d_ring = nullptr;          // [lag + 1] slots
+    char *h_stage = nullptr;         // pinned: one slot
+    double *h_res = nullptr;         // pinned: the result record
+    size_t slot_bytes = 0;
+    double half_size = 0;
+    int64_t n = 0;                   // pushes accepted
+    double times[LIVE_MAX_W];        // by ring slot
+    int cnt[LIVE_MAX_W];
+};
+
+namespace {
+
+constexpr int LIVE_ST_ANCHOR = 6 * LIVE_MAX_W, LIVE_ST_EF = LIVE_ST_ANCHOR + 8, LIVE_ST_PE = LIVE_ST_EF + LIVE_MAX_W, LIVE_ST_RES = LIVE_ST_PE + LIVE_MAX_W,
+              LIVE_ST_DOUBLES = LIVE_ST_RES + LIVE_RES_DOUBLES;
+
+// the caller's struct read up to its struct_size, the rest at the defaults; false: too short to hold lag and smooth
+bool tracker_params_read(const aar_tracker_params *in, aar_tracker_params *out) {
+    aar_tracker_default_params(out);
+    if (in->struct_size < offsetof(aar_tracker_params, smooth) + sizeof(int32_t)) return false;
+    memcpy(out, in, std::min<size_t>(in->struct_size, sizeof *out));
+    out->struct_size = (uint32_t)sizeof *out;
+    return true;
+}
+
+}  // namespace
+
+void aar_tracker_default_params(aar_tracker_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof *p;
+    p->huber_delta = 2.5f;
+    p->max_obs_per_frame = 256;
+}
+
+int aar_tracker_params_validate(const aar_dataset *sol, const aar_tracker_params *in) {
+    if (!sol || !in) return set_error(AAR_ERR_INVALID, "aar_tracker_params_validate: null argument");
+    aar_tracker_params p;
+    if (!tracker_params_read(in, &p)) return set_error(AAR_ERR_INVALID, "aar_tracker_params: struct_size %u does not reach lag / smooth", (unsigned)in->struct_size);
+    if (p.lag < 0 || p.lag > AAR_TRACKER_MAX_LAG) return set_error(AAR_ERR_INVALID, "aar_tracker_params: lag = %d is outside 0 .. %d", (int)p.lag, AAR_TRACKER_MAX_LAG);
+    if (p.smooth != 0 && p.smooth != 1) return set_error(AAR_ERR_INVALID, "aar_tracker_params: smooth = %d must be 0 or 1", (int)p.smooth);
+    if (!p.smooth && p.lag > 0) return set_error(AAR_ERR_INVALID, "aar_tracker_params: lag = %d needs smooth = 1 (without a prior every frame stands alone)", (int)p.lag);
+    if (p.smooth) {
+        if (!(p.sigma_rot > 0.0) || !std::isfinite(p.sigma_rot)) return set_error(AAR_ERR_INVALID, "aar_tracker_params: sigma_rot = %g must be positive and finite", p.sigma_rot);
+        if (!(p.sigma_trans > 0.0) || !std::isfinite(p.sigma_trans)) return set_error(AAR_ERR_INVALID, "aar_tracker_params: sigma_trans = %g must be positive and finite", p.sigma_trans);
+    }
+    if (p.with_huber && (!(p.huber_delta > 0.f) || !std::isfinite(p.huber_delta)))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_params: huber_delta = %g must be positive and finite", (double)p.huber_delta);
+    if (p.max_obs_per_frame < 1 || p.max_obs_per_frame > (1 << 20))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_params: max_obs_per_frame = %d is outside 1 .. %d", (int)p.max_obs_per_frame, 1 << 20);
+    const int C = sol->num_cams, M = sol->num_markers;
+    if (C < 1 || M < 1 || (int64_t)C + M >= 32768) return set_error(AAR_ERR_INVALID, "aar_tracker: solution with %d cameras / %d markers", C, M);
+    if (sol->root_cam < 0 || sol->root_cam >= C || sol->root_marker < 0 || sol->root_marker >= M)
+        return set_error(AAR_ERR_INVALID, "aar_tracker: solution root_cam = %d / root_marker = %d out of range", (int)sol->root_cam, (int)sol->root_marker);
+    if (!sol->cam_mats || (C + M > 2 && !sol->x_full)) return set_error(AAR_ERR_INVALID, "aar_tracker: solution without cam_mats / x_full");
+    if (!(sol->marker_size > 0.0) || !std::isfinite(sol->marker_size)) return set_error(AAR_ERR_INVALID, "aar_tracker: solution marker_size = %g must be positive and finite", sol->marker_size);
+    for (int i = 0; i < 9 * C; i++)
+        if (!std::isfinite(sol->cam_mats[i])) return set_error(AAR_ERR_INVALID, "aar_tracker: solution cam_mats[%d][%d] is not finite", i / 9, i % 9);
+    for (int i = 0; i < 6 * (C - 1) + 6 * (M - 1); i++)
+        if (!std::isfinite(sol->x_full[i])) return set_error(AAR_ERR_INVALID, "aar_tracker: solution x_full[%d] (a camera / marker pose) is not finite", i);
+    return AAR_OK;
+}
+
+void aar_tracker_destroy(aar_tracker *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    if (t->stream) (void)hipStreamSynchronize(t->stream);
+    if (t->d_ent) (void)hipFree(t->d_ent);
+    if (t->d_K) (void)hipFree(t->d_K);
+    if (t->d_state) (void)hipFree(t->d_state);
+    if (t->d_ring) (void)hipFree(t->d_ring);
+    if (t->h_stage) (void)hipHostFree(t->h_stage);
+    if (t->h_res) (void)hipHostFree(t->h_res);
+    if (t->stream) (void)hipStreamDestroy(t->stream);
+    delete t;
+}
+
+int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, const aar_lm_params *lm, aar_tracker **out) {
+    if (!sol || !in || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_create: null argument");
+    *out = nullptr;
+    int rc = aar_tracker_params_validate(sol, in);
+    if (rc) return rc;
+    aar_tracker_params p;
+    (void)tracker_params_read(in, &p);
+    if ((rc = ensure_device(p.device_id))) return rc;
+    aar_tracker *t = new aar_tracker();
+    t->prm = p;
+    if (lm) t->lm = *lm; else aar_lm_default_params(&t->lm);
+    t->C = sol->num_cams; t->M = sol->num_markers; t->device = p.device_id;
+    t->half_size = (double)((float)sol->marker_size / 2.f);
+    t->slot_bytes = live_slot_bytes(p.max_obs_per_frame);
+    const int C = t->C, M = t->M, A = C + M;
+    double *d_z = nullptr;
+    auto fail = [&](int code) { if (d_z) (void)hipFree(d_z); aar_tracker_destroy(t); return code; };
+    if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipStreamCreate failed"));
+    if (hipMalloc((void **)&t->d_ent, (size_t)A * ENT_STRIDE * sizeof(double)) != hipSuccess || hipMalloc((void **)&t->d_K, (size_t)9 * C * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&t->d_state, LIVE_ST_DOUBLES * sizeof(double)) != hipSuccess || hipMalloc((void **)&t->d_ring, (size_t)(p.lag + 1) * t->slot_bytes) != hipSuccess ||
+        hipMalloc((void **)&d_z, (size_t)6 * A * sizeof(double)) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMalloc failed"));
+    if (hipHostMalloc((void **)&t->h_stage, t->slot_bytes, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&t->h_res, LIVE_RES_DOUBLES * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipHostMalloc failed"));
+    if (hipMemsetAsync(t->d_state, 0, LIVE_ST_DOUBLES * sizeof(double), t->stream) != hipSuccess ||
+        hipMemsetAsync(t->d_ring, 0, (size_t)(p.lag + 1) * t->slot_bytes, t->stream) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMemset failed"));
+    // the entity rows of the fixed cameras and markers, by the problem's own unpack kernel (roots: the identity)
+    PoseLayout L;
+    L.C = C; L.M = M; L.F = 0; L.rc = sol->root_cam; L.rm = sol->root_marker;
+    std::vector<double> z((size_t)6 * A, 0.0);
+    for (int c = 0; c < C; c++)
+        if (c != L.rc) memcpy(&z[6 * (size_t)c], sol->x_full + L.full_cam0() + 6LL * L.cam_slot(c), 6 * sizeof(double));
+    for (int m = 0; m < M; m++)
+        if (m != L.rm) memcpy(&z[6 * (size_t)(C + m)], sol->x_full + L.full_mk0() + 6LL * L.mk_slot(m), 6 * sizeof(double));
+    const char *what = "";
+    if (h2d(d_z, z.data(), z.size() * sizeof(double), t->stream, &what) || h2d(t->d_K, sol->cam_mats, (size_t)9 * C * sizeof(double), t->stream, &what))
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: %s failed", what));
+    DeviceProblem P;
+    P.C = C; P.M = M; P.A = A; P.F = 0; P.intr = 0;
+    P.z[0] = d_z; P.ent[0] = t->d_ent;
+    launch_unpack(P, 0, t->stream);
+    if (hipStreamSynchronize(t->stream) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: the unpack launch failed"));
+    (void)hipFree(d_z);
+    d_z = nullptr;
+    if ((rc = check_async("tracker creation"))) return fail(rc);
+    *out = t;
+    return AAR_OK;
+}
+
+int aar_tracker_reset(aar_tracker *t) {
+    if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_reset: null argument");
+    t->n = 0;
+    return AAR_OK;
+}
+
+int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker, const float *obs_uv,
+                     const double *pose_init, aar_tracker_result *result) {
+    if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_push: null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    const aar_tracker_params &p = t->prm;
+    const int slots = p.lag + 1;
+    const int64_t n = t->n;
+    if (n_obs < 0 || n_obs > p.max_obs_per_frame)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_push: n_obs = %d is outside 0 .. max_obs_per_frame = %d", (int)n_obs, (int)p.max_obs_per_frame);
+    if (n_obs > 0 && (!obs_cam || !obs_marker || !obs_uv)) return set_error(AAR_ERR_INVALID, "aar_tracker_push: null observation array");
+    for (int o = 0; o < n_obs; o++) {
+        if (obs_cam[o] < 0 || obs_cam[o] >= t->C) return set_error(AAR_ERR_INVALID, "aar_tracker_push: obs_cam[%d] = %d is outside 0 .. %d", o, (int)obs_cam[o], t->C - 1);
+        if (obs_marker[o] < 0 || obs_marker[o] >= t->M) return set_error(AAR_ERR_INVALID, "aar_tracker_push: obs_marker[%d] = %d is outside 0 .. %d", o, (int)obs_marker[o], t->M - 1);
+    }
+    if (!std::isfinite(frame_time)) return set_error(AAR_ERR_INVALID, "aar_tracker_push: frame_time is not finite");
+    const int ns = (int)(n % slots), ps = (int)((n + slots - 1) % slots);
+    if (n > 0 && (!(frame_time > t->times[ps]) || !std::isfinite(frame_time - t->times[ps])))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_push: frame_time = %g does not ascend from the previous push's %g", frame_time, t->times[ps]);
+    if (n == 0 && !pose_init) return set_error(AAR_ERR_INVALID, "aar_tracker_push: the first push needs a pose_init");
+    if (pose_init)
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(pose_init[k])) return set_error(AAR_ERR_INVALID, "aar_tracker_push: pose_init[%d] is not finite", k);
+    HIP_TRY(hipSetDevice(t->device));
+    // the frame's slot: header | records, staged in page-locked memory
+    double *hdr = reinterpret_cast<double *>(t->h_stage);
+    for (int k = 0; k < 8; k++) hdr[k] = (pose_init && k < 6) ? pose_init[k] : 0.0;
+    for (int o = 0; o < n_obs; o++) {
+        char *rec = t->h_stage + LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * o;
+        ObsIdx id;
+        id.frame = 0; id.cam = obs_cam[o]; id.marker = t->C + obs_marker[o]; id.slots = 0;
+        memcpy(rec, &id, sizeof id);
+        memcpy(rec + sizeof id, obs_uv + 8 * (size_t)o, 8 * sizeof(float));
+    }
+    const int W = (int)std::min<int64_t>(n + 1, slots);
+    const bool has_anchor = n - slots >= 0;
+    LiveArgs a;
+    a.ent = t->d_ent; a.Kmat = t->d_K; a.ring = t->d_ring; a.slot_bytes = t->slot_bytes;
+    a.zslot = t->d_state; a.anchor = t->d_state + LIVE_ST_ANCHOR; a.Ef = t->d_state + LIVE_ST_EF; a.Pe = t->d_state + LIVE_ST_PE; a.res = t->d_state + LIVE_ST_RES;
+    a.huber = p.with_huber ? p.huber_delta : -1.f;
+    a.h = t->half_size;
+    a.max_iters = t->lm.max_iters; a.min_error = t->lm.min_error; a.min_step_error_diff = t->lm.min_step_error_diff;
+    a.min_average_step_error_diff = t->lm.min_average_step_error_diff; a.tau = t->lm.tau;
+    a.W = W; a.slots = slots; a.first_slot = (int)((n + 1 - W) % slots);
+    a.has_anchor = has_anchor ? 1 : 0; a.smooth = p.smooth; a.has_init = pose_init ? 1 : 0;
+    int64_t det = 0;
+    for (int i = 0; i < LIVE_MAX_W; i++) { a.cnt[i] = 0; a.lam[i][0] = a.lam[i][1] = 0.0; }
+    for (int i = 0; i < W; i++) {
+        const int sl = (a.first_slot + i) % slots;
+        const bool newest = i == W - 1;
+        a.cnt[i] = newest ? n_obs : t->cnt[sl];
+        det += a.cnt[i];
+        const double ti = newest ? frame_time : t->times[sl];
+        double tp = 0.0;
+        bool pair = false;
+        if (i > 0) { tp = t->times[(a.first_slot + i - 1) % slots]; pair = true; }
+        else if (has_anchor) { tp = t->times[ns]; pair = true; }   // the anchor's time still sits in the slot the new frame takes
+        if (pair && p.smooth) {
+            const double dt = ti - tp;
+            a.lam[i][0] = 1.0 / (p.sigma_rot * p.sigma_rot * dt);
+            a.lam[i][1] = 1.0 / (p.sigma_trans * p.sigma_trans * dt);
+        }
+    }
+    a.rows = 8.0 * (double)det + (p.smooth ? 6.0 * (double)(W - 1 + (has_anchor ? 1 : 0)) : 0.0);
+    HIP_TRY(hipMemcpyAsync(t->d_ring + (size_t)ns * t->slot_bytes, t->h_stage, LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * n_obs, hipMemcpyHostToDevice, t->stream));
+    launch_live_push(a, t->stream);
+    HIP_TRY(hipMemcpyAsync(t->h_res, a.res, LIVE_RES_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    int rc = check_async("k_live_push");
+    if (rc) return rc;
+    // the push is accepted: the frame that leaves the window hands its slot to the new one
+    t->times[ns] = frame_time;
+    t->cnt[ns] = n_obs;
+    t->n = n + 1;
+    if (result) {
+        aar_tracker_result r;
+        memset(&r, 0, sizeof r);
+        const double *h = t->h_res;
+        r.struct_size = result->struct_size;
+        r.frame_index = n; r.window_frames = W;
+        r.iterations = (int32_t)h[0]; r.stop_code = (int32_t)h[1]; r.rejected_tries = (int32_t)h[2];
+        r.initial_cost = h[3]; r.final_cost = h[4]; r.final_data_cost = h[5]; r.final_prior_cost = h[6]; r.final_mu = h[7];
+        for (int k = 0; k < 6; k++) { r.pose[k] = h[8 + k]; r.lagged_pose[k] = W == slots ? h[14 + k] : 0.0; }
+        r.has_lagged = W == slots ? 1 : 0;
+        r.lagged_index = W == slots ? n + 1 - W : -1;
+        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        memcpy(result, &r, std::min<size_t>(result->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
+int aar_tracker_window(aar_tracker *t, int32_t *n_out, int64_t *frame_index, double *poses, double *frame_err, double *pair_err, double anchor_pose[6],
+                       int32_t *has_anchor) {
+    if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_window: null argument");
+    const int slots = t->prm.lag + 1;
+    const int W = (int)std::min<int64_t>(t->n, slots);
+    const bool anchored = t->n - 1 - slots >= 0;
+    if (n_out) *n_out = W;
+    if (has_anchor) *has_anchor = anchored ? 1 : 0;
+    if (frame_index) for (int i = 0; i < W; i++) frame_index[i] = t->n - W + i;
+    if (W == 0 || (!poses && !frame_err && !pair_err && !anchor_pose)) return AAR_OK;
+    HIP_TRY(hipSetDevice(t->device));
+    double st[LIVE_ST_RES];
+    const char *what = "";
+    if (d2h(st, t->d_state, sizeof st, t->stream, &what)) return set_error(AAR_ERR_HIP, "aar_tracker_window: %s failed", what);
+    for (int i = 0; i < W; i++) {
+        const int sl = (int)((t->n - W + i) % slots);
+        if (poses) memcpy(poses + 6 * (size_t)i, st + 6 * sl, 6 * sizeof(double));
+        if (frame_err) frame_err[i] = st[LIVE_ST_EF + i];
+        if (pair_err) pair_err[i] = st[LIVE_ST_PE + i];
+    }
+    if (anchor_pose) for (int k = 0; k < 6; k++) anchor_pose[k] = anchored ? st[LIVE_ST_ANCHOR + k] : 0.0;
+    return AAR_OK;
+}
+
 }  // extern "C"

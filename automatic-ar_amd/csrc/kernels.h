@@ -307,6 +307,31 @@ void smooth_work_carve(SmoothWork &w, double *base, int F);
 void launch_smooth_eval(const DeviceProblem &P, int which, const SmoothWork &w, int cur, bool with_j, hipStream_t st);   // two launches
 int launch_smooth_solve(const SmoothWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
 
+// live tracker (live_kernels.hip): one frame per push, the whole LM of the window in ONE launch of one workgroup
+constexpr int LIVE_MAX_W = 16;            // window frames (AAR_TRACKER_MAX_LAG + 1)
+constexpr int LIVE_HDR_BYTES = 64;        // a ring slot starts with the frame's header: pose_init [6] | 2 idle doubles
+constexpr int LIVE_REC_BYTES = 48;        // ... followed by its records: ObsIdx (16 bytes) | eight corner coordinates (32 bytes)
+constexpr int LIVE_RES_DOUBLES = 24;      // the result record: iterations, stop code, rejected tries, initial / final / data / prior cost, mu,
+                                          // the newest pose [8..13], the oldest window pose [14..19], tries, 0
+inline size_t live_slot_bytes(int max_obs) { return LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * (size_t)max_obs; }
+struct LiveArgs {
+    const double *ent, *Kmat;             // [A][ENT_STRIDE] rows of the fixed cameras and markers, [C][9]
+    const char *ring;                     // [lag + 1] slots of slot_bytes
+    size_t slot_bytes;
+    double *zslot;                        // [lag + 1][6] pose of the frame in each ring slot
+    double *anchor;                       // [6] the frame that left the window last
+    double *Ef, *Pe;                      // [LIVE_MAX_W] by window position: data cost, cost of the pair that ENDS at the frame (position 0: the anchor pair)
+    double *res;                          // [LIVE_RES_DOUBLES]
+    float huber; double h;
+    int max_iters; double min_error, min_step_error_diff, min_average_step_error_diff, tau;
+    int W, slots, first_slot;             // window frames, ring slots (lag + 1), slot of the oldest window frame (the others follow, modulo slots)
+    int has_anchor, smooth, has_init;     // has_init: the new frame starts from its header's pose, else from the previous frame's estimate
+    double rows;                          // 8 detections of the window + 6 pairs
+    int cnt[LIVE_MAX_W];                  // detections by window position
+    double lam[LIVE_MAX_W][2];            // by window position: 1 / (sigma_rot^2 dt), 1 / (sigma_trans^2 dt) of the pair that ends there
+};
+void launch_live_push(const LiveArgs &a, hipStream_t st);   // ONE launch
+
 // covariance (cov_kernels.hip): S (stride n_pad) -> S2 (stride n2 >= n_pad, zero beyond n_pad), rows with rowmask set -> identity
 void launch_cov_stage(const double *S, int n_pad, double *S2, int n2, const int32_t *rowmask, hipStream_t st);
 // the LDL^T factor launch_chol left for S2 (nT2 tiles, fused_m = the panel rule it ran with) -> Sinv = S^-1, lower 32 x 32 tiles of the first

@@ -1,0 +1,340 @@
+// Live tracker: frames arrive one per push; the last lag + 1 of them (the window) are refined together, the frame that
+// left the window last (the anchor) is held fixed,
+//
+//   E = sum_{f in window} E_f(z_f) + sum_{f, f+1 in window} e_f^T L_f e_f + [anchor] e_a^T L_a e_a,   e_a = e(z_anchor, z_first)
+//
+// with E_f track()'s frame error (track_eval.hpp) and e_f, L_f the smoothed tracker's between factor (pair_terms.hpp).  smooth = 0 drops every
+// prior: the window is one frame and the loop is k_track's.
+//
+// k_live_push runs the WHOLE LM of one push in ONE workgroup of four wavefronts; the phases are separated by workgroup barriers and hand
+// over through LDS:
+//   assembly   wavefront w takes the window frames w, w + 4, ...: V_f, g_f, E_f by track_eval, then the between factors of the pair that
+//              ends at the frame (its J_b half; for the first frame that is the anchor pair) and of the pair that starts there (its J_a half
+//              and the off-diagonal block) -> H_ff, H_{f,f+1}, b_f, the costs
+//   solve      wavefront 0, every lane the same registers: (H + mu I) delta = b by sequential block elimination, pivots inverted by
+//              spd6_inverse; a non-positive pivot sets the flag
+//   trial      the costs at z + delta, |delta_f|^2 and delta_f . b_f per frame
+//   decide     every thread adds the per-frame values in window order and takes the same accept / mu / exit decision
+// No atomics; every sum has one owner and a fixed order, so two trackers fed the same pushes give the same bits.
+#include "geom.hpp"
+#include "kernels.h"
+#include "pair_terms.hpp"
+#include "track_eval.hpp"
+
+namespace aar {
+
+namespace {
+
+struct LiveShared {
+    double D[LIVE_MAX_W][36], O[LIVE_MAX_W][36], inv[LIVE_MAX_W][36];   // H_ff, H_{f,f+1}, the inverted pivots of the last solve
+    double b[LIVE_MAX_W][6], c[LIVE_MAX_W][6], dl[LIVE_MAX_W][6];       // b_f, the eliminated right-hand side, the step
+    double z[LIVE_MAX_W][6], zt[LIVE_MAX_W][6];                         // the current point and the trial point
+    double Ef[2][LIVE_MAX_W], Pe[2][LIVE_MAX_W];                        // costs of the two points; Pe[.][i]: the pair that ends at frame i
+    double lin[LIVE_MAX_W][2];                                          // |delta_f|^2, delta_f . b_f
+    double za[6];                                                       // the anchor
+    int flag;                                                           // a non-positive pivot in the last solve
+};
+
+__device__ __forceinline__ const char *live_slot(const LiveArgs &a, int i) {
+    int s = a.first_slot + i;
+    if (s >= a.slots) s -= a.slots;
+    return a.ring + (size_t)s * a.slot_bytes;
+}
+
+// WITH_J: H, b and the costs at s.z; else the costs at s.z + s.dl (-> s.zt) with the linear model's sums
+template <bool WITH_J>
+__device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta, LiveShared &s, int wv, int lane) {
+    const int W = a.W, out = WITH_J ? 0 : 1;
+    for (int i = wv; i < W; i += 4) {
+        double zc[6], rowc[ENT_STRIDE];
+        ld6(s.z[i], zc);
+        if (!WITH_J) {
+            double d[6];
+            ld6(s.dl[i], d);
+            double d2 = 0.0, dg = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                zc[k] += d[k];
+                d2 += d[k] * d[k];
+                dg += d[k] * s.b[i][k];
+            }
+            if (lane < 6) s.zt[i][lane] = s.z[i][lane] + s.dl[i][lane];
+            if (lane == 0) { s.lin[i][0] = d2; s.lin[i][1] = dg; }
+        }
+        make_ent_row(zc, rowc);
+        double V[21], g[6];
+        const char *rec = live_slot(a, i) + LIVE_HDR_BYTES;
+        const double Ef = track_eval_range<WITH_J, LIVE_REC_BYTES, LIVE_REC_BYTES>(ta, rec, rec + sizeof(ObsIdx), 0, a.cnt[i], zc, lane, V, g);
+        double D[6][6], b[6];
+        if (WITH_J) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                b[k] = g[k];   // track_eval's g is already -J^T r_w
+#pragma unroll
+                for (int j = 0; j < 6; j++) D[k][j] = V[sym6(k, j)];
+            }
+        }
+        // the pair that ends here: this frame is its b side; for the first window frame the a side is the anchor, a constant
+        double Pe = 0.0;
+        if (a.smooth && (i > 0 || a.has_anchor)) {
+            double zp[6], rowp[ENT_STRIDE];
+            if (i > 0) {
+                ld6(s.z[i - 1], zp);
+                if (!WITH_J) {
+#pragma unroll
+                    for (int k = 0; k < 6; k++) zp[k] += s.dl[i - 1][k];
+                }
+            } else {
+                ld6(s.za, zp);
+            }
+            make_ent_row(zp, rowp);
+            double phi[3], et[3], Ma[9], Mb[9];
+            pair_terms<WITH_J>(rowp, rowc, nullptr, phi, et, Ma, Mb);
+            const double lr = a.lam[i][0], lt = a.lam[i][1];
+            Pe = lr * (phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]) + lt * (et[0] * et[0] + et[1] * et[1] + et[2] * et[2]);
+            if (WITH_J) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+#pragma unroll
+                    for (int j = 0; j < 3; j++) D[k][j] += lr * (Mb[k] * Mb[j] + Mb[3 + k] * Mb[3 + j] + Mb[6 + k] * Mb[6 + j]);
+                    D[3 + k][3 + k] += lt;
+                    b[k] -= lr * (Mb[k] * phi[0] + Mb[3 + k] * phi[1] + Mb[6 + k] * phi[2]);
+                    b[3 + k] -= lt * et[k];
+                }
+            }
+        }
+        // the pair that starts here: its a side and the off-diagonal block
+        if (WITH_J && a.smooth && i + 1 < W) {
+            double zn[6], rown[ENT_STRIDE];
+            ld6(s.z[i + 1], zn);
+            make_ent_row(zn, rown);
+            double phi[3], et[3], Ma[9], Mb[9];
+            pair_terms<true>(rowc, rown, nullptr, phi, et, Ma, Mb);
+            const double lr = a.lam[i + 1][0], lt = a.lam[i + 1][1];
+            double O[36];
+#pragma unroll
+            for (int k = 0; k < 36; k++) O[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+                    D[k][j] += lr * (Ma[k] * Ma[j] + Ma[3 + k] * Ma[3 + j] + Ma[6 + k] * Ma[6 + j]);
+                    O[6 * k + j] = lr * (Ma[k] * Mb[j] + Ma[3 + k] * Mb[3 + j] + Ma[6 + k] * Mb[6 + j]);
+                }
+                D[3 + k][3 + k] += lt;
+                O[6 * (3 + k) + 3 + k] = -lt;
+                b[k] -= lr * (Ma[k] * phi[0] + Ma[3 + k] * phi[1] + Ma[6 + k] * phi[2]);
+                b[3 + k] += lt * et[k];
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 36; k++) s.O[i][k] = O[k];
+            }
+        }
+        if (lane == 0) {
+            s.Ef[out][i] = Ef;
+            s.Pe[out][i] = Pe;
+            if (WITH_J) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    s.b[i][k] = b[k];
+#pragma unroll
+                    for (int j = 0; j < 6; j++) s.D[i][6 * k + j] = D[k][j];
+                }
+            }
+        }
+    }
+}
+
+// (H + mu I) delta = b, block tridiagonal, by one wavefront whose lanes all carry the same values (every lane writes what it later reads):
+//   P_0 = D_0 + mu I,  T_f = O_{f-1}^T P_{f-1}^-1,  P_f = D_f + mu I - T_f O_{f-1},  c_f = b_f - T_f c_{f-1};  x_f = P_f^-1 (c_f - O_f x_{f+1})
+__device__ __forceinline__ void live_solve(LiveShared &s, int W, double mu) {
+    bool ok = true;
+    double inv[36], c[6];
+    for (int f = 0; f < W; f++) {
+        double P[6][6], cn[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            cn[i] = s.b[f][i];
+#pragma unroll
+            for (int k = 0; k < 6; k++) P[i][k] = s.D[f][6 * i + k] + (i == k ? mu : 0.0);
+        }
+        if (f > 0) {
+            double O[36], T[36];
+#pragma unroll
+            for (int i = 0; i < 36; i++) O[i] = s.O[f - 1][i];
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int p = 0; p < 6; p++) t = fma(O[6 * p + i], inv[6 * p + k], t);
+                    T[6 * i + k] = t;
+                }
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+#pragma unroll
+                for (int k = 0; k <= i; k++) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int p = 0; p < 6; p++) t = fma(T[6 * i + p], O[6 * p + k], t);
+                    P[i][k] -= t;
+                    if (k != i) P[k][i] = P[i][k];
+                }
+                double t = 0.0;
+#pragma unroll
+                for (int p = 0; p < 6; p++) t = fma(T[6 * i + p], c[p], t);
+                cn[i] -= t;
+            }
+        }
+        ok = spd6_inverse(P, inv) && ok;
+#pragma unroll
+        for (int i = 0; i < 6; i++) c[i] = cn[i];
+#pragma unroll
+        for (int i = 0; i < 36; i++) s.inv[f][i] = inv[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) s.c[f][i] = c[i];
+    }
+    double x[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; j++) t += inv[6 * i + j] * c[j];
+        x[i] = t;
+        s.dl[W - 1][i] = t;
+    }
+    for (int f = W - 2; f >= 0; f--) {
+        double v[6], xn[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double t = s.c[f][i];
+#pragma unroll
+            for (int p = 0; p < 6; p++) t = fma(-s.O[f][6 * i + p], x[p], t);
+            v[i] = t;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double t = 0.0;
+#pragma unroll
+            for (int p = 0; p < 6; p++) t = fma(s.inv[f][6 * i + p], v[p], t);
+            xn[i] = t;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) { x[i] = xn[i]; s.dl[f][i] = xn[i]; }
+    }
+    s.flag = ok ? 0 : 1;
+}
+
+__global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
+    __shared__ LiveShared s;
+    const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform
+    const int W = a.W;
+    TrackArgs ta;
+    ta.idx = nullptr; ta.uv = nullptr; ta.ent = a.ent; ta.Kmat = a.Kmat; ta.frame_obs_start = nullptr;
+    ta.kstride = 9; ta.A = 0; ta.F = W; ta.huber = a.huber; ta.h = a.h;
+    ta.max_iters = 0; ta.min_error = ta.min_step_error_diff = ta.min_average_step_error_diff = ta.tau = 0.0;
+    ta.z = nullptr; ta.iters_out = nullptr; ta.err_out = nullptr;
+    // the window's poses.  The new frame takes the ring slot of the frame that leaves the window: that pose becomes the anchor before the
+    // slot is overwritten; the new frame starts from its header's pose or from the previous frame's estimate (read before any write)
+    {
+        int ns = a.first_slot + W - 1, ps = a.first_slot + W - 2;
+        if (ns >= a.slots) ns -= a.slots;
+        if (ps >= a.slots) ps -= a.slots;
+        if (ps < 0) ps = ns;   // a window of one frame: the previous frame is the one that leaves
+        if (t < 6) {
+            if (a.has_anchor) {
+                const double av = a.zslot[6 * ns + t];
+                s.za[t] = av;
+                a.anchor[t] = av;
+            }
+            s.z[W - 1][t] = a.has_init ? reinterpret_cast<const double *>(a.ring + (size_t)ns * a.slot_bytes)[t] : a.zslot[6 * ps + t];
+        } else if (t >= 64 && t < 64 + 6 * (W - 1)) {
+            const int i = (t - 64) / 6, k = (t - 64) % 6;
+            int sl = a.first_slot + i;
+            if (sl >= a.slots) sl -= a.slots;
+            s.z[i][k] = a.zslot[6 * sl + k];
+        }
+    }
+    __syncthreads();
+    live_eval<true>(a, ta, s, wv, lane);   // init: the first evaluation also yields the first step's system
+    __syncthreads();
+    double currData = 0.0, currPrior = 0.0;
+    for (int i = 0; i < W; i++) { currData += s.Ef[0][i]; currPrior += s.Pe[0][i]; }
+    double currErr = currData + currPrior, prevErr = currErr;
+    const double initial = currErr, rows = a.rows;
+    double mu = -1.0, v = 2.0;
+    int mustExit = 0, iters = 0, rejected = 0, tries = 0;
+    for (int it = 0; it < a.max_iters && !mustExit && rows > 0; it++) {
+        if (it > 0) {
+            live_eval<true>(a, ta, s, wv, lane);   // H, b at the current point (its costs are those already held)
+            __syncthreads();
+        }
+        if (mu < 0) {
+            double mx = s.D[0][0];
+            for (int i = 0; i < W; i++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) mx = fmax(mx, s.D[i][7 * k]);
+            mu = mx * a.tau;
+        }
+        double gain = 0.0;
+        int ntries = 0;
+        bool accepted = false;
+        do {
+            if (wv == 0) live_solve(s, W, mu);
+            __syncthreads();
+            live_eval<false>(a, ta, s, wv, lane);
+            __syncthreads();
+            double eD = 0.0, eP = 0.0, d2 = 0.0, dg = 0.0;
+            for (int i = 0; i < W; i++) { eD += s.Ef[1][i]; eP += s.Pe[1][i]; d2 += s.lin[i][0]; dg += s.lin[i][1]; }
+            const double err = eD + eP;
+            const bool bad_pivot = a.smooth && s.flag != 0;   // (track() ignores the pivots of its 6x6 solve)
+            const double Lq = 0.5 * (mu * d2 - dg);
+            gain = (err - prevErr) / Lq;
+            tries++;
+            if (!bad_pivot && gain > 0 && (err - prevErr) < 0) {
+                const double q = 2 * gain - 1;
+                mu = mu * fmax(0.33, 1.0 - q * q * q);
+                v = 2.0;
+                currErr = err; currData = eD; currPrior = eP;
+                if (t < 6 * W) s.z[t / 6][t % 6] = s.zt[t / 6][t % 6];
+                if (t >= 128 && t < 128 + W) { s.Ef[0][t - 128] = s.Ef[1][t - 128]; s.Pe[0][t - 128] = s.Pe[1][t - 128]; }
+                accepted = true;
+            } else {
+                if (bad_pivot) gain = 0.0;   // a failed factorisation is a rejected try: more damping, and the retry rule below applies
+                mu = mu * v;
+                v = v * 5;
+                rejected++;
+            }
+            __syncthreads();   // the decision's reads are done before the next solve or assembly writes
+        } while (gain <= 0 && ntries++ < 5 && !accepted);
+        if (currErr < a.min_error) mustExit = 1;
+        if (fabs(prevErr - currErr) <= a.min_step_error_diff || fabs((prevErr - currErr) / rows) <= a.min_average_step_error_diff || !accepted)
+            mustExit = 2;
+        if (currErr > prevErr) mustExit = 3;
+        iters++;
+        prevErr = currErr;
+    }
+    // the window back into the ring's poses, the costs by window position, the result record
+    if (t < 6 * W) {
+        int sl = a.first_slot + t / 6;
+        if (sl >= a.slots) sl -= a.slots;
+        a.zslot[6 * sl + t % 6] = s.z[t / 6][t % 6];
+    }
+    if (t >= 128 && t < 128 + W) { a.Ef[t - 128] = s.Ef[0][t - 128]; a.Pe[t - 128] = s.Pe[0][t - 128]; }
+    if (t >= 192 && t < 198) { a.res[8 + t - 192] = s.z[W - 1][t - 192]; a.res[14 + t - 192] = s.z[0][t - 192]; }
+    if (t == 64) {
+        a.res[0] = (double)iters; a.res[1] = (double)mustExit; a.res[2] = (double)rejected; a.res[3] = initial;
+        a.res[4] = currErr; a.res[5] = currData; a.res[6] = currPrior; a.res[7] = mu;
+        a.res[20] = (double)tries; a.res[21] = 0.0; a.res[22] = 0.0; a.res[23] = 0.0;
+    }
+}
+
+}  // namespace
+
+void launch_live_push(const LiveArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(k_live_push, dim3(1), dim3(256), 0, st, a);
+}
+
+}  // namespace aar

@@ -23,9 +23,13 @@ struct TrackArgs {
     double *err_out;      // [F]
 };
 
-// residual sum (and optionally V (21 packed), g (6)) of one frame at pose zf, summed over the wave
-template <bool WITH_J>
-__device__ __forceinline__ double track_eval(const TrackArgs &a, int f, const double zf[6], int lane, double V[21], double g[6]) {
+// residual sum (and optionally V (21 packed), g (6)) of the observations [o0, o1) at pose zf, summed over the wave.  Observation o has its
+// ObsIdx at idx + o * IDX_STRIDE bytes and its eight corner coordinates at uv + o * UV_STRIDE bytes (16-byte aligned): the problem's
+// two arrays (strides 16 and 32), or the interleaved records of the live tracker's ring (live_kernels.hip).  Reads a.ent, a.Kmat, a.kstride,
+// a.huber, a.h.
+template <bool WITH_J, int IDX_STRIDE, int UV_STRIDE>
+__device__ __forceinline__ double track_eval_range(const TrackArgs &a, const char *idx, const char *uv, int o0, int o1, const double zf[6], int lane,
+                                                   double V[21], double g[6]) {
     double row[ENT_STRIDE];
     make_ent_row(zf, row);
     Ent ef;
@@ -36,11 +40,10 @@ __device__ __forceinline__ double track_eval(const TrackArgs &a, int f, const do
     double acc[28];
 #pragma unroll
     for (int i = 0; i < 28; i++) acc[i] = 0.0;
-    const int o0 = a.frame_obs_start[f], o1 = a.frame_obs_start[f + 1];
     for (int o = o0 + lane; o < o1; o += 64) {
-        const ObsIdx id = a.idx[o];
-        const float4 uv0 = reinterpret_cast<const float4 *>(a.uv)[2 * (int64_t)o];
-        const float4 uv1 = reinterpret_cast<const float4 *>(a.uv)[2 * (int64_t)o + 1];
+        const ObsIdx id = *reinterpret_cast<const ObsIdx *>(idx + (int64_t)o * IDX_STRIDE);
+        const float4 uv0 = reinterpret_cast<const float4 *>(uv + (int64_t)o * UV_STRIDE)[0];
+        const float4 uv1 = reinterpret_cast<const float4 *>(uv + (int64_t)o * UV_STRIDE)[1];
         const float ou[8] = {uv0.x, uv0.y, uv0.z, uv0.w, uv1.x, uv1.y, uv1.z, uv1.w};
         Ent ec, em;
         load_ent(a.ent, id.cam, ec);
@@ -100,6 +103,13 @@ __device__ __forceinline__ double track_eval(const TrackArgs &a, int f, const do
         for (int i = 0; i < 6; i++) g[i] = wave_sum(acc[21 + i]);
     }
     return wave_sum(acc[27]);
+}
+
+// ... of frame f of the problem behind a
+template <bool WITH_J>
+__device__ __forceinline__ double track_eval(const TrackArgs &a, int f, const double zf[6], int lane, double V[21], double g[6]) {
+    return track_eval_range<WITH_J, (int)sizeof(ObsIdx), 32>(a, reinterpret_cast<const char *>(a.idx), reinterpret_cast<const char *>(a.uv),
+                                                             a.frame_obs_start[f], a.frame_obs_start[f + 1], zf, lane, V, g);
 }
 
 }  // namespace aar

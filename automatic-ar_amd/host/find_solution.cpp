@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -200,8 +200,13 @@ int main(int argc, char *argv[]) {
     bool smooth = false;
     double smooth_sigma[2] = {0.0, 0.0};
     int smooth_args = 0;
+    // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
+    // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
+    bool live = false;
+    int live_lag = -1, live_args = 0;
+    double live_sigma[2] = {0.0, 0.0};
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, Smooth } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, Smooth, Live } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -221,6 +226,21 @@ int main(int argc, char *argv[]) {
         else if (a == "-prior-sigma-deg") arg_flag = PriorDeg;
         else if (a == "-prior-sigma-m") arg_flag = PriorM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
+        else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
+        else if (arg_flag == Live) {
+            char *end = nullptr;
+            if (live_args == 0) {
+                const long v = strtol(a.c_str(), &end, 10);
+                if (*end != '\0' || a.empty() || v < 0 || v > AAR_TRACKER_MAX_LAG) return print_usage(argv[0]);
+                live_lag = (int)v;
+                live_args = 1;
+            } else {
+                const double v = strtod(a.c_str(), &end);
+                if (*end != '\0' || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+                live_sigma[live_args++ - 1] = v;
+                if (live_args == 3) arg_flag = NONE;
+            }
+        }
         else if (arg_flag == Smooth) {
             char *end = nullptr;
             const double v = strtod(a.c_str(), &end);
@@ -256,6 +276,7 @@ int main(int argc, char *argv[]) {
         else if (arg_flag == Threshold) { threshold = stod(a); arg_flag = NONE; }
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
+    if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     string name = "";
     if (tracking_only) name += "_tracking_only";
     if (use_subseqs) name += "_subseqs";
@@ -347,6 +368,22 @@ int main(int argc, char *argv[]) {
         }
     }
     const auto start = chrono::system_clock::now();
+    if (live) {
+        try {
+            mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1]);
+            long long its = 0, rej = 0;
+            double sec = 0, cost = 0;
+            for (const aar_tracker_result &r : mcm.live_results) { its += r.iterations; rej += r.rejected_tries; sec += r.seconds; cost += r.final_cost; }
+            cout << "live: " << mcm.live_results.size() << " pushes, lag " << live_lag << ", " << its << " LM iterations (" << rej << " rejected tries), summed cost "
+                 << cost << ", " << (mcm.live_results.empty() ? 0.0 : 1e6 * sec / mcm.live_results.size()) << " us per push" << endl;
+        } catch (const exception &e) {
+            cerr << "live tracking failed: " << e.what() << endl;
+            return 6;
+        }
+        mcm.write_solution_file(final_path);
+        mcm.write_text_solution_file(final_path + ".yaml");
+        return 0;
+    }
     try {
         mcm.solve();
     } catch (const exception &e) {

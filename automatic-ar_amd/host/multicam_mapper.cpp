@@ -566,6 +566,104 @@ void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans) {
     eVec2Mats(io_vec);
 }
 
+// The live loop over the data set's frames (aar_tracker_*): what apps/track.cpp does per incoming frame, with the
+// mapper's own frames as the stream.
+void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double sigma_trans) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::track_live: no data set");
+    hubberDelta = 10;  // as track()
+    const int F = data_->num_frames;
+    std::vector<int64_t> start(F + 1, 0);
+    for (int64_t o = 0; o < data_->num_obs; o++) start[data_->obs_frame[o] + 1]++;
+    int64_t most = 1;
+    for (int f = 0; f < F; f++) { most = std::max(most, start[f + 1]); start[f + 1] += start[f]; }
+    LiveTracker::Options o;
+    o.lag = lag; o.smooth = smooth; o.sigma_rot = sigma_rot; o.sigma_trans = sigma_trans;
+    o.with_huber = with_huber_; o.huber_delta = hubberDelta; o.max_obs_per_frame = (int)most; o.device_id = device_id;
+    LiveTracker lt(*this, o, &solver_params);
+    PoseLayout L;
+    L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
+    std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
+    live_results.assign(F, aar_tracker_result());
+    std::vector<LiveTracker::Detection> det;
+    for (int f = 0; f < F; f++) {
+        det.clear();
+        for (int64_t k = start[f]; k < start[f + 1]; k++) {
+            LiveTracker::Detection d;
+            d.cam_id = data_->cam_ids[data_->obs_cam[k]];
+            d.marker_id = data_->marker_ids[data_->obs_marker[k]];
+            memcpy(d.uv, data_->obs_uv + 8 * k, sizeof d.uv);
+            det.push_back(d);
+        }
+        const aar_tracker_result r = lt.push((double)data_->frame_ids[f], det, data_->x_full + L.full_fr0() + 6LL * f);
+        live_results[f] = r;
+        if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
+    }
+    const LiveTracker::Window w = lt.window();   // the frames that never left the window
+    for (size_t i = 0; i < w.frame_index.size(); i++) memcpy(&z[6 * (size_t)w.frame_index[i]], w.poses[i].data(), 6 * sizeof(double));
+    memcpy(data_->x_full + L.full_fr0(), z.data(), z.size() * sizeof(double));
+    mats2eVec();
+}
+
+LiveTracker::LiveTracker(const MultiCamMapper &solution, const Options &o, const SparseLevMarq<double>::Params *lm) {
+    const aar_dataset *d = solution.dataset();
+    if (!d) throw std::runtime_error("LiveTracker: the mapper holds no solution");
+    for (int c = 0; c < d->num_cams; c++) cam_index_[d->cam_ids[c]] = c;
+    for (int m = 0; m < d->num_markers; m++) marker_index_[d->marker_ids[m]] = m;
+    aar_tracker_params p;
+    aar_tracker_default_params(&p);
+    p.lag = o.lag; p.smooth = o.smooth ? 1 : 0; p.sigma_rot = o.sigma_rot; p.sigma_trans = o.sigma_trans;
+    p.with_huber = o.with_huber ? 1 : 0; p.huber_delta = o.huber_delta; p.max_obs_per_frame = o.max_obs_per_frame; p.device_id = o.device_id;
+    aar_lm_params q;
+    aar_lm_default_params(&q);
+    if (lm) {
+        q.max_iters = lm->maxIters; q.min_error = lm->minError; q.min_step_error_diff = lm->min_step_error_diff;
+        q.min_average_step_error_diff = lm->min_average_step_error_diff; q.tau = lm->tau;
+    }
+    if (aar_tracker_create(d, &p, &q, &tracker_)) throw std::runtime_error(aar_last_error());
+}
+
+LiveTracker::~LiveTracker() { aar_tracker_destroy(tracker_); }
+
+aar_tracker_result LiveTracker::push(double frame_time, const std::vector<Detection> &detections, const double *start) {
+    cam_.clear(); marker_.clear(); uv_.clear();
+    for (const Detection &d : detections) {
+        const auto c = cam_index_.find(d.cam_id);
+        const auto m = marker_index_.find(d.marker_id);
+        if (c == cam_index_.end() || m == marker_index_.end()) continue;
+        cam_.push_back(c->second);
+        marker_.push_back(m->second);
+        uv_.insert(uv_.end(), d.uv, d.uv + 8);
+    }
+    aar_tracker_result r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = sizeof r;
+    if (aar_tracker_push(tracker_, frame_time, (int32_t)cam_.size(), cam_.data(), marker_.data(), uv_.data(), start, &r)) throw std::runtime_error(aar_last_error());
+    return r;
+}
+
+LiveTracker::Window LiveTracker::window() {
+    Window w;
+    int32_t n = 0, has = 0;
+    int64_t idx[AAR_TRACKER_MAX_LAG + 1];
+    double poses[6 * (AAR_TRACKER_MAX_LAG + 1)], fe[AAR_TRACKER_MAX_LAG + 1], pe[AAR_TRACKER_MAX_LAG + 1], anchor[6];
+    if (aar_tracker_window(tracker_, &n, idx, poses, fe, pe, anchor, &has)) throw std::runtime_error(aar_last_error());
+    for (int i = 0; i < n; i++) {
+        w.frame_index.push_back(idx[i]);
+        std::array<double, 6> z;
+        memcpy(z.data(), poses + 6 * i, sizeof z);
+        w.poses.push_back(z);
+        w.frame_err.push_back(fe[i]);
+        w.pair_err.push_back(pe[i]);
+    }
+    w.has_anchor = has != 0;
+    if (has) memcpy(w.anchor_pose.data(), anchor, sizeof anchor);
+    return w;
+}
+
+void LiveTracker::reset() {
+    if (aar_tracker_reset(tracker_)) throw std::runtime_error(aar_last_error());
+}
+
 bool MultiCamMapper::write_solution_file(std::string path) {
     if (!data_) return false;
     aar_dataset tmp = *data_;

@@ -394,6 +394,10 @@ class MultiCamMapper {
     // metre per sqrt(frame id step)), all frames in one LM on the device (aar_track_smooth); the report lands in smooth_report, E_f in
     // track_errors and the pairs' prior costs in smooth_pair_errors
     void track_smooth(double sigma_rot, double sigma_trans);
+    // no counterpart in the reference as a method: apps/track.cpp's loop (:102-136) over the data set's frames, one frame per push through a
+    // LiveTracker (below): each frame starts from its own pose in the data set, the frame ids are the time axis; every frame ends at its lagged
+    // pose, the last window at aar_tracker_window's.  smooth = false needs lag = 0.  The pushes' results land in live_results.
+    void track_live(int lag, bool smooth, double sigma_rot, double sigma_trans);
     void error_function(const eVector &input, eVector &error);  // :731-737
     // :739-801 (private in the reference; public here so that reference-shaped caller code outside the class can bind it).  The
     // Jacobian of the accelerated path is analytic and never leaves the device: called by the solver mirror's probe it names
@@ -426,6 +430,7 @@ class MultiCamMapper {
     std::vector<double> track_errors;
     aar_smooth_report smooth_report = {};         // after track_smooth()
     std::vector<double> smooth_pair_errors;       // [num_frames - 1] e_f^T L_f e_f, after track_smooth()
+    std::vector<aar_tracker_result> live_results; // per frame, after track_live()
     int device_id = 0;
     int residual_mode = AAR_RES_F32;
     // How the damped normal equations are solved (aar_solver_options, include/aar.h) -- the counterpart of configuring the reference's solver object
@@ -520,6 +525,47 @@ class MultiCamMapper {
     bool with_huber_ = false;
     std::set<int> fixed_cam_ids_, fixed_marker_ids_;
     std::vector<PosePrior> pose_priors_;
+};
+
+// EXTENSION, no counterpart in the reference as a class: the live tracker (aar_tracker_*) by camera ID and marker ID.
+// Built from a mapper that holds a solution (its cameras, markers and intrinsics; its frames are ignored), then fed one frame per push, in time
+// order -- the body of apps/track.cpp's loop (:102-136) without re-initialising anything per frame.  Throws std::runtime_error on failure.
+class LiveTracker {
+   public:
+    struct Detection {
+        int cam_id = 0, marker_id = 0;
+        float uv[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // undistorted corners x0 y0 .. x3 y3
+    };
+    struct Options {
+        int lag = 0;                  // 0 .. AAR_TRACKER_MAX_LAG
+        bool smooth = false;          // false needs lag = 0
+        double sigma_rot = 0, sigma_trans = 0;
+        bool with_huber = false;
+        float huber_delta = 2.5f;
+        int max_obs_per_frame = 256;
+        int device_id = 0;
+    };
+    struct Window {
+        std::vector<int64_t> frame_index;
+        std::vector<std::array<double, 6>> poses;
+        std::vector<double> frame_err, pair_err;   // pair_err[i]: the pair that ends at window frame i (0: the anchor pair)
+        bool has_anchor = false;
+        std::array<double, 6> anchor_pose{};
+    };
+    LiveTracker(const MultiCamMapper &solution, const Options &options, const SparseLevMarq<double>::Params *lm = nullptr);
+    ~LiveTracker();
+    LiveTracker(const LiveTracker &) = delete;
+    LiveTracker &operator=(const LiveTracker &) = delete;
+    // detections of cameras or markers the solution does not hold are dropped; start: (rvec, t) or NULL = the previous frame's estimate
+    aar_tracker_result push(double frame_time, const std::vector<Detection> &detections, const double *start = nullptr);
+    Window window();
+    void reset();
+
+   private:
+    aar_tracker *tracker_ = nullptr;
+    std::map<int, int> cam_index_, marker_index_;
+    std::vector<int32_t> cam_, marker_;
+    std::vector<float> uv_;
 };
 
 }  // namespace aar

@@ -569,6 +569,68 @@ int aar_track_smooth(aar_problem *, double *x_full, const aar_lm_params *, const
 int aar_track_smooth_system(aar_problem *, const double *x_full, const aar_smooth_params *, double mu, double *diag, double *off, double *rhs,
                             double *delta, double cost[2]);
 
+/* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
+ * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are
+ * ignored -- and then fed ONE FRAME PER CALL, in time order.  After push n the window holds the last W = min(n + 1, lag + 1) pushed frames: these
+ * are still refined.  The frame that has just left the window (n - lag - 1, if it exists) is the anchor: its pose is final and held fixed.
+ *   smooth = 0 (needs lag = 0): no prior.  A push minimises E_n(z_n) exactly as aar_track does for one frame (rows = 8 n_obs); a frame without
+ *     detections keeps its start, with 0 iterations.
+ *   smooth = 1: a push minimises over the window's poses
+ *         E = sum_{f in window} E_f(z_f) + sum_{f, f+1 in window} e_f^T L_f e_f + [anchor exists] e_a^T L_a e_a
+ *     with e_f, L_f as in aar_track_smooth (D_f from the pushes' frame_time, no rel_motion) and e_a = e(z_anchor, z_first), z_anchor constant.
+ *     The LM is aar_track_smooth's, restarted on every push: mu = tau max diag H over the window's blocks, v = 2, the gain test with at most five
+ *     retries, exits 1 / 2 / 3 with rows = 8 (detections in the window) + 6 (pairs, the anchor pair included); a non-positive pivot of the
+ *     block-tridiagonal solve rejects the try.  Frames without detections are allowed: the prior carries them.
+ *   The new frame starts from pose_init when given, otherwise from the current estimate of the previous frame (the first push must give one);
+ *   older window frames start from their estimates after the previous push.  E_f uses double residuals and, with with_huber, Huber weights
+ *   with huber_delta; the prior is never Huber-weighted.
+ * One push is one host -> device copy of the frame's records, ONE kernel launch (the whole LM runs inside it) and one device -> host copy of the
+ * result.  Two trackers fed the same pushes give the same bits.  A rejected push (AAR_ERR_INVALID, the message names the entry) leaves the
+ * tracker exactly as it was.  Structs are size-versioned: the caller sets struct_size. */
+#define AAR_TRACKER_MAX_LAG 15
+typedef struct aar_tracker aar_tracker;
+typedef struct aar_tracker_params {
+    uint32_t struct_size;
+    int32_t lag;                 /* 0 .. AAR_TRACKER_MAX_LAG: frames that stay in the window behind the newest one */
+    int32_t smooth;              /* 0 | 1; 0 requires lag = 0 */
+    double sigma_rot;            /* rad   per sqrt(unit of frame_time), > 0 finite when smooth */
+    double sigma_trans;          /* metre per sqrt(unit of frame_time), > 0 finite when smooth */
+    int32_t with_huber;          /* 0 | 1 */
+    float huber_delta;           /* pixels, > 0 finite when with_huber */
+    int32_t max_obs_per_frame;   /* >= 1: detections one push may carry (sizes the ring) */
+    int32_t device_id;
+} aar_tracker_params;
+typedef struct aar_tracker_result {
+    uint32_t struct_size;
+    int64_t frame_index;         /* n: pushes accepted before this one */
+    int32_t window_frames;       /* W */
+    int32_t iterations, stop_code, rejected_tries;
+    double initial_cost, final_cost, final_data_cost, final_prior_cost, final_mu;
+    double pose[6];              /* the newest frame */
+    int32_t has_lagged;          /* the window is full: lagged_pose is the oldest window frame, which becomes the anchor at the next push --
+                                    its final, fixed-lag smoothed value */
+    int64_t lagged_index;
+    double lagged_pose[6];
+    double seconds;              /* wall time of the push */
+} aar_tracker_result;
+void aar_tracker_default_params(aar_tracker_params *);   /* struct_size set; lag 0, smooth 0, no Huber (delta 2.5), 256 detections, device 0 */
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the field: lag out of range, smooth = 0 with lag > 0, a
+ * sigma that is not positive and finite when smooth is set, huber_delta likewise when with_huber is set, max_obs_per_frame < 1, a malformed
+ * solution (sizes, roots, null arrays, a non-finite camera / marker pose or marker_size). */
+int aar_tracker_params_validate(const aar_dataset *solution, const aar_tracker_params *);
+int aar_tracker_create(const aar_dataset *solution, const aar_tracker_params *, const aar_lm_params * /* NULL = defaults */, aar_tracker **out);
+/* obs_cam / obs_marker: INDICES into the solution's cameras / markers, obs_uv: [n_obs][8] undistorted corners, pose_init: [6] (rvec, t) or NULL.
+ * Rejected (AAR_ERR_INVALID): n_obs above max_obs_per_frame, an index out of range, a frame_time that is not finite or not above the previous
+ * one, a missing first pose_init, a non-finite pose_init.  result may be NULL. */
+int aar_tracker_push(aar_tracker *, double frame_time, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker, const float *obs_uv,
+                     const double *pose_init, aar_tracker_result *result);
+/* The current window, oldest frame first (to flush the end of a stream): n = W, frame_index [n], poses [n][6], frame_err [n] = E_f, pair_err [n] =
+ * cost of the pair that ENDS at the frame (entry 0: the anchor pair, 0 without an anchor), anchor_pose, has_anchor.  Any output may be NULL. */
+int aar_tracker_window(aar_tracker *, int32_t *n, int64_t *frame_index, double *poses, double *frame_err, double *pair_err, double anchor_pose[6],
+                       int32_t *has_anchor);
+int aar_tracker_reset(aar_tracker *);     /* forgets all frames, keeps the solution */
+void aar_tracker_destroy(aar_tracker *);
+
 /* per-stage device time of the last aar_lm_solve, seconds, in the reference's verbose-timer vocabulary
  * (libs/sparselevmarq.h:425) extended with the stages that only exist here */
 typedef struct aar_stage_times {

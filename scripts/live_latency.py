@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Wall time per push of the live tracker (aar_tracker_push) beside the whole-recording API used one frame at a time
+(aar_problem_create of a one-frame problem + aar_track + aar_problem_destroy), on the frames of the tracking versions of configs 3 and 5.
+Not part of bench.py.  Run on the MI355X:
+
+    python scripts/live_latency.py > profiles/live_latency.txt
+    rocprofv3 --kernel-trace --stats -d <dir> -- python scripts/live_latency.py --configs 3     # kernel time and call count of k_live_push
+
+Every push is ONE launch of k_live_push (aar_tracker_push issues nothing else); the script prints the number of pushes it made, the kernel
+trace's call count of k_live_push must equal it.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "automatic-ar_amd"))
+import aar  # noqa: E402
+
+
+def ns(ds):
+    return 6 * (ds.num_cams - 1) + 6 * (ds.num_markers - 1)
+
+
+def one_frame(ds, f, x0):
+    out = aar.Dataset.__new__(aar.Dataset)
+    out.__dict__.update(ds.__dict__)
+    sel = np.asarray(ds.obs_frame) == f
+    out.num_frames, out.frame_ids = 1, ds.frame_ids[f:f + 1]
+    out.obs_frame, out.obs_cam, out.obs_marker, out.obs_uv = np.zeros(int(sel.sum()), np.int32), ds.obs_cam[sel], ds.obs_marker[sel], ds.obs_uv[sel]
+    out.num_obs = int(sel.sum())
+    out.x_full = np.r_[x0[:ns(ds)], x0[ns(ds) + 6 * f: ns(ds) + 6 * f + 6]]
+    return out
+
+
+def stats(t):
+    t = 1e6 * np.asarray(t)
+    return "%8.1f us  (%.1f ... %.1f)" % (np.median(t), t.min(), t.max())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", type=int, nargs="+", default=[3, 5])
+    ap.add_argument("--pushes", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    a = ap.parse_args()
+    n = a.pushes + a.warmup
+    total = 0
+    for cfg in a.configs:
+        ds = aar.synth(cfg, num_frames=n)
+        x0 = np.array(ds.x_full)
+        x0[:ns(ds)] = ds.x_truth[:ns(ds)]            # tracking: cameras and markers known, the frames at their perturbed starts
+        sol = aar.Dataset.__new__(aar.Dataset)
+        sol.__dict__.update(ds.__dict__)
+        sol.x_full = x0
+        z0 = x0[ns(ds):].reshape(-1, 6)
+        obs = []
+        for f in range(n):
+            sel = np.asarray(ds.obs_frame) == f
+            obs.append((ds.obs_cam[sel], ds.obs_marker[sel], ds.obs_uv[sel]))
+        most = max(len(o[0]) for o in obs)
+        print("config %d: %d cameras, %d markers, %.1f detections per frame (at most %d), %d pushes after %d warm-up" % (
+            cfg, ds.num_cams, ds.num_markers, ds.num_obs / n, most, a.pushes, a.warmup))
+        for label, kw in (("smooth 0", dict(lag=0, smooth=False)), ("smooth 1 lag 0", dict(lag=0, smooth=True)),
+                          ("smooth 1 lag 4", dict(lag=4, smooth=True)), ("smooth 1 lag 15", dict(lag=15, smooth=True))):
+            if kw["smooth"]:
+                kw.update(sigma_rot=0.05, sigma_trans=0.02)
+            wall, lib, its = [], [], []
+            with aar.Tracker(sol, max_obs_per_frame=most, **kw) as t:
+                for f in range(n):
+                    t0 = time.perf_counter()
+                    g = t.push(float(f), *obs[f], pose_init=z0[f])
+                    wall.append(time.perf_counter() - t0)
+                    lib.append(g["seconds"])
+                    its.append(g["iterations"])
+                    total += 1
+            w = a.warmup
+            print("  %-16s push %s   inside the library %s   %.1f LM iterations per push" % (label, stats(wall[w:]), stats(lib[w:]), np.mean(its[w:])))
+        frames = [one_frame(ds, f, x0) for f in range(n)]
+        wall, its = [], []
+        prm = aar.lm_default_params()
+        for f in range(n):
+            t0 = time.perf_counter()
+            with aar.Problem(frames[f]) as p:
+                _, it, _ = p.track(frames[f].x_full, prm)
+            wall.append(time.perf_counter() - t0)
+            its.append(int(it[0]))
+        print("  %-16s      %s   (aar_problem_create + aar_track + aar_problem_destroy per frame)   %.1f LM iterations per frame" % (
+            "create+track", stats(wall[a.warmup:]), np.mean(its[a.warmup:])))
+    print("pushes made: %d; launches per push: 1 (k_live_push; its call count in a kernel trace of this script equals the pushes made)" % total)
+
+
+if __name__ == "__main__":
+    main()
