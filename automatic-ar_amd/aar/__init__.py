@@ -41,8 +41,12 @@ SYMBOLS = [
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
+    "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
+    "aar_tracker_push_detections",
 ]
 TRACKER_MAX_LAG = 15
+TRACKER_START_VOTE, TRACKER_START_BEST = 1, 2
+TRACKER_STARTS = {"vote": TRACKER_START_VOTE, "best": TRACKER_START_BEST}
 NUM_KERNELS = 18
 PRIOR_CAMERA, PRIOR_MARKER = 0, 1
 PRIOR_KINDS = {"camera": PRIOR_CAMERA, "marker": PRIOR_MARKER}
@@ -252,6 +256,11 @@ def tracker_params(lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_hub
     return p
 
 
+class CTrackerStartInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("voted", C.c_int32), ("candidates", C.c_int32), ("winner", C.c_int32), ("vote_cost", C.c_double),
+                ("start_source", C.c_int32), ("cost_prediction", C.c_double), ("cost_vote", C.c_double), ("start_pose", C.c_double * 6)]
+
+
 def tracker_params_validate(ds, **kw):
     """aar_tracker_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
     c = ds.as_c()
@@ -290,6 +299,11 @@ STOP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 class CCamModel(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 12), ("n_dist", C.c_int32), ("width", C.c_int32),
                 ("height", C.c_int32)]
+
+
+class CTrackerDetectionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cams", C.POINTER(CCamModel)), ("ippe_threshold", C.c_double), ("min_detections", C.c_int32),
+                ("start_policy", C.c_int32)]
 
 
 class CDetections(C.Structure):
@@ -387,6 +401,12 @@ def lib():
                                    C.POINTER(CTrackerResult)]
     L.aar_tracker_window.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), dp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.aar_tracker_reset.argtypes = [C.c_void_p]
+    L.aar_tracker_default_detection_params.argtypes = [C.POINTER(CTrackerDetectionParams)]
+    L.aar_tracker_default_detection_params.restype = None
+    L.aar_tracker_detection_params_validate.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerDetectionParams)]
+    L.aar_tracker_enable_detections.argtypes = [C.c_void_p, C.POINTER(CTrackerDetectionParams)]
+    L.aar_tracker_push_detections.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), dp,
+                                              C.POINTER(CTrackerResult), C.POINTER(CTrackerStartInfo)]
     L.aar_tracker_destroy.argtypes = [C.c_void_p]
     L.aar_tracker_destroy.restype = None
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
@@ -848,6 +868,33 @@ def residual_report_write_yaml(path, ds, rr, det_err=True):
                                                 _u8ptr(k) if det_err else None, C.byref(r)))
 
 
+def tracker_detection_params(Ks=None, dists=None, ippe_threshold=None, min_detections=None, start_policy=None, struct_size=None):
+    """(aar_tracker_detection_params, the camera array it points to) from Python values (None = the library's default; Ks / dists by camera
+    INDEX, None = the solution's own); start_policy: "vote" | "best" or the number"""
+    p = CTrackerDetectionParams()
+    lib().aar_tracker_default_detection_params(C.byref(p))
+    cams = None
+    if Ks is not None:
+        cams = cam_models(Ks, dists if dists is not None else [np.zeros(0)] * len(Ks))
+        p.cams = C.cast(cams, C.POINTER(CCamModel))
+    if ippe_threshold is not None:
+        p.ippe_threshold = float(ippe_threshold)
+    if min_detections is not None:
+        p.min_detections = int(min_detections)
+    if start_policy is not None:
+        p.start_policy = TRACKER_STARTS.get(start_policy, start_policy)
+    if struct_size is not None:
+        p.struct_size = int(struct_size)
+    return p, cams
+
+
+def tracker_detection_params_validate(ds, **kw):
+    """aar_tracker_detection_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
+    c = ds.as_c()
+    p, cams = tracker_detection_params(**kw)
+    _check(lib().aar_tracker_detection_params_validate(C.byref(c), C.byref(p)))
+
+
 class Tracker:
     """aar_tracker: the live tracker.  Built from a solution data set (its cameras, markers, cam_mats, marker_size and
     roots; its frames are ignored) and fed one frame per push."""
@@ -891,6 +938,33 @@ class Tracker:
         out["pose"] = np.array(r.pose[:])
         out["lagged_pose"] = np.array(r.lagged_pose[:]) if r.has_lagged else None
         return out
+
+    def enable_detections(self, Ks=None, dists=None, ippe_threshold=None, min_detections=None, start_policy=None):
+        """aar_tracker_enable_detections: once after creation or reset (see tracker_detection_params)"""
+        p, cams = tracker_detection_params(Ks, dists, ippe_threshold, min_detections, start_policy)
+        _check(lib().aar_tracker_enable_detections(self.handle, C.byref(p)))
+
+    def push_detections(self, frame_time, det_cam, det_marker, uv_raw, pose_init=None):
+        """aar_tracker_push_detections: one frame's RAW detections (camera / marker INDICES, corners as detected [n, 8]).  Returns
+        (result, info): push()'s dict and a dict of the aar_tracker_start_info fields (start_pose as an array)."""
+        cam = np.ascontiguousarray(det_cam, dtype=np.int32).reshape(-1)
+        mk = np.ascontiguousarray(det_marker, dtype=np.int32).reshape(-1)
+        uv = np.ascontiguousarray(uv_raw, dtype=np.float32).reshape(-1)
+        n = len(cam)
+        assert len(mk) == n and len(uv) == 8 * n
+        init = None if pose_init is None else np.ascontiguousarray(pose_init, dtype=np.float64).reshape(6)
+        r, si = CTrackerResult(), CTrackerStartInfo()
+        r.struct_size, si.struct_size = C.sizeof(CTrackerResult), C.sizeof(CTrackerStartInfo)
+        ip = C.POINTER(C.c_int32)
+        _check(lib().aar_tracker_push_detections(self.handle, float(frame_time), n, cam.ctypes.data_as(ip), mk.ctypes.data_as(ip),
+                                                 uv.ctypes.data_as(C.POINTER(C.c_float)), _dptr(init) if init is not None else None, C.byref(r),
+                                                 C.byref(si)))
+        out = {k: getattr(r, k) for k, _ in CTrackerResult._fields_ if k not in ("struct_size", "pose", "lagged_pose")}
+        out["pose"] = np.array(r.pose[:])
+        out["lagged_pose"] = np.array(r.lagged_pose[:]) if r.has_lagged else None
+        info = {k: getattr(si, k) for k, _ in CTrackerStartInfo._fields_ if k not in ("struct_size", "start_pose")}
+        info["start_pose"] = np.array(si.start_pose[:])
+        return out, info
 
     def window(self):
         """aar_tracker_window: dict(n, frame_index [n], poses [n, 6], frame_err [n], pair_err [n] (entry i: the pair that ends at window

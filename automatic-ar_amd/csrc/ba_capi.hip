@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../host/internal.h"
+#include "../host/se3.h"
 #include "geom.hpp"
 #include "hostcopy.h"
 #include "kernels.h"
@@ -2948,12 +2949,23 @@ struct aar_tracker {
     int64_t n = 0;                   // pushes accepted
     double times[LIVE_MAX_W];        // by ring slot
     int cnt[LIVE_MAX_W];
+    // pushes of raw detections (aar_tracker_enable_detections)
+    std::vector<double> sol_x, sol_K, sol_dist;   // the solution's camera | marker poses, cam_mats, dist_coeffs (zeros when it has none)
+    int rc = 0, rm = 0;
+    double marker_size = 0;
+    bool det_on = false;
+    aar_tracker_detection_params det;
+    void *d_cams = nullptr;          // [C] CamTab
+    double *d_toroot = nullptr;      // [C][12] | [M][12]
+    double *d_work = nullptr;        // poses | Tc | BJ | cost, then has2 | fin (ints): sized by max_obs_per_frame, allocated once
+    std::vector<int32_t> order;      // scratch of the candidate order
 };
 
 namespace {
 
 constexpr int LIVE_ST_ANCHOR = 6 * LIVE_MAX_W, LIVE_ST_EF = LIVE_ST_ANCHOR + 8, LIVE_ST_PE = LIVE_ST_EF + LIVE_MAX_W, LIVE_ST_RES = LIVE_ST_PE + LIVE_MAX_W,
-              LIVE_ST_DOUBLES = LIVE_ST_RES + LIVE_RES_DOUBLES;
+              LIVE_ST_INFO = LIVE_ST_RES + LIVE_RES_DOUBLES, LIVE_ST_DOUBLES = LIVE_ST_INFO + LIVE_INFO_DOUBLES;   // (the info record rides behind the result: one copy)
+constexpr int LIVE_DET_MAX_OBS = 4096;   // the vote is n^2 in ONE workgroup: a frame of raw detections is capped here
 
 // the caller's struct read up to its struct_size, the rest at the defaults; false: too short to hold lag and smooth
 bool tracker_params_read(const aar_tracker_params *in, aar_tracker_params *out) {
@@ -3010,6 +3022,9 @@ void aar_tracker_destroy(aar_tracker *t) {
     if (t->d_K) (void)hipFree(t->d_K);
     if (t->d_state) (void)hipFree(t->d_state);
     if (t->d_ring) (void)hipFree(t->d_ring);
+    if (t->d_cams) (void)hipFree(t->d_cams);
+    if (t->d_toroot) (void)hipFree(t->d_toroot);
+    if (t->d_work) (void)hipFree(t->d_work);
     if (t->h_stage) (void)hipHostFree(t->h_stage);
     if (t->h_res) (void)hipHostFree(t->h_res);
     if (t->stream) (void)hipStreamDestroy(t->stream);
@@ -3029,6 +3044,11 @@ int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, con
     if (lm) t->lm = *lm; else aar_lm_default_params(&t->lm);
     t->C = sol->num_cams; t->M = sol->num_markers; t->device = p.device_id;
     t->half_size = (double)((float)sol->marker_size / 2.f);
+    t->rc = sol->root_cam; t->rm = sol->root_marker; t->marker_size = sol->marker_size;
+    if (sol->x_full) t->sol_x.assign(sol->x_full, sol->x_full + 6 * (size_t)(sol->num_cams - 1 + sol->num_markers - 1));
+    t->sol_K.assign(sol->cam_mats, sol->cam_mats + 9 * (size_t)sol->num_cams);
+    t->sol_dist.assign(5 * (size_t)sol->num_cams, 0.0);
+    if (sol->dist_coeffs) t->sol_dist.assign(sol->dist_coeffs, sol->dist_coeffs + 5 * (size_t)sol->num_cams);
     t->slot_bytes = live_slot_bytes(p.max_obs_per_frame);
     const int C = t->C, M = t->M, A = C + M;
     double *d_z = nullptr;
@@ -3039,7 +3059,7 @@ int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, con
         hipMalloc((void **)&d_z, (size_t)6 * A * sizeof(double)) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMalloc failed"));
     if (hipHostMalloc((void **)&t->h_stage, t->slot_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&t->h_res, LIVE_RES_DOUBLES * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        hipHostMalloc((void **)&t->h_res, (LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES) * sizeof(double), hipHostMallocDefault) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipHostMalloc failed"));
     if (hipMemsetAsync(t->d_state, 0, LIVE_ST_DOUBLES * sizeof(double), t->stream) != hipSuccess ||
         hipMemsetAsync(t->d_ring, 0, (size_t)(p.lag + 1) * t->slot_bytes, t->stream) != hipSuccess)
@@ -3070,31 +3090,44 @@ int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, con
 int aar_tracker_reset(aar_tracker *t) {
     if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_reset: null argument");
     t->n = 0;
+    t->det_on = false;   // (the buffers stay; aar_tracker_enable_detections fills them again)
     return AAR_OK;
 }
 
-int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker, const float *obs_uv,
-                     const double *pose_init, aar_tracker_result *result) {
-    if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_push: null argument");
+namespace {
+
+// one push.  info == nullptr && !raw: aar_tracker_push (corners already undistorted, ONE launch).  raw: aar_tracker_push_detections -- the
+// corners are raw, k_live_init undistorts them in the slot and chooses the start, then the same k_live_push runs from the slot's header.
+int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker,
+                 const float *obs_uv, const double *pose_init, aar_tracker_result *result, aar_tracker_start_info *info) {
+    if (!t) return set_error(AAR_ERR_INVALID, "%s: null argument", fn);
     const auto t0 = std::chrono::steady_clock::now();
     const aar_tracker_params &p = t->prm;
     const int slots = p.lag + 1;
     const int64_t n = t->n;
+    if (raw && !t->det_on) return set_error(AAR_ERR_INVALID, "%s: call aar_tracker_enable_detections first", fn);
     if (n_obs < 0 || n_obs > p.max_obs_per_frame)
-        return set_error(AAR_ERR_INVALID, "aar_tracker_push: n_obs = %d is outside 0 .. max_obs_per_frame = %d", (int)n_obs, (int)p.max_obs_per_frame);
-    if (n_obs > 0 && (!obs_cam || !obs_marker || !obs_uv)) return set_error(AAR_ERR_INVALID, "aar_tracker_push: null observation array");
+        return set_error(AAR_ERR_INVALID, "%s: %s = %d is outside 0 .. max_obs_per_frame = %d", fn, raw ? "n_det" : "n_obs", (int)n_obs, (int)p.max_obs_per_frame);
+    if (n_obs > 0 && (!obs_cam || !obs_marker || !obs_uv)) return set_error(AAR_ERR_INVALID, "%s: null %s array", fn, raw ? "detection" : "observation");
     for (int o = 0; o < n_obs; o++) {
-        if (obs_cam[o] < 0 || obs_cam[o] >= t->C) return set_error(AAR_ERR_INVALID, "aar_tracker_push: obs_cam[%d] = %d is outside 0 .. %d", o, (int)obs_cam[o], t->C - 1);
-        if (obs_marker[o] < 0 || obs_marker[o] >= t->M) return set_error(AAR_ERR_INVALID, "aar_tracker_push: obs_marker[%d] = %d is outside 0 .. %d", o, (int)obs_marker[o], t->M - 1);
+        if (obs_cam[o] < 0 || obs_cam[o] >= t->C)
+            return set_error(AAR_ERR_INVALID, "%s: %s[%d] = %d is outside 0 .. %d", fn, raw ? "det_cam" : "obs_cam", o, (int)obs_cam[o], t->C - 1);
+        if (obs_marker[o] < 0 || obs_marker[o] >= t->M)
+            return set_error(AAR_ERR_INVALID, "%s: %s[%d] = %d is outside 0 .. %d", fn, raw ? "det_marker" : "obs_marker", o, (int)obs_marker[o], t->M - 1);
     }
-    if (!std::isfinite(frame_time)) return set_error(AAR_ERR_INVALID, "aar_tracker_push: frame_time is not finite");
+    if (!std::isfinite(frame_time)) return set_error(AAR_ERR_INVALID, "%s: frame_time is not finite", fn);
     const int ns = (int)(n % slots), ps = (int)((n + slots - 1) % slots);
     if (n > 0 && (!(frame_time > t->times[ps]) || !std::isfinite(frame_time - t->times[ps])))
-        return set_error(AAR_ERR_INVALID, "aar_tracker_push: frame_time = %g does not ascend from the previous push's %g", frame_time, t->times[ps]);
-    if (n == 0 && !pose_init) return set_error(AAR_ERR_INVALID, "aar_tracker_push: the first push needs a pose_init");
+        return set_error(AAR_ERR_INVALID, "%s: frame_time = %g does not ascend from the previous push's %g", fn, frame_time, t->times[ps]);
+    // a vote is held unless the caller's pose_init settles the start (policy VOTE) or the frame has too few detections
+    const bool do_vote = raw && n_obs >= t->det.min_detections && !(pose_init && t->det.start_policy == AAR_TRACKER_START_VOTE);
+    if (n == 0 && !pose_init && !raw) return set_error(AAR_ERR_INVALID, "%s: the first push needs a pose_init", fn);
+    if (n == 0 && !pose_init && !do_vote)
+        return set_error(AAR_ERR_INVALID, "%s: the first push has %d detections, fewer than min_detections = %d, and no pose_init: nothing to start from", fn,
+                         (int)n_obs, (int)t->det.min_detections);
     if (pose_init)
         for (int k = 0; k < 6; k++)
-            if (!std::isfinite(pose_init[k])) return set_error(AAR_ERR_INVALID, "aar_tracker_push: pose_init[%d] is not finite", k);
+            if (!std::isfinite(pose_init[k])) return set_error(AAR_ERR_INVALID, "%s: pose_init[%d] is not finite", fn, k);
     HIP_TRY(hipSetDevice(t->device));
     // the frame's slot: header | records, staged in page-locked memory
     double *hdr = reinterpret_cast<double *>(t->h_stage);
@@ -3106,6 +3139,17 @@ int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int
         memcpy(rec, &id, sizeof id);
         memcpy(rec + sizeof id, obs_uv + 8 * (size_t)o, 8 * sizeof(float));
     }
+    size_t copy_bytes = LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * n_obs;
+    if (raw) {
+        // the candidate order of init_object_transforms: marker, then camera, stable (host/initializer.cpp); behind the records, same copy
+        t->order.resize((size_t)n_obs);
+        for (int o = 0; o < n_obs; o++) t->order[o] = o;
+        std::stable_sort(t->order.begin(), t->order.end(), [&](int32_t x, int32_t y) {
+            return obs_marker[x] != obs_marker[y] ? obs_marker[x] < obs_marker[y] : obs_cam[x] < obs_cam[y];
+        });
+        if (n_obs) memcpy(t->h_stage + copy_bytes, t->order.data(), sizeof(int32_t) * (size_t)n_obs);
+        copy_bytes += sizeof(int32_t) * (size_t)n_obs;
+    }
     const int W = (int)std::min<int64_t>(n + 1, slots);
     const bool has_anchor = n - slots >= 0;
     LiveArgs a;
@@ -3116,7 +3160,7 @@ int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int
     a.max_iters = t->lm.max_iters; a.min_error = t->lm.min_error; a.min_step_error_diff = t->lm.min_step_error_diff;
     a.min_average_step_error_diff = t->lm.min_average_step_error_diff; a.tau = t->lm.tau;
     a.W = W; a.slots = slots; a.first_slot = (int)((n + 1 - W) % slots);
-    a.has_anchor = has_anchor ? 1 : 0; a.smooth = p.smooth; a.has_init = pose_init ? 1 : 0;
+    a.has_anchor = has_anchor ? 1 : 0; a.smooth = p.smooth; a.has_init = (pose_init || raw) ? 1 : 0;   // raw: k_live_init wrote the header
     int64_t det = 0;
     for (int i = 0; i < LIVE_MAX_W; i++) { a.cnt[i] = 0; a.lam[i][0] = a.lam[i][1] = 0.0; }
     for (int i = 0; i < W; i++) {
@@ -3136,9 +3180,33 @@ int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int
         }
     }
     a.rows = 8.0 * (double)det + (p.smooth ? 6.0 * (double)(W - 1 + (has_anchor ? 1 : 0)) : 0.0);
-    HIP_TRY(hipMemcpyAsync(t->d_ring + (size_t)ns * t->slot_bytes, t->h_stage, LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * n_obs, hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->d_ring + (size_t)ns * t->slot_bytes, t->h_stage, copy_bytes, hipMemcpyHostToDevice, t->stream));
+    double *h_info = t->h_res + LIVE_RES_DOUBLES;
+    if (raw) {
+        const size_t mo = (size_t)p.max_obs_per_frame;
+        LiveInitArgs li;
+        li.slot = t->d_ring + (size_t)ns * t->slot_bytes; li.n_det = n_obs;
+        li.cams = t->d_cams; li.Tcr = t->d_toroot; li.Tmr = t->d_toroot + 12 * (size_t)t->C; li.C = t->C;
+        li.hf = (float)t->marker_size / 2.0f; li.h = t->marker_size / 2;   // as the Initializer: float for IPPE, double for the vote
+        li.threshold = t->det.ippe_threshold;
+        li.do_vote = do_vote ? 1 : 0; li.policy = t->det.start_policy; li.has_init = pose_init ? 1 : 0; li.has_prev = n > 0 ? 1 : 0;
+        li.zprev = t->d_state + 6 * ps;
+        li.ent = t->d_ent; li.Kmat = t->d_K; li.huber = a.huber; li.h_track = t->half_size;
+        li.poses = t->d_work; li.Tc = li.poses + 24 * mo; li.BJ = li.Tc + 24 * mo; li.cost = li.BJ + 48 * mo;
+        li.has2 = reinterpret_cast<int *>(li.cost + 2 * mo); li.fin = li.has2 + mo;
+        li.info = t->d_state + LIVE_ST_INFO;
+        launch_live_init(li, t->stream);
+        if (n == 0 && !pose_init) {
+            // the only push a vote can fail with nothing to fall back on: read the info before the window is touched
+            HIP_TRY(hipMemcpyAsync(h_info, li.info, LIVE_INFO_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+            HIP_TRY(hipStreamSynchronize(t->stream));
+            if (int rc = check_async("k_live_init")) return rc;
+            if (h_info[4] < 0.0)
+                return set_error(AAR_ERR_NUMERIC, "%s: no finite object pose candidate among %d, and neither a pose_init nor a previous estimate", fn, (int)h_info[1]);
+        }
+    }
     launch_live_push(a, t->stream);
-    HIP_TRY(hipMemcpyAsync(t->h_res, a.res, LIVE_RES_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipMemcpyAsync(t->h_res, a.res, (LIVE_RES_DOUBLES + (raw ? LIVE_INFO_DOUBLES : 0)) * sizeof(double), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     int rc = check_async("k_live_push");
     if (rc) return rc;
@@ -3160,6 +3228,129 @@ int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int
         r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         memcpy(result, &r, std::min<size_t>(result->struct_size, sizeof r));
     }
+    if (info) {
+        aar_tracker_start_info si;
+        memset(&si, 0, sizeof si);
+        si.struct_size = (uint32_t)std::min<size_t>(info->struct_size, sizeof si);
+        si.voted = (int32_t)h_info[0]; si.candidates = (int32_t)h_info[1]; si.winner = (int32_t)h_info[2]; si.vote_cost = h_info[3];
+        si.start_source = (int32_t)h_info[4]; si.cost_prediction = h_info[5]; si.cost_vote = h_info[6];
+        for (int k = 0; k < 6; k++) si.start_pose[k] = h_info[8 + k];
+        memcpy(info, &si, si.struct_size);
+    }
+    return AAR_OK;
+}
+
+// the caller's struct read up to its struct_size, the rest at the defaults; false: too short to hold start_policy
+bool detection_params_read(const aar_tracker_detection_params *in, aar_tracker_detection_params *out) {
+    aar_tracker_default_detection_params(out);
+    if (in->struct_size < offsetof(aar_tracker_detection_params, start_policy) + sizeof(int32_t)) return false;
+    memcpy(out, in, std::min<size_t>(in->struct_size, sizeof *out));
+    out->struct_size = (uint32_t)sizeof *out;
+    return true;
+}
+
+int detection_params_check(int C, const aar_tracker_detection_params *in, aar_tracker_detection_params *p) {
+    if (!detection_params_read(in, p))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: struct_size %u does not reach start_policy", (unsigned)in->struct_size);
+    if (!(p->ippe_threshold > 0.0) || !std::isfinite(p->ippe_threshold))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: ippe_threshold = %g must be positive and finite", p->ippe_threshold);
+    if (p->min_detections < 1) return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: min_detections = %d must be at least 1", (int)p->min_detections);
+    if (p->start_policy != AAR_TRACKER_START_VOTE && p->start_policy != AAR_TRACKER_START_BEST)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: start_policy = %d is neither AAR_TRACKER_START_VOTE nor AAR_TRACKER_START_BEST",
+                         (int)p->start_policy);
+    for (int c = 0; p->cams && c < C; c++) {
+        const aar_cam_model &m = p->cams[c];
+        for (int i = 0; i < 9; i++)
+            if (!std::isfinite(m.K[i])) return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: cams[%d].K[%d] is not finite", c, i);
+        if (m.n_dist < 0 || m.n_dist > AAR_MAX_DIST)
+            return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: cams[%d].n_dist = %d is outside 0 .. %d", c, (int)m.n_dist, AAR_MAX_DIST);
+        for (int i = 0; i < m.n_dist; i++)
+            if (!std::isfinite(m.dist[i])) return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params: cams[%d].dist[%d] is not finite", c, i);
+    }
+    return AAR_OK;
+}
+
+}  // namespace
+
+int aar_tracker_push(aar_tracker *t, double frame_time, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker, const float *obs_uv,
+                     const double *pose_init, aar_tracker_result *result) {
+    return tracker_push(t, "aar_tracker_push", false, frame_time, n_obs, obs_cam, obs_marker, obs_uv, pose_init, result, nullptr);
+}
+
+int aar_tracker_push_detections(aar_tracker *t, double frame_time, int32_t n_det, const int32_t *det_cam, const int32_t *det_marker,
+                                const float *det_uv_raw, const double *pose_init, aar_tracker_result *result, aar_tracker_start_info *info) {
+    return tracker_push(t, "aar_tracker_push_detections", true, frame_time, n_det, det_cam, det_marker, det_uv_raw, pose_init, result, info);
+}
+
+void aar_tracker_default_detection_params(aar_tracker_detection_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof *p;
+    p->ippe_threshold = 2.0;
+    p->min_detections = 2;
+    p->start_policy = AAR_TRACKER_START_VOTE;
+}
+
+int aar_tracker_detection_params_validate(const aar_dataset *sol, const aar_tracker_detection_params *in) {
+    if (!sol || !in) return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params_validate: null argument");
+    if (sol->num_cams < 1) return set_error(AAR_ERR_INVALID, "aar_tracker_detection_params_validate: solution with %d cameras", (int)sol->num_cams);
+    aar_tracker_detection_params p;
+    return detection_params_check(sol->num_cams, in, &p);
+}
+
+int aar_tracker_enable_detections(aar_tracker *t, const aar_tracker_detection_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_detections: null argument");
+    if (!t) {   // no tracker exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_tracker_enable_detections: null tracker");
+    }
+    if (t->det_on) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_detections: already enabled (aar_tracker_reset first)");
+    if (t->n != 0) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_detections: call it after aar_tracker_create or aar_tracker_reset, before the first push");
+    aar_tracker_detection_params p;
+    if (int rc = detection_params_check(t->C, in, &p)) return rc;
+    if (t->prm.max_obs_per_frame > LIVE_DET_MAX_OBS)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_tracker_enable_detections: max_obs_per_frame = %d is above %d (the vote runs in one workgroup)",
+                         (int)t->prm.max_obs_per_frame, LIVE_DET_MAX_OBS);
+    HIP_TRY(hipSetDevice(t->device));
+    const int C = t->C, M = t->M;
+    const size_t mo = (size_t)t->prm.max_obs_per_frame;
+    if (!t->d_cams) HIP_TRY(hipMalloc(&t->d_cams, (size_t)C * (9 + AAR_MAX_DIST) * sizeof(double)));
+    if (!t->d_toroot) HIP_TRY(hipMalloc((void **)&t->d_toroot, 12 * (size_t)(C + M) * sizeof(double)));
+    if (!t->d_work) HIP_TRY(hipMalloc((void **)&t->d_work, 98 * mo * sizeof(double) + 3 * mo * sizeof(int)));
+    // K and twelve coefficients by camera index (CamTab); the to-root 3x4 of every camera and marker exactly as aar_initializer_object_poses
+    // builds them from the solution (host cv::Rodrigues), the identity for the roots
+    std::vector<double> tab((size_t)C * (9 + AAR_MAX_DIST), 0.0), tr(12 * (size_t)(C + M), 0.0);
+    for (int c = 0; c < C; c++) {
+        double *row = &tab[(size_t)c * (9 + AAR_MAX_DIST)];
+        if (p.cams) {
+            memcpy(row, p.cams[c].K, 9 * sizeof(double));
+            for (int i = 0; i < p.cams[c].n_dist; i++) row[9 + i] = p.cams[c].dist[i];
+        } else {
+            memcpy(row, &t->sol_K[9 * (size_t)c], 9 * sizeof(double));
+            memcpy(row + 9, &t->sol_dist[5 * (size_t)c], 5 * sizeof(double));
+        }
+    }
+    PoseLayout L;
+    L.C = C; L.M = M; L.F = 0; L.rc = t->rc; L.rm = t->rm;
+    for (int e = 0; e < C + M; e++) {
+        double *m = &tr[12 * (size_t)e];
+        m[0] = m[5] = m[10] = 1.0;
+        const bool cam = e < C;
+        if (cam ? e == L.rc : e - C == L.rm) continue;
+        const double *v = t->sol_x.data() + (cam ? L.full_cam0() + 6LL * L.cam_slot(e) : L.full_mk0() + 6LL * L.mk_slot(e - C));
+        const Rigid r = pose_to_rigid(v);
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) m[i * 4 + j] = r.R[i * 3 + j];
+            m[i * 4 + 3] = r.t[i];
+        }
+    }
+    const char *what = "";
+    if (h2d(t->d_cams, tab.data(), tab.size() * sizeof(double), t->stream, &what) || h2d(t->d_toroot, tr.data(), tr.size() * sizeof(double), t->stream, &what))
+        return set_error(AAR_ERR_HIP, "aar_tracker_enable_detections: %s failed", what);
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    p.cams = nullptr;   // (copied; the caller's array is not kept)
+    t->det = p;
+    t->det_on = true;
     return AAR_OK;
 }
 

@@ -313,7 +313,12 @@ constexpr int LIVE_HDR_BYTES = 64;        // a ring slot starts with the frame's
 constexpr int LIVE_REC_BYTES = 48;        // ... followed by its records: ObsIdx (16 bytes) | eight corner coordinates (32 bytes)
 constexpr int LIVE_RES_DOUBLES = 24;      // the result record: iterations, stop code, rejected tries, initial / final / data / prior cost, mu,
                                           // the newest pose [8..13], the oldest window pose [14..19], tries, 0
-inline size_t live_slot_bytes(int max_obs) { return LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * (size_t)max_obs; }
+constexpr int LIVE_INFO_DOUBLES = 16;     // the start record of k_live_init, right behind the result record: voted, candidates, winner, vote cost,
+                                          // start source, E_f at the prediction, E_f at the vote, 0, the start pose [8..13], 0, 0
+// ... and, on a push of raw detections, by one int per record behind the LAST record: the order of the vote's candidates (live_init_kernels.hip)
+inline size_t live_slot_bytes(int max_obs) {
+    return (LIVE_HDR_BYTES + (size_t)(LIVE_REC_BYTES + sizeof(int32_t)) * (size_t)max_obs + 15) / 16 * 16;
+}
 struct LiveArgs {
     const double *ent, *Kmat;             // [A][ENT_STRIDE] rows of the fixed cameras and markers, [C][9]
     const char *ring;                     // [lag + 1] slots of slot_bytes
@@ -331,6 +336,26 @@ struct LiveArgs {
     double lam[LIVE_MAX_W][2];            // by window position: 1 / (sigma_rot^2 dt), 1 / (sigma_trans^2 dt) of the pair that ends there
 };
 void launch_live_push(const LiveArgs &a, hipStream_t st);   // ONE launch
+
+// the start of a frame pushed as raw detections (live_init_kernels.hip): undistortion, IPPE, the object pose candidates and
+// their vote in ONE launch of one workgroup, on the slot the frame was just copied into
+constexpr int LIVE_START_VOTE = 1, LIVE_START_BEST = 2;   // AAR_TRACKER_START_*
+struct LiveInitArgs {
+    char *slot;                           // header | n_det records (raw corners in, P = K corners out) | n_det ints: detections in candidate order
+    int n_det;
+    const void *cams;                     // [C] CamTab (ippe_vote.hpp): K and twelve distortion coefficients by camera index
+    const double *Tcr, *Tmr;              // [C][12], [M][12] to-root transforms of the solution (the identity for the roots)
+    int C;                                // a record's marker entity is C + marker index
+    float hf; double h;                   // half marker side: float for IPPE, double for the vote
+    double threshold;                     // second IPPE solution kept when (double)e2 / (double)e1 < threshold
+    int do_vote, policy, has_init, has_prev;
+    const double *zprev;                  // [6] the previous frame's estimate (has_prev)
+    const double *ent, *Kmat; float huber; double h_track;   // k_live_push's model, for E_f at the two starts (LIVE_START_BEST)
+    double *poses; int *has2;             // workspace: [2 max_obs][12], [max_obs]
+    double *Tc, *BJ, *cost; int *fin;     //            [2 max_obs][12], [2 max_obs][24], [2 max_obs], [2 max_obs]
+    double *info;                         // [LIVE_INFO_DOUBLES]
+};
+void launch_live_init(const LiveInitArgs &a, hipStream_t st);   // ONE launch
 
 // covariance (cov_kernels.hip): S (stride n_pad) -> S2 (stride n2 >= n_pad, zero beyond n_pad), rows with rowmask set -> identity
 void launch_cov_stage(const double *S, int n_pad, double *S2, int n2, const int32_t *rowmask, hipStream_t st);

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -202,7 +202,10 @@ int main(int argc, char *argv[]) {
     int smooth_args = 0;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
-    bool live = false;
+    // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
+    // own vote, as apps/track.cpp does; the solution file's object poses are not read and the Initializer does not run
+    bool live = false, from_detections = false;
+    int start_policy = AAR_TRACKER_START_VOTE;
     int live_lag = -1, live_args = 0;
     double live_sigma[2] = {0.0, 0.0};
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
@@ -227,6 +230,11 @@ int main(int argc, char *argv[]) {
         else if (a == "-prior-sigma-m") arg_flag = PriorM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
+        else if (a == "-from-detections") {
+            from_detections = true; arg_flag = NONE;
+            if (i + 1 < argc && (string(argv[i + 1]) == "vote" || string(argv[i + 1]) == "best"))
+                start_policy = string(argv[++i]) == "best" ? AAR_TRACKER_START_BEST : AAR_TRACKER_START_VOTE;
+        }
         else if (arg_flag == Live) {
             char *end = nullptr;
             if (live_args == 0) {
@@ -277,6 +285,7 @@ int main(int argc, char *argv[]) {
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
+    if (from_detections && (!live || from_initial || use_subseqs || !excluded_cams.empty())) return print_usage(argv[0]);
     string name = "";
     if (tracking_only) name += "_tracking_only";
     if (use_subseqs) name += "_subseqs";
@@ -298,8 +307,13 @@ int main(int argc, char *argv[]) {
     aar_cam_model *cams = nullptr;
     int32_t n_cams = 0;
     if (!from_initial && aar_cam_configs_read(folder_path.c_str(), &cams, &n_cams) != AAR_OK) n_cams = 0;
+    const vector<aar_cam_model> cam_models(cams, cams + n_cams);
+    if (from_detections && n_cams == 0) {
+        cerr << "-from-detections: no calibration folders under " << folder_path << endl;
+        return 1;
+    }
     aar_dataset *init = nullptr;
-    if (!from_initial && n_cams > 0) {
+    if (!from_initial && !from_detections && n_cams > 0) {
         try {
             vector<int> subseqs;
             if (use_subseqs) {
@@ -370,12 +384,28 @@ int main(int argc, char *argv[]) {
     const auto start = chrono::system_clock::now();
     if (live) {
         try {
-            mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1]);
+            if (from_detections) {
+                aar_detections *detections = aar::Initializer::read_detections_file(folder_path + "/aruco.detections", vector<int>());
+                try {
+                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy);
+                } catch (...) {
+                    aar_detections_free(detections);
+                    throw;
+                }
+                aar_detections_free(detections);
+            } else {
+                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1]);
+            }
             long long its = 0, rej = 0;
             double sec = 0, cost = 0;
             for (const aar_tracker_result &r : mcm.live_results) { its += r.iterations; rej += r.rejected_tries; sec += r.seconds; cost += r.final_cost; }
             cout << "live: " << mcm.live_results.size() << " pushes, lag " << live_lag << ", " << its << " LM iterations (" << rej << " rejected tries), summed cost "
                  << cost << ", " << (mcm.live_results.empty() ? 0.0 : 1e6 * sec / mcm.live_results.size()) << " us per push" << endl;
+            if (from_detections) {
+                long long held = 0, won = 0;
+                for (const aar_tracker_start_info &si : mcm.live_starts) { held += si.voted; won += si.start_source == 2; }
+                cout << "votes: " << held << " held, " << won << " won (start policy " << (start_policy == AAR_TRACKER_START_BEST ? "best" : "vote") << ")" << endl;
+            }
         } catch (const exception &e) {
             cerr << "live tracking failed: " << e.what() << endl;
             return 6;

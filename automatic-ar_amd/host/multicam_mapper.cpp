@@ -604,6 +604,58 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
     mats2eVec();
 }
 
+void MultiCamMapper::track_live_from_detections(const aar_detections *det, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
+                                                double sigma_trans, int start_policy) {
+    if (!data_ || !det) throw std::runtime_error("MultiCamMapper::track_live_from_detections: no data set / no detections");
+    hubberDelta = 10;  // as track()
+    const int F = data_->num_frames;
+    // the detections of every frame id, in file order
+    std::map<int, std::vector<int64_t>> of_frame;
+    size_t most = 1;
+    for (int64_t i = 0; i < det->num_det; i++) {
+        std::vector<int64_t> &v = of_frame[det->det_frame[i]];
+        v.push_back(i);
+        most = std::max(most, v.size());
+    }
+    LiveTracker::Options o;
+    o.lag = lag; o.smooth = smooth; o.sigma_rot = sigma_rot; o.sigma_trans = sigma_trans;
+    o.with_huber = with_huber_; o.huber_delta = hubberDelta; o.max_obs_per_frame = (int)most; o.device_id = device_id;
+    LiveTracker lt(*this, o, &solver_params);
+    LiveTracker::DetectionOptions dopt;
+    for (int c = 0; c < data_->num_cams; c++) {
+        const int id = data_->cam_ids[c];
+        if (id < 0 || id >= (int)cams.size()) throw std::runtime_error("MultiCamMapper::track_live_from_detections: no calibration for camera " + std::to_string(id));
+        dopt.cams[id] = cams[id];
+    }
+    dopt.start_policy = start_policy;
+    lt.enable_detections(dopt);
+    PoseLayout L;
+    L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
+    std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
+    live_results.assign(F, aar_tracker_result());
+    live_starts.assign(F, aar_tracker_start_info());
+    std::vector<LiveTracker::Detection> dets;
+    for (int f = 0; f < F; f++) {
+        dets.clear();
+        const auto it = of_frame.find(data_->frame_ids[f]);
+        if (it != of_frame.end())
+            for (int64_t k : it->second) {
+                LiveTracker::Detection d;
+                d.cam_id = det->det_cam[k];
+                d.marker_id = det->det_id[k];
+                memcpy(d.uv, det->det_uv + 8 * k, sizeof d.uv);
+                dets.push_back(d);
+            }
+        const aar_tracker_result r = lt.push_detections((double)data_->frame_ids[f], dets, nullptr, &live_starts[f]);
+        live_results[f] = r;
+        if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
+    }
+    const LiveTracker::Window w = lt.window();   // the frames that never left the window
+    for (size_t i = 0; i < w.frame_index.size(); i++) memcpy(&z[6 * (size_t)w.frame_index[i]], w.poses[i].data(), 6 * sizeof(double));
+    memcpy(data_->x_full + L.full_fr0(), z.data(), z.size() * sizeof(double));
+    mats2eVec();
+}
+
 LiveTracker::LiveTracker(const MultiCamMapper &solution, const Options &o, const SparseLevMarq<double>::Params *lm) {
     const aar_dataset *d = solution.dataset();
     if (!d) throw std::runtime_error("LiveTracker: the mapper holds no solution");
@@ -638,6 +690,43 @@ aar_tracker_result LiveTracker::push(double frame_time, const std::vector<Detect
     memset(&r, 0, sizeof r);
     r.struct_size = sizeof r;
     if (aar_tracker_push(tracker_, frame_time, (int32_t)cam_.size(), cam_.data(), marker_.data(), uv_.data(), start, &r)) throw std::runtime_error(aar_last_error());
+    return r;
+}
+
+void LiveTracker::enable_detections(const DetectionOptions &o) {
+    aar_tracker_detection_params p;
+    aar_tracker_default_detection_params(&p);
+    std::vector<aar_cam_model> by_index;
+    if (!o.cams.empty()) {
+        by_index.resize(cam_index_.size());
+        for (const auto &ci : cam_index_) {
+            const auto it = o.cams.find(ci.first);
+            if (it == o.cams.end()) throw std::runtime_error("LiveTracker::enable_detections: no calibration for camera " + std::to_string(ci.first));
+            by_index[ci.second] = it->second;
+        }
+        p.cams = by_index.data();
+    }
+    p.ippe_threshold = o.ippe_threshold; p.min_detections = o.min_detections; p.start_policy = o.start_policy;
+    if (aar_tracker_enable_detections(tracker_, &p)) throw std::runtime_error(aar_last_error());
+}
+
+aar_tracker_result LiveTracker::push_detections(double frame_time, const std::vector<Detection> &detections, const double *start,
+                                                aar_tracker_start_info *info) {
+    cam_.clear(); marker_.clear(); uv_.clear();
+    for (const Detection &d : detections) {
+        const auto c = cam_index_.find(d.cam_id);
+        const auto m = marker_index_.find(d.marker_id);
+        if (c == cam_index_.end() || m == marker_index_.end()) continue;
+        cam_.push_back(c->second);
+        marker_.push_back(m->second);
+        uv_.insert(uv_.end(), d.uv, d.uv + 8);
+    }
+    aar_tracker_result r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = sizeof r;
+    if (info) { memset(info, 0, sizeof *info); info->struct_size = sizeof *info; }
+    if (aar_tracker_push_detections(tracker_, frame_time, (int32_t)cam_.size(), cam_.data(), marker_.data(), uv_.data(), start, &r, info))
+        throw std::runtime_error(aar_last_error());
     return r;
 }
 

@@ -398,6 +398,11 @@ class MultiCamMapper {
     // LiveTracker (below): each frame starts from its own pose in the data set, the frame ids are the time axis; every frame ends at its lagged
     // pose, the last window at aar_tracker_window's.  smooth = false needs lag = 0.  The pushes' results land in live_results.
     void track_live(int lag, bool smooth, double sigma_rot, double sigma_trans);
+    // ... the whole of that loop (:117-133): every frame of the data set is fed the RAW detections that carry its frame id (cams: calibrations by
+    // camera ID, as the Initializer takes them) and starts from its own vote (start_policy AAR_TRACKER_START_VOTE) or from the cheaper of vote
+    // and previous estimate (AAR_TRACKER_START_BEST); the data set's own object poses are not read.  The starts land in live_starts.
+    void track_live_from_detections(const aar_detections *detections, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
+                                    double sigma_trans, int start_policy = AAR_TRACKER_START_VOTE);
     void error_function(const eVector &input, eVector &error);  // :731-737
     // :739-801 (private in the reference; public here so that reference-shaped caller code outside the class can bind it).  The
     // Jacobian of the accelerated path is analytic and never leaves the device: called by the solver mirror's probe it names
@@ -431,6 +436,7 @@ class MultiCamMapper {
     aar_smooth_report smooth_report = {};         // after track_smooth()
     std::vector<double> smooth_pair_errors;       // [num_frames - 1] e_f^T L_f e_f, after track_smooth()
     std::vector<aar_tracker_result> live_results; // per frame, after track_live()
+    std::vector<aar_tracker_start_info> live_starts;   // per frame, after track_live_from_detections()
     int device_id = 0;
     int residual_mode = AAR_RES_F32;
     // How the damped normal equations are solved (aar_solver_options, include/aar.h) -- the counterpart of configuring the reference's solver object
@@ -558,6 +564,17 @@ class LiveTracker {
     LiveTracker &operator=(const LiveTracker &) = delete;
     // detections of cameras or markers the solution does not hold are dropped; start: (rvec, t) or NULL = the previous frame's estimate
     aar_tracker_result push(double frame_time, const std::vector<Detection> &detections, const double *start = nullptr);
+    // raw detections: once after construction or reset().  cams: calibrations by camera ID (empty: the solution's cam_mats
+    // and its five coefficients); then push_detections() takes corners as detected and starts the frame from its own vote (see aar.h)
+    struct DetectionOptions {
+        std::map<int, aar_cam_model> cams;
+        double ippe_threshold = 2.0;
+        int min_detections = 2;
+        int start_policy = AAR_TRACKER_START_VOTE;
+    };
+    void enable_detections(const DetectionOptions &options);
+    aar_tracker_result push_detections(double frame_time, const std::vector<Detection> &detections, const double *start = nullptr,
+                                       aar_tracker_start_info *info = nullptr);
     Window window();
     void reset();
 

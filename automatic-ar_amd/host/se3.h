@@ -5,6 +5,13 @@
 #include <cmath>
 #include <cstring>
 
+// the matrix -> vector half also runs on the device (csrc/ippe_vote.hpp: the live tracker's start pose)
+#if defined(__HIP__)
+#define AAR_HD __host__ __device__
+#else
+#define AAR_HD
+#endif
+
 namespace aar {
 
 struct Mat3 {
@@ -66,9 +73,9 @@ inline void rodrigues_vec2mat(const double w[3], double R[9]) {
 
 // One-sided Jacobi SVD of a 3x3: returns U*V^T, the orthogonal polar factor cv::Rodrigues substitutes
 // for its input before extracting the rotation vector.
-inline void nearest_rotation(const double Rin[9], double Q[9]) {
+AAR_HD inline void nearest_rotation(const double Rin[9], double Q[9]) {
     double A[9], V[9];
-    std::memcpy(A, Rin, sizeof A);
+    for (int i = 0; i < 9; i++) A[i] = Rin[i];
     for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
     for (int sweep = 0; sweep < 30; sweep++) {
         double off = 0;
@@ -109,7 +116,7 @@ inline void nearest_rotation(const double Rin[9], double Q[9]) {
 }
 
 // cv::Rodrigues matrix -> vector, including the theta ~ pi branch
-inline void rodrigues_mat2vec(const double Rin[9], double w[3]) {
+AAR_HD inline void rodrigues_mat2vec(const double Rin[9], double w[3]) {
     double R[9];
     nearest_rotation(Rin, R);
     double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];

@@ -628,7 +628,54 @@ int aar_tracker_push(aar_tracker *, double frame_time, int32_t n_obs, const int3
  * cost of the pair that ENDS at the frame (entry 0: the anchor pair, 0 without an anchor), anchor_pose, has_anchor.  Any output may be NULL. */
 int aar_tracker_window(aar_tracker *, int32_t *n, int64_t *frame_index, double *poses, double *frame_err, double *pair_err, double anchor_pose[6],
                        int32_t *has_anchor);
-int aar_tracker_reset(aar_tracker *);     /* forgets all frames, keeps the solution */
+int aar_tracker_reset(aar_tracker *);     /* forgets all frames (and aar_tracker_enable_detections), keeps the solution */
+
+/* The live tracker fed RAW detections: the first half of apps/track.cpp's loop (:117-133) on the device as well.  Per push
+ * the frame's corners are undistorted with the camera's K and up to AAR_MAX_DIST coefficients (they replace the raw ones in the window, so the
+ * refinement sees what aar_tracker_push would be given), IPPE runs on every detection (obtain_pose_estimations), the object pose candidates of
+ * init_object_transforms are enumerated in the reference's order -- by marker index, then camera index; first solution, then the second when
+ * (double)e2 / (double)e1 < ippe_threshold -- and voted on (find_best_transformation: first minimum of the summed corner distances, NaN never
+ * wins; a candidate with a non-finite entry is also left out of the other candidates' sums).  All of it is ONE extra launch of one workgroup
+ * (k_live_init) in front of aar_tracker_push's launch: one copy in, two launches, one copy out that carries result and info; nothing is
+ * allocated per push.  The start of the new frame:
+ *   pose_init given, policy VOTE          no vote: aar_tracker_push on the undistorted corners
+ *   n_det < min_detections                no vote: pose_init, else the previous estimate; neither (first push) -> AAR_ERR_INVALID
+ *   policy VOTE                           the vote's winner; no finite candidate -> the previous estimate, without one AAR_ERR_NUMERIC
+ *   policy BEST                           prediction = pose_init, else the previous estimate.  The new frame's data cost E_f is evaluated at the
+ *                                         prediction and at the vote's winner; the vote starts the frame only when strictly cheaper.  Without a
+ *                                         prediction the vote alone decides; without a finite candidate the prediction does.
+ * Only a first push without pose_init can be rejected after the device has run (the host then waits for k_live_init before it launches the
+ * refinement); every rejected push leaves the tracker exactly as it was.  max_obs_per_frame above 4096 is AAR_ERR_UNSUPPORTED here: the vote
+ * is quadratic in the candidates (at most two per detection) on one compute unit. */
+#define AAR_TRACKER_START_VOTE 1   /* every frame without a pose_init starts from its own vote (the reference's loop) */
+#define AAR_TRACKER_START_BEST 2   /* the cheaper of {pose_init or previous estimate, vote} in the new frame's data cost */
+typedef struct aar_tracker_detection_params {
+    uint32_t struct_size;
+    const aar_cam_model *cams;   /* [solution->num_cams] by camera INDEX; NULL = the solution's cam_mats + its 5 dist_coeffs */
+    double ippe_threshold;       /* default 2.0 (aar_init_params.threshold) */
+    int32_t min_detections;      /* default 2: fewer usable detections -> no vote for that frame */
+    int32_t start_policy;        /* default AAR_TRACKER_START_VOTE */
+} aar_tracker_detection_params;
+typedef struct aar_tracker_start_info {
+    uint32_t struct_size;
+    int32_t voted;               /* a vote was held */
+    int32_t candidates, winner;  /* winner: index in candidate order, -1 = none finite */
+    double vote_cost;            /* the winner's summed error (find_best_transformation's weight) */
+    int32_t start_source;        /* 0 pose_init, 1 previous estimate, 2 vote */
+    double cost_prediction, cost_vote;  /* new frame's E_f at the two starts (BEST with both a prediction and a winner, else 0) */
+    double start_pose[6];
+} aar_tracker_start_info;
+void aar_tracker_default_detection_params(aar_tracker_detection_params *);   /* struct_size set; cams NULL, 2.0, 2, AAR_TRACKER_START_VOTE */
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the field: a struct_size that does not reach start_policy,
+ * ippe_threshold not positive and finite, min_detections < 1, an unknown start_policy, a cams entry with a non-finite K / dist or a bad n_dist. */
+int aar_tracker_detection_params_validate(const aar_dataset *solution, const aar_tracker_detection_params *);
+/* Once after aar_tracker_create or aar_tracker_reset, before the first push; again without a reset: AAR_ERR_INVALID.  The cams array is copied. */
+int aar_tracker_enable_detections(aar_tracker *, const aar_tracker_detection_params *);
+/* det_cam / det_marker: INDICES into the solution's cameras / markers, det_uv_raw: [n_det][8] corners as detected.  Rejections as
+ * aar_tracker_push, plus a call before aar_tracker_enable_detections.  result and info may be NULL.  May be mixed with aar_tracker_push. */
+int aar_tracker_push_detections(aar_tracker *, double frame_time, int32_t n_det, const int32_t *det_cam, const int32_t *det_marker,
+                                const float *det_uv_raw, const double *pose_init /* may always be NULL */,
+                                aar_tracker_result *, aar_tracker_start_info *);
 void aar_tracker_destroy(aar_tracker *);
 
 /* per-stage device time of the last aar_lm_solve, seconds, in the reference's verbose-timer vocabulary

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Wall time per push of the live tracker (aar_tracker_push) beside the whole-recording API used one frame at a time
+"""Wall time per push of the live tracker (aar_tracker_push, and aar_tracker_push_detections beside the per-frame Initializer it replaces) beside the whole-recording API used one frame at a time
 (aar_problem_create of a one-frame problem + aar_track + aar_problem_destroy), on the frames of the tracking versions of configs 3 and 5.
 Not part of bench.py.  Run on the MI355X:
 
@@ -48,7 +48,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     a = ap.parse_args()
     n = a.pushes + a.warmup
-    total = 0
+    total = total_det = 0
     for cfg in a.configs:
         ds = aar.synth(cfg, num_frames=n)
         x0 = np.array(ds.x_full)
@@ -90,6 +90,35 @@ def main():
             its.append(int(it[0]))
         print("  %-16s      %s   (aar_problem_create + aar_track + aar_problem_destroy per frame)   %.1f LM iterations per frame" % (
             "create+track", stats(wall[a.warmup:]), np.mean(its[a.warmup:])))
+        # raw detections: aar_tracker_push_detections under policy VOTE beside what it replaces, the Initializer on a
+        # one-frame detection set with the map fixed (aar_initializer_object_poses) followed by aar_tracker_push from its pose
+        K = ds.cam_mats.reshape(-1, 3, 3)
+        dists = [np.zeros(5)] * ds.num_cams
+        wall, its, cands = [], [], []
+        with aar.Tracker(sol, max_obs_per_frame=most) as t:
+            t.enable_detections(Ks=K, dists=dists, start_policy="vote")
+            for f in range(n):
+                t0 = time.perf_counter()
+                g, info = t.push_detections(float(f), *obs[f])
+                wall.append(time.perf_counter() - t0)
+                its.append(g["iterations"])
+                cands.append(info["candidates"])
+                total_det += 1
+        w = a.warmup
+        print("  %-16s push %s   %.1f candidates, %.1f LM iterations per push" % ("detections vote", stats(wall[w:]), np.mean(cands[w:]), np.mean(its[w:])))
+        wall, its = [], []
+        with aar.Tracker(sol, max_obs_per_frame=most) as t:
+            for f in range(n):
+                cam, mk, uv = obs[f]
+                t0 = time.perf_counter()
+                det = aar.Detections(int(ds.cam_ids.max()) + 1, 1, np.zeros(len(cam), np.int32), ds.cam_ids[cam], ds.marker_ids[mk], uv)
+                one = aar.initializer_run(det, K, dists, ds.marker_size, solution=sol)
+                g = t.push(float(f), one.obs_cam, one.obs_marker, one.obs_uv, pose_init=one.x_full[ns(ds):ns(ds) + 6])
+                wall.append(time.perf_counter() - t0)
+                its.append(g["iterations"])
+        print("  %-16s      %s   (aar_initializer_object_poses on one frame + aar_tracker_push)   %.1f LM iterations per push" % (
+            "init+push", stats(wall[w:]), np.mean(its[w:])))
+    print("detection pushes made: %d; launches per detection push: 2 (k_live_init, k_live_push)" % total_det)
     print("pushes made: %d; launches per push: 1 (k_live_push; its call count in a kernel trace of this script equals the pushes made)" % total)
 
 
