@@ -42,10 +42,12 @@ SYMBOLS = [
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
-    "aar_tracker_push_detections",
+    "aar_tracker_push_detections", "aar_tracker_uncertainty", "aar_tracker_covariance_write_yaml",
 ]
 TRACKER_MAX_LAG = 15
 TRACKER_START_VOTE, TRACKER_START_BEST = 1, 2
+TRACKER_ANCHOR_FIXED, TRACKER_ANCHOR_MARGINAL = 0, 1
+TRACKER_ANCHORS = {"fixed": TRACKER_ANCHOR_FIXED, "marginal": TRACKER_ANCHOR_MARGINAL}
 TRACKER_STARTS = {"vote": TRACKER_START_VOTE, "best": TRACKER_START_BEST}
 NUM_KERNELS = 18
 PRIOR_CAMERA, PRIOR_MARKER = 0, 1
@@ -230,7 +232,14 @@ def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, 
 
 class CTrackerParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lag", C.c_int32), ("smooth", C.c_int32), ("sigma_rot", C.c_double), ("sigma_trans", C.c_double),
-                ("with_huber", C.c_int32), ("huber_delta", C.c_float), ("max_obs_per_frame", C.c_int32), ("device_id", C.c_int32)]
+                ("with_huber", C.c_int32), ("huber_delta", C.c_float), ("max_obs_per_frame", C.c_int32), ("device_id", C.c_int32),
+                ("anchor_mode", C.c_int32), ("covariance", C.c_int32)]
+
+
+class CTrackerUncertainty(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cov_valid", C.c_int32), ("sigma2", C.c_double), ("window_frames", C.c_int32),
+                ("has_marginal", C.c_int32), ("frame_index", C.c_int64 * 16), ("cov", C.c_double * (16 * 36)), ("marginal_index", C.c_int64),
+                ("marginal_info", C.c_double * 36), ("marginal_mean", C.c_double * 6), ("marginal_dropped", C.c_int64)]
 
 
 class CTrackerResult(C.Structure):
@@ -241,12 +250,13 @@ class CTrackerResult(C.Structure):
 
 
 def tracker_params(lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None, device=0,
-                   struct_size=None):
-    """aar_tracker_params from Python values (None = the library's default)"""
+                   struct_size=None, anchor="fixed", covariance=False):
+    """aar_tracker_params from Python values (None = the library's default); anchor: "fixed" | "marginal" (or the integer)"""
     p = CTrackerParams()
     lib().aar_tracker_default_params(C.byref(p))
     p.lag, p.smooth, p.sigma_rot, p.sigma_trans = int(lag), int(smooth), float(sigma_rot), float(sigma_trans)
     p.with_huber, p.device_id = int(bool(with_huber)), int(device)
+    p.anchor_mode, p.covariance = int(TRACKER_ANCHORS.get(anchor, anchor)), int(covariance)
     if huber_delta is not None:
         p.huber_delta = float(huber_delta)
     if max_obs_per_frame is not None:
@@ -407,6 +417,8 @@ def lib():
     L.aar_tracker_enable_detections.argtypes = [C.c_void_p, C.POINTER(CTrackerDetectionParams)]
     L.aar_tracker_push_detections.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), dp,
                                               C.POINTER(CTrackerResult), C.POINTER(CTrackerStartInfo)]
+    L.aar_tracker_uncertainty.argtypes = [C.c_void_p, C.POINTER(CTrackerUncertainty)]
+    L.aar_tracker_covariance_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.POINTER(C.c_uint8)]
     L.aar_tracker_destroy.argtypes = [C.c_void_p]
     L.aar_tracker_destroy.restype = None
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
@@ -900,11 +912,13 @@ class Tracker:
     roots; its frames are ignored) and fed one frame per push."""
 
     def __init__(self, ds, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
-                 device=0, params=None):
-        """params: aar_lm_params (lm_default_params(...)) or None for the defaults"""
+                 device=0, params=None, anchor="fixed", covariance=False):
+        """params: aar_lm_params (lm_default_params(...)) or None for the defaults; anchor "fixed" | "marginal", covariance: DESIGN.md
+        section 19 (uncertainty() after a push)"""
         self.ds = ds
         self._cds = ds.as_c()
-        self.prm = tracker_params(lag, smooth, sigma_rot, sigma_trans, with_huber, huber_delta, max_obs_per_frame, device)
+        self.prm = tracker_params(lag, smooth, sigma_rot, sigma_trans, with_huber, huber_delta, max_obs_per_frame, device, anchor=anchor,
+                                  covariance=covariance)
         self.handle = C.c_void_p()
         _check(lib().aar_tracker_create(C.byref(self._cds), C.byref(self.prm), C.byref(params) if params is not None else None,
                                         C.byref(self.handle)))
@@ -978,6 +992,18 @@ class Tracker:
         w = n.value
         return dict(n=w, frame_index=idx[:w].copy(), poses=poses[:w].copy(), frame_err=fe[:w].copy(), pair_err=pe[:w].copy(),
                     anchor_pose=anchor if has.value else None)
+
+    def uncertainty(self):
+        """aar_tracker_uncertainty after the last push: dict(cov_valid, sigma2, window_frames, frame_index [W], cov [W, 6, 6] (unscaled blocks of
+        H^-1, oldest first), has_marginal, marginal_index, marginal_info [6, 6], marginal_mean [6], marginal_dropped)"""
+        u = CTrackerUncertainty()
+        u.struct_size = C.sizeof(CTrackerUncertainty)
+        _check(lib().aar_tracker_uncertainty(self.handle, C.byref(u)))
+        w = u.window_frames
+        return dict(cov_valid=u.cov_valid, sigma2=u.sigma2, window_frames=w, frame_index=np.array(u.frame_index[:w], dtype=np.int64),
+                    cov=np.array(u.cov[:36 * w]).reshape(w, 6, 6), has_marginal=u.has_marginal, marginal_index=u.marginal_index,
+                    marginal_info=np.array(u.marginal_info[:]).reshape(6, 6), marginal_mean=np.array(u.marginal_mean[:]),
+                    marginal_dropped=u.marginal_dropped)
 
     def reset(self):
         _check(lib().aar_tracker_reset(self.handle))

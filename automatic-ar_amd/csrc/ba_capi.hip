@@ -2943,7 +2943,13 @@ struct aar_tracker {
     double *d_state = nullptr;       // zslot [16][6] | anchor [6] + 2 idle | Ef [16] | Pe [16] | result record
     char *d_ring = nullptr;          // [lag + 1] slots
     char *h_stage = nullptr;         // pinned: one slot
-    double *h_res = nullptr;         // pinned: the result record
+    double *h_res = nullptr;         // pinned: the result record | start record | uncertainty record
+    // marginalised anchor and covariance: what the last accepted push left
+    bool unc_set = false;            // h_res holds the uncertainty record of push n - 1
+    int has_marginal = 0;            // the next push puts the device's (Lambda_m, m) on its first window frame
+    int64_t marginal_dropped = 0;
+    int unc_W = 0;
+    double unc_sigma2 = 0;
     size_t slot_bytes = 0;
     double half_size = 0;
     int64_t n = 0;                   // pushes accepted
@@ -2964,7 +2970,8 @@ struct aar_tracker {
 namespace {
 
 constexpr int LIVE_ST_ANCHOR = 6 * LIVE_MAX_W, LIVE_ST_EF = LIVE_ST_ANCHOR + 8, LIVE_ST_PE = LIVE_ST_EF + LIVE_MAX_W, LIVE_ST_RES = LIVE_ST_PE + LIVE_MAX_W,
-              LIVE_ST_INFO = LIVE_ST_RES + LIVE_RES_DOUBLES, LIVE_ST_DOUBLES = LIVE_ST_INFO + LIVE_INFO_DOUBLES;   // (the info record rides behind the result: one copy)
+              LIVE_ST_INFO = LIVE_ST_RES + LIVE_RES_DOUBLES, LIVE_ST_UNC = LIVE_ST_INFO + LIVE_INFO_DOUBLES,
+              LIVE_ST_DOUBLES = LIVE_ST_UNC + LIVE_UNC_DOUBLES;   // (the info and uncertainty records ride behind the result: one copy)
 constexpr int LIVE_DET_MAX_OBS = 4096;   // the vote is n^2 in ONE workgroup: a frame of raw detections is capped here
 
 // the caller's struct read up to its struct_size, the rest at the defaults; false: too short to hold lag and smooth
@@ -3001,6 +3008,15 @@ int aar_tracker_params_validate(const aar_dataset *sol, const aar_tracker_params
         return set_error(AAR_ERR_INVALID, "aar_tracker_params: huber_delta = %g must be positive and finite", (double)p.huber_delta);
     if (p.max_obs_per_frame < 1 || p.max_obs_per_frame > (1 << 20))
         return set_error(AAR_ERR_INVALID, "aar_tracker_params: max_obs_per_frame = %d is outside 1 .. %d", (int)p.max_obs_per_frame, 1 << 20);
+    if (p.anchor_mode != AAR_TRACKER_ANCHOR_FIXED && p.anchor_mode != AAR_TRACKER_ANCHOR_MARGINAL)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_params: anchor_mode = %d is neither AAR_TRACKER_ANCHOR_FIXED nor AAR_TRACKER_ANCHOR_MARGINAL",
+                         (int)p.anchor_mode);
+    if (p.anchor_mode == AAR_TRACKER_ANCHOR_MARGINAL && !p.smooth)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_params: anchor_mode = AAR_TRACKER_ANCHOR_MARGINAL needs smooth = 1 (the marginal is the prior's)");
+    if (p.anchor_mode == AAR_TRACKER_ANCHOR_MARGINAL && p.lag < 1)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_params: anchor_mode = AAR_TRACKER_ANCHOR_MARGINAL needs lag >= 1 (with lag = 0 the next pair's "
+                                          "time step is not known when the frame leaves)");
+    if (p.covariance != 0 && p.covariance != 1) return set_error(AAR_ERR_INVALID, "aar_tracker_params: covariance = %d must be 0 or 1", (int)p.covariance);
     const int C = sol->num_cams, M = sol->num_markers;
     if (C < 1 || M < 1 || (int64_t)C + M >= 32768) return set_error(AAR_ERR_INVALID, "aar_tracker: solution with %d cameras / %d markers", C, M);
     if (sol->root_cam < 0 || sol->root_cam >= C || sol->root_marker < 0 || sol->root_marker >= M)
@@ -3059,7 +3075,7 @@ int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, con
         hipMalloc((void **)&d_z, (size_t)6 * A * sizeof(double)) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMalloc failed"));
     if (hipHostMalloc((void **)&t->h_stage, t->slot_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&t->h_res, (LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES) * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        hipHostMalloc((void **)&t->h_res, (LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_DOUBLES) * sizeof(double), hipHostMallocDefault) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipHostMalloc failed"));
     if (hipMemsetAsync(t->d_state, 0, LIVE_ST_DOUBLES * sizeof(double), t->stream) != hipSuccess ||
         hipMemsetAsync(t->d_ring, 0, (size_t)(p.lag + 1) * t->slot_bytes, t->stream) != hipSuccess)
@@ -3091,6 +3107,9 @@ int aar_tracker_reset(aar_tracker *t) {
     if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_reset: null argument");
     t->n = 0;
     t->det_on = false;   // (the buffers stay; aar_tracker_enable_detections fills them again)
+    t->unc_set = false;  // (the device's marginal stays where it is: no push reads it while has_marginal is 0)
+    t->has_marginal = 0;
+    t->marginal_dropped = 0;
     return AAR_OK;
 }
 
@@ -3179,7 +3198,12 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
             a.lam[i][1] = 1.0 / (p.sigma_trans * p.sigma_trans * dt);
         }
     }
-    a.rows = 8.0 * (double)det + (p.smooth ? 6.0 * (double)(W - 1 + (has_anchor ? 1 : 0)) : 0.0);
+    const bool marginal = p.anchor_mode == AAR_TRACKER_ANCHOR_MARGINAL, tail = marginal || p.covariance;
+    a.anchor_pair = has_anchor && !marginal ? 1 : 0;
+    a.marginal = marginal ? 1 : 0; a.has_marginal = marginal ? t->has_marginal : 0; a.covariance = p.covariance;
+    a.unc = t->d_state + LIVE_ST_UNC;
+    // 6 rows per pair; the anchor pair's 6 are the marginal prior's in that mode (none after a dropped marginal)
+    a.rows = 8.0 * (double)det + (p.smooth ? 6.0 * (double)(W - 1 + (marginal ? a.has_marginal : has_anchor ? 1 : 0)) : 0.0);
     HIP_TRY(hipMemcpyAsync(t->d_ring + (size_t)ns * t->slot_bytes, t->h_stage, copy_bytes, hipMemcpyHostToDevice, t->stream));
     double *h_info = t->h_res + LIVE_RES_DOUBLES;
     if (raw) {
@@ -3206,7 +3230,11 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
         }
     }
     launch_live_push(a, t->stream);
-    HIP_TRY(hipMemcpyAsync(t->h_res, a.res, (LIVE_RES_DOUBLES + (raw ? LIVE_INFO_DOUBLES : 0)) * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    // one copy: the result, the start record (also when the tail's record behind it is wanted) and the uncertainty record up to the window's blocks
+    const size_t back = tail ? LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_HDR + (p.covariance ? 36 * (size_t)W : 0)
+                             : LIVE_RES_DOUBLES + (raw ? LIVE_INFO_DOUBLES : 0);
+    if (tail) t->unc_set = false;   // the copy overwrites the record aar_tracker_uncertainty serves: a push that fails from here on leaves none
+    HIP_TRY(hipMemcpyAsync(t->h_res, a.res, back * sizeof(double), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     int rc = check_async("k_live_push");
     if (rc) return rc;
@@ -3214,6 +3242,15 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
     t->times[ns] = frame_time;
     t->cnt[ns] = n_obs;
     t->n = n + 1;
+    if (tail) {
+        const double *u = t->h_res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
+        t->unc_set = true;
+        t->unc_W = W;
+        t->has_marginal = marginal && u[LIVE_UNC_HAS] != 0.0 ? 1 : 0;
+        if (marginal && u[LIVE_UNC_DROP] != 0.0) t->marginal_dropped++;
+        const double dof = a.rows - 6.0 * (double)W;
+        t->unc_sigma2 = dof > 0.0 ? t->h_res[4] / dof : 0.0;
+    }
     if (result) {
         aar_tracker_result r;
         memset(&r, 0, sizeof r);
@@ -3351,6 +3388,34 @@ int aar_tracker_enable_detections(aar_tracker *t, const aar_tracker_detection_pa
     p.cams = nullptr;   // (copied; the caller's array is not kept)
     t->det = p;
     t->det_on = true;
+    return AAR_OK;
+}
+
+int aar_tracker_uncertainty(aar_tracker *t, aar_tracker_uncertainty_record *out) {
+    if (!t || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_uncertainty: null argument");
+    if (t->prm.anchor_mode == AAR_TRACKER_ANCHOR_FIXED && !t->prm.covariance)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_uncertainty: the tracker was created with anchor_mode fixed and covariance = 0: nothing is kept");
+    if (!t->unc_set || t->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_uncertainty: no push since creation / reset");
+    if (out->struct_size < offsetof(aar_tracker_uncertainty_record, cov_valid) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_uncertainty: struct_size %u does not reach cov_valid", (unsigned)out->struct_size);
+    aar_tracker_uncertainty_record r;
+    memset(&r, 0, sizeof r);
+    const double *u = t->h_res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
+    const int W = t->unc_W;
+    r.struct_size = out->struct_size;
+    r.cov_valid = t->prm.covariance && u[LIVE_UNC_VALID] != 0.0 ? 1 : 0;
+    r.sigma2 = t->prm.covariance ? t->unc_sigma2 : 0.0;
+    r.window_frames = W;
+    for (int i = 0; i < W; i++) r.frame_index[i] = t->n - W + i;
+    if (r.cov_valid) memcpy(r.cov, u + LIVE_UNC_HDR, 36 * (size_t)W * sizeof(double));
+    r.has_marginal = t->has_marginal;
+    r.marginal_index = t->has_marginal ? t->n - W + 1 : -1;
+    if (t->has_marginal) {
+        memcpy(r.marginal_info, u + LIVE_UNC_LM, 36 * sizeof(double));
+        memcpy(r.marginal_mean, u + LIVE_UNC_M, 6 * sizeof(double));
+    }
+    r.marginal_dropped = t->marginal_dropped;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
     return AAR_OK;
 }
 

@@ -334,8 +334,20 @@ struct LiveArgs {
     double rows;                          // 8 detections of the window + 6 pairs
     int cnt[LIVE_MAX_W];                  // detections by window position
     double lam[LIVE_MAX_W][2];            // by window position: 1 / (sigma_rot^2 dt), 1 / (sigma_trans^2 dt) of the pair that ends there
+    // DESIGN.md section 19; marginal = covariance = 0 (and anchor_pair = has_anchor) = the kernel of section 17
+    int anchor_pair;                      // the first window frame carries the anchor pair: has_anchor, unless the anchor is marginalised
+    int marginal, has_marginal;           // marginalised anchor: no anchor pair; has_marginal: the prior in unc sits on the first window frame
+    int covariance;                       // the blocks of H^-1 at the final point
+    double *unc;                          // [LIVE_UNC_HDR + 36 LIVE_MAX_W] the uncertainty record (read: the prior; written: the next one)
 };
-void launch_live_push(const LiveArgs &a, hipStream_t st);   // ONE launch
+// the uncertainty record, behind the start record: cov_valid, the marginal is valid, it was dropped in this push, 0 | Lambda_m [36] | m [6] | 0 0
+// | Sigma_f [36] by window position
+constexpr int LIVE_UNC_VALID = 0, LIVE_UNC_HAS = 1, LIVE_UNC_DROP = 2, LIVE_UNC_LM = 4, LIVE_UNC_M = 40, LIVE_UNC_HDR = 48;
+constexpr int LIVE_UNC_DOUBLES = LIVE_UNC_HDR + 36 * LIVE_MAX_W;
+// a pivot of Lambda' below this fraction of the pair's own J_b^T L J_b diagonal counts as non-positive: what is left of an empty chain is
+// rounding noise of either sign around an exact 0
+constexpr double LIVE_MARGINAL_PIVOT_REL = 1e-10;
+void launch_live_push(const LiveArgs &a, hipStream_t st);   // ONE launch; the tail instance when marginal or covariance is set
 
 // the start of a frame pushed as raw detections (live_init_kernels.hip): undistortion, IPPE, the object pose candidates and
 // their vote in ONE launch of one workgroup, on the slot the frame was just copied into

@@ -16,6 +16,8 @@
 //   trial      the costs at z + delta, |delta_f|^2 and delta_f . b_f per frame
 //   decide     every thread adds the per-frame values in window order and takes the same accept / mu / exit decision
 // No atomics; every sum has one owner and a fixed order, so two trackers fed the same pushes give the same bits.
+// k_live_push<true> adds the marginal prior in the anchor pair's place and, behind the LM, a tail: one fresh assembly at the
+// final point, then on wavefront 0 the elimination at mu = 0, the marginal of the frame that leaves and the covariance blocks.
 #include "geom.hpp"
 #include "kernels.h"
 #include "pair_terms.hpp"
@@ -33,6 +35,13 @@ struct LiveShared {
     double lin[LIVE_MAX_W][2];                                          // |delta_f|^2, delta_f . b_f
     double za[6];                                                       // the anchor
     int flag;                                                           // a non-positive pivot in the last solve
+};
+
+// what the tail instance adds
+struct LiveTail {
+    double Lm[36], m[6];                // the marginal prior on the first window frame
+    double B[36], cB[6];                // the J_b half of pair (0, 1) alone: J_b^T L_1 J_b, -J_b^T L_1 e_0
+    double S[LIVE_MAX_W][36];           // the diagonal blocks of H^-1
 };
 
 __device__ __forceinline__ const char *live_slot(const LiveArgs &a, int i) {
@@ -76,7 +85,7 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
         }
         // the pair that ends here: this frame is its b side; for the first window frame the a side is the anchor, a constant
         double Pe = 0.0;
-        if (a.smooth && (i > 0 || a.has_anchor)) {
+        if (a.smooth && (i > 0 || a.anchor_pair)) {
             double zp[6], rowp[ENT_STRIDE];
             if (i > 0) {
                 ld6(s.z[i - 1], zp);
@@ -142,6 +151,33 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
                     for (int j = 0; j < 6; j++) s.D[i][6 * k + j] = D[k][j];
                 }
             }
+        }
+    }
+}
+
+// The marginal prior (z_0 - m)^T Lm (z_0 - m) on the first window frame, added by the wavefront that has just assembled that frame (wavefront 0,
+// behind its live_eval: lane 0 wrote the entries it now reads).  Its Jacobian is the identity: D_0 += Lm, b_0 -= Lm (z_0 - m), Pe[0] = E_m.
+template <bool WITH_J>
+__device__ __forceinline__ void live_prior(LiveShared &s, const LiveTail &tl, int lane) {
+    double e[6], Le[6], Pm = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) e[k] = (WITH_J ? s.z[0][k] : s.z[0][k] + s.dl[0][k]) - tl.m[k];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; j++) t = fma(tl.Lm[6 * k + j], e[j], t);
+        Le[k] = t;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) Pm = fma(e[k], Le[k], Pm);
+    if (lane == 0) {
+        s.Pe[WITH_J ? 0 : 1][0] = Pm;   // (no anchor pair in this mode: the entry held 0)
+        if (WITH_J) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) s.b[0][k] -= Le[k];
+#pragma unroll
+            for (int k = 0; k < 36; k++) s.D[0][k] += tl.Lm[k];
         }
     }
 }
@@ -227,8 +263,154 @@ __device__ __forceinline__ void live_solve(LiveShared &s, int W, double mu) {
     s.flag = ok ? 0 : 1;
 }
 
+// The tail, by wavefront 0 after the fresh assembly at the final point, every lane the same registers as in live_solve:
+//   elimination   live_solve at mu = 0 leaves P_f^-1 in s.inv
+//   marginal      Lambda' = B - O^T A^-1 O, b' = c - O^T A^-1 a, m' = z_1 + Lambda'^-1 b'   (A = D_0 = P_0, a = b_0, O = O_0)
+//   covariance    Sigma_{W-1} = P_{W-1}^-1, Sigma_f = P_f^-1 + G_f Sigma_{f+1} G_f^T, G_f = P_f^-1 O_f
+// Not inlined: it runs when the LM's registers are dead.
+__device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc, int W, int do_marginal, int do_cov, double lr, double lt, int lane) {
+    live_solve(s, W, 0.0);
+    const bool ok = s.flag == 0;
+    if (do_marginal) {
+        // the J_b half of pair (0, 1) alone (lr, lt: its weights): B = J_b^T L_1 J_b, c = -J_b^T L_1 e_0
+        {
+            double z0[6], z1[6], row0[ENT_STRIDE], row1[ENT_STRIDE], phi[3], et[3], Ma[9], Mb[9];
+            ld6(s.z[0], z0);
+            ld6(s.z[1], z1);
+            make_ent_row(z0, row0);
+            make_ent_row(z1, row1);
+            pair_terms<true>(row0, row1, nullptr, phi, et, Ma, Mb);
+#pragma unroll
+            for (int k = 0; k < 36; k++) tl.B[k] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+#pragma unroll
+                for (int j = 0; j < 3; j++) tl.B[6 * k + j] = lr * (Mb[k] * Mb[j] + Mb[3 + k] * Mb[3 + j] + Mb[6 + k] * Mb[6 + j]);
+                tl.B[7 * (3 + k)] = lt;
+                tl.cB[k] = -lr * (Mb[k] * phi[0] + Mb[3 + k] * phi[1] + Mb[6 + k] * phi[2]);
+                tl.cB[3 + k] = -lt * et[k];
+            }
+        }
+        double T[36], L[6][6], bp[6];
+        // T = O^T A^-1
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                double t = 0.0;
+#pragma unroll
+                for (int p = 0; p < 6; p++) t = fma(s.O[0][6 * p + i], s.inv[0][6 * p + k], t);
+                T[6 * i + k] = t;
+            }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+#pragma unroll
+            for (int k = 0; k <= i; k++) {
+                double t = 0.0;
+#pragma unroll
+                for (int p = 0; p < 6; p++) t = fma(T[6 * i + p], s.O[0][6 * p + k], t);
+                L[i][k] = tl.B[6 * i + k] - t;
+                L[k][i] = L[i][k];
+            }
+            double t = 0.0;
+#pragma unroll
+            for (int p = 0; p < 6; p++) t = fma(T[6 * i + p], s.b[0][p], t);
+            bp[i] = tl.cB[i] - t;
+        }
+        // the pivots of Lambda' against the pair's own information (L is consumed); the inverse only of a matrix that passed
+        double Lk[36], Li[36], mn[6];
+#pragma unroll
+        for (int i = 0; i < 36; i++) { Lk[i] = L[i / 6][i % 6]; Li[i] = 0.0; }
+        bool keep = ok;   // (ok: A = P_0 is among the elimination's pivots)
+#pragma unroll
+        for (int p = 0; p < 6; p++) {
+            const double d = L[p][p];
+            keep = keep && d > LIVE_MARGINAL_PIVOT_REL * tl.B[7 * p];
+            const double di = 1.0 / (keep ? d : 1.0);
+#pragma unroll
+            for (int r = p + 1; r < 6; r++)
+#pragma unroll
+                for (int c = p + 1; c <= r; c++) L[r][c] = fma(-L[r][p] * di, L[c][p], L[r][c]);
+        }
+        if (keep) {
+            double Lc[6][6];
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) Lc[i][k] = Lk[6 * i + k];
+            keep = spd6_inverse(Lc, Li);
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double t = 0.0;
+#pragma unroll
+            for (int p = 0; p < 6; p++) t = fma(Li[6 * i + p], bp[p], t);
+            mn[i] = s.z[1][i] + t;
+        }
+        // (the prior in tl was read by the assembly; nothing reads it after this point)
+#pragma unroll
+        for (int i = 0; i < 36; i++) tl.Lm[i] = keep ? Lk[i] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; i++) tl.m[i] = keep ? mn[i] : 0.0;
+        if (lane < 36) unc[LIVE_UNC_LM + lane] = tl.Lm[lane];
+        if (lane < 6) unc[LIVE_UNC_M + lane] = tl.m[lane];
+        if (lane == 0) { unc[LIVE_UNC_HAS] = keep ? 1.0 : 0.0; unc[LIVE_UNC_DROP] = keep ? 0.0 : 1.0; }
+    } else if (lane == 0) {
+        unc[LIVE_UNC_HAS] = 0.0;
+        unc[LIVE_UNC_DROP] = 0.0;
+    }
+    if (do_cov) {
+        double Sn[36];
+#pragma unroll
+        for (int i = 0; i < 36; i++) { Sn[i] = s.inv[W - 1][i]; tl.S[W - 1][i] = ok ? Sn[i] : 0.0; }
+        for (int f = W - 2; f >= 0; f--) {
+            double G[36], GS[36], Sf[36];
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int p = 0; p < 6; p++) t = fma(s.inv[f][6 * i + p], s.O[f][6 * p + k], t);
+                    G[6 * i + k] = t;
+                }
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    double t = 0.0;
+#pragma unroll
+                    for (int p = 0; p < 6; p++) t = fma(G[6 * i + p], Sn[6 * p + k], t);
+                    GS[6 * i + k] = t;
+                }
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k <= i; k++) {
+                    double t = s.inv[f][6 * i + k];
+#pragma unroll
+                    for (int p = 0; p < 6; p++) t = fma(GS[6 * i + p], G[6 * k + p], t);
+                    Sf[6 * i + k] = t;
+                    Sf[6 * k + i] = t;
+                }
+#pragma unroll
+            for (int i = 0; i < 36; i++) { Sn[i] = Sf[i]; tl.S[f][i] = ok ? Sf[i] : 0.0; }
+        }
+        for (int k = lane; k < 36 * W; k += 64) unc[LIVE_UNC_HDR + k] = tl.S[k / 36][k % 36];
+        if (lane == 0) unc[LIVE_UNC_VALID] = ok ? 1.0 : 0.0;
+    } else if (lane == 0) {
+        unc[LIVE_UNC_VALID] = 0.0;
+    }
+}
+
+template <bool TAIL>
 __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
     __shared__ LiveShared s;
+    LiveTail *tl = nullptr;
+    if constexpr (TAIL) {
+        __shared__ LiveTail tail;
+        tl = &tail;
+    }
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform
     const int W = a.W;
     TrackArgs ta;
@@ -256,9 +438,18 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
             if (sl >= a.slots) sl -= a.slots;
             s.z[i][k] = a.zslot[6 * sl + k];
         }
+        if constexpr (TAIL) {
+            if (a.marginal && a.has_marginal && t >= 192 && t < 192 + 42) {
+                if (t < 192 + 36) tl->Lm[t - 192] = a.unc[LIVE_UNC_LM + t - 192];
+                else tl->m[t - 228] = a.unc[LIVE_UNC_M + t - 228];
+            }
+        }
     }
     __syncthreads();
+    bool prior = false;   // the marginal prior is on the first window frame (tail instance only)
+    if constexpr (TAIL) prior = a.marginal && a.has_marginal && wv == 0;
     live_eval<true>(a, ta, s, wv, lane);   // init: the first evaluation also yields the first step's system
+    if constexpr (TAIL) { if (prior) live_prior<true>(s, *tl, lane); }
     __syncthreads();
     double currData = 0.0, currPrior = 0.0;
     for (int i = 0; i < W; i++) { currData += s.Ef[0][i]; currPrior += s.Pe[0][i]; }
@@ -269,6 +460,7 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
     for (int it = 0; it < a.max_iters && !mustExit && rows > 0; it++) {
         if (it > 0) {
             live_eval<true>(a, ta, s, wv, lane);   // H, b at the current point (its costs are those already held)
+            if constexpr (TAIL) { if (prior) live_prior<true>(s, *tl, lane); }
             __syncthreads();
         }
         if (mu < 0) {
@@ -285,6 +477,7 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
             if (wv == 0) live_solve(s, W, mu);
             __syncthreads();
             live_eval<false>(a, ta, s, wv, lane);
+            if constexpr (TAIL) { if (prior) live_prior<false>(s, *tl, lane); }
             __syncthreads();
             double eD = 0.0, eP = 0.0, d2 = 0.0, dg = 0.0;
             for (int i = 0; i < W; i++) { eD += s.Ef[1][i]; eP += s.Pe[1][i]; d2 += s.lin[i][0]; dg += s.lin[i][1]; }
@@ -329,12 +522,26 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
         a.res[4] = currErr; a.res[5] = currData; a.res[6] = currPrior; a.res[7] = mu;
         a.res[20] = (double)tries; a.res[21] = 0.0; a.res[22] = 0.0; a.res[23] = 0.0;
     }
+    if constexpr (TAIL) {
+        // one fresh system at the final point, mu = 0, for the marginal of the frame that leaves and for the covariance
+        const int do_marginal = a.marginal && W == a.slots, do_cov = a.covariance;
+        __syncthreads();   // the stores above have read the costs this assembly writes again
+        if (do_marginal || do_cov) {
+            live_eval<true>(a, ta, s, wv, lane);
+            if (prior) live_prior<true>(s, *tl, lane);
+            __syncthreads();
+            if (wv == 0) live_tail(s, *tl, a.unc, W, do_marginal, do_cov, a.lam[1][0], a.lam[1][1], lane);
+        } else if (t < 3) {
+            a.unc[t] = 0.0;   // LIVE_UNC_VALID, _HAS, _DROP: the window is still filling
+        }
+    }
 }
 
 }  // namespace
 
 void launch_live_push(const LiveArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL(k_live_push, dim3(1), dim3(256), 0, st, a);
+    if (a.marginal || a.covariance) hipLaunchKernelGGL(k_live_push<true>, dim3(1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_live_push<false>, dim3(1), dim3(256), 0, st, a);
 }
 
 }  // namespace aar

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -207,9 +207,13 @@ int main(int argc, char *argv[]) {
     bool live = false, from_detections = false;
     int start_policy = AAR_TRACKER_START_VOTE;
     int live_lag = -1, live_args = 0;
+    // ... -anchor marginal marginalises the frame that leaves the window instead of freezing it (needs the sigmas and a lag >= 1); -live-covariance
+    // also writes every frame's lagged 6x6 covariance block and sigma2 to final<name>.covariance.yaml beside the poses
+    int live_anchor = AAR_TRACKER_ANCHOR_FIXED;
+    bool live_anchor_set = false, live_covariance = false;
     double live_sigma[2] = {0.0, 0.0};
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, Smooth, Live } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, Smooth, Live, Anchor } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -230,6 +234,13 @@ int main(int argc, char *argv[]) {
         else if (a == "-prior-sigma-m") arg_flag = PriorM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
+        else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
+        else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
+        else if (arg_flag == Anchor) {
+            if (a != "fixed" && a != "marginal") return print_usage(argv[0]);
+            live_anchor = a == "marginal" ? AAR_TRACKER_ANCHOR_MARGINAL : AAR_TRACKER_ANCHOR_FIXED;
+            arg_flag = NONE;
+        }
         else if (a == "-from-detections") {
             from_detections = true; arg_flag = NONE;
             if (i + 1 < argc && (string(argv[i + 1]) == "vote" || string(argv[i + 1]) == "best"))
@@ -285,6 +296,8 @@ int main(int argc, char *argv[]) {
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
+    if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
+    if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
     if (from_detections && (!live || from_initial || use_subseqs || !excluded_cams.empty())) return print_usage(argv[0]);
     string name = "";
     if (tracking_only) name += "_tracking_only";
@@ -383,18 +396,20 @@ int main(int argc, char *argv[]) {
     }
     const auto start = chrono::system_clock::now();
     if (live) {
+        aar::MultiCamMapper::LiveCovariance live_cov;
+        aar::MultiCamMapper::LiveCovariance *want_cov = live_covariance ? &live_cov : nullptr;
         try {
             if (from_detections) {
                 aar_detections *detections = aar::Initializer::read_detections_file(folder_path + "/aruco.detections", vector<int>());
                 try {
-                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy);
+                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy, live_anchor, want_cov);
                 } catch (...) {
                     aar_detections_free(detections);
                     throw;
                 }
                 aar_detections_free(detections);
             } else {
-                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1]);
+                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1], live_anchor, want_cov);
             }
             long long its = 0, rej = 0;
             double sec = 0, cost = 0;
@@ -412,6 +427,15 @@ int main(int argc, char *argv[]) {
         }
         mcm.write_solution_file(final_path);
         mcm.write_text_solution_file(final_path + ".yaml");
+        if (live_covariance) {
+            const string cov_path = final_path + ".covariance.yaml";
+            if (!mcm.write_live_covariance_file(cov_path, live_cov)) {
+                cerr << "live covariance: " << aar_last_error() << endl;
+                return 6;
+            }
+            cout << "live covariance: " << live_cov.valid.size() << " lagged blocks (anchor " << (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL ? "marginal" : "fixed")
+                 << ") written to " << cov_path << endl;
+        }
         return 0;
     }
     try {

@@ -568,7 +568,27 @@ void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans) {
 
 // The live loop over the data set's frames (aar_tracker_*): what apps/track.cpp does per incoming frame, with the
 // mapper's own frames as the stream.
-void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double sigma_trans) {
+namespace {
+// the covariance blocks of the window after a push: a frame keeps those of the last push it was in the window of -- its lagged block
+void take_live_covariance(LiveTracker &lt, MultiCamMapper::LiveCovariance *cov) {
+    if (!cov) return;
+    const aar_tracker_uncertainty_record u = lt.uncertainty();
+    for (int i = 0; i < u.window_frames; i++) {
+        const size_t f = (size_t)u.frame_index[i];
+        memcpy(&cov->frame_cov[36 * f], u.cov[i], sizeof u.cov[i]);
+        cov->sigma2[f] = u.sigma2;
+        cov->valid[f] = u.cov_valid ? 1 : 0;
+    }
+}
+void size_live_covariance(MultiCamMapper::LiveCovariance *cov, int F) {
+    if (!cov) return;
+    cov->frame_cov.assign(36 * (size_t)F, 0.0);
+    cov->sigma2.assign((size_t)F, 0.0);
+    cov->valid.assign((size_t)F, 0);
+}
+}  // namespace
+
+void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double sigma_trans, int anchor_mode, LiveCovariance *covariance) {
     if (!data_) throw std::runtime_error("MultiCamMapper::track_live: no data set");
     hubberDelta = 10;  // as track()
     const int F = data_->num_frames;
@@ -579,7 +599,9 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
     LiveTracker::Options o;
     o.lag = lag; o.smooth = smooth; o.sigma_rot = sigma_rot; o.sigma_trans = sigma_trans;
     o.with_huber = with_huber_; o.huber_delta = hubberDelta; o.max_obs_per_frame = (int)most; o.device_id = device_id;
+    o.anchor_mode = anchor_mode; o.covariance = covariance != nullptr;
     LiveTracker lt(*this, o, &solver_params);
+    size_live_covariance(covariance, F);
     PoseLayout L;
     L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
     std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
@@ -596,6 +618,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
         }
         const aar_tracker_result r = lt.push((double)data_->frame_ids[f], det, data_->x_full + L.full_fr0() + 6LL * f);
         live_results[f] = r;
+        take_live_covariance(lt, covariance);
         if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
     }
     const LiveTracker::Window w = lt.window();   // the frames that never left the window
@@ -605,7 +628,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
 }
 
 void MultiCamMapper::track_live_from_detections(const aar_detections *det, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
-                                                double sigma_trans, int start_policy) {
+                                                double sigma_trans, int start_policy, int anchor_mode, LiveCovariance *covariance) {
     if (!data_ || !det) throw std::runtime_error("MultiCamMapper::track_live_from_detections: no data set / no detections");
     hubberDelta = 10;  // as track()
     const int F = data_->num_frames;
@@ -620,7 +643,9 @@ void MultiCamMapper::track_live_from_detections(const aar_detections *det, const
     LiveTracker::Options o;
     o.lag = lag; o.smooth = smooth; o.sigma_rot = sigma_rot; o.sigma_trans = sigma_trans;
     o.with_huber = with_huber_; o.huber_delta = hubberDelta; o.max_obs_per_frame = (int)most; o.device_id = device_id;
+    o.anchor_mode = anchor_mode; o.covariance = covariance != nullptr;
     LiveTracker lt(*this, o, &solver_params);
+    size_live_covariance(covariance, F);
     LiveTracker::DetectionOptions dopt;
     for (int c = 0; c < data_->num_cams; c++) {
         const int id = data_->cam_ids[c];
@@ -648,12 +673,18 @@ void MultiCamMapper::track_live_from_detections(const aar_detections *det, const
             }
         const aar_tracker_result r = lt.push_detections((double)data_->frame_ids[f], dets, nullptr, &live_starts[f]);
         live_results[f] = r;
+        take_live_covariance(lt, covariance);
         if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
     }
     const LiveTracker::Window w = lt.window();   // the frames that never left the window
     for (size_t i = 0; i < w.frame_index.size(); i++) memcpy(&z[6 * (size_t)w.frame_index[i]], w.poses[i].data(), 6 * sizeof(double));
     memcpy(data_->x_full + L.full_fr0(), z.data(), z.size() * sizeof(double));
     mats2eVec();
+}
+
+bool MultiCamMapper::write_live_covariance_file(const std::string &path, const LiveCovariance &cov) {
+    if (!data_ || cov.valid.size() != (size_t)data_->num_frames) return false;
+    return aar_tracker_covariance_write_yaml(path.c_str(), data_, cov.frame_cov.data(), cov.sigma2.data(), cov.valid.data()) == AAR_OK;
 }
 
 LiveTracker::LiveTracker(const MultiCamMapper &solution, const Options &o, const SparseLevMarq<double>::Params *lm) {
@@ -665,6 +696,7 @@ LiveTracker::LiveTracker(const MultiCamMapper &solution, const Options &o, const
     aar_tracker_default_params(&p);
     p.lag = o.lag; p.smooth = o.smooth ? 1 : 0; p.sigma_rot = o.sigma_rot; p.sigma_trans = o.sigma_trans;
     p.with_huber = o.with_huber ? 1 : 0; p.huber_delta = o.huber_delta; p.max_obs_per_frame = o.max_obs_per_frame; p.device_id = o.device_id;
+    p.anchor_mode = o.anchor_mode; p.covariance = o.covariance ? 1 : 0;
     aar_lm_params q;
     aar_lm_default_params(&q);
     if (lm) {
@@ -747,6 +779,14 @@ LiveTracker::Window LiveTracker::window() {
     w.has_anchor = has != 0;
     if (has) memcpy(w.anchor_pose.data(), anchor, sizeof anchor);
     return w;
+}
+
+aar_tracker_uncertainty_record LiveTracker::uncertainty() {
+    aar_tracker_uncertainty_record u;
+    memset(&u, 0, sizeof u);
+    u.struct_size = sizeof u;
+    if (aar_tracker_uncertainty(tracker_, &u)) throw std::runtime_error(aar_last_error());
+    return u;
 }
 
 void LiveTracker::reset() {

@@ -397,12 +397,22 @@ class MultiCamMapper {
     // no counterpart in the reference as a method: apps/track.cpp's loop (:102-136) over the data set's frames, one frame per push through a
     // LiveTracker (below): each frame starts from its own pose in the data set, the frame ids are the time axis; every frame ends at its lagged
     // pose, the last window at aar_tracker_window's.  smooth = false needs lag = 0.  The pushes' results land in live_results.
-    void track_live(int lag, bool smooth, double sigma_rot, double sigma_trans);
+    // anchor_mode AAR_TRACKER_ANCHOR_MARGINAL (needs smooth and lag >= 1) marginalises the frame that leaves the window instead of freezing it;
+    // covariance != NULL also asks for the per-push covariance and receives every frame's lagged block.
+    struct LiveCovariance {
+        std::vector<double> frame_cov;   // [num_frames][36] the unscaled 6x6 block of H^-1 of the last push that had the frame in its window
+        std::vector<double> sigma2;      // [num_frames] that push's sigma2: the pose covariance is sigma2[f] * frame_cov[f]
+        std::vector<uint8_t> valid;      // [num_frames] that push's cov_valid
+    };
+    void track_live(int lag, bool smooth, double sigma_rot, double sigma_trans, int anchor_mode = AAR_TRACKER_ANCHOR_FIXED,
+                    LiveCovariance *covariance = nullptr);
     // ... the whole of that loop (:117-133): every frame of the data set is fed the RAW detections that carry its frame id (cams: calibrations by
     // camera ID, as the Initializer takes them) and starts from its own vote (start_policy AAR_TRACKER_START_VOTE) or from the cheaper of vote
     // and previous estimate (AAR_TRACKER_START_BEST); the data set's own object poses are not read.  The starts land in live_starts.
     void track_live_from_detections(const aar_detections *detections, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
-                                    double sigma_trans, int start_policy = AAR_TRACKER_START_VOTE);
+                                    double sigma_trans, int start_policy = AAR_TRACKER_START_VOTE, int anchor_mode = AAR_TRACKER_ANCHOR_FIXED,
+                                    LiveCovariance *covariance = nullptr);
+    bool write_live_covariance_file(const std::string &path, const LiveCovariance &cov);   // YAML, aar_tracker_covariance_write_yaml
     void error_function(const eVector &input, eVector &error);  // :731-737
     // :739-801 (private in the reference; public here so that reference-shaped caller code outside the class can bind it).  The
     // Jacobian of the accelerated path is analytic and never leaves the device: called by the solver mirror's probe it names
@@ -550,6 +560,8 @@ class LiveTracker {
         float huber_delta = 2.5f;
         int max_obs_per_frame = 256;
         int device_id = 0;
+        int anchor_mode = AAR_TRACKER_ANCHOR_FIXED;   // AAR_TRACKER_ANCHOR_MARGINAL needs smooth and lag >= 1
+        bool covariance = false;                      // every push leaves the window's covariance blocks for uncertainty()
     };
     struct Window {
         std::vector<int64_t> frame_index;
@@ -576,6 +588,8 @@ class LiveTracker {
     aar_tracker_result push_detections(double frame_time, const std::vector<Detection> &detections, const double *start = nullptr,
                                        aar_tracker_start_info *info = nullptr);
     Window window();
+    // aar_tracker_uncertainty: the record of the last push (needs anchor_mode marginal or covariance, and a push since construction / reset)
+    aar_tracker_uncertainty_record uncertainty();
     void reset();
 
    private:

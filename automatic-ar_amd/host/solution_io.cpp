@@ -305,6 +305,23 @@ int aar_covariance_write_yaml(const char *path, const aar_dataset *d, const doub
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
 }
 
+int aar_tracker_covariance_write_yaml(const char *path, const aar_dataset *d, const double *frame_cov, const double *frame_sigma2, const uint8_t *valid) {
+    if (!path || !d || !frame_cov || !frame_sigma2 || !valid) return set_error(AAR_ERR_INVALID, "aar_tracker_covariance_write_yaml: null argument");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    std::vector<double> nan_blk(36, NAN);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "object_poses:\n");
+    for (int i = 0; i < d->num_frames; i++)
+        yaml_cov_block(f, "frame_id", d->frame_ids[i], valid[i] ? frame_cov + 36LL * i : nan_blk.data(), valid[i] ? frame_sigma2[i] : 1.0);
+    fprintf(f, "frame_sigma2:\n");
+    for (int i = 0; i < d->num_frames; i++)
+        fprintf(f, "   - { frame_id:%d, sigma2: %s }\n", d->frame_ids[i], fs_double_nf(valid[i] ? frame_sigma2[i] : NAN).c_str());
+    const bool good = !ferror(f);
+    fclose(f);
+    return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
+}
+
 int aar_residual_report_write_yaml(const char *path, const aar_dataset *d, const double *cam_stats, const double *marker_stats, const double *det_err,
                                    const uint8_t *keep, const aar_residual_report *rep) {
     if (!path || !d || !cam_stats || !marker_stats || !rep || (!det_err != !keep)) return set_error(AAR_ERR_INVALID, "aar_residual_report_write_yaml: null argument");

@@ -588,6 +588,8 @@ int aar_track_smooth_system(aar_problem *, const double *x_full, const aar_smoot
  * result.  Two trackers fed the same pushes give the same bits.  A rejected push (AAR_ERR_INVALID, the message names the entry) leaves the
  * tracker exactly as it was.  Structs are size-versioned: the caller sets struct_size. */
 #define AAR_TRACKER_MAX_LAG 15
+#define AAR_TRACKER_ANCHOR_FIXED 0      /* the frame that leaves the window becomes a constant (above) */
+#define AAR_TRACKER_ANCHOR_MARGINAL 1   /* ... is marginalised into a 6x6 Gaussian prior on the frame behind it (below) */
 typedef struct aar_tracker aar_tracker;
 typedef struct aar_tracker_params {
     uint32_t struct_size;
@@ -599,6 +601,8 @@ typedef struct aar_tracker_params {
     float huber_delta;           /* pixels, > 0 finite when with_huber */
     int32_t max_obs_per_frame;   /* >= 1: detections one push may carry (sizes the ring) */
     int32_t device_id;
+    int32_t anchor_mode;         /* AAR_TRACKER_ANCHOR_FIXED (default) | AAR_TRACKER_ANCHOR_MARGINAL (needs smooth = 1 and lag >= 1) */
+    int32_t covariance;          /* 0 | 1: every push also leaves the window's pose covariance blocks for aar_tracker_uncertainty */
 } aar_tracker_params;
 typedef struct aar_tracker_result {
     uint32_t struct_size;
@@ -616,7 +620,8 @@ typedef struct aar_tracker_result {
 void aar_tracker_default_params(aar_tracker_params *);   /* struct_size set; lag 0, smooth 0, no Huber (delta 2.5), 256 detections, device 0 */
 /* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the field: lag out of range, smooth = 0 with lag > 0, a
  * sigma that is not positive and finite when smooth is set, huber_delta likewise when with_huber is set, max_obs_per_frame < 1, a malformed
- * solution (sizes, roots, null arrays, a non-finite camera / marker pose or marker_size). */
+ * solution (sizes, roots, null arrays, a non-finite camera / marker pose or marker_size), an unknown anchor_mode, AAR_TRACKER_ANCHOR_MARGINAL
+ * with smooth = 0 or lag = 0, covariance not 0 / 1.  A struct_size that ends before anchor_mode means fixed anchor, no covariance. */
 int aar_tracker_params_validate(const aar_dataset *solution, const aar_tracker_params *);
 int aar_tracker_create(const aar_dataset *solution, const aar_tracker_params *, const aar_lm_params * /* NULL = defaults */, aar_tracker **out);
 /* obs_cam / obs_marker: INDICES into the solution's cameras / markers, obs_uv: [n_obs][8] undistorted corners, pose_init: [6] (rvec, t) or NULL.
@@ -628,7 +633,46 @@ int aar_tracker_push(aar_tracker *, double frame_time, int32_t n_obs, const int3
  * cost of the pair that ENDS at the frame (entry 0: the anchor pair, 0 without an anchor), anchor_pose, has_anchor.  Any output may be NULL. */
 int aar_tracker_window(aar_tracker *, int32_t *n, int64_t *frame_index, double *poses, double *frame_err, double *pair_err, double anchor_pose[6],
                        int32_t *has_anchor);
-int aar_tracker_reset(aar_tracker *);     /* forgets all frames (and aar_tracker_enable_detections), keeps the solution */
+int aar_tracker_reset(aar_tracker *);     /* forgets all frames, the marginal prior (and aar_tracker_enable_detections), keeps the solution */
+
+/* Marginalised anchor and per-push pose covariance.  Both are off by default, and then a push runs the same kernel and
+ * gives the same bits as before they existed; with either set a push is still one launch and one copy back.
+ *   anchor_mode = AAR_TRACKER_ANCHOR_MARGINAL (smooth = 1, lag >= 1; lag = 0 is refused and left for later: the next pair's time step is not
+ *     known when the frame leaves).  The anchor pair is replaced by a prior on the first window frame, E_m(z_0) = (z_0 - m)^T L_m (z_0 - m),
+ *     which counts 6 rows where the anchor pair did.  At the end of every push with a full window the oldest frame is marginalised at the final
+ *     point z^: from one fresh system at mu = 0, with A, a the first diagonal block and right-hand side (old prior, E_0 and the J_a half of pair
+ *     (0, 1)), O the first off-diagonal block and B, c the J_b half of pair (0, 1) alone,
+ *         L' = B - O^T A^-1 O,   b' = c - O^T A^-1 a,   m' = z^_1 + L'^-1 b'
+ *     and (L', m') is the prior of the next push.  When L' has a non-positive pivot -- below 1e-10 of the matching diagonal entry of B, which is
+ *     how an exact 0 shows in floating point: a leaving frame with neither prior nor detections -- the next push carries no prior and
+ *     marginal_dropped counts it.  The fixed anchor_pose of aar_tracker_window is still kept.
+ *   covariance = 1 (any anchor_mode, also smooth = 0): from the same fresh system, the diagonal 6x6 blocks of H^-1 (H = J^T J over the window's
+ *     6 W unknowns, prior and pairs included) for every window frame, by the block elimination's backward recursion.  They are reported
+ *     UNSCALED with sigma2 = final_cost / (rows - 6 W), 0 when rows <= 6 W (the convention of aar_problem_covariance).  A non-positive pivot
+ *     (smooth = 0 on a frame without detections) gives cov_valid = 0 and zeros.
+ * aar_tracker_uncertainty is served from the host copy of the last accepted push (no device work) and describes the tracker after that push:
+ * cov [i] belongs to frame_index [i], oldest first; has_marginal / marginal_index / marginal_info / marginal_mean are the prior the NEXT push
+ * will put on frame marginal_index.  AAR_ERR_INVALID before any push, after a reset, with both options off, or after a push that failed with
+ * AAR_ERR_HIP (its copy has overwritten the record; a push rejected with AAR_ERR_INVALID leaves it as it was).  out is size-versioned. */
+typedef struct aar_tracker_uncertainty_record {
+    uint32_t struct_size;
+    int32_t cov_valid;
+    double sigma2;
+    int32_t window_frames;
+    int32_t has_marginal;
+    int64_t frame_index[AAR_TRACKER_MAX_LAG + 1];
+    double cov[AAR_TRACKER_MAX_LAG + 1][36];   /* row-major 6x6 over (rvec, t), zeros past window_frames */
+    int64_t marginal_index;      /* -1 without a marginal */
+    double marginal_info[36];    /* L_m, row-major */
+    double marginal_mean[6];     /* m */
+    int64_t marginal_dropped;    /* pushes since creation / reset whose marginal was dropped */
+} aar_tracker_uncertainty_record;
+int aar_tracker_uncertainty(aar_tracker *, aar_tracker_uncertainty_record *out);
+/* The lagged covariance blocks of a live run as YAML, in aar_covariance_write_yaml's dialect: object_poses holds one record per frame of d
+ * (frame_id, sigma_rot, sigma_trans, covariance = frame_sigma2[f] * frame_cov[f], a block of NaN where valid[f] is 0), frame_sigma2 one
+ * { frame_id, sigma2 } per frame.  frame_cov: [num_frames][36] unscaled, frame_sigma2 / valid: [num_frames]. */
+int aar_tracker_covariance_write_yaml(const char *path, const aar_dataset *d, const double *frame_cov, const double *frame_sigma2,
+                                      const uint8_t *valid);
 
 /* The live tracker fed RAW detections: the first half of apps/track.cpp's loop (:117-133) on the device as well.  Per push
  * the frame's corners are undistorted with the camera's K and up to AAR_MAX_DIST coefficients (they replace the raw ones in the window, so the

@@ -65,7 +65,15 @@ def main():
         print("config %d: %d cameras, %d markers, %.1f detections per frame (at most %d), %d pushes after %d warm-up" % (
             cfg, ds.num_cams, ds.num_markers, ds.num_obs / n, most, a.pushes, a.warmup))
         for label, kw in (("smooth 0", dict(lag=0, smooth=False)), ("smooth 1 lag 0", dict(lag=0, smooth=True)),
-                          ("smooth 1 lag 4", dict(lag=4, smooth=True)), ("smooth 1 lag 15", dict(lag=15, smooth=True))):
+                          ("smooth 1 lag 4", dict(lag=4, smooth=True)), ("smooth 1 lag 15", dict(lag=15, smooth=True)),
+                          # the tail instance of k_live_push (still one launch per push)
+                          ("lag 4 marginal", dict(lag=4, smooth=True, anchor="marginal")),
+                          ("lag 4 covariance", dict(lag=4, smooth=True, covariance=True)),
+                          ("lag 4 both", dict(lag=4, smooth=True, anchor="marginal", covariance=True)),
+                          ("lag 15 marginal", dict(lag=15, smooth=True, anchor="marginal")),
+                          ("lag 15 covariance", dict(lag=15, smooth=True, covariance=True)),
+                          ("lag 15 both", dict(lag=15, smooth=True, anchor="marginal", covariance=True)),
+                          ("smooth 0 covar.", dict(lag=0, smooth=False, covariance=True))):
             if kw["smooth"]:
                 kw.update(sigma_rot=0.05, sigma_trans=0.02)
             wall, lib, its = [], [], []
