@@ -223,6 +223,33 @@ class ReducedSystem:
             Dinv[s, s] = np.linalg.inv(A[s, s])
         return Dinv
 
+    # ---- the absolute-value sums of the direct chain's rounding bound (tests/direct_certificate.py) ----
+    def frame_conds(self):
+        """cond_2 of every damped frame block V_f [F]: the device inverts V_f, that inverse's error enters with this factor"""
+        return np.linalg.cond(self.V) if self.F else np.zeros(0)
+
+    def abs_sums(self):
+        """the sums below, computed once per system"""
+        if not hasattr(self, "_abs"):
+            self._abs = self._abs_sums()
+        return self._abs
+
+    def _abs_sums(self):
+        """(|U| + sum_f kappa_f |W_f| |V_f^-1| |W_f^T|  [n][n],  |g_s| + sum_f kappa_f |W_f| |V_f^-1| |g_f|  [n]) with fp64 W: what the terms of A
+        and b add up to in absolute value, every frame's share weighted with the condition number of the block that is inverted for it"""
+        n = len(self.ent)
+        if not self.F:
+            return np.abs(self.U), np.abs(self.gs)
+        Wa = np.abs(self.W64)
+        T = np.einsum("efi,fij->efj", Wa, self.frame_conds()[:, None, None] * np.abs(self.Vinv))
+        EA = np.abs(self.U) + T.reshape(n, 6 * self.F) @ Wa.reshape(n, 6 * self.F).T
+        Eb = np.abs(self.gs) + np.einsum("efj,fj->e", T, np.abs(self.gf))
+        return EA, Eb
+
+    def frames_seen(self):
+        """per entity unknown: the number of frames whose W block has an entry in its row"""
+        return (self.W64 != 0.0).any(axis=2).sum(axis=1) if self.F else np.zeros(len(self.ent), int)
+
     def energy_norms(self, ds_, w32=None):
         """(r^T D^-1 r, b^T D^-1 b, b^T A^-1 b)"""
         A, b = self._pick(w32)
