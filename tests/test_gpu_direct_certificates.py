@@ -19,8 +19,6 @@ Ratios: every certified step's |r| / bar and worst frame ratio are collected per
 steps, worst, median.  The float64 reference's ratios on the same data sets are in tests/test_direct_certificate_host.py (worst 1.1e-3, medians
 2e-5 .. 3e-4); NO DEVICE RATIO HAS BEEN MEASURED YET -- this module has not run on an MI355X, none of its families.
 """
-import threading
-
 import numpy as np
 import pytest
 
@@ -28,6 +26,7 @@ import aar
 import direct_cases as dc
 import oracle_lib as ol
 from conftest import load_golden
+from direct_cases import ldl_env as _ldl_env, ldl_expected as _ldl_expected, run_ranks as _run_ranks
 from direct_certificate import build_system, certify_direct, entity_blocks
 from reduced_system import slot_col
 
@@ -94,28 +93,6 @@ def test_tile_sweep(nT, mfma, monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # LDL^T launch structures
-def _ldl_expected(nT, fused, lookahead, bs_rides):
-    """launches of one factorisation (launch_chol, solve_kernels.hip)"""
-    panel = trsm = update = 0
-    for s in range(nT):
-        m = nT - s - 1
-        if 0 < m <= fused:
-            panel += 1
-        elif m > 0:
-            trsm += 1
-            if not (lookahead and m >= 2):
-                update += 1
-    back = 1 if nT > 1 and not (bs_rides and nT <= 3) else 0
-    return dict(k_ldl_diag=nT, k_ldl_panel=panel, k_ldl_trsm=trsm, k_ldl_update=update, k_ldl_backsolve=back)
-
-
-def _ldl_env(monkeypatch, fused=3, lookahead=1, bs_rides=1, backsub_rides=0):
-    monkeypatch.setenv("AAR_FUSED_PANEL", str(fused))
-    monkeypatch.setenv("AAR_LDL_LOOKAHEAD", str(lookahead))
-    monkeypatch.setenv("AAR_BS_RIDES", str(bs_rides))
-    monkeypatch.setenv("AAR_BACKSUB_RIDES", str(backsub_rides))
-
-
 def _launch_counts(p, ds, mu):
     p.set_kernel_profiling(True)
     p.eval_damped_step(np.asarray(ds.x_full, dtype=np.float64), mu)
@@ -334,29 +311,6 @@ def test_features(feature):
     kw = dict(huber=dict(with_huber=True), intrinsics=dict(intrinsics=True), priors=dict(priors=_priors(ds, np.asarray(ds.x_full))))[feature]
     with _problem(ds, **kw) as p:
         _certify("features", feature, p, ds, intr=feature == "intrinsics")       # (the device's H carries the Huber weights and the priors' blocks)
-
-
-def _run_ranks(world, fn):
-    grp = aar.LocalGroup(world)
-    out, errs = [None] * world, []
-
-    def run(rank):
-        try:
-            comm = aar.Comm.local(grp, rank)
-            try:
-                out[rank] = fn(comm, rank)
-            finally:
-                comm.close()
-        except Exception as e:      # noqa: BLE001
-            errs.append((rank, e))
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join()
-    grp.close()
-    assert not errs, errs
-    return out
 
 
 @pytest.mark.parametrize("pack", ["0", "1"])
