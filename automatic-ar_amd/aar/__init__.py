@@ -43,7 +43,11 @@ SYMBOLS = [
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
     "aar_tracker_push_detections", "aar_tracker_uncertainty", "aar_tracker_covariance_write_yaml",
+    "aar_tracker_bank_params_validate", "aar_tracker_bank_create", "aar_tracker_bank_size", "aar_tracker_bank_push",
+    "aar_tracker_bank_enable_detections", "aar_tracker_bank_push_detections", "aar_tracker_bank_window", "aar_tracker_bank_uncertainty",
+    "aar_tracker_bank_reset", "aar_tracker_bank_get_stats", "aar_tracker_bank_destroy",
 ]
+TRACKER_BANK_MAX_MEMBERS = 1024
 TRACKER_MAX_LAG = 15
 TRACKER_START_VOTE, TRACKER_START_BEST = 1, 2
 TRACKER_ANCHOR_FIXED, TRACKER_ANCHOR_MARGINAL = 0, 1
@@ -242,6 +246,11 @@ class CTrackerUncertainty(C.Structure):
                 ("marginal_info", C.c_double * 36), ("marginal_mean", C.c_double * 6), ("marginal_dropped", C.c_int64)]
 
 
+class CTrackerBankStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("members", C.c_int32), ("pushes", C.c_int64), ("launches", C.c_int64), ("h2d_copies", C.c_int64),
+                ("h2d_bytes", C.c_int64), ("d2h_copies", C.c_int64), ("d2h_bytes", C.c_int64)]
+
+
 class CTrackerResult(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("frame_index", C.c_int64), ("window_frames", C.c_int32), ("iterations", C.c_int32),
                 ("stop_code", C.c_int32), ("rejected_tries", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
@@ -421,6 +430,22 @@ def lib():
     L.aar_tracker_covariance_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.POINTER(C.c_uint8)]
     L.aar_tracker_destroy.argtypes = [C.c_void_p]
     L.aar_tracker_destroy.restype = None
+    dsp, u8p = C.POINTER(C.POINTER(CDataset)), C.POINTER(C.c_uint8)
+    L.aar_tracker_bank_params_validate.argtypes = [C.c_int32, dsp, C.POINTER(CTrackerParams)]
+    L.aar_tracker_bank_create.argtypes = [C.c_int32, dsp, C.POINTER(CTrackerParams), C.POINTER(CLmParams), C.POINTER(C.c_void_p)]
+    L.aar_tracker_bank_size.argtypes = [C.c_void_p]
+    L.aar_tracker_bank_size.restype = C.c_int32
+    L.aar_tracker_bank_push.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                        dp, u8p, C.POINTER(CTrackerResult)]
+    L.aar_tracker_bank_enable_detections.argtypes = [C.c_void_p, C.POINTER(C.POINTER(CTrackerDetectionParams))]
+    L.aar_tracker_bank_push_detections.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_float), dp, u8p, C.POINTER(CTrackerResult), C.POINTER(CTrackerStartInfo)]
+    L.aar_tracker_bank_window.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.aar_tracker_bank_uncertainty.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CTrackerUncertainty)]
+    L.aar_tracker_bank_reset.argtypes = [C.c_void_p]
+    L.aar_tracker_bank_get_stats.argtypes = [C.c_void_p, C.POINTER(CTrackerBankStats)]
+    L.aar_tracker_bank_destroy.argtypes = [C.c_void_p]
+    L.aar_tracker_bank_destroy.restype = None
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.aar_local_group_destroy.argtypes = [C.c_void_p]
     L.aar_local_group_destroy.restype = None
@@ -907,6 +932,145 @@ def tracker_detection_params_validate(ds, **kw):
     _check(lib().aar_tracker_detection_params_validate(C.byref(c), C.byref(p)))
 
 
+def _tracker_result(r):
+    out = {k: getattr(r, k) for k, _ in CTrackerResult._fields_ if k not in ("struct_size", "pose", "lagged_pose")}
+    out["pose"] = np.array(r.pose[:])
+    out["lagged_pose"] = np.array(r.lagged_pose[:]) if r.has_lagged else None
+    return out
+
+
+def _tracker_start_info(si):
+    info = {k: getattr(si, k) for k, _ in CTrackerStartInfo._fields_ if k not in ("struct_size", "start_pose")}
+    info["start_pose"] = np.array(si.start_pose[:])
+    return info
+
+
+def _tracker_uncertainty(u):
+    w = u.window_frames
+    return dict(cov_valid=u.cov_valid, sigma2=u.sigma2, window_frames=w, frame_index=np.array(u.frame_index[:w], dtype=np.int64),
+                cov=np.array(u.cov[:36 * w]).reshape(w, 6, 6), has_marginal=u.has_marginal, marginal_index=u.marginal_index,
+                marginal_info=np.array(u.marginal_info[:]).reshape(6, 6), marginal_mean=np.array(u.marginal_mean[:]),
+                marginal_dropped=u.marginal_dropped)
+
+
+def tracker_bank_params_validate(solutions, n_members=None, **kw):
+    """aar_tracker_bank_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  solutions: data sets, a None
+    entry is passed as a null pointer; n_members: the count to pass (default len(solutions))"""
+    cds = [None if d is None else d.as_c() for d in solutions]
+    arr = (C.POINTER(CDataset) * max(len(cds), 1))(*[C.pointer(c) if c is not None else None for c in cds])
+    p = tracker_params(**kw)
+    _check(lib().aar_tracker_bank_params_validate(len(cds) if n_members is None else int(n_members), arr, C.byref(p)))
+
+
+class TrackerBank:
+    """aar_tracker_bank: B live trackers, one per solution in `solutions`, with the same parameters, advanced in lockstep --
+    one copy in, one launch of B workgroups, one copy out per push."""
+
+    def __init__(self, solutions, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
+                 device=0, params=None, anchor="fixed", covariance=False):
+        self.solutions = list(solutions)
+        self._cds = [d.as_c() for d in self.solutions]
+        arr = (C.POINTER(CDataset) * len(self._cds))(*[C.pointer(c) for c in self._cds])
+        self.prm = tracker_params(lag, smooth, sigma_rot, sigma_trans, with_huber, huber_delta, max_obs_per_frame, device, anchor=anchor,
+                                  covariance=covariance)
+        self.handle = C.c_void_p()
+        _check(lib().aar_tracker_bank_create(len(self._cds), arr, C.byref(self.prm), C.byref(params) if params is not None else None,
+                                             C.byref(self.handle)))
+        self.size = lib().aar_tracker_bank_size(self.handle)
+
+    def close(self):
+        if self.handle:
+            lib().aar_tracker_bank_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __len__(self):
+        return self.size
+
+    def pack(self, frames, pose_init):
+        """frames: [B] of (cam, marker, uv [n, 8]); pose_init: None, [B, 6], or a list of [6] / None per member"""
+        B = self.size
+        assert len(frames) == B
+        n = np.array([len(np.reshape(f[0], -1)) for f in frames], dtype=np.int32)
+        cam = np.ascontiguousarray(np.concatenate([np.reshape(f[0], -1) for f in frames]), dtype=np.int32)
+        mk = np.ascontiguousarray(np.concatenate([np.reshape(f[1], -1) for f in frames]), dtype=np.int32)
+        uv = np.ascontiguousarray(np.concatenate([np.reshape(f[2], -1) for f in frames]), dtype=np.float32)
+        assert len(mk) == len(cam) and len(uv) == 8 * len(cam)
+        init = has = None
+        if pose_init is not None and any(z is not None for z in pose_init):
+            assert len(pose_init) == B
+            has = np.array([z is not None for z in pose_init], dtype=np.uint8)
+            init = np.ascontiguousarray([np.zeros(6) if z is None else np.reshape(z, 6) for z in pose_init], dtype=np.float64)
+        ip = C.POINTER(C.c_int32)
+        return (n.ctypes.data_as(ip), cam.ctypes.data_as(ip), mk.ctypes.data_as(ip), uv.ctypes.data_as(C.POINTER(C.c_float)),
+                _dptr(init) if init is not None else None, _u8ptr(has) if has is not None else None), (n, cam, mk, uv, init, has)
+
+    def result_array(self):
+        r = (CTrackerResult * self.size)()
+        for x in r:
+            x.struct_size = C.sizeof(CTrackerResult)
+        return r
+
+    def push(self, frame_time, frames, pose_init=None):
+        """aar_tracker_bank_push: frames [B] of (obs_cam, obs_marker, obs_uv [n, 8]) in the member's own indices; pose_init None, or per member
+        a pose [6] or None.  Returns the [B] result dicts of Tracker.push."""
+        args, keep = self.pack(frames, pose_init)
+        r = self.result_array()
+        _check(lib().aar_tracker_bank_push(self.handle, float(frame_time), *args, r))
+        return [_tracker_result(x) for x in r]
+
+    def enable_detections(self, per_member=None):
+        """aar_tracker_bank_enable_detections: per_member None or [B] of None / a dict of tracker_detection_params' keywords"""
+        keep = [None if kw is None else tracker_detection_params(**kw) for kw in (per_member or [None] * self.size)]
+        assert len(keep) == self.size
+        arr = (C.POINTER(CTrackerDetectionParams) * self.size)(*[C.pointer(k[0]) if k is not None else None for k in keep])
+        _check(lib().aar_tracker_bank_enable_detections(self.handle, arr))
+
+    def push_detections(self, frame_time, frames, pose_init=None):
+        """aar_tracker_bank_push_detections: as push() with RAW corners.  Returns ([B] results, [B] start infos)."""
+        args, keep = self.pack(frames, pose_init)
+        r = self.result_array()
+        si = (CTrackerStartInfo * self.size)()
+        for x in si:
+            x.struct_size = C.sizeof(CTrackerStartInfo)
+        _check(lib().aar_tracker_bank_push_detections(self.handle, float(frame_time), *args, r, si))
+        return [_tracker_result(x) for x in r], [_tracker_start_info(x) for x in si]
+
+    def window(self, member):
+        """aar_tracker_bank_window: Tracker.window() of one member"""
+        cap = TRACKER_MAX_LAG + 1
+        n, has = C.c_int32(0), C.c_int32(0)
+        idx = np.zeros(cap, dtype=np.int64)
+        poses, fe, pe, anchor = np.zeros((cap, 6)), np.zeros(cap), np.zeros(cap), np.zeros(6)
+        _check(lib().aar_tracker_bank_window(self.handle, int(member), C.byref(n), idx.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(poses), _dptr(fe),
+                                             _dptr(pe), _dptr(anchor), C.byref(has)))
+        w = n.value
+        return dict(n=w, frame_index=idx[:w].copy(), poses=poses[:w].copy(), frame_err=fe[:w].copy(), pair_err=pe[:w].copy(),
+                    anchor_pose=anchor if has.value else None)
+
+    def uncertainty(self, member):
+        """aar_tracker_bank_uncertainty: Tracker.uncertainty() of one member"""
+        u = CTrackerUncertainty()
+        u.struct_size = C.sizeof(CTrackerUncertainty)
+        _check(lib().aar_tracker_bank_uncertainty(self.handle, int(member), C.byref(u)))
+        return _tracker_uncertainty(u)
+
+    def reset(self):
+        _check(lib().aar_tracker_bank_reset(self.handle))
+
+    def stats(self, struct_size=None):
+        """aar_tracker_bank_get_stats: dict(members, pushes, launches, h2d_copies, h2d_bytes, d2h_copies, d2h_bytes) counted on the host"""
+        st = CTrackerBankStats()
+        st.struct_size = C.sizeof(CTrackerBankStats) if struct_size is None else int(struct_size)
+        _check(lib().aar_tracker_bank_get_stats(self.handle, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in CTrackerBankStats._fields_}
+
+
 class Tracker:
     """aar_tracker: the live tracker.  Built from a solution data set (its cameras, markers, cam_mats, marker_size and
     roots; its frames are ignored) and fed one frame per push."""
@@ -948,10 +1112,7 @@ class Tracker:
         ip = C.POINTER(C.c_int32)
         _check(lib().aar_tracker_push(self.handle, float(frame_time), n, cam.ctypes.data_as(ip), mk.ctypes.data_as(ip),
                                       uv.ctypes.data_as(C.POINTER(C.c_float)), _dptr(init) if init is not None else None, C.byref(r)))
-        out = {k: getattr(r, k) for k, _ in CTrackerResult._fields_ if k not in ("struct_size", "pose", "lagged_pose")}
-        out["pose"] = np.array(r.pose[:])
-        out["lagged_pose"] = np.array(r.lagged_pose[:]) if r.has_lagged else None
-        return out
+        return _tracker_result(r)
 
     def enable_detections(self, Ks=None, dists=None, ippe_threshold=None, min_detections=None, start_policy=None):
         """aar_tracker_enable_detections: once after creation or reset (see tracker_detection_params)"""
@@ -973,12 +1134,7 @@ class Tracker:
         _check(lib().aar_tracker_push_detections(self.handle, float(frame_time), n, cam.ctypes.data_as(ip), mk.ctypes.data_as(ip),
                                                  uv.ctypes.data_as(C.POINTER(C.c_float)), _dptr(init) if init is not None else None, C.byref(r),
                                                  C.byref(si)))
-        out = {k: getattr(r, k) for k, _ in CTrackerResult._fields_ if k not in ("struct_size", "pose", "lagged_pose")}
-        out["pose"] = np.array(r.pose[:])
-        out["lagged_pose"] = np.array(r.lagged_pose[:]) if r.has_lagged else None
-        info = {k: getattr(si, k) for k, _ in CTrackerStartInfo._fields_ if k not in ("struct_size", "start_pose")}
-        info["start_pose"] = np.array(si.start_pose[:])
-        return out, info
+        return _tracker_result(r), _tracker_start_info(si)
 
     def window(self):
         """aar_tracker_window: dict(n, frame_index [n], poses [n, 6], frame_err [n], pair_err [n] (entry i: the pair that ends at window
@@ -999,11 +1155,7 @@ class Tracker:
         u = CTrackerUncertainty()
         u.struct_size = C.sizeof(CTrackerUncertainty)
         _check(lib().aar_tracker_uncertainty(self.handle, C.byref(u)))
-        w = u.window_frames
-        return dict(cov_valid=u.cov_valid, sigma2=u.sigma2, window_frames=w, frame_index=np.array(u.frame_index[:w], dtype=np.int64),
-                    cov=np.array(u.cov[:36 * w]).reshape(w, 6, 6), has_marginal=u.has_marginal, marginal_index=u.marginal_index,
-                    marginal_info=np.array(u.marginal_info[:]).reshape(6, 6), marginal_mean=np.array(u.marginal_mean[:]),
-                    marginal_dropped=u.marginal_dropped)
+        return _tracker_uncertainty(u)
 
     def reset(self):
         _check(lib().aar_tracker_reset(self.handle))

@@ -2975,6 +2975,8 @@ constexpr int LIVE_ST_ANCHOR = 6 * LIVE_MAX_W, LIVE_ST_EF = LIVE_ST_ANCHOR + 8, 
 constexpr int LIVE_DET_MAX_OBS = 4096;   // the vote is n^2 in ONE workgroup: a frame of raw detections is capped here
 
 // the caller's struct read up to its struct_size, the rest at the defaults; false: too short to hold lag and smooth
+void live_solution_z(const aar_dataset *sol, std::vector<double> &z);   // (below, with what a tracker and a bank member share)
+
 bool tracker_params_read(const aar_tracker_params *in, aar_tracker_params *out) {
     aar_tracker_default_params(out);
     if (in->struct_size < offsetof(aar_tracker_params, smooth) + sizeof(int32_t)) return false;
@@ -3081,13 +3083,8 @@ int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, con
         hipMemsetAsync(t->d_ring, 0, (size_t)(p.lag + 1) * t->slot_bytes, t->stream) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMemset failed"));
     // the entity rows of the fixed cameras and markers, by the problem's own unpack kernel (roots: the identity)
-    PoseLayout L;
-    L.C = C; L.M = M; L.F = 0; L.rc = sol->root_cam; L.rm = sol->root_marker;
-    std::vector<double> z((size_t)6 * A, 0.0);
-    for (int c = 0; c < C; c++)
-        if (c != L.rc) memcpy(&z[6 * (size_t)c], sol->x_full + L.full_cam0() + 6LL * L.cam_slot(c), 6 * sizeof(double));
-    for (int m = 0; m < M; m++)
-        if (m != L.rm) memcpy(&z[6 * (size_t)(C + m)], sol->x_full + L.full_mk0() + 6LL * L.mk_slot(m), 6 * sizeof(double));
+    std::vector<double> z;
+    live_solution_z(sol, z);
     const char *what = "";
     if (h2d(d_z, z.data(), z.size() * sizeof(double), t->stream, &what) || h2d(t->d_K, sol->cam_mats, (size_t)9 * C * sizeof(double), t->stream, &what))
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: %s failed", what));
@@ -3115,6 +3112,209 @@ int aar_tracker_reset(aar_tracker *t) {
 
 namespace {
 
+// ---- what a single tracker and a member of a tracker bank share; who: "" or "member b: " ----
+
+// the rows of the fixed cameras and markers of a solution as the unpack kernel reads them: [C + M][6], the roots zero (the identity)
+void live_solution_z(const aar_dataset *sol, std::vector<double> &z) {
+    const int C = sol->num_cams, M = sol->num_markers;
+    PoseLayout L;
+    L.C = C; L.M = M; L.F = 0; L.rc = sol->root_cam; L.rm = sol->root_marker;
+    const size_t at = z.size();
+    z.resize(at + (size_t)6 * (C + M), 0.0);
+    for (int c = 0; c < C; c++)
+        if (c != L.rc) memcpy(&z[at + 6 * (size_t)c], sol->x_full + L.full_cam0() + 6LL * L.cam_slot(c), 6 * sizeof(double));
+    for (int m = 0; m < M; m++)
+        if (m != L.rm) memcpy(&z[at + 6 * (size_t)(C + m)], sol->x_full + L.full_mk0() + 6LL * L.mk_slot(m), 6 * sizeof(double));
+}
+
+// one frame's detections against the tracker's sizes
+int live_check_frame(const char *fn, const char *who, bool raw, int C, int M, int max_obs, int32_t n_obs, const int32_t *obs_cam,
+                     const int32_t *obs_marker, const float *obs_uv) {
+    if (n_obs < 0 || n_obs > max_obs)
+        return set_error(AAR_ERR_INVALID, "%s: %s%s = %d is outside 0 .. max_obs_per_frame = %d", fn, who, raw ? "n_det" : "n_obs", (int)n_obs, max_obs);
+    if (n_obs > 0 && (!obs_cam || !obs_marker || !obs_uv)) return set_error(AAR_ERR_INVALID, "%s: %snull %s array", fn, who, raw ? "detection" : "observation");
+    for (int o = 0; o < n_obs; o++) {
+        if (obs_cam[o] < 0 || obs_cam[o] >= C)
+            return set_error(AAR_ERR_INVALID, "%s: %s%s[%d] = %d is outside 0 .. %d", fn, who, raw ? "det_cam" : "obs_cam", o, (int)obs_cam[o], C - 1);
+        if (obs_marker[o] < 0 || obs_marker[o] >= M)
+            return set_error(AAR_ERR_INVALID, "%s: %s%s[%d] = %d is outside 0 .. %d", fn, who, raw ? "det_marker" : "obs_marker", o, (int)obs_marker[o], M - 1);
+    }
+    return AAR_OK;
+}
+
+int live_check_pose_init(const char *fn, const char *who, const double *pose_init) {
+    for (int k = 0; pose_init && k < 6; k++)
+        if (!std::isfinite(pose_init[k])) return set_error(AAR_ERR_INVALID, "%s: %spose_init[%d] is not finite", fn, who, k);
+    return AAR_OK;
+}
+
+// a vote is held unless the caller's pose_init settles the start (policy VOTE) or the frame has too few detections
+bool live_do_vote(const aar_tracker_detection_params &det, int32_t n_obs, bool has_init) {
+    return n_obs >= det.min_detections && !(has_init && det.start_policy == AAR_TRACKER_START_VOTE);
+}
+
+// the frame's slot: header | records (| on a push of raw detections the candidate order), staged in page-locked memory; returns its bytes
+size_t live_stage_slot(char *slot, int C, bool raw, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker, const float *obs_uv,
+                       const double *pose_init, std::vector<int32_t> &order) {
+    double *hdr = reinterpret_cast<double *>(slot);
+    for (int k = 0; k < 8; k++) hdr[k] = (pose_init && k < 6) ? pose_init[k] : 0.0;
+    for (int o = 0; o < n_obs; o++) {
+        char *rec = slot + LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * o;
+        ObsIdx id;
+        id.frame = 0; id.cam = obs_cam[o]; id.marker = C + obs_marker[o]; id.slots = 0;
+        memcpy(rec, &id, sizeof id);
+        memcpy(rec + sizeof id, obs_uv + 8 * (size_t)o, 8 * sizeof(float));
+    }
+    size_t bytes = LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * n_obs;
+    if (raw) {
+        // the candidate order of init_object_transforms: marker, then camera, stable (host/initializer.cpp); behind the records, same copy
+        order.resize((size_t)n_obs);
+        for (int o = 0; o < n_obs; o++) order[o] = o;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+            return obs_marker[x] != obs_marker[y] ? obs_marker[x] < obs_marker[y] : obs_cam[x] < obs_cam[y];
+        });
+        if (n_obs) memcpy(slot + bytes, order.data(), sizeof(int32_t) * (size_t)n_obs);
+        bytes += sizeof(int32_t) * (size_t)n_obs;
+    }
+    return bytes;
+}
+
+// what push n (n pushes accepted before it) at frame_time gives every tracker with these parameters: the LM's settings, the window in the ring,
+// the pair weights from the times by ring slot.  cnt is zeroed; ent .. res, has_init, has_marginal, rows and unc are the caller's.
+void live_window_args(LiveArgs &a, const aar_tracker_params &p, const aar_lm_params &lm, int64_t n, double frame_time, const double *times) {
+    const int slots = p.lag + 1, ns = (int)(n % slots);
+    const int W = (int)std::min<int64_t>(n + 1, slots);
+    const bool has_anchor = n - slots >= 0;
+    a.huber = p.with_huber ? p.huber_delta : -1.f;
+    a.max_iters = lm.max_iters; a.min_error = lm.min_error; a.min_step_error_diff = lm.min_step_error_diff;
+    a.min_average_step_error_diff = lm.min_average_step_error_diff; a.tau = lm.tau;
+    a.W = W; a.slots = slots; a.first_slot = (int)((n + 1 - W) % slots);
+    a.has_anchor = has_anchor ? 1 : 0; a.smooth = p.smooth;
+    for (int i = 0; i < LIVE_MAX_W; i++) { a.cnt[i] = 0; a.lam[i][0] = a.lam[i][1] = 0.0; }
+    for (int i = 0; i < W; i++) {
+        const int sl = (a.first_slot + i) % slots;
+        const double ti = i == W - 1 ? frame_time : times[sl];
+        double tp = 0.0;
+        bool pair = false;
+        if (i > 0) { tp = times[(a.first_slot + i - 1) % slots]; pair = true; }
+        else if (has_anchor) { tp = times[ns]; pair = true; }   // the anchor's time still sits in the slot the new frame takes
+        if (pair && p.smooth) {
+            const double dt = ti - tp;
+            a.lam[i][0] = 1.0 / (p.sigma_rot * p.sigma_rot * dt);
+            a.lam[i][1] = 1.0 / (p.sigma_trans * p.sigma_trans * dt);
+        }
+    }
+    const bool marginal = p.anchor_mode == AAR_TRACKER_ANCHOR_MARGINAL;
+    a.anchor_pair = has_anchor && !marginal ? 1 : 0;
+    a.marginal = marginal ? 1 : 0; a.covariance = p.covariance;
+}
+
+// 8 rows per detection of the window, 6 per pair; the anchor pair's 6 are the marginal prior's in that mode (none after a dropped marginal)
+double live_rows(const LiveArgs &a, int64_t det, int has_marginal) {
+    return 8.0 * (double)det + (a.smooth ? 6.0 * (double)(a.W - 1 + (a.marginal ? has_marginal : a.has_anchor ? 1 : 0)) : 0.0);
+}
+
+double live_sigma2(double rows, int W, double final_cost) {
+    const double dof = rows - 6.0 * (double)W;
+    return dof > 0.0 ? final_cost / dof : 0.0;
+}
+
+// the device's result record h of push n -> the caller's struct
+void live_fill_result(const double *h, int64_t n, int W, int slots, std::chrono::steady_clock::time_point t0, aar_tracker_result *result) {
+    aar_tracker_result r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = result->struct_size;
+    r.frame_index = n; r.window_frames = W;
+    r.iterations = (int32_t)h[0]; r.stop_code = (int32_t)h[1]; r.rejected_tries = (int32_t)h[2];
+    r.initial_cost = h[3]; r.final_cost = h[4]; r.final_data_cost = h[5]; r.final_prior_cost = h[6]; r.final_mu = h[7];
+    for (int k = 0; k < 6; k++) { r.pose[k] = h[8 + k]; r.lagged_pose[k] = W == slots ? h[14 + k] : 0.0; }
+    r.has_lagged = W == slots ? 1 : 0;
+    r.lagged_index = W == slots ? n + 1 - W : -1;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    memcpy(result, &r, std::min<size_t>(result->struct_size, sizeof r));
+}
+
+void live_fill_info(const double *h_info, aar_tracker_start_info *info) {
+    aar_tracker_start_info si;
+    memset(&si, 0, sizeof si);
+    si.struct_size = (uint32_t)std::min<size_t>(info->struct_size, sizeof si);
+    si.voted = (int32_t)h_info[0]; si.candidates = (int32_t)h_info[1]; si.winner = (int32_t)h_info[2]; si.vote_cost = h_info[3];
+    si.start_source = (int32_t)h_info[4]; si.cost_prediction = h_info[5]; si.cost_vote = h_info[6];
+    for (int k = 0; k < 6; k++) si.start_pose[k] = h_info[8 + k];
+    memcpy(info, &si, si.struct_size);
+}
+
+// the host copy u of the device's uncertainty record after push n - 1 -> the caller's struct
+void live_fill_uncertainty(const aar_tracker_params &prm, const double *u, int W, int64_t n, int has_marginal, int64_t marginal_dropped, double sigma2,
+                           aar_tracker_uncertainty_record *out) {
+    aar_tracker_uncertainty_record r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = out->struct_size;
+    r.cov_valid = prm.covariance && u[LIVE_UNC_VALID] != 0.0 ? 1 : 0;
+    r.sigma2 = prm.covariance ? sigma2 : 0.0;
+    r.window_frames = W;
+    for (int i = 0; i < W; i++) r.frame_index[i] = n - W + i;
+    if (r.cov_valid) memcpy(r.cov, u + LIVE_UNC_HDR, 36 * (size_t)W * sizeof(double));
+    r.has_marginal = has_marginal;
+    r.marginal_index = has_marginal ? n - W + 1 : -1;
+    if (has_marginal) {
+        memcpy(r.marginal_info, u + LIVE_UNC_LM, 36 * sizeof(double));
+        memcpy(r.marginal_mean, u + LIVE_UNC_M, 6 * sizeof(double));
+    }
+    r.marginal_dropped = marginal_dropped;
+    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+}
+
+// aar_tracker_window's outputs from a tracker's state st [LIVE_ST_RES] after n pushes; without st only the counts
+void live_window_out(const double *st, int64_t n, int slots, int32_t *n_out, int64_t *frame_index, double *poses, double *frame_err, double *pair_err,
+                     double anchor_pose[6], int32_t *has_anchor) {
+    const int W = (int)std::min<int64_t>(n, slots);
+    const bool anchored = n - 1 - slots >= 0;
+    if (n_out) *n_out = W;
+    if (has_anchor) *has_anchor = anchored ? 1 : 0;
+    if (frame_index) for (int i = 0; i < W; i++) frame_index[i] = n - W + i;
+    if (!st) return;
+    for (int i = 0; i < W; i++) {
+        const int sl = (int)((n - W + i) % slots);
+        if (poses) memcpy(poses + 6 * (size_t)i, st + 6 * sl, 6 * sizeof(double));
+        if (frame_err) frame_err[i] = st[LIVE_ST_EF + i];
+        if (pair_err) pair_err[i] = st[LIVE_ST_PE + i];
+    }
+    if (anchor_pose) for (int k = 0; k < 6; k++) anchor_pose[k] = anchored ? st[LIVE_ST_ANCHOR + k] : 0.0;
+}
+
+// the tables k_live_init reads: K and twelve coefficients by camera index (CamTab); the to-root 3x4 of every camera and marker exactly as
+// aar_initializer_object_poses builds them from the solution (host cv::Rodrigues), the identity for the roots
+void live_detection_tables(int C, int M, int rc, int rm, const aar_cam_model *cams, const double *sol_x, const double *sol_K, const double *sol_dist,
+                           double *tab, double *tr) {
+    for (int c = 0; c < C; c++) {
+        double *row = tab + (size_t)c * (9 + AAR_MAX_DIST);
+        for (int i = 0; i < 9 + AAR_MAX_DIST; i++) row[i] = 0.0;
+        if (cams) {
+            memcpy(row, cams[c].K, 9 * sizeof(double));
+            for (int i = 0; i < cams[c].n_dist; i++) row[9 + i] = cams[c].dist[i];
+        } else {
+            memcpy(row, sol_K + 9 * (size_t)c, 9 * sizeof(double));
+            memcpy(row + 9, sol_dist + 5 * (size_t)c, 5 * sizeof(double));
+        }
+    }
+    PoseLayout L;
+    L.C = C; L.M = M; L.F = 0; L.rc = rc; L.rm = rm;
+    for (int e = 0; e < C + M; e++) {
+        double *m = tr + 12 * (size_t)e;
+        for (int i = 0; i < 12; i++) m[i] = 0.0;
+        m[0] = m[5] = m[10] = 1.0;
+        const bool cam = e < C;
+        if (cam ? e == L.rc : e - C == L.rm) continue;
+        const double *v = sol_x + (cam ? L.full_cam0() + 6LL * L.cam_slot(e) : L.full_mk0() + 6LL * L.mk_slot(e - C));
+        const Rigid r = pose_to_rigid(v);
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) m[i * 4 + j] = r.R[i * 3 + j];
+            m[i * 4 + 3] = r.t[i];
+        }
+    }
+}
+
 // one push.  info == nullptr && !raw: aar_tracker_push (corners already undistorted, ONE launch).  raw: aar_tracker_push_detections -- the
 // corners are raw, k_live_init undistorts them in the slot and chooses the start, then the same k_live_push runs from the slot's header.
 int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, int32_t n_obs, const int32_t *obs_cam, const int32_t *obs_marker,
@@ -3125,85 +3325,35 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
     const int slots = p.lag + 1;
     const int64_t n = t->n;
     if (raw && !t->det_on) return set_error(AAR_ERR_INVALID, "%s: call aar_tracker_enable_detections first", fn);
-    if (n_obs < 0 || n_obs > p.max_obs_per_frame)
-        return set_error(AAR_ERR_INVALID, "%s: %s = %d is outside 0 .. max_obs_per_frame = %d", fn, raw ? "n_det" : "n_obs", (int)n_obs, (int)p.max_obs_per_frame);
-    if (n_obs > 0 && (!obs_cam || !obs_marker || !obs_uv)) return set_error(AAR_ERR_INVALID, "%s: null %s array", fn, raw ? "detection" : "observation");
-    for (int o = 0; o < n_obs; o++) {
-        if (obs_cam[o] < 0 || obs_cam[o] >= t->C)
-            return set_error(AAR_ERR_INVALID, "%s: %s[%d] = %d is outside 0 .. %d", fn, raw ? "det_cam" : "obs_cam", o, (int)obs_cam[o], t->C - 1);
-        if (obs_marker[o] < 0 || obs_marker[o] >= t->M)
-            return set_error(AAR_ERR_INVALID, "%s: %s[%d] = %d is outside 0 .. %d", fn, raw ? "det_marker" : "obs_marker", o, (int)obs_marker[o], t->M - 1);
-    }
+    if (int rc = live_check_frame(fn, "", raw, t->C, t->M, p.max_obs_per_frame, n_obs, obs_cam, obs_marker, obs_uv)) return rc;
     if (!std::isfinite(frame_time)) return set_error(AAR_ERR_INVALID, "%s: frame_time is not finite", fn);
     const int ns = (int)(n % slots), ps = (int)((n + slots - 1) % slots);
     if (n > 0 && (!(frame_time > t->times[ps]) || !std::isfinite(frame_time - t->times[ps])))
         return set_error(AAR_ERR_INVALID, "%s: frame_time = %g does not ascend from the previous push's %g", fn, frame_time, t->times[ps]);
-    // a vote is held unless the caller's pose_init settles the start (policy VOTE) or the frame has too few detections
-    const bool do_vote = raw && n_obs >= t->det.min_detections && !(pose_init && t->det.start_policy == AAR_TRACKER_START_VOTE);
+    const bool do_vote = raw && live_do_vote(t->det, n_obs, pose_init != nullptr);
     if (n == 0 && !pose_init && !raw) return set_error(AAR_ERR_INVALID, "%s: the first push needs a pose_init", fn);
     if (n == 0 && !pose_init && !do_vote)
         return set_error(AAR_ERR_INVALID, "%s: the first push has %d detections, fewer than min_detections = %d, and no pose_init: nothing to start from", fn,
                          (int)n_obs, (int)t->det.min_detections);
-    if (pose_init)
-        for (int k = 0; k < 6; k++)
-            if (!std::isfinite(pose_init[k])) return set_error(AAR_ERR_INVALID, "%s: pose_init[%d] is not finite", fn, k);
+    if (int rc = live_check_pose_init(fn, "", pose_init)) return rc;
     HIP_TRY(hipSetDevice(t->device));
-    // the frame's slot: header | records, staged in page-locked memory
-    double *hdr = reinterpret_cast<double *>(t->h_stage);
-    for (int k = 0; k < 8; k++) hdr[k] = (pose_init && k < 6) ? pose_init[k] : 0.0;
-    for (int o = 0; o < n_obs; o++) {
-        char *rec = t->h_stage + LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * o;
-        ObsIdx id;
-        id.frame = 0; id.cam = obs_cam[o]; id.marker = t->C + obs_marker[o]; id.slots = 0;
-        memcpy(rec, &id, sizeof id);
-        memcpy(rec + sizeof id, obs_uv + 8 * (size_t)o, 8 * sizeof(float));
-    }
-    size_t copy_bytes = LIVE_HDR_BYTES + (size_t)LIVE_REC_BYTES * n_obs;
-    if (raw) {
-        // the candidate order of init_object_transforms: marker, then camera, stable (host/initializer.cpp); behind the records, same copy
-        t->order.resize((size_t)n_obs);
-        for (int o = 0; o < n_obs; o++) t->order[o] = o;
-        std::stable_sort(t->order.begin(), t->order.end(), [&](int32_t x, int32_t y) {
-            return obs_marker[x] != obs_marker[y] ? obs_marker[x] < obs_marker[y] : obs_cam[x] < obs_cam[y];
-        });
-        if (n_obs) memcpy(t->h_stage + copy_bytes, t->order.data(), sizeof(int32_t) * (size_t)n_obs);
-        copy_bytes += sizeof(int32_t) * (size_t)n_obs;
-    }
-    const int W = (int)std::min<int64_t>(n + 1, slots);
-    const bool has_anchor = n - slots >= 0;
+    const size_t copy_bytes = live_stage_slot(t->h_stage, t->C, raw, n_obs, obs_cam, obs_marker, obs_uv, pose_init, t->order);
     LiveArgs a;
+    live_window_args(a, p, t->lm, n, frame_time, t->times);
     a.ent = t->d_ent; a.Kmat = t->d_K; a.ring = t->d_ring; a.slot_bytes = t->slot_bytes;
     a.zslot = t->d_state; a.anchor = t->d_state + LIVE_ST_ANCHOR; a.Ef = t->d_state + LIVE_ST_EF; a.Pe = t->d_state + LIVE_ST_PE; a.res = t->d_state + LIVE_ST_RES;
-    a.huber = p.with_huber ? p.huber_delta : -1.f;
     a.h = t->half_size;
-    a.max_iters = t->lm.max_iters; a.min_error = t->lm.min_error; a.min_step_error_diff = t->lm.min_step_error_diff;
-    a.min_average_step_error_diff = t->lm.min_average_step_error_diff; a.tau = t->lm.tau;
-    a.W = W; a.slots = slots; a.first_slot = (int)((n + 1 - W) % slots);
-    a.has_anchor = has_anchor ? 1 : 0; a.smooth = p.smooth; a.has_init = (pose_init || raw) ? 1 : 0;   // raw: k_live_init wrote the header
+    a.has_init = (pose_init || raw) ? 1 : 0;   // raw: k_live_init wrote the header
+    const int W = a.W;
     int64_t det = 0;
-    for (int i = 0; i < LIVE_MAX_W; i++) { a.cnt[i] = 0; a.lam[i][0] = a.lam[i][1] = 0.0; }
     for (int i = 0; i < W; i++) {
-        const int sl = (a.first_slot + i) % slots;
-        const bool newest = i == W - 1;
-        a.cnt[i] = newest ? n_obs : t->cnt[sl];
+        a.cnt[i] = i == W - 1 ? n_obs : t->cnt[(a.first_slot + i) % slots];
         det += a.cnt[i];
-        const double ti = newest ? frame_time : t->times[sl];
-        double tp = 0.0;
-        bool pair = false;
-        if (i > 0) { tp = t->times[(a.first_slot + i - 1) % slots]; pair = true; }
-        else if (has_anchor) { tp = t->times[ns]; pair = true; }   // the anchor's time still sits in the slot the new frame takes
-        if (pair && p.smooth) {
-            const double dt = ti - tp;
-            a.lam[i][0] = 1.0 / (p.sigma_rot * p.sigma_rot * dt);
-            a.lam[i][1] = 1.0 / (p.sigma_trans * p.sigma_trans * dt);
-        }
     }
-    const bool marginal = p.anchor_mode == AAR_TRACKER_ANCHOR_MARGINAL, tail = marginal || p.covariance;
-    a.anchor_pair = has_anchor && !marginal ? 1 : 0;
-    a.marginal = marginal ? 1 : 0; a.has_marginal = marginal ? t->has_marginal : 0; a.covariance = p.covariance;
+    const bool marginal = a.marginal != 0, tail = marginal || p.covariance;
+    a.has_marginal = marginal ? t->has_marginal : 0;
     a.unc = t->d_state + LIVE_ST_UNC;
-    // 6 rows per pair; the anchor pair's 6 are the marginal prior's in that mode (none after a dropped marginal)
-    a.rows = 8.0 * (double)det + (p.smooth ? 6.0 * (double)(W - 1 + (marginal ? a.has_marginal : has_anchor ? 1 : 0)) : 0.0);
+    a.rows = live_rows(a, det, a.has_marginal);
     HIP_TRY(hipMemcpyAsync(t->d_ring + (size_t)ns * t->slot_bytes, t->h_stage, copy_bytes, hipMemcpyHostToDevice, t->stream));
     double *h_info = t->h_res + LIVE_RES_DOUBLES;
     if (raw) {
@@ -3216,8 +3366,7 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
         li.do_vote = do_vote ? 1 : 0; li.policy = t->det.start_policy; li.has_init = pose_init ? 1 : 0; li.has_prev = n > 0 ? 1 : 0;
         li.zprev = t->d_state + 6 * ps;
         li.ent = t->d_ent; li.Kmat = t->d_K; li.huber = a.huber; li.h_track = t->half_size;
-        li.poses = t->d_work; li.Tc = li.poses + 24 * mo; li.BJ = li.Tc + 24 * mo; li.cost = li.BJ + 48 * mo;
-        li.has2 = reinterpret_cast<int *>(li.cost + 2 * mo); li.fin = li.has2 + mo;
+        live_init_work_carve(li, t->d_work, mo);
         li.info = t->d_state + LIVE_ST_INFO;
         launch_live_init(li, t->stream);
         if (n == 0 && !pose_init) {
@@ -3248,32 +3397,10 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
         t->unc_W = W;
         t->has_marginal = marginal && u[LIVE_UNC_HAS] != 0.0 ? 1 : 0;
         if (marginal && u[LIVE_UNC_DROP] != 0.0) t->marginal_dropped++;
-        const double dof = a.rows - 6.0 * (double)W;
-        t->unc_sigma2 = dof > 0.0 ? t->h_res[4] / dof : 0.0;
+        t->unc_sigma2 = live_sigma2(a.rows, W, t->h_res[4]);
     }
-    if (result) {
-        aar_tracker_result r;
-        memset(&r, 0, sizeof r);
-        const double *h = t->h_res;
-        r.struct_size = result->struct_size;
-        r.frame_index = n; r.window_frames = W;
-        r.iterations = (int32_t)h[0]; r.stop_code = (int32_t)h[1]; r.rejected_tries = (int32_t)h[2];
-        r.initial_cost = h[3]; r.final_cost = h[4]; r.final_data_cost = h[5]; r.final_prior_cost = h[6]; r.final_mu = h[7];
-        for (int k = 0; k < 6; k++) { r.pose[k] = h[8 + k]; r.lagged_pose[k] = W == slots ? h[14 + k] : 0.0; }
-        r.has_lagged = W == slots ? 1 : 0;
-        r.lagged_index = W == slots ? n + 1 - W : -1;
-        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        memcpy(result, &r, std::min<size_t>(result->struct_size, sizeof r));
-    }
-    if (info) {
-        aar_tracker_start_info si;
-        memset(&si, 0, sizeof si);
-        si.struct_size = (uint32_t)std::min<size_t>(info->struct_size, sizeof si);
-        si.voted = (int32_t)h_info[0]; si.candidates = (int32_t)h_info[1]; si.winner = (int32_t)h_info[2]; si.vote_cost = h_info[3];
-        si.start_source = (int32_t)h_info[4]; si.cost_prediction = h_info[5]; si.cost_vote = h_info[6];
-        for (int k = 0; k < 6; k++) si.start_pose[k] = h_info[8 + k];
-        memcpy(info, &si, si.struct_size);
-    }
+    if (result) live_fill_result(t->h_res, n, W, slots, t0, result);
+    if (info) live_fill_info(h_info, info);
     return AAR_OK;
 }
 
@@ -3354,33 +3481,8 @@ int aar_tracker_enable_detections(aar_tracker *t, const aar_tracker_detection_pa
     if (!t->d_cams) HIP_TRY(hipMalloc(&t->d_cams, (size_t)C * (9 + AAR_MAX_DIST) * sizeof(double)));
     if (!t->d_toroot) HIP_TRY(hipMalloc((void **)&t->d_toroot, 12 * (size_t)(C + M) * sizeof(double)));
     if (!t->d_work) HIP_TRY(hipMalloc((void **)&t->d_work, 98 * mo * sizeof(double) + 3 * mo * sizeof(int)));
-    // K and twelve coefficients by camera index (CamTab); the to-root 3x4 of every camera and marker exactly as aar_initializer_object_poses
-    // builds them from the solution (host cv::Rodrigues), the identity for the roots
     std::vector<double> tab((size_t)C * (9 + AAR_MAX_DIST), 0.0), tr(12 * (size_t)(C + M), 0.0);
-    for (int c = 0; c < C; c++) {
-        double *row = &tab[(size_t)c * (9 + AAR_MAX_DIST)];
-        if (p.cams) {
-            memcpy(row, p.cams[c].K, 9 * sizeof(double));
-            for (int i = 0; i < p.cams[c].n_dist; i++) row[9 + i] = p.cams[c].dist[i];
-        } else {
-            memcpy(row, &t->sol_K[9 * (size_t)c], 9 * sizeof(double));
-            memcpy(row + 9, &t->sol_dist[5 * (size_t)c], 5 * sizeof(double));
-        }
-    }
-    PoseLayout L;
-    L.C = C; L.M = M; L.F = 0; L.rc = t->rc; L.rm = t->rm;
-    for (int e = 0; e < C + M; e++) {
-        double *m = &tr[12 * (size_t)e];
-        m[0] = m[5] = m[10] = 1.0;
-        const bool cam = e < C;
-        if (cam ? e == L.rc : e - C == L.rm) continue;
-        const double *v = t->sol_x.data() + (cam ? L.full_cam0() + 6LL * L.cam_slot(e) : L.full_mk0() + 6LL * L.mk_slot(e - C));
-        const Rigid r = pose_to_rigid(v);
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) m[i * 4 + j] = r.R[i * 3 + j];
-            m[i * 4 + 3] = r.t[i];
-        }
-    }
+    live_detection_tables(C, M, t->rc, t->rm, p.cams, t->sol_x.data(), t->sol_K.data(), t->sol_dist.data(), tab.data(), tr.data());
     const char *what = "";
     if (h2d(t->d_cams, tab.data(), tab.size() * sizeof(double), t->stream, &what) || h2d(t->d_toroot, tr.data(), tr.size() * sizeof(double), t->stream, &what))
         return set_error(AAR_ERR_HIP, "aar_tracker_enable_detections: %s failed", what);
@@ -3398,24 +3500,7 @@ int aar_tracker_uncertainty(aar_tracker *t, aar_tracker_uncertainty_record *out)
     if (!t->unc_set || t->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_uncertainty: no push since creation / reset");
     if (out->struct_size < offsetof(aar_tracker_uncertainty_record, cov_valid) + sizeof(int32_t))
         return set_error(AAR_ERR_INVALID, "aar_tracker_uncertainty: struct_size %u does not reach cov_valid", (unsigned)out->struct_size);
-    aar_tracker_uncertainty_record r;
-    memset(&r, 0, sizeof r);
-    const double *u = t->h_res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
-    const int W = t->unc_W;
-    r.struct_size = out->struct_size;
-    r.cov_valid = t->prm.covariance && u[LIVE_UNC_VALID] != 0.0 ? 1 : 0;
-    r.sigma2 = t->prm.covariance ? t->unc_sigma2 : 0.0;
-    r.window_frames = W;
-    for (int i = 0; i < W; i++) r.frame_index[i] = t->n - W + i;
-    if (r.cov_valid) memcpy(r.cov, u + LIVE_UNC_HDR, 36 * (size_t)W * sizeof(double));
-    r.has_marginal = t->has_marginal;
-    r.marginal_index = t->has_marginal ? t->n - W + 1 : -1;
-    if (t->has_marginal) {
-        memcpy(r.marginal_info, u + LIVE_UNC_LM, 36 * sizeof(double));
-        memcpy(r.marginal_mean, u + LIVE_UNC_M, 6 * sizeof(double));
-    }
-    r.marginal_dropped = t->marginal_dropped;
-    memcpy(out, &r, std::min<size_t>(out->struct_size, sizeof r));
+    live_fill_uncertainty(t->prm, t->h_res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES, t->unc_W, t->n, t->has_marginal, t->marginal_dropped, t->unc_sigma2, out);
     return AAR_OK;
 }
 
@@ -3423,23 +3508,398 @@ int aar_tracker_window(aar_tracker *t, int32_t *n_out, int64_t *frame_index, dou
                        int32_t *has_anchor) {
     if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_window: null argument");
     const int slots = t->prm.lag + 1;
-    const int W = (int)std::min<int64_t>(t->n, slots);
-    const bool anchored = t->n - 1 - slots >= 0;
-    if (n_out) *n_out = W;
-    if (has_anchor) *has_anchor = anchored ? 1 : 0;
-    if (frame_index) for (int i = 0; i < W; i++) frame_index[i] = t->n - W + i;
-    if (W == 0 || (!poses && !frame_err && !pair_err && !anchor_pose)) return AAR_OK;
+    live_window_out(nullptr, t->n, slots, n_out, frame_index, poses, frame_err, pair_err, anchor_pose, has_anchor);
+    if (t->n == 0 || (!poses && !frame_err && !pair_err && !anchor_pose)) return AAR_OK;
     HIP_TRY(hipSetDevice(t->device));
     double st[LIVE_ST_RES];
     const char *what = "";
     if (d2h(st, t->d_state, sizeof st, t->stream, &what)) return set_error(AAR_ERR_HIP, "aar_tracker_window: %s failed", what);
-    for (int i = 0; i < W; i++) {
-        const int sl = (int)((t->n - W + i) % slots);
-        if (poses) memcpy(poses + 6 * (size_t)i, st + 6 * sl, 6 * sizeof(double));
-        if (frame_err) frame_err[i] = st[LIVE_ST_EF + i];
-        if (pair_err) pair_err[i] = st[LIVE_ST_PE + i];
+    live_window_out(st, t->n, slots, nullptr, nullptr, poses, frame_err, pair_err, anchor_pose, nullptr);
+    return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tracker bank: B live trackers in lockstep, member b = workgroup b of one launch
+// ------------------------------------------------------------------------------------------------
+struct aar_tracker_bank {
+    struct Member {
+        int C = 0, M = 0, rc = 0, rm = 0;
+        double marker_size = 0, half_size = 0;
+        size_t ent0 = 0, cam0 = 0;       // its first entity row / camera in the bank's tables
+        std::vector<double> sol_x, sol_K, sol_dist;
+        int cnt[LIVE_MAX_W];             // detections by ring slot
+        int has_marginal = 0;
+        int64_t marginal_dropped = 0;
+        double unc_sigma2 = 0;
+        aar_tracker_detection_params det;
+    };
+    aar_tracker_params prm;
+    aar_lm_params lm;
+    int B = 0, device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<Member> mem;
+    double *d_ent = nullptr, *d_K = nullptr;
+    double *d_state = nullptr;           // [B][LIVE_ST_RES]: zslot | anchor | Ef | Pe of every member
+    double *d_out = nullptr;             // [B][out_stride]: result | start record (| uncertainty record) of every member: ONE copy back
+    char *d_ring = nullptr;              // [lag + 1][B] slots
+    LiveMember *d_tab = nullptr;         // [B]
+    char *h_stage = nullptr;             // pinned: [B] slots
+    double *h_out = nullptr;             // pinned: [B][out_stride]
+    size_t slot_bytes = 0, out_stride = 0, total_ent = 0, total_cams = 0;
+    int64_t n = 0;
+    double times[LIVE_MAX_W];
+    bool unc_set = false;
+    int unc_W = 0;
+    bool det_on = false;
+    void *d_cams = nullptr;
+    double *d_toroot = nullptr, *d_work = nullptr;
+    LiveInitMember *d_itab = nullptr;
+    std::vector<int32_t> order;
+    aar_tracker_bank_stats stats;
+};
+
+namespace {
+
+// an error of a member's check, with the member in front of the message
+int bank_member_error(int rc, int b) {
+    const std::string msg = aar_last_error();
+    return set_error(rc, "member %d: %s", b, msg.c_str());
+}
+
+int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, const int32_t *n_obs, const int32_t *obs_cam, const int32_t *obs_marker,
+              const float *obs_uv, const double *pose_init, const uint8_t *has_init, aar_tracker_result *results, aar_tracker_start_info *infos) {
+    if (!k || !n_obs) return set_error(AAR_ERR_INVALID, "%s: null argument", fn);
+    const auto t0 = std::chrono::steady_clock::now();
+    const aar_tracker_params &p = k->prm;
+    const int B = k->B, slots = p.lag + 1;
+    const int64_t n = k->n;
+    if (raw && !k->det_on) return set_error(AAR_ERR_INVALID, "%s: call aar_tracker_bank_enable_detections first", fn);
+    // every member's input is checked before anything is touched: a bank push is all or nothing
+    char who[32];
+    size_t off = 0;
+    for (int b = 0; b < B; b++) {
+        snprintf(who, sizeof who, "member %d: ", b);
+        const aar_tracker_bank::Member &m = k->mem[b];
+        if (int rc = live_check_frame(fn, who, raw, m.C, m.M, p.max_obs_per_frame, n_obs[b], obs_cam ? obs_cam + off : nullptr,
+                                      obs_marker ? obs_marker + off : nullptr, obs_uv ? obs_uv + 8 * off : nullptr))
+            return rc;
+        off += (size_t)n_obs[b];
     }
-    if (anchor_pose) for (int k = 0; k < 6; k++) anchor_pose[k] = anchored ? st[LIVE_ST_ANCHOR + k] : 0.0;
+    if (!std::isfinite(frame_time)) return set_error(AAR_ERR_INVALID, "%s: frame_time is not finite", fn);
+    const int ns = (int)(n % slots), ps = (int)((n + slots - 1) % slots);
+    if (n > 0 && (!(frame_time > k->times[ps]) || !std::isfinite(frame_time - k->times[ps])))
+        return set_error(AAR_ERR_INVALID, "%s: frame_time = %g does not ascend from the previous push's %g", fn, frame_time, k->times[ps]);
+    bool all_init = true;
+    for (int b = 0; b < B; b++) {
+        snprintf(who, sizeof who, "member %d: ", b);
+        const aar_tracker_bank::Member &m = k->mem[b];
+        const double *init = pose_init && (!has_init || has_init[b]) ? pose_init + 6 * (size_t)b : nullptr;
+        all_init = all_init && init;
+        if (n == 0 && !init && !raw) return set_error(AAR_ERR_INVALID, "%s: %sthe first push needs a pose_init", fn, who);
+        if (n == 0 && !init && !live_do_vote(m.det, n_obs[b], false))
+            return set_error(AAR_ERR_INVALID, "%s: %sthe first push has %d detections, fewer than min_detections = %d, and no pose_init: nothing to start from",
+                             fn, who, (int)n_obs[b], (int)m.det.min_detections);
+        if (int rc = live_check_pose_init(fn, who, init)) return rc;
+    }
+    HIP_TRY(hipSetDevice(k->device));
+    // the new slot of every member, staged one behind the other: ONE copy.  The header's idle doubles carry what differs by member
+    size_t copy_bytes = 0;
+    off = 0;
+    for (int b = 0; b < B; b++) {
+        char *slot = k->h_stage + (size_t)b * k->slot_bytes;
+        const double *init = pose_init && (!has_init || has_init[b]) ? pose_init + 6 * (size_t)b : nullptr;
+        const size_t used = live_stage_slot(slot, k->mem[b].C, raw, n_obs[b], obs_cam ? obs_cam + off : nullptr, obs_marker ? obs_marker + off : nullptr,
+                                            obs_uv ? obs_uv + 8 * off : nullptr, init, k->order);
+        double *hdr = reinterpret_cast<double *>(slot);
+        hdr[LIVE_HDR_CNT] = (double)n_obs[b];
+        hdr[LIVE_HDR_INIT] = init ? 1.0 : 0.0;
+        copy_bytes = (size_t)b * k->slot_bytes + used;
+        off += (size_t)n_obs[b];
+    }
+    LiveBankArgs ba;
+    memset(&ba, 0, sizeof ba);
+    live_window_args(ba.sh, p, k->lm, n, frame_time, k->times);
+    ba.sh.slot_bytes = (size_t)B * k->slot_bytes;
+    ba.tab = k->d_tab; ba.raw = raw ? 1 : 0; ba.fresh = n == 0 ? 1 : 0;
+    const int W = ba.sh.W;
+    const bool marginal = ba.sh.marginal != 0, tail = marginal || p.covariance;
+    char *new_slots = k->d_ring + (size_t)ns * B * k->slot_bytes;
+    aar_tracker_bank_stats &st = k->stats;
+    HIP_TRY(hipMemcpyAsync(new_slots, k->h_stage, copy_bytes, hipMemcpyHostToDevice, k->stream));
+    st.h2d_copies++; st.h2d_bytes += (int64_t)copy_bytes;
+    const size_t out_bytes = (size_t)B * k->out_stride * sizeof(double);
+    if (raw) {
+        LiveInitBankArgs li;
+        li.tab = k->d_itab; li.slot0 = new_slots; li.slot_bytes = k->slot_bytes; li.max_obs = (size_t)p.max_obs_per_frame;
+        li.has_prev = n > 0 ? 1 : 0; li.prev_slot = ps; li.huber = ba.sh.huber;
+        launch_live_init_bank(li, B, k->stream);
+        st.launches++;
+        if (n == 0 && !all_init) {
+            // the only push a vote can fail with nothing to fall back on: read the start records before any window is touched
+            HIP_TRY(hipMemcpyAsync(k->h_out, k->d_out, out_bytes, hipMemcpyDeviceToHost, k->stream));
+            st.d2h_copies++; st.d2h_bytes += (int64_t)out_bytes;
+            HIP_TRY(hipStreamSynchronize(k->stream));
+            if (int rc = check_async("k_live_init_bank")) return rc;
+            for (int b = 0; b < B; b++) {
+                const double *h_info = k->h_out + (size_t)b * k->out_stride + LIVE_RES_DOUBLES;
+                if (h_info[4] < 0.0)
+                    return set_error(AAR_ERR_NUMERIC, "%s: member %d: no finite object pose candidate among %d, and neither a pose_init nor a previous estimate",
+                                     fn, b, (int)h_info[1]);
+            }
+        }
+    }
+    launch_live_push_bank(ba, B, k->stream);
+    st.launches++;
+    if (tail) k->unc_set = false;   // the copy overwrites the records aar_tracker_bank_uncertainty serves
+    HIP_TRY(hipMemcpyAsync(k->h_out, k->d_out, out_bytes, hipMemcpyDeviceToHost, k->stream));
+    st.d2h_copies++; st.d2h_bytes += (int64_t)out_bytes;
+    HIP_TRY(hipStreamSynchronize(k->stream));
+    if (int rc = check_async("k_live_push_bank")) return rc;
+    // the push is accepted
+    for (int b = 0; b < B; b++) {
+        aar_tracker_bank::Member &m = k->mem[b];
+        const double *h = k->h_out + (size_t)b * k->out_stride;
+        if (tail) {
+            // rows as the member's workgroup counted them (its has_marginal was the one this member held)
+            int64_t det = n_obs[b];
+            for (int i = 0; i < W - 1; i++) det += m.cnt[(ba.sh.first_slot + i) % slots];
+            const double rows = live_rows(ba.sh, det, marginal ? m.has_marginal : 0);
+            const double *u = h + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
+            m.has_marginal = marginal && u[LIVE_UNC_HAS] != 0.0 ? 1 : 0;
+            if (marginal && u[LIVE_UNC_DROP] != 0.0) m.marginal_dropped++;
+            m.unc_sigma2 = live_sigma2(rows, W, h[4]);
+        }
+        m.cnt[ns] = n_obs[b];
+        if (results) live_fill_result(h, n, W, slots, t0, results + b);
+        if (infos) live_fill_info(h + LIVE_RES_DOUBLES, infos + b);
+    }
+    if (tail) { k->unc_set = true; k->unc_W = W; }
+    k->times[ns] = frame_time;
+    k->n = n + 1;
+    st.pushes++;
+    return AAR_OK;
+}
+
+}  // namespace
+
+int aar_tracker_bank_params_validate(int32_t n_members, const aar_dataset *const *solutions, const aar_tracker_params *in) {
+    if (!solutions || !in) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_params_validate: null argument");
+    if (n_members < 1 || n_members > AAR_TRACKER_BANK_MAX_MEMBERS)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_bank: n_members = %d is outside 1 .. %d", (int)n_members, AAR_TRACKER_BANK_MAX_MEMBERS);
+    for (int b = 0; b < n_members; b++) {
+        if (!solutions[b]) return set_error(AAR_ERR_INVALID, "aar_tracker_bank: member %d: null solution", b);
+        if (int rc = aar_tracker_params_validate(solutions[b], in)) return bank_member_error(rc, b);
+    }
+    return AAR_OK;
+}
+
+void aar_tracker_bank_destroy(aar_tracker_bank *k) {
+    if (!k) return;
+    (void)hipSetDevice(k->device);
+    if (k->stream) (void)hipStreamSynchronize(k->stream);
+    void *dev[] = {k->d_ent, k->d_K, k->d_state, k->d_out, k->d_ring, k->d_tab, k->d_cams, k->d_toroot, k->d_work, k->d_itab};
+    for (void *q : dev)
+        if (q) (void)hipFree(q);
+    if (k->h_stage) (void)hipHostFree(k->h_stage);
+    if (k->h_out) (void)hipHostFree(k->h_out);
+    if (k->stream) (void)hipStreamDestroy(k->stream);
+    delete k;
+}
+
+int aar_tracker_bank_create(int32_t n_members, const aar_dataset *const *solutions, const aar_tracker_params *in, const aar_lm_params *lm,
+                            aar_tracker_bank **out) {
+    if (!solutions || !in || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_create: null argument");
+    *out = nullptr;
+    int rc = aar_tracker_bank_params_validate(n_members, solutions, in);
+    if (rc) return rc;
+    aar_tracker_params p;
+    (void)tracker_params_read(in, &p);
+    if ((rc = ensure_device(p.device_id))) return rc;
+    aar_tracker_bank *k = new aar_tracker_bank();
+    const int B = n_members, slots = p.lag + 1;
+    k->prm = p;
+    if (lm) k->lm = *lm; else aar_lm_default_params(&k->lm);
+    k->B = B; k->device = p.device_id;
+    memset(&k->stats, 0, sizeof k->stats);
+    k->stats.members = B;
+    for (int i = 0; i < LIVE_MAX_W; i++) k->times[i] = 0.0;
+    k->mem.resize((size_t)B);
+    std::vector<double> z, Ks;
+    for (int b = 0; b < B; b++) {
+        const aar_dataset *sol = solutions[b];
+        aar_tracker_bank::Member &m = k->mem[b];
+        m.C = sol->num_cams; m.M = sol->num_markers; m.rc = sol->root_cam; m.rm = sol->root_marker;
+        m.marker_size = sol->marker_size; m.half_size = (double)((float)sol->marker_size / 2.f);
+        m.ent0 = k->total_ent; m.cam0 = k->total_cams;
+        k->total_ent += (size_t)(m.C + m.M); k->total_cams += (size_t)m.C;
+        if (sol->x_full) m.sol_x.assign(sol->x_full, sol->x_full + 6 * (size_t)(m.C - 1 + m.M - 1));
+        m.sol_K.assign(sol->cam_mats, sol->cam_mats + 9 * (size_t)m.C);
+        m.sol_dist.assign(5 * (size_t)m.C, 0.0);
+        if (sol->dist_coeffs) m.sol_dist.assign(sol->dist_coeffs, sol->dist_coeffs + 5 * (size_t)m.C);
+        for (int i = 0; i < LIVE_MAX_W; i++) m.cnt[i] = 0;
+        aar_tracker_default_detection_params(&m.det);
+        live_solution_z(sol, z);
+        Ks.insert(Ks.end(), sol->cam_mats, sol->cam_mats + 9 * (size_t)m.C);
+    }
+    const bool tail = p.anchor_mode == AAR_TRACKER_ANCHOR_MARGINAL || p.covariance;
+    k->slot_bytes = live_slot_bytes(p.max_obs_per_frame);
+    k->out_stride = LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + (tail ? LIVE_UNC_HDR + (p.covariance ? 36 * (size_t)slots : 0) : 0);
+    const size_t ring_bytes = (size_t)slots * B * k->slot_bytes, state_bytes = (size_t)B * LIVE_ST_RES * sizeof(double),
+                 out_bytes = (size_t)B * k->out_stride * sizeof(double);
+    double *d_z = nullptr;
+    auto fail = [&](int code) { if (d_z) (void)hipFree(d_z); aar_tracker_bank_destroy(k); return code; };
+    if (hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipStreamCreate failed"));
+    if (hipMalloc((void **)&k->d_ent, k->total_ent * ENT_STRIDE * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&k->d_K, 9 * k->total_cams * sizeof(double)) != hipSuccess || hipMalloc((void **)&k->d_state, state_bytes) != hipSuccess ||
+        hipMalloc((void **)&k->d_out, out_bytes) != hipSuccess || hipMalloc((void **)&k->d_ring, ring_bytes) != hipSuccess ||
+        hipMalloc((void **)&k->d_tab, (size_t)B * sizeof(LiveMember)) != hipSuccess || hipMalloc((void **)&d_z, z.size() * sizeof(double)) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: hipMalloc failed (%d members, ring of %zu bytes)", B, ring_bytes));
+    if (hipHostMalloc((void **)&k->h_stage, (size_t)B * k->slot_bytes, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&k->h_out, out_bytes, hipHostMallocDefault) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: hipHostMalloc failed"));
+    memset(k->h_stage, 0, (size_t)B * k->slot_bytes);
+    if (hipMemsetAsync(k->d_state, 0, state_bytes, k->stream) != hipSuccess || hipMemsetAsync(k->d_out, 0, out_bytes, k->stream) != hipSuccess ||
+        hipMemsetAsync(k->d_ring, 0, ring_bytes, k->stream) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: hipMemset failed"));
+    // the member table: written once
+    std::vector<LiveMember> tab((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const aar_tracker_bank::Member &m = k->mem[b];
+        LiveMember &r = tab[b];
+        double *stt = k->d_state + (size_t)b * LIVE_ST_RES;
+        r.ent = k->d_ent + m.ent0 * ENT_STRIDE; r.Kmat = k->d_K + 9 * m.cam0; r.h = m.half_size;
+        r.ring = k->d_ring + (size_t)b * k->slot_bytes;
+        r.zslot = stt; r.anchor = stt + LIVE_ST_ANCHOR; r.Ef = stt + LIVE_ST_EF; r.Pe = stt + LIVE_ST_PE;
+        r.res = k->d_out + (size_t)b * k->out_stride;
+        r.unc = tail ? r.res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES : nullptr;
+    }
+    const char *what = "";
+    if (h2d(d_z, z.data(), z.size() * sizeof(double), k->stream, &what) || h2d(k->d_K, Ks.data(), Ks.size() * sizeof(double), k->stream, &what) ||
+        h2d(k->d_tab, tab.data(), tab.size() * sizeof(LiveMember), k->stream, &what))
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: %s failed", what));
+    // the entity rows of every member's fixed cameras and markers in ONE launch of the problem's unpack kernel (roots: the identity)
+    DeviceProblem P;
+    P.C = (int)k->total_ent; P.M = 0; P.A = (int)k->total_ent; P.F = 0; P.intr = 0;
+    P.z[0] = d_z; P.ent[0] = k->d_ent;
+    launch_unpack(P, 0, k->stream);
+    if (hipStreamSynchronize(k->stream) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: the unpack launch failed"));
+    (void)hipFree(d_z);
+    d_z = nullptr;
+    if ((rc = check_async("tracker bank creation"))) return fail(rc);
+    *out = k;
+    return AAR_OK;
+}
+
+int32_t aar_tracker_bank_size(const aar_tracker_bank *k) { return k ? k->B : 0; }
+
+int aar_tracker_bank_reset(aar_tracker_bank *k) {
+    if (!k) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_reset: null argument");
+    k->n = 0;
+    k->det_on = false;   // (the buffers stay; aar_tracker_bank_enable_detections fills them again)
+    k->unc_set = false;  // (the device's marginals stay where they are: the first push of a bank reads none)
+    for (auto &m : k->mem) { m.has_marginal = 0; m.marginal_dropped = 0; }
+    return AAR_OK;
+}
+
+int aar_tracker_bank_push(aar_tracker_bank *k, double frame_time, const int32_t *n_obs, const int32_t *obs_cam, const int32_t *obs_marker,
+                          const float *obs_uv, const double *pose_init, const uint8_t *has_init, aar_tracker_result *results) {
+    return bank_push(k, "aar_tracker_bank_push", false, frame_time, n_obs, obs_cam, obs_marker, obs_uv, pose_init, has_init, results, nullptr);
+}
+
+int aar_tracker_bank_push_detections(aar_tracker_bank *k, double frame_time, const int32_t *n_det, const int32_t *det_cam, const int32_t *det_marker,
+                                     const float *det_uv_raw, const double *pose_init, const uint8_t *has_init, aar_tracker_result *results,
+                                     aar_tracker_start_info *infos) {
+    return bank_push(k, "aar_tracker_bank_push_detections", true, frame_time, n_det, det_cam, det_marker, det_uv_raw, pose_init, has_init, results, infos);
+}
+
+int aar_tracker_bank_enable_detections(aar_tracker_bank *k, const aar_tracker_detection_params *const *per_member) {
+    if (!k) {   // no bank exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_tracker_bank_enable_detections: null bank");
+    }
+    if (k->det_on) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_enable_detections: already enabled (aar_tracker_bank_reset first)");
+    if (k->n != 0)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_bank_enable_detections: call it after aar_tracker_bank_create or aar_tracker_bank_reset, before the first push");
+    const int B = k->B;
+    aar_tracker_detection_params dflt;
+    aar_tracker_default_detection_params(&dflt);
+    std::vector<aar_tracker_detection_params> det((size_t)B);
+    for (int b = 0; b < B; b++)
+        if (int rc = detection_params_check(k->mem[b].C, per_member && per_member[b] ? per_member[b] : &dflt, &det[b])) return bank_member_error(rc, b);
+    if (k->prm.max_obs_per_frame > LIVE_DET_MAX_OBS)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_tracker_bank_enable_detections: max_obs_per_frame = %d is above %d (a member's vote runs in one workgroup)",
+                         (int)k->prm.max_obs_per_frame, LIVE_DET_MAX_OBS);
+    HIP_TRY(hipSetDevice(k->device));
+    const size_t mo = (size_t)k->prm.max_obs_per_frame, work = live_init_work_doubles(mo), cam_row = 9 + AAR_MAX_DIST;
+    if (!k->d_cams) HIP_TRY(hipMalloc(&k->d_cams, k->total_cams * cam_row * sizeof(double)));
+    if (!k->d_toroot) HIP_TRY(hipMalloc((void **)&k->d_toroot, 12 * k->total_ent * sizeof(double)));
+    if (!k->d_work) HIP_TRY(hipMalloc((void **)&k->d_work, (size_t)B * work * sizeof(double)));
+    if (!k->d_itab) HIP_TRY(hipMalloc((void **)&k->d_itab, (size_t)B * sizeof(LiveInitMember)));
+    std::vector<double> tab(k->total_cams * cam_row, 0.0), tr(12 * k->total_ent, 0.0);
+    std::vector<LiveInitMember> itab((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const aar_tracker_bank::Member &m = k->mem[b];
+        live_detection_tables(m.C, m.M, m.rc, m.rm, det[b].cams, m.sol_x.data(), m.sol_K.data(), m.sol_dist.data(), &tab[m.cam0 * cam_row], &tr[12 * m.ent0]);
+        LiveInitMember &r = itab[b];
+        r.cams = reinterpret_cast<const double *>(k->d_cams) + m.cam0 * cam_row;
+        r.Tcr = k->d_toroot + 12 * m.ent0; r.Tmr = r.Tcr + 12 * (size_t)m.C;
+        r.C = m.C; r.policy = det[b].start_policy; r.min_detections = det[b].min_detections;
+        r.hf = (float)m.marker_size / 2.0f; r.h = m.marker_size / 2; r.threshold = det[b].ippe_threshold;   // as the Initializer: float for IPPE, double for the vote
+        r.ent = k->d_ent + m.ent0 * ENT_STRIDE; r.Kmat = k->d_K + 9 * m.cam0; r.h_track = m.half_size;
+        r.zslot = k->d_state + (size_t)b * LIVE_ST_RES;
+        r.work = k->d_work + (size_t)b * work;
+        r.info = k->d_out + (size_t)b * k->out_stride + LIVE_RES_DOUBLES;
+    }
+    const char *what = "";
+    if (h2d(k->d_cams, tab.data(), tab.size() * sizeof(double), k->stream, &what) || h2d(k->d_toroot, tr.data(), tr.size() * sizeof(double), k->stream, &what) ||
+        h2d(k->d_itab, itab.data(), itab.size() * sizeof(LiveInitMember), k->stream, &what))
+        return set_error(AAR_ERR_HIP, "aar_tracker_bank_enable_detections: %s failed", what);
+    HIP_TRY(hipStreamSynchronize(k->stream));
+    for (int b = 0; b < B; b++) {
+        det[b].cams = nullptr;   // (copied; the caller's array is not kept)
+        k->mem[b].det = det[b];
+    }
+    k->det_on = true;
+    return AAR_OK;
+}
+
+int aar_tracker_bank_uncertainty(aar_tracker_bank *k, int32_t member, aar_tracker_uncertainty_record *out) {
+    if (!k || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_uncertainty: null argument");
+    if (member < 0 || member >= k->B) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_uncertainty: member = %d is outside 0 .. %d", (int)member, k->B - 1);
+    if (k->prm.anchor_mode == AAR_TRACKER_ANCHOR_FIXED && !k->prm.covariance)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_bank_uncertainty: the bank was created with anchor_mode fixed and covariance = 0: nothing is kept");
+    if (!k->unc_set || k->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_uncertainty: no push since creation / reset");
+    if (out->struct_size < offsetof(aar_tracker_uncertainty_record, cov_valid) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_bank_uncertainty: struct_size %u does not reach cov_valid", (unsigned)out->struct_size);
+    const aar_tracker_bank::Member &m = k->mem[member];
+    live_fill_uncertainty(k->prm, k->h_out + (size_t)member * k->out_stride + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES, k->unc_W, k->n, m.has_marginal,
+                          m.marginal_dropped, m.unc_sigma2, out);
+    return AAR_OK;
+}
+
+int aar_tracker_bank_window(aar_tracker_bank *k, int32_t member, int32_t *n_out, int64_t *frame_index, double *poses, double *frame_err, double *pair_err,
+                            double anchor_pose[6], int32_t *has_anchor) {
+    if (!k) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_window: null argument");
+    if (member < 0 || member >= k->B) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_window: member = %d is outside 0 .. %d", (int)member, k->B - 1);
+    const int slots = k->prm.lag + 1;
+    live_window_out(nullptr, k->n, slots, n_out, frame_index, poses, frame_err, pair_err, anchor_pose, has_anchor);
+    if (k->n == 0 || (!poses && !frame_err && !pair_err && !anchor_pose)) return AAR_OK;
+    HIP_TRY(hipSetDevice(k->device));
+    double st[LIVE_ST_RES];
+    const char *what = "";
+    if (d2h(st, k->d_state + (size_t)member * LIVE_ST_RES, sizeof st, k->stream, &what)) return set_error(AAR_ERR_HIP, "aar_tracker_bank_window: %s failed", what);
+    live_window_out(st, k->n, slots, nullptr, nullptr, poses, frame_err, pair_err, anchor_pose, nullptr);
+    return AAR_OK;
+}
+
+int aar_tracker_bank_get_stats(const aar_tracker_bank *k, aar_tracker_bank_stats *out) {
+    if (!k || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_get_stats: null argument");
+    const size_t cap = out->struct_size;
+    if (cap < 2 * sizeof(int32_t) || cap > 4096)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_bank_stats.struct_size is not set (sizeof(aar_tracker_bank_stats) of the caller)");
+    aar_tracker_bank_stats st = k->stats;
+    st.struct_size = (uint32_t)std::min(cap, sizeof st);
+    memcpy(out, &st, std::min(cap, sizeof st));
     return AAR_OK;
 }
 

@@ -349,6 +349,26 @@ constexpr int LIVE_UNC_DOUBLES = LIVE_UNC_HDR + 36 * LIVE_MAX_W;
 constexpr double LIVE_MARGINAL_PIVOT_REL = 1e-10;
 void launch_live_push(const LiveArgs &a, hipStream_t st);   // ONE launch; the tail instance when marginal or covariance is set
 
+// tracker bank: B independent live trackers advance in lockstep, workgroup b of k_live_push_bank runs member b's push.
+// The ring is [slot][member]: the slots one push fills are contiguous (ONE copy), member b's ring is ring + b slot_bytes with stride B slot_bytes.
+// What differs by member and push rides in the slot header's two idle doubles: [6] the frame's detection count, [7] its header holds a start pose.
+constexpr int LIVE_HDR_CNT = 6, LIVE_HDR_INIT = 7;
+struct LiveMember {                       // one row of the member table, written once at create
+    const double *ent, *Kmat;             // the member's solution
+    double h;
+    const char *ring;                     // bank ring + b slot_bytes
+    double *zslot, *anchor, *Ef, *Pe;     // the member's state (as LiveArgs)
+    double *res, *unc;                    // the member's records in the bank's output block
+};
+struct LiveBankArgs {
+    LiveArgs sh;                          // what all members share: LM parameters, huber, W, slots, first_slot, has_anchor, smooth, lam, anchor_pair,
+                                          // marginal, covariance; slot_bytes = the ring's slot stride B slot_bytes.  The rest is the member's: unused
+    const LiveMember *tab;                // [B]
+    int raw;                              // the push is of raw detections: k_live_init_bank has written every header's start pose
+    int fresh;                            // the first push since creation / reset: no marginal prior whatever the device still holds
+};
+void launch_live_push_bank(const LiveBankArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
+
 // the start of a frame pushed as raw detections (live_init_kernels.hip): undistortion, IPPE, the object pose candidates and
 // their vote in ONE launch of one workgroup, on the slot the frame was just copied into
 constexpr int LIVE_START_VOTE = 1, LIVE_START_BEST = 2;   // AAR_TRACKER_START_*
@@ -368,6 +388,30 @@ struct LiveInitArgs {
     double *info;                         // [LIVE_INFO_DOUBLES]
 };
 void launch_live_init(const LiveInitArgs &a, hipStream_t st);   // ONE launch
+// the doubles of one k_live_init workspace (poses | Tc | BJ | cost, then has2 | fin as ints), and its carving
+inline size_t live_init_work_doubles(size_t max_obs) { return 98 * max_obs + (3 * max_obs * sizeof(int) + sizeof(double) - 1) / sizeof(double); }
+__host__ __device__ inline void live_init_work_carve(LiveInitArgs &a, double *work, size_t max_obs) {
+    a.poses = work; a.Tc = a.poses + 24 * max_obs; a.BJ = a.Tc + 24 * max_obs; a.cost = a.BJ + 48 * max_obs;
+    a.has2 = reinterpret_cast<int *>(a.cost + 2 * max_obs); a.fin = a.has2 + max_obs;
+}
+// the bank's start: workgroup b does k_live_init's work on member b's new slot, in its own workspace slice
+struct LiveInitMember {                   // one row of the table, written at aar_tracker_bank_enable_detections
+    const void *cams; const double *Tcr, *Tmr;
+    int C, policy, min_detections;
+    float hf; double h, threshold;
+    const double *ent, *Kmat; double h_track;
+    const double *zslot;                  // the member's poses by ring slot
+    double *work;                         // live_init_work_doubles(max_obs) of its own
+    double *info;
+};
+struct LiveInitBankArgs {
+    const LiveInitMember *tab;            // [B]
+    char *slot0;                          // the new slot of member 0; member b's follows at b slot_bytes
+    size_t slot_bytes, max_obs;
+    int has_prev, prev_slot;              // a previous frame exists, its ring slot
+    float huber;
+};
+void launch_live_init_bank(const LiveInitBankArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
 
 // covariance (cov_kernels.hip): S (stride n_pad) -> S2 (stride n2 >= n_pad, zero beyond n_pad), rows with rowmask set -> identity
 void launch_cov_stage(const double *S, int n_pad, double *S2, int n2, const int32_t *rowmask, hipStream_t st);

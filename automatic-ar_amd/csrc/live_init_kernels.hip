@@ -38,8 +38,8 @@ __device__ __forceinline__ bool finite12(const double *p) {
     return ok;
 }
 
-__global__ void __launch_bounds__(LI_THREADS) k_live_init(const LiveInitArgs a) {
-    __shared__ LiveInitShared s;
+// The start of one frame by one workgroup of LI_THREADS threads: the kernels below call it.
+__device__ __forceinline__ void live_init_body(const LiveInitArgs &a, LiveInitShared &s) {
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n = a.n_det;
     char *recs = a.slot + LIVE_HDR_BYTES;
@@ -175,7 +175,48 @@ __global__ void __launch_bounds__(LI_THREADS) k_live_init(const LiveInitArgs a) 
     }
 }
 
+__global__ void __launch_bounds__(LI_THREADS) k_live_init(const LiveInitArgs a) {
+    __shared__ LiveInitShared s;
+    live_init_body(a, s);
+}
+
+__device__ __forceinline__ unsigned long long uni64(unsigned long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+template <typename T>
+__device__ __forceinline__ T *uni_ptr(T *p) { return reinterpret_cast<T *>(uni64(reinterpret_cast<unsigned long long>(p))); }
+
+// The bank: workgroup b starts member b's new frame.  The member's row of the table, the shared block and the new slot's
+// header (detection count, whether it holds a pose_init) give its LiveInitArgs; everything is indexed by blockIdx.x alone.  A member's
+// workspace slice is its own, so the workgroups of a launch share nothing but read-only tables.
+__global__ void __launch_bounds__(LI_THREADS) k_live_init_bank(const LiveInitBankArgs ba) {
+    __shared__ LiveInitShared s;
+    const LiveInitMember *m = ba.tab + blockIdx.x;
+    LiveInitArgs a;
+    a.slot = ba.slot0 + (size_t)blockIdx.x * ba.slot_bytes;
+    const double *hdr = reinterpret_cast<const double *>(a.slot);
+    a.n_det = __builtin_amdgcn_readfirstlane((int)hdr[LIVE_HDR_CNT]);
+    a.has_init = __builtin_amdgcn_readfirstlane((int)hdr[LIVE_HDR_INIT]);
+    a.cams = uni_ptr(m->cams); a.Tcr = uni_ptr(m->Tcr); a.Tmr = uni_ptr(m->Tmr);
+    a.C = __builtin_amdgcn_readfirstlane(m->C);
+    a.hf = m->hf; a.h = m->h; a.threshold = m->threshold;
+    a.policy = __builtin_amdgcn_readfirstlane(m->policy);
+    // a vote is held unless the caller's pose_init settles the start (policy VOTE) or the frame has too few detections
+    a.do_vote = (a.n_det >= __builtin_amdgcn_readfirstlane(m->min_detections) && !(a.has_init && a.policy == LIVE_START_VOTE)) ? 1 : 0;
+    a.has_prev = ba.has_prev;
+    a.zprev = uni_ptr(m->zslot) + 6 * ba.prev_slot;
+    a.ent = uni_ptr(m->ent); a.Kmat = uni_ptr(m->Kmat); a.huber = ba.huber; a.h_track = m->h_track;
+    live_init_work_carve(a, uni_ptr(m->work), ba.max_obs);
+    a.info = uni_ptr(m->info);
+    live_init_body(a, s);
+}
+
 }  // namespace
+
+void launch_live_init_bank(const LiveInitBankArgs &a, int B, hipStream_t st) {
+    hipLaunchKernelGGL(k_live_init_bank, dim3(B), dim3(LI_THREADS), 0, st, a);
+}
 
 void launch_live_init(const LiveInitArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(k_live_init, dim3(1), dim3(LI_THREADS), 0, st, a);

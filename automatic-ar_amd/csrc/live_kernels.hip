@@ -37,6 +37,12 @@ struct LiveShared {
     int flag;                                                           // a non-positive pivot in the last solve
 };
 
+// a bank member's workgroup also keeps, by window position, what a single tracker has in its kernel arguments
+struct LiveBankShared : LiveShared {
+    int cnt[LIVE_MAX_W];                // LiveArgs::cnt, read from the window's slot headers
+    double lam[LIVE_MAX_W][2];          // LiveArgs::lam, from the shared argument block
+};
+
 // what the tail instance adds
 struct LiveTail {
     double Lm[36], m[6];                // the marginal prior on the first window frame
@@ -50,8 +56,30 @@ __device__ __forceinline__ const char *live_slot(const LiveArgs &a, int i) {
     return a.ring + (size_t)s * a.slot_bytes;
 }
 
+// a value every lane holds alike, into scalar registers
+__device__ __forceinline__ unsigned long long uni64(unsigned long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+template <typename T>
+__device__ __forceinline__ T *uni_ptr(T *p) { return reinterpret_cast<T *>(uni64(reinterpret_cast<unsigned long long>(p))); }
+__device__ __forceinline__ double uni_f64(double v) { return __longlong_as_double((long long)uni64((unsigned long long)__double_as_longlong(v))); }
+
+// the window's detection counts and pair weights: a single tracker has them in its kernel arguments; a bank member (BANK) in LDS, where its
+// kernel put them (s is then a LiveBankShared) -- a member's LiveArgs is built in registers, which cannot be indexed by window position
+template <bool BANK>
+__device__ __forceinline__ int live_cnt(const LiveArgs &a, const LiveShared &s, int i) {
+    if constexpr (BANK) return __builtin_amdgcn_readfirstlane(static_cast<const LiveBankShared &>(s).cnt[i]);
+    else return a.cnt[i];
+}
+template <bool BANK>
+__device__ __forceinline__ double live_lam(const LiveArgs &a, const LiveShared &s, int i, int k) {
+    if constexpr (BANK) return static_cast<const LiveBankShared &>(s).lam[i][k];
+    else return a.lam[i][k];
+}
+
 // WITH_J: H, b and the costs at s.z; else the costs at s.z + s.dl (-> s.zt) with the linear model's sums
-template <bool WITH_J>
+template <bool WITH_J, bool BANK>
 __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta, LiveShared &s, int wv, int lane) {
     const int W = a.W, out = WITH_J ? 0 : 1;
     for (int i = wv; i < W; i += 4) {
@@ -73,7 +101,7 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
         make_ent_row(zc, rowc);
         double V[21], g[6];
         const char *rec = live_slot(a, i) + LIVE_HDR_BYTES;
-        const double Ef = track_eval_range<WITH_J, LIVE_REC_BYTES, LIVE_REC_BYTES>(ta, rec, rec + sizeof(ObsIdx), 0, a.cnt[i], zc, lane, V, g);
+        const double Ef = track_eval_range<WITH_J, LIVE_REC_BYTES, LIVE_REC_BYTES>(ta, rec, rec + sizeof(ObsIdx), 0, live_cnt<BANK>(a, s, i), zc, lane, V, g);
         double D[6][6], b[6];
         if (WITH_J) {
 #pragma unroll
@@ -99,7 +127,7 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
             make_ent_row(zp, rowp);
             double phi[3], et[3], Ma[9], Mb[9];
             pair_terms<WITH_J>(rowp, rowc, nullptr, phi, et, Ma, Mb);
-            const double lr = a.lam[i][0], lt = a.lam[i][1];
+            const double lr = live_lam<BANK>(a, s, i, 0), lt = live_lam<BANK>(a, s, i, 1);
             Pe = lr * (phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]) + lt * (et[0] * et[0] + et[1] * et[1] + et[2] * et[2]);
             if (WITH_J) {
 #pragma unroll
@@ -119,7 +147,7 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
             make_ent_row(zn, rown);
             double phi[3], et[3], Ma[9], Mb[9];
             pair_terms<true>(rowc, rown, nullptr, phi, et, Ma, Mb);
-            const double lr = a.lam[i + 1][0], lt = a.lam[i + 1][1];
+            const double lr = live_lam<BANK>(a, s, i + 1, 0), lt = live_lam<BANK>(a, s, i + 1, 1);
             double O[36];
 #pragma unroll
             for (int k = 0; k < 36; k++) O[k] = 0.0;
@@ -267,7 +295,9 @@ __device__ __forceinline__ void live_solve(LiveShared &s, int W, double mu) {
 //   elimination   live_solve at mu = 0 leaves P_f^-1 in s.inv
 //   marginal      Lambda' = B - O^T A^-1 O, b' = c - O^T A^-1 a, m' = z_1 + Lambda'^-1 b'   (A = D_0 = P_0, a = b_0, O = O_0)
 //   covariance    Sigma_{W-1} = P_{W-1}^-1, Sigma_f = P_f^-1 + G_f Sigma_{f+1} G_f^T, G_f = P_f^-1 O_f
-// Not inlined: it runs when the LM's registers are dead.
+// Not inlined: it runs when the LM's registers are dead.  One instance per kernel (BANK), so that each has ONE caller and keeps seeing that
+// kernel's LDS objects by their addresses.
+template <bool BANK>
 __device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc, int W, int do_marginal, int do_cov, double lr, double lt, int lane) {
     live_solve(s, W, 0.0);
     const bool ok = s.flag == 0;
@@ -403,14 +433,10 @@ __device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc,
     }
 }
 
-template <bool TAIL>
-__global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
-    __shared__ LiveShared s;
-    LiveTail *tl = nullptr;
-    if constexpr (TAIL) {
-        __shared__ LiveTail tail;
-        tl = &tail;
-    }
+// One push of one tracker by one workgroup of 256 threads: the kernels below call it.  BANK: s is a LiveBankShared whose cnt and lam the caller has filled (a.cnt, a.lam
+// are not read) and the threads have met at a barrier since.
+template <bool TAIL, bool BANK>
+__device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s, LiveTail *tl) {
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform
     const int W = a.W;
     TrackArgs ta;
@@ -448,7 +474,7 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
     __syncthreads();
     bool prior = false;   // the marginal prior is on the first window frame (tail instance only)
     if constexpr (TAIL) prior = a.marginal && a.has_marginal && wv == 0;
-    live_eval<true>(a, ta, s, wv, lane);   // init: the first evaluation also yields the first step's system
+    live_eval<true, BANK>(a, ta, s, wv, lane);   // init: the first evaluation also yields the first step's system
     if constexpr (TAIL) { if (prior) live_prior<true>(s, *tl, lane); }
     __syncthreads();
     double currData = 0.0, currPrior = 0.0;
@@ -459,7 +485,7 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
     int mustExit = 0, iters = 0, rejected = 0, tries = 0;
     for (int it = 0; it < a.max_iters && !mustExit && rows > 0; it++) {
         if (it > 0) {
-            live_eval<true>(a, ta, s, wv, lane);   // H, b at the current point (its costs are those already held)
+            live_eval<true, BANK>(a, ta, s, wv, lane);   // H, b at the current point (its costs are those already held)
             if constexpr (TAIL) { if (prior) live_prior<true>(s, *tl, lane); }
             __syncthreads();
         }
@@ -476,7 +502,7 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
         do {
             if (wv == 0) live_solve(s, W, mu);
             __syncthreads();
-            live_eval<false>(a, ta, s, wv, lane);
+            live_eval<false, BANK>(a, ta, s, wv, lane);
             if constexpr (TAIL) { if (prior) live_prior<false>(s, *tl, lane); }
             __syncthreads();
             double eD = 0.0, eP = 0.0, d2 = 0.0, dg = 0.0;
@@ -527,17 +553,75 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
         const int do_marginal = a.marginal && W == a.slots, do_cov = a.covariance;
         __syncthreads();   // the stores above have read the costs this assembly writes again
         if (do_marginal || do_cov) {
-            live_eval<true>(a, ta, s, wv, lane);
+            live_eval<true, BANK>(a, ta, s, wv, lane);
             if (prior) live_prior<true>(s, *tl, lane);
             __syncthreads();
-            if (wv == 0) live_tail(s, *tl, a.unc, W, do_marginal, do_cov, a.lam[1][0], a.lam[1][1], lane);
+            if (wv == 0) live_tail<BANK>(s, *tl, a.unc, W, do_marginal, do_cov, live_lam<BANK>(a, s, 1, 0), live_lam<BANK>(a, s, 1, 1), lane);
         } else if (t < 3) {
             a.unc[t] = 0.0;   // LIVE_UNC_VALID, _HAS, _DROP: the window is still filling
         }
     }
 }
 
+template <bool TAIL>
+__global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
+    __shared__ LiveShared s;
+    LiveTail *tl = nullptr;
+    if constexpr (TAIL) {
+        __shared__ LiveTail tail;
+        tl = &tail;
+    }
+    live_push_body<TAIL, false>(a, s, tl);
+}
+
+// The bank: workgroup b is member b.  Its LiveArgs: the shared block, the member's row of the table and, from the device's
+// own memory, what differs by member and push -- the window's detection counts and whether the new frame brings a start pose (slot headers),
+// whether a marginal prior exists (the member's uncertainty record), rows.  Everything is indexed by blockIdx.x alone, hence wave-uniform; the
+// workgroups of a launch share nothing but read-only tables.
+template <bool TAIL>
+__global__ void __launch_bounds__(256) k_live_push_bank(const LiveBankArgs ba) {
+    __shared__ LiveBankShared s;
+    LiveTail *tl = nullptr;
+    if constexpr (TAIL) {
+        __shared__ LiveTail tail;
+        tl = &tail;
+    }
+    const int t = threadIdx.x;
+    const LiveMember *m = ba.tab + blockIdx.x;
+    LiveArgs a;
+    a.ent = uni_ptr(m->ent); a.Kmat = uni_ptr(m->Kmat); a.h = uni_f64(m->h); a.ring = uni_ptr(m->ring);
+    a.zslot = uni_ptr(m->zslot); a.anchor = uni_ptr(m->anchor); a.Ef = uni_ptr(m->Ef); a.Pe = uni_ptr(m->Pe);
+    a.res = uni_ptr(m->res); a.unc = uni_ptr(m->unc);
+    a.slot_bytes = ba.sh.slot_bytes; a.huber = ba.sh.huber;
+    a.max_iters = ba.sh.max_iters; a.min_error = ba.sh.min_error; a.min_step_error_diff = ba.sh.min_step_error_diff;
+    a.min_average_step_error_diff = ba.sh.min_average_step_error_diff; a.tau = ba.sh.tau;
+    a.W = ba.sh.W; a.slots = ba.sh.slots; a.first_slot = ba.sh.first_slot;
+    a.has_anchor = ba.sh.has_anchor; a.smooth = ba.sh.smooth; a.anchor_pair = ba.sh.anchor_pair;
+    a.marginal = ba.sh.marginal; a.covariance = ba.sh.covariance;
+    const int W = a.W;
+    if (t < W) s.cnt[t] = (int)reinterpret_cast<const double *>(live_slot(a, t))[LIVE_HDR_CNT];
+    if (t >= 64 && t < 64 + 2 * W) s.lam[(t - 64) >> 1][(t - 64) & 1] = ba.sh.lam[(t - 64) >> 1][(t - 64) & 1];
+    const double *newest = reinterpret_cast<const double *>(live_slot(a, W - 1));
+    a.has_init = ba.raw ? 1 : __builtin_amdgcn_readfirstlane((int)newest[LIVE_HDR_INIT]);
+    a.has_marginal = 0;
+    if constexpr (TAIL) {
+        if (a.marginal && !ba.fresh) a.has_marginal = __builtin_amdgcn_readfirstlane(a.unc[LIVE_UNC_HAS] != 0.0 ? 1 : 0);
+    }
+    __syncthreads();
+    // rows as the host counts them for a single tracker: 8 per detection of the window, 6 per pair, the anchor pair's 6 the marginal prior's
+    int det = 0;
+    for (int i = 0; i < W; i++) det += live_cnt<true>(a, s, i);
+    const int pairs = a.smooth ? W - 1 + (a.marginal ? a.has_marginal : a.has_anchor) : 0;
+    a.rows = 8.0 * (double)det + 6.0 * (double)pairs;
+    live_push_body<TAIL, true>(a, s, tl);
+}
+
 }  // namespace
+
+void launch_live_push_bank(const LiveBankArgs &a, int B, hipStream_t st) {
+    if (a.sh.marginal || a.sh.covariance) hipLaunchKernelGGL(k_live_push_bank<true>, dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_live_push_bank<false>, dim3(B), dim3(256), 0, st, a);
+}
 
 void launch_live_push(const LiveArgs &a, hipStream_t st) {
     if (a.marginal || a.covariance) hipLaunchKernelGGL(k_live_push<true>, dim3(1), dim3(256), 0, st, a);

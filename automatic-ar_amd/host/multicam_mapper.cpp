@@ -687,87 +687,69 @@ bool MultiCamMapper::write_live_covariance_file(const std::string &path, const L
     return aar_tracker_covariance_write_yaml(path.c_str(), data_, cov.frame_cov.data(), cov.sigma2.data(), cov.valid.data()) == AAR_OK;
 }
 
-LiveTracker::LiveTracker(const MultiCamMapper &solution, const Options &o, const SparseLevMarq<double>::Params *lm) {
-    const aar_dataset *d = solution.dataset();
-    if (!d) throw std::runtime_error("LiveTracker: the mapper holds no solution");
-    for (int c = 0; c < d->num_cams; c++) cam_index_[d->cam_ids[c]] = c;
-    for (int m = 0; m < d->num_markers; m++) marker_index_[d->marker_ids[m]] = m;
+// ---- what LiveTracker and LiveTrackerBank share ----
+namespace {
+
+aar_tracker_params live_params(const LiveTracker::Options &o) {
     aar_tracker_params p;
     aar_tracker_default_params(&p);
     p.lag = o.lag; p.smooth = o.smooth ? 1 : 0; p.sigma_rot = o.sigma_rot; p.sigma_trans = o.sigma_trans;
     p.with_huber = o.with_huber ? 1 : 0; p.huber_delta = o.huber_delta; p.max_obs_per_frame = o.max_obs_per_frame; p.device_id = o.device_id;
     p.anchor_mode = o.anchor_mode; p.covariance = o.covariance ? 1 : 0;
+    return p;
+}
+
+aar_lm_params live_lm_params(const SparseLevMarq<double>::Params *lm) {
     aar_lm_params q;
     aar_lm_default_params(&q);
     if (lm) {
         q.max_iters = lm->maxIters; q.min_error = lm->minError; q.min_step_error_diff = lm->min_step_error_diff;
         q.min_average_step_error_diff = lm->min_average_step_error_diff; q.tau = lm->tau;
     }
-    if (aar_tracker_create(d, &p, &q, &tracker_)) throw std::runtime_error(aar_last_error());
+    return q;
 }
 
-LiveTracker::~LiveTracker() { aar_tracker_destroy(tracker_); }
+void live_index_ids(const aar_dataset *d, std::map<int, int> &cam_index, std::map<int, int> &marker_index) {
+    for (int c = 0; c < d->num_cams; c++) cam_index[d->cam_ids[c]] = c;
+    for (int m = 0; m < d->num_markers; m++) marker_index[d->marker_ids[m]] = m;
+}
 
-aar_tracker_result LiveTracker::push(double frame_time, const std::vector<Detection> &detections, const double *start) {
-    cam_.clear(); marker_.clear(); uv_.clear();
-    for (const Detection &d : detections) {
-        const auto c = cam_index_.find(d.cam_id);
-        const auto m = marker_index_.find(d.marker_id);
-        if (c == cam_index_.end() || m == marker_index_.end()) continue;
-        cam_.push_back(c->second);
-        marker_.push_back(m->second);
-        uv_.insert(uv_.end(), d.uv, d.uv + 8);
+// appends the detections of known cameras and markers by INDEX; returns how many
+int32_t live_append(const std::map<int, int> &cam_index, const std::map<int, int> &marker_index, const std::vector<LiveTracker::Detection> &detections,
+                    std::vector<int32_t> &cam, std::vector<int32_t> &marker, std::vector<float> &uv) {
+    int32_t n = 0;
+    for (const LiveTracker::Detection &d : detections) {
+        const auto c = cam_index.find(d.cam_id);
+        const auto m = marker_index.find(d.marker_id);
+        if (c == cam_index.end() || m == marker_index.end()) continue;
+        cam.push_back(c->second);
+        marker.push_back(m->second);
+        uv.insert(uv.end(), d.uv, d.uv + 8);
+        n++;
     }
-    aar_tracker_result r;
-    memset(&r, 0, sizeof r);
-    r.struct_size = sizeof r;
-    if (aar_tracker_push(tracker_, frame_time, (int32_t)cam_.size(), cam_.data(), marker_.data(), uv_.data(), start, &r)) throw std::runtime_error(aar_last_error());
-    return r;
+    return n;
 }
 
-void LiveTracker::enable_detections(const DetectionOptions &o) {
+// o as aar_tracker_detection_params; by_index keeps the calibrations p.cams points to
+aar_tracker_detection_params live_detection_params(const std::map<int, int> &cam_index, const LiveTracker::DetectionOptions &o,
+                                                   std::vector<aar_cam_model> &by_index, const char *who) {
     aar_tracker_detection_params p;
     aar_tracker_default_detection_params(&p);
-    std::vector<aar_cam_model> by_index;
     if (!o.cams.empty()) {
-        by_index.resize(cam_index_.size());
-        for (const auto &ci : cam_index_) {
+        by_index.resize(cam_index.size());
+        for (const auto &ci : cam_index) {
             const auto it = o.cams.find(ci.first);
-            if (it == o.cams.end()) throw std::runtime_error("LiveTracker::enable_detections: no calibration for camera " + std::to_string(ci.first));
+            if (it == o.cams.end()) throw std::runtime_error(std::string(who) + "::enable_detections: no calibration for camera " + std::to_string(ci.first));
             by_index[ci.second] = it->second;
         }
         p.cams = by_index.data();
     }
     p.ippe_threshold = o.ippe_threshold; p.min_detections = o.min_detections; p.start_policy = o.start_policy;
-    if (aar_tracker_enable_detections(tracker_, &p)) throw std::runtime_error(aar_last_error());
+    return p;
 }
 
-aar_tracker_result LiveTracker::push_detections(double frame_time, const std::vector<Detection> &detections, const double *start,
-                                                aar_tracker_start_info *info) {
-    cam_.clear(); marker_.clear(); uv_.clear();
-    for (const Detection &d : detections) {
-        const auto c = cam_index_.find(d.cam_id);
-        const auto m = marker_index_.find(d.marker_id);
-        if (c == cam_index_.end() || m == marker_index_.end()) continue;
-        cam_.push_back(c->second);
-        marker_.push_back(m->second);
-        uv_.insert(uv_.end(), d.uv, d.uv + 8);
-    }
-    aar_tracker_result r;
-    memset(&r, 0, sizeof r);
-    r.struct_size = sizeof r;
-    if (info) { memset(info, 0, sizeof *info); info->struct_size = sizeof *info; }
-    if (aar_tracker_push_detections(tracker_, frame_time, (int32_t)cam_.size(), cam_.data(), marker_.data(), uv_.data(), start, &r, info))
-        throw std::runtime_error(aar_last_error());
-    return r;
-}
-
-LiveTracker::Window LiveTracker::window() {
-    Window w;
-    int32_t n = 0, has = 0;
-    int64_t idx[AAR_TRACKER_MAX_LAG + 1];
-    double poses[6 * (AAR_TRACKER_MAX_LAG + 1)], fe[AAR_TRACKER_MAX_LAG + 1], pe[AAR_TRACKER_MAX_LAG + 1], anchor[6];
-    if (aar_tracker_window(tracker_, &n, idx, poses, fe, pe, anchor, &has)) throw std::runtime_error(aar_last_error());
+LiveTracker::Window live_window(int32_t n, const int64_t *idx, const double *poses, const double *fe, const double *pe, const double *anchor, int32_t has) {
+    LiveTracker::Window w;
     for (int i = 0; i < n; i++) {
         w.frame_index.push_back(idx[i]);
         std::array<double, 6> z;
@@ -777,8 +759,61 @@ LiveTracker::Window LiveTracker::window() {
         w.pair_err.push_back(pe[i]);
     }
     w.has_anchor = has != 0;
-    if (has) memcpy(w.anchor_pose.data(), anchor, sizeof anchor);
+    if (has) memcpy(w.anchor_pose.data(), anchor, 6 * sizeof(double));
     return w;
+}
+
+aar_tracker_result blank_result() {
+    aar_tracker_result r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = sizeof r;
+    return r;
+}
+
+}  // namespace
+
+LiveTracker::LiveTracker(const MultiCamMapper &solution, const Options &o, const SparseLevMarq<double>::Params *lm) {
+    const aar_dataset *d = solution.dataset();
+    if (!d) throw std::runtime_error("LiveTracker: the mapper holds no solution");
+    live_index_ids(d, cam_index_, marker_index_);
+    const aar_tracker_params p = live_params(o);
+    const aar_lm_params q = live_lm_params(lm);
+    if (aar_tracker_create(d, &p, &q, &tracker_)) throw std::runtime_error(aar_last_error());
+}
+
+LiveTracker::~LiveTracker() { aar_tracker_destroy(tracker_); }
+
+aar_tracker_result LiveTracker::push(double frame_time, const std::vector<Detection> &detections, const double *start) {
+    cam_.clear(); marker_.clear(); uv_.clear();
+    const int32_t n = live_append(cam_index_, marker_index_, detections, cam_, marker_, uv_);
+    aar_tracker_result r = blank_result();
+    if (aar_tracker_push(tracker_, frame_time, n, cam_.data(), marker_.data(), uv_.data(), start, &r)) throw std::runtime_error(aar_last_error());
+    return r;
+}
+
+void LiveTracker::enable_detections(const DetectionOptions &o) {
+    std::vector<aar_cam_model> by_index;
+    const aar_tracker_detection_params p = live_detection_params(cam_index_, o, by_index, "LiveTracker");
+    if (aar_tracker_enable_detections(tracker_, &p)) throw std::runtime_error(aar_last_error());
+}
+
+aar_tracker_result LiveTracker::push_detections(double frame_time, const std::vector<Detection> &detections, const double *start,
+                                                aar_tracker_start_info *info) {
+    cam_.clear(); marker_.clear(); uv_.clear();
+    const int32_t n = live_append(cam_index_, marker_index_, detections, cam_, marker_, uv_);
+    aar_tracker_result r = blank_result();
+    if (info) { memset(info, 0, sizeof *info); info->struct_size = sizeof *info; }
+    if (aar_tracker_push_detections(tracker_, frame_time, n, cam_.data(), marker_.data(), uv_.data(), start, &r, info))
+        throw std::runtime_error(aar_last_error());
+    return r;
+}
+
+LiveTracker::Window LiveTracker::window() {
+    int32_t n = 0, has = 0;
+    int64_t idx[AAR_TRACKER_MAX_LAG + 1];
+    double poses[6 * (AAR_TRACKER_MAX_LAG + 1)], fe[AAR_TRACKER_MAX_LAG + 1], pe[AAR_TRACKER_MAX_LAG + 1], anchor[6];
+    if (aar_tracker_window(tracker_, &n, idx, poses, fe, pe, anchor, &has)) throw std::runtime_error(aar_last_error());
+    return live_window(n, idx, poses, fe, pe, anchor, has);
 }
 
 aar_tracker_uncertainty_record LiveTracker::uncertainty() {
@@ -791,6 +826,111 @@ aar_tracker_uncertainty_record LiveTracker::uncertainty() {
 
 void LiveTracker::reset() {
     if (aar_tracker_reset(tracker_)) throw std::runtime_error(aar_last_error());
+}
+
+// ---- LiveTrackerBank ----
+LiveTrackerBank::LiveTrackerBank(const std::vector<const MultiCamMapper *> &solutions, const LiveTracker::Options &o,
+                                 const SparseLevMarq<double>::Params *lm) {
+    std::vector<const aar_dataset *> ds;
+    for (const MultiCamMapper *s : solutions) {
+        const aar_dataset *d = s ? s->dataset() : nullptr;
+        if (!d) throw std::runtime_error("LiveTrackerBank: member " + std::to_string(ds.size()) + " holds no solution");
+        ds.push_back(d);
+        cam_index_.emplace_back();
+        marker_index_.emplace_back();
+        live_index_ids(d, cam_index_.back(), marker_index_.back());
+    }
+    const aar_tracker_params p = live_params(o);
+    const aar_lm_params q = live_lm_params(lm);
+    if (aar_tracker_bank_create((int32_t)ds.size(), ds.data(), &p, &q, &bank_)) throw std::runtime_error(aar_last_error());
+}
+
+LiveTrackerBank::~LiveTrackerBank() { aar_tracker_bank_destroy(bank_); }
+
+int LiveTrackerBank::size() const { return aar_tracker_bank_size(bank_); }
+
+void LiveTrackerBank::pack(const std::vector<std::vector<LiveTracker::Detection>> &detections, const std::vector<const double *> &starts) {
+    const size_t B = cam_index_.size();
+    if (detections.size() != B || (!starts.empty() && starts.size() != B)) throw std::runtime_error("LiveTrackerBank: one entry per member is needed");
+    n_.clear(); cam_.clear(); marker_.clear(); uv_.clear();
+    for (size_t b = 0; b < B; b++) n_.push_back(live_append(cam_index_[b], marker_index_[b], detections[b], cam_, marker_, uv_));
+    start_.assign(6 * B, 0.0);
+    has_start_.assign(B, 0);
+    any_start_ = false;
+    for (size_t b = 0; b < starts.size(); b++)
+        if (starts[b]) {
+            memcpy(&start_[6 * b], starts[b], 6 * sizeof(double));
+            has_start_[b] = 1;
+            any_start_ = true;
+        }
+}
+
+std::vector<aar_tracker_result> LiveTrackerBank::push(double frame_time, const std::vector<std::vector<LiveTracker::Detection>> &detections,
+                                                      const std::vector<const double *> &starts) {
+    pack(detections, starts);
+    std::vector<aar_tracker_result> r(cam_index_.size(), blank_result());
+    if (aar_tracker_bank_push(bank_, frame_time, n_.data(), cam_.data(), marker_.data(), uv_.data(), any_start_ ? start_.data() : nullptr,
+                              any_start_ ? has_start_.data() : nullptr, r.data()))
+        throw std::runtime_error(aar_last_error());
+    return r;
+}
+
+void LiveTrackerBank::enable_detections(const std::vector<LiveTracker::DetectionOptions> &per_member) {
+    const size_t B = cam_index_.size();
+    if (!per_member.empty() && per_member.size() != B) throw std::runtime_error("LiveTrackerBank::enable_detections: one entry per member, or none");
+    std::vector<std::vector<aar_cam_model>> by_index(B);
+    std::vector<aar_tracker_detection_params> p(B);
+    std::vector<const aar_tracker_detection_params *> ptr(B, nullptr);
+    for (size_t b = 0; b < per_member.size(); b++) {
+        p[b] = live_detection_params(cam_index_[b], per_member[b], by_index[b], "LiveTrackerBank");
+        ptr[b] = &p[b];
+    }
+    if (aar_tracker_bank_enable_detections(bank_, ptr.data())) throw std::runtime_error(aar_last_error());
+}
+
+std::vector<aar_tracker_result> LiveTrackerBank::push_detections(double frame_time, const std::vector<std::vector<LiveTracker::Detection>> &detections,
+                                                                 const std::vector<const double *> &starts, std::vector<aar_tracker_start_info> *infos) {
+    pack(detections, starts);
+    const size_t B = cam_index_.size();
+    std::vector<aar_tracker_result> r(B, blank_result());
+    if (infos) {
+        aar_tracker_start_info si;
+        memset(&si, 0, sizeof si);
+        si.struct_size = sizeof si;
+        infos->assign(B, si);
+    }
+    if (aar_tracker_bank_push_detections(bank_, frame_time, n_.data(), cam_.data(), marker_.data(), uv_.data(), any_start_ ? start_.data() : nullptr,
+                                         any_start_ ? has_start_.data() : nullptr, r.data(), infos ? infos->data() : nullptr))
+        throw std::runtime_error(aar_last_error());
+    return r;
+}
+
+LiveTracker::Window LiveTrackerBank::window(int member) {
+    int32_t n = 0, has = 0;
+    int64_t idx[AAR_TRACKER_MAX_LAG + 1];
+    double poses[6 * (AAR_TRACKER_MAX_LAG + 1)], fe[AAR_TRACKER_MAX_LAG + 1], pe[AAR_TRACKER_MAX_LAG + 1], anchor[6];
+    if (aar_tracker_bank_window(bank_, member, &n, idx, poses, fe, pe, anchor, &has)) throw std::runtime_error(aar_last_error());
+    return live_window(n, idx, poses, fe, pe, anchor, has);
+}
+
+aar_tracker_uncertainty_record LiveTrackerBank::uncertainty(int member) {
+    aar_tracker_uncertainty_record u;
+    memset(&u, 0, sizeof u);
+    u.struct_size = sizeof u;
+    if (aar_tracker_bank_uncertainty(bank_, member, &u)) throw std::runtime_error(aar_last_error());
+    return u;
+}
+
+aar_tracker_bank_stats LiveTrackerBank::stats() const {
+    aar_tracker_bank_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    if (aar_tracker_bank_get_stats(bank_, &st)) throw std::runtime_error(aar_last_error());
+    return st;
+}
+
+void LiveTrackerBank::reset() {
+    if (aar_tracker_bank_reset(bank_)) throw std::runtime_error(aar_last_error());
 }
 
 bool MultiCamMapper::write_solution_file(std::string path) {

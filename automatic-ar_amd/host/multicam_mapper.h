@@ -599,4 +599,38 @@ class LiveTracker {
     std::vector<float> uv_;
 };
 
+// aar_tracker_bank: B live trackers, one per solution, with the same options, advanced in lockstep -- one copy in, one launch of B workgroups and
+// one copy out per push.  Every per-member argument is a vector with one entry per member.
+class LiveTrackerBank {
+   public:
+    LiveTrackerBank(const std::vector<const MultiCamMapper *> &solutions, const LiveTracker::Options &options,
+                    const SparseLevMarq<double>::Params *lm = nullptr);
+    ~LiveTrackerBank();
+    LiveTrackerBank(const LiveTrackerBank &) = delete;
+    LiveTrackerBank &operator=(const LiveTrackerBank &) = delete;
+    int size() const;
+    // detections[b]: member b's frame (empty: the object was not seen); starts: empty, or per member (rvec, t) or NULL = its previous estimate
+    std::vector<aar_tracker_result> push(double frame_time, const std::vector<std::vector<LiveTracker::Detection>> &detections,
+                                         const std::vector<const double *> &starts = {});
+    // per_member: empty = the defaults for every member
+    void enable_detections(const std::vector<LiveTracker::DetectionOptions> &per_member = {});
+    std::vector<aar_tracker_result> push_detections(double frame_time, const std::vector<std::vector<LiveTracker::Detection>> &detections,
+                                                    const std::vector<const double *> &starts = {},
+                                                    std::vector<aar_tracker_start_info> *infos = nullptr);
+    LiveTracker::Window window(int member);
+    aar_tracker_uncertainty_record uncertainty(int member);
+    aar_tracker_bank_stats stats() const;
+    void reset();
+
+   private:
+    void pack(const std::vector<std::vector<LiveTracker::Detection>> &detections, const std::vector<const double *> &starts);
+    aar_tracker_bank *bank_ = nullptr;
+    std::vector<std::map<int, int>> cam_index_, marker_index_;
+    std::vector<int32_t> n_, cam_, marker_;
+    std::vector<float> uv_;
+    std::vector<double> start_;
+    std::vector<uint8_t> has_start_;
+    bool any_start_ = false;
+};
+
 }  // namespace aar

@@ -722,6 +722,55 @@ int aar_tracker_push_detections(aar_tracker *, double frame_time, int32_t n_det,
                                 aar_tracker_result *, aar_tracker_start_info *);
 void aar_tracker_destroy(aar_tracker *);
 
+/* Tracker bank: B independent live trackers -- one per object of a rig, each with its own solution, all with the same
+ * aar_tracker_params and aar_lm_params -- that advance in lockstep, one frame per call.  Member b is exactly an aar_tracker created from
+ * solutions[b]: same window, same LM, same anchor / covariance options, same start rules; nothing couples the members.  On the device member b is
+ * workgroup b of ONE launch, so a bank push is ONE host -> device copy (the ring is laid out [slot][member]: the slots a push fills are contiguous),
+ * ONE launch of B workgroups (TWO on a push of raw detections) and ONE device -> host copy, whatever B.  All memory is allocated by
+ * aar_tracker_bank_create (the detection workspaces by aar_tracker_bank_enable_detections), nothing per push.  Members may differ in their
+ * numbers of cameras and markers; max_obs_per_frame bounds every member's n_obs / n_det.
+ * A bank push is all or nothing: when any member's input is rejected (AAR_ERR_INVALID, the message names the member and the entry), the time does
+ * not ascend, or -- first push of raw detections -- a member has no finite candidate and nothing to fall back on (AAR_ERR_NUMERIC, the message
+ * names the member), every member stays exactly as it was. */
+#define AAR_TRACKER_BANK_MAX_MEMBERS 1024
+typedef struct aar_tracker_bank aar_tracker_bank;
+typedef struct aar_tracker_bank_stats {
+    uint32_t struct_size;
+    int32_t members;
+    int64_t pushes;              /* accepted */
+    int64_t launches;            /* kernel launches, counted on the host where they are issued (rejected pushes included) */
+    int64_t h2d_copies, h2d_bytes;
+    int64_t d2h_copies, d2h_bytes;
+} aar_tracker_bank_stats;
+/* Host function (no device needed): AAR_ERR_INVALID for n_members outside 1 .. AAR_TRACKER_BANK_MAX_MEMBERS, a null entry of solutions, or a
+ * member that aar_tracker_params_validate refuses (the message then starts with "member b: "). */
+int aar_tracker_bank_params_validate(int32_t n_members, const aar_dataset *const *solutions, const aar_tracker_params *);
+int aar_tracker_bank_create(int32_t n_members, const aar_dataset *const *solutions, const aar_tracker_params *,
+                            const aar_lm_params * /* NULL = defaults */, aar_tracker_bank **out);
+int32_t aar_tracker_bank_size(const aar_tracker_bank *);   /* B; 0 for NULL */
+/* n_obs: [B]; obs_cam / obs_marker / obs_uv: the members' frames one behind the other (member 0's n_obs[0] detections first), indices into the
+ * MEMBER's solution.  n_obs[b] = 0: object b was not seen -- the frame is bridged by the prior (smooth = 1) or keeps its start (smooth = 0), as
+ * in aar_tracker_push.  pose_init: [B][6] or NULL; has_init: [B], nonzero = member b's row of pose_init is given, NULL = every row is (when
+ * pose_init is not NULL).  The first push needs a start for every member.  results: [B] (every struct_size set) or NULL. */
+int aar_tracker_bank_push(aar_tracker_bank *, double frame_time, const int32_t *n_obs, const int32_t *obs_cam, const int32_t *obs_marker,
+                          const float *obs_uv, const double *pose_init, const uint8_t *has_init, aar_tracker_result *results);
+/* per_member: [B] or NULL, a NULL entry (or NULL array) = aar_tracker_default_detection_params for that member.  As
+ * aar_tracker_enable_detections: once after create or reset, before the first push. */
+int aar_tracker_bank_enable_detections(aar_tracker_bank *, const aar_tracker_detection_params *const *per_member);
+/* aar_tracker_push_detections for every member (n_det: [B], the arrays concatenated as above); infos: [B] or NULL.  On a first push in which
+ * some member has no pose_init the host waits for the start kernel before it launches the refinement, as the single tracker does. */
+int aar_tracker_bank_push_detections(aar_tracker_bank *, double frame_time, const int32_t *n_det, const int32_t *det_cam, const int32_t *det_marker,
+                                     const float *det_uv_raw, const double *pose_init, const uint8_t *has_init, aar_tracker_result *results,
+                                     aar_tracker_start_info *infos);
+/* aar_tracker_window / aar_tracker_uncertainty of one member */
+int aar_tracker_bank_window(aar_tracker_bank *, int32_t member, int32_t *n, int64_t *frame_index, double *poses, double *frame_err, double *pair_err,
+                            double anchor_pose[6], int32_t *has_anchor);
+int aar_tracker_bank_uncertainty(aar_tracker_bank *, int32_t member, aar_tracker_uncertainty_record *out);
+int aar_tracker_bank_reset(aar_tracker_bank *);   /* aar_tracker_reset for every member; the counters of aar_tracker_bank_get_stats stay */
+/* out->struct_size: the caller's sizeof; at most that many bytes are written and struct_size says how many were. */
+int aar_tracker_bank_get_stats(const aar_tracker_bank *, aar_tracker_bank_stats *out);
+void aar_tracker_bank_destroy(aar_tracker_bank *);
+
 /* per-stage device time of the last aar_lm_solve, seconds, in the reference's verbose-timer vocabulary
  * (libs/sparselevmarq.h:425) extended with the stages that only exist here */
 typedef struct aar_stage_times {
