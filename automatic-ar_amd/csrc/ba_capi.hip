@@ -1711,6 +1711,7 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     for (int c = 0; c < C; c++) ent_fixed[c] = (c == L.rc || !L.oc) ? 1 : 0;
     for (int m = 0; m < M; m++) ent_fixed[C + m] = (m == L.rm || !L.om) ? 1 : 0;
     for (int e = 0; e < C + M; e++) ent_fixed[e] |= held[e];
+    spcg_build_fixed_mask(P, ent_fixed.data());   // (k_spcg reads the same flags as bits in its arguments)
     // (intrinsics entities are free, root camera included: fill_io_vec_cam_intrinsics covers ALL cameras, libs/multicam_mapper.cpp:488-498;
     //  their two idle parameters have zero rows and columns and get mu on the diagonal, like the reference's five distortion columns)
     std::vector<double> Kh(d->cam_mats, d->cam_mats + 9 * (size_t)C);

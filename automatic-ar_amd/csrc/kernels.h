@@ -12,6 +12,9 @@ constexpr int PASSB_CHUNK = 1024;  // upper limit of AAR_PASSB_CHUNK (observatio
 // CG on the explicit reduced system (spcg_kernels.hip): iteration cap (sizes the hand-over buffers: one per iteration plus the
 // start-up and the final one), largest system (tiles of 96 unknowns: the six rows of an entity live in one wavefront's registers)
 constexpr int SPCG_MAX_IT = 128, SPCG_BUFS = SPCG_MAX_IT + 2, SPCG_MAX_NT = 14;
+constexpr int SPCG_MASK_WORDS = (16 * SPCG_MAX_NT + 63) / 64;   // 64-bit words of the fixed-entity mask in k_spcg's arguments (16 entities per tile)
+constexpr int SPCG_STAGE_MAX_NT = 5;  // k_spcg<NT, false> reads its rows of S in 16-byte pieces through the LDS (9 NT loads of 4 registers in flight per lane) up to this many tiles: at six the kernel starts to spill scalar registers
+constexpr int SPCG_RIDE_MAX_NT = 8;   // the back-substitution rides only while all CG wavefronts share one XCD (spcg_spread 8): at most 128 entities
 // default cap by system size: up to four tiles the direct chain (<= 120 us) is cheaper than a CG solve of more than ~64 iterations; larger systems' chains cost 200-500 us
 inline int spcg_default_cap(int nT) { return nT <= 4 ? 64 : SPCG_MAX_IT; }
 // Default forcing terms of the inexact solvers (include/aar.h: aar_solver_options.pcg_eta; DESIGN.md section 12, profiles/r05_eta_pose_sweep.txt).  Chosen for the
@@ -140,6 +143,7 @@ struct DeviceProblem {
     double *spcg_pre = nullptr;           // workspace of k_spcg_pre (spcg_pre_doubles): augmented rows | right-hand side | inverse blocks | Z | (A Z)^T | shares | counter
     mutable int spcg_pre_epoch = 0;       // launches of k_spcg_pre (its arrival counter is monotonic)
     int spcg_root_c = -1, spcg_root_m = -1, spcg_n_free = 0;   // the fixed entity of each group whose slot carries the group's rigid-motion unknowns (-1: none); free entities
+    unsigned long long spcg_fixed[SPCG_MASK_WORDS] = {~0ull, ~0ull, ~0ull, ~0ull};   // ent_fixed and the padding entities as bits (spcg_build_fixed_mask: whenever ent_fixed is set)
     int spcg_test_drop = -1;              // test hook (AAR_SPCG_TEST_DROP=entity): that entity's wavefront never shows up -> every hand-over times out -> flag 4 -> direct chain
     double *spcg_ws = nullptr;            // [2][SPCG_BUFS][spcg_stride(n_pad)] hand-over slots (sentinel-filled when idle)
     int32_t *spcg_iters = nullptr;        // [0] iterations of the last solve, [1] running total, [2] solves, [3] solves that hit the cap (flag 8)
@@ -262,6 +266,7 @@ int pcg_max_grid(int A, bool coarse, int cus);   // largest co-resident grid of 
 bool launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial = -1);   // trial >= 0: launch_backsub(which, trial) may ride (true: it did)
 int spcg_resident_per_cu(int nT, bool coarse);             // occupancy query: wavefronts of k_spcg<nT> one CU holds (0: unknown)
 inline bool spcg_coarse_now(const DeviceProblem &P) { return P.spcg_coarse && (P.spcg_root_c >= 0 || P.spcg_root_m >= 0); }   // this problem's k_spcg can carry the coarse space
+void spcg_build_fixed_mask(DeviceProblem &P, const int32_t *ent_fixed_host);   // P.spcg_fixed from the host's copy of ent_fixed [P.n / 6]
 bool spcg_fits(int nT);                                    // the system's rows fit the wavefronts' registers
 size_t spcg_ws_doubles(int n_pad);
 size_t spcg_pre_doubles(int n_pad);

@@ -29,6 +29,20 @@
 // each side.  Measured (scripts/probe/spcg_probe.hip, cycle stamps): an iteration is ~3 300 shader cycles -- publish 300, the poll's round trip 960 (260 per
 // 16-byte load instruction: the number of records matters, not their placement), the sums over the gathered shares 720, the matrix-vector product 750, scalars
 // and recurrences 560 -- and every piece of straight-line set-up code costs about one cycle per byte of instructions (the instruction cache is cold at every launch).
+//
+// Start-up.  Because once-run code costs its size, the default kernel is kept small and makes no avoidable round trip (profiles/spcg_startup.txt):
+//  * the back-substitution riders (AAR_SPCG_BACKSUB_RIDES=1, an experiment that lost) live in an instantiation of their own, k_spcg<NT, CO, true>, with their own
+//    arguments (SpcgRideArgs): the default k_spcg<NT, CO, false> carries neither backsub_body's 12.5 KB nor BacksubArgs;
+//  * which entities have identity rows arrives as bit words in the kernel arguments (SpcgArgs::fixed_mask), so the early exit, the reporting wavefront, the poll mask
+//    and the zeroed columns are scalar work and the loads of S / the assembled rows are the first memory operations a wavefront issues; the clearing of the other
+//    buffer set, whose bound is a load (iters[0]), comes behind them;
+//  * k_spcg<NT, false> up to SPCG_STAGE_MAX_NT tiles reads its rows in 16-byte pieces -- row part and column part of the lower triangle, both contiguous -- and
+//    turns them into the register layout through its own LDS; the diagonal block comes out of the same pieces.  Above that (and in the riding instantiations'
+//    larger shapes) the element-wise symmetric reads stay, with the row stride a compile-time constant (n_pad = 96 NT: the 64-bit address arithmetic was what
+//    made the large instantiations spill);
+// (One copy of publish / gather / product for the start-up pass and the iterations was built too: the compiler then contracts the loop's products differently
+// and the bits change, so the start-up pass keeps its own copy.)  None of this touches the arithmetic: a solve returns the same bits for the same S (tests/test_gpu_spcg_startup.py, against the build before).
+#include <type_traits>
 #include "geom.hpp"
 #include "kernels.h"
 #include "backsub.hpp"
@@ -57,15 +71,25 @@ __device__ unsigned long long g_sp_stamps[512];
 __device__ int g_sp_polls[80];
 #define SP_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (e == e0 && lane == 0 && (k) < 512) g_sp_stamps[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define SP_VAL(k, v) do { if (e == e0 && lane == 0 && (k) < 512) g_sp_stamps[k] = (unsigned long long)__double_as_longlong(v); } while (0)
+// set-up stamps 440 ..: kernel entry (taken before e0 is known, written once it is) | long loads issued | loads back (the diagnostic build drains the memory queue there)
+#define SP_ENTRY() unsigned long long sp_t_entry; do { __builtin_amdgcn_sched_barrier(0); sp_t_entry = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define SP_ENTRY_PUT(k) do { if (e == e0 && lane == 0) g_sp_stamps[k] = sp_t_entry; } while (0)
+#define SP_DRAIN() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
 #else
 #define SP_STAMP(k) do { } while (0)
 #define SP_VAL(k, v) do { } while (0)
+#define SP_ENTRY() do { } while (0)
+#define SP_ENTRY_PUT(k) do { } while (0)
+#define SP_DRAIN() do { } while (0)
 #endif
 
 struct SpcgArgs {
     const double *S, *rhs, *g0;       // lower triangle of the Schur complement (no damping), Schur part of the rhs, shared gradient
-    const int32_t *ent_fixed;
-    int n, n_pad;
+    // bit ent: entity ent has identity rows -- a gauge / switched-off / held entity (DeviceProblem::spcg_fixed, built with ent_fixed) or padding behind the last one;
+    // a launch that carries the coarse space has the two roots' bits cleared.  In the kernel arguments, so that whoever asks reads a scalar: no load stands
+    // between the kernel's entry and its loads of S
+    unsigned long long fixed_mask[SPCG_MASK_WORDS];
+    int n_pad;
     double mu, eta2;
     double abs2_mu;                   // eps^2 mu: the ABSOLUTE stopping threshold on r^T M^-1 r (along a weakly determined direction M ~ mu, so |A^-1 r|^2 ~ r^T M^-1 r / mu <= eps^2)
     int max_it;
@@ -76,12 +100,6 @@ struct SpcgArgs {
     int32_t *iters;                   // [0] iterations of this solve, [1] running total, [2] solves, [3] solves that gave up (flag 8), [4] solves whose wavefronts all shared one XCD
     int32_t *flags;
     int spread;                       // 8: every eighth workgroup works (one XCD under round-robin placement); 1: every workgroup
-    // riders: the workgroups of the grid that are NOT CG wavefronts do the frame back-substitution of the try (backsub.hpp) -- they fetch what does not depend
-    // on delta_s (the frame's W blocks, g_f, V_f^-1) while the CG runs on the other XCD and wait for ONE flag, raised by the last CG wavefront to leave
-    int ride, n_ent_total, n_riders;
-    BacksubArgs bs;
-    int32_t *done;                    // [0] arrivals (monotonic over launches), [1] flag = done_epoch once all n_ent_total CG workgroups of this launch have left
-    int done_epoch;
     int test_drop;                    // test hook (AAR_SPCG_TEST_DROP): the wavefront of this entity leaves without a word, as if it had never been scheduled
     // CO kernels (two-level preconditioner through the AUGMENTED system, see k_spcg_pre): everything a wavefront keeps comes assembled from k_spcg_pre --
     // rows of the augmented matrix [n_pad][n_pad] (damping in, columns of fixed entities zero, the groups' roots turned into the coarse unknowns), right-hand side
@@ -90,57 +108,82 @@ struct SpcgArgs {
     int root_c, root_m;               // the fixed entity whose slot carries the cameras' / markers' rigid-motion unknowns (-1: that group has none)
     int C, M;
 };
+// what the RIDING instantiation k_spcg<NT, CO, true> gets on top (AAR_SPCG_BACKSUB_RIDES=1, an experiment that measured slower: profiles/r05_attempts.txt section 8).
+// Riders: the workgroups of the grid that are NOT CG wavefronts do the frame back-substitution of the try (backsub.hpp) -- they fetch what does not depend
+// on delta_s (the frame's W blocks, g_f, V_f^-1) while the CG runs on the other XCD and wait for ONE flag, raised by the last CG wavefront to leave.
+// The default instantiation carries neither these arguments nor backsub_body's code.
+struct SpcgRideArgs : SpcgArgs {
+    int n_riders;
+    BacksubArgs bs;
+    int32_t *done;                    // [0] arrivals (monotonic over launches), [1] flag = done_epoch once all CG workgroups of this launch have left
+    int done_epoch;
+};
 
 typedef unsigned int sp_u32x4 __attribute__((ext_vector_type(4)));
 
-template <int NT, bool CO>
-__global__ void __launch_bounds__(64) k_spcg(const SpcgArgs a) {
+template <int NT, bool CO, bool RIDE>
+__global__ void __launch_bounds__(64) k_spcg(const std::conditional_t<RIDE, SpcgRideArgs, SpcgArgs> a) {
     // NL: 16-byte pieces of a buffer per lane (a buffer = 16 NT records of 64 bytes = 64 NT pieces); piece c = lane + 64 k belongs to record
     // c / 4 and holds its words 2 (lane % 4), 2 (lane % 4) + 1: lanes with lane % 4 < 3 gather entries of m, lanes with lane % 4 == 3 the two shares
     constexpr int NPAD = 96 * NT, NK = 6 * NT, NENT = 16 * NT, NL = NT, NEB = (NENT + 63) / 64;
-    __shared__ __align__(16) double mv[NPAD];
+    // STAGED (block-Jacobi, up to SPCG_STAGE_MAX_NT tiles): the set-up reads S in 16-byte pieces and turns them into the register layout through this wavefront's
+    // own LDS, [6][NPAD] doubles; the CG's vector mv takes the front of the same array once the rows are in registers
+    constexpr bool STAGED = !CO && NT <= SPCG_STAGE_MAX_NT;
+    __shared__ __align__(16) double lds[STAGED ? 6 * NPAD : NPAD];
+    double *const mv = lds;
     // Placement.  Workgroups are dealt round-robin over the 8 XCDs (observed, not promised): with a.spread == 8 only every eighth workgroup works, so
     // that all wavefronts of the solve share ONE XCD and its L2.  Whether they really do is checked at run time (every wavefront publishes its
     // XCC id in the first, placement-independent hand-over): if so, the later hand-overs keep their records in that L2 (sc0 stores; the sc1 loads
     // are L2-served) instead of sending every store out to the fabric and every poll after it -- a hand-over then costs an L2 round trip, not a memory one.
-    if (blockIdx.x % a.spread || (int)blockIdx.x >= a.n_ent_total * a.spread) {
-        if (!a.ride || blockIdx.x % 8 == 0) return;   // (position 0 mod 8 behind the CG range: the CG's XCD -- left alone)
-        __shared__ double red[32];
-        const int bx = (int)blockIdx.x, cg_range = a.n_ent_total * a.spread;
-        const int rid = bx < cg_range ? bx - bx / a.spread - 1 : a.n_ent_total * (a.spread - 1) + (bx - cg_range) - (bx - cg_range + 7) / 8;
-        for (int blk = rid; blk <= a.bs.n_frame_blocks; blk += a.n_riders) backsub_body(a.bs, blk, red, a.done + 1, a.done_epoch, a.flags);
+    if (blockIdx.x % a.spread || (int)blockIdx.x >= NENT * a.spread) {
+        if constexpr (RIDE) {
+            if (blockIdx.x % 8 == 0) return;   // (position 0 mod 8 behind the CG range: the CG's XCD -- left alone)
+            __shared__ double red[32];
+            const int bx = (int)blockIdx.x, cg_range = NENT * a.spread;
+            const int rid = bx < cg_range ? bx - bx / a.spread - 1 : NENT * (a.spread - 1) + (bx - cg_range) - (bx - cg_range + 7) / 8;
+            for (int blk = rid; blk <= a.bs.n_frame_blocks; blk += a.n_riders) backsub_body(a.bs, blk, red, a.done + 1, a.done_epoch, a.flags);
+        }
         return;
     }
     const int lane = threadIdx.x, e = blockIdx.x / a.spread, i = lane >> 3, g = lane & 7;
+    SP_ENTRY();
     auto leave = [&]() {   // this workgroup's entries of delta_s are on their way (agent-scope stores): drain them, arrive; the last one raises the riders' flag
-        if (!a.ride) return;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) {
-            const int old = __hip_atomic_fetch_add(a.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old + 1 == a.done_epoch * a.n_ent_total) __hip_atomic_store(a.done + 1, a.done_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (RIDE) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (lane == 0) {
+                const int old = __hip_atomic_fetch_add(a.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (old + 1 == a.done_epoch * NENT) __hip_atomic_store(a.done + 1, a.done_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     };
-    const int n_free_ent = a.n / 6;   // entities beyond are padding: identity rows
-    // (CO: a group's root carries the group's coarse unknowns -- its wavefront works, its record is read like any other)
-    auto fixed = [&](int ent) -> bool { return ent >= n_free_ent || (a.ent_fixed[ent < n_free_ent ? ent : 0] != 0 && !(CO && (ent == a.root_c || ent == a.root_m))); };
+    // identity rows: gauge / switched-off / held / padding entities (CO: a group's root carries the group's coarse unknowns -- its wavefront works, its record
+    // is read like any other: the launcher has cleared its bit).  The word is picked by selects, never by an index: the mask stays in scalar registers
+    auto fixed = [&](int ent) -> bool {
+        unsigned long long w = a.fixed_mask[0];
+#pragma unroll
+        for (int q = 1; q < NEB; q++) w = (ent >> 6) == q ? a.fixed_mask[q] : w;
+        return ((w >> (ent & 63)) & 1ull) != 0ull;
+    };
     double *set = a.ws + (size_t)a.parity * a.set_len, *other = a.ws + (size_t)(1 - a.parity) * a.set_len;
-    const int nprev_raw = a.iters[0];
-    {   // the record this wavefront owns in the other set's buffers, for the launch after this one (the previous launch dirtied iters[0] + 2 of them): 8 buffers per store.
-        // Wavefronts of fixed entities do it too: a root's record is written by the launches that carry the coarse space and must read as idle to the others
+    const int nprev_raw = a.iters[0];   // (asked for here, needed only behind the long loads)
+    // the record this wavefront owns in the other set's buffers, for the launch after this one (the previous launch dirtied iters[0] + 2 of them): 8 buffers per store.
+    // Wavefronts of fixed entities do it too: a root's record is written by the launches that carry the coarse space and must read as idle to the others
+    auto clear_other = [&]() {
         const int nprev = min(nprev_raw + 2, SPCG_BUFS);
         for (int bq = lane >> 3; bq < nprev; bq += 8) sp_st(other + (size_t)bq * a.stride + 8 * e + (lane & 7), __longlong_as_double((long long)SPCG_EMPTY));
-    }
-    if (fixed(e)) {   // gauge / switched-off / padding entity: identity rows, zero right-hand side; nobody waits for this wavefront
+    };
+    if (fixed(e)) {   // identity rows, zero right-hand side; nobody waits for this wavefront
+        clear_other();
         if (lane < 6) sp_st(a.x_out + 6 * e + lane, 0.0);
         leave();
         return;
     }
-    if (e == a.test_drop) return;
-    // ---- every load of the set-up is issued before the first is used: one memory latency, not one per stage ----
+    if (e == a.test_drop) { clear_other(); return; }
+    // ---- every load of the set-up is issued before the first is used, and nothing is waited for before they are: one memory latency, not one per stage ----
     int e0 = -1, n_act = 0;    // the first free entity (its wavefront reports), the number of free entities
 #pragma unroll
     for (int k = 0; k < NEB; k++) {
-        const unsigned long long fr = __ballot(lane + 64 * k < NENT && !fixed(lane + 64 * k));
+        const unsigned long long fr = ~a.fixed_mask[k] & (NENT - 64 * k >= 64 ? ~0ull : (1ull << ((NENT - 64 * k) & 63)) - 1ull);
         if (e0 < 0 && fr) e0 = 64 * k + __builtin_ctzll(fr);
         n_act += __builtin_popcountll(fr);
     }
@@ -174,21 +217,83 @@ __global__ void __launch_bounds__(64) k_spcg(const SpcgArgs a) {
             const bool zon = ra && !pseudo && my_root >= 0;
             zo[2 * k] = zon ? z2.x : 0.0; zo[2 * k + 1] = zon ? z2.y : 0.0;
         }
-        r = (ra && !pseudo) ? a.rhs[row] + a.g0[row] : 0.0;
+        const double r_b = a.rhs[row], r_g = a.g0[row];
+        clear_other();
+        SP_ENTRY_PUT(440); SP_STAMP(441); SP_DRAIN(); SP_STAMP(442);
+        r = (ra && !pseudo) ? r_b + r_g : 0.0;
     } else {
-        unsigned long long cfx[(NK + 63) / 64] = {};   // bit k: column pair k belongs to a gauge / padding entity
+        unsigned long long cfx[(NK + 63) / 64] = {};   // bit k: column pair k belongs to an entity with identity rows (a pair never straddles two entities)
 #pragma unroll
-        for (int k = 0; k < NK; k++) {
-            const int c0 = 16 * k + 2 * g, c1 = c0 + 1;
-            A2[2 * k] = a.S[(c0 <= row) ? (size_t)row * a.n_pad + c0 : (size_t)c0 * a.n_pad + row];
-            A2[2 * k + 1] = a.S[(c1 <= row) ? (size_t)row * a.n_pad + c1 : (size_t)c1 * a.n_pad + row];
-            if (fixed(c0 / 6)) cfx[k >> 6] |= 1ull << (k & 63);
+        for (int k = 0; k < NK; k++) if (fixed((16 * k + 2 * g) / 6)) cfx[k >> 6] |= 1ull << (k & 63);
+        double r_b, r_g;
+        if constexpr (STAGED) {
+            // The wavefront's six rows of the symmetric matrix lie in the lower triangle as two contiguous shapes: the ROW part -- its own rows 6e .. 6e+5 up to
+            // and including the diagonal block, inside the contiguous [6][NPAD] slab of those rows -- and the COLUMN part -- the 48 bytes S[r][6e .. 6e+5] of every
+            // row r below.  Both are read in 16-byte pieces, piece = lane + 64 j, every load in flight before the first is used (9 NT loads a lane, against
+            // 12 NT + 21 loads of 8 bytes element by element); the column part is transposed on its way into the LDS
+            constexpr int NRP = (3 * NPAD + 63) / 64, NCP = (3 * (NPAD - 6) + 63) / 64;
+            const double2 *slab = reinterpret_cast<const double2 *>(a.S + (size_t)6 * e * NPAD);
+            const double2 *below = reinterpret_cast<const double2 *>(a.S + (size_t)(6 * e + 6) * NPAD + 6 * e);
+            const int wcol = 3 * e + 3;       // pieces of a row up to the end of the diagonal block
+            double2 rp[NRP], cp[NCP];
+#pragma unroll
+            for (int j = 0; j < NRP; j++) {
+                const int c = lane + 64 * j;
+                rp[j] = (c < 3 * NPAD && c % (NPAD / 2) < wcol) ? slab[c] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int j = 0; j < NCP; j++) {
+                const int c = lane + 64 * j, rr = c / 3, t = c - 3 * rr;
+                cp[j] = (6 * e + 6 + rr < NPAD) ? below[(size_t)rr * (NPAD / 2) + t] : make_double2(0.0, 0.0);
+            }
+            r_b = a.rhs[row]; r_g = a.g0[row];
+            clear_other();
+            SP_ENTRY_PUT(440); SP_STAMP(441); SP_DRAIN(); SP_STAMP(442);
+#pragma unroll
+            for (int j = 0; j < NRP; j++) {
+                const int c = lane + 64 * j;
+                if (c < 3 * NPAD && c % (NPAD / 2) < wcol) reinterpret_cast<double2 *>(lds)[c] = rp[j];
+            }
+#pragma unroll
+            for (int j = 0; j < NCP; j++) {
+                const int c = lane + 64 * j, rr = c / 3, t = c - 3 * rr, rw = 6 * e + 6 + rr;
+                if (rw < NPAD) { lds[(2 * t) * NPAD + rw] = cp[j].x; lds[(2 * t + 1) * NPAD + rw] = cp[j].y; }
+            }
+            __builtin_amdgcn_wave_barrier();   // (one wavefront, LDS operations complete in order)
+            {   // the diagonal block's upper triangle is its lower one, transposed
+                const int p = lane / 6, q = lane - 6 * p;
+                const bool up = lane < 36 && q > p;
+                const double v = up ? lds[q * NPAD + 6 * e + p] : 0.0;
+                __builtin_amdgcn_wave_barrier();
+                if (up) lds[p * NPAD + 6 * e + q] = v;
+                __builtin_amdgcn_wave_barrier();
+            }
+#pragma unroll
+            for (int k = 0; k < NK; k++) {
+                const double2 t = reinterpret_cast<const double2 *>(lds + (ra ? i : 0) * NPAD)[8 * k + g];
+                A2[2 * k] = t.x; A2[2 * k + 1] = t.y;
+            }
+#pragma unroll
+            for (int p = 0; p < 6; p++)
+#pragma unroll
+                for (int q = 0; q <= p; q++) blk[p][q] = lds[p * NPAD + 6 * e + q];
+            __builtin_amdgcn_wave_barrier();   // (mv, the front of the same array, is written by the first gather: program order is enough)
+        } else {
+#pragma unroll
+            for (int k = 0; k < NK; k++) {
+                const int c0 = 16 * k + 2 * g, c1 = c0 + 1;
+                A2[2 * k] = a.S[(c0 <= row) ? row * NPAD + c0 : c0 * NPAD + row];
+                A2[2 * k + 1] = a.S[(c1 <= row) ? row * NPAD + c1 : c1 * NPAD + row];
+            }
+#pragma unroll
+            for (int p = 0; p < 6; p++)
+#pragma unroll
+                for (int q = 0; q <= p; q++) blk[p][q] = a.S[(6 * e + p) * NPAD + 6 * e + q];
+            r_b = a.rhs[row]; r_g = a.g0[row];
+            clear_other();
+            SP_ENTRY_PUT(440); SP_STAMP(441); SP_DRAIN(); SP_STAMP(442);
         }
-#pragma unroll
-        for (int p = 0; p < 6; p++)
-#pragma unroll
-            for (int q = 0; q <= p; q++) blk[p][q] = a.S[(size_t)(6 * e + p) * a.n_pad + 6 * e + q];
-        r = a.rhs[row] + a.g0[row];
+        r = r_b + r_g;
 #pragma unroll
         for (int k = 0; k < NK; k++) {
             const int c0 = 16 * k + 2 * g;
@@ -270,6 +375,7 @@ __global__ void __launch_bounds__(64) k_spcg(const SpcgArgs a) {
         r = ra ? mv[72 + i] : 0.0;
         __builtin_amdgcn_wave_barrier();
     }
+    SP_STAMP(443);
     auto prec = [&](double w) -> double {   // (M^-1 w)_i from the six entries of w in this wavefront
         double s = 0.0;
 #pragma unroll
@@ -624,8 +730,8 @@ int spcg_resident_per_cu(int nT, bool coarse) {
     int nb = 0;
     hipError_t rc = hipErrorInvalidValue;
     switch (nT) {
-#define SPCG_CASE(t) case t: { int nc = 1 << 30; if (coarse) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_spcg<t, true>, 64, 0); \
-                               if (!coarse || rc == hipSuccess) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_spcg<t, false>, 64, 0); nb = std::min(nb, nc); } break;
+#define SPCG_CASE(t) case t: { int nc = 1 << 30; if (coarse) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_spcg<t, true, false>, 64, 0); \
+                               if (!coarse || rc == hipSuccess) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_spcg<t, false, false>, 64, 0); nb = std::min(nb, nc); } break;
         SPCG_CASE(1) SPCG_CASE(2) SPCG_CASE(3) SPCG_CASE(4) SPCG_CASE(5) SPCG_CASE(6) SPCG_CASE(7) SPCG_CASE(8)
         SPCG_CASE(9) SPCG_CASE(10) SPCG_CASE(11) SPCG_CASE(12) SPCG_CASE(13) SPCG_CASE(14)
 #undef SPCG_CASE
@@ -646,40 +752,61 @@ void spcg_ws_reset(const DeviceProblem &P, hipStream_t st) {
 bool launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial) {
     const DeviceProblem::Blocks &b = P.blk[which];
     SpcgArgs a;
-    a.S = b.S; a.rhs = b.rhs; a.g0 = b.g0; a.ent_fixed = P.ent_fixed; a.n = P.n; a.n_pad = P.n_pad;
+    a.S = b.S; a.rhs = b.rhs; a.g0 = b.g0; a.n_pad = P.n_pad;
+    for (int q = 0; q < SPCG_MASK_WORDS; q++) a.fixed_mask[q] = P.spcg_fixed[q];
     a.mu = mu; a.eta2 = P.pcg_eta_now * P.pcg_eta_now; a.abs2_mu = P.pcg_abs_tol * P.pcg_abs_tol * mu; a.max_it = std::min(P.spcg_max_it, SPCG_MAX_IT);
     a.ws = P.spcg_ws; a.stride = spcg_stride(P.n_pad); a.set_len = (long long)SPCG_BUFS * a.stride; a.parity = P.spcg_parity;
     a.x_out = P.delta_s; a.iters = P.spcg_iters; a.flags = P.flags; a.test_drop = P.spcg_test_drop;
     a.pre_rows = a.pre_minv = a.pre_z = a.pre_azt = a.pre_share = nullptr; a.root_c = a.root_m = -1; a.C = P.C; a.M = P.M;
     const bool coarse = spcg_coarse_now(P) && P.spcg_coarse_on;   // this solve carries the coarse space: k_spcg_pre assembles the augmented system first
-    if (coarse) launch_spcg_pre(P, which, mu, st, a);
+    if (coarse) {   // the roots' wavefronts work: they carry their groups' coarse unknowns
+        launch_spcg_pre(P, which, mu, st, a);
+        for (int root : {a.root_c, a.root_m})
+            if (root >= 0) a.fixed_mask[root >> 6] &= ~(1ull << (root & 63));
+    }
     a.spread = P.spcg_spread;
     P.spcg_parity ^= 1;
     const int n_ent = P.n_pad / 6;
-    a.n_ent_total = n_ent;
-    // riders: only where the CG leaves seven XCDs idle anyway, and not when somebody wants the back-substitution's own time
-    a.ride = (trial >= 0 && P.tune.spcg_backsub_rides && a.spread >= 8 && !P.hook.pre && P.F > 0) ? 1 : 0;
-    a.bs = backsub_args(P, which, trial >= 0 ? trial : which, 1);
-    a.done = P.spcg_done; a.done_epoch = 0; a.n_riders = 0;
-    int grid = n_ent * a.spread;
-    if (a.ride) {
-        a.done_epoch = ++P.spcg_epoch;
-        const int base = n_ent * (a.spread - 1), want = std::min(a.bs.n_frame_blocks + 1, 4096);
+    const int grid = n_ent * a.spread;
+    // riders: only where the CG leaves seven XCDs idle anyway (which takes a system of at most SPCG_RIDE_MAX_NT tiles), and not when somebody wants the
+    // back-substitution's own time
+    const bool ride = trial >= 0 && P.tune.spcg_backsub_rides && a.spread >= 8 && P.nT <= SPCG_RIDE_MAX_NT && !P.hook.pre && P.F > 0;
+    HookScope _h(P, KID_SPCG);
+    if (ride) {
+        SpcgRideArgs ar;
+        static_cast<SpcgArgs &>(ar) = a;
+        ar.bs = backsub_args(P, which, trial, 1);
+        ar.done = P.spcg_done; ar.done_epoch = ++P.spcg_epoch;
+        const int base = n_ent * (a.spread - 1), want = std::min(ar.bs.n_frame_blocks + 1, 4096);
         int extra = 0;
         if (base < want) extra = ((want - base) * 8 + 6) / 7;            // (every eighth block behind the CG range sits on the CG's XCD and is left alone)
-        grid += extra;
-        a.n_riders = base + extra - (extra + 7) / 8;
+        ar.n_riders = base + extra - (extra + 7) / 8;
+        switch (P.nT) {
+#define SPCG_CASE(t) case t: if (coarse) hipLaunchKernelGGL((k_spcg<t, true, true>), dim3(grid + extra), dim3(64), 0, st, ar); \
+                             else hipLaunchKernelGGL((k_spcg<t, false, true>), dim3(grid + extra), dim3(64), 0, st, ar); break;
+            SPCG_CASE(1) SPCG_CASE(2) SPCG_CASE(3) SPCG_CASE(4) SPCG_CASE(5) SPCG_CASE(6) SPCG_CASE(7) SPCG_CASE(8)
+#undef SPCG_CASE
+            default: break;
+        }
+        static_assert(SPCG_RIDE_MAX_NT == 8, "one riding instantiation per tile count that can ride");
+        return true;
     }
-    HookScope _h(P, KID_SPCG);
     switch (P.nT) {
-#define SPCG_CASE(t) case t: if (coarse) hipLaunchKernelGGL((k_spcg<t, true>), dim3(grid), dim3(64), 0, st, a); \
-                             else hipLaunchKernelGGL((k_spcg<t, false>), dim3(grid), dim3(64), 0, st, a); break;
+#define SPCG_CASE(t) case t: if (coarse) hipLaunchKernelGGL((k_spcg<t, true, false>), dim3(grid), dim3(64), 0, st, a); \
+                             else hipLaunchKernelGGL((k_spcg<t, false, false>), dim3(grid), dim3(64), 0, st, a); break;
         SPCG_CASE(1) SPCG_CASE(2) SPCG_CASE(3) SPCG_CASE(4) SPCG_CASE(5) SPCG_CASE(6) SPCG_CASE(7) SPCG_CASE(8)
         SPCG_CASE(9) SPCG_CASE(10) SPCG_CASE(11) SPCG_CASE(12) SPCG_CASE(13) SPCG_CASE(14)
 #undef SPCG_CASE
         default: break;   // (spcg_fits() is checked when the solver is chosen)
     }
-    return a.ride != 0;
+    return false;
+}
+
+void spcg_build_fixed_mask(DeviceProblem &P, const int32_t *ent_fixed_host) {
+    const int n_free_ent = P.n / 6;   // entities beyond are padding: identity rows
+    for (int q = 0; q < SPCG_MASK_WORDS; q++) P.spcg_fixed[q] = 0ull;
+    for (int ent = 0; ent < 64 * SPCG_MASK_WORDS; ent++)
+        if (ent >= n_free_ent || ent_fixed_host[ent] != 0) P.spcg_fixed[ent >> 6] |= 1ull << (ent & 63);
 }
 
 }  // namespace aar

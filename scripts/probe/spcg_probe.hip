@@ -8,7 +8,7 @@
 #include <vector>
 #include <random>
 using namespace aar;
-namespace aar { volatile int g_last_kernel_id = 0; BacksubArgs backsub_args(const DeviceProblem &, int, int, int) { return BacksubArgs(); } }   // (the probe launches no riders; the real one lives in solve_kernels.hip)
+namespace aar { volatile int g_last_kernel_id = 0; void raise_dynamic_lds(const void *k, size_t bytes) { if (bytes > 48 * 1024) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); } BacksubArgs backsub_args(const DeviceProblem &, int, int, int) { return BacksubArgs(); } }   // (the probe launches no riders; the real one lives in solve_kernels.hip)
 int main(int argc, char **argv) {
     const int nT = argc > 1 ? atoi(argv[1]) : 3;
     const double eta = argc > 2 ? atof(argv[2]) : 1e-6;
@@ -33,6 +33,7 @@ int main(int argc, char **argv) {
     }
     std::vector<int32_t> fx(A, 0); fx[0] = 1; fx[8 < A ? 8 : A - 1] = 1;   // two gauge entities, as in a bundle problem
     (void)hipMemcpy(P.ent_fixed, fx.data(), 4 * A, hipMemcpyHostToDevice);
+    spcg_build_fixed_mask(P, fx.data());
     std::vector<double> b(n, 1.0);
     (void)hipMemcpy(P.blk[0].S, S.data(), 8*(size_t)n*n, hipMemcpyHostToDevice);
     (void)hipMemcpy(P.blk[0].g0, b.data(), 8*n, hipMemcpyHostToDevice);
@@ -50,6 +51,8 @@ int main(int argc, char **argv) {
         (void)hipMemcpy(it, P.spcg_iters, 16, hipMemcpyDeviceToHost);
         printf("rep %d: k_spcg_pre + k_spcg %.1f us (events), %d iterations; shader cycles: slab %llu | inverse + prec(r) %llu | publish0 %llu | gather0 %llu | pass0 %llu | total %llu\n", rep, ms*1e3, it[0],
                st[1]-st[0], st[2]-st[1], st[3]-st[2], st[4]-st[3], st[6]-st[4], st[5]-st[0]);
+        printf("        set-up from kernel entry: long loads issued %llu | loads back %llu | rows ready %llu | inverse done %llu | prec(r) %llu | first publish %llu | first gather %llu | first matrix-vector product %llu\n",
+               st[441]-st[440], st[442]-st[440], st[1]-st[440], st[443]-st[440], st[2]-st[440], st[3]-st[440], st[4]-st[440], st[6]-st[440]);
         if (rep == 3) for (int k = 0; k < it[0] && k < 24; k++)
             printf("   it %2d: prec+shares+publish %llu | poll %llu | gather %llu (re-polls %d) | matvec %llu | scalars+updates %llu\n", k, st[9+4*k]-st[8+4*k], st[300+k+1]-st[9+4*k], st[10+4*k]-st[9+4*k], polls[k+1],
                    st[11+4*k]-st[10+4*k], (k + 1 < it[0] ? st[8+4*(k+1)] : st[11+4*k]) - st[11+4*k]);
