@@ -38,6 +38,7 @@ SYMBOLS = [
     "aar_problem_covariance", "aar_covariance_write_yaml",
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
+    "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
@@ -142,11 +143,22 @@ class CConstraints(C.Structure):
                 ("n_priors", C.c_int32), ("priors", C.POINTER(CPosePrior))]
 
 
+class CPairPrior(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index_a", C.c_int32), ("index_b", C.c_int32), ("x6_rel", C.c_double * 6), ("info", C.c_double * 36)]
+
+
+class CConstraintsV2(C.Structure):
+    """aar_problem_constraints with the fields appended for the pair priors (CConstraints is the struct as it was before them: the
+    library takes either, by struct_size)"""
+    _fields_ = CConstraints._fields_ + [("n_pair_priors", C.c_int32), ("pair_priors", C.POINTER(CPairPrior))]
+
+
 class Constraints:
     """aar_problem_constraints built from Python values (kept alive with the struct).  fixed_cams / fixed_markers: indices; priors: a list of
-    (kind, index, x6, info) with kind "camera" | "marker" (or PRIOR_CAMERA / PRIOR_MARKER), x6 the 6-vector (rvec, t), info the 6x6 information matrix."""
+    (kind, index, x6, info) with kind "camera" | "marker" (or PRIOR_CAMERA / PRIOR_MARKER), x6 the 6-vector (rvec, t), info the 6x6 information matrix;
+    pair_priors: a list of (kind, index_a, index_b, x6_rel, info), x6_rel the (rvec, t) of T_a^-1 T_b (relative_pose)."""
 
-    def __init__(self, fixed_cams=None, fixed_markers=None, priors=None):
+    def __init__(self, fixed_cams=None, fixed_markers=None, priors=None, pair_priors=None):
         self._fc = np.ascontiguousarray(list(fixed_cams or []), dtype=np.int32)
         self._fm = np.ascontiguousarray(list(fixed_markers or []), dtype=np.int32)
         pr = list(priors or [])
@@ -161,8 +173,23 @@ class Constraints:
                 q.x6[k] = float(x6[k])
             for k in range(36):
                 q.info[k] = float(info[k])
-        c = CConstraints()
-        c.struct_size = C.sizeof(CConstraints)
+        pp = list(pair_priors or [])
+        self._pp = (CPairPrior * max(len(pp), 1))()
+        for i, (kind, ia, ib, x6, info) in enumerate(pp):
+            q = self._pp[i]
+            q.kind = PRIOR_KINDS[kind] if isinstance(kind, str) else int(kind)
+            q.index_a, q.index_b = int(ia), int(ib)
+            x6 = np.asarray(x6, dtype=np.float64).reshape(6)
+            info = np.asarray(info, dtype=np.float64).reshape(36)
+            for k in range(6):
+                q.x6_rel[k] = float(x6[k])
+            for k in range(36):
+                q.info[k] = float(info[k])
+        c = CConstraintsV2()
+        c.struct_size = C.sizeof(CConstraintsV2)
+        c.n_pair_priors = len(pp)
+        c.pair_priors = C.cast(self._pp, C.POINTER(CPairPrior)) if pp else None
+        self.n_pair_priors = len(pp)
         c.n_fixed_cams = len(self._fc)
         c.fixed_cams = self._fc.ctypes.data_as(C.POINTER(C.c_int32)) if len(self._fc) else None
         c.n_fixed_markers = len(self._fm)
@@ -173,10 +200,10 @@ class Constraints:
         self.n_priors = len(pr)
 
     def empty(self):
-        return self.c.n_fixed_cams == 0 and self.c.n_fixed_markers == 0 and self.c.n_priors == 0
+        return self.c.n_fixed_cams == 0 and self.c.n_fixed_markers == 0 and self.c.n_priors == 0 and self.c.n_pair_priors == 0
 
 
-def constraints_validate(ds, fixed_cams=None, fixed_markers=None, priors=None, optimize=None, struct_size=None):
+def constraints_validate(ds, fixed_cams=None, fixed_markers=None, priors=None, optimize=None, struct_size=None, pair_priors=None):
     """aar_problem_constraints_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  struct_size overrides
     the struct's own size (versioning tests)."""
     cds = ds.as_c()
@@ -184,7 +211,7 @@ def constraints_validate(ds, fixed_cams=None, fixed_markers=None, priors=None, o
     lib().aar_problem_desc_from_dataset(C.byref(cds), C.byref(d))
     if optimize is not None:
         d.optimize_cam_poses, d.optimize_marker_poses, d.optimize_object_poses = [int(b) for b in optimize]
-    k = Constraints(fixed_cams, fixed_markers, priors)
+    k = Constraints(fixed_cams, fixed_markers, priors, pair_priors)
     if struct_size is not None:
         k.c.struct_size = int(struct_size)
     _check(lib().aar_problem_constraints_validate(C.byref(d), C.byref(k.c)))
@@ -370,11 +397,16 @@ def lib():
     L.aar_problem_desc_from_dataset.restype = None
     L.aar_problem_create.argtypes = [C.POINTER(CProblemDesc), C.POINTER(C.c_void_p)]
     L.aar_problem_create_ex.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CSolverOptions), C.POINTER(C.c_void_p)]
-    L.aar_problem_constraints_validate.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CConstraints)]
-    L.aar_problem_create_constrained.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CSolverOptions), C.POINTER(CConstraints), C.POINTER(C.c_void_p)]
+    # (the constraints are size-versioned: CConstraints or CConstraintsV2, by struct_size)
+    L.aar_problem_constraints_validate.argtypes = [C.POINTER(CProblemDesc), C.c_void_p]
+    L.aar_problem_create_constrained.argtypes = [C.POINTER(CProblemDesc), C.POINTER(CSolverOptions), C.c_void_p, C.POINTER(C.c_void_p)]
     L.aar_problem_num_priors.argtypes = [C.c_void_p]
     L.aar_problem_num_priors.restype = C.c_int32
     L.aar_problem_eval_priors.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.aar_problem_num_pair_priors.argtypes = [C.c_void_p]
+    L.aar_problem_num_pair_priors.restype = C.c_int32
+    L.aar_problem_eval_pair_priors.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.aar_relative_pose.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.aar_solver_default_options.argtypes = [C.POINTER(CSolverOptions)]
     L.aar_solver_default_options.restype = None
     L.aar_problem_get_solver_stats.argtypes = [C.c_void_p, C.POINTER(CSolverStats)]
@@ -642,6 +674,15 @@ def rodrigues_mat2vec(R):
     w = np.zeros(3)
     lib().aar_rodrigues_mat2vec(_dptr(R), _dptr(w))
     return w
+
+
+def relative_pose(x6_a, x6_b):
+    """aar_relative_pose: the (rvec, t) of T_a^-1 T_b for two poses given as (rvec, t) -- a pair prior's x6_rel"""
+    a = np.ascontiguousarray(x6_a, dtype=np.float64).reshape(6)
+    b = np.ascontiguousarray(x6_b, dtype=np.float64).reshape(6)
+    out = np.zeros(6)
+    _check(lib().aar_relative_pose(_dptr(a), _dptr(b), _dptr(out)))
+    return out
 
 
 MAX_DIST = 12
@@ -1166,13 +1207,14 @@ class Problem:
 
     def __init__(self, ds, residual_mode=RES_F32, device=0, comm=None, optimize=None, with_huber=False, intrinsics=False,
                  solver=None, deterministic=None, pcg_eta=None, pcg_max_it=None, pcg_eta_loose=None, pcg_eta_switch=None, pcg_abs_tol=None,
-                 fixed_cams=None, fixed_markers=None, priors=None, constrained=False):
+                 fixed_cams=None, fixed_markers=None, priors=None, constrained=False, pair_priors=None):
         """intrinsics=True: Config::optimize_cam_intrinsics -- every vector ends with 9 per camera (x_with_intrinsics builds one)
         solver ("direct" | "spcg" | "pcg" | "auto"), deterministic, pcg_eta, pcg_max_it, pcg_eta_loose, pcg_eta_switch: aar_solver_options
         (None = the library's default: solver AUTO -- direct for one tile of unknowns, SPCG wherever it fits, PCG for many entities per frame x many frames -- with
         one pose-grade forcing term and an absolute tolerance; a forcing SEQUENCE only when pcg_eta_loose is given)
         fixed_cams, fixed_markers (indices), priors (list of (kind, index, x6, info)): aar_problem_constraints, created through
-        aar_problem_create_constrained (also taken, with empty constraints, when constrained=True)"""
+        aar_problem_create_constrained (also taken, with empty constraints, when constrained=True)
+        pair_priors (list of (kind, index_a, index_b, x6_rel, info)): relative pose priors between two cameras / two markers"""
         self.ds = ds
         self._cds = ds.as_c()
         d = CProblemDesc()
@@ -1187,8 +1229,9 @@ class Problem:
         self.optimize = (bool(d.optimize_cam_poses), bool(d.optimize_marker_poses), bool(d.optimize_object_poses))
         self.intrinsics = bool(intrinsics)
         self.handle = C.c_void_p()
-        self._cons = Constraints(fixed_cams, fixed_markers, priors)
+        self._cons = Constraints(fixed_cams, fixed_markers, priors, pair_priors)
         self.n_priors = self._cons.n_priors
+        self.n_pair_priors = self._cons.n_pair_priors
         if all(v is None for v in (solver, deterministic, pcg_eta, pcg_max_it, pcg_eta_loose, pcg_eta_switch, pcg_abs_tol)) and \
                 self._cons.empty() and not constrained:
             _check(lib().aar_problem_create(C.byref(d), C.byref(self.handle)))
@@ -1263,6 +1306,14 @@ class Problem:
         cost = C.c_double()
         _check(lib().aar_problem_eval_priors(self.handle, _dptr(x), _dptr(e), C.byref(cost)))
         return e[:self.n_priors], cost.value
+
+    def eval_pair_priors(self, x_full):
+        """aar_problem_eval_pair_priors: (e [n_pair_priors][6], summed cost e^T L e) at x_full"""
+        x = self._x(x_full)
+        e = np.zeros((max(self.n_pair_priors, 1), 6))
+        cost = C.c_double()
+        _check(lib().aar_problem_eval_pair_priors(self.handle, _dptr(x), _dptr(e), C.byref(cost)))
+        return e[:self.n_pair_priors], cost.value
 
     def eval_damped_step(self, x_full, mu):
         x = self._x(x_full)

@@ -576,12 +576,13 @@ int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool s
         StageTimer t(pb, &pb->times.jacobian_normal_eq);
         if (pb->merge_passes && launch_passAB(P, which, mu_pred, zero_blk, pb->stream)) {
             launch_prior(P, which, true, pb->stream);   // (priors: after pass B, before anything reads S)
+            launch_pair_prior(P, which, true, pb->stream);
             if (spec_schur) launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
-            pb->launches += (spec_schur ? 2 : 1) + (P.n_prior ? 1 : 0);
+            pb->launches += (spec_schur ? 2 : 1) + n_prior_launches(P);
             return check_async("normal-equation kernels");
         }
         launch_passA(P, which, mu_pred, zero_blk, pb->stream);
-        if (spec_schur && pb->overlap && !pb->profiling && !pb->stage_timers && P.n_prior == 0) {
+        if (spec_schur && pb->overlap && !pb->profiling && !pb->stage_timers && n_prior_launches(P) == 0) {
             HIP_TRY(hipEventRecord(pb->ev_fork, pb->stream));
             HIP_TRY(hipStreamWaitEvent(pb->stream2, pb->ev_fork, 0));
             launch_passB(P, which, pb->stream2);
@@ -591,11 +592,12 @@ int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool s
         } else {
             launch_passB(P, which, pb->stream);
             launch_prior(P, which, true, pb->stream);
+            launch_pair_prior(P, which, true, pb->stream);
             if (spec_schur) launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
         }
     }
     if (spec_schur) panels_now(pb, which, mu_pred);
-    pb->launches += (spec_schur ? 3 : 2) + (P.n_prior ? 1 : 0);
+    pb->launches += (spec_schur ? 3 : 2) + n_prior_launches(P);
     return check_async("normal-equation kernels");
 }
 
@@ -743,7 +745,8 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
             if (rc) return rc;
             launch_passB(P, cur, pb->stream);
             launch_prior(P, cur, true, pb->stream);
-            pb->launches += P.n_prior ? 2 : 1;
+            launch_pair_prior(P, cur, true, pb->stream);
+            pb->launches += 1 + n_prior_launches(P);
             pb->s_reduced = false;
         } else if (pb->schur_mu >= 0) {
             // the speculative Schur complement was taken with another damping than the step now needs (gain < 0.94): take it
@@ -1108,7 +1111,7 @@ aar_problem_constraints constraints_of(const aar_problem_constraints *c) {
     k.struct_size = (uint32_t)sizeof k;
     return k;
 }
-bool constraints_empty(const aar_problem_constraints &k) { return k.n_fixed_cams == 0 && k.n_fixed_markers == 0 && k.n_priors == 0; }
+bool constraints_empty(const aar_problem_constraints &k) { return k.n_fixed_cams == 0 && k.n_fixed_markers == 0 && k.n_priors == 0 && k.n_pair_priors == 0; }
 // symmetric positive semi-definite: LDL^T without pivoting, a negative pivot or a zero pivot over a non-zero column fails
 bool info_psd(const double *I) {
     double scale = 0;
@@ -1145,8 +1148,8 @@ int aar_problem_constraints_validate(const aar_problem_desc *d, const aar_proble
     if (cons->struct_size < sizeof(uint32_t) + sizeof(int32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_constraints.struct_size is not set");
     const aar_problem_constraints k = constraints_of(cons);
     const int C = d->num_cams, M = d->num_markers;
-    if (k.n_fixed_cams < 0 || k.n_fixed_markers < 0 || k.n_priors < 0) return set_error(AAR_ERR_INVALID, "aar_problem_constraints: negative count");
-    if ((k.n_fixed_cams && !k.fixed_cams) || (k.n_fixed_markers && !k.fixed_markers) || (k.n_priors && !k.priors))
+    if (k.n_fixed_cams < 0 || k.n_fixed_markers < 0 || k.n_priors < 0 || k.n_pair_priors < 0) return set_error(AAR_ERR_INVALID, "aar_problem_constraints: negative count");
+    if ((k.n_fixed_cams && !k.fixed_cams) || (k.n_fixed_markers && !k.fixed_markers) || (k.n_priors && !k.priors) || (k.n_pair_priors && !k.pair_priors))
         return set_error(AAR_ERR_INVALID, "aar_problem_constraints: null array with a non-zero count");
     std::vector<uint8_t> fixed((size_t)std::max(C, 0) + std::max(M, 0), 0);
     for (int c = 0; c < C; c++) fixed[c] = (c == d->root_cam || !d->optimize_cam_poses) ? 1 : 0;
@@ -1178,6 +1181,26 @@ int aar_problem_constraints_validate(const aar_problem_desc *d, const aar_proble
             if (!std::isfinite(q.info[i])) return set_error(AAR_ERR_INVALID, "priors[%d]: info[%d] is not finite", p, i);
         if (!info_psd(q.info)) return set_error(AAR_ERR_INVALID, "priors[%d]: the information matrix is not symmetric positive semi-definite (its Cholesky fails)", p);
     }
+    std::map<std::pair<size_t, size_t>, int> seen;   // unordered pair of entities -> the entry that named it
+    for (int p = 0; p < k.n_pair_priors; p++) {
+        const aar_pair_prior &q = k.pair_priors[p];
+        const char *what = q.kind == AAR_PRIOR_CAMERA ? "camera" : "marker";
+        if (q.kind != AAR_PRIOR_CAMERA && q.kind != AAR_PRIOR_MARKER) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: kind %d is not AAR_PRIOR_CAMERA or AAR_PRIOR_MARKER", p, q.kind);
+        const int lim = q.kind == AAR_PRIOR_CAMERA ? C : M;
+        if (q.index_a < 0 || q.index_a >= lim) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: %s index_a %d out of range [0, %d)", p, what, q.index_a, lim);
+        if (q.index_b < 0 || q.index_b >= lim) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: %s index_b %d out of range [0, %d)", p, what, q.index_b, lim);
+        if (q.index_a == q.index_b) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: index_a and index_b are both %s %d", p, what, q.index_a);
+        const size_t ea = q.kind == AAR_PRIOR_CAMERA ? (size_t)q.index_a : (size_t)C + q.index_a, eb = q.kind == AAR_PRIOR_CAMERA ? (size_t)q.index_b : (size_t)C + q.index_b;
+        const auto ins = seen.insert({{std::min(ea, eb), std::max(ea, eb)}, p});
+        if (!ins.second) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: %ss %d and %d already have a pair prior (pair_priors[%d])", p, what, q.index_a, q.index_b, ins.first->second);
+        if (fixed[ea] && fixed[eb])
+            return set_error(AAR_ERR_INVALID, "pair_priors[%d]: %ss %d and %d are both fixed (root, non-optimised group or fixed index)", p, what, q.index_a, q.index_b);
+        for (int i = 0; i < 6; i++)
+            if (!std::isfinite(q.x6_rel[i])) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: x6_rel[%d] is not finite", p, i);
+        for (int i = 0; i < 36; i++)
+            if (!std::isfinite(q.info[i])) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: info[%d] is not finite", p, i);
+        if (!info_psd(q.info)) return set_error(AAR_ERR_INVALID, "pair_priors[%d]: the information matrix is not symmetric positive semi-definite (its Cholesky fails)", p);
+    }
     return AAR_OK;
 }
 
@@ -1191,6 +1214,7 @@ int aar_problem_create_constrained(const aar_problem_desc *d, const aar_solver_o
 }
 
 int32_t aar_problem_num_priors(const aar_problem *pb) { return pb ? pb->P.n_prior : 0; }
+int32_t aar_problem_num_pair_priors(const aar_problem *pb) { return pb ? pb->P.n_pair : 0; }
 
 // AAR_ABORT_BACKTRACE=<file> (diagnostics): the native stack of whoever raises SIGABRT in this process (a runtime library giving up) is appended to the file before the default action
 static int abort_bt_fd = 2;
@@ -1322,6 +1346,8 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
         for (int i = 0; i < cons->n_fixed_cams; i++) { const int c = cons->fixed_cams[i]; if (c != L.rc && L.oc) { held[c] = 1; held_extra = true; } }
         for (int i = 0; i < cons->n_fixed_markers; i++) { const int m = cons->fixed_markers[i]; if (m != L.rm && L.om) { held[C + m] = 1; held_extra = true; } }
     }
+
+    auto pair_end_fixed = [&](int e) { return held[e] || (e < C ? (e == L.rc || !L.oc) : (e - C == L.rm || !L.om)); };   // (e: a camera or marker entity)
 
     int local_rc = AAR_OK;   // rank-local limits: decided collectively below
     // ---- ordering A (reference order) + per-frame slot lists ----
@@ -1516,6 +1542,14 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
             for (int x = 0; x < 3; x++)
                 for (int y = 0; y < 3; y++)
                     if (x != y && ents[x] >= 0 && ents[y] >= 0) nb[ents[x]].push_back(ents[y]);
+        }
+        // relative pose priors: the camera-camera / marker-marker block of a pair whose two ends are free (a fixed end has no block)
+        for (int p = 0; cons && p < cons->n_pair_priors; p++) {
+            const aar_pair_prior &q = cons->pair_priors[p];
+            const int off = q.kind == AAR_PRIOR_CAMERA ? 0 : C, ea = off + q.index_a, eb = off + q.index_b;
+            if (pair_end_fixed(ea) || pair_end_fixed(eb)) continue;
+            nb[ea].push_back(eb);
+            nb[eb].push_back(ea);
         }
         for (int a = 0; a < A; a++) {
             std::sort(nb[a].begin(), nb[a].end());
@@ -1816,6 +1850,42 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
         P.prior_rank0 = rank == 0 ? 1 : 0;
         pb->priors.assign(cons->priors, cons->priors + np_);
     }
+    if (cons && cons->n_pair_priors > 0) {
+        // per pair: its ends and record; per free end entity: the (pair, side) items that add to its diagonal block, in ascending pair order
+        const int np_ = cons->n_pair_priors;
+        std::vector<int32_t> ends((size_t)np_ * 4, 0);
+        std::vector<double> pdat((size_t)np_ * PRIOR_DAT);
+        std::vector<std::vector<int32_t>> items(C + M);
+        for (int p = 0; p < np_; p++) {
+            const aar_pair_prior &q = cons->pair_priors[p];
+            const int off = q.kind == AAR_PRIOR_CAMERA ? 0 : C, ea = off + q.index_a, eb = off + q.index_b;
+            const bool fa = ent_fixed[ea] != 0, fb = ent_fixed[eb] != 0;
+            ends[4 * (size_t)p] = ea; ends[4 * (size_t)p + 1] = eb; ends[4 * (size_t)p + 2] = (!fa && !fb) ? 1 : 0;
+            if (!fa) items[ea].push_back(2 * p);
+            if (!fb) items[eb].push_back(2 * p + 1);
+            memcpy(&pdat[(size_t)p * PRIOR_DAT], q.x6_rel, 6 * sizeof(double));
+            memcpy(&pdat[(size_t)p * PRIOR_DAT + 6], q.info, 36 * sizeof(double));
+        }
+        std::vector<int32_t> el_ent, el_start, el_item;
+        for (int e = 0; e < C + M; e++) {
+            if (items[e].empty()) continue;
+            el_ent.push_back(e);
+            el_start.push_back((int32_t)el_item.size());
+            el_item.insert(el_item.end(), items[e].begin(), items[e].end());
+        }
+        el_start.push_back((int32_t)el_item.size());
+        P.n_pair_el = (int)el_ent.size();
+        P.n_pair_items = (int)el_item.size();
+        if (el_ent.empty()) el_ent.push_back(0);
+        if (el_item.empty()) el_item.push_back(0);
+        if ((rc = dev_upload(pb, &P.pair_ends, ends)) || (rc = dev_upload(pb, &P.pair_dat, pdat)) || (rc = dev_upload(pb, &P.pair_el_ent, el_ent)) ||
+            (rc = dev_upload(pb, &P.pair_el_start, el_start)) || (rc = dev_upload(pb, &P.pair_el_item, el_item)))
+            return fail(rc);
+        AL(pair_rec_ws, (size_t)np_ * 54);
+        AL(pair_out, (size_t)np_ * 8 + 1);
+        P.n_pair = np_;
+        P.prior_rank0 = rank == 0 ? 1 : 0;
+    }
 #undef AL
     if ((rc = dev_alloc(pb, &pb->d_diag, P.n_pad))) return fail(rc);
     if (pb->comm && (rc = dev_alloc(pb, &pb->d_frames_all, 6 * (size_t)std::max(Fg, 1)))) return fail(rc);
@@ -2000,6 +2070,39 @@ int aar_problem_eval_priors(aar_problem *pb, const double *x_full, double *e_out
     if (e_out)
         for (int p = 0; p < P.n_prior; p++) memcpy(e_out + 6 * (size_t)p, &h[8 * (size_t)p], 6 * sizeof(double));
     if (cost) *cost = h[(size_t)P.n_prior * 8];
+    return AAR_OK;
+}
+
+int aar_problem_eval_pair_priors(aar_problem *pb, const double *x_full, double *e_out, double *cost) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_problem_eval_pair_priors: null argument");
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    if (P.n_pair == 0) {
+        if (cost) *cost = 0.0;
+        return AAR_OK;
+    }
+    int rc = upload_z(pb, x_full, pb->cur);
+    if (rc) return rc;
+    // the entity rows of `cur` are rewritten: whatever the LM state was, it is gone
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    launch_unpack(P, pb->cur, pb->stream);
+    launch_pair_prior(P, pb->cur, /*add=*/false, pb->stream);
+    pb->launches += 2;
+    if ((rc = check_async("pair prior kernels"))) return rc;
+    HIP_TRY(hipStreamSynchronize(pb->stream));
+    std::vector<double> h((size_t)P.n_pair * 8 + 1);
+    if ((rc = copy_d2h(pb, h.data(), P.pair_out, h.size() * sizeof(double)))) return rc;
+    if (e_out)
+        for (int p = 0; p < P.n_pair; p++) memcpy(e_out + 6 * (size_t)p, &h[8 * (size_t)p], 6 * sizeof(double));
+    if (cost) *cost = h[(size_t)P.n_pair * 8];
+    return AAR_OK;
+}
+
+// T_a^-1 T_b of two poses given as (rvec, t), as (rvec, t): what aar_pair_prior.x6_rel holds.  Host code.
+int aar_relative_pose(const double *x6_a, const double *x6_b, double *x6_rel_out) {
+    if (!x6_a || !x6_b || !x6_rel_out) return set_error(AAR_ERR_INVALID, "aar_relative_pose: null argument");
+    aar::rigid_to_pose(aar::compose(aar::inverse(aar::pose_to_rigid(x6_a)), aar::pose_to_rigid(x6_b)), x6_rel_out);
     return AAR_OK;
 }
 

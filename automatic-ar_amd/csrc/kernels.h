@@ -206,6 +206,13 @@ struct DeviceProblem {
     int32_t *prior_ent = nullptr;         // [n_prior] shared entity
     double *prior_dat = nullptr;          // [n_prior][PRIOR_DAT] x6 | information matrix
     double *prior_out = nullptr;          // [n_prior][8] e | cost | 0, then the summed cost
+    // relative pose priors between two cameras / two markers (pair_prior_kernels.hip): held and added as the pose priors are
+    int n_pair = 0, n_pair_el = 0, n_pair_items = 0;
+    int32_t *pair_ends = nullptr;         // [n_pair][4] entity a, entity b, 1 = both ends free, 0
+    double *pair_dat = nullptr;           // [n_pair][PRIOR_DAT] x6_rel | information matrix
+    int32_t *pair_el_ent = nullptr, *pair_el_start = nullptr, *pair_el_item = nullptr;   // free end entities -> their (pair, side) items, ascending
+    double *pair_rec_ws = nullptr;        // [n_pair][54] the diagonal contributions between the kernel's two phases
+    double *pair_out = nullptr;           // [n_pair][8] e | cost | 0, then the summed cost
     LaunchHook hook;
 };
 
@@ -286,7 +293,11 @@ int residual_blocks(const DeviceProblem &P);   // entries of err_part written by
 constexpr int PRIOR_DAT = 42;
 void launch_prior(const DeviceProblem &P, int which, bool add, hipStream_t st);
 // entries of err_part the step's error sums: the frames' and, with priors on this rank, their cost behind them
-inline int n_err_terms(const DeviceProblem &P) { return P.F + ((P.n_prior > 0 && P.prior_rank0) ? 1 : 0); }
+inline int n_err_terms(const DeviceProblem &P) { return P.F + (((P.n_prior > 0 || P.n_pair > 0) && P.prior_rank0) ? 1 : 0); }
+// relative pose priors at ent[which], right behind launch_prior at every site: e and the costs into pair_out; add (and rank 0): the two diagonal
+// blocks and the cross block of every pair into blk[which].S, -J^T L e into its g0, the summed cost into err_part[F] (added to k_prior's, if any)
+void launch_pair_prior(const DeviceProblem &P, int which, bool add, hipStream_t st);
+inline int n_prior_launches(const DeviceProblem &P) { return (P.n_prior ? 1 : 0) + (P.n_pair ? 1 : 0); }
 // track(): every frame's own 6-DoF LM, whole loop on the device; needs ent[which] rows of the shared entities (launch_unpack)
 void launch_track(const DeviceProblem &P, int which, int max_iters, double min_error, double min_step, double min_avg, double tau,
                   int32_t *iters_out, double *err_out, hipStream_t st);

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -40,6 +40,10 @@ static int print_usage(const char *a0) {
     cout << "                            prior, information diag(1/sigma_rot^2 x3, 1/sigma_t^2 x3)); f must have the same root camera and marker ids" << endl;
     cout << "       -prior-sigma-deg d   rotation sigma of those priors in degrees (default 1)" << endl;
     cout << "       -prior-sigma-m m     translation sigma of those priors in metres (default 0.01)" << endl;
+    cout << "       -relative-prior-solution f   hold the RELATIVE poses of the .solution file f: a chain of pair priors between consecutive cameras /" << endl;
+    cout << "                            markers (ascending problem index) that f has, each an isotropic prior on T_a^-1 T_b; f may have other roots" << endl;
+    cout << "       -relative-kinds k    cams | markers | both (default both)" << endl;
+    cout << "       -relative-sigma-deg d, -relative-sigma-m m   sigmas of those priors (defaults 1 degree, 0.01 m)" << endl;
     cout << "       " << a0 << " --synth <config 1..5> <out_folder>   (write a synthetic data set in the reference's file formats)" << endl;
     return -1;
 }
@@ -126,6 +130,51 @@ static int read_pose_priors(const string &path, const aar_dataset *d, double sig
     return 0;
 }
 
+// -relative-prior-solution: a chain of pair priors between consecutive cameras / markers of the problem (ascending index) that the file has, each
+// T_a^-1 T_b of the file's poses with an isotropic information matrix.  Relative poses do not depend on the roots, so the file may have its own.
+static int read_relative_priors(const string &path, const aar_dataset *d, int kinds, double sigma_deg, double sigma_m, vector<aar::MultiCamMapper::RelativePrior> &out) {
+    aar_dataset *p = nullptr;
+    if (aar_solution_read(path.c_str(), &p)) {
+        cerr << "cannot read the relative prior solution " << path << ": " << aar_last_error() << endl;
+        return 1;
+    }
+    std::unique_ptr<aar_dataset, void (*)(aar_dataset *)> hold(p, aar_dataset_free);
+    const double sr = sigma_deg * M_PI / 180.0;
+    aar::MultiCamMapper::Mat66 info{};
+    for (int i = 0; i < 6; i++) info[7 * i] = i < 3 ? 1.0 / (sr * sr) : 1.0 / (sigma_m * sigma_m);
+    // the file's pose of entity `idx` of a group of n with root `root` whose x_full block starts at `base`
+    auto pose_of = [&](int idx, int root, size_t base) {
+        if (idx == root) return aar::Rigid::identity();
+        return aar::pose_to_rigid(p->x_full + base + 6 * (size_t)(idx - (idx > root ? 1 : 0)));
+    };
+    auto chain = [&](int kind, const int32_t *ids, int n, const int32_t *fids, int fn, int froot, size_t base) {
+        int prev_id = 0;
+        aar::Rigid prev{};
+        bool have = false;
+        for (int i = 0; i < n; i++) {
+            const int32_t *e = fids + fn, *q = std::lower_bound(fids, e, ids[i]);
+            if (q == e || *q != ids[i]) continue;
+            const aar::Rigid cur = pose_of((int)(q - fids), froot, base);
+            if (have) {
+                const aar::Rigid rel = aar::compose(aar::inverse(prev), cur);
+                aar::MultiCamMapper::RelativePrior r;
+                r.kind = kind; r.id_a = prev_id; r.id_b = ids[i];
+                for (int a = 0; a < 3; a++) {
+                    for (int b = 0; b < 3; b++) r.T[4 * a + b] = rel.R[3 * a + b];
+                    r.T[4 * a + 3] = rel.t[a];
+                }
+                r.T[15] = 1.0;
+                r.info = info;
+                out.push_back(r);
+            }
+            prev = cur; prev_id = ids[i]; have = true;
+        }
+    };
+    if (kinds & 1) chain(AAR_PRIOR_CAMERA, d->cam_ids, d->num_cams, p->cam_ids, p->num_cams, p->root_cam, 0);
+    if (kinds & 2) chain(AAR_PRIOR_MARKER, d->marker_ids, d->num_markers, p->marker_ids, p->num_markers, p->root_marker, 6 * (size_t)(p->num_cams - 1));
+    return 0;
+}
+
 // -reject-outliers: report, drop, solve again from that solution -- until a round drops nothing, at most 3 rounds.  final.residuals.yaml
 // then holds the final solution's statistics over the detections it kept; its rejected counts and list cover every detection dropped in
 // any round (with its error in the round that dropped it), against the detections the first solve had.
@@ -195,6 +244,10 @@ int main(int argc, char *argv[]) {
     bool fix_cams = false, fix_markers = false;
     string prior_path;
     double prior_sigma_deg = 1.0, prior_sigma_m = 0.01;
+    // nor these: -relative-prior-solution holds the relative poses of consecutive cameras / markers of a solution file (pair priors)
+    string rel_path;
+    int rel_kinds = 3;   // bit 0: cameras, bit 1: markers
+    double rel_sigma_deg = 1.0, rel_sigma_m = 0.01;
     // nor this: -smooth <sigma_rot> <sigma_trans> (only with -tracking-only) refines every frame with track() after the solve and then smooths the
     // trajectory with a motion prior between consecutive frames (MultiCamMapper::track_smooth)
     bool smooth = false;
@@ -213,7 +266,7 @@ int main(int argc, char *argv[]) {
     bool live_anchor_set = false, live_covariance = false;
     double live_sigma[2] = {0.0, 0.0};
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, Smooth, Live, Anchor } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Live, Anchor } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -232,6 +285,10 @@ int main(int argc, char *argv[]) {
         else if (a == "-prior-solution") arg_flag = PriorPath;
         else if (a == "-prior-sigma-deg") arg_flag = PriorDeg;
         else if (a == "-prior-sigma-m") arg_flag = PriorM;
+        else if (a == "-relative-prior-solution") arg_flag = RelPath;
+        else if (a == "-relative-kinds") arg_flag = RelKinds;
+        else if (a == "-relative-sigma-deg") arg_flag = RelDeg;
+        else if (a == "-relative-sigma-m") arg_flag = RelM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
@@ -273,6 +330,19 @@ int main(int argc, char *argv[]) {
             arg_flag = NONE;
         }
         else if (arg_flag == PriorPath) { prior_path = a; arg_flag = NONE; }
+        else if (arg_flag == RelPath) { rel_path = a; arg_flag = NONE; }
+        else if (arg_flag == RelKinds) {
+            if (a != "cams" && a != "markers" && a != "both") return print_usage(argv[0]);
+            rel_kinds = a == "cams" ? 1 : (a == "markers" ? 2 : 3);
+            arg_flag = NONE;
+        }
+        else if (arg_flag == RelDeg || arg_flag == RelM) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            (arg_flag == RelDeg ? rel_sigma_deg : rel_sigma_m) = v;
+            arg_flag = NONE;
+        }
         else if (arg_flag == PriorDeg || arg_flag == PriorM) {
             char *end = nullptr;
             const double v = strtod(a.c_str(), &end);
@@ -374,7 +444,7 @@ int main(int argc, char *argv[]) {
         so.solver = solver;
         mcm.set_solver_options(so);
     }
-    const bool constrained = fix_cams || fix_markers || !prior_path.empty();
+    const bool constrained = fix_cams || fix_markers || !prior_path.empty() || !rel_path.empty();
     if (constrained) {
         if (fix_cams) mcm.set_fixed_cams(fixed_cams);
         if (fix_markers) mcm.set_fixed_markers(fixed_markers);
@@ -383,12 +453,20 @@ int main(int argc, char *argv[]) {
             if (read_pose_priors(prior_path, mcm.dataset(), prior_sigma_deg, prior_sigma_m, priors)) return 5;
             mcm.set_pose_priors(priors);
         }
+        if (!rel_path.empty()) {
+            vector<aar::MultiCamMapper::RelativePrior> rel;
+            if (read_relative_priors(rel_path, mcm.dataset(), rel_kinds, rel_sigma_deg, rel_sigma_m, rel)) return 5;
+            mcm.set_relative_priors(rel);
+        }
         try {
             const aar::MultiCamMapper::ConstraintIndices k = mcm.constraint_indices();
             cout << "constraints: " << k.fixed_cams.size() << " fixed camera(s), " << k.fixed_markers.size() << " fixed marker(s), " << k.priors.size()
                  << " pose prior(s)";
             if (!prior_path.empty()) cout << " from " << prior_path << " (sigma " << prior_sigma_deg << " deg, " << prior_sigma_m << " m)";
             cout << endl;
+            if (!rel_path.empty())
+                cout << "constraints: " << k.pair_priors.size() << " relative pose prior(s) from " << rel_path << " (" << (rel_kinds == 1 ? "cams" : rel_kinds == 2 ? "markers" : "both")
+                     << ", sigma " << rel_sigma_deg << " deg, " << rel_sigma_m << " m)" << endl;
         } catch (const exception &e) {
             cerr << "constraints: " << e.what() << endl;
             return 5;
@@ -495,8 +573,10 @@ int main(int argc, char *argv[]) {
          << " LM it/s in the solver loop)" << endl;
     if (constrained) {
         try {
-            const double pc = mcm.prior_cost();
-            cout << "final error: reprojection " << r.final_err - pc << " + prior " << pc << endl;
+            const double pc = mcm.prior_cost(), rc_ = rel_path.empty() ? 0.0 : mcm.relative_prior_cost();
+            cout << "final error: reprojection " << r.final_err - pc - rc_ << " + prior " << pc;
+            if (!rel_path.empty()) cout << " + relative prior " << rc_;
+            cout << endl;
         } catch (const exception &e) {
             cerr << "prior cost failed: " << e.what() << endl;
             return 3;

@@ -297,6 +297,7 @@ int MultiCamMapper::ensure_problem() {
         c.n_fixed_cams = (int32_t)k.fixed_cams.size(); c.fixed_cams = k.fixed_cams.data();
         c.n_fixed_markers = (int32_t)k.fixed_markers.size(); c.fixed_markers = k.fixed_markers.data();
         c.n_priors = (int32_t)k.priors.size(); c.priors = k.priors.data();
+        c.n_pair_priors = (int32_t)k.pair_priors.size(); c.pair_priors = k.pair_priors.data();
         rc = aar_problem_create_constrained(&d, &so, &c, &problem_);
     }
     if (!rc && with_huber_) rc = aar_problem_set_huber_delta(problem_, hubberDelta);
@@ -306,6 +307,7 @@ int MultiCamMapper::ensure_problem() {
 void MultiCamMapper::set_fixed_cams(std::set<int> ids) { fixed_cam_ids_ = std::move(ids); drop_problem(); }
 void MultiCamMapper::set_fixed_markers(std::set<int> ids) { fixed_marker_ids_ = std::move(ids); drop_problem(); }
 void MultiCamMapper::set_pose_priors(std::vector<PosePrior> priors) { pose_priors_ = std::move(priors); drop_problem(); }
+void MultiCamMapper::set_relative_priors(std::vector<RelativePrior> priors) { relative_priors_ = std::move(priors); drop_problem(); }
 
 MultiCamMapper::ConstraintIndices MultiCamMapper::constraint_indices() const {
     ConstraintIndices k;
@@ -331,7 +333,29 @@ MultiCamMapper::ConstraintIndices MultiCamMapper::constraint_indices() const {
         memcpy(p.info, q.info.data(), sizeof p.info);
         k.priors.push_back(p);
     }
+    for (const RelativePrior &q : relative_priors_) {
+        aar_pair_prior p;
+        memset(&p, 0, sizeof p);
+        p.kind = q.kind;
+        const bool cam = q.kind == AAR_PRIOR_CAMERA;
+        p.index_a = cam ? index_of(data_->cam_ids, C, q.id_a, "camera") : index_of(data_->marker_ids, M, q.id_a, "marker");
+        p.index_b = cam ? index_of(data_->cam_ids, C, q.id_b, "camera") : index_of(data_->marker_ids, M, q.id_b, "marker");
+        if (held[cam ? p.index_a : C + p.index_a] && held[cam ? p.index_b : C + p.index_b]) continue;
+        rigid_to_pose(from44(q.T), p.x6_rel);
+        memcpy(p.info, q.info.data(), sizeof p.info);
+        k.pair_priors.push_back(p);
+    }
     return k;
+}
+
+double MultiCamMapper::relative_prior_cost() {
+    if (!data_) throw std::runtime_error("MultiCamMapper::relative_prior_cost: no data set");
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    if (aar_problem_num_pair_priors(problem_) == 0) return 0.0;
+    std::vector<double> x = problem_vector();
+    double cost = 0;
+    if (aar_problem_eval_pair_priors(problem_, x.data(), nullptr, &cost)) throw std::runtime_error(aar_last_error());
+    return cost;
 }
 
 double MultiCamMapper::prior_cost() {

@@ -508,16 +508,28 @@ class MultiCamMapper {
         Mat44 T{};
         Mat66 info{};
     };
+    // relative pose priors: T is the prior for T_a^-1 T_b of two cameras / two markers given by id (a stereo baseline, a
+    // printed board, a bracket).  Held like the pose priors; a pair whose two ends the Config or the fixed sets hold is left out (one held end
+    // stays: it is a constant of the term).
+    struct RelativePrior {
+        int kind = AAR_PRIOR_CAMERA;   // AAR_PRIOR_CAMERA | AAR_PRIOR_MARKER: both ends
+        int id_a = 0, id_b = 0;
+        Mat44 T{};
+        Mat66 info{};
+    };
+    void set_relative_priors(std::vector<RelativePrior> priors);
     void set_fixed_cams(std::set<int> ids);
     void set_fixed_markers(std::set<int> ids);
     void set_pose_priors(std::vector<PosePrior> priors);
     struct ConstraintIndices {   // what the device problem gets: indices, and the priors as x6 in x_full's convention
         std::vector<int32_t> fixed_cams, fixed_markers;
         std::vector<aar_pose_prior> priors;
-        bool empty() const { return fixed_cams.empty() && fixed_markers.empty() && priors.empty(); }
+        std::vector<aar_pair_prior> pair_priors;
+        bool empty() const { return fixed_cams.empty() && fixed_markers.empty() && priors.empty() && pair_priors.empty(); }
     };
     ConstraintIndices constraint_indices() const;
     double prior_cost();   // sum of e^T L e at the current solution (aar_problem_eval_priors); 0 without priors
+    double relative_prior_cost();   // the same of the relative priors (aar_problem_eval_pair_priors)
 
     const aar_dataset *dataset() const { return data_; }
 
@@ -541,6 +553,7 @@ class MultiCamMapper {
     bool with_huber_ = false;
     std::set<int> fixed_cam_ids_, fixed_marker_ids_;
     std::vector<PosePrior> pose_priors_;
+    std::vector<RelativePrior> relative_priors_;
 };
 
 // EXTENSION, no counterpart in the reference as a class: the live tracker (aar_tracker_*) by camera ID and marker ID.

@@ -448,6 +448,22 @@ typedef struct aar_pose_prior {
     double x6[6];                             /* prior pose (rx ry rz tx ty tz), x_full's convention                      */
     double info[36];                          /* row-major 6x6 information matrix, rotation rows first                    */
 } aar_pose_prior;
+/* Relative pose priors between two cameras or two markers: what a caller who knows a stereo baseline, a printed
+ * board layout or a machined bracket knows.  For two entities a != b of the same kind, (R_rel, t_rel) from x6_rel -- the (rvec, t) of
+ * T_a^-1 T_b, see aar_relative_pose -- and an information matrix L as in aar_pose_prior (a root's pose is the identity):
+ *        R_ab = R_a^T R_b,   t_ab = R_a^T (t_b - t_a),   phi = log(R_rel^T R_ab)^v,   e = [phi ; t_ab - t_rel],   cost = e^T L e
+ *    The cost joins the error exactly where the pose priors' does; J_a^T L J_a and J_b^T L J_b join the two entities' diagonal blocks of
+ *    J^T J, J_a^T L J_b the block between them, -J^T L e joins B.  Never Huber-weighted; L = 0 adds exact zeros.  An end that is fixed
+ *    (root, non-optimised group or fixed index) is a constant of the term: none of its rows, columns or blocks are touched.  Several pairs may
+ *    share an entity (a board as a star or a chain), and an entity may carry a pose prior and pair priors together.
+ *  Validation (AAR_ERR_INVALID, the message names the entry): an unknown kind, an index out of range, index_a == index_b, the same
+ *    unordered pair given twice, both ends fixed, a non-finite value, L not symmetric or not positive semi-definite. */
+typedef struct aar_pair_prior {
+    int32_t kind;                             /* AAR_PRIOR_CAMERA | AAR_PRIOR_MARKER: both ends are of this kind                 */
+    int32_t index_a, index_b;                 /* camera / marker indices                                                  */
+    double x6_rel[6];                         /* prior for T_a^-1 T_b as (rx ry rz tx ty tz)                              */
+    double info[36];                          /* row-major 6x6 information matrix, rotation rows first                    */
+} aar_pair_prior;
 typedef struct aar_problem_constraints {
     uint32_t struct_size;                     /* sizeof(aar_problem_constraints) of the caller: fields beyond it count as empty */
     int32_t n_fixed_cams;
@@ -456,6 +472,8 @@ typedef struct aar_problem_constraints {
     const int32_t *fixed_markers;             /* [n_fixed_markers] marker indices                                         */
     int32_t n_priors;
     const aar_pose_prior *priors;             /* [n_priors]                                                               */
+    int32_t n_pair_priors;                    /* (appended: a caller whose struct_size stops before these two has none)   */
+    const aar_pair_prior *pair_priors;        /* [n_pair_priors]                                                          */
 } aar_problem_constraints;
 /* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the offending entry.  NULL constraints are valid. */
 int aar_problem_constraints_validate(const aar_problem_desc *, const aar_problem_constraints *);
@@ -468,6 +486,12 @@ int32_t aar_problem_num_priors(const aar_problem *);
 /* The priors at x_full, by the device code the solver runs: e_out [n_priors][6] (may be NULL), cost = sum of e^T L e (may be NULL).
  * With a communicator every rank gets the same values.  Leaves the problem as aar_eval_damped_step does (no LM state). */
 int aar_problem_eval_priors(aar_problem *, const double *x_full, double *e_out, double *cost);
+int32_t aar_problem_num_pair_priors(const aar_problem *);
+/* The pair priors at x_full, by the device code the solver runs: e_out [n_pair_priors][6] (may be NULL), cost = sum of e^T L e (may be NULL).
+ * With a communicator every rank gets the same values.  Leaves the problem as aar_eval_damped_step does (no LM state). */
+int aar_problem_eval_pair_priors(aar_problem *, const double *x_full, double *e_out, double *cost);
+/* x6_rel_out = the (rvec, t) of T_a^-1 T_b for two poses given as (rvec, t): aar_pair_prior.x6_rel of a pair that is where it should be.  Host code. */
+int aar_relative_pose(const double *x6_a, const double *x6_b, double *x6_rel_out);
 
 /* ucoslam::SparseLevMarq<T>::Params (libs/sparselevmarq.h:30-50) with the values
  * MultiCamMapper::init installs (libs/multicam_mapper.cpp:326-330). */
