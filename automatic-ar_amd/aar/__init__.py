@@ -47,6 +47,8 @@ SYMBOLS = [
     "aar_tracker_bank_params_validate", "aar_tracker_bank_create", "aar_tracker_bank_size", "aar_tracker_bank_push",
     "aar_tracker_bank_enable_detections", "aar_tracker_bank_push_detections", "aar_tracker_bank_window", "aar_tracker_bank_uncertainty",
     "aar_tracker_bank_reset", "aar_tracker_bank_get_stats", "aar_tracker_bank_destroy",
+    "aar_tracker_default_gate_params", "aar_tracker_gate_params_validate", "aar_tracker_enable_gate", "aar_tracker_last_gate",
+    "aar_tracker_gate_detail", "aar_tracker_gate_bank_enable", "aar_tracker_gate_bank_last", "aar_tracker_gate_bank_detail",
 ]
 TRACKER_BANK_MAX_MEMBERS = 1024
 TRACKER_MAX_LAG = 15
@@ -273,6 +275,15 @@ class CTrackerUncertainty(C.Structure):
                 ("marginal_info", C.c_double * 36), ("marginal_mean", C.c_double * 6), ("marginal_dropped", C.c_int64)]
 
 
+class CTrackerGateParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("k_median", C.c_double), ("min_px", C.c_double), ("min_detections", C.c_int32)]
+
+
+class CTrackerGateInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("gated", C.c_int32), ("n_in", C.c_int32), ("n_kept", C.c_int32), ("n_nonfinite", C.c_int32),
+                ("median", C.c_double), ("max", C.c_double), ("threshold", C.c_double)]
+
+
 class CTrackerBankStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("members", C.c_int32), ("pushes", C.c_int64), ("launches", C.c_int64), ("h2d_copies", C.c_int64),
                 ("h2d_bytes", C.c_int64), ("d2h_copies", C.c_int64), ("d2h_bytes", C.c_int64)]
@@ -478,6 +489,15 @@ def lib():
     L.aar_tracker_bank_get_stats.argtypes = [C.c_void_p, C.POINTER(CTrackerBankStats)]
     L.aar_tracker_bank_destroy.argtypes = [C.c_void_p]
     L.aar_tracker_bank_destroy.restype = None
+    L.aar_tracker_default_gate_params.argtypes = [C.POINTER(CTrackerGateParams)]
+    L.aar_tracker_default_gate_params.restype = None
+    L.aar_tracker_gate_params_validate.argtypes = [C.POINTER(CTrackerGateParams)]
+    L.aar_tracker_enable_gate.argtypes = [C.c_void_p, C.POINTER(CTrackerGateParams)]
+    L.aar_tracker_last_gate.argtypes = [C.c_void_p, C.POINTER(CTrackerGateInfo)]
+    L.aar_tracker_gate_detail.argtypes = [C.c_void_p, C.POINTER(C.c_int32), dp, u8p]
+    L.aar_tracker_gate_bank_enable.argtypes = [C.c_void_p, C.POINTER(CTrackerGateParams)]
+    L.aar_tracker_gate_bank_last.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CTrackerGateInfo)]
+    L.aar_tracker_gate_bank_detail.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), dp, u8p]
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.aar_local_group_destroy.argtypes = [C.c_void_p]
     L.aar_local_group_destroy.restype = None
@@ -973,6 +993,31 @@ def tracker_detection_params_validate(ds, **kw):
     _check(lib().aar_tracker_detection_params_validate(C.byref(c), C.byref(p)))
 
 
+def tracker_gate_params(k_median=None, min_px=None, min_detections=None, struct_size=None):
+    """aar_tracker_gate_params from Python values (None = the library's default: 6, 3, 4)"""
+    p = CTrackerGateParams()
+    lib().aar_tracker_default_gate_params(C.byref(p))
+    if k_median is not None:
+        p.k_median = float(k_median)
+    if min_px is not None:
+        p.min_px = float(min_px)
+    if min_detections is not None:
+        p.min_detections = int(min_detections)
+    if struct_size is not None:
+        p.struct_size = int(struct_size)
+    return p
+
+
+def tracker_gate_params_validate(**kw):
+    """aar_tracker_gate_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
+    p = tracker_gate_params(**kw)
+    _check(lib().aar_tracker_gate_params_validate(C.byref(p)))
+
+
+def _tracker_gate_info(g):
+    return {k: getattr(g, k) for k, _ in CTrackerGateInfo._fields_ if k != "struct_size"}
+
+
 def _tracker_result(r):
     out = {k: getattr(r, k) for k, _ in CTrackerResult._fields_ if k not in ("struct_size", "pose", "lagged_pose")}
     out["pose"] = np.array(r.pose[:])
@@ -1008,7 +1053,8 @@ class TrackerBank:
     one copy in, one launch of B workgroups, one copy out per push."""
 
     def __init__(self, solutions, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
-                 device=0, params=None, anchor="fixed", covariance=False):
+                 device=0, params=None, anchor="fixed", covariance=False, gate=None):
+        """gate: None, or a dict of tracker_gate_params' keywords: enable_gate(**gate) right after creation"""
         self.solutions = list(solutions)
         self._cds = [d.as_c() for d in self.solutions]
         arr = (C.POINTER(CDataset) * len(self._cds))(*[C.pointer(c) for c in self._cds])
@@ -1018,6 +1064,8 @@ class TrackerBank:
         _check(lib().aar_tracker_bank_create(len(self._cds), arr, C.byref(self.prm), C.byref(params) if params is not None else None,
                                              C.byref(self.handle)))
         self.size = lib().aar_tracker_bank_size(self.handle)
+        if gate is not None:
+            self.enable_gate(**gate)
 
     def close(self):
         if self.handle:
@@ -1104,6 +1152,25 @@ class TrackerBank:
     def reset(self):
         _check(lib().aar_tracker_bank_reset(self.handle))
 
+    def enable_gate(self, k_median=None, min_px=None, min_detections=None):
+        """aar_tracker_gate_bank_enable: once after creation or reset; one parameter set for all members"""
+        p = tracker_gate_params(k_median, min_px, min_detections)
+        _check(lib().aar_tracker_gate_bank_enable(self.handle, C.byref(p)))
+
+    def last_gate(self, member):
+        """aar_tracker_gate_bank_last: Tracker.last_gate() of one member"""
+        g = CTrackerGateInfo()
+        g.struct_size = C.sizeof(CTrackerGateInfo)
+        _check(lib().aar_tracker_gate_bank_last(self.handle, int(member), C.byref(g)))
+        return _tracker_gate_info(g)
+
+    def gate_detail(self, member):
+        """aar_tracker_gate_bank_detail: Tracker.gate_detail() of one member"""
+        cap = int(self.prm.max_obs_per_frame)
+        n, e, k = C.c_int32(0), np.zeros(cap), np.zeros(cap, dtype=np.uint8)
+        _check(lib().aar_tracker_gate_bank_detail(self.handle, int(member), C.byref(n), _dptr(e), _u8ptr(k)))
+        return e[:n.value].copy(), k[:n.value].copy()
+
     def stats(self, struct_size=None):
         """aar_tracker_bank_get_stats: dict(members, pushes, launches, h2d_copies, h2d_bytes, d2h_copies, d2h_bytes) counted on the host"""
         st = CTrackerBankStats()
@@ -1117,9 +1184,10 @@ class Tracker:
     roots; its frames are ignored) and fed one frame per push."""
 
     def __init__(self, ds, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
-                 device=0, params=None, anchor="fixed", covariance=False):
+                 device=0, params=None, anchor="fixed", covariance=False, gate=None):
         """params: aar_lm_params (lm_default_params(...)) or None for the defaults; anchor "fixed" | "marginal", covariance: DESIGN.md
-        section 19 (uncertainty() after a push)"""
+        section 19 (uncertainty() after a push); gate: None, or a dict of tracker_gate_params' keywords:
+        enable_gate(**gate) right after creation"""
         self.ds = ds
         self._cds = ds.as_c()
         self.prm = tracker_params(lag, smooth, sigma_rot, sigma_trans, with_huber, huber_delta, max_obs_per_frame, device, anchor=anchor,
@@ -1127,6 +1195,8 @@ class Tracker:
         self.handle = C.c_void_p()
         _check(lib().aar_tracker_create(C.byref(self._cds), C.byref(self.prm), C.byref(params) if params is not None else None,
                                         C.byref(self.handle)))
+        if gate is not None:
+            self.enable_gate(**gate)
 
     def close(self):
         if self.handle:
@@ -1197,6 +1267,25 @@ class Tracker:
         u.struct_size = C.sizeof(CTrackerUncertainty)
         _check(lib().aar_tracker_uncertainty(self.handle, C.byref(u)))
         return _tracker_uncertainty(u)
+
+    def enable_gate(self, k_median=None, min_px=None, min_detections=None):
+        """aar_tracker_enable_gate: once after creation or reset, before the first push (see tracker_gate_params)"""
+        p = tracker_gate_params(k_median, min_px, min_detections)
+        _check(lib().aar_tracker_enable_gate(self.handle, C.byref(p)))
+
+    def last_gate(self):
+        """aar_tracker_last_gate: dict(gated, n_in, n_kept, n_nonfinite, median, max, threshold) of the last accepted push"""
+        g = CTrackerGateInfo()
+        g.struct_size = C.sizeof(CTrackerGateInfo)
+        _check(lib().aar_tracker_last_gate(self.handle, C.byref(g)))
+        return _tracker_gate_info(g)
+
+    def gate_detail(self):
+        """aar_tracker_gate_detail: (e_d [n_in], keep [n_in] uint8) of the newest frame in the order it was pushed"""
+        cap = int(self.prm.max_obs_per_frame)
+        n, e, k = C.c_int32(0), np.zeros(cap), np.zeros(cap, dtype=np.uint8)
+        _check(lib().aar_tracker_gate_detail(self.handle, C.byref(n), _dptr(e), _u8ptr(k)))
+        return e[:n.value].copy(), k[:n.value].copy()
 
     def reset(self):
         _check(lib().aar_tracker_reset(self.handle))

@@ -3069,11 +3069,20 @@ struct aar_tracker {
     double *d_toroot = nullptr;      // [C][12] | [M][12]
     double *d_work = nullptr;        // poses | Tc | BJ | cost, then has2 | fin (ints): sized by max_obs_per_frame, allocated once
     std::vector<int32_t> order;      // scratch of the candidate order
+    // the gate (aar_tracker_enable_gate): a gated push refines through k_live_push_bank with this one-row member table,
+    // which reads the kept count the gate kernel left in the slot header
+    bool gate_on = false, gate_set = false;   // gate_set: gate_rec is the record of the last accepted push
+    aar_tracker_gate_params gate;
+    double gate_rec[LIVE_GATE_DOUBLES];
+    double *h_back = nullptr;        // pinned: the gate record in front of h_res (one allocation, one copy back)
+    LiveMember *d_gtab = nullptr;    // [1]
+    double *d_gerr = nullptr;        // [max_obs_per_frame] e_d of the newest frame, then its keep flags (bytes)
 };
 
 namespace {
 
-constexpr int LIVE_ST_ANCHOR = 6 * LIVE_MAX_W, LIVE_ST_EF = LIVE_ST_ANCHOR + 8, LIVE_ST_PE = LIVE_ST_EF + LIVE_MAX_W, LIVE_ST_RES = LIVE_ST_PE + LIVE_MAX_W,
+constexpr int LIVE_ST_ANCHOR = 6 * LIVE_MAX_W, LIVE_ST_EF = LIVE_ST_ANCHOR + 8, LIVE_ST_PE = LIVE_ST_EF + LIVE_MAX_W,
+              LIVE_ST_GATE = LIVE_ST_PE + LIVE_MAX_W, LIVE_ST_RES = LIVE_ST_GATE + LIVE_GATE_DOUBLES,   // (the gate record rides in FRONT of the result)
               LIVE_ST_INFO = LIVE_ST_RES + LIVE_RES_DOUBLES, LIVE_ST_UNC = LIVE_ST_INFO + LIVE_INFO_DOUBLES,
               LIVE_ST_DOUBLES = LIVE_ST_UNC + LIVE_UNC_DOUBLES;   // (the info and uncertainty records ride behind the result: one copy)
 constexpr int LIVE_DET_MAX_OBS = 4096;   // the vote is n^2 in ONE workgroup: a frame of raw detections is capped here
@@ -3148,7 +3157,9 @@ void aar_tracker_destroy(aar_tracker *t) {
     if (t->d_toroot) (void)hipFree(t->d_toroot);
     if (t->d_work) (void)hipFree(t->d_work);
     if (t->h_stage) (void)hipHostFree(t->h_stage);
-    if (t->h_res) (void)hipHostFree(t->h_res);
+    if (t->h_back) (void)hipHostFree(t->h_back);
+    if (t->d_gtab) (void)hipFree(t->d_gtab);
+    if (t->d_gerr) (void)hipFree(t->d_gerr);
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;
 }
@@ -3181,8 +3192,10 @@ int aar_tracker_create(const aar_dataset *sol, const aar_tracker_params *in, con
         hipMalloc((void **)&d_z, (size_t)6 * A * sizeof(double)) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMalloc failed"));
     if (hipHostMalloc((void **)&t->h_stage, t->slot_bytes, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&t->h_res, (LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_DOUBLES) * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        hipHostMalloc((void **)&t->h_back, (LIVE_GATE_DOUBLES + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_DOUBLES) * sizeof(double),
+                      hipHostMallocDefault) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipHostMalloc failed"));
+    t->h_res = t->h_back + LIVE_GATE_DOUBLES;
     if (hipMemsetAsync(t->d_state, 0, LIVE_ST_DOUBLES * sizeof(double), t->stream) != hipSuccess ||
         hipMemsetAsync(t->d_ring, 0, (size_t)(p.lag + 1) * t->slot_bytes, t->stream) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_create: hipMemset failed"));
@@ -3208,6 +3221,8 @@ int aar_tracker_reset(aar_tracker *t) {
     if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_reset: null argument");
     t->n = 0;
     t->det_on = false;   // (the buffers stay; aar_tracker_enable_detections fills them again)
+    t->gate_on = false;  // (likewise aar_tracker_enable_gate)
+    t->gate_set = false;
     t->unc_set = false;  // (the device's marginal stays where it is: no push reads it while has_marginal is 0)
     t->has_marginal = 0;
     t->marginal_dropped = 0;
@@ -3442,6 +3457,12 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
     if (int rc = live_check_pose_init(fn, "", pose_init)) return rc;
     HIP_TRY(hipSetDevice(t->device));
     const size_t copy_bytes = live_stage_slot(t->h_stage, t->C, raw, n_obs, obs_cam, obs_marker, obs_uv, pose_init, t->order);
+    const bool gate = t->gate_on;
+    if (gate) {   // as a bank member: the gate and the refinement read the frame's count and whether it brings a start from the header
+        double *hdr = reinterpret_cast<double *>(t->h_stage);
+        hdr[LIVE_HDR_CNT] = (double)n_obs;
+        hdr[LIVE_HDR_INIT] = pose_init ? 1.0 : 0.0;
+    }
     LiveArgs a;
     live_window_args(a, p, t->lm, n, frame_time, t->times);
     a.ent = t->d_ent; a.Kmat = t->d_K; a.ring = t->d_ring; a.slot_bytes = t->slot_bytes;
@@ -3482,18 +3503,43 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
                 return set_error(AAR_ERR_NUMERIC, "%s: no finite object pose candidate among %d, and neither a pose_init nor a previous estimate", fn, (int)h_info[1]);
         }
     }
-    launch_live_push(a, t->stream);
+    if (gate) {
+        // the gate compacts the new slot and leaves the kept count in its header; the refinement is the bank's instance on a one-row table, which
+        // reads every window frame's count from the headers (the earlier frames' were left there by their own pushes): no host wait in between
+        LiveGateArgs ga;
+        ga.slot = t->d_ring + (size_t)ns * t->slot_bytes; ga.n = n_obs; ga.has_init = a.has_init; ga.zprev = t->d_state + 6 * ps;
+        ga.ent = t->d_ent; ga.Kmat = t->d_K; ga.h = t->half_size;
+        ga.g.k_median = t->gate.k_median; ga.g.min_px = t->gate.min_px; ga.g.min_detections = t->gate.min_detections;
+        ga.rec = t->d_state + LIVE_ST_GATE; ga.det_err = t->d_gerr;
+        ga.keep = reinterpret_cast<uint8_t *>(t->d_gerr + (size_t)p.max_obs_per_frame);
+        launch_live_gate(ga, t->stream);
+        LiveBankArgs ba;
+        memset(&ba, 0, sizeof ba);
+        ba.sh = a;
+        ba.tab = t->d_gtab; ba.raw = raw ? 1 : 0; ba.fresh = n == 0 ? 1 : 0;
+        launch_live_push_bank(ba, 1, t->stream);
+    } else {
+        launch_live_push(a, t->stream);
+    }
     // one copy: the result, the start record (also when the tail's record behind it is wanted) and the uncertainty record up to the window's blocks
+    // (and, in front of the result, the gate record)
     const size_t back = tail ? LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_HDR + (p.covariance ? 36 * (size_t)W : 0)
                              : LIVE_RES_DOUBLES + (raw ? LIVE_INFO_DOUBLES : 0);
     if (tail) t->unc_set = false;   // the copy overwrites the record aar_tracker_uncertainty serves: a push that fails from here on leaves none
-    HIP_TRY(hipMemcpyAsync(t->h_res, a.res, back * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    if (gate) HIP_TRY(hipMemcpyAsync(t->h_back, t->d_state + LIVE_ST_GATE, (LIVE_GATE_DOUBLES + back) * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    else HIP_TRY(hipMemcpyAsync(t->h_res, a.res, back * sizeof(double), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     int rc = check_async("k_live_push");
     if (rc) return rc;
     // the push is accepted: the frame that leaves the window hands its slot to the new one
     t->times[ns] = frame_time;
     t->cnt[ns] = n_obs;
+    if (gate) {   // later pushes, the rows and sigma2 see the compacted frame
+        memcpy(t->gate_rec, t->h_back, sizeof t->gate_rec);
+        t->gate_set = true;
+        t->cnt[ns] = (int)t->gate_rec[2];
+        a.rows = live_rows(a, det - n_obs + t->cnt[ns], a.has_marginal);
+    }
     t->n = n + 1;
     if (tail) {
         const double *u = t->h_res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
@@ -3660,6 +3706,12 @@ struct aar_tracker_bank {
     LiveInitMember *d_itab = nullptr;
     std::vector<int32_t> order;
     aar_tracker_bank_stats stats;
+    // the gate (aar_tracker_gate_bank_enable); the members' gate records sit behind the [B][out_stride] block of d_out / h_out
+    bool gate_on = false, gate_set = false;
+    aar_tracker_gate_params gate;
+    std::vector<double> gate_rec;        // [B][LIVE_GATE_DOUBLES] of the last accepted push
+    LiveGateMember *d_gtab = nullptr;    // [B]
+    double *d_gerr = nullptr;            // [B][max_obs_per_frame] e_d of the newest frames, then [B][max_obs_per_frame] keep flags (bytes)
 };
 
 namespace {
@@ -3752,20 +3804,36 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
             }
         }
     }
+    const bool gate = k->gate_on;
+    if (gate) {
+        // every member's new slot compacted in place, the kept counts into the headers the refinement reads
+        LiveGateBankArgs ga;
+        ga.tab = k->d_gtab; ga.slot0 = new_slots; ga.slot_bytes = k->slot_bytes; ga.raw = raw ? 1 : 0; ga.prev_slot = ps;
+        ga.g.k_median = k->gate.k_median; ga.g.min_px = k->gate.min_px; ga.g.min_detections = k->gate.min_detections;
+        launch_live_gate_bank(ga, B, k->stream);
+        st.launches++;
+    }
     launch_live_push_bank(ba, B, k->stream);
     st.launches++;
     if (tail) k->unc_set = false;   // the copy overwrites the records aar_tracker_bank_uncertainty serves
-    HIP_TRY(hipMemcpyAsync(k->h_out, k->d_out, out_bytes, hipMemcpyDeviceToHost, k->stream));
-    st.d2h_copies++; st.d2h_bytes += (int64_t)out_bytes;
+    const size_t back_bytes = out_bytes + (gate ? (size_t)B * LIVE_GATE_DOUBLES * sizeof(double) : 0);   // (the gate records ride behind: one copy)
+    HIP_TRY(hipMemcpyAsync(k->h_out, k->d_out, back_bytes, hipMemcpyDeviceToHost, k->stream));
+    st.d2h_copies++; st.d2h_bytes += (int64_t)back_bytes;
     HIP_TRY(hipStreamSynchronize(k->stream));
     if (int rc = check_async("k_live_push_bank")) return rc;
     // the push is accepted
     for (int b = 0; b < B; b++) {
         aar_tracker_bank::Member &m = k->mem[b];
         const double *h = k->h_out + (size_t)b * k->out_stride;
+        int kept = n_obs[b];
+        if (gate) {   // later pushes, the rows and sigma2 see the compacted frame
+            memcpy(&k->gate_rec[(size_t)b * LIVE_GATE_DOUBLES], k->h_out + (size_t)B * k->out_stride + (size_t)b * LIVE_GATE_DOUBLES,
+                   LIVE_GATE_DOUBLES * sizeof(double));
+            kept = (int)k->gate_rec[(size_t)b * LIVE_GATE_DOUBLES + 2];
+        }
         if (tail) {
             // rows as the member's workgroup counted them (its has_marginal was the one this member held)
-            int64_t det = n_obs[b];
+            int64_t det = kept;
             for (int i = 0; i < W - 1; i++) det += m.cnt[(ba.sh.first_slot + i) % slots];
             const double rows = live_rows(ba.sh, det, marginal ? m.has_marginal : 0);
             const double *u = h + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
@@ -3773,11 +3841,12 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
             if (marginal && u[LIVE_UNC_DROP] != 0.0) m.marginal_dropped++;
             m.unc_sigma2 = live_sigma2(rows, W, h[4]);
         }
-        m.cnt[ns] = n_obs[b];
+        m.cnt[ns] = kept;
         if (results) live_fill_result(h, n, W, slots, t0, results + b);
         if (infos) live_fill_info(h + LIVE_RES_DOUBLES, infos + b);
     }
     if (tail) { k->unc_set = true; k->unc_W = W; }
+    if (gate) k->gate_set = true;
     k->times[ns] = frame_time;
     k->n = n + 1;
     st.pushes++;
@@ -3801,7 +3870,7 @@ void aar_tracker_bank_destroy(aar_tracker_bank *k) {
     if (!k) return;
     (void)hipSetDevice(k->device);
     if (k->stream) (void)hipStreamSynchronize(k->stream);
-    void *dev[] = {k->d_ent, k->d_K, k->d_state, k->d_out, k->d_ring, k->d_tab, k->d_cams, k->d_toroot, k->d_work, k->d_itab};
+    void *dev[] = {k->d_ent, k->d_K, k->d_state, k->d_out, k->d_ring, k->d_tab, k->d_cams, k->d_toroot, k->d_work, k->d_itab, k->d_gtab, k->d_gerr};
     for (void *q : dev)
         if (q) (void)hipFree(q);
     if (k->h_stage) (void)hipHostFree(k->h_stage);
@@ -3849,7 +3918,7 @@ int aar_tracker_bank_create(int32_t n_members, const aar_dataset *const *solutio
     k->slot_bytes = live_slot_bytes(p.max_obs_per_frame);
     k->out_stride = LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + (tail ? LIVE_UNC_HDR + (p.covariance ? 36 * (size_t)slots : 0) : 0);
     const size_t ring_bytes = (size_t)slots * B * k->slot_bytes, state_bytes = (size_t)B * LIVE_ST_RES * sizeof(double),
-                 out_bytes = (size_t)B * k->out_stride * sizeof(double);
+                 out_bytes = ((size_t)B * k->out_stride + (size_t)B * LIVE_GATE_DOUBLES) * sizeof(double);   // (behind the records: the gate's)
     double *d_z = nullptr;
     auto fail = [&](int code) { if (d_z) (void)hipFree(d_z); aar_tracker_bank_destroy(k); return code; };
     if (hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipStreamCreate failed"));
@@ -3900,6 +3969,8 @@ int aar_tracker_bank_reset(aar_tracker_bank *k) {
     if (!k) return set_error(AAR_ERR_INVALID, "aar_tracker_bank_reset: null argument");
     k->n = 0;
     k->det_on = false;   // (the buffers stay; aar_tracker_bank_enable_detections fills them again)
+    k->gate_on = false;  // (likewise aar_tracker_gate_bank_enable)
+    k->gate_set = false;
     k->unc_set = false;  // (the device's marginals stay where they are: the first push of a bank reads none)
     for (auto &m : k->mem) { m.has_marginal = 0; m.marginal_dropped = 0; }
     return AAR_OK;
@@ -4005,6 +4076,174 @@ int aar_tracker_bank_get_stats(const aar_tracker_bank *k, aar_tracker_bank_stats
     st.struct_size = (uint32_t)std::min(cap, sizeof st);
     memcpy(out, &st, std::min(cap, sizeof st));
     return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The gate of the live trackers (live_gate_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+int gate_params_check(const aar_tracker_gate_params *in, aar_tracker_gate_params *p) {
+    aar_tracker_default_gate_params(p);
+    if (in->struct_size < offsetof(aar_tracker_gate_params, min_detections) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_gate_params: struct_size %u does not reach min_detections", (unsigned)in->struct_size);
+    memcpy(p, in, std::min<size_t>(in->struct_size, sizeof *p));
+    p->struct_size = (uint32_t)sizeof *p;
+    if (!std::isfinite(p->min_px) || p->min_px < 0.0) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_params: min_px = %g must be finite and not negative", p->min_px);
+    if (!std::isfinite(p->k_median)) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_params: k_median = %g must be finite", p->k_median);
+    if (p->k_median <= 0.0 && p->min_px <= 0.0)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_gate_params: k_median = %g and min_px = %g are both <= 0: no threshold", p->k_median, p->min_px);
+    if (p->min_detections < 1) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_params: min_detections = %d must be at least 1", (int)p->min_detections);
+    return AAR_OK;
+}
+
+int gate_fill_info(const char *fn, const double *rec, aar_tracker_gate_info *out) {
+    if (out->struct_size < offsetof(aar_tracker_gate_info, gated) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "%s: struct_size %u does not reach gated", fn, (unsigned)out->struct_size);
+    aar_tracker_gate_info r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof r);
+    r.gated = (int32_t)rec[0]; r.n_in = (int32_t)rec[1]; r.n_kept = (int32_t)rec[2]; r.n_nonfinite = (int32_t)rec[3];
+    r.median = rec[4]; r.max = rec[5]; r.threshold = rec[6];
+    memcpy(out, &r, r.struct_size);
+    return AAR_OK;
+}
+
+// e_d and the keep flags of a newest frame of n detections: the second copy, made only here
+int gate_detail_out(const char *fn, hipStream_t stream, const double *d_err, const uint8_t *d_keep, int n, int32_t *n_out, double *det_err, uint8_t *keep) {
+    if (n_out) *n_out = n;
+    const char *what = "";
+    if (n > 0 && det_err && d2h(det_err, d_err, (size_t)n * sizeof(double), stream, &what)) return set_error(AAR_ERR_HIP, "%s: %s failed", fn, what);
+    if (n > 0 && keep && d2h(keep, d_keep, (size_t)n, stream, &what)) return set_error(AAR_ERR_HIP, "%s: %s failed", fn, what);
+    return AAR_OK;
+}
+
+}  // namespace
+
+void aar_tracker_default_gate_params(aar_tracker_gate_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof *p;
+    p->k_median = 6.0;
+    p->min_px = 3.0;
+    p->min_detections = 4;
+}
+
+int aar_tracker_gate_params_validate(const aar_tracker_gate_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_params_validate: null argument");
+    aar_tracker_gate_params p;
+    return gate_params_check(in, &p);
+}
+
+int aar_tracker_enable_gate(aar_tracker *t, const aar_tracker_gate_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_gate: null argument");
+    aar_tracker_gate_params p;
+    if (int rc = gate_params_check(in, &p)) return rc;
+    if (!t) {   // no tracker exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_tracker_enable_gate: null tracker");
+    }
+    if (t->gate_on) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_gate: already enabled (aar_tracker_reset first)");
+    if (t->n != 0) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_gate: call it after aar_tracker_create or aar_tracker_reset, before the first push");
+    if (t->prm.max_obs_per_frame > LIVE_GATE_MAX_OBS)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_tracker_enable_gate: max_obs_per_frame = %d is above %d (the median sorts the frame in one workgroup)",
+                         (int)t->prm.max_obs_per_frame, LIVE_GATE_MAX_OBS);
+    HIP_TRY(hipSetDevice(t->device));
+    const size_t mo = (size_t)t->prm.max_obs_per_frame;
+    if (!t->d_gerr) HIP_TRY(hipMalloc((void **)&t->d_gerr, mo * sizeof(double) + mo));
+    if (!t->d_gtab) {
+        HIP_TRY(hipMalloc((void **)&t->d_gtab, sizeof(LiveMember)));
+        // the tracker as the one member of a bank: the same state, the records where the single tracker's kernels leave them
+        LiveMember r;
+        r.ent = t->d_ent; r.Kmat = t->d_K; r.h = t->half_size; r.ring = t->d_ring;
+        r.zslot = t->d_state; r.anchor = t->d_state + LIVE_ST_ANCHOR; r.Ef = t->d_state + LIVE_ST_EF; r.Pe = t->d_state + LIVE_ST_PE;
+        r.res = t->d_state + LIVE_ST_RES; r.unc = t->d_state + LIVE_ST_UNC;
+        const char *what = "";
+        if (h2d(t->d_gtab, &r, sizeof r, t->stream, &what)) return set_error(AAR_ERR_HIP, "aar_tracker_enable_gate: %s failed", what);
+        HIP_TRY(hipStreamSynchronize(t->stream));
+    }
+    t->gate = p;
+    t->gate_on = true;
+    t->gate_set = false;
+    return AAR_OK;
+}
+
+int aar_tracker_last_gate(aar_tracker *t, aar_tracker_gate_info *out) {
+    if (!t || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_last_gate: null argument");
+    if (!t->gate_on) return set_error(AAR_ERR_INVALID, "aar_tracker_last_gate: the tracker has no gate (aar_tracker_enable_gate)");
+    if (!t->gate_set || t->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_last_gate: no push since creation / reset");
+    return gate_fill_info("aar_tracker_last_gate", t->gate_rec, out);
+}
+
+int aar_tracker_gate_detail(aar_tracker *t, int32_t *n, double *det_err, uint8_t *keep) {
+    if (!t) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_detail: null argument");
+    if (!t->gate_on) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_detail: the tracker has no gate (aar_tracker_enable_gate)");
+    if (!t->gate_set || t->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_detail: no push since creation / reset");
+    HIP_TRY(hipSetDevice(t->device));
+    return gate_detail_out("aar_tracker_gate_detail", t->stream, t->d_gerr, reinterpret_cast<const uint8_t *>(t->d_gerr + (size_t)t->prm.max_obs_per_frame),
+                           (int)t->gate_rec[1], n, det_err, keep);
+}
+
+int aar_tracker_gate_bank_enable(aar_tracker_bank *k, const aar_tracker_gate_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_enable: null argument");
+    aar_tracker_gate_params p;
+    if (int rc = gate_params_check(in, &p)) return rc;
+    if (!k) {   // no bank exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_enable: null bank");
+    }
+    if (k->gate_on) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_enable: already enabled (aar_tracker_bank_reset first)");
+    if (k->n != 0)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_enable: call it after aar_tracker_bank_create or aar_tracker_bank_reset, before the first push");
+    if (k->prm.max_obs_per_frame > LIVE_GATE_MAX_OBS)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_tracker_gate_bank_enable: max_obs_per_frame = %d is above %d (a member's median sorts its frame in one workgroup)",
+                         (int)k->prm.max_obs_per_frame, LIVE_GATE_MAX_OBS);
+    HIP_TRY(hipSetDevice(k->device));
+    const int B = k->B;
+    const size_t mo = (size_t)k->prm.max_obs_per_frame;
+    if (!k->d_gerr) HIP_TRY(hipMalloc((void **)&k->d_gerr, (size_t)B * (mo * sizeof(double) + mo)));
+    if (!k->d_gtab) {
+        HIP_TRY(hipMalloc((void **)&k->d_gtab, (size_t)B * sizeof(LiveGateMember)));
+        std::vector<LiveGateMember> tab((size_t)B);
+        for (int b = 0; b < B; b++) {
+            const aar_tracker_bank::Member &m = k->mem[b];
+            LiveGateMember &r = tab[b];
+            r.ent = k->d_ent + m.ent0 * ENT_STRIDE; r.Kmat = k->d_K + 9 * m.cam0; r.h = m.half_size;
+            r.zslot = k->d_state + (size_t)b * LIVE_ST_RES;
+            r.rec = k->d_out + (size_t)B * k->out_stride + (size_t)b * LIVE_GATE_DOUBLES;
+            r.det_err = k->d_gerr + (size_t)b * mo;
+            r.keep = reinterpret_cast<uint8_t *>(k->d_gerr + (size_t)B * mo) + (size_t)b * mo;
+        }
+        const char *what = "";
+        if (h2d(k->d_gtab, tab.data(), tab.size() * sizeof(LiveGateMember), k->stream, &what))
+            return set_error(AAR_ERR_HIP, "aar_tracker_gate_bank_enable: %s failed", what);
+        HIP_TRY(hipStreamSynchronize(k->stream));
+    }
+    k->gate_rec.assign((size_t)B * LIVE_GATE_DOUBLES, 0.0);
+    k->gate = p;
+    k->gate_on = true;
+    k->gate_set = false;
+    return AAR_OK;
+}
+
+int aar_tracker_gate_bank_last(aar_tracker_bank *k, int32_t member, aar_tracker_gate_info *out) {
+    if (!k || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_last: null argument");
+    if (member < 0 || member >= k->B) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_last: member = %d is outside 0 .. %d", (int)member, k->B - 1);
+    if (!k->gate_on) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_last: the bank has no gate (aar_tracker_gate_bank_enable)");
+    if (!k->gate_set || k->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_last: no push since creation / reset");
+    return gate_fill_info("aar_tracker_gate_bank_last", &k->gate_rec[(size_t)member * LIVE_GATE_DOUBLES], out);
+}
+
+int aar_tracker_gate_bank_detail(aar_tracker_bank *k, int32_t member, int32_t *n, double *det_err, uint8_t *keep) {
+    if (!k) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_detail: null argument");
+    if (member < 0 || member >= k->B) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_detail: member = %d is outside 0 .. %d", (int)member, k->B - 1);
+    if (!k->gate_on) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_detail: the bank has no gate (aar_tracker_gate_bank_enable)");
+    if (!k->gate_set || k->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_gate_bank_detail: no push since creation / reset");
+    HIP_TRY(hipSetDevice(k->device));
+    const size_t mo = (size_t)k->prm.max_obs_per_frame;
+    return gate_detail_out("aar_tracker_gate_bank_detail", k->stream, k->d_gerr + (size_t)member * mo,
+                           reinterpret_cast<const uint8_t *>(k->d_gerr + (size_t)k->B * mo) + (size_t)member * mo,
+                           (int)k->gate_rec[(size_t)member * LIVE_GATE_DOUBLES + 1], n, det_err, keep);
 }
 
 }  // extern "C"

@@ -429,6 +429,38 @@ struct LiveInitBankArgs {
 };
 void launch_live_init_bank(const LiveInitBankArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
 
+// the gate of a pushed frame (live_gate_kernels.hip): aar_outlier_rule on the NEW frame at the pose the push starts from,
+// the slot's records compacted in place and the kept count written into the header's LIVE_HDR_CNT -- ONE launch between start and refinement
+constexpr int LIVE_GATE_MAX_OBS = 4096;   // the exact median sorts the frame's errors in one workgroup's LDS
+constexpr int LIVE_GATE_DOUBLES = 8;      // the gate record: gated, n_in, n_kept, n_nonfinite, median, max, threshold, 0
+struct LiveGateParams {
+    double k_median, min_px;
+    int min_detections;
+};
+struct LiveGateArgs {
+    char *slot;                           // header | n records
+    int n, has_init;                      // has_init: the start pose is the header's (pose_init, or k_live_init's choice), else zprev
+    const double *zprev;                  // [6] the previous frame's estimate
+    const double *ent, *Kmat; double h;   // k_live_push's model
+    LiveGateParams g;
+    double *rec;                          // [LIVE_GATE_DOUBLES]
+    double *det_err; uint8_t *keep;       // [max_obs] each, in the caller's order
+};
+void launch_live_gate(const LiveGateArgs &a, hipStream_t st);   // ONE launch
+struct LiveGateMember {                   // one row of the table, written at aar_tracker_gate_bank_enable
+    const double *ent, *Kmat; double h;
+    const double *zslot;                  // the member's poses by ring slot
+    double *rec, *det_err; uint8_t *keep;
+};
+struct LiveGateBankArgs {
+    const LiveGateMember *tab;            // [B]
+    char *slot0;                          // the new slot of member 0; member b's follows at b slot_bytes
+    size_t slot_bytes;
+    int raw, prev_slot;                   // raw: k_live_init_bank wrote every header's start pose; the previous frame's ring slot
+    LiveGateParams g;
+};
+void launch_live_gate_bank(const LiveGateBankArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
+
 // covariance (cov_kernels.hip): S (stride n_pad) -> S2 (stride n2 >= n_pad, zero beyond n_pad), rows with rowmask set -> identity
 void launch_cov_stage(const double *S, int n_pad, double *S2, int n2, const int32_t *rowmask, hipStream_t st);
 // the LDL^T factor launch_chol left for S2 (nT2 tiles, fused_m = the panel rule it ran with) -> Sinv = S^-1, lower 32 x 32 tiles of the first

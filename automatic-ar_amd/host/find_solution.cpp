@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -265,8 +265,13 @@ int main(int argc, char *argv[]) {
     int live_anchor = AAR_TRACKER_ANCHOR_FIXED;
     bool live_anchor_set = false, live_covariance = false;
     double live_sigma[2] = {0.0, 0.0};
+    // ... -gate <k_median> <min_px> gates every pushed frame on the device with the batch path's outlier rule (-reject-outliers / -reject-min-px)
+    // at the pose the push starts from; one of the two may be 0
+    bool live_gate = false;
+    int gate_args = 0;
+    double gate_v[2] = {0.0, 0.0};
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Live, Anchor } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Live, Anchor, Gate } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -293,6 +298,14 @@ int main(int argc, char *argv[]) {
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
+        else if (a == "-gate") { live_gate = true; gate_args = 0; arg_flag = Gate; }
+        else if (arg_flag == Gate) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || a.empty() || !(v >= 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            gate_v[gate_args++] = v;
+            if (gate_args == 2) arg_flag = NONE;
+        }
         else if (arg_flag == Anchor) {
             if (a != "fixed" && a != "marginal") return print_usage(argv[0]);
             live_anchor = a == "marginal" ? AAR_TRACKER_ANCHOR_MARGINAL : AAR_TRACKER_ANCHOR_FIXED;
@@ -368,6 +381,7 @@ int main(int argc, char *argv[]) {
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
+    if (live_gate && (!live || gate_args != 2 || (gate_v[0] <= 0.0 && gate_v[1] <= 0.0))) return print_usage(argv[0]);
     if (from_detections && (!live || from_initial || use_subseqs || !excluded_cams.empty())) return print_usage(argv[0]);
     string name = "";
     if (tracking_only) name += "_tracking_only";
@@ -476,18 +490,23 @@ int main(int argc, char *argv[]) {
     if (live) {
         aar::MultiCamMapper::LiveCovariance live_cov;
         aar::MultiCamMapper::LiveCovariance *want_cov = live_covariance ? &live_cov : nullptr;
+        aar_tracker_gate_params gate_params;
+        aar_tracker_default_gate_params(&gate_params);
+        gate_params.k_median = gate_v[0];
+        gate_params.min_px = gate_v[1];
+        const aar_tracker_gate_params *want_gate = live_gate ? &gate_params : nullptr;
         try {
             if (from_detections) {
                 aar_detections *detections = aar::Initializer::read_detections_file(folder_path + "/aruco.detections", vector<int>());
                 try {
-                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy, live_anchor, want_cov);
+                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy, live_anchor, want_cov, want_gate);
                 } catch (...) {
                     aar_detections_free(detections);
                     throw;
                 }
                 aar_detections_free(detections);
             } else {
-                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1], live_anchor, want_cov);
+                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1], live_anchor, want_cov, want_gate);
             }
             long long its = 0, rej = 0;
             double sec = 0, cost = 0;
@@ -498,6 +517,12 @@ int main(int argc, char *argv[]) {
                 long long held = 0, won = 0;
                 for (const aar_tracker_start_info &si : mcm.live_starts) { held += si.voted; won += si.start_source == 2; }
                 cout << "votes: " << held << " held, " << won << " won (start policy " << (start_policy == AAR_TRACKER_START_BEST ? "best" : "vote") << ")" << endl;
+            }
+            if (live_gate) {
+                long long rejected = 0, frames = 0, small = 0;
+                for (const aar_tracker_gate_info &g : mcm.live_gates) { rejected += g.n_in - g.n_kept; frames += g.n_kept < g.n_in; small += !g.gated; }
+                cout << "gate: " << rejected << " detections rejected in " << frames << " frames (k_median " << gate_v[0] << ", min_px " << gate_v[1] << "; "
+                     << small << " frames below min_detections = " << gate_params.min_detections << " were not gated)" << endl;
             }
         } catch (const exception &e) {
             cerr << "live tracking failed: " << e.what() << endl;

@@ -604,6 +604,13 @@ void take_live_covariance(LiveTracker &lt, MultiCamMapper::LiveCovariance *cov) 
         cov->valid[f] = u.cov_valid ? 1 : 0;
     }
 }
+// the gate on (gate != NULL), and room for every frame's record
+void start_live_gate(LiveTracker &lt, const aar_tracker_gate_params *gate, int F, std::vector<aar_tracker_gate_info> &out) {
+    out.clear();
+    if (!gate) return;
+    lt.enable_gate(gate);
+    out.assign((size_t)F, aar_tracker_gate_info());
+}
 void size_live_covariance(MultiCamMapper::LiveCovariance *cov, int F) {
     if (!cov) return;
     cov->frame_cov.assign(36 * (size_t)F, 0.0);
@@ -612,7 +619,8 @@ void size_live_covariance(MultiCamMapper::LiveCovariance *cov, int F) {
 }
 }  // namespace
 
-void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double sigma_trans, int anchor_mode, LiveCovariance *covariance) {
+void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double sigma_trans, int anchor_mode, LiveCovariance *covariance,
+                                const aar_tracker_gate_params *gate) {
     if (!data_) throw std::runtime_error("MultiCamMapper::track_live: no data set");
     hubberDelta = 10;  // as track()
     const int F = data_->num_frames;
@@ -626,6 +634,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
     o.anchor_mode = anchor_mode; o.covariance = covariance != nullptr;
     LiveTracker lt(*this, o, &solver_params);
     size_live_covariance(covariance, F);
+    start_live_gate(lt, gate, F, live_gates);
     PoseLayout L;
     L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
     std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
@@ -642,6 +651,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
         }
         const aar_tracker_result r = lt.push((double)data_->frame_ids[f], det, data_->x_full + L.full_fr0() + 6LL * f);
         live_results[f] = r;
+        if (gate) live_gates[f] = lt.last_gate();
         take_live_covariance(lt, covariance);
         if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
     }
@@ -652,7 +662,8 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
 }
 
 void MultiCamMapper::track_live_from_detections(const aar_detections *det, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
-                                                double sigma_trans, int start_policy, int anchor_mode, LiveCovariance *covariance) {
+                                                double sigma_trans, int start_policy, int anchor_mode, LiveCovariance *covariance,
+                                                const aar_tracker_gate_params *gate) {
     if (!data_ || !det) throw std::runtime_error("MultiCamMapper::track_live_from_detections: no data set / no detections");
     hubberDelta = 10;  // as track()
     const int F = data_->num_frames;
@@ -678,6 +689,7 @@ void MultiCamMapper::track_live_from_detections(const aar_detections *det, const
     }
     dopt.start_policy = start_policy;
     lt.enable_detections(dopt);
+    start_live_gate(lt, gate, F, live_gates);
     PoseLayout L;
     L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
     std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
@@ -697,6 +709,7 @@ void MultiCamMapper::track_live_from_detections(const aar_detections *det, const
             }
         const aar_tracker_result r = lt.push_detections((double)data_->frame_ids[f], dets, nullptr, &live_starts[f]);
         live_results[f] = r;
+        if (gate) live_gates[f] = lt.last_gate();
         take_live_covariance(lt, covariance);
         if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
     }
@@ -832,6 +845,28 @@ aar_tracker_result LiveTracker::push_detections(double frame_time, const std::ve
     return r;
 }
 
+void LiveTracker::enable_gate(const aar_tracker_gate_params *params) {
+    aar_tracker_gate_params p;
+    aar_tracker_default_gate_params(&p);
+    if (aar_tracker_enable_gate(tracker_, params ? params : &p)) throw std::runtime_error(aar_last_error());
+}
+
+aar_tracker_gate_info LiveTracker::last_gate() {
+    aar_tracker_gate_info g;
+    memset(&g, 0, sizeof g);
+    g.struct_size = sizeof g;
+    if (aar_tracker_last_gate(tracker_, &g)) throw std::runtime_error(aar_last_error());
+    return g;
+}
+
+void LiveTracker::gate_detail(std::vector<double> &det_err, std::vector<uint8_t> &keep) {
+    const aar_tracker_gate_info g = last_gate();
+    det_err.assign((size_t)g.n_in, 0.0);
+    keep.assign((size_t)g.n_in, 0);
+    int32_t n = 0;
+    if (aar_tracker_gate_detail(tracker_, &n, det_err.data(), keep.data())) throw std::runtime_error(aar_last_error());
+}
+
 LiveTracker::Window LiveTracker::window() {
     int32_t n = 0, has = 0;
     int64_t idx[AAR_TRACKER_MAX_LAG + 1];
@@ -927,6 +962,28 @@ std::vector<aar_tracker_result> LiveTrackerBank::push_detections(double frame_ti
                                          any_start_ ? has_start_.data() : nullptr, r.data(), infos ? infos->data() : nullptr))
         throw std::runtime_error(aar_last_error());
     return r;
+}
+
+void LiveTrackerBank::enable_gate(const aar_tracker_gate_params *params) {
+    aar_tracker_gate_params p;
+    aar_tracker_default_gate_params(&p);
+    if (aar_tracker_gate_bank_enable(bank_, params ? params : &p)) throw std::runtime_error(aar_last_error());
+}
+
+aar_tracker_gate_info LiveTrackerBank::last_gate(int member) {
+    aar_tracker_gate_info g;
+    memset(&g, 0, sizeof g);
+    g.struct_size = sizeof g;
+    if (aar_tracker_gate_bank_last(bank_, member, &g)) throw std::runtime_error(aar_last_error());
+    return g;
+}
+
+void LiveTrackerBank::gate_detail(int member, std::vector<double> &det_err, std::vector<uint8_t> &keep) {
+    const aar_tracker_gate_info g = last_gate(member);
+    det_err.assign((size_t)g.n_in, 0.0);
+    keep.assign((size_t)g.n_in, 0);
+    int32_t n = 0;
+    if (aar_tracker_gate_bank_detail(bank_, member, &n, det_err.data(), keep.data())) throw std::runtime_error(aar_last_error());
 }
 
 LiveTracker::Window LiveTrackerBank::window(int member) {

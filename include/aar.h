@@ -657,7 +657,7 @@ int aar_tracker_push(aar_tracker *, double frame_time, int32_t n_obs, const int3
  * cost of the pair that ENDS at the frame (entry 0: the anchor pair, 0 without an anchor), anchor_pose, has_anchor.  Any output may be NULL. */
 int aar_tracker_window(aar_tracker *, int32_t *n, int64_t *frame_index, double *poses, double *frame_err, double *pair_err, double anchor_pose[6],
                        int32_t *has_anchor);
-int aar_tracker_reset(aar_tracker *);     /* forgets all frames, the marginal prior (and aar_tracker_enable_detections), keeps the solution */
+int aar_tracker_reset(aar_tracker *);     /* forgets all frames, the marginal prior (and aar_tracker_enable_detections / _enable_gate), keeps the solution */
 
 /* Marginalised anchor and per-push pose covariance.  Both are off by default, and then a push runs the same kernel and
  * gives the same bits as before they existed; with either set a push is still one launch and one copy back.
@@ -824,6 +824,54 @@ int aar_reproj_stats(aar_problem *, const double *x_full, double *rmse, double *
 
 int aar_device_count(void);
 int aar_device_synchronize(void);
+
+/* The gate of the live trackers: aar_outlier_rule of the residual report above, applied on the device to the NEW frame of
+ * every push, as ONE extra launch between the frame's start and its refinement.  Definitions, word for word those of the residual report:
+ *   start pose  z0 = the pose the push starts from: the caller's pose_init, else what the start kernel wrote (the vote's winner, or the choice of
+ *               AAR_TRACKER_START_BEST), else the previous frame's current estimate
+ *   e_d         sqrt((sum over the 4 corners of rx^2 + ry^2) / 4) in pixels at z0: fp64, summed in corner order, UNWEIGHTED (Huber is ignored),
+ *               the tracker's double residuals
+ *   median      the exact lower median (element floor((n-1)/2) of the ascending order), max the exact maximum; a non-finite e_d sorts above
+ *               every finite one (and reads as +inf in median / max)
+ *   threshold   t = max(min_px, k_median * median) in fp64; k_median <= 0: t = min_px
+ *   kept        iff e_d <= t, so a non-finite e_d never is
+ * A frame of fewer than min_detections detections is not gated: everything is kept, gated = 0, threshold = +inf.  The kept detections stay in
+ * the caller's order; the refinement, aar_tracker_result.final_data_cost, the window's frame_err and the rows all see the kept detections only,
+ * with the bits an ungated tracker gives when the caller leaves the rejected detections out.  A gate that keeps nothing is legal: the frame
+ * then is a push with n_obs = 0.  AAR_TRACKER_START_BEST evaluates its two starts on ALL detections: the start kernel runs before the gate.
+ * A gated push is the ungated push's launches plus one; still one copy in and one copy out, and no host wait in between (except, as before,
+ * on a first raw push without pose_init).  max_obs_per_frame above 4096 with the gate is AAR_ERR_UNSUPPORTED (the median sorts the frame in
+ * one workgroup). */
+typedef struct aar_tracker_gate_params {
+    uint32_t struct_size;
+    double k_median;             /* t = max(min_px, k_median * median); <= 0: t = min_px */
+    double min_px;
+    int32_t min_detections;      /* frames with fewer detections are not gated */
+} aar_tracker_gate_params;
+typedef struct aar_tracker_gate_info {
+    uint32_t struct_size;
+    int32_t gated;               /* 0: the frame had fewer than min_detections detections, everything was kept */
+    int32_t n_in, n_kept, n_nonfinite;
+    double median, max, threshold;
+} aar_tracker_gate_info;
+void aar_tracker_default_gate_params(aar_tracker_gate_params *);   /* struct_size set; k_median 6, min_px 3, min_detections 4 (choices) */
+/* Host function (no device needed): AAR_ERR_INVALID, the message naming the field, for a struct_size that does not reach min_detections, a
+ * non-finite or negative min_px, a non-finite k_median, k_median and min_px both <= 0, min_detections < 1. */
+int aar_tracker_gate_params_validate(const aar_tracker_gate_params *);
+/* Once after aar_tracker_create or aar_tracker_reset, before the first push; again without a reset, or after a push: AAR_ERR_INVALID.
+ * aar_tracker_reset forgets it.  Independent of aar_tracker_enable_detections; gates aar_tracker_push and aar_tracker_push_detections alike. */
+int aar_tracker_enable_gate(aar_tracker *, const aar_tracker_gate_params *);
+/* The gate record of the last accepted push, from its one copy back (no device work).  AAR_ERR_INVALID before any push, after a reset, or
+ * without a gate. */
+int aar_tracker_last_gate(aar_tracker *, aar_tracker_gate_info *out);
+/* e_d and the keep flags of the newest frame in the order the caller pushed them: *n = n_in, det_err / keep: room for max_obs_per_frame
+ * entries, either may be NULL.  The one call that makes a second device -> host copy. */
+int aar_tracker_gate_detail(aar_tracker *, int32_t *n, double *det_err, uint8_t *keep);
+/* The same for a bank (aar_tracker_bank_*): one parameter set for all members; the gate is ONE launch of B workgroups per push.  (The three are
+ * named aar_tracker_gate_bank_*: the set of aar_tracker_bank_* symbols is pinned by tests/test_live_bank_host.py.) */
+int aar_tracker_gate_bank_enable(aar_tracker_bank *, const aar_tracker_gate_params *);
+int aar_tracker_gate_bank_last(aar_tracker_bank *, int32_t member, aar_tracker_gate_info *out);
+int aar_tracker_gate_bank_detail(aar_tracker_bank *, int32_t member, int32_t *n, double *det_err, uint8_t *keep);
 
 #ifdef __cplusplus
 }

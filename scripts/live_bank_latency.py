@@ -8,6 +8,9 @@ Not part of bench.py.  Run on the MI355X:
 Every member tracks the object of config 3's tracking version; member b is fed the recording shifted by 7 b frames, so that the members' inputs
 differ.  Times are taken around the library calls alone (the arrays are laid out beforehand).  The script's one condition, checked at the end:
 at B = 8 the median bank push lies below the median of the eight sequential pushes together.
+
+    python scripts/live_bank_latency.py --gate      # a second, gated bank pushed beside the ungated one, push by push
+                                                    # (same build, same frames, interleaved); prints the added time per push
 """
 import argparse
 import ctypes as C
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--members", type=int, nargs="+", default=[1, 8, 64, 256])
     ap.add_argument("--pushes", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--gate", action="store_true", help="also push a gated bank (k_median 6, min_px 3), interleaved with the ungated one")
     a = ap.parse_args()
     n, w = a.pushes + a.warmup, a.warmup
     ds = aar.synth(3, num_frames=n)
@@ -60,16 +64,23 @@ def main():
         for B in a.members:
             src = [[(f + 7 * b) % n for b in range(B)] for f in range(n)]           # the recording's frame member b is fed at push f
             # ---- the bank ----
-            wall = []
-            with aar.TrackerBank([sol] * B, max_obs_per_frame=most, **kw) as k:
-                res = k.result_array()
+            wall, gwall = [], []
+            with aar.TrackerBank([sol] * B, max_obs_per_frame=most, **kw) as k, \
+                    aar.TrackerBank([sol] * (B if a.gate else 1), max_obs_per_frame=most, gate={} if a.gate else None, **kw) as kg:
+                res, gres = k.result_array(), kg.result_array()
                 for f in range(n):
                     args, keep = k.pack([obs[s] for s in src[f]], [z0[s] for s in src[f]])
                     t0 = time.perf_counter()
                     rc = L.aar_tracker_bank_push(k.handle, float(f), *args, res)
                     wall.append(time.perf_counter() - t0)
                     assert rc == 0, L.aar_last_error()
+                    if a.gate:
+                        t0 = time.perf_counter()
+                        rc = L.aar_tracker_bank_push(kg.handle, float(f), *args, gres)
+                        gwall.append(time.perf_counter() - t0)
+                        assert rc == 0, L.aar_last_error()
                 st = k.stats()
+                gst = kg.stats()
                 its = np.mean([r.iterations for r in res])
             # ---- what the parent offers: B trackers pushed one after the other ----
             seq = []
@@ -97,6 +108,9 @@ def main():
                   "launches per push %.0f   %.1f LM iterations at the last push" % (
                       B, stats(wall[w:]), B, stats(seq[w:]), ms / mb, st["h2d_bytes"] // st["pushes"], st["d2h_bytes"] // st["pushes"],
                       st["launches"] / st["pushes"], its))
+            if a.gate:
+                print("  B %4d   + gate    %s   gate adds %.1f us per push (difference of the medians)   copied out %d bytes   launches per push %.0f" % (
+                    B, stats(gwall[w:]), 1e6 * (np.median(gwall[w:]) - mb), gst["d2h_bytes"] // gst["pushes"], gst["launches"] / gst["pushes"]))
     ok = all(medians[(label, 8)][0] < medians[(label, 8)][1] for label, B in medians if B == 8)
     print("condition (B = 8: bank push median below the eight sequential pushes together): %s" % ("met" if ok else "NOT MET"))
     return 0 if ok else 1

@@ -8,6 +8,9 @@ Not part of bench.py.  Run on the MI355X:
 
 Every push is ONE launch of k_live_push (aar_tracker_push issues nothing else); the script prints the number of pushes it made, the kernel
 trace's call count of k_live_push must equal it.
+
+    python scripts/live_latency.py --gate       # every tracker a second time with the gate on, push by push beside the
+                                                # ungated one (same build, same frames, interleaved); prints the added time per push
 """
 import argparse
 import os
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--configs", type=int, nargs="+", default=[3, 5])
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--gate", action="store_true", help="also run every tracker gated (k_median 6, min_px 3), interleaved with the ungated one")
     a = ap.parse_args()
     n = a.pushes + a.warmup
     total = total_det = 0
@@ -77,7 +81,8 @@ def main():
             if kw["smooth"]:
                 kw.update(sigma_rot=0.05, sigma_trans=0.02)
             wall, lib, its = [], [], []
-            with aar.Tracker(sol, max_obs_per_frame=most, **kw) as t:
+            gwall, kept = [], []
+            with aar.Tracker(sol, max_obs_per_frame=most, **kw) as t, aar.Tracker(sol, max_obs_per_frame=most, gate={} if a.gate else None, **kw) as tg:
                 for f in range(n):
                     t0 = time.perf_counter()
                     g = t.push(float(f), *obs[f], pose_init=z0[f])
@@ -85,8 +90,16 @@ def main():
                     lib.append(g["seconds"])
                     its.append(g["iterations"])
                     total += 1
+                    if a.gate:
+                        t0 = time.perf_counter()
+                        tg.push(float(f), *obs[f], pose_init=z0[f])
+                        gwall.append(time.perf_counter() - t0)
+                        kept.append(tg.last_gate()["n_kept"] / max(len(obs[f][0]), 1))
             w = a.warmup
             print("  %-16s push %s   inside the library %s   %.1f LM iterations per push" % (label, stats(wall[w:]), stats(lib[w:]), np.mean(its[w:])))
+            if a.gate:
+                print("  %-16s push %s   gate adds %.1f us per push (difference of the medians), %.1f%% of the detections kept" % (
+                    "  + gate", stats(gwall[w:]), 1e6 * (np.median(gwall[w:]) - np.median(wall[w:])), 100 * np.mean(kept[w:])))
         frames = [one_frame(ds, f, x0) for f in range(n)]
         wall, its = [], []
         prm = aar.lm_default_params()
@@ -102,9 +115,10 @@ def main():
         # one-frame detection set with the map fixed (aar_initializer_object_poses) followed by aar_tracker_push from its pose
         K = ds.cam_mats.reshape(-1, 3, 3)
         dists = [np.zeros(5)] * ds.num_cams
-        wall, its, cands = [], [], []
-        with aar.Tracker(sol, max_obs_per_frame=most) as t:
+        wall, its, cands, gwall = [], [], [], []
+        with aar.Tracker(sol, max_obs_per_frame=most) as t, aar.Tracker(sol, max_obs_per_frame=most, gate={} if a.gate else None) as tg:
             t.enable_detections(Ks=K, dists=dists, start_policy="vote")
+            tg.enable_detections(Ks=K, dists=dists, start_policy="vote")
             for f in range(n):
                 t0 = time.perf_counter()
                 g, info = t.push_detections(float(f), *obs[f])
@@ -112,8 +126,15 @@ def main():
                 its.append(g["iterations"])
                 cands.append(info["candidates"])
                 total_det += 1
+                if a.gate:
+                    t0 = time.perf_counter()
+                    tg.push_detections(float(f), *obs[f])
+                    gwall.append(time.perf_counter() - t0)
         w = a.warmup
         print("  %-16s push %s   %.1f candidates, %.1f LM iterations per push" % ("detections vote", stats(wall[w:]), np.mean(cands[w:]), np.mean(its[w:])))
+        if a.gate:
+            print("  %-16s push %s   gate adds %.1f us per push (difference of the medians)" % (
+                "  + gate", stats(gwall[w:]), 1e6 * (np.median(gwall[w:]) - np.median(wall[w:]))))
         wall, its = [], []
         with aar.Tracker(sol, max_obs_per_frame=most) as t:
             for f in range(n):
