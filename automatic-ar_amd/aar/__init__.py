@@ -49,6 +49,8 @@ SYMBOLS = [
     "aar_tracker_bank_reset", "aar_tracker_bank_get_stats", "aar_tracker_bank_destroy",
     "aar_tracker_default_gate_params", "aar_tracker_gate_params_validate", "aar_tracker_enable_gate", "aar_tracker_last_gate",
     "aar_tracker_gate_detail", "aar_tracker_gate_bank_enable", "aar_tracker_gate_bank_last", "aar_tracker_gate_bank_detail",
+    "aar_tracker_default_motion_params", "aar_tracker_motion_params_validate", "aar_tracker_enable_motion", "aar_tracker_last_motion",
+    "aar_tracker_predict", "aar_tracker_motion_bank_enable", "aar_tracker_motion_bank_last", "aar_tracker_motion_bank_predict",
 ]
 TRACKER_BANK_MAX_MEMBERS = 1024
 TRACKER_MAX_LAG = 15
@@ -284,6 +286,15 @@ class CTrackerGateInfo(C.Structure):
                 ("median", C.c_double), ("max", C.c_double), ("threshold", C.c_double)]
 
 
+class CTrackerMotionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("model", C.c_int32), ("max_dt", C.c_double)]
+
+
+class CTrackerMotionInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("model", C.c_int32), ("predicted", C.c_int32), ("rel", C.c_double * 6),
+                ("velocity", C.c_double * 6), ("newest_time", C.c_double)]
+
+
 class CTrackerBankStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("members", C.c_int32), ("pushes", C.c_int64), ("launches", C.c_int64), ("h2d_copies", C.c_int64),
                 ("h2d_bytes", C.c_int64), ("d2h_copies", C.c_int64), ("d2h_bytes", C.c_int64)]
@@ -498,6 +509,15 @@ def lib():
     L.aar_tracker_gate_bank_enable.argtypes = [C.c_void_p, C.POINTER(CTrackerGateParams)]
     L.aar_tracker_gate_bank_last.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CTrackerGateInfo)]
     L.aar_tracker_gate_bank_detail.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), dp, u8p]
+    L.aar_tracker_default_motion_params.argtypes = [C.POINTER(CTrackerMotionParams)]
+    L.aar_tracker_default_motion_params.restype = None
+    L.aar_tracker_motion_params_validate.argtypes = [C.POINTER(CTrackerParams), C.POINTER(CTrackerMotionParams)]
+    L.aar_tracker_enable_motion.argtypes = [C.c_void_p, C.POINTER(CTrackerMotionParams)]
+    L.aar_tracker_last_motion.argtypes = [C.c_void_p, C.POINTER(CTrackerMotionInfo)]
+    L.aar_tracker_predict.argtypes = [C.c_void_p, C.c_double, dp]
+    L.aar_tracker_motion_bank_enable.argtypes = [C.c_void_p, C.POINTER(CTrackerMotionParams)]
+    L.aar_tracker_motion_bank_last.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CTrackerMotionInfo)]
+    L.aar_tracker_motion_bank_predict.argtypes = [C.c_void_p, C.c_int32, C.c_double, dp]
     L.aar_local_group_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.aar_local_group_destroy.argtypes = [C.c_void_p]
     L.aar_local_group_destroy.restype = None
@@ -1014,6 +1034,35 @@ def tracker_gate_params_validate(**kw):
     _check(lib().aar_tracker_gate_params_validate(C.byref(p)))
 
 
+TRACKER_MOTIONS = {"random_walk": 0, "rw": 0, "constant_velocity": 1, "cv": 1}
+
+
+def tracker_motion_params(model=None, max_dt=None, struct_size=None):
+    """aar_tracker_motion_params from Python values (None = the library's default: constant velocity, no max_dt); model: "cv" |
+    "constant_velocity" | "rw" | "random_walk" (or the integer)"""
+    p = CTrackerMotionParams()
+    lib().aar_tracker_default_motion_params(C.byref(p))
+    if model is not None:
+        p.model = int(TRACKER_MOTIONS.get(model, model))
+    if max_dt is not None:
+        p.max_dt = float(max_dt)
+    if struct_size is not None:
+        p.struct_size = int(struct_size)
+    return p
+
+
+def tracker_motion_params_validate(tracker=None, **kw):
+    """aar_tracker_motion_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  tracker: a dict of
+    tracker_params' keywords (None: smooth = 1, lag 0, unit sigmas)"""
+    tp = tracker_params(**(dict(smooth=True, sigma_rot=1.0, sigma_trans=1.0) if tracker is None else tracker))
+    p = tracker_motion_params(**kw)
+    _check(lib().aar_tracker_motion_params_validate(C.byref(tp), C.byref(p)))
+
+
+def _tracker_motion_info(m):
+    return dict(model=m.model, predicted=m.predicted, rel=np.array(m.rel[:]), velocity=np.array(m.velocity[:]), newest_time=m.newest_time)
+
+
 def _tracker_gate_info(g):
     return {k: getattr(g, k) for k, _ in CTrackerGateInfo._fields_ if k != "struct_size"}
 
@@ -1053,8 +1102,9 @@ class TrackerBank:
     one copy in, one launch of B workgroups, one copy out per push."""
 
     def __init__(self, solutions, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
-                 device=0, params=None, anchor="fixed", covariance=False, gate=None):
-        """gate: None, or a dict of tracker_gate_params' keywords: enable_gate(**gate) right after creation"""
+                 device=0, params=None, anchor="fixed", covariance=False, gate=None, motion=None):
+        """gate: None, or a dict of tracker_gate_params' keywords: enable_gate(**gate) right after creation; motion: None, a
+        model name ("cv") or a dict of tracker_motion_params' keywords: enable_motion(**motion) right after creation"""
         self.solutions = list(solutions)
         self._cds = [d.as_c() for d in self.solutions]
         arr = (C.POINTER(CDataset) * len(self._cds))(*[C.pointer(c) for c in self._cds])
@@ -1066,6 +1116,8 @@ class TrackerBank:
         self.size = lib().aar_tracker_bank_size(self.handle)
         if gate is not None:
             self.enable_gate(**gate)
+        if motion is not None:
+            self.enable_motion(**(motion if isinstance(motion, dict) else dict(model=motion)))
 
     def close(self):
         if self.handle:
@@ -1157,6 +1209,24 @@ class TrackerBank:
         p = tracker_gate_params(k_median, min_px, min_detections)
         _check(lib().aar_tracker_gate_bank_enable(self.handle, C.byref(p)))
 
+    def enable_motion(self, model=None, max_dt=None):
+        """aar_tracker_motion_bank_enable: once after creation or reset; one parameter set for all members"""
+        p = tracker_motion_params(model, max_dt)
+        _check(lib().aar_tracker_motion_bank_enable(self.handle, C.byref(p)))
+
+    def last_motion(self, member):
+        """aar_tracker_motion_bank_last: Tracker.last_motion() of one member"""
+        m = CTrackerMotionInfo()
+        m.struct_size = C.sizeof(CTrackerMotionInfo)
+        _check(lib().aar_tracker_motion_bank_last(self.handle, int(member), C.byref(m)))
+        return _tracker_motion_info(m)
+
+    def predict(self, member, time):
+        """aar_tracker_motion_bank_predict: Tracker.predict() of one member"""
+        pose = np.zeros(6)
+        _check(lib().aar_tracker_motion_bank_predict(self.handle, int(member), float(time), _dptr(pose)))
+        return pose
+
     def last_gate(self, member):
         """aar_tracker_gate_bank_last: Tracker.last_gate() of one member"""
         g = CTrackerGateInfo()
@@ -1184,10 +1254,11 @@ class Tracker:
     roots; its frames are ignored) and fed one frame per push."""
 
     def __init__(self, ds, lag=0, smooth=False, sigma_rot=0.0, sigma_trans=0.0, with_huber=False, huber_delta=None, max_obs_per_frame=None,
-                 device=0, params=None, anchor="fixed", covariance=False, gate=None):
+                 device=0, params=None, anchor="fixed", covariance=False, gate=None, motion=None):
         """params: aar_lm_params (lm_default_params(...)) or None for the defaults; anchor "fixed" | "marginal", covariance: DESIGN.md
         section 19 (uncertainty() after a push); gate: None, or a dict of tracker_gate_params' keywords:
-        enable_gate(**gate) right after creation"""
+        enable_gate(**gate) right after creation; motion: None, a model name ("cv") or a dict of tracker_motion_params' keywords (DESIGN.md
+        section 25): enable_motion(**motion) right after creation"""
         self.ds = ds
         self._cds = ds.as_c()
         self.prm = tracker_params(lag, smooth, sigma_rot, sigma_trans, with_huber, huber_delta, max_obs_per_frame, device, anchor=anchor,
@@ -1197,6 +1268,8 @@ class Tracker:
                                         C.byref(self.handle)))
         if gate is not None:
             self.enable_gate(**gate)
+        if motion is not None:
+            self.enable_motion(**(motion if isinstance(motion, dict) else dict(model=motion)))
 
     def close(self):
         if self.handle:
@@ -1286,6 +1359,24 @@ class Tracker:
         n, e, k = C.c_int32(0), np.zeros(cap), np.zeros(cap, dtype=np.uint8)
         _check(lib().aar_tracker_gate_detail(self.handle, C.byref(n), _dptr(e), _u8ptr(k)))
         return e[:n.value].copy(), k[:n.value].copy()
+
+    def enable_motion(self, model=None, max_dt=None):
+        """aar_tracker_enable_motion: once after creation or reset, before the first push (see tracker_motion_params)"""
+        p = tracker_motion_params(model, max_dt)
+        _check(lib().aar_tracker_enable_motion(self.handle, C.byref(p)))
+
+    def last_motion(self):
+        """aar_tracker_last_motion: dict(model, predicted, rel [6], velocity [6], newest_time) of the last accepted push"""
+        m = CTrackerMotionInfo()
+        m.struct_size = C.sizeof(CTrackerMotionInfo)
+        _check(lib().aar_tracker_last_motion(self.handle, C.byref(m)))
+        return _tracker_motion_info(m)
+
+    def predict(self, time):
+        """aar_tracker_predict: the newest pose carried to time with the last push's velocity, [6] (rvec, t)"""
+        pose = np.zeros(6)
+        _check(lib().aar_tracker_predict(self.handle, float(time), _dptr(pose)))
+        return pose
 
     def reset(self):
         _check(lib().aar_tracker_reset(self.handle))

@@ -25,6 +25,7 @@
 
 #include "../host/internal.h"
 #include "../host/se3.h"
+#include "../host/motion_model.h"
 #include "geom.hpp"
 #include "hostcopy.h"
 #include "kernels.h"
@@ -3077,6 +3078,15 @@ struct aar_tracker {
     double *h_back = nullptr;        // pinned: the gate record in front of h_res (one allocation, one copy back)
     LiveMember *d_gtab = nullptr;    // [1]
     double *d_gerr = nullptr;        // [max_obs_per_frame] e_d of the newest frame, then its keep flags (bytes)
+    // constant-velocity motion model (aar_tracker_enable_motion): its pushes leave their records in a block of their own,
+    // motion record | result | start record | uncertainty record, copied back in one piece; h_res then points into h_mot
+    bool motion_called = false, motion_on = false, motion_set = false;   // motion_set: the fields below are those of the last accepted push
+    aar_tracker_motion_params motion;
+    MotionState mstate;              // the two newest estimates and their times
+    double rel_slot[LIVE_MAX_W][6];  // by ring slot: the expected motion of the pair that ends at the frame
+    double last_rel[6];
+    int last_predicted = 0;
+    double *d_mot = nullptr, *h_mot = nullptr;
 };
 
 namespace {
@@ -3160,6 +3170,8 @@ void aar_tracker_destroy(aar_tracker *t) {
     if (t->h_back) (void)hipHostFree(t->h_back);
     if (t->d_gtab) (void)hipFree(t->d_gtab);
     if (t->d_gerr) (void)hipFree(t->d_gerr);
+    if (t->d_mot) (void)hipFree(t->d_mot);
+    if (t->h_mot) (void)hipHostFree(t->h_mot);
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;
 }
@@ -3223,6 +3235,10 @@ int aar_tracker_reset(aar_tracker *t) {
     t->det_on = false;   // (the buffers stay; aar_tracker_enable_detections fills them again)
     t->gate_on = false;  // (likewise aar_tracker_enable_gate)
     t->gate_set = false;
+    t->motion_called = t->motion_on = t->motion_set = false;   // (likewise aar_tracker_enable_motion)
+    t->mstate = MotionState();
+    t->h_res = t->h_back + LIVE_GATE_DOUBLES;   // (d_gtab's row may still point into d_mot: it is read only while gate_on, and
+                                                // aar_tracker_enable_gate writes it again)
     t->unc_set = false;  // (the device's marginal stays where it is: no push reads it while has_marginal is 0)
     t->has_marginal = 0;
     t->marginal_dropped = 0;
@@ -3463,12 +3479,29 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
         hdr[LIVE_HDR_CNT] = (double)n_obs;
         hdr[LIVE_HDR_INIT] = pose_init ? 1.0 : 0.0;
     }
+    // the motion model: the expected motion of the new pair and the prediction, from the estimates the last accepted push left.  The prediction
+    // rides in the slot header, where a caller's pose_init would be: a frame without one starts there
+    const bool motion = t->motion_on;
+    double rel_n[6] = {0, 0, 0, 0, 0, 0}, pred[6];
+    bool predicted = false, start_pred = false;
+    if (motion) {
+        predicted = motion_measure(t->mstate, frame_time, t->motion.max_dt, rel_n, pred);
+        if (!pose_init && n > 0) {
+            double *hdr = reinterpret_cast<double *>(t->h_stage);
+            memcpy(hdr, pred, sizeof pred);
+            if (gate && !raw) hdr[LIVE_HDR_INIT] = 1.0;
+            start_pred = true;
+        }
+    }
+    // the records of a push, gate record | result | start record | uncertainty record: in the tracker's state, or behind the motion record in the
+    // model's own block
+    double *d_rec = motion ? t->d_mot + LIVE_MOT_DOUBLES : t->d_state + LIVE_ST_GATE;
     LiveArgs a;
     live_window_args(a, p, t->lm, n, frame_time, t->times);
     a.ent = t->d_ent; a.Kmat = t->d_K; a.ring = t->d_ring; a.slot_bytes = t->slot_bytes;
-    a.zslot = t->d_state; a.anchor = t->d_state + LIVE_ST_ANCHOR; a.Ef = t->d_state + LIVE_ST_EF; a.Pe = t->d_state + LIVE_ST_PE; a.res = t->d_state + LIVE_ST_RES;
+    a.zslot = t->d_state; a.anchor = t->d_state + LIVE_ST_ANCHOR; a.Ef = t->d_state + LIVE_ST_EF; a.Pe = t->d_state + LIVE_ST_PE; a.res = d_rec + LIVE_GATE_DOUBLES;
     a.h = t->half_size;
-    a.has_init = (pose_init || raw) ? 1 : 0;   // raw: k_live_init wrote the header
+    a.has_init = (pose_init || raw || start_pred) ? 1 : 0;   // raw: k_live_init wrote the header
     const int W = a.W;
     int64_t det = 0;
     for (int i = 0; i < W; i++) {
@@ -3477,8 +3510,14 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
     }
     const bool marginal = a.marginal != 0, tail = marginal || p.covariance;
     a.has_marginal = marginal ? t->has_marginal : 0;
-    a.unc = t->d_state + LIVE_ST_UNC;
+    a.unc = a.res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
     a.rows = live_rows(a, det, a.has_marginal);
+    double rel[LIVE_MAX_W][6];   // by window position
+    if (motion) {
+        memset(rel, 0, sizeof rel);
+        memcpy(rel[W - 1], rel_n, sizeof rel_n);
+        for (int i = 0; i + 1 < W; i++) memcpy(rel[i], t->rel_slot[(a.first_slot + i) % slots], sizeof rel[i]);
+    }
     HIP_TRY(hipMemcpyAsync(t->d_ring + (size_t)ns * t->slot_bytes, t->h_stage, copy_bytes, hipMemcpyHostToDevice, t->stream));
     double *h_info = t->h_res + LIVE_RES_DOUBLES;
     if (raw) {
@@ -3489,10 +3528,10 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
         li.hf = (float)t->marker_size / 2.0f; li.h = t->marker_size / 2;   // as the Initializer: float for IPPE, double for the vote
         li.threshold = t->det.ippe_threshold;
         li.do_vote = do_vote ? 1 : 0; li.policy = t->det.start_policy; li.has_init = pose_init ? 1 : 0; li.has_prev = n > 0 ? 1 : 0;
-        li.zprev = t->d_state + 6 * ps;
+        li.zprev = start_pred ? reinterpret_cast<const double *>(li.slot) : t->d_state + 6 * ps;   // (the kernel reads it before it writes the header)
         li.ent = t->d_ent; li.Kmat = t->d_K; li.huber = a.huber; li.h_track = t->half_size;
         live_init_work_carve(li, t->d_work, mo);
-        li.info = t->d_state + LIVE_ST_INFO;
+        li.info = a.res + LIVE_RES_DOUBLES;
         launch_live_init(li, t->stream);
         if (n == 0 && !pose_init) {
             // the only push a vote can fail with nothing to fall back on: read the info before the window is touched
@@ -3510,14 +3549,28 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
         ga.slot = t->d_ring + (size_t)ns * t->slot_bytes; ga.n = n_obs; ga.has_init = a.has_init; ga.zprev = t->d_state + 6 * ps;
         ga.ent = t->d_ent; ga.Kmat = t->d_K; ga.h = t->half_size;
         ga.g.k_median = t->gate.k_median; ga.g.min_px = t->gate.min_px; ga.g.min_detections = t->gate.min_detections;
-        ga.rec = t->d_state + LIVE_ST_GATE; ga.det_err = t->d_gerr;
+        ga.rec = d_rec; ga.det_err = t->d_gerr;
         ga.keep = reinterpret_cast<uint8_t *>(t->d_gerr + (size_t)p.max_obs_per_frame);
         launch_live_gate(ga, t->stream);
         LiveBankArgs ba;
         memset(&ba, 0, sizeof ba);
         ba.sh = a;
         ba.tab = t->d_gtab; ba.raw = raw ? 1 : 0; ba.fresh = n == 0 ? 1 : 0;
-        launch_live_push_bank(ba, 1, t->stream);
+        if (motion) {
+            LiveMemberMotionArgs gm;
+            gm.ba = ba;
+            memcpy(gm.rel, rel, sizeof rel);
+            gm.mot = t->d_mot;
+            launch_live_push_member_motion(gm, t->stream);
+        } else {
+            launch_live_push_bank(ba, 1, t->stream);
+        }
+    } else if (motion) {
+        LiveMotionArgs ma;
+        ma.a = a;
+        memcpy(ma.rel, rel, sizeof rel);
+        ma.mot = t->d_mot;
+        launch_live_push_motion(ma, t->stream);
     } else {
         launch_live_push(a, t->stream);
     }
@@ -3526,7 +3579,8 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
     const size_t back = tail ? LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_HDR + (p.covariance ? 36 * (size_t)W : 0)
                              : LIVE_RES_DOUBLES + (raw ? LIVE_INFO_DOUBLES : 0);
     if (tail) t->unc_set = false;   // the copy overwrites the record aar_tracker_uncertainty serves: a push that fails from here on leaves none
-    if (gate) HIP_TRY(hipMemcpyAsync(t->h_back, t->d_state + LIVE_ST_GATE, (LIVE_GATE_DOUBLES + back) * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    if (motion) HIP_TRY(hipMemcpyAsync(t->h_mot, t->d_mot, (LIVE_MOT_DOUBLES + LIVE_GATE_DOUBLES + back) * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+    else if (gate) HIP_TRY(hipMemcpyAsync(t->h_back, d_rec, (LIVE_GATE_DOUBLES + back) * sizeof(double), hipMemcpyDeviceToHost, t->stream));
     else HIP_TRY(hipMemcpyAsync(t->h_res, a.res, back * sizeof(double), hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     int rc = check_async("k_live_push");
@@ -3535,12 +3589,25 @@ int tracker_push(aar_tracker *t, const char *fn, bool raw, double frame_time, in
     t->times[ns] = frame_time;
     t->cnt[ns] = n_obs;
     if (gate) {   // later pushes, the rows and sigma2 see the compacted frame
-        memcpy(t->gate_rec, t->h_back, sizeof t->gate_rec);
+        memcpy(t->gate_rec, t->h_res - LIVE_GATE_DOUBLES, sizeof t->gate_rec);
         t->gate_set = true;
         t->cnt[ns] = (int)t->gate_rec[2];
         a.rows = live_rows(a, det - n_obs + t->cnt[ns], a.has_marginal);
     }
     t->n = n + 1;
+    if (motion) {
+        // the two newest estimates at this push's final point: the kernel's motion record and the result's newest pose
+        MotionState &m = t->mstate;
+        if (n > 0) { memcpy(m.za, t->h_mot, sizeof m.za); m.ta = m.tb; }
+        memcpy(m.zb, t->h_res + 8, sizeof m.zb);
+        m.tb = frame_time;
+        m.frames = n > 0 ? 2 : 1;
+        memcpy(t->rel_slot[ns], rel_n, sizeof t->rel_slot[ns]);
+        memcpy(t->last_rel, rel_n, sizeof t->last_rel);
+        t->last_predicted = predicted ? 1 : 0;
+        t->motion_set = true;
+        if (raw && start_pred && predicted && h_info[4] == 1.0) h_info[4] = 3.0;   // the "previous estimate" the start kernel chose was the motion prediction
+    }
     if (tail) {
         const double *u = t->h_res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
         t->unc_set = true;
@@ -3682,6 +3749,9 @@ struct aar_tracker_bank {
         int64_t marginal_dropped = 0;
         double unc_sigma2 = 0;
         aar_tracker_detection_params det;
+        MotionState ms;                  // the motion model: the member's two newest estimates, its last push's expected motion
+        double last_rel[6];
+        int last_predicted = 0;
     };
     aar_tracker_params prm;
     aar_lm_params lm;
@@ -3712,6 +3782,15 @@ struct aar_tracker_bank {
     std::vector<double> gate_rec;        // [B][LIVE_GATE_DOUBLES] of the last accepted push
     LiveGateMember *d_gtab = nullptr;    // [B]
     double *d_gerr = nullptr;            // [B][max_obs_per_frame] e_d of the newest frames, then [B][max_obs_per_frame] keep flags (bytes)
+    // the motion model (aar_tracker_motion_bank_enable): every ring slot then is the members' slots followed by their
+    // expected motions [B][6]; the members' motion records sit behind the gate records of d_out / h_out
+    bool motion_called = false, motion_on = false, motion_set = false;
+    aar_tracker_motion_params motion;
+    size_t ring_cap = 0, stage_cap = 0;  // bytes allocated
+    size_t stride() const {              // of one ring slot of all members
+        const size_t s = (size_t)B * slot_bytes;
+        return motion_on ? (s + (size_t)B * 6 * sizeof(double) + 15) / 16 * 16 : s;
+    }
 };
 
 namespace {
@@ -3758,7 +3837,12 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
         if (int rc = live_check_pose_init(fn, who, init)) return rc;
     }
     HIP_TRY(hipSetDevice(k->device));
-    // the new slot of every member, staged one behind the other: ONE copy.  The header's idle doubles carry what differs by member
+    // the new slot of every member, staged one behind the other: ONE copy.  The header's idle doubles carry what differs by member.  With the
+    // motion model the members' expected motions follow the slots in the same copy, and a member without a pose_init finds its prediction in the
+    // header, where a pose_init would be
+    const bool motion = k->motion_on;
+    double *h_rel = reinterpret_cast<double *>(k->h_stage + (size_t)B * k->slot_bytes);   // [B][6] (motion only)
+    std::vector<uint8_t> start_pred((size_t)B, 0), predicted((size_t)B, 0);
     size_t copy_bytes = 0;
     off = 0;
     for (int b = 0; b < B; b++) {
@@ -3769,17 +3853,27 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
         double *hdr = reinterpret_cast<double *>(slot);
         hdr[LIVE_HDR_CNT] = (double)n_obs[b];
         hdr[LIVE_HDR_INIT] = init ? 1.0 : 0.0;
+        if (motion) {
+            double pred[6];
+            predicted[b] = motion_measure(k->mem[b].ms, frame_time, k->motion.max_dt, h_rel + 6 * (size_t)b, pred) ? 1 : 0;
+            if (!init && n > 0) {
+                memcpy(hdr, pred, sizeof pred);
+                if (!raw) hdr[LIVE_HDR_INIT] = 1.0;   // (raw: the start kernel takes it as its previous estimate, a vote is still held)
+                start_pred[b] = 1;
+            }
+        }
         copy_bytes = (size_t)b * k->slot_bytes + used;
         off += (size_t)n_obs[b];
     }
+    if (motion) copy_bytes = (size_t)B * k->slot_bytes + (size_t)B * 6 * sizeof(double);
     LiveBankArgs ba;
     memset(&ba, 0, sizeof ba);
     live_window_args(ba.sh, p, k->lm, n, frame_time, k->times);
-    ba.sh.slot_bytes = (size_t)B * k->slot_bytes;
+    ba.sh.slot_bytes = k->stride();
     ba.tab = k->d_tab; ba.raw = raw ? 1 : 0; ba.fresh = n == 0 ? 1 : 0;
     const int W = ba.sh.W;
     const bool marginal = ba.sh.marginal != 0, tail = marginal || p.covariance;
-    char *new_slots = k->d_ring + (size_t)ns * B * k->slot_bytes;
+    char *new_slots = k->d_ring + (size_t)ns * k->stride();
     aar_tracker_bank_stats &st = k->stats;
     HIP_TRY(hipMemcpyAsync(new_slots, k->h_stage, copy_bytes, hipMemcpyHostToDevice, k->stream));
     st.h2d_copies++; st.h2d_bytes += (int64_t)copy_bytes;
@@ -3788,6 +3882,7 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
         LiveInitBankArgs li;
         li.tab = k->d_itab; li.slot0 = new_slots; li.slot_bytes = k->slot_bytes; li.max_obs = (size_t)p.max_obs_per_frame;
         li.has_prev = n > 0 ? 1 : 0; li.prev_slot = ps; li.huber = ba.sh.huber;
+        li.pred_in_header = motion ? 1 : 0;
         launch_live_init_bank(li, B, k->stream);
         st.launches++;
         if (n == 0 && !all_init) {
@@ -3813,10 +3908,18 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
         launch_live_gate_bank(ga, B, k->stream);
         st.launches++;
     }
-    launch_live_push_bank(ba, B, k->stream);
+    if (motion) {
+        LiveBankMotionArgs bm;
+        bm.ba = ba; bm.ring = k->d_ring; bm.rel_off = (size_t)B * k->slot_bytes;
+        bm.mot = k->d_out + (size_t)B * k->out_stride + (size_t)B * LIVE_GATE_DOUBLES;   // [B][LIVE_MOT_DOUBLES], behind the gate records
+        launch_live_push_bank_motion(bm, B, k->stream);
+    } else {
+        launch_live_push_bank(ba, B, k->stream);
+    }
     st.launches++;
     if (tail) k->unc_set = false;   // the copy overwrites the records aar_tracker_bank_uncertainty serves
-    const size_t back_bytes = out_bytes + (gate ? (size_t)B * LIVE_GATE_DOUBLES * sizeof(double) : 0);   // (the gate records ride behind: one copy)
+    const size_t back_bytes = out_bytes + (gate || motion ? (size_t)B * LIVE_GATE_DOUBLES * sizeof(double) : 0) +   // (the gate records ride behind: one copy)
+                              (motion ? (size_t)B * LIVE_MOT_DOUBLES * sizeof(double) : 0);                            // (and behind them the motion records)
     HIP_TRY(hipMemcpyAsync(k->h_out, k->d_out, back_bytes, hipMemcpyDeviceToHost, k->stream));
     st.d2h_copies++; st.d2h_bytes += (int64_t)back_bytes;
     HIP_TRY(hipStreamSynchronize(k->stream));
@@ -3842,9 +3945,22 @@ int bank_push(aar_tracker_bank *k, const char *fn, bool raw, double frame_time, 
             m.unc_sigma2 = live_sigma2(rows, W, h[4]);
         }
         m.cnt[ns] = kept;
+        if (motion) {
+            // the member's two newest estimates at this push's final point: its motion record and its result's newest pose
+            MotionState &ms = m.ms;
+            if (n > 0) { memcpy(ms.za, k->h_out + (size_t)B * k->out_stride + (size_t)B * LIVE_GATE_DOUBLES + (size_t)b * LIVE_MOT_DOUBLES, sizeof ms.za); ms.ta = ms.tb; }
+            memcpy(ms.zb, h + 8, sizeof ms.zb);
+            ms.tb = frame_time;
+            ms.frames = n > 0 ? 2 : 1;
+            memcpy(m.last_rel, h_rel + 6 * (size_t)b, sizeof m.last_rel);
+            m.last_predicted = predicted[b];
+            double *h_info = k->h_out + (size_t)b * k->out_stride + LIVE_RES_DOUBLES;
+            if (raw && start_pred[b] && predicted[b] && h_info[4] == 1.0) h_info[4] = 3.0;   // the "previous estimate" was the motion prediction
+        }
         if (results) live_fill_result(h, n, W, slots, t0, results + b);
         if (infos) live_fill_info(h + LIVE_RES_DOUBLES, infos + b);
     }
+    if (motion) k->motion_set = true;
     if (tail) { k->unc_set = true; k->unc_W = W; }
     if (gate) k->gate_set = true;
     k->times[ns] = frame_time;
@@ -3918,7 +4034,7 @@ int aar_tracker_bank_create(int32_t n_members, const aar_dataset *const *solutio
     k->slot_bytes = live_slot_bytes(p.max_obs_per_frame);
     k->out_stride = LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + (tail ? LIVE_UNC_HDR + (p.covariance ? 36 * (size_t)slots : 0) : 0);
     const size_t ring_bytes = (size_t)slots * B * k->slot_bytes, state_bytes = (size_t)B * LIVE_ST_RES * sizeof(double),
-                 out_bytes = ((size_t)B * k->out_stride + (size_t)B * LIVE_GATE_DOUBLES) * sizeof(double);   // (behind the records: the gate's)
+                 out_bytes = ((size_t)B * k->out_stride + (size_t)B * LIVE_GATE_DOUBLES + (size_t)B * LIVE_MOT_DOUBLES) * sizeof(double);   // (behind the records: the gate's, the motion model's)
     double *d_z = nullptr;
     auto fail = [&](int code) { if (d_z) (void)hipFree(d_z); aar_tracker_bank_destroy(k); return code; };
     if (hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipStreamCreate failed"));
@@ -3931,6 +4047,7 @@ int aar_tracker_bank_create(int32_t n_members, const aar_dataset *const *solutio
         hipHostMalloc((void **)&k->h_out, out_bytes, hipHostMallocDefault) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: hipHostMalloc failed"));
     memset(k->h_stage, 0, (size_t)B * k->slot_bytes);
+    k->ring_cap = ring_bytes; k->stage_cap = (size_t)B * k->slot_bytes;
     if (hipMemsetAsync(k->d_state, 0, state_bytes, k->stream) != hipSuccess || hipMemsetAsync(k->d_out, 0, out_bytes, k->stream) != hipSuccess ||
         hipMemsetAsync(k->d_ring, 0, ring_bytes, k->stream) != hipSuccess)
         return fail(set_error(AAR_ERR_HIP, "aar_tracker_bank_create: hipMemset failed"));
@@ -3971,8 +4088,9 @@ int aar_tracker_bank_reset(aar_tracker_bank *k) {
     k->det_on = false;   // (the buffers stay; aar_tracker_bank_enable_detections fills them again)
     k->gate_on = false;  // (likewise aar_tracker_gate_bank_enable)
     k->gate_set = false;
+    k->motion_called = k->motion_on = k->motion_set = false;   // (likewise aar_tracker_motion_bank_enable; the larger ring stays allocated)
     k->unc_set = false;  // (the device's marginals stay where they are: the first push of a bank reads none)
-    for (auto &m : k->mem) { m.has_marginal = 0; m.marginal_dropped = 0; }
+    for (auto &m : k->mem) { m.has_marginal = 0; m.marginal_dropped = 0; m.ms = MotionState(); }
     return AAR_OK;
 }
 
@@ -4083,6 +4201,20 @@ int aar_tracker_bank_get_stats(const aar_tracker_bank *k, aar_tracker_bank_stats
 // ------------------------------------------------------------------------------------------------
 namespace {
 
+// the tracker as the one member of a bank (the gated refinement): the same state, the records where the single tracker's kernels leave them --
+// behind the motion record in the model's own block when the motion model is on
+int tracker_write_member_row(aar_tracker *t, const char *fn) {
+    LiveMember r;
+    r.ent = t->d_ent; r.Kmat = t->d_K; r.h = t->half_size; r.ring = t->d_ring;
+    r.zslot = t->d_state; r.anchor = t->d_state + LIVE_ST_ANCHOR; r.Ef = t->d_state + LIVE_ST_EF; r.Pe = t->d_state + LIVE_ST_PE;
+    r.res = t->motion_on ? t->d_mot + LIVE_MOT_DOUBLES + LIVE_GATE_DOUBLES : t->d_state + LIVE_ST_RES;
+    r.unc = r.res + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES;
+    const char *what = "";
+    if (h2d(t->d_gtab, &r, sizeof r, t->stream, &what)) return set_error(AAR_ERR_HIP, "%s: %s failed", fn, what);
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    return AAR_OK;
+}
+
 int gate_params_check(const aar_tracker_gate_params *in, aar_tracker_gate_params *p) {
     aar_tracker_default_gate_params(p);
     if (in->struct_size < offsetof(aar_tracker_gate_params, min_detections) + sizeof(int32_t))
@@ -4151,17 +4283,8 @@ int aar_tracker_enable_gate(aar_tracker *t, const aar_tracker_gate_params *in) {
     HIP_TRY(hipSetDevice(t->device));
     const size_t mo = (size_t)t->prm.max_obs_per_frame;
     if (!t->d_gerr) HIP_TRY(hipMalloc((void **)&t->d_gerr, mo * sizeof(double) + mo));
-    if (!t->d_gtab) {
-        HIP_TRY(hipMalloc((void **)&t->d_gtab, sizeof(LiveMember)));
-        // the tracker as the one member of a bank: the same state, the records where the single tracker's kernels leave them
-        LiveMember r;
-        r.ent = t->d_ent; r.Kmat = t->d_K; r.h = t->half_size; r.ring = t->d_ring;
-        r.zslot = t->d_state; r.anchor = t->d_state + LIVE_ST_ANCHOR; r.Ef = t->d_state + LIVE_ST_EF; r.Pe = t->d_state + LIVE_ST_PE;
-        r.res = t->d_state + LIVE_ST_RES; r.unc = t->d_state + LIVE_ST_UNC;
-        const char *what = "";
-        if (h2d(t->d_gtab, &r, sizeof r, t->stream, &what)) return set_error(AAR_ERR_HIP, "aar_tracker_enable_gate: %s failed", what);
-        HIP_TRY(hipStreamSynchronize(t->stream));
-    }
+    if (!t->d_gtab) HIP_TRY(hipMalloc((void **)&t->d_gtab, sizeof(LiveMember)));
+    if (int rc = tracker_write_member_row(t, "aar_tracker_enable_gate")) return rc;
     t->gate = p;
     t->gate_on = true;
     t->gate_set = false;
@@ -4244,6 +4367,185 @@ int aar_tracker_gate_bank_detail(aar_tracker_bank *k, int32_t member, int32_t *n
     return gate_detail_out("aar_tracker_gate_bank_detail", k->stream, k->d_gerr + (size_t)member * mo,
                            reinterpret_cast<const uint8_t *>(k->d_gerr + (size_t)k->B * mo) + (size_t)member * mo,
                            (int)k->gate_rec[(size_t)member * LIVE_GATE_DOUBLES + 1], n, det_err, keep);
+}
+
+// ---- constant-velocity motion model of the live tracker ----
+namespace {
+
+// a tracker's block of push records with the model: motion record | gate record | result | start record | uncertainty record
+constexpr size_t LIVE_MOT_BLOCK = LIVE_MOT_DOUBLES + LIVE_GATE_DOUBLES + LIVE_RES_DOUBLES + LIVE_INFO_DOUBLES + LIVE_UNC_DOUBLES;
+
+int motion_params_check(const aar_tracker_params *tp, const aar_tracker_motion_params *in, aar_tracker_motion_params *p) {
+    aar_tracker_default_motion_params(p);
+    if (in->struct_size < offsetof(aar_tracker_motion_params, model) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_params: struct_size %u does not reach model", (unsigned)in->struct_size);
+    memcpy(p, in, std::min<size_t>(in->struct_size, sizeof *p));
+    p->struct_size = (uint32_t)sizeof *p;
+    if (p->model != AAR_TRACKER_MOTION_RANDOM_WALK && p->model != AAR_TRACKER_MOTION_CONSTANT_VELOCITY)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_params: model = %d is neither AAR_TRACKER_MOTION_RANDOM_WALK nor AAR_TRACKER_MOTION_CONSTANT_VELOCITY",
+                         (int)p->model);
+    if (!std::isfinite(p->max_dt) || p->max_dt < 0.0)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_params: max_dt = %g must be finite and not negative", p->max_dt);
+    aar_tracker_params q;
+    if (!tracker_params_read(tp, &q))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_params: struct_size %u does not reach lag / smooth", (unsigned)tp->struct_size);
+    if (p->model == AAR_TRACKER_MOTION_CONSTANT_VELOCITY && !q.smooth)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_params: model = AAR_TRACKER_MOTION_CONSTANT_VELOCITY needs smooth = 1 (the prior carries the expected motion)");
+    return AAR_OK;
+}
+
+}  // namespace
+
+void aar_tracker_default_motion_params(aar_tracker_motion_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof *p;
+    p->model = AAR_TRACKER_MOTION_CONSTANT_VELOCITY;
+    p->max_dt = 0.0;
+}
+
+int aar_tracker_motion_params_validate(const aar_tracker_params *tp, const aar_tracker_motion_params *in) {
+    if (!tp || !in) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_params_validate: null argument");
+    aar_tracker_motion_params p;
+    return motion_params_check(tp, in, &p);
+}
+
+int aar_tracker_enable_motion(aar_tracker *t, const aar_tracker_motion_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_motion: null argument");
+    if (!t) {   // no tracker exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_tracker_enable_motion: null tracker");
+    }
+    aar_tracker_motion_params p;
+    if (int rc = motion_params_check(&t->prm, in, &p)) return rc;
+    if (t->motion_called) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_motion: already called (aar_tracker_reset first)");
+    if (t->n != 0) return set_error(AAR_ERR_INVALID, "aar_tracker_enable_motion: call it after aar_tracker_create or aar_tracker_reset, before the first push");
+    if (p.model == AAR_TRACKER_MOTION_RANDOM_WALK) {   // the tracker stays as it is
+        t->motion_called = true;
+        return AAR_OK;
+    }
+    HIP_TRY(hipSetDevice(t->device));
+    const size_t doubles = LIVE_MOT_BLOCK;
+    if (!t->d_mot) HIP_TRY(hipMalloc((void **)&t->d_mot, doubles * sizeof(double)));
+    if (!t->h_mot) HIP_TRY(hipHostMalloc((void **)&t->h_mot, doubles * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipMemsetAsync(t->d_mot, 0, doubles * sizeof(double), t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    memset(t->h_mot, 0, doubles * sizeof(double));
+    t->h_res = t->h_mot + LIVE_MOT_DOUBLES + LIVE_GATE_DOUBLES;
+    t->motion = p;
+    t->mstate = MotionState();
+    memset(t->rel_slot, 0, sizeof t->rel_slot);
+    t->motion_called = t->motion_on = true;
+    t->motion_set = false;
+    if (t->gate_on) return tracker_write_member_row(t, "aar_tracker_enable_motion");   // the gated refinement's records move with the others
+    return AAR_OK;
+}
+
+int aar_tracker_last_motion(aar_tracker *t, aar_tracker_motion_info *out) {
+    if (!t || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_last_motion: null argument");
+    if (!t->motion_on) return set_error(AAR_ERR_INVALID, "aar_tracker_last_motion: the tracker has no motion model (aar_tracker_enable_motion)");
+    if (!t->motion_set || t->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_last_motion: no push since creation / reset");
+    if (out->struct_size < offsetof(aar_tracker_motion_info, predicted) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_last_motion: struct_size %u does not reach predicted", (unsigned)out->struct_size);
+    aar_tracker_motion_info r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof r);
+    r.model = t->motion.model; r.predicted = t->last_predicted;
+    memcpy(r.rel, t->last_rel, sizeof r.rel);
+    motion_velocity(t->mstate, r.velocity);
+    r.newest_time = t->mstate.tb;
+    memcpy(out, &r, r.struct_size);
+    return AAR_OK;
+}
+
+int aar_tracker_predict(aar_tracker *t, double time, double pose[6]) {
+    if (!t || !pose) return set_error(AAR_ERR_INVALID, "aar_tracker_predict: null argument");
+    if (!t->motion_on) return set_error(AAR_ERR_INVALID, "aar_tracker_predict: the tracker has no motion model (aar_tracker_enable_motion)");
+    if (!t->motion_set || t->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_predict: no push since creation / reset");
+    if (!std::isfinite(time) || time < t->mstate.tb)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_predict: time = %g is not finite or lies before the newest frame's %g", time, t->mstate.tb);
+    motion_predict(t->mstate, time, t->motion.max_dt, pose);
+    return AAR_OK;
+}
+
+int aar_tracker_motion_bank_enable(aar_tracker_bank *k, const aar_tracker_motion_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_enable: null argument");
+    if (!k) {   // no bank exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_enable: null bank");
+    }
+    aar_tracker_motion_params p;
+    if (int rc = motion_params_check(&k->prm, in, &p)) return rc;
+    if (k->motion_called) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_enable: already called (aar_tracker_bank_reset first)");
+    if (k->n != 0)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_enable: call it after aar_tracker_bank_create or aar_tracker_bank_reset, before the first push");
+    if (p.model == AAR_TRACKER_MOTION_RANDOM_WALK) {   // the bank stays as it is
+        k->motion_called = true;
+        return AAR_OK;
+    }
+    HIP_TRY(hipSetDevice(k->device));
+    // room for the members' expected motions behind their slots, in the ring and in the staging buffer (the ring is empty: no frame is lost)
+    const int B = k->B, slots = k->prm.lag + 1;
+    k->motion_on = true;
+    const size_t stride = k->stride();
+    auto fail = [&](int code) { k->motion_on = false; return code; };
+    if (k->ring_cap < (size_t)slots * stride || k->stage_cap < stride) {
+        char *ring = nullptr, *stage = nullptr;
+        if (hipMalloc((void **)&ring, (size_t)slots * stride) != hipSuccess || hipHostMalloc((void **)&stage, stride, hipHostMallocDefault) != hipSuccess) {
+            if (ring) (void)hipFree(ring);
+            return fail(set_error(AAR_ERR_HIP, "aar_tracker_motion_bank_enable: allocation failed (ring of %zu bytes)", (size_t)slots * stride));
+        }
+        (void)hipStreamSynchronize(k->stream);
+        (void)hipFree(k->d_ring);
+        (void)hipHostFree(k->h_stage);
+        k->d_ring = ring; k->h_stage = stage;
+        k->ring_cap = (size_t)slots * stride; k->stage_cap = stride;
+        memset(k->h_stage, 0, stride);
+        // the member table's ring pointers follow
+        std::vector<LiveMember> tab((size_t)B);
+        const char *what = "";
+        if (d2h(tab.data(), k->d_tab, tab.size() * sizeof(LiveMember), k->stream, &what)) return fail(set_error(AAR_ERR_HIP, "aar_tracker_motion_bank_enable: %s failed", what));
+        for (int b = 0; b < B; b++) tab[b].ring = k->d_ring + (size_t)b * k->slot_bytes;
+        if (h2d(k->d_tab, tab.data(), tab.size() * sizeof(LiveMember), k->stream, &what)) return fail(set_error(AAR_ERR_HIP, "aar_tracker_motion_bank_enable: %s failed", what));
+    }
+    if (hipMemsetAsync(k->d_ring, 0, (size_t)slots * stride, k->stream) != hipSuccess || hipStreamSynchronize(k->stream) != hipSuccess)
+        return fail(set_error(AAR_ERR_HIP, "aar_tracker_motion_bank_enable: hipMemset failed"));
+    for (auto &m : k->mem) { m.ms = MotionState(); memset(m.last_rel, 0, sizeof m.last_rel); m.last_predicted = 0; }
+    k->motion = p;
+    k->motion_called = true;
+    k->motion_set = false;
+    return AAR_OK;
+}
+
+int aar_tracker_motion_bank_last(aar_tracker_bank *k, int32_t member, aar_tracker_motion_info *out) {
+    if (!k || !out) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_last: null argument");
+    if (member < 0 || member >= k->B) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_last: member = %d is outside 0 .. %d", (int)member, k->B - 1);
+    if (!k->motion_on) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_last: the bank has no motion model (aar_tracker_motion_bank_enable)");
+    if (!k->motion_set || k->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_last: no push since creation / reset");
+    if (out->struct_size < offsetof(aar_tracker_motion_info, predicted) + sizeof(int32_t))
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_last: struct_size %u does not reach predicted", (unsigned)out->struct_size);
+    const aar_tracker_bank::Member &m = k->mem[member];
+    aar_tracker_motion_info r;
+    memset(&r, 0, sizeof r);
+    r.struct_size = (uint32_t)std::min<size_t>(out->struct_size, sizeof r);
+    r.model = k->motion.model; r.predicted = m.last_predicted;
+    memcpy(r.rel, m.last_rel, sizeof r.rel);
+    motion_velocity(m.ms, r.velocity);
+    r.newest_time = m.ms.tb;
+    memcpy(out, &r, r.struct_size);
+    return AAR_OK;
+}
+
+int aar_tracker_motion_bank_predict(aar_tracker_bank *k, int32_t member, double time, double pose[6]) {
+    if (!k || !pose) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_predict: null argument");
+    if (member < 0 || member >= k->B) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_predict: member = %d is outside 0 .. %d", (int)member, k->B - 1);
+    if (!k->motion_on) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_predict: the bank has no motion model (aar_tracker_motion_bank_enable)");
+    if (!k->motion_set || k->n == 0) return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_predict: no push since creation / reset");
+    const MotionState &ms = k->mem[member].ms;
+    if (!std::isfinite(time) || time < ms.tb)
+        return set_error(AAR_ERR_INVALID, "aar_tracker_motion_bank_predict: time = %g is not finite or lies before the newest frame's %g", time, ms.tb);
+    motion_predict(ms, time, k->motion.max_dt, pose);
+    return AAR_OK;
 }
 
 }  // extern "C"

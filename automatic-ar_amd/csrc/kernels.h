@@ -364,6 +364,14 @@ constexpr int LIVE_UNC_DOUBLES = LIVE_UNC_HDR + 36 * LIVE_MAX_W;
 // rounding noise of either sign around an exact 0
 constexpr double LIVE_MARGINAL_PIVOT_REL = 1e-10;
 void launch_live_push(const LiveArgs &a, hipStream_t st);   // ONE launch; the tail instance when marginal or covariance is set
+// constant-velocity motion model: the same push with an expected motion on every pair -- its own kernel instances
+constexpr int LIVE_MOT_DOUBLES = 8;       // the motion record: the pose of the frame before the newest at the final point [0..5], 0 0
+struct LiveMotionArgs {
+    LiveArgs a;                           // res .. unc lie in the motion tracker's own block, behind the motion record
+    double rel[LIVE_MAX_W][6];            // by window position: (rvec, t) expected of the pair that ends there (position 0: the anchor pair's)
+    double *mot;                          // [LIVE_MOT_DOUBLES]
+};
+void launch_live_push_motion(const LiveMotionArgs &a, hipStream_t st);   // ONE launch, as launch_live_push
 
 // tracker bank: B independent live trackers advance in lockstep, workgroup b of k_live_push_bank runs member b's push.
 // The ring is [slot][member]: the slots one push fills are contiguous (ONE copy), member b's ring is ring + b slot_bytes with stride B slot_bytes.
@@ -384,6 +392,22 @@ struct LiveBankArgs {
     int fresh;                            // the first push since creation / reset: no marginal prior whatever the device still holds
 };
 void launch_live_push_bank(const LiveBankArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
+// the gated single tracker with the motion model: launch_live_push_bank on its one-row table with the expected motions
+struct LiveMemberMotionArgs {
+    LiveBankArgs ba;
+    double rel[LIVE_MAX_W][6];            // as LiveMotionArgs
+    double *mot;
+};
+void launch_live_push_member_motion(const LiveMemberMotionArgs &a, hipStream_t st);   // ONE launch of one workgroup
+// the bank with the motion model: every ring slot is the members' slots followed by their expected motions, [B][6] doubles at rel_off (the
+// motion of the pair that ENDS at the slot's frame); sh.slot_bytes is the stride of that whole group
+struct LiveBankMotionArgs {
+    LiveBankArgs ba;
+    const char *ring;                     // the bank's ring
+    size_t rel_off;                       // B member slots
+    double *mot;                          // [B][LIVE_MOT_DOUBLES]
+};
+void launch_live_push_bank_motion(const LiveBankMotionArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
 
 // the start of a frame pushed as raw detections (live_init_kernels.hip): undistortion, IPPE, the object pose candidates and
 // their vote in ONE launch of one workgroup, on the slot the frame was just copied into
@@ -426,6 +450,7 @@ struct LiveInitBankArgs {
     size_t slot_bytes, max_obs;
     int has_prev, prev_slot;              // a previous frame exists, its ring slot
     float huber;
+    int pred_in_header;                   // motion model: a member without a start pose finds its prediction in its slot header, not in zslot
 };
 void launch_live_init_bank(const LiveInitBankArgs &a, int B, hipStream_t st);   // ONE launch of B workgroups
 

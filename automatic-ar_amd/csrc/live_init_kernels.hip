@@ -138,6 +138,7 @@ __device__ __forceinline__ void live_init_body(const LiveInitArgs &a, LiveInitSh
 #pragma unroll
         for (int k = 0; k < 6; k++) {
             s.zv[k] = zv[k];
+            // (zprev may BE hdr, the motion model's prediction: it is read here, two barriers before the header is written below)
             s.zp[k] = a.has_init ? hdr[k] : (a.has_prev ? a.zprev[k] : 0.0);
         }
         s.Ev = 0.0;
@@ -205,7 +206,7 @@ __global__ void __launch_bounds__(LI_THREADS) k_live_init_bank(const LiveInitBan
     // a vote is held unless the caller's pose_init settles the start (policy VOTE) or the frame has too few detections
     a.do_vote = (a.n_det >= __builtin_amdgcn_readfirstlane(m->min_detections) && !(a.has_init && a.policy == LIVE_START_VOTE)) ? 1 : 0;
     a.has_prev = ba.has_prev;
-    a.zprev = uni_ptr(m->zslot) + 6 * ba.prev_slot;
+    a.zprev = ba.pred_in_header ? hdr : uni_ptr(m->zslot) + 6 * ba.prev_slot;
     a.ent = uni_ptr(m->ent); a.Kmat = uni_ptr(m->Kmat); a.huber = ba.huber; a.h_track = m->h_track;
     live_init_work_carve(a, uni_ptr(m->work), ba.max_obs);
     a.info = uni_ptr(m->info);

@@ -43,6 +43,16 @@ struct LiveBankShared : LiveShared {
     double lam[LIVE_MAX_W][2];          // LiveArgs::lam, from the shared argument block
 };
 
+// the constant-velocity instance keeps, by window position, the expected motion (rvec, t) of the pair that ENDS at the
+// frame (position 0: the anchor pair's): the caller copies them from the kernel arguments before the first barrier
+struct LiveMotionShared : LiveShared {
+    double rel[LIVE_MAX_W][6];
+};
+// ... and the same behind a bank member's cnt and lam (the gated single tracker refines as the one member of a bank)
+struct LiveBankMotionShared : LiveBankShared {
+    double rel[LIVE_MAX_W][6];
+};
+
 // what the tail instance adds
 struct LiveTail {
     double Lm[36], m[6];                // the marginal prior on the first window frame
@@ -78,8 +88,16 @@ __device__ __forceinline__ double live_lam(const LiveArgs &a, const LiveShared &
     else return a.lam[i][k];
 }
 
+// the expected motion of the pair that ends at window frame i: none (the random walk) unless MOTION (s is then a LiveMotionShared)
+template <bool BANK, bool MOTION>
+__device__ __forceinline__ const double *live_rel(const LiveShared &s, int i) {
+    if constexpr (MOTION && BANK) return static_cast<const LiveBankMotionShared &>(s).rel[i];
+    else if constexpr (MOTION) return static_cast<const LiveMotionShared &>(s).rel[i];
+    else return nullptr;
+}
+
 // WITH_J: H, b and the costs at s.z; else the costs at s.z + s.dl (-> s.zt) with the linear model's sums
-template <bool WITH_J, bool BANK>
+template <bool WITH_J, bool BANK, bool MOTION>
 __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta, LiveShared &s, int wv, int lane) {
     const int W = a.W, out = WITH_J ? 0 : 1;
     for (int i = wv; i < W; i += 4) {
@@ -126,7 +144,7 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
             }
             make_ent_row(zp, rowp);
             double phi[3], et[3], Ma[9], Mb[9];
-            pair_terms<WITH_J>(rowp, rowc, nullptr, phi, et, Ma, Mb);
+            pair_terms<WITH_J>(rowp, rowc, live_rel<BANK, MOTION>(s, i), phi, et, Ma, Mb);
             const double lr = live_lam<BANK>(a, s, i, 0), lt = live_lam<BANK>(a, s, i, 1);
             Pe = lr * (phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]) + lt * (et[0] * et[0] + et[1] * et[1] + et[2] * et[2]);
             if (WITH_J) {
@@ -146,7 +164,7 @@ __device__ __forceinline__ void live_eval(const LiveArgs &a, const TrackArgs &ta
             ld6(s.z[i + 1], zn);
             make_ent_row(zn, rown);
             double phi[3], et[3], Ma[9], Mb[9];
-            pair_terms<true>(rowc, rown, nullptr, phi, et, Ma, Mb);
+            pair_terms<true>(rowc, rown, live_rel<BANK, MOTION>(s, i + 1), phi, et, Ma, Mb);
             const double lr = live_lam<BANK>(a, s, i + 1, 0), lt = live_lam<BANK>(a, s, i + 1, 1);
             double O[36];
 #pragma unroll
@@ -295,10 +313,9 @@ __device__ __forceinline__ void live_solve(LiveShared &s, int W, double mu) {
 //   elimination   live_solve at mu = 0 leaves P_f^-1 in s.inv
 //   marginal      Lambda' = B - O^T A^-1 O, b' = c - O^T A^-1 a, m' = z_1 + Lambda'^-1 b'   (A = D_0 = P_0, a = b_0, O = O_0)
 //   covariance    Sigma_{W-1} = P_{W-1}^-1, Sigma_f = P_f^-1 + G_f Sigma_{f+1} G_f^T, G_f = P_f^-1 O_f
-// Not inlined: it runs when the LM's registers are dead.  One instance per kernel (BANK), so that each has ONE caller and keeps seeing that
-// kernel's LDS objects by their addresses.
-template <bool BANK>
-__device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc, int W, int do_marginal, int do_cov, double lr, double lt, int lane) {
+// The motion instances take it inline: no call frame, no scratch.
+template <bool BANK, bool MOTION>
+__device__ __forceinline__ void live_tail_body(LiveShared &s, LiveTail &tl, double *unc, int W, int do_marginal, int do_cov, double lr, double lt, int lane) {
     live_solve(s, W, 0.0);
     const bool ok = s.flag == 0;
     if (do_marginal) {
@@ -309,7 +326,7 @@ __device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc,
             ld6(s.z[1], z1);
             make_ent_row(z0, row0);
             make_ent_row(z1, row1);
-            pair_terms<true>(row0, row1, nullptr, phi, et, Ma, Mb);
+            pair_terms<true>(row0, row1, live_rel<BANK, MOTION>(s, 1), phi, et, Ma, Mb);
 #pragma unroll
             for (int k = 0; k < 36; k++) tl.B[k] = 0.0;
 #pragma unroll
@@ -433,10 +450,19 @@ __device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc,
     }
 }
 
+// The instances of sections 17 - 24 call it: not inlined, it runs when the LM's registers are dead.  One instance per kernel (BANK), so that each
+// has ONE caller and keeps seeing that kernel's LDS objects by their addresses.
+template <bool BANK>
+__device__ __noinline__ void live_tail(LiveShared &s, LiveTail &tl, double *unc, int W, int do_marginal, int do_cov, double lr, double lt, int lane) {
+    live_tail_body<BANK, false>(s, tl, unc, W, do_marginal, do_cov, lr, lt, lane);
+}
+
 // One push of one tracker by one workgroup of 256 threads: the kernels below call it.  BANK: s is a LiveBankShared whose cnt and lam the caller has filled (a.cnt, a.lam
-// are not read) and the threads have met at a barrier since.
-template <bool TAIL, bool BANK>
-__device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s, LiveTail *tl) {
+// are not read) and the threads have met at a barrier since.  MOTION: s is a LiveMotionShared whose rel the caller has filled (no barrier needed: the
+// one below comes first); mot takes the pose of the frame before the newest at the final point.  (The prediction a new frame starts from needs nothing
+// here: the host puts it into the slot header, where a caller's start pose would be.)
+template <bool TAIL, bool BANK, bool MOTION = false>
+__device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s, LiveTail *tl, double *mot = nullptr) {
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform
     const int W = a.W;
     TrackArgs ta;
@@ -474,7 +500,7 @@ __device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s,
     __syncthreads();
     bool prior = false;   // the marginal prior is on the first window frame (tail instance only)
     if constexpr (TAIL) prior = a.marginal && a.has_marginal && wv == 0;
-    live_eval<true, BANK>(a, ta, s, wv, lane);   // init: the first evaluation also yields the first step's system
+    live_eval<true, BANK, MOTION>(a, ta, s, wv, lane);   // init: the first evaluation also yields the first step's system
     if constexpr (TAIL) { if (prior) live_prior<true>(s, *tl, lane); }
     __syncthreads();
     double currData = 0.0, currPrior = 0.0;
@@ -485,7 +511,7 @@ __device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s,
     int mustExit = 0, iters = 0, rejected = 0, tries = 0;
     for (int it = 0; it < a.max_iters && !mustExit && rows > 0; it++) {
         if (it > 0) {
-            live_eval<true, BANK>(a, ta, s, wv, lane);   // H, b at the current point (its costs are those already held)
+            live_eval<true, BANK, MOTION>(a, ta, s, wv, lane);   // H, b at the current point (its costs are those already held)
             if constexpr (TAIL) { if (prior) live_prior<true>(s, *tl, lane); }
             __syncthreads();
         }
@@ -502,7 +528,7 @@ __device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s,
         do {
             if (wv == 0) live_solve(s, W, mu);
             __syncthreads();
-            live_eval<false, BANK>(a, ta, s, wv, lane);
+            live_eval<false, BANK, MOTION>(a, ta, s, wv, lane);
             if constexpr (TAIL) { if (prior) live_prior<false>(s, *tl, lane); }
             __syncthreads();
             double eD = 0.0, eP = 0.0, d2 = 0.0, dg = 0.0;
@@ -543,6 +569,10 @@ __device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s,
     }
     if (t >= 128 && t < 128 + W) { a.Ef[t - 128] = s.Ef[0][t - 128]; a.Pe[t - 128] = s.Pe[0][t - 128]; }
     if (t >= 192 && t < 198) { a.res[8 + t - 192] = s.z[W - 1][t - 192]; a.res[14 + t - 192] = s.z[0][t - 192]; }
+    if constexpr (MOTION) {
+        // the frame before the newest: the window's, or with a window of one frame the anchor (zeros before there is one)
+        if (t >= 200 && t < 206) mot[t - 200] = W >= 2 ? s.z[W - 2][t - 200] : (a.has_anchor ? s.za[t - 200] : 0.0);
+    }
     if (t == 64) {
         a.res[0] = (double)iters; a.res[1] = (double)mustExit; a.res[2] = (double)rejected; a.res[3] = initial;
         a.res[4] = currErr; a.res[5] = currData; a.res[6] = currPrior; a.res[7] = mu;
@@ -553,10 +583,14 @@ __device__ __forceinline__ void live_push_body(const LiveArgs &a, LiveShared &s,
         const int do_marginal = a.marginal && W == a.slots, do_cov = a.covariance;
         __syncthreads();   // the stores above have read the costs this assembly writes again
         if (do_marginal || do_cov) {
-            live_eval<true, BANK>(a, ta, s, wv, lane);
+            live_eval<true, BANK, MOTION>(a, ta, s, wv, lane);
             if (prior) live_prior<true>(s, *tl, lane);
             __syncthreads();
-            if (wv == 0) live_tail<BANK>(s, *tl, a.unc, W, do_marginal, do_cov, live_lam<BANK>(a, s, 1, 0), live_lam<BANK>(a, s, 1, 1), lane);
+            if (wv == 0) {
+                // the motion instances take the tail inline: no call frame, no scratch
+                if constexpr (MOTION) live_tail_body<BANK, true>(s, *tl, a.unc, W, do_marginal, do_cov, live_lam<BANK>(a, s, 1, 0), live_lam<BANK>(a, s, 1, 1), lane);
+                else live_tail<BANK>(s, *tl, a.unc, W, do_marginal, do_cov, live_lam<BANK>(a, s, 1, 0), live_lam<BANK>(a, s, 1, 1), lane);
+            }
         } else if (t < 3) {
             a.unc[t] = 0.0;   // LIVE_UNC_VALID, _HAS, _DROP: the window is still filling
         }
@@ -574,18 +608,27 @@ __global__ void __launch_bounds__(256) k_live_push(const LiveArgs a) {
     live_push_body<TAIL, false>(a, s, tl);
 }
 
-// The bank (DESIGN.md section 22): workgroup b is member b.  Its LiveArgs: the shared block, the member's row of the table and, from the device's
-// own memory, what differs by member and push -- the window's detection counts and whether the new frame brings a start pose (slot headers),
-// whether a marginal prior exists (the member's uncertainty record), rows.  Everything is indexed by blockIdx.x alone, hence wave-uniform; the
-// workgroups of a launch share nothing but read-only tables.
+// The constant-velocity instance: k_live_push with an expected motion on every pair, measured by the host when the pair's
+// second frame was pushed and carried in the kernel arguments.
 template <bool TAIL>
-__global__ void __launch_bounds__(256) k_live_push_bank(const LiveBankArgs ba) {
-    __shared__ LiveBankShared s;
+__global__ void __launch_bounds__(256) k_live_push_cv(const LiveMotionArgs ma) {
+    __shared__ LiveMotionShared s;
     LiveTail *tl = nullptr;
     if constexpr (TAIL) {
         __shared__ LiveTail tail;
         tl = &tail;
     }
+    const int t = threadIdx.x;
+    if (t < 6 * ma.a.W) s.rel[t / 6][t % 6] = ma.rel[t / 6][t % 6];
+    live_push_body<TAIL, false, true>(ma.a, s, tl, ma.mot);
+}
+
+// The bank (DESIGN.md section 22): workgroup b is member b.  Its LiveArgs: the shared block, the member's row of the table and, from the device's
+// own memory, what differs by member and push -- the window's detection counts and whether the new frame brings a start pose (slot headers),
+// whether a marginal prior exists (the member's uncertainty record), rows.  Everything is indexed by blockIdx.x alone, hence wave-uniform; the
+// workgroups of a launch share nothing but read-only tables.
+template <bool TAIL, bool MOTION = false>
+__device__ __forceinline__ void live_member_body(const LiveBankArgs &ba, LiveBankShared &s, LiveTail *tl, double *mot = nullptr) {
     const int t = threadIdx.x;
     const LiveMember *m = ba.tab + blockIdx.x;
     LiveArgs a;
@@ -613,14 +656,75 @@ __global__ void __launch_bounds__(256) k_live_push_bank(const LiveBankArgs ba) {
     for (int i = 0; i < W; i++) det += live_cnt<true>(a, s, i);
     const int pairs = a.smooth ? W - 1 + (a.marginal ? a.has_marginal : a.has_anchor) : 0;
     a.rows = 8.0 * (double)det + 6.0 * (double)pairs;
-    live_push_body<TAIL, true>(a, s, tl);
+    live_push_body<TAIL, true, MOTION>(a, s, tl, mot);
+}
+
+template <bool TAIL>
+__global__ void __launch_bounds__(256) k_live_push_bank(const LiveBankArgs ba) {
+    __shared__ LiveBankShared s;
+    LiveTail *tl = nullptr;
+    if constexpr (TAIL) {
+        __shared__ LiveTail tail;
+        tl = &tail;
+    }
+    live_member_body<TAIL>(ba, s, tl);
+}
+
+// The gated single tracker with the motion model: the bank's instance on its one-row table (ONE workgroup), the expected motions in the arguments
+// as in k_live_push_cv.
+template <bool TAIL>
+__global__ void __launch_bounds__(256) k_live_push_member_cv(const LiveMemberMotionArgs ga) {
+    __shared__ LiveBankMotionShared s;
+    LiveTail *tl = nullptr;
+    if constexpr (TAIL) {
+        __shared__ LiveTail tail;
+        tl = &tail;
+    }
+    const int t = threadIdx.x;
+    if (t >= 128 && t < 128 + 6 * ga.ba.sh.W) s.rel[(t - 128) / 6][(t - 128) % 6] = ga.rel[(t - 128) / 6][(t - 128) % 6];
+    live_member_body<TAIL, true>(ga.ba, s, tl, ga.mot);
+}
+
+// The bank with the motion model: member b's expected motions lie behind the members' slots of every ring slot, [B][6] doubles at rel_off, and
+// came in with the frame that ends the pair (the bank's one copy); they are read where lam is, into LDS by window position.
+template <bool TAIL>
+__global__ void __launch_bounds__(256) k_live_push_bank_cv(const LiveBankMotionArgs ga) {
+    __shared__ LiveBankMotionShared s;
+    LiveTail *tl = nullptr;
+    if constexpr (TAIL) {
+        __shared__ LiveTail tail;
+        tl = &tail;
+    }
+    const int t = threadIdx.x;
+    if (t >= 128 && t < 128 + 6 * ga.ba.sh.W) {
+        const int i = (t - 128) / 6;
+        int sl = ga.ba.sh.first_slot + i;
+        if (sl >= ga.ba.sh.slots) sl -= ga.ba.sh.slots;
+        s.rel[i][(t - 128) % 6] = reinterpret_cast<const double *>(ga.ring + (size_t)sl * ga.ba.sh.slot_bytes + ga.rel_off)[6 * blockIdx.x + (t - 128) % 6];
+    }
+    live_member_body<TAIL, true>(ga.ba, s, tl, ga.mot + LIVE_MOT_DOUBLES * blockIdx.x);
 }
 
 }  // namespace
 
+void launch_live_push_bank_motion(const LiveBankMotionArgs &a, int B, hipStream_t st) {
+    if (a.ba.sh.marginal || a.ba.sh.covariance) hipLaunchKernelGGL(k_live_push_bank_cv<true>, dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_live_push_bank_cv<false>, dim3(B), dim3(256), 0, st, a);
+}
+
 void launch_live_push_bank(const LiveBankArgs &a, int B, hipStream_t st) {
     if (a.sh.marginal || a.sh.covariance) hipLaunchKernelGGL(k_live_push_bank<true>, dim3(B), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_live_push_bank<false>, dim3(B), dim3(256), 0, st, a);
+}
+
+void launch_live_push_member_motion(const LiveMemberMotionArgs &a, hipStream_t st) {
+    if (a.ba.sh.marginal || a.ba.sh.covariance) hipLaunchKernelGGL(k_live_push_member_cv<true>, dim3(1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_live_push_member_cv<false>, dim3(1), dim3(256), 0, st, a);
+}
+
+void launch_live_push_motion(const LiveMotionArgs &a, hipStream_t st) {
+    if (a.a.marginal || a.a.covariance) hipLaunchKernelGGL(k_live_push_cv<true>, dim3(1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_live_push_cv<false>, dim3(1), dim3(256), 0, st, a);
 }
 
 void launch_live_push(const LiveArgs &a, hipStream_t st) {

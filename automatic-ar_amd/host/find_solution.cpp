@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -270,8 +270,13 @@ int main(int argc, char *argv[]) {
     bool live_gate = false;
     int gate_args = 0;
     double gate_v[2] = {0.0, 0.0};
+    // ... -motion cv [<max_dt>] gives every pair the motion expected from the two newest estimates, constant velocity (needs
+    // the sigmas); no prediction across a gap of frame ids above max_dt (0 or absent: no limit); -motion rw is the default, the random walk
+    bool live_motion = false;
+    int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
+    double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Live, Anchor, Gate } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Live, Anchor, Gate, Motion } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -299,6 +304,20 @@ int main(int argc, char *argv[]) {
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
         else if (a == "-gate") { live_gate = true; gate_args = 0; arg_flag = Gate; }
+        else if (a == "-motion") { live_motion = true; motion_args = 0; arg_flag = Motion; }
+        else if (arg_flag == Motion && motion_args == 0) {
+            if (a != "cv" && a != "rw") return print_usage(argv[0]);
+            motion_model = a == "cv" ? AAR_TRACKER_MOTION_CONSTANT_VELOCITY : AAR_TRACKER_MOTION_RANDOM_WALK;
+            motion_args = 1;
+        }
+        else if (arg_flag == Motion && !a.empty() && a[0] != '-') {   // the optional max_dt
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || !(v >= 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            motion_max_dt = v;
+            motion_args = 2;
+            arg_flag = NONE;
+        }
         else if (arg_flag == Gate) {
             char *end = nullptr;
             const double v = strtod(a.c_str(), &end);
@@ -382,6 +401,7 @@ int main(int argc, char *argv[]) {
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
     if (live_gate && (!live || gate_args != 2 || (gate_v[0] <= 0.0 && gate_v[1] <= 0.0))) return print_usage(argv[0]);
+    if (live_motion && (!live || motion_args < 1 || (motion_model == AAR_TRACKER_MOTION_CONSTANT_VELOCITY && live_args != 3))) return print_usage(argv[0]);
     if (from_detections && (!live || from_initial || use_subseqs || !excluded_cams.empty())) return print_usage(argv[0]);
     string name = "";
     if (tracking_only) name += "_tracking_only";
@@ -495,18 +515,23 @@ int main(int argc, char *argv[]) {
         gate_params.k_median = gate_v[0];
         gate_params.min_px = gate_v[1];
         const aar_tracker_gate_params *want_gate = live_gate ? &gate_params : nullptr;
+        aar_tracker_motion_params motion_params;
+        aar_tracker_default_motion_params(&motion_params);
+        motion_params.model = motion_model;
+        motion_params.max_dt = motion_max_dt;
+        const aar_tracker_motion_params *want_motion = live_motion ? &motion_params : nullptr;
         try {
             if (from_detections) {
                 aar_detections *detections = aar::Initializer::read_detections_file(folder_path + "/aruco.detections", vector<int>());
                 try {
-                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy, live_anchor, want_cov, want_gate);
+                    mcm.track_live_from_detections(detections, cam_models, live_lag, live_args == 3, live_sigma[0], live_sigma[1], start_policy, live_anchor, want_cov, want_gate, want_motion);
                 } catch (...) {
                     aar_detections_free(detections);
                     throw;
                 }
                 aar_detections_free(detections);
             } else {
-                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1], live_anchor, want_cov, want_gate);
+                mcm.track_live(live_lag, live_args == 3, live_sigma[0], live_sigma[1], live_anchor, want_cov, want_gate, want_motion);
             }
             long long its = 0, rej = 0;
             double sec = 0, cost = 0;
@@ -517,6 +542,11 @@ int main(int argc, char *argv[]) {
                 long long held = 0, won = 0;
                 for (const aar_tracker_start_info &si : mcm.live_starts) { held += si.voted; won += si.start_source == 2; }
                 cout << "votes: " << held << " held, " << won << " won (start policy " << (start_policy == AAR_TRACKER_START_BEST ? "best" : "vote") << ")" << endl;
+            }
+            if (!mcm.live_motions.empty()) {
+                long long predicted = 0;
+                for (const aar_tracker_motion_info &m : mcm.live_motions) predicted += m.predicted;
+                cout << "motion: constant velocity, " << predicted << " of " << mcm.live_motions.size() << " pushes with an expected motion (max_dt " << motion_max_dt << ")" << endl;
             }
             if (live_gate) {
                 long long rejected = 0, frames = 0, small = 0;

@@ -611,6 +611,13 @@ void start_live_gate(LiveTracker &lt, const aar_tracker_gate_params *gate, int F
     lt.enable_gate(gate);
     out.assign((size_t)F, aar_tracker_gate_info());
 }
+// the motion model on (motion != NULL), and room for every frame's record
+void start_live_motion(LiveTracker &lt, const aar_tracker_motion_params *motion, int F, std::vector<aar_tracker_motion_info> &out) {
+    out.clear();
+    if (!motion) return;
+    lt.enable_motion(motion);
+    if (motion->model != AAR_TRACKER_MOTION_RANDOM_WALK) out.assign((size_t)F, aar_tracker_motion_info());
+}
 void size_live_covariance(MultiCamMapper::LiveCovariance *cov, int F) {
     if (!cov) return;
     cov->frame_cov.assign(36 * (size_t)F, 0.0);
@@ -620,7 +627,7 @@ void size_live_covariance(MultiCamMapper::LiveCovariance *cov, int F) {
 }  // namespace
 
 void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double sigma_trans, int anchor_mode, LiveCovariance *covariance,
-                                const aar_tracker_gate_params *gate) {
+                                const aar_tracker_gate_params *gate, const aar_tracker_motion_params *motion) {
     if (!data_) throw std::runtime_error("MultiCamMapper::track_live: no data set");
     hubberDelta = 10;  // as track()
     const int F = data_->num_frames;
@@ -635,6 +642,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
     LiveTracker lt(*this, o, &solver_params);
     size_live_covariance(covariance, F);
     start_live_gate(lt, gate, F, live_gates);
+    start_live_motion(lt, motion, F, live_motions);
     PoseLayout L;
     L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
     std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
@@ -652,6 +660,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
         const aar_tracker_result r = lt.push((double)data_->frame_ids[f], det, data_->x_full + L.full_fr0() + 6LL * f);
         live_results[f] = r;
         if (gate) live_gates[f] = lt.last_gate();
+        if (!live_motions.empty()) live_motions[f] = lt.last_motion();
         take_live_covariance(lt, covariance);
         if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
     }
@@ -663,7 +672,7 @@ void MultiCamMapper::track_live(int lag, bool smooth, double sigma_rot, double s
 
 void MultiCamMapper::track_live_from_detections(const aar_detections *det, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
                                                 double sigma_trans, int start_policy, int anchor_mode, LiveCovariance *covariance,
-                                                const aar_tracker_gate_params *gate) {
+                                                const aar_tracker_gate_params *gate, const aar_tracker_motion_params *motion) {
     if (!data_ || !det) throw std::runtime_error("MultiCamMapper::track_live_from_detections: no data set / no detections");
     hubberDelta = 10;  // as track()
     const int F = data_->num_frames;
@@ -690,6 +699,7 @@ void MultiCamMapper::track_live_from_detections(const aar_detections *det, const
     dopt.start_policy = start_policy;
     lt.enable_detections(dopt);
     start_live_gate(lt, gate, F, live_gates);
+    start_live_motion(lt, motion, F, live_motions);
     PoseLayout L;
     L.C = data_->num_cams; L.M = data_->num_markers; L.F = F;
     std::vector<double> z(data_->x_full + L.full_fr0(), data_->x_full + L.full_fr0() + 6LL * F);
@@ -710,6 +720,7 @@ void MultiCamMapper::track_live_from_detections(const aar_detections *det, const
         const aar_tracker_result r = lt.push_detections((double)data_->frame_ids[f], dets, nullptr, &live_starts[f]);
         live_results[f] = r;
         if (gate) live_gates[f] = lt.last_gate();
+        if (!live_motions.empty()) live_motions[f] = lt.last_motion();
         take_live_covariance(lt, covariance);
         if (r.has_lagged) memcpy(&z[6 * (size_t)r.lagged_index], r.lagged_pose, sizeof r.lagged_pose);
     }
@@ -851,6 +862,26 @@ void LiveTracker::enable_gate(const aar_tracker_gate_params *params) {
     if (aar_tracker_enable_gate(tracker_, params ? params : &p)) throw std::runtime_error(aar_last_error());
 }
 
+void LiveTracker::enable_motion(const aar_tracker_motion_params *params) {
+    aar_tracker_motion_params p;
+    aar_tracker_default_motion_params(&p);
+    if (aar_tracker_enable_motion(tracker_, params ? params : &p)) throw std::runtime_error(aar_last_error());
+}
+
+aar_tracker_motion_info LiveTracker::last_motion() {
+    aar_tracker_motion_info m;
+    memset(&m, 0, sizeof m);
+    m.struct_size = (uint32_t)sizeof m;
+    if (aar_tracker_last_motion(tracker_, &m)) throw std::runtime_error(aar_last_error());
+    return m;
+}
+
+std::array<double, 6> LiveTracker::predict(double time) {
+    std::array<double, 6> pose;
+    if (aar_tracker_predict(tracker_, time, pose.data())) throw std::runtime_error(aar_last_error());
+    return pose;
+}
+
 aar_tracker_gate_info LiveTracker::last_gate() {
     aar_tracker_gate_info g;
     memset(&g, 0, sizeof g);
@@ -968,6 +999,26 @@ void LiveTrackerBank::enable_gate(const aar_tracker_gate_params *params) {
     aar_tracker_gate_params p;
     aar_tracker_default_gate_params(&p);
     if (aar_tracker_gate_bank_enable(bank_, params ? params : &p)) throw std::runtime_error(aar_last_error());
+}
+
+void LiveTrackerBank::enable_motion(const aar_tracker_motion_params *params) {
+    aar_tracker_motion_params p;
+    aar_tracker_default_motion_params(&p);
+    if (aar_tracker_motion_bank_enable(bank_, params ? params : &p)) throw std::runtime_error(aar_last_error());
+}
+
+aar_tracker_motion_info LiveTrackerBank::last_motion(int member) {
+    aar_tracker_motion_info m;
+    memset(&m, 0, sizeof m);
+    m.struct_size = (uint32_t)sizeof m;
+    if (aar_tracker_motion_bank_last(bank_, member, &m)) throw std::runtime_error(aar_last_error());
+    return m;
+}
+
+std::array<double, 6> LiveTrackerBank::predict(int member, double time) {
+    std::array<double, 6> pose;
+    if (aar_tracker_motion_bank_predict(bank_, member, time, pose.data())) throw std::runtime_error(aar_last_error());
+    return pose;
 }
 
 aar_tracker_gate_info LiveTrackerBank::last_gate(int member) {

@@ -405,14 +405,17 @@ class MultiCamMapper {
         std::vector<uint8_t> valid;      // [num_frames] that push's cov_valid
     };
     // gate != NULL gates every pushed frame on the device (aar_tracker_enable_gate); the gate records land in live_gates.
+    // motion != NULL gives the tracker a motion model (aar_tracker_enable_motion); the motion records land in live_motions.
     void track_live(int lag, bool smooth, double sigma_rot, double sigma_trans, int anchor_mode = AAR_TRACKER_ANCHOR_FIXED,
-                    LiveCovariance *covariance = nullptr, const aar_tracker_gate_params *gate = nullptr);
+                    LiveCovariance *covariance = nullptr, const aar_tracker_gate_params *gate = nullptr,
+                    const aar_tracker_motion_params *motion = nullptr);
     // ... the whole of that loop (:117-133): every frame of the data set is fed the RAW detections that carry its frame id (cams: calibrations by
     // camera ID, as the Initializer takes them) and starts from its own vote (start_policy AAR_TRACKER_START_VOTE) or from the cheaper of vote
     // and previous estimate (AAR_TRACKER_START_BEST); the data set's own object poses are not read.  The starts land in live_starts.
     void track_live_from_detections(const aar_detections *detections, const std::vector<aar_cam_model> &cams, int lag, bool smooth, double sigma_rot,
                                     double sigma_trans, int start_policy = AAR_TRACKER_START_VOTE, int anchor_mode = AAR_TRACKER_ANCHOR_FIXED,
-                                    LiveCovariance *covariance = nullptr, const aar_tracker_gate_params *gate = nullptr);
+                                    LiveCovariance *covariance = nullptr, const aar_tracker_gate_params *gate = nullptr,
+                                    const aar_tracker_motion_params *motion = nullptr);
     bool write_live_covariance_file(const std::string &path, const LiveCovariance &cov);   // YAML, aar_tracker_covariance_write_yaml
     void error_function(const eVector &input, eVector &error);  // :731-737
     // :739-801 (private in the reference; public here so that reference-shaped caller code outside the class can bind it).  The
@@ -449,6 +452,7 @@ class MultiCamMapper {
     std::vector<aar_tracker_result> live_results; // per frame, after track_live()
     std::vector<aar_tracker_start_info> live_starts;   // per frame, after track_live_from_detections()
     std::vector<aar_tracker_gate_info> live_gates;     // per frame, after track_live() / track_live_from_detections() with a gate
+    std::vector<aar_tracker_motion_info> live_motions; // per frame, after track_live() / track_live_from_detections() with a motion model
     int device_id = 0;
     int residual_mode = AAR_RES_F32;
     // How the damped normal equations are solved (aar_solver_options, include/aar.h) -- the counterpart of configuring the reference's solver object
@@ -607,6 +611,12 @@ class LiveTracker {
     void enable_gate(const aar_tracker_gate_params *params = nullptr);
     aar_tracker_gate_info last_gate();                                            // the gate record of the last push
     void gate_detail(std::vector<double> &det_err, std::vector<uint8_t> &keep);   // e_d and keep flags of the newest frame, as pushed to the tracker
+    // the motion model: once after construction or reset(), before the first push; NULL = aar_tracker_default_motion_params
+    // (constant velocity, no max_dt).  Every pair then carries the motion expected from the two newest estimates, and a frame without a start
+    // begins at the prediction
+    void enable_motion(const aar_tracker_motion_params *params = nullptr);
+    aar_tracker_motion_info last_motion();                                        // the motion record of the last push
+    std::array<double, 6> predict(double time);                                   // the newest pose carried to time (host math)
     Window window();
     // aar_tracker_uncertainty: the record of the last push (needs anchor_mode marginal or covariance, and a push since construction / reset)
     aar_tracker_uncertainty_record uncertainty();
@@ -641,6 +651,10 @@ class LiveTrackerBank {
     void enable_gate(const aar_tracker_gate_params *params = nullptr);
     aar_tracker_gate_info last_gate(int member);
     void gate_detail(int member, std::vector<double> &det_err, std::vector<uint8_t> &keep);
+    // LiveTracker::enable_motion / last_motion / predict: one parameter set for all members
+    void enable_motion(const aar_tracker_motion_params *params = nullptr);
+    aar_tracker_motion_info last_motion(int member);
+    std::array<double, 6> predict(int member, double time);
     LiveTracker::Window window(int member);
     aar_tracker_uncertainty_record uncertainty(int member);
     aar_tracker_bank_stats stats() const;

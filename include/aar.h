@@ -657,7 +657,7 @@ int aar_tracker_push(aar_tracker *, double frame_time, int32_t n_obs, const int3
  * cost of the pair that ENDS at the frame (entry 0: the anchor pair, 0 without an anchor), anchor_pose, has_anchor.  Any output may be NULL. */
 int aar_tracker_window(aar_tracker *, int32_t *n, int64_t *frame_index, double *poses, double *frame_err, double *pair_err, double anchor_pose[6],
                        int32_t *has_anchor);
-int aar_tracker_reset(aar_tracker *);     /* forgets all frames, the marginal prior (and aar_tracker_enable_detections / _enable_gate), keeps the solution */
+int aar_tracker_reset(aar_tracker *);     /* forgets all frames, the marginal prior (and aar_tracker_enable_detections / _enable_gate / _enable_motion), keeps the solution */
 
 /* Marginalised anchor and per-push pose covariance.  Both are off by default, and then a push runs the same kernel and
  * gives the same bits as before they existed; with either set a push is still one launch and one copy back.
@@ -729,7 +729,7 @@ typedef struct aar_tracker_start_info {
     int32_t voted;               /* a vote was held */
     int32_t candidates, winner;  /* winner: index in candidate order, -1 = none finite */
     double vote_cost;            /* the winner's summed error (find_best_transformation's weight) */
-    int32_t start_source;        /* 0 pose_init, 1 previous estimate, 2 vote */
+    int32_t start_source;        /* 0 pose_init, 1 previous estimate, 2 vote, 3 motion prediction (aar_tracker_enable_motion) */
     double cost_prediction, cost_vote;  /* new frame's E_f at the two starts (BEST with both a prediction and a winner, else 0) */
     double start_pose[6];
 } aar_tracker_start_info;
@@ -872,6 +872,62 @@ int aar_tracker_gate_detail(aar_tracker *, int32_t *n, double *det_err, uint8_t 
 int aar_tracker_gate_bank_enable(aar_tracker_bank *, const aar_tracker_gate_params *);
 int aar_tracker_gate_bank_last(aar_tracker_bank *, int32_t member, aar_tracker_gate_info *out);
 int aar_tracker_gate_bank_detail(aar_tracker_bank *, int32_t member, int32_t *n, double *det_err, uint8_t *keep);
+
+/* Constant-velocity motion model of the live tracker.  Off by default: a tracker that never enables it (or enables
+ * AAR_TRACKER_MOTION_RANDOM_WALK) runs the kernels, copies the bytes and gives the bits described above.  With the model every pair keeps the
+ * form of aar_track_smooth,
+ *       e_f = [ log((R_f dR_f)^T R_{f+1}) ; t_{f+1} - t_f - dt_f ],   L_f unchanged,
+ * and the pair that ENDS at pushed frame n carries an expected motion rel_n = (dR_n, dt_n) as (rvec, t):
+ *   measured  once, when frame n is pushed, from the two newest estimates as push n - 1 left them (frames a = n - 2 and b = n - 1; with lag 0
+ *             frame a is the anchor): omega = log(R_a^T R_b), v = t_b - t_a, s = (time_n - time_b) / (time_b - time_a), rel_n = (s omega, s v) --
+ *             constant angular velocity in the body frame, constant linear velocity in the root camera's frame, the convention of e_f
+ *   zero      for n < 2, and when max_dt > 0 and either of the two gaps exceeds max_dt (no coasting across a hole in the recording)
+ *   lifetime  rel_n stays with frame n: it serves the window pair, the anchor pair once n - 1 is the anchor, and pair (0, 1) in the
+ *             marginalisation and the covariance of AAR_TRACKER_ANCHOR_MARGINAL / covariance = 1.  It is never measured again.
+ *   start     wherever the text above says "the current estimate of the previous frame", the new frame starts from the prediction
+ *             (R_b exp(s omega), t_b + s v) instead; a pose_init still wins, and rel_n is measured from the estimates either way.
+ * sigma_rot and sigma_trans then bound the deviation from CONSTANT VELOCITY per sqrt(unit of frame_time), no longer the motion itself.  rel_n is
+ * an estimate fed back as a prior and frozen when measured -- the "relative motions of a previous pass" of aar_smooth_params.rel_motion -- which
+ * keeps the system block tridiagonal; a second-difference prior would not.  The expected motions and the prediction are formed on the host in fp64
+ * and travel in the kernel arguments and in the slot header: a push with the model makes the launches and copies of the same push without it.
+ * Independent of aar_tracker_enable_detections and aar_tracker_enable_gate: AAR_TRACKER_START_BEST compares the vote with the prediction
+ * (aar_tracker_start_info.start_source = 3 where it wins), the gate takes e_d there.  A tracker bank takes the model through
+ * aar_tracker_motion_bank_*: one parameter set, every member its own expected motions and prediction; member b stays exactly an aar_tracker
+ * with the model, and a bank push keeps its launches and its one copy each way (the copy in then carries 48 bytes per member more). */
+#define AAR_TRACKER_MOTION_RANDOM_WALK 0
+#define AAR_TRACKER_MOTION_CONSTANT_VELOCITY 1
+typedef struct aar_tracker_motion_params {
+    uint32_t struct_size;
+    int32_t model;               /* AAR_TRACKER_MOTION_* */
+    double max_dt;               /* >= 0 finite, in units of frame_time; 0 = no limit */
+} aar_tracker_motion_params;
+typedef struct aar_tracker_motion_info {
+    uint32_t struct_size;
+    int32_t model, predicted;    /* predicted: the rule measured rel for this push (n >= 2 and no gap above max_dt) */
+    double rel[6];               /* the expected motion this push used (zeros when not predicted) */
+    double velocity[6];          /* (omega, v) per unit of frame_time of the newest pair at the final point; zeros before two frames */
+    double newest_time;
+} aar_tracker_motion_info;
+void aar_tracker_default_motion_params(aar_tracker_motion_params *);   /* struct_size set; AAR_TRACKER_MOTION_CONSTANT_VELOCITY, max_dt 0 */
+/* Host function (no device needed): AAR_ERR_INVALID, the message naming the field, for a struct_size that does not reach model, an unknown
+ * model, a negative or non-finite max_dt, and AAR_TRACKER_MOTION_CONSTANT_VELOCITY with smooth = 0 (there is no prior to carry it). */
+int aar_tracker_motion_params_validate(const aar_tracker_params *, const aar_tracker_motion_params *);
+/* Once after aar_tracker_create or aar_tracker_reset, before the first push; again without a reset, or after a push: AAR_ERR_INVALID.
+ * aar_tracker_reset forgets it.  AAR_TRACKER_MOTION_RANDOM_WALK is accepted and leaves the tracker as if the call were not made. */
+int aar_tracker_enable_motion(aar_tracker *, const aar_tracker_motion_params *);
+/* The motion record of the last accepted push, from its one copy back (no device work).  AAR_ERR_INVALID before any push, after a reset, or
+ * without the model.  A rejected push leaves it as it was. */
+int aar_tracker_last_motion(aar_tracker *, aar_tracker_motion_info *out);
+/* Host math: the newest pose (R_n, t_n) of the last accepted push carried to time >= newest_time with that push's velocity,
+ * (R_n exp((time - t_n) omega), t_n + (time - t_n) v) as (rvec, t); the newest pose itself when max_dt > 0 and time - newest_time > max_dt.
+ * AAR_ERR_INVALID for an earlier or non-finite time, before any push, or without the model.  The pose only: no covariance is propagated. */
+int aar_tracker_predict(aar_tracker *, double time, double pose[6]);
+/* The same for a bank: one parameter set for all members, enabled once after aar_tracker_bank_create or aar_tracker_bank_reset, before the first
+ * push (aar_tracker_bank_reset forgets it); the record and the prediction of one member.  A rejected bank push leaves every member's motion state
+ * as it was.  (Named aar_tracker_motion_bank_*: the set of aar_tracker_bank_* symbols is pinned by tests/test_live_bank_host.py.) */
+int aar_tracker_motion_bank_enable(aar_tracker_bank *, const aar_tracker_motion_params *);
+int aar_tracker_motion_bank_last(aar_tracker_bank *, int32_t member, aar_tracker_motion_info *out);
+int aar_tracker_motion_bank_predict(aar_tracker_bank *, int32_t member, double time, double pose[6]);
 
 #ifdef __cplusplus
 }

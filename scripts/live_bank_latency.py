@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--pushes", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--gate", action="store_true", help="also push a gated bank (k_median 6, min_px 3), interleaved with the ungated one")
+    ap.add_argument("--motion", action="store_true", help="also push every smoothed bank with the constant-velocity motion model (DESIGN.md section 25), interleaved")
+    ap.add_argument("--lags", type=int, nargs="+", default=[4], help="lags of the smoothed banks")
     a = ap.parse_args()
     n, w = a.pushes + a.warmup, a.warmup
     ds = aar.synth(3, num_frames=n)
@@ -59,15 +61,18 @@ def main():
     L = aar.lib()
     ip, fp, dp = C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double)
     medians = {}
-    for label, kw in (("smooth 0", dict(lag=0, smooth=False)), ("smooth 1 lag 4", dict(lag=4, smooth=True, sigma_rot=0.05, sigma_trans=0.02))):
+    modes = [("smooth 0", dict(lag=0, smooth=False))] + [("smooth 1 lag %d" % lag, dict(lag=lag, smooth=True, sigma_rot=0.05, sigma_trans=0.02)) for lag in a.lags]
+    for label, kw in modes:
         print("%s" % label)
         for B in a.members:
             src = [[(f + 7 * b) % n for b in range(B)] for f in range(n)]           # the recording's frame member b is fed at push f
             # ---- the bank ----
-            wall, gwall = [], []
+            wall, gwall, mwall = [], [], []
+            mot = a.motion and kw["smooth"]
             with aar.TrackerBank([sol] * B, max_obs_per_frame=most, **kw) as k, \
-                    aar.TrackerBank([sol] * (B if a.gate else 1), max_obs_per_frame=most, gate={} if a.gate else None, **kw) as kg:
-                res, gres = k.result_array(), kg.result_array()
+                    aar.TrackerBank([sol] * (B if a.gate else 1), max_obs_per_frame=most, gate={} if a.gate else None, **kw) as kg, \
+                    aar.TrackerBank([sol] * (B if mot else 1), max_obs_per_frame=most, motion="cv" if mot else None, **kw) as km:
+                res, gres, mres = k.result_array(), kg.result_array(), km.result_array()
                 for f in range(n):
                     args, keep = k.pack([obs[s] for s in src[f]], [z0[s] for s in src[f]])
                     t0 = time.perf_counter()
@@ -79,8 +84,14 @@ def main():
                         rc = L.aar_tracker_bank_push(kg.handle, float(f), *args, gres)
                         gwall.append(time.perf_counter() - t0)
                         assert rc == 0, L.aar_last_error()
+                    if mot:
+                        t0 = time.perf_counter()
+                        rc = L.aar_tracker_bank_push(km.handle, float(f), *args, mres)
+                        mwall.append(time.perf_counter() - t0)
+                        assert rc == 0, L.aar_last_error()
                 st = k.stats()
                 gst = kg.stats()
+                mst = km.stats()
                 its = np.mean([r.iterations for r in res])
             # ---- what the parent offers: B trackers pushed one after the other ----
             seq = []
@@ -111,6 +122,10 @@ def main():
             if a.gate:
                 print("  B %4d   + gate    %s   gate adds %.1f us per push (difference of the medians)   copied out %d bytes   launches per push %.0f" % (
                     B, stats(gwall[w:]), 1e6 * (np.median(gwall[w:]) - mb), gst["d2h_bytes"] // gst["pushes"], gst["launches"] / gst["pushes"]))
+            if mot:
+                print("  B %4d   + motion  %s   motion model adds %.1f us per push (difference of the medians)   copied per push: in %d bytes, out %d bytes   "
+                      "launches per push %.0f" % (B, stats(mwall[w:]), 1e6 * (np.median(mwall[w:]) - mb), mst["h2d_bytes"] // mst["pushes"],
+                                                  mst["d2h_bytes"] // mst["pushes"], mst["launches"] / mst["pushes"]))
     ok = all(medians[(label, 8)][0] < medians[(label, 8)][1] for label, B in medians if B == 8)
     print("condition (B = 8: bank push median below the eight sequential pushes together): %s" % ("met" if ok else "NOT MET"))
     return 0 if ok else 1

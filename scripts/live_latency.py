@@ -11,8 +11,11 @@ trace's call count of k_live_push must equal it.
 
     python scripts/live_latency.py --gate       # every tracker a second time with the gate on, push by push beside the
                                                 # ungated one (same build, same frames, interleaved); prints the added time per push
+    python scripts/live_latency.py --motion     # every smoothed tracker a second time with the constant-velocity model,
+                                                # interleaved in the same way (k_live_push_cv in place of k_live_push)
 """
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -50,6 +53,7 @@ def main():
     ap.add_argument("--pushes", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--gate", action="store_true", help="also run every tracker gated (k_median 6, min_px 3), interleaved with the ungated one")
+    ap.add_argument("--motion", action="store_true", help="also run every smoothed tracker with the constant-velocity motion model, interleaved")
     a = ap.parse_args()
     n = a.pushes + a.warmup
     total = total_det = 0
@@ -81,8 +85,11 @@ def main():
             if kw["smooth"]:
                 kw.update(sigma_rot=0.05, sigma_trans=0.02)
             wall, lib, its = [], [], []
-            gwall, kept = [], []
-            with aar.Tracker(sol, max_obs_per_frame=most, **kw) as t, aar.Tracker(sol, max_obs_per_frame=most, gate={} if a.gate else None, **kw) as tg:
+            gwall, kept, mwall, mits = [], [], [], []
+            with contextlib.ExitStack() as stack:
+                t = stack.enter_context(aar.Tracker(sol, max_obs_per_frame=most, **kw))
+                tg = stack.enter_context(aar.Tracker(sol, max_obs_per_frame=most, gate={} if a.gate else None, **kw))
+                tm = stack.enter_context(aar.Tracker(sol, max_obs_per_frame=most, motion="cv", **kw)) if a.motion and kw["smooth"] else None
                 for f in range(n):
                     t0 = time.perf_counter()
                     g = t.push(float(f), *obs[f], pose_init=z0[f])
@@ -95,11 +102,19 @@ def main():
                         tg.push(float(f), *obs[f], pose_init=z0[f])
                         gwall.append(time.perf_counter() - t0)
                         kept.append(tg.last_gate()["n_kept"] / max(len(obs[f][0]), 1))
+                    if a.motion and kw["smooth"]:
+                        t0 = time.perf_counter()
+                        g = tm.push(float(f), *obs[f], pose_init=z0[f])
+                        mwall.append(time.perf_counter() - t0)
+                        mits.append(g["iterations"])
             w = a.warmup
             print("  %-16s push %s   inside the library %s   %.1f LM iterations per push" % (label, stats(wall[w:]), stats(lib[w:]), np.mean(its[w:])))
             if a.gate:
                 print("  %-16s push %s   gate adds %.1f us per push (difference of the medians), %.1f%% of the detections kept" % (
                     "  + gate", stats(gwall[w:]), 1e6 * (np.median(gwall[w:]) - np.median(wall[w:])), 100 * np.mean(kept[w:])))
+            if a.motion and kw["smooth"]:
+                print("  %-16s push %s   motion model adds %.1f us per push (difference of the medians), %.1f LM iterations per push" % (
+                    "  + motion cv", stats(mwall[w:]), 1e6 * (np.median(mwall[w:]) - np.median(wall[w:])), np.mean(mits[w:])))
         frames = [one_frame(ds, f, x0) for f in range(n)]
         wall, its = [], []
         prm = aar.lm_default_params()
