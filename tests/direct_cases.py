@@ -1,4 +1,5 @@
-"""The data sets of the direct chain's certificates (tests/test_direct_certificate_host.py, tests/test_gpu_direct_certificates.py), by name --
+"""The data sets of the direct chain's certificates (tests/test_direct_certificate_host.py, tests/test_gpu_direct_certificates.py, and the runs of
+tests/test_direct_run_certificate_host.py, tests/test_gpu_speculative_path.py), by name --
 TEST INFRASTRUCTURE ONLY.  Every builder returns a synthetic aar.Dataset; the shapes are the smallest at which the launch shape under test exists.
 
 Rows of the device's reduced system: six per camera and marker, ROOTS INCLUDED (identity rows), cameras first -- so the root marker of a set
@@ -9,6 +10,8 @@ import threading
 import numpy as np
 
 import aar
+from pair_priors_restated import pose_of
+from reduced_system import rodrigues, slot_col, so3_log
 
 
 def tiles_of(ds, intrinsics=False):
@@ -189,3 +192,103 @@ def run_ranks(world, fn):
     grp.close()
     assert not errs, errs
     return out
+
+
+# ---- the LM runs of the speculative path (tests/test_direct_run_certificate_host.py finds on the CPU that every one offers its predicted steps;
+# tests/test_gpu_speculative_path.py runs them on the device) ----
+def passa_cut_ds():
+    """two tiles, 24 frames, five of them cut down to SMALL_TARGETS slots: frames with fewer slots than a wavefront has lanes"""
+    return cut_frames(worklist_ds(24), SMALL_TARGETS)[0]
+
+
+def sparse_view_ds():
+    """two tiles, 24 frames, markers seen only close to head-on: between 15 and 30 observations per frame"""
+    return aar.synth(2, num_cams=4, num_markers=20, num_frames=24, min_view_cos=0.5, seed=324)
+
+
+def far_start_ds():
+    """config 2 cut to 40 frames, started twenty times as far from the solution as the default: with tau = 1e-6 its run has rejected tries,
+    accepted steps with a gain below 0.94 and predicted steps (the set of test_steps_of_a_run_with_rejected_tries)"""
+    return aar.synth(2, num_frames=40, init_scale=20.0)
+
+
+def fixed_entities(ds):
+    fc = [c for c in range(ds.num_cams) if c != ds.root_cam][:2]
+    fm = [m for m in range(ds.num_markers) if m != ds.root_marker][3:4]
+    return dict(fixed_cams=fc, fixed_markers=fm)
+
+
+def camera_priors(ds, x):
+    """a pose prior on every camera but the root, near its pose at x"""
+    rng = np.random.default_rng(3)
+    pr = []
+    for c in range(ds.num_cams):
+        if c != ds.root_cam:
+            col = slot_col(ds, "camera", c)
+            A = rng.standard_normal((6, 6))
+            pr.append(("camera", c, x[col:col + 6] + np.r_[0.02 * rng.standard_normal(3), 0.01 * rng.standard_normal(3)], 1e3 * (A @ A.T + 6 * np.eye(6))))
+    return pr
+
+
+def marker_pair_priors(ds, x, n=6):
+    """relative pose priors between n pairs of neighbouring markers (one with a root end), near their relative poses at x"""
+    rng = np.random.default_rng(5)
+    free = [m for m in range(ds.num_markers) if m != ds.root_marker]
+    ends = [(ds.root_marker, free[0])] + [(free[2 * i + 1], free[2 * i + 2]) for i in range(n - 1)]
+    out = []
+    for a, b in ends:
+        xa, xb = pose_of(ds, x, "marker", a), pose_of(ds, x, "marker", b)
+        Ra, Rb = rodrigues(xa[:3]), rodrigues(xb[:3])
+        u = rng.standard_normal(3)
+        Rrel = Ra.T @ Rb @ rodrigues(0.02 * u / np.linalg.norm(u)).T
+        A = rng.standard_normal((6, 6))
+        out.append(("marker", a, b, np.r_[so3_log(Rrel), Ra.T @ (xb[3:] - xa[3:]) + 0.02 * rng.standard_normal(3)], 1e2 * (A @ A.T + 6 * np.eye(6))))
+    return out
+
+
+def _golden(name):
+    from conftest import load_golden
+    return load_golden(name)[0]
+
+
+# name -> (data set, Problem options beside solver [priors / pair_priors / fixed as the strings the callers resolve], tau, predicted steps the run
+# must offer among its first ten)
+SPEC_RUNS = {
+    "passa_cut": (passa_cut_ds, {}, 1.0, 3), "avg_le_14": (lambda: sweep_ds(1), {}, 1.0, 3), "avg_15_30": (sparse_view_ds, {}, 1.0, 3),
+    "avg_31_96": (lambda: worklist_ds(24), {}, 1.0, 3), "avg_gt_96": (lambda: sweep_ds(5), {}, 1.0, 3),
+    "wide_84": (lambda: wide_frames_ds(84), {}, 1.0, 3), "worklist_F60": (lambda: worklist_ds(60), {}, 1.0, 3),
+    "huber": (lambda: _golden("g1_cfg2_huber"), dict(with_huber=True, huber_delta=2.5), 1.0, 3),
+    "intrinsics": (lambda: _golden("g1_cfg2_intr"), dict(intrinsics=True), 1.0, 3),
+    "priors": (lambda: _golden("g1_cfg3_cut"), dict(priors="camera", pair_priors="marker"), 1.0, 3),
+    "fixed": (lambda: gauge_ds(16, 3), dict(fixed=True), 1.0, 3),
+    "cams_off": (lambda: gauge_ds(16, 3), dict(optimize=(False, True, True)), 1.0, 3),
+    "markers_off": (lambda: gauge_ds(16, 3), dict(optimize=(True, False, True)), 1.0, 3),
+    "frames_off": (lambda: gauge_ds(16, 3), dict(optimize=(True, True, False)), 1.0, 3),
+    "sweep1": (lambda: sweep_ds(1), {}, 1.0, 3), "sweep2": (lambda: sweep_ds(2), {}, 1.0, 3), "sweep3": (lambda: sweep_ds(3), {}, 1.0, 3),
+    "sweep5": (lambda: sweep_ds(5), {}, 1.0, 3),
+    "far_start": (far_start_ds, {}, 1e-6, 3),
+}
+for _F in (1, 2, 3, 5, 9):
+    SPEC_RUNS["mfma_F%d" % _F] = (lambda F=_F: mfma_frames_ds(F), {}, 1.0, 3)
+for _e in (30, 31, 32):
+    SPEC_RUNS["dense_%d" % (_e + 1)] = (lambda e=_e: dense_count_ds(e), {}, 1.0, 3)
+
+
+def spec_run(name):
+    """(ds, x0, Problem keyword arguments, tau, minimum of predicted steps, huber delta or None) of a named run"""
+    make, opts, tau, need = SPEC_RUNS[name]
+    ds = make()
+    kw = dict(opts)
+    x = np.asarray(ds.x_full, dtype=np.float64)
+    huber = kw.pop("huber_delta", None)
+    if kw.pop("fixed", False):
+        kw.update(fixed_entities(ds))
+    if kw.get("priors") == "camera":
+        kw["priors"] = camera_priors(ds, x)
+    if kw.get("pair_priors") == "marker":
+        kw["pair_priors"] = marker_pair_priors(ds, x)
+    if kw.get("intrinsics"):
+        K = np.asarray(ds.cam_mats, dtype=np.float64).reshape(-1, 9)
+        d = np.asarray(ds.dist_coeffs, dtype=np.float64).reshape(-1, 5)
+        x = np.concatenate([x, np.concatenate([np.stack([K[:, 0], K[:, 2], K[:, 4], K[:, 5]], axis=1), d], axis=1).reshape(-1)])
+    return ds, x, kw, tau, need, huber

@@ -13,7 +13,9 @@ Steps of a run: the take-back of the Schur complement (launch_schur with sign -1
 eliminated (blocks_valid = false) and a rejected step's blocks are rebuilt from the observations before the re-damped Schur complement and
 factorisation.  The take-back runs in damped_try (ba_capi.hip, "the speculative Schur complement was taken with another damping") on the first try
 after a step that was ACCEPTED with gain < 0.94, whose speculative complement used mu / 3.  test_steps_of_a_run_with_rejected_tries certifies
-both kinds: accepted steps with tries > 1, and steps that follow an accepted step with gain < 0.94.
+both kinds: accepted steps with tries > 1, and steps that follow an accepted step with gain < 0.94.  Both are repairs of the speculative path; a
+correctly predicted step -- no k_frame_inv, no Schur launch of its own, pass A's inverses and panels -- is certified in
+tests/test_gpu_speculative_path.py.
 
 Ratios: every certified step's |r| / bar and worst frame ratio are collected per family and printed when the module finishes (run with -s):
 steps, worst, median.  The float64 reference's ratios on the same data sets are in tests/test_direct_certificate_host.py (worst 1.1e-3, medians
@@ -28,6 +30,7 @@ import oracle_lib as ol
 from conftest import load_golden
 from direct_cases import ldl_env as _ldl_env, ldl_expected as _ldl_expected, run_ranks as _run_ranks
 from direct_certificate import build_system, certify_direct, entity_blocks
+from direct_run_certificate import mu_used as _mu_used
 from reduced_system import slot_col
 
 pytestmark = pytest.mark.gpu
@@ -250,6 +253,9 @@ def test_mfma_schur_frame_pieces(split, monkeypatch):
 @pytest.mark.parametrize("passa", ["0", "1"])
 @pytest.mark.parametrize("F", [1, 2, 3, 4, 5, 8, 9])
 def test_mfma_schur_short_frame_lists(F, passa, monkeypatch):
+    # (these one-off steps do NOT read pass A's panels: eval_damped_step asks pass A for no predicted damping, so the panels come from k_schur_fill
+    #  and the inverses from k_frame_inv whatever AAR_DENSE_FROM_PASSA says -- both parameter values run the same code here.  Where the switch
+    #  selects code, inside an LM run, it is certified by tests/test_gpu_speculative_path.py)
     monkeypatch.setenv("AAR_SCHUR_MFMA", "1")
     monkeypatch.setenv("AAR_DENSE_FROM_PASSA", passa)
     ds = dc.mfma_frames_ds(F)
@@ -338,15 +344,6 @@ def test_sharded_system_as_it_lies_and_packed(world, nT, pack, monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # steps of a run with rejected tries
-def _mu_used(trace, k, mu0):
-    """damping of the ACCEPTED try of step k: the trace records the damping AFTER the step, the rejected tries before it multiplied by 2, 10, 50, ..."""
-    mu = mu0 if k == 0 else trace[k - 1]["mu"]
-    v = 2.0
-    for _ in range(trace[k]["tries"] - 1):
-        mu, v = mu * v, v * 5
-    return mu
-
-
 def test_steps_of_a_run_with_rejected_tries():
     ds = aar.synth(2, num_frames=40, init_scale=20.0)
     o = ol.Oracle(ds)

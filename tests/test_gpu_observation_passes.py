@@ -23,9 +23,9 @@ observations per frame, AAR_PASSAB_OCC2 and AAR_PASSB_WRENCH_MERGED with intrins
 NOT covered here: what pass A writes for the NEXT solve -- (V_f + mu I)^-1 and h_f, and with the MFMA Schur kernel the dense panels W,
 Y = W (V_f + mu I)^-1 (passA_epilogue and its wrench twin).  It is written only when the LM loop evaluates a trial point with a predicted
 damping; eval_normal_equations and eval_damped_step never ask for it (their panels come from k_schur_fill, their inverses from k_frame_inv),
-so AAR_DENSE_FROM_PASSA makes no difference to them and is not part of any matrix below.  That epilogue stays pinned only by the LM-trace
-tests against the oracle and the real solver (tests/test_gpu_parity.py: test_schur_mfma_kernel_forced_on_small_problems,
-test_tile_counts_and_schur_kernels_against_oracle, the LM traces), i.e. at the default workgroup shape of their fixtures.
+so AAR_DENSE_FROM_PASSA makes no difference to them and is not part of any matrix below.  That epilogue is certified where it runs, inside
+LM runs, in every workgroup shape: tests/test_gpu_speculative_path.py (and, at the default shape of their fixtures, pinned by the LM traces
+of tests/test_gpu_parity.py against the oracle and the real solver).
 
 MEASURED on an MI355X (largest over each test's combinations; H and B relative to max|H_ref|, max|B_ref|):
   edge poses (25 data sets x 20 problems):  H 4.2e-15 (theta = 0.01 + 1e-6; elsewhere <= 1.7e-15), B 2.2e-13 (double mode), rows 4.6e-13 px,

@@ -27,6 +27,7 @@ import pytest
 import aar
 import oracle_lib as ol
 from conftest import load_golden
+from direct_run_certificate import mu_used as _mu_used
 from reduced_system import ReducedSystem, held_mask, prior_terms, slot_col, split_indices
 
 pytestmark = pytest.mark.gpu
@@ -177,17 +178,6 @@ def _lm_run(case, p, x0, every=4, max_checked=6):
     x, rep = p.lm_solve(x0)
     p.set_step_callback(None)
     return zs, info, rep["trace"], rep
-
-
-def _mu_used(trace, k, mu0):
-    """damping of the ACCEPTED try of step k: the trace records the damping AFTER the step (aar_lm_step: out->mu = pb->mu), the rejected tries
-    before it multiplied it by v = 2, 10, 50, ..."""
-    mu = mu0 if k == 0 else trace[k - 1]["mu"]
-    v = 2.0
-    for _ in range(trace[k]["tries"] - 1):
-        mu = mu * v
-        v = v * 5
-    return mu
 
 
 def _certify_run(case, p, x0, solver, eta, w32, coarse_possible, what, tau=1.0, n_check=5):
