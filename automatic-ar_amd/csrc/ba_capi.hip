@@ -16,9 +16,11 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <map>
 #include <numeric>
+#include <optional>
 #include <condition_variable>
 #include <mutex>
 #include <vector>
@@ -26,6 +28,7 @@
 #include "../host/internal.h"
 #include "../host/se3.h"
 #include "../host/motion_model.h"
+#include "../host/problem_plan.h"
 #include "geom.hpp"
 #include "hostcopy.h"
 #include "kernels.h"
@@ -1230,11 +1233,30 @@ static void abort_backtrace(int sig) {
 
 int aar_problem_create_ex(const aar_problem_desc *d, const aar_solver_options *opts, aar_problem **out) { return problem_create(d, opts, nullptr, out); }
 
-// cons: validated and not empty, or NULL
-static int problem_create(const aar_problem_desc *d, const aar_solver_options *opts, const aar_problem_constraints *cons, aar_problem **out) {
-    { static bool once = false; if (!once && getenv("AAR_ABORT_BACKTRACE")) { once = true; const int fd = open(getenv("AAR_ABORT_BACKTRACE"), O_WRONLY | O_CREAT | O_APPEND, 0644); if (fd >= 0) abort_bt_fd = fd; signal(SIGABRT, abort_backtrace); } }
-    if (!d || !out) return set_error(AAR_ERR_INVALID, "aar_problem_create: null argument");
+// ------------------------------------------------------------------------------------------------
+// Problem creation: a sequence of steps, each a function below; problem_create at the end calls them in order.  The index
+// tables come from the planner (host/problem_plan.cpp): no step here builds one.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// Step 1's result: the caller's options with the environment's overrides, and every AAR_* variable of problem creation (an empty
+// optional: the variable is not set -- the step that owns the default applies it where it always was applied)
+struct CreateEnv {
     aar_solver_options so;
+    int env_over = 0;                  // AAR_ENV_* bits
+    DeviceProblem::Tuning tune;        // tuning switches of this problem (kernels.h, DeviceProblem::Tuning)
+    PlanKnobs knobs;                   // the planner's part (its solver-dependent switches: choose_solver)
+    bool stage_timers = false;
+    std::optional<bool> overlap, merge_passes, fused_comm, spec_chol;
+    std::optional<int> dense_from_passA, spcg_coarse, spcg_coarse_from, pcg_coarse, pcg_coarse_from, pcg_e_every, pcg_resident, spcg_spread;
+    std::optional<double> pcg_eta_loose, pcg_abs_tol, pcg_eta_switch;
+    std::optional<int> schur_mfma, schur_panel_mb, pcg_fused, pcg_w32, pcg_grid;
+};
+
+// ---- step 1: options struct and environment ----
+int read_create_options(const aar_solver_options *opts, CreateEnv &E) {
+    { static bool once = false; if (!once && getenv("AAR_ABORT_BACKTRACE")) { once = true; const int fd = open(getenv("AAR_ABORT_BACKTRACE"), O_WRONLY | O_CREAT | O_APPEND, 0644); if (fd >= 0) abort_bt_fd = fd; signal(SIGABRT, abort_backtrace); } }
+    aar_solver_options &so = E.so;
     aar_solver_default_options(&so);
     if (opts) {   // a caller built against an older header passes a shorter struct: the fields it does not know keep their defaults
         if (opts->struct_size < 2 * sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_solver_options.struct_size is not set (use aar_solver_default_options)");
@@ -1243,7 +1265,7 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     }
     // environment overrides (tuning / bisecting only: the options struct is the interface): they apply to fields the caller left at their defaults
     // -- an explicitly chosen solver, forcing term or cap always wins -- and are reported (aar_solver_stats.env_overrides)
-    int env_over = 0;
+    int &env_over = E.env_over;
     if (const char *e = getenv("AAR_SOLVER")) {
         if (so.solver == AAR_SOLVER_AUTO) {
             int v = -1;
@@ -1258,6 +1280,46 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     if (const char *e = getenv("AAR_PCG_MAX_IT")) if (so.pcg_max_it == 0 && atoi(e) > 0) { so.pcg_max_it = atoi(e); env_over |= AAR_ENV_PCG_MAX_IT; }
     if (so.solver < AAR_SOLVER_DIRECT || so.solver > AAR_SOLVER_AUTO) return set_error(AAR_ERR_INVALID, "aar_solver_options.solver %d is not one of AAR_SOLVER_*", so.solver);
     if (so.pcg_eta < 0 || so.pcg_max_it < 0 || so.pcg_eta_loose < 0 || so.pcg_eta_switch < 0 || so.pcg_abs_tol < 0) return set_error(AAR_ERR_INVALID, "aar_solver_options: negative pcg_eta / pcg_eta_loose / pcg_eta_switch / pcg_abs_tol / pcg_max_it");
+    const char *tenv = getenv("AAR_STAGE_TIMERS");
+    E.stage_timers = tenv && tenv[0] == '1';
+    { const char *e = getenv("AAR_OVERLAP"); E.overlap = (e && e[0] == '1'); }  // measured slower than one stream at config 3: off by default
+    { const char *e = getenv("AAR_MERGE_PASSES"); if (e) E.merge_passes = (e[0] != '0'); }
+    { const char *e = getenv("AAR_FUSED_COMM"); if (e) E.fused_comm = (e[0] != '0'); }
+    { const char *e = getenv("AAR_SPEC_CHOL"); if (e) E.spec_chol = (e[0] != '0'); }
+    {   // tuning switches of this problem (kernels.h, DeviceProblem::Tuning)
+        auto env_int = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
+        env_int("AAR_FUSED_PANEL", E.tune.fused_panel); env_int("AAR_BS_RIDES", E.tune.bs_rides); env_int("AAR_BACKSUB_RIDES", E.tune.backsub_rides);
+        env_int("AAR_LDL_LOOKAHEAD", E.tune.lookahead); env_int("AAR_PASSA_VARIANT", E.tune.passA_variant); env_int("AAR_PACK_SYSTEM", E.tune.pack_system);
+        env_int("AAR_INIT_HEADSTART", E.tune.init_headstart); env_int("AAR_PASSB_LEAN", E.tune.passB_lean); env_int("AAR_PASSA_WRENCH", E.tune.passA_wrench); env_int("AAR_PASSB_WRENCH_MERGED", E.tune.passB_wrench_merged); env_int("AAR_SPCG_BACKSUB_RIDES", E.tune.spcg_backsub_rides); env_int("AAR_PASSAB_OCC2", E.tune.passAB_occ2);
+    }
+    { const char *e = getenv("AAR_DENSE_FROM_PASSA"); if (e) E.dense_from_passA = atoi(e) != 0 ? 1 : 0; }
+    if (const char *t = getenv("AAR_SPCG_COARSE")) E.spcg_coarse = atoi(t) != 0;
+    if (const char *t = getenv("AAR_SPCG_COARSE_FROM")) E.spcg_coarse_from = atoi(t);
+    if (const char *t = getenv("AAR_PCG_COARSE")) E.pcg_coarse = atoi(t) != 0;
+    if (const char *t = getenv("AAR_PCG_COARSE_FROM")) E.pcg_coarse_from = atoi(t);
+    if (const char *t = getenv("AAR_PCG_E_EVERY")) E.pcg_e_every = std::max(1, atoi(t));
+    if (const char *t = getenv("AAR_PCG_RESIDENT")) E.pcg_resident = atoi(t) != 0;
+    if (const char *t = getenv("AAR_SPCG_SPREAD")) E.spcg_spread = std::max(1, atoi(t));
+    if (const char *e = getenv("AAR_PCG_ETA_LOOSE")) E.pcg_eta_loose = atof(e);
+    if (const char *e = getenv("AAR_PCG_ABS_TOL")) E.pcg_abs_tol = atof(e);
+    if (const char *e = getenv("AAR_PCG_ETA_SWITCH")) E.pcg_eta_switch = atof(e);
+    if (const char *e = getenv("AAR_SCHUR_MFMA")) E.schur_mfma = atoi(e);
+    if (const char *e = getenv("AAR_SCHUR_PANEL_MB")) E.schur_panel_mb = atoi(e);
+    if (const char *t = getenv("AAR_PCG_FUSED")) E.pcg_fused = atoi(t) != 0 ? 1 : 0;
+    if (const char *t = getenv("AAR_PCG_W32")) E.pcg_w32 = atoi(t) != 0 ? 1 : 0;
+    if (const char *t = getenv("AAR_PCG_GRID")) E.pcg_grid = std::max(1, atoi(t));
+    // the planner's knobs (host/problem_plan.h)
+    if (const char *e = getenv("AAR_PASSB_CHUNK")) E.knobs.passb_chunk = atoi(e);
+    if (const char *e = getenv("AAR_SCHUR_ITEM")) E.knobs.schur_item = atoi(e);
+    if (const char *e = getenv("AAR_SCHUR_WINDOW")) E.knobs.schur_window = atoi(e);
+    if (const char *e = getenv("AAR_SCHUR_XCD")) E.knobs.schur_xcd = atoi(e);
+    if (const char *e = getenv("AAR_SCHUR_SPLIT")) E.knobs.schur_split = atoi(e);
+    if (const char *t = getenv("AAR_PCG_CHUNK")) E.knobs.pcg_chunk = atoll(t);
+    return AAR_OK;
+}
+
+// ---- step 2: validation and counting ----
+int validate_and_count(const aar_problem_desc *d, std::vector<int64_t> &per_frame, int64_t &global_slots) {
     const int C = d->num_cams, M = d->num_markers, Fg = d->num_frames;
     const int64_t Ng = d->num_obs;
     if (C < 1 || M < 1 || Fg < 0 || Ng < 0) return set_error(AAR_ERR_INVALID, "aar_problem_create: bad sizes");
@@ -1266,55 +1328,57 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     if (!d->cam_mats || (Ng > 0 && (!d->obs_frame || !d->obs_cam || !d->obs_marker || !d->obs_uv)))
         return set_error(AAR_ERR_INVALID, "aar_problem_create: null array");
     if (Ng >= (1LL << 31) || (int64_t)C + M >= 32768) return set_error(AAR_ERR_UNSUPPORTED, "problem too large for 32-bit indexing");
-    std::vector<int64_t> per_frame(Fg, 0);
+    per_frame.assign(Fg, 0);
     // (entity, frame) incidences of the WHOLE data set, counted the same way on every rank: what AUTO's choice between the two CG solvers rests on must not
     // depend on which frames a rank happens to own (ranks that chose differently would wait in different collectives forever)
-    int64_t global_slots = 0;
-    {
-        std::vector<int32_t> seen_c(C, -1), seen_m(M, -1);
-        for (int64_t o = 0; o < Ng; o++) {
-            const int f = d->obs_frame[o], c = d->obs_cam[o], m = d->obs_marker[o];
-            if (f < 0 || f >= Fg || c < 0 || c >= C || m < 0 || m >= M) return set_error(AAR_ERR_INVALID, "observation %lld has an index out of range", (long long)o);
-            if (o > 0 && f < d->obs_frame[o - 1]) return set_error(AAR_ERR_INVALID, "observations must be ordered by frame (reference residual order)");
-            per_frame[f]++;
-            if (seen_c[c] != f) { seen_c[c] = f; global_slots += d->optimize_cam_intrinsics ? 2 : 1; }
-            if (seen_m[m] != f) { seen_m[m] = f; global_slots += 1; }
-        }
+    global_slots = 0;
+    std::vector<int32_t> seen_c(C, -1), seen_m(M, -1);
+    for (int64_t o = 0; o < Ng; o++) {
+        const int f = d->obs_frame[o], c = d->obs_cam[o], m = d->obs_marker[o];
+        if (f < 0 || f >= Fg || c < 0 || c >= C || m < 0 || m >= M) return set_error(AAR_ERR_INVALID, "observation %lld has an index out of range", (long long)o);
+        if (o > 0 && f < d->obs_frame[o - 1]) return set_error(AAR_ERR_INVALID, "observations must be ordered by frame (reference residual order)");
+        per_frame[f]++;
+        if (seen_c[c] != f) { seen_c[c] = f; global_slots += d->optimize_cam_intrinsics ? 2 : 1; }
+        if (seen_m[m] != f) { seen_m[m] = f; global_slots += 1; }
     }
-    int rc = ensure_device(d->device_id);
-    if (rc) return rc;
+    return AAR_OK;
+}
 
-    aar_problem *pb = new aar_problem();
+// ---- step 3: device, streams and events (pb: freshly made, its device selected) ----
+int open_streams(const aar_problem_desc *d, const CreateEnv &E, aar_problem *pb) {
     pb->device = d->device_id;
     pb->comm = d->comm;
     aar_lm_default_params(&pb->prm);
     memset(&pb->times, 0, sizeof pb->times);
-    const char *tenv = getenv("AAR_STAGE_TIMERS");
-    pb->stage_timers = tenv && tenv[0] == '1';
-    auto fail = [&](int code) { aar_problem_destroy(pb); return code; };
-    if (hipStreamCreateWithFlags(&pb->stream, hipStreamNonBlocking) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipStreamCreate failed"));
+    pb->stage_timers = E.stage_timers;
+    if (hipStreamCreateWithFlags(&pb->stream, hipStreamNonBlocking) != hipSuccess) return set_error(AAR_ERR_HIP, "hipStreamCreate failed");
     (void)hipEventCreate(&pb->ev[0]);
     (void)hipEventCreate(&pb->ev[1]);
     if (hipStreamCreateWithFlags(&pb->stream2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&pb->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&pb->ev_join, hipEventDisableTiming) != hipSuccess)
-        return fail(set_error(AAR_ERR_HIP, "second stream / events could not be created"));
-    { const char *e = getenv("AAR_OVERLAP"); pb->overlap = (e && e[0] == '1'); }  // measured slower than one stream at config 3: off by default
-    { const char *e = getenv("AAR_MERGE_PASSES"); if (e) pb->merge_passes = (e[0] != '0'); }
-    { const char *e = getenv("AAR_FUSED_COMM"); if (e) pb->fused_comm = (e[0] != '0'); }
-    { const char *e = getenv("AAR_SPEC_CHOL"); if (e) pb->spec_chol = (e[0] != '0'); }
+        return set_error(AAR_ERR_HIP, "second stream / events could not be created");
+    if (E.overlap) pb->overlap = *E.overlap;
+    if (E.merge_passes) pb->merge_passes = *E.merge_passes;
+    if (E.fused_comm) pb->fused_comm = *E.fused_comm;
+    if (E.spec_chol) pb->spec_chol = *E.spec_chol;
+    return AAR_OK;
+}
 
+// ---- step 4: layout, shard by frame range, sizes ----
+int plan_shard(const aar_problem_desc *d, const std::vector<int64_t> &per_frame, aar_problem *pb) {
+    const int C = d->num_cams, M = d->num_markers, Fg = d->num_frames;
     PoseLayout &L = pb->L;
     L.C = C; L.M = M; L.F = Fg; L.rc = d->root_cam; L.rm = d->root_marker;
     L.oc = d->optimize_cam_poses != 0; L.om = d->optimize_marker_poses != 0; L.of = d->optimize_object_poses != 0;
     L.oi = d->optimize_cam_intrinsics != 0;
-    pb->N_global = Ng;
+    pb->N_global = d->num_obs;
 
-    // ---- shard by frame range ----
     const int world = pb->comm ? pb->comm->world : 1, rank = pb->comm ? pb->comm->rank : 0;
     pb->P.pcg_rank0 = rank == 0 ? 1 : 0;
     std::vector<int32_t> begin(world + 1, 0);
-    if ((rc = aar_plan_shards(Fg, per_frame.data(), world, begin.data()))) return fail(rc);
+    int rc;
+    if ((rc = aar_plan_shards(Fg, per_frame.data(), world, begin.data()))) return rc;
     pb->f_begin = begin[rank];
     pb->f_end = begin[rank + 1];
     int64_t ob = 0;
@@ -1339,70 +1403,17 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     P.huber = pb->with_huber ? pb->hubber_delta : -1.f;
     P.half_size = (double)((float)d->marker_size / 2.f);
     P.frames_fixed = L.of ? 0 : 1;
-    const int A = P.A, F = P.F;
-    // entities the caller fixed that would be free otherwise
-    std::vector<int32_t> held(C + M, 0);
-    bool held_extra = false;
-    if (cons) {
-        for (int i = 0; i < cons->n_fixed_cams; i++) { const int c = cons->fixed_cams[i]; if (c != L.rc && L.oc) { held[c] = 1; held_extra = true; } }
-        for (int i = 0; i < cons->n_fixed_markers; i++) { const int m = cons->fixed_markers[i]; if (m != L.rm && L.om) { held[C + m] = 1; held_extra = true; } }
-    }
+    return AAR_OK;
+}
 
-    auto pair_end_fixed = [&](int e) { return held[e] || (e < C ? (e == L.rc || !L.oc) : (e - C == L.rm || !L.om)); };   // (e: a camera or marker entity)
-
-    int local_rc = AAR_OK;   // rank-local limits: decided collectively below
-    // ---- ordering A (reference order) + per-frame slot lists ----
-    std::vector<int32_t> frame_obs_start(F + 1, 0), fslot_start(F + 1, 0), fslot_ent;
-    std::vector<ObsIdx> a_idx(N);
-    std::vector<float> a_uv((size_t)8 * N);
-    if (N) memcpy(a_uv.data(), d->obs_uv + 8 * ob, sizeof(float) * 8 * N);
-    {
-        int64_t o = 0;
-        std::vector<int32_t> slot_of(A, -1);
-        for (int f = 0; f < F; f++) {
-            frame_obs_start[f] = (int32_t)o;
-            const int64_t cnt = per_frame[pb->f_begin + f];
-            std::vector<int32_t> ents;
-            for (int64_t k = 0; k < cnt; k++) {
-                const int64_t g = ob + o + k;
-                ents.push_back(d->obs_cam[g]);
-                ents.push_back(C + d->obs_marker[g]);
-                if (L.oi) ents.push_back(C + M + d->obs_cam[g]);
-            }
-            std::sort(ents.begin(), ents.end());
-            ents.erase(std::unique(ents.begin(), ents.end()), ents.end());
-            if (ents.size() >= (1u << SLOT_C_BITS) && !local_rc) local_rc = set_error(AAR_ERR_UNSUPPORTED, "frame %d touches %zu entities (limit %d)", f, ents.size(), (1 << SLOT_C_BITS) - 1);
-            for (size_t s = 0; s < ents.size(); s++) slot_of[ents[s]] = (int32_t)s;
-            for (int64_t k = 0; k < cnt; k++) {
-                const int64_t g = ob + o + k;
-                ObsIdx id;
-                id.frame = f; id.cam = d->obs_cam[g]; id.marker = C + d->obs_marker[g];
-                id.slots = pack_slots(slot_of[id.cam], slot_of[id.marker], L.oi ? slot_of[C + M + id.cam] : 0);
-                a_idx[o + k] = id;
-            }
-            fslot_start[f] = (int32_t)fslot_ent.size();
-            fslot_ent.insert(fslot_ent.end(), ents.begin(), ents.end());
-            P.max_kf = std::max<int>(P.max_kf, (int)ents.size());
-            o += cnt;
-        }
-        frame_obs_start[F] = (int32_t)o;
-        fslot_start[F] = (int32_t)fslot_ent.size();
-    }
-    P.total_slots = (int)fslot_ent.size();
-    std::vector<int32_t> frame_stride(F, 1);   // the observations of a frame are camera-major: a stride of ~ n / 8, coprime with n, puts different cameras into neighbouring lanes
-    for (int f = 0; f < F; f++) {
-        const int n = frame_obs_start[f + 1] - frame_obs_start[f];
-        if (n <= 16) continue;
-        int st = n / 8 + 1;
-        while (std::gcd(st, n) != 1) st++;
-        frame_stride[f] = st;
-    }
-    {   // tuning switches of this problem (kernels.h, DeviceProblem::Tuning)
-        auto env_int = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
-        env_int("AAR_FUSED_PANEL", P.tune.fused_panel); env_int("AAR_BS_RIDES", P.tune.bs_rides); env_int("AAR_BACKSUB_RIDES", P.tune.backsub_rides);
-        env_int("AAR_LDL_LOOKAHEAD", P.tune.lookahead); env_int("AAR_PASSA_VARIANT", P.tune.passA_variant); env_int("AAR_PACK_SYSTEM", P.tune.pack_system);
-        env_int("AAR_INIT_HEADSTART", P.tune.init_headstart); env_int("AAR_PASSB_LEAN", P.tune.passB_lean); env_int("AAR_PASSA_WRENCH", P.tune.passA_wrench); env_int("AAR_PASSB_WRENCH_MERGED", P.tune.passB_wrench_merged); env_int("AAR_SPCG_BACKSUB_RIDES", P.tune.spcg_backsub_rides); env_int("AAR_PASSAB_OCC2", P.tune.passAB_occ2);
-    }
+// ---- step 6: solver choice and limits.  global_slots: (entity, frame) incidences of the whole data set; held_extra: the caller fixed entities that
+// would be free otherwise; local_rc: this rank's status so far (the first limit that is exceeded is kept); schur_mfma: which Schur kernel ----
+void choose_solver(aar_problem *pb, const CreateEnv &E, int64_t global_slots, bool held_extra, int &local_rc, bool &schur_mfma) {
+    DeviceProblem &P = pb->P;
+    const PoseLayout &L = pb->L;
+    const aar_solver_options &so = E.so;
+    const int A = P.A, F = P.F, Fg = L.F, world = pb->comm ? pb->comm->world : 1;
+    P.tune = E.tune;
     // the frame-block kernel keeps a frame's slots in LDS: sized by the form that is actually launched (wrench form: 21 + 4 doubles per slot; row form: 62)
     const size_t ldsA = P.tune.passA_wrench ? passA_wrench_lds_bytes(P.max_kf, L.oi)
                                             : std::max(passA_lds_bytes(P.max_kf, 256), passA_lds_bytes(P.max_kf, 64));
@@ -1413,7 +1424,7 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     // entities -- so they must fit a budget (half of the free device memory; AAR_SCHUR_PANEL_MB overrides), else the
     // output-stationary kernel, which needs none of this, takes over.  Only THAT kernel keeps a row panel of all entities in LDS.
     P.deterministic = so.deterministic ? 1 : 0;
-    { const char *e = getenv("AAR_DENSE_FROM_PASSA"); if (e) P.dense_from_passA = atoi(e) != 0 ? 1 : 0; }
+    if (E.dense_from_passA) P.dense_from_passA = *E.dense_from_passA;
     {   // which solver (aar_solver_options; AUTO: DESIGN.md section 12)
         hipDeviceProp_t prop;
         const int cus = (hipGetDeviceProperties(&prop, pb->device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 64;
@@ -1421,18 +1432,18 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
         const bool pcg_ok = pcg_lds_bytes(A) <= 150 * 1024;
         // one wavefront per entity, every one of them resident AT ONCE (they hand over to each other): asked of the runtime's occupancy calculator for this
         // kernel's registers and LDS, as pcg_max_grid asks for the PCG grid.  (Another process on the device can still take the slots: k_spcg's time-out.)
-        if (const char *t = getenv("AAR_SPCG_COARSE")) P.spcg_coarse = atoi(t) != 0;
-        if (const char *t = getenv("AAR_SPCG_COARSE_FROM")) P.spcg_coarse_from = atoi(t);
-        if (const char *t = getenv("AAR_PCG_COARSE")) P.pcg_coarse = atoi(t) != 0;
-        if (const char *t = getenv("AAR_PCG_COARSE_FROM")) P.pcg_coarse_from = atoi(t);
+        if (E.spcg_coarse) P.spcg_coarse = *E.spcg_coarse;
+        if (E.spcg_coarse_from) P.spcg_coarse_from = *E.spcg_coarse_from;
+        if (E.pcg_coarse) P.pcg_coarse = *E.pcg_coarse;
+        if (E.pcg_coarse_from) P.pcg_coarse_from = *E.pcg_coarse_from;
         // both coarse spaces are built for groups whose only fixed entity is the root (its slot carries the group's rigid motion): with entities
         // fixed by the caller they are off
         if (held_extra) { P.spcg_coarse = 0; P.pcg_coarse = 0; }
         // the coarse operator's pass costs like ~1.5 CG iterations and a kept operator ~0.1 - 0.7 more iterations per solve: keeping it pays on long sequences only
         // (profiles/r06_attempts.txt section 3: +3.7 % at 160 entities x 4 000 frames, +1.4 % at config 5, -1 .. -3 % on 500-frame problems)
         P.pcg_e_every = P.total_slots >= 300000 ? 3 : 1;
-        if (const char *t = getenv("AAR_PCG_E_EVERY")) P.pcg_e_every = std::max(1, atoi(t));
-        if (const char *t = getenv("AAR_PCG_RESIDENT")) P.pcg_resident = atoi(t) != 0;
+        if (E.pcg_e_every) P.pcg_e_every = *E.pcg_e_every;
+        if (E.pcg_resident) P.pcg_resident = *E.pcg_resident;
         if (pcg_lds_bytes(A, true) > 150 * 1024) P.pcg_coarse = 0;   // (the coarse space's tables do not fit beside the vectors of this many entities: block-Jacobi only)
         const int spcg_per_cu = spcg_fits(P.nT) ? spcg_resident_per_cu(P.nT, spcg_coarse_now(P)) : 0;
         const bool spcg_ok = spcg_fits(P.nT) && P.n_pad / 6 <= std::max(1, spcg_per_cu) * cus;
@@ -1455,10 +1466,10 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
             else solver = AAR_SOLVER_DIRECT;
         }
         pb->solver = solver;
-        pb->env_overrides = env_over;
+        pb->env_overrides = E.env_over;
         P.use_pcg = solver == AAR_SOLVER_PCG ? 1 : 0;
         P.use_spcg = solver == AAR_SOLVER_SPCG ? 1 : 0;
-        if (const char *t = getenv("AAR_SPCG_SPREAD")) P.spcg_spread = std::max(1, atoi(t));
+        if (E.spcg_spread) P.spcg_spread = *E.spcg_spread;
         // (one XCD has an eighth of the CUs: more entities than that many wavefront slots would not all be resident there)
         if (P.n_pad / 6 > std::min(4, std::max(1, spcg_per_cu)) * (cus / 8)) P.spcg_spread = 1;
         // Forcing term of the inexact solvers (include/aar.h; defaults and why: kernels.h).  The CG through the frame blocks measures |r| / |b|; the CG on the
@@ -1468,321 +1479,80 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
         P.pcg_eta_loose = 0.0;
         if (so.pcg_eta_loose > 0) P.pcg_eta_loose = so.pcg_eta_loose;
         else if (so.pcg_eta == 0 && (P.use_pcg || P.use_spcg)) P.pcg_eta_loose = P.use_pcg ? PCG_ETA_LOOSE_DEFAULT : SPCG_ETA_LOOSE_DEFAULT;   // (0: none)
-        if (const char *e = getenv("AAR_PCG_ETA_LOOSE")) if (so.pcg_eta_loose == 0) P.pcg_eta_loose = atof(e);
+        if (E.pcg_eta_loose) if (so.pcg_eta_loose == 0) P.pcg_eta_loose = *E.pcg_eta_loose;
         if (P.pcg_eta_loose <= P.pcg_eta) P.pcg_eta_loose = 0.0;   // (no sequence: one forcing term throughout)
         P.pcg_abs_tol = P.use_pcg ? PCG_ABS_TOL_DEFAULT : SPCG_ABS_TOL_DEFAULT;
         if (so.pcg_abs_tol > 0) P.pcg_abs_tol = so.pcg_abs_tol;
-        else if (const char *e = getenv("AAR_PCG_ABS_TOL")) P.pcg_abs_tol = atof(e);
+        else if (E.pcg_abs_tol) P.pcg_abs_tol = *E.pcg_abs_tol;
         if (so.pcg_eta_switch > 0) P.pcg_eta_switch = so.pcg_eta_switch;
-        else if (const char *e = getenv("AAR_PCG_ETA_SWITCH")) P.pcg_eta_switch = atof(e);
+        else if (E.pcg_eta_switch) P.pcg_eta_switch = *E.pcg_eta_switch;
         P.pcg_eta_now = P.pcg_eta;
         P.spcg_max_it = spcg_default_cap(P.nT);
         if (so.pcg_max_it > 0) { P.pcg_max_it = so.pcg_max_it; P.spcg_max_it = std::min(so.pcg_max_it, SPCG_MAX_IT); }
         if (P.use_pcg && !pcg_ok && !local_rc) local_rc = set_error(AAR_ERR_UNSUPPORTED, "AAR_SOLVER_PCG keeps the CG vectors and the preconditioner of %d unknowns in LDS: too many shared entities", 6 * A);
         if (P.use_spcg && !spcg_ok && !local_rc) local_rc = set_error(AAR_ERR_UNSUPPORTED, "AAR_SOLVER_SPCG keeps the reduced system in the registers of one wavefront per shared entity: %d unknowns are too many (limit %d, and at most %d entities)", 6 * A, 96 * SPCG_MAX_NT, std::max(1, spcg_per_cu) * cus);
     }
-    bool schur_mfma = A >= 96 && F > 0;
-    if (const char *e = getenv("AAR_SCHUR_MFMA")) schur_mfma = atoi(e) != 0 && F > 0;
+    schur_mfma = A >= 96 && F > 0;
+    if (E.schur_mfma) schur_mfma = *E.schur_mfma != 0 && F > 0;
     if (P.deterministic) schur_mfma = false;   // fixed-order sums exist for the output-stationary kernel only (kernels.h)
     if (P.use_pcg) schur_mfma = true;          // (no Schur complement is ever formed in that mode: no LDS row panel to fit; the dense panels are not allocated either)
     if (schur_mfma) {
         const size_t panel_bytes = (size_t)2 * F * ((A + 1 + 31) / 32 * 32) * 288;
         size_t free_b = 0, total_b = 0;
         size_t budget = (hipMemGetInfo(&free_b, &total_b) == hipSuccess) ? free_b / 2 : (size_t)64 << 30;
-        if (const char *e = getenv("AAR_SCHUR_PANEL_MB")) budget = (size_t)std::max(0, atoi(e)) << 20;
+        if (E.schur_panel_mb) budget = (size_t)std::max(0, *E.schur_panel_mb) << 20;
         if (panel_bytes > budget) schur_mfma = false;
     }
     if (!schur_mfma && (size_t)A * 36 * 8 + 2048 > 160 * 1024 && !local_rc)
         local_rc = set_error(AAR_ERR_UNSUPPORTED, "%d cameras+markers exceed the row panel the output-stationary Schur kernel holds in LDS (and the dense panels of the MFMA kernel do not fit the memory budget)", A);
-    {   // the limits above depend on the rank's own frames: agree on the outcome before anybody returns (see collective_status)
-        if (pb->comm && (rc = dev_alloc(pb, &pb->d_status, 1))) return fail(rc);
-        int agreed = local_rc;
-        if ((rc = collective_status(pb, local_rc, &agreed))) return fail(rc);
-        if (local_rc) return fail(local_rc);
-        if (agreed) return fail(set_error(agreed, "another rank could not create its shard of the problem (status %d)", agreed));
-    }
+}
 
-    // ---- ordering B: (camera, marker, frame) runs cut into wave-sized chunks ----
-    std::vector<int32_t> perm(N);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
-        const ObsIdx &p = a_idx[x], &q = a_idx[y];
-        if (p.cam != q.cam) return p.cam < q.cam;
-        if (p.marker != q.marker) return p.marker < q.marker;
-        return p.frame < q.frame;
-    });
-    std::vector<ObsIdx> b_idx(N);
-    std::vector<float> b_uv((size_t)8 * N);
-    for (int64_t i = 0; i < N; i++) {
-        b_idx[i] = a_idx[perm[i]];
-        memcpy(&b_uv[8 * i], &a_uv[8 * (size_t)perm[i]], 8 * sizeof(float));
-    }
-    // (a wavefront pays a wave sum of 90 values and 90 atomics per chunk whatever its length: config 5's runs of ~390 observations as ONE chunk each, 3 200 wavefronts,
-    //  run 11 % faster than cut at 256 -- profiles/r04_attempts.txt section 17; small problems keep 64 and the parallelism)
-    int chunk_len = (int)((N / 2048 + 63) / 64 * 64);
-    chunk_len = std::min(std::max(chunk_len, 64), 512);
-    if (const char *e = getenv("AAR_PASSB_CHUNK")) chunk_len = std::min(std::max(atoi(e) / 64 * 64, 64), PASSB_CHUNK);   // tuning knob (observations of a run per wavefront)
-    std::vector<int32_t> chunk_start;
-    for (int64_t i = 0; i < N;) {
-        int64_t e = i;
-        while (e < N && b_idx[e].cam == b_idx[i].cam && b_idx[e].marker == b_idx[i].marker) e++;
-        for (int64_t s = i; s < e; s += chunk_len) chunk_start.push_back((int32_t)s);
-        i = e;
-    }
-    P.n_chunks = (int)chunk_start.size();
-    chunk_start.push_back((int32_t)N);
+// ---- step 7: collective agreement.  The limits above depend on the rank's own frames: agree on the outcome before anybody returns (see collective_status) ----
+int agree_on_status(aar_problem *pb, int local_rc) {
+    int rc;
+    if (pb->comm && (rc = dev_alloc(pb, &pb->d_status, 1))) return rc;
+    int agreed = local_rc;
+    if ((rc = collective_status(pb, local_rc, &agreed))) return rc;
+    if (local_rc) return local_rc;
+    if (agreed) return set_error(agreed, "another rank could not create its shard of the problem (status %d)", agreed);
+    return AAR_OK;
+}
 
-    // ---- which off-diagonal blocks of U exist: entities that share an observation (camera x marker; with intrinsics entities also those of the camera) ----
-    std::vector<int32_t> up_start(A + 1, 0), up_ent;
-    {
-        std::vector<std::vector<int32_t>> nb(A);
-        for (int ch = 0; ch < P.n_chunks; ch++) {
-            const ObsIdx &h = b_idx[chunk_start[ch]];
-            if (ch > 0 && b_idx[chunk_start[ch - 1]].cam == h.cam && b_idx[chunk_start[ch - 1]].marker == h.marker) continue;
-            int ents[3] = {h.cam, h.marker, L.oi ? C + M + h.cam : -1};
-            for (int x = 0; x < 3; x++)
-                for (int y = 0; y < 3; y++)
-                    if (x != y && ents[x] >= 0 && ents[y] >= 0) nb[ents[x]].push_back(ents[y]);
-        }
-        // relative pose priors: the camera-camera / marker-marker block of a pair whose two ends are free (a fixed end has no block)
-        for (int p = 0; cons && p < cons->n_pair_priors; p++) {
-            const aar_pair_prior &q = cons->pair_priors[p];
-            const int off = q.kind == AAR_PRIOR_CAMERA ? 0 : C, ea = off + q.index_a, eb = off + q.index_b;
-            if (pair_end_fixed(ea) || pair_end_fixed(eb)) continue;
-            nb[ea].push_back(eb);
-            nb[eb].push_back(ea);
-        }
-        for (int a = 0; a < A; a++) {
-            std::sort(nb[a].begin(), nb[a].end());
-            nb[a].erase(std::unique(nb[a].begin(), nb[a].end()), nb[a].end());
-            up_start[a] = (int32_t)up_ent.size();
-            up_ent.insert(up_ent.end(), nb[a].begin(), nb[a].end());
-        }
-        up_start[A] = (int32_t)up_ent.size();
-        if (up_ent.empty()) up_ent.push_back(0);
-    }
+// the device reads the planner's pair_rec as int4
+static_assert(sizeof(PairRec) == sizeof(int4) && alignof(int4) % alignof(PairRec) == 0 && offsetof(PairRec, frame) == 0 && offsetof(PairRec, slot) == 4 &&
+              offsetof(PairRec, frame_slot0) == 8 && offsetof(PairRec, pad) == 12, "PairRec must lay out as the int4 {x, y, z, w} the kernels read");
 
-    // ---- (entity, frame) incidence for the Schur complement ----
-    std::vector<std::vector<std::pair<int32_t, int32_t>>> inc(A);
-    for (int f = 0; f < F; f++)
-        for (int s = fslot_start[f]; s < fslot_start[f + 1]; s++) inc[fslot_ent[s]].push_back({f, s});
-    std::vector<int4> pair_rec;
-    std::vector<int32_t> sw_ent, sw_begin, sw_end;
-    const int64_t total_pairs = P.total_slots;
-    // (entity, frame) pairs per workgroup: measured optimum 16 (config 3) ... 64 (configs 4, 5); every workgroup ends with
-    // an atomic flush of its row panel, so fewer, longer items win once the grid is large enough to fill the chip
-    int per_item = (int)std::min<int64_t>(64, std::max<int64_t>(16, total_pairs / 1024));
-    per_item = (per_item + 3) / 4 * 4;
-    if (const char *e = getenv("AAR_SCHUR_ITEM")) per_item = std::max(4, atoi(e));  // tuning knob (pairs per workgroup)
-    std::vector<int> pair_base(A + 1, 0);
-    for (int a = 0; a < A; a++) {
-        pair_base[a] = (int)pair_rec.size();
-        for (auto &pr : inc[a]) pair_rec.push_back(make_int4(pr.first, pr.second, fslot_start[pr.first], 0));
-    }
-    pair_base[A] = (int)pair_rec.size();
-    // Large problems (the kernel is then bound by re-reading W blocks): items are cut by FRAME WINDOW and ordered window-major,
-    // so that the workgroups in flight at any time walk the same frames and find each other's W blocks in L2 / MALL.
-    // Small problems: plain runs of per_item pairs, entity-major (fewer, fuller workgroups).
-    int window = 0;
-    if (total_pairs >= 262144) window = 64;
-    if (const char *e = getenv("AAR_SCHUR_WINDOW")) window = std::max(0, atoi(e));
-    if (window > 0) {
-        std::vector<int> cursor(A, 0);
-        for (int f0 = 0; f0 < F; f0 += window)
-            for (int a = 0; a < A; a++) {
-                int c = cursor[a];
-                const int cnt = (int)inc[a].size();
-                int e = c;
-                while (e < cnt && inc[a][e].first < f0 + window) e++;
-                if (e > c) {
-                    sw_ent.push_back(a);
-                    sw_begin.push_back(pair_base[a] + c);
-                    sw_end.push_back(pair_base[a] + e);
-                }
-                cursor[a] = e;
-            }
-    } else {
-        // XCD-aware order (opt-in, AAR_SCHUR_XCD=1).  Workgroups are dealt round-robin over the 8 XCDs, each with its own L2: with entity-major items every
-        // XCD ends up walking ALL frames and pulls the whole of W through its L2 (8 x 3.6 MB per launch at config 3 for 0.67 MB of output).  Here the frames
-        // are cut into 8 contiguous ranges instead, an item stays inside one range, and the items of range x sit at positions = x (mod 8): an XCD then
-        // only ever touches an eighth of W (holes are padded with empty items; the launch's rider shifts every range by the same XCD).  Measured (round 4,
-        // profiles/r04_attempts.txt): k_schur 20.9 -> 20.3 us at config 3, 51.7 -> 59.4 us at config 4 (more, shorter items; every one ends with an atomic
-        // flush of its row panel): the kernel is not bound by those fetches -- not the default.
-        int xcd = 1;
-        if (const char *e = getenv("AAR_SCHUR_XCD")) xcd = atoi(e) != 0 ? 8 : 1;
-        std::vector<std::vector<std::array<int32_t, 3>>> lists(xcd);
-        for (int a = 0; a < A; a++) {
-            const int cnt = (int)inc[a].size();
-            int s = 0;
-            for (int x = 0; x < xcd; x++) {
-                const int f_hi = (int)((int64_t)F * (x + 1) / xcd);
-                int e = s;
-                while (e < cnt && inc[a][e].first < f_hi) e++;
-                for (int c = s; c < e; c += per_item)
-                    lists[x].push_back({(int32_t)a, (int32_t)(pair_base[a] + c), (int32_t)(pair_base[a] + std::min(e, c + per_item))});
-                s = e;
-            }
-        }
-        size_t longest = 0;
-        for (auto &l : lists) longest = std::max(longest, l.size());
-        for (size_t k = 0; k < longest; k++)
-            for (int x = 0; x < xcd; x++) {
-                if (k < lists[x].size()) { sw_ent.push_back(lists[x][k][0]); sw_begin.push_back(lists[x][k][1]); sw_end.push_back(lists[x][k][2]); }
-                else if (xcd > 1) { sw_ent.push_back(0); sw_begin.push_back(0); sw_end.push_back(0); }   // a hole: nothing to walk, an empty panel to flush
-            }
-    }
-    P.n_swork = (int)sw_ent.size();
-    // deterministic mode: a record per Schur work item, the items of every entity in ascending frame order; a record per
-    // pass-B chunk, the chunks of every camera / marker / (camera, marker) pair in ascending order
-    std::vector<int64_t> sp_off;
-    std::vector<int32_t> se_start, se_items, pbr_start, pbr_chunk, pbr_kind, pbr_a, pbr_b;
-    int64_t sp_total = 0;
-    if (P.deterministic) {
-        sp_off.resize(sw_ent.size());
-        std::vector<std::vector<int32_t>> items(A);
-        for (size_t w = 0; w < sw_ent.size(); w++) {
-            sp_off[w] = sp_total;
-            sp_total += ((int64_t)(sw_ent[w] + 1) * 36 + 8);
-            items[sw_ent[w]].push_back((int32_t)w);
-        }
-        se_start.assign(A + 1, 0);
-        for (int a = 0; a < A; a++) {
-            // frame-ascending: an entity's pairs are frame-ascending in pair_rec, so ordering its items by their first pair does it
-            std::sort(items[a].begin(), items[a].end(), [&](int32_t x, int32_t y) { return sw_begin[x] < sw_begin[y]; });
-            se_start[a] = (int32_t)se_items.size();
-            se_items.insert(se_items.end(), items[a].begin(), items[a].end());
-        }
-        se_start[A] = (int32_t)se_items.size();
-        std::vector<std::vector<int32_t>> by_cam(C), by_mk(A);
-        pbr_start.push_back(0);
-        auto emit = [&](int kind, int ea, int eb, const std::vector<int32_t> &chs) {
-            if (chs.empty()) return;
-            pbr_chunk.insert(pbr_chunk.end(), chs.begin(), chs.end());
-            pbr_start.push_back((int32_t)pbr_chunk.size());
-            pbr_kind.push_back(kind); pbr_a.push_back(ea); pbr_b.push_back(eb);
-        };
-        std::vector<int32_t> run;
-        for (int ch = 0; ch < P.n_chunks; ch++) {
-            const ObsIdx &h = b_idx[chunk_start[ch]];
-            by_cam[h.cam].push_back(ch);
-            by_mk[h.marker].push_back(ch);
-            run.push_back(ch);
-            const bool last = ch + 1 == P.n_chunks || b_idx[chunk_start[ch + 1]].cam != h.cam || b_idx[chunk_start[ch + 1]].marker != h.marker;
-            if (last) { emit(2, h.cam, h.marker, run); run.clear(); }
-        }
-        for (int c = 0; c < C; c++) emit(0, c, 0, by_cam[c]);
-        for (int m = 0; m < A; m++) emit(1, m, 0, by_mk[m]);
-        P.n_pbr = (int)pbr_kind.size();
-        P.pb_stride = L.oi ? 152 : 90;
-    }
-    // many shared entities: the MFMA kernel owns 16 x 32-entity blocks of S and streams frame ranges (solve_kernels.hip);
-    // frame ranges are cut so that the grid is a few workgroups per CU
-    std::vector<int32_t> sm_ga, sm_gb, sm_fb, sm_fe, slot_frame, slot_dense, dense_ent;
-    std::vector<int32_t> sm_frames;   // frame lists of the blocks, back to back
-    if (schur_mfma && !P.use_pcg) {
-        // dense entity 0 = the pseudo entity g_f; then the entities that are seen at all, MOST FREQUENT FIRST (ties: ascending):
-        // the often-seen entities form dense groups, the rarely seen ones share groups that whole stretches of frames do not
-        // touch at all -- a block of S then only streams the frames in which both of its entity groups are present
-        std::vector<int32_t> seen;
-        for (int a = 0; a < A; a++)
-            if (!inc[a].empty()) seen.push_back(a);
-        std::stable_sort(seen.begin(), seen.end(), [&](int32_t x, int32_t y) { return inc[x].size() > inc[y].size(); });
-        std::vector<int32_t> dense_of(A, -1);
-        dense_ent.push_back(-1);
-        for (int32_t a : seen) { dense_of[a] = (int32_t)dense_ent.size(); dense_ent.push_back(a); }
-        P.Ad = ((int)dense_ent.size() + 31) / 32 * 32;
-        dense_ent.resize(P.Ad, -1);
-        const int nga = P.Ad / 16, ngb = P.Ad / 32;
-        // frames in which a group of 16 (a side) / 32 (b side) dense entities has anybody present; the pseudo entity is everywhere
-        std::vector<std::vector<uint8_t>> pa(nga, std::vector<uint8_t>(F, 0)), pb(ngb, std::vector<uint8_t>(F, 0));
-        for (int f = 0; f < F; f++) {
-            pa[0][f] = pb[0][f] = 1;
-            for (int s = fslot_start[f]; s < fslot_start[f + 1]; s++) {
-                const int dd = dense_of[fslot_ent[s]];
-                pa[dd / 16][f] = 1;
-                pb[dd / 32][f] = 1;
-            }
-        }
-        struct Blk { int ga, gb; std::vector<int32_t> fr; };
-        std::vector<Blk> blks;
-        int64_t total_steps = 0;
-        for (int ga = 0; ga < nga; ga++)
-            for (int gb = 0; gb <= (16 * ga + 15) / 32; gb++) {
-                Blk bk{ga, gb, {}};
-                for (int f = 0; f < F; f++)
-                    if (pa[ga][f] && pb[gb][f]) bk.fr.push_back(f);
-                if (bk.fr.empty()) continue;
-                total_steps += ((int64_t)bk.fr.size() + 1) / 2;
-                blks.push_back(std::move(bk));
-            }
-        // cut every block's frame list into pieces of about total / target frames (even lengths: two frames per step), pieces of
-        // the same stretch of frames next to each other so that the workgroups in flight share panels in L2
-        int target = 12 * (int)blks.size();   // pieces per block: measured optimum at config 5 (8: -1 %, 24: -9 %); AAR_SCHUR_SPLIT overrides
-        if (const char *e = getenv("AAR_SCHUR_SPLIT")) target = std::max(1, atoi(e)) * (int)blks.size();
-        const int64_t plen = std::max<int64_t>(16, ((2 * total_steps + target - 1) / target + 3) / 4 * 4);   // whole steps of the kernel's K loop (2 or 4 frames)
-        struct Piece { int blk; int64_t b, e; int f0; };
-        std::vector<Piece> pieces;
-        for (size_t k = 0; k < blks.size(); k++)
-            for (int64_t b0 = 0; b0 < (int64_t)blks[k].fr.size(); b0 += plen)
-                pieces.push_back({(int)k, b0, std::min<int64_t>(b0 + plen, (int64_t)blks[k].fr.size()), blks[k].fr[b0]});
-        std::stable_sort(pieces.begin(), pieces.end(), [](const Piece &x, const Piece &y) { return x.f0 < y.f0; });
-        for (const Piece &pc : pieces) {
-            sm_ga.push_back(blks[pc.blk].ga); sm_gb.push_back(blks[pc.blk].gb);
-            sm_fb.push_back((int32_t)sm_frames.size());
-            sm_frames.insert(sm_frames.end(), blks[pc.blk].fr.begin() + pc.b, blks[pc.blk].fr.begin() + pc.e);
-            sm_fe.push_back((int32_t)sm_frames.size());
-        }
-        slot_frame.resize(P.total_slots);
-        slot_dense.resize(P.total_slots);
-        for (int f = 0; f < F; f++)
-            for (int s = fslot_start[f]; s < fslot_start[f + 1]; s++) {
-                slot_frame[s] = f;
-                slot_dense[s] = dense_of[fslot_ent[s]];
-            }
-        P.n_smwork = (int)sm_ga.size();
-    }
-
-    std::vector<int32_t> ent_fixed(A, 0);
-    for (int c = 0; c < C; c++) ent_fixed[c] = (c == L.rc || !L.oc) ? 1 : 0;
-    for (int m = 0; m < M; m++) ent_fixed[C + m] = (m == L.rm || !L.om) ? 1 : 0;
-    for (int e = 0; e < C + M; e++) ent_fixed[e] |= held[e];
-    spcg_build_fixed_mask(P, ent_fixed.data());   // (k_spcg reads the same flags as bits in its arguments)
-    // (intrinsics entities are free, root camera included: fill_io_vec_cam_intrinsics covers ALL cameras, libs/multicam_mapper.cpp:488-498;
-    //  their two idle parameters have zero rows and columns and get mu on the diagonal, like the reference's five distortion columns)
-    std::vector<double> Kh(d->cam_mats, d->cam_mats + 9 * (size_t)C);
-
-    // ---- upload ----
-#define UP(field, vec) if ((rc = dev_upload(pb, &P.field, vec))) return fail(rc)
-    UP(K, Kh); UP(a_idx, a_idx); UP(a_uv, a_uv); UP(frame_obs_start, frame_obs_start); UP(frame_stride, frame_stride);
-    UP(fslot_start, fslot_start); UP(fslot_ent, fslot_ent); UP(b_idx, b_idx); UP(b_uv, b_uv);
-    UP(chunk_start, chunk_start); UP(ent_fixed, ent_fixed); UP(up_start, up_start); UP(up_ent, up_ent);
-    UP(sw_ent, sw_ent); UP(sw_begin, sw_begin); UP(sw_end, sw_end); UP(pair_rec, pair_rec);
-    if (P.use_pcg) {   // balanced work items: at most `chunk` incidences of one entity each, 1 .. 8 items per entity (PCG_MAX_ITEMS)
-        const int cus = P.n_cus;
-        int64_t longest = 0;
-        for (int a = 0; a < A; a++) longest = std::max<int64_t>(longest, pair_base[a + 1] - pair_base[a]);
-        int64_t chunk = std::max<int64_t>(256, (total_pairs + 2LL * cus - 1) / (2LL * cus));
-        chunk = std::max<int64_t>(chunk, (longest + 7) / 8);
-        if (const char *t = getenv("AAR_PCG_CHUNK")) chunk = std::max<int64_t>((longest + 7) / 8, atoll(t));
-        std::vector<int32_t> it_ent, it_begin, it_end, ent_item_start(A + 1, 0);
-        for (int a = 0; a < A; a++) {
-            ent_item_start[a] = (int32_t)it_ent.size();
-            const int64_t b0 = pair_base[a], e0 = ent_fixed[a] ? pair_base[a] : pair_base[a + 1];
-            int64_t b = b0;
-            do {
-                const int64_t e = std::min<int64_t>(e0, b + chunk);
-                it_ent.push_back(a); it_begin.push_back((int32_t)b); it_end.push_back((int32_t)e);
-                b = e;
-            } while (b < e0);
-        }
-        ent_item_start[A] = (int32_t)it_ent.size();
-        P.pcg_n_items = (int)it_ent.size();
-        UP(pcg_it_ent, it_ent); UP(pcg_it_begin, it_begin); UP(pcg_it_end, it_end); UP(pcg_ent_item_start, ent_item_start);
-    }
-    if (P.deterministic) { UP(sp_off, sp_off); UP(se_start, se_start); UP(se_items, se_items); UP(pbr_start, pbr_start); UP(pbr_chunk, pbr_chunk); UP(pbr_kind, pbr_kind); UP(pbr_a, pbr_a); UP(pbr_b, pbr_b); }
-    if (P.n_smwork) { UP(sm_ga, sm_ga); UP(sm_gb, sm_gb); UP(sm_fb, sm_fb); UP(sm_fe, sm_fe); UP(slot_dense, slot_dense); UP(slot_frame, slot_frame); UP(dense_ent, dense_ent); UP(sm_frames, sm_frames); }
+// ---- step 9: upload of the plan's tables (and the counts that go with them) ----
+int upload_plan(aar_problem *pb, const aar_problem_desc *d, const FramePlan &fp, const TablePlan &tp) {
+    DeviceProblem &P = pb->P;
+    int rc;
+    P.n_chunks = tp.n_chunks; P.n_swork = tp.n_swork;
+    P.n_pbr = tp.n_pbr; P.pb_stride = tp.pb_stride;
+    P.Ad = tp.Ad; P.n_smwork = tp.n_smwork;
+    P.pcg_n_items = tp.pcg_n_items;
+    spcg_build_fixed_mask(P, tp.ent_fixed.data());   // (k_spcg reads the same flags as bits in its arguments)
+    std::vector<double> Kh(d->cam_mats, d->cam_mats + 9 * (size_t)P.C);
+#define UP(field, vec) if ((rc = dev_upload(pb, &P.field, vec))) return rc
+    UP(K, Kh); UP(a_idx, fp.a_idx); UP(a_uv, fp.a_uv); UP(frame_obs_start, fp.frame_obs_start); UP(frame_stride, fp.frame_stride);
+    UP(fslot_start, fp.fslot_start); UP(fslot_ent, fp.fslot_ent); UP(b_idx, tp.b_idx); UP(b_uv, tp.b_uv);
+    UP(chunk_start, tp.chunk_start); UP(ent_fixed, tp.ent_fixed); UP(up_start, tp.up_start); UP(up_ent, tp.up_ent);
+    UP(sw_ent, tp.sw_ent); UP(sw_begin, tp.sw_begin); UP(sw_end, tp.sw_end);
+    if ((rc = dev_upload(pb, reinterpret_cast<PairRec **>(&P.pair_rec), tp.pair_rec))) return rc;
+    if (P.use_pcg) { UP(pcg_it_ent, tp.pcg_it_ent); UP(pcg_it_begin, tp.pcg_it_begin); UP(pcg_it_end, tp.pcg_it_end); UP(pcg_ent_item_start, tp.pcg_ent_item_start); }
+    if (P.deterministic) { UP(sp_off, tp.sp_off); UP(se_start, tp.se_start); UP(se_items, tp.se_items); UP(pbr_start, tp.pbr_start); UP(pbr_chunk, tp.pbr_chunk); UP(pbr_kind, tp.pbr_kind); UP(pbr_a, tp.pbr_a); UP(pbr_b, tp.pbr_b); }
+    if (P.n_smwork) { UP(sm_ga, tp.sm_ga); UP(sm_gb, tp.sm_gb); UP(sm_fb, tp.sm_fb); UP(sm_fe, tp.sm_fe); UP(slot_dense, tp.slot_dense); UP(slot_frame, tp.slot_frame); UP(dense_ent, tp.dense_ent); UP(sm_frames, tp.sm_frames); }
 #undef UP
-#define AL(field, count) if ((rc = dev_alloc(pb, &P.field, (size_t)(count)))) return fail(rc)
+    return AAR_OK;
+}
+
+#define AL(field, count) if ((rc = dev_alloc(pb, &P.field, (size_t)(count)))) return rc
+
+// ---- step 10: workspaces ----
+int alloc_workspaces(aar_problem *pb, const CreateEnv &E, int64_t sp_total) {
+    DeviceProblem &P = pb->P;
+    const int A = P.A, F = P.F;
+    const int64_t N = P.N;
+    int rc;
     AL(z[0], 6 * (size_t)(A + F)); AL(z[1], 6 * (size_t)(A + F));
     AL(ent[0], (size_t)(A + F) * ENT_STRIDE); AL(ent[1], (size_t)(A + F) * ENT_STRIDE);
     for (int w = 0; w < 2; w++) {
@@ -1794,16 +1564,16 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
         P.blk[w].rhs = P.blk[w].S + (size_t)P.n_pad * P.n_pad;
         P.blk[w].g0 = P.blk[w].rhs + P.n_pad;
         P.blk[w].tail = P.blk[w].g0 + P.n_pad;
-        if (hipMemset(P.blk[w].tail, 0, 8 * sizeof(double)) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipMemset failed"));
+        if (hipMemset(P.blk[w].tail, 0, 8 * sizeof(double)) != hipSuccess) return set_error(AAR_ERR_HIP, "hipMemset failed");
     }
     if (P.deterministic) { AL(sp_part, (size_t)sp_total); AL(pb_part, (size_t)P.n_chunks * P.pb_stride); }
     if (P.use_pcg) {
         AL(pcg_ws, (size_t)P.pcg_n_items * 28 + 6 * (size_t)F + 8); AL(pcg_counter, 8);
         AL(pcg_yg, (size_t)3 * PCG_NYV * P.n_pad + (size_t)28 * A + 160 + 8); AL(pcg_hop, 2 * PCG_HOP_WORDS);   // (+ 160: the coarse operator's accumulator)
-        if (const char *t = getenv("AAR_PCG_FUSED")) P.pcg_fused = atoi(t) != 0 ? 1 : 0;
+        if (E.pcg_fused) P.pcg_fused = *E.pcg_fused;
         {   // k_pcgf's operator reads an fp32 copy of W (half the bytes of its pass over the frames; written by pass A instead of the fp64 blocks): non-deterministic runs, one rank or many
             int w32 = 1;
-            if (const char *t = getenv("AAR_PCG_W32")) w32 = atoi(t) != 0 ? 1 : 0;
+            if (E.pcg_w32) w32 = *E.pcg_w32;
             if (w32 && P.pcg_fused && !P.deterministic && P.pcg_eta >= PCG_W32_MIN_ETA)   // (a caller who asks for residuals below 1e-4 gets fp64 blocks throughout)
                 for (int w = 0; w < 2; w++) AL(blk[w].Wf, (size_t)P.total_slots * 36 + 4);
         }
@@ -1816,11 +1586,11 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
             AL(pcgd_setup, (size_t)A * 28 + 152); AL(pcgd_minv, (size_t)A * 36 + 72 + (size_t)12 * A + 8);   // (+ the coarse operator's shares; + its inverse blocks and the table of Z)
             AL(pcgd_state, 2 * (18 * (size_t)A + 8)); AL(pcgd_y, 3 * (6 * (size_t)A + 8));
             if (hipHostMalloc((void **)&pb->h_pcg, 8 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-                return fail(set_error(AAR_ERR_HIP, "hipHostMalloc failed"));
+                return set_error(AAR_ERR_HIP, "hipHostMalloc failed");
             memset(pb->h_pcg, 0, 8 * sizeof(double));
-            if (hipHostGetDevicePointer((void **)&P.pcgd_host, pb->h_pcg, 0) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "hipHostGetDevicePointer failed"));
+            if (hipHostGetDevicePointer((void **)&P.pcgd_host, pb->h_pcg, 0) != hipSuccess) return set_error(AAR_ERR_HIP, "hipHostGetDevicePointer failed");
         }
-        if (const char *t = getenv("AAR_PCG_GRID")) P.pcg_grid = std::max(1, atoi(t));
+        if (E.pcg_grid) P.pcg_grid = *E.pcg_grid;
         // the kernels' grid-wide hand-overs need every workgroup resident: never more than the occupancy query admits (the override included),
         // asked at the footprint they are launched with (P.pcg_coarse is final: cut above where its tables do not fit)
         P.pcg_grid = std::min(P.pcg_grid, pcg_max_grid(A, P.pcg_coarse != 0, P.n_cus));
@@ -1835,6 +1605,14 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
     AL(Lp, (size_t)P.nT * P.n_pad * CHOL_NB); AL(zf, P.n_pad);
     AL(err_part, std::max<size_t>((size_t)F, (size_t)((N + 255) / 256)) + 1);
     AL(lin_part, 2 * (size_t)(F + 1)); AL(scal, 8); AL(flags, 4);
+    return AAR_OK;
+}
+
+// ---- step 11: priors (the pose priors' and pair priors' data, the pair priors' element lists from the plan, their outputs) ----
+int upload_priors(aar_problem *pb, const aar_problem_constraints *cons, const TablePlan &tp) {
+    DeviceProblem &P = pb->P;
+    const int C = P.C, rank = pb->comm ? pb->comm->rank : 0;
+    int rc;
     if (cons && cons->n_priors > 0) {
         const int np_ = cons->n_priors;
         std::vector<int32_t> pent(np_);
@@ -1845,69 +1623,96 @@ static int problem_create(const aar_problem_desc *d, const aar_solver_options *o
             memcpy(&pdat[(size_t)p * PRIOR_DAT], q.x6, 6 * sizeof(double));
             memcpy(&pdat[(size_t)p * PRIOR_DAT + 6], q.info, 36 * sizeof(double));
         }
-        if ((rc = dev_upload(pb, &P.prior_ent, pent)) || (rc = dev_upload(pb, &P.prior_dat, pdat))) return fail(rc);
+        if ((rc = dev_upload(pb, &P.prior_ent, pent)) || (rc = dev_upload(pb, &P.prior_dat, pdat))) return rc;
         AL(prior_out, (size_t)np_ * 8 + 1);
         P.n_prior = np_;
         P.prior_rank0 = rank == 0 ? 1 : 0;
         pb->priors.assign(cons->priors, cons->priors + np_);
     }
     if (cons && cons->n_pair_priors > 0) {
-        // per pair: its ends and record; per free end entity: the (pair, side) items that add to its diagonal block, in ascending pair order
         const int np_ = cons->n_pair_priors;
-        std::vector<int32_t> ends((size_t)np_ * 4, 0);
         std::vector<double> pdat((size_t)np_ * PRIOR_DAT);
-        std::vector<std::vector<int32_t>> items(C + M);
         for (int p = 0; p < np_; p++) {
             const aar_pair_prior &q = cons->pair_priors[p];
-            const int off = q.kind == AAR_PRIOR_CAMERA ? 0 : C, ea = off + q.index_a, eb = off + q.index_b;
-            const bool fa = ent_fixed[ea] != 0, fb = ent_fixed[eb] != 0;
-            ends[4 * (size_t)p] = ea; ends[4 * (size_t)p + 1] = eb; ends[4 * (size_t)p + 2] = (!fa && !fb) ? 1 : 0;
-            if (!fa) items[ea].push_back(2 * p);
-            if (!fb) items[eb].push_back(2 * p + 1);
             memcpy(&pdat[(size_t)p * PRIOR_DAT], q.x6_rel, 6 * sizeof(double));
             memcpy(&pdat[(size_t)p * PRIOR_DAT + 6], q.info, 36 * sizeof(double));
         }
-        std::vector<int32_t> el_ent, el_start, el_item;
-        for (int e = 0; e < C + M; e++) {
-            if (items[e].empty()) continue;
-            el_ent.push_back(e);
-            el_start.push_back((int32_t)el_item.size());
-            el_item.insert(el_item.end(), items[e].begin(), items[e].end());
-        }
-        el_start.push_back((int32_t)el_item.size());
-        P.n_pair_el = (int)el_ent.size();
-        P.n_pair_items = (int)el_item.size();
-        if (el_ent.empty()) el_ent.push_back(0);
-        if (el_item.empty()) el_item.push_back(0);
-        if ((rc = dev_upload(pb, &P.pair_ends, ends)) || (rc = dev_upload(pb, &P.pair_dat, pdat)) || (rc = dev_upload(pb, &P.pair_el_ent, el_ent)) ||
-            (rc = dev_upload(pb, &P.pair_el_start, el_start)) || (rc = dev_upload(pb, &P.pair_el_item, el_item)))
-            return fail(rc);
+        P.n_pair_el = tp.n_pair_el;
+        P.n_pair_items = tp.n_pair_items;
+        if ((rc = dev_upload(pb, &P.pair_ends, tp.pair_ends)) || (rc = dev_upload(pb, &P.pair_dat, pdat)) || (rc = dev_upload(pb, &P.pair_el_ent, tp.pair_el_ent)) ||
+            (rc = dev_upload(pb, &P.pair_el_start, tp.pair_el_start)) || (rc = dev_upload(pb, &P.pair_el_item, tp.pair_el_item)))
+            return rc;
         AL(pair_rec_ws, (size_t)np_ * 54);
         AL(pair_out, (size_t)np_ * 8 + 1);
         P.n_pair = np_;
         P.prior_rank0 = rank == 0 ? 1 : 0;
     }
+    return AAR_OK;
+}
 #undef AL
-    if ((rc = dev_alloc(pb, &pb->d_diag, P.n_pad))) return fail(rc);
-    if (pb->comm && (rc = dev_alloc(pb, &pb->d_frames_all, 6 * (size_t)std::max(Fg, 1)))) return fail(rc);
-    if (pb->comm && (rc = dev_alloc(pb, &pb->d_pack, (size_t)P.n_pad * (P.n_pad + 1) / 2 + 2 * (size_t)P.n_pad + 8))) return fail(rc);
+
+// ---- step 12: the exchange buffers, the host's result record, and the warm-up copy ----
+int finish_uploads(aar_problem *pb) {
+    DeviceProblem &P = pb->P;
+    const int A = P.A, F = P.F, Fg = pb->L.F;
+    int rc;
+    if ((rc = dev_alloc(pb, &pb->d_diag, P.n_pad))) return rc;
+    if (pb->comm && (rc = dev_alloc(pb, &pb->d_frames_all, 6 * (size_t)std::max(Fg, 1)))) return rc;
+    if (pb->comm && (rc = dev_alloc(pb, &pb->d_pack, (size_t)P.n_pad * (P.n_pad + 1) / 2 + 2 * (size_t)P.n_pad + 8))) return rc;
     if (hipHostMalloc((void **)&pb->h_scal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-        return fail(set_error(AAR_ERR_HIP, "hipHostMalloc failed"));
+        return set_error(AAR_ERR_HIP, "hipHostMalloc failed");
     memset(pb->h_scal, 0, 16 * sizeof(double));
     if (hipHostGetDevicePointer((void **)&P.host_result, pb->h_scal, 0) != hipSuccess)
-        return fail(set_error(AAR_ERR_HIP, "hipHostGetDevicePointer failed"));
-    if (hipStreamSynchronize(pb->stream) != hipSuccess) return fail(set_error(AAR_ERR_HIP, "upload failed"));
+        return set_error(AAR_ERR_HIP, "hipHostGetDevicePointer failed");
+    if (hipStreamSynchronize(pb->stream) != hipSuccess) return set_error(AAR_ERR_HIP, "upload failed");
     {   // the runtime brings its device-to-host copy path up on first use (8-13 ms, once per process: scripts/probe/outlier2.py):
         // better here than inside the caller's first solve
-        if (pb->h_z.reserve((size_t)6 * (A + F))) return fail(set_error(AAR_ERR_HIP, "hipHostMalloc(pose staging) failed"));
+        if (pb->h_z.reserve((size_t)6 * (A + F))) return set_error(AAR_ERR_HIP, "hipHostMalloc(pose staging) failed");
         if (hipEventCreateWithFlags(&pb->up_ev, hipEventDisableTiming) != hipSuccess) { pb->up_ev = nullptr; (void)hipGetLastError(); }
         if (hipMemcpyAsync(pb->h_z.data(), P.z[0], (size_t)6 * (A + F) * sizeof(double), hipMemcpyDeviceToHost, pb->stream) != hipSuccess ||
             hipStreamSynchronize(pb->stream) != hipSuccess)
-            return fail(set_error(AAR_ERR_HIP, "device-to-host copy failed"));
+            return set_error(AAR_ERR_HIP, "device-to-host copy failed");
     }
-    pb->h_fslot_start = fslot_start;
-    pb->h_fslot_ent = fslot_ent;
-    pb->h_ent_fixed = ent_fixed;
+    return AAR_OK;
+}
+
+}  // namespace
+
+// cons: validated and not empty, or NULL
+static int problem_create(const aar_problem_desc *d, const aar_solver_options *opts, const aar_problem_constraints *cons, aar_problem **out) {
+    if (!d || !out) return set_error(AAR_ERR_INVALID, "aar_problem_create: null argument");
+    CreateEnv E;
+    int rc = read_create_options(opts, E);                                   // 1. options struct and environment
+    if (rc) return rc;
+    std::vector<int64_t> per_frame;
+    int64_t global_slots = 0;
+    if ((rc = validate_and_count(d, per_frame, global_slots))) return rc;   // 2. validation and counting
+    if ((rc = ensure_device(d->device_id))) return rc;                      // 3. device, streams and events
+    aar_problem *pb = new aar_problem();
+    auto fail = [&](int code) { aar_problem_destroy(pb); return code; };
+    if ((rc = open_streams(d, E, pb))) return fail(rc);
+    if ((rc = plan_shard(d, per_frame, pb))) return fail(rc);               // 4. shard range
+    DeviceProblem &P = pb->P;
+    FramePlan fp = plan_frames(*d, pb->L, per_frame, pb->f_begin, pb->f_end, pb->o_begin);   // 5. frame stage
+    P.max_kf = fp.max_kf;
+    P.total_slots = fp.total_slots;
+    int local_rc = fp.status;   // rank-local limits: decided collectively below
+    const std::vector<int32_t> held = plan_held_entities(pb->L, cons);
+    const bool held_extra = std::find(held.begin(), held.end(), 1) != held.end();
+    bool schur_mfma = false;
+    choose_solver(pb, E, global_slots, held_extra, local_rc, schur_mfma);   // 6. solver choice and limits
+    if ((rc = agree_on_status(pb, local_rc))) return fail(rc);              // 7. collective agreement
+    PlanKnobs knobs = E.knobs;
+    knobs.deterministic = P.deterministic != 0; knobs.schur_mfma = schur_mfma; knobs.use_pcg = P.use_pcg != 0; knobs.n_cus = P.n_cus;
+    TablePlan tp = plan_tables(pb->L, fp, cons, knobs);                     // 8. table stage
+    if ((rc = upload_plan(pb, d, fp, tp))) return fail(rc);                 // 9. upload
+    if ((rc = alloc_workspaces(pb, E, tp.sp_total))) return fail(rc);       // 10. workspaces
+    if ((rc = upload_priors(pb, cons, tp))) return fail(rc);                // 11. priors
+    if ((rc = finish_uploads(pb))) return fail(rc);                         // 12. warm-up copy
+    // host copies of the index structure: the plan's own vectors
+    pb->h_fslot_start = std::move(fp.fslot_start);
+    pb->h_fslot_ent = std::move(fp.fslot_ent);
+    pb->h_ent_fixed = std::move(tp.ent_fixed);
     *out = pb;
     return AAR_OK;
 }
@@ -2294,32 +2099,21 @@ int rr_setup(aar_problem *pb) {
     RRWork &w = pb->rr;
     const int64_t N = P.N;
     const int C = P.C, M = P.M;
-    // ordering B as the problem built it (a stable sort of ordering A by camera, marker): rebuilt here from the device's ordering A,
+    // ordering B as the problem built it: rebuilt by the planner's own function (host/problem_plan.h) from the device's ordering A,
     // its (camera, marker) runs and their lists per camera / marker
     std::vector<ObsIdx> a_idx((size_t)N);
     int rc;
     if (N && (rc = copy_d2h(pb, a_idx.data(), P.a_idx, (size_t)N * sizeof(ObsIdx)))) return rc;
-    std::vector<int32_t> perm((size_t)N);
-    std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) {
-        const ObsIdx &p = a_idx[x], &q = a_idx[y];
-        if (p.cam != q.cam) return p.cam < q.cam;
-        if (p.marker != q.marker) return p.marker < q.marker;
-        return p.frame < q.frame;
-    });
-    std::vector<int32_t> run_start, run_mk, cam_run_start(C + 1, 0), mk_run_start(M + 1, 0), mk_runs;
-    for (int64_t i = 0; i < N;) {
-        const ObsIdx &h = a_idx[perm[i]];
-        int64_t e = i;
-        while (e < N && a_idx[perm[e]].cam == h.cam && a_idx[perm[e]].marker == h.marker) e++;
+    const OrderingB B = plan_ordering_b(a_idx.data(), N);
+    const std::vector<int32_t> &perm = B.perm, &run_start = B.run_start;
+    const int R = (int)run_start.size() - 1;
+    std::vector<int32_t> run_mk(R), cam_run_start(C + 1, 0), mk_run_start(M + 1, 0), mk_runs;
+    for (int r = 0; r < R; r++) {
+        const ObsIdx &h = a_idx[perm[run_start[r]]];
         cam_run_start[h.cam + 1]++;
         mk_run_start[h.marker - C + 1]++;
-        run_start.push_back((int32_t)i);
-        run_mk.push_back(h.marker - C);
-        i = e;
+        run_mk[r] = h.marker - C;
     }
-    const int R = (int)run_start.size();
-    run_start.push_back((int32_t)N);
     for (int c = 0; c < C; c++) cam_run_start[c + 1] += cam_run_start[c];
     for (int m = 0; m < M; m++) mk_run_start[m + 1] += mk_run_start[m];
     mk_runs.resize(R);

@@ -5,10 +5,10 @@
 #include <stdint.h>
 #include <utility>
 
+#include "../host/plan_types.h"   // CHOL_NB, PASSB_CHUNK, ObsIdx, pack_slots: what the host-only planner shares with the kernels
+
 namespace aar {
 
-constexpr int CHOL_NB = 96;       // dense LDL^T tile (16 entity blocks of 6)
-constexpr int PASSB_CHUNK = 1024;  // upper limit of AAR_PASSB_CHUNK (observations of one (camera, marker) run handled by one wavefront; the default rule stops at 512)
 // CG on the explicit reduced system (spcg_kernels.hip): iteration cap (sizes the hand-over buffers: one per iteration plus the
 // start-up and the final one), largest system (tiles of 96 unknowns: the six rows of an entity live in one wavefront's registers)
 constexpr int SPCG_MAX_IT = 128, SPCG_BUFS = SPCG_MAX_IT + 2, SPCG_MAX_NT = 14;
@@ -44,11 +44,6 @@ struct LaunchHook {  // called around every kernel launch when profiling is on
     void (*pre)(void *ctx, int kid) = nullptr;
     void (*post)(void *ctx, int kid) = nullptr;
     void *ctx = nullptr;
-};
-
-// Per-observation record of an ordering: {frame (local), camera, marker, frame-local W slots: camera | marker << 10 | intrinsics << 21}
-struct ObsIdx {
-    int32_t frame, cam, marker, slots;
 };
 
 struct DeviceProblem {
@@ -234,8 +229,6 @@ inline KTable k_table(const DeviceProblem &P, int which) {
     if (P.intr) return KTable{P.ent[which] + (size_t)(P.C + P.M) * ENT_STRIDE_H, ENT_STRIDE_H};
     return KTable{P.K, 9};
 }
-constexpr int SLOT_C_BITS = 10, SLOT_M_BITS = 11;   // ObsIdx::slots
-inline int pack_slots(int sc, int sm, int sk) { return sc | (sm << SLOT_C_BITS) | (sk << (SLOT_C_BITS + SLOT_M_BITS)); }
 
 extern volatile int g_last_kernel_id;   // the kernel id of the most recent launch of this process (diagnostics: AAR_ABORT_BACKTRACE prints it)
 struct HookScope {  // RAII: pre/post around one launch

@@ -336,12 +336,13 @@ def test_solution_writer_gathers_interleaved_cameras(tmp_path):
 
 
 def test_host_code_under_address_and_ub_sanitizers(tmp_path):
-    # file formats, shard plan, detections / calibration readers (truncated and malformed inputs included) compiled with
+    # file formats, shard plan, detections / calibration readers (truncated and malformed inputs included), the problem planner's index
+    # tables (default, deterministic, MFMA, solver pcg, pair priors, the empty problem) compiled with
     # -fsanitize=address,undefined against stubs of the device entry points: the HOST code of the product, no GPU needed
     import subprocess
     from conftest import PKG, ROOT
     exe = str(tmp_path / "asan_host_main")
-    host = [os.path.join(PKG, "host", f) for f in ("dataset.cpp", "synth.cpp", "solution_io.cpp", "cam_config.cpp", "initializer.cpp")]
+    host = [os.path.join(PKG, "host", f) for f in ("dataset.cpp", "synth.cpp", "solution_io.cpp", "cam_config.cpp", "initializer.cpp", "problem_plan.cpp")]
     cc = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
                          os.path.join(ROOT, "tests", "tools", "asan_host_main.cpp")] + host + ["-o", exe], capture_output=True, text=True)
     assert cc.returncode == 0, cc.stderr[-3000:]
@@ -352,6 +353,7 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr and "LeakSanitizer" not in run.stderr
     assert "obs " in run.stdout and "subseqs" in run.stdout
+    assert run.stdout.count("plan ") == 8 and "plan empty: chunks 0 items 0" in run.stdout
 
 
 def test_reference_shaped_solver_code_compiles_against_the_mirror(tmp_path):
