@@ -38,7 +38,9 @@ __device__ __forceinline__ void so3_log(const double *Q, double *phi, double &th
 
 // J_r(phi)^-1 (row-major) of phi with |phi| = th
 __device__ __forceinline__ void so3_jr_inv(const double *phi, double th, double *Ji) {
-    // J_r(phi)^-1 = I + [phi]x / 2 + k [phi]x^2,  k = 1/th^2 - (1 + cos th) / (2 th sin th)
+    // J_r(phi)^-1 = I + [phi]x / 2 + k [phi]x^2,  k = 1/th^2 - cot(th/2) / (2 th),  cot(th/2) = (1 + cos th) / sin th = sin th / (1 - cos th).
+    // The first quotient divides two quantities that vanish at pi and there carries the rounding of 1 + cos th divided by sin th (7e-11 in k at
+    // pi - 1e-6, 8e-10 at pi - 1e-9); the second does the same at 0.  Each is used on its own side of pi / 2, where it has no cancellation.
     double k;
     if (th < 1e-2) {
         const double t2 = th * th;
@@ -46,7 +48,7 @@ __device__ __forceinline__ void so3_jr_inv(const double *phi, double th, double 
     } else {
         double s, c;
         sincos(th, &s, &c);
-        k = 1.0 / (th * th) - (1.0 + c) / (2.0 * th * s);
+        k = 1.0 / (th * th) - (c > 0.0 ? (1.0 + c) / (2.0 * th * s) : s / (2.0 * th * (1.0 - c)));
     }
     const double x = phi[0], y = phi[1], z = phi[2], p2 = x * x + y * y + z * z;
     Ji[0] = 1.0 + k * (x * x - p2); Ji[1] = -0.5 * z + k * x * y;    Ji[2] = 0.5 * y + k * x * z;

@@ -8,7 +8,10 @@
 
 namespace aar {
 
-// log(Q)^v of a rotation matrix, as csrc/so3.hpp: theta from atan2 (exact at small angles, where cv::Rodrigues' matrix -> vector gives 0)
+// log(Q)^v of a rotation matrix, as csrc/so3.hpp in all three branches: theta from atan2 (exact at small angles, where cv::Rodrigues' matrix ->
+// vector gives 0); near pi the axis from the symmetric part (Q + Q^T) / 2 - cos(theta) I = (1 - cos(theta)) n n^T, its sign from v.
+// (rodrigues_mat2vec is the reference's cv::Rodrigues, not this: its theta comes from acos, and below sin(theta) = 1e-5 it takes the axis from
+// the diagonal alone with OpenCV's sign rule -- off by up to twice the distance to pi for a board that faces the root camera.)
 inline void motion_so3_log(const double Q[9], double phi[3]) {
     const double v0 = Q[7] - Q[5], v1 = Q[2] - Q[6], v2 = Q[3] - Q[1];
     const double s2 = std::sqrt(v0 * v0 + v1 * v1 + v2 * v2);   // 2 sin(theta)
@@ -19,7 +22,22 @@ inline void motion_so3_log(const double Q[9], double phi[3]) {
         phi[0] = k * v0; phi[1] = k * v1; phi[2] = k * v2;
         return;
     }
-    rodrigues_mat2vec(Q, phi);   // near pi: the branch that takes the axis from the symmetric part
+    const double oc = 1.0 - c;
+    const double d0 = (Q[0] - c) / oc, d1 = (Q[4] - c) / oc, d2 = (Q[8] - c) / oc;   // n_i^2
+    double n0, n1, n2;
+    if (d0 >= d1 && d0 >= d2) {
+        n0 = std::sqrt(std::fmax(d0, 0.0));
+        n1 = 0.5 * (Q[1] + Q[3]) / (oc * n0); n2 = 0.5 * (Q[2] + Q[6]) / (oc * n0);
+    } else if (d1 >= d2) {
+        n1 = std::sqrt(std::fmax(d1, 0.0));
+        n0 = 0.5 * (Q[1] + Q[3]) / (oc * n1); n2 = 0.5 * (Q[5] + Q[7]) / (oc * n1);
+    } else {
+        n2 = std::sqrt(std::fmax(d2, 0.0));
+        n0 = 0.5 * (Q[2] + Q[6]) / (oc * n2); n1 = 0.5 * (Q[5] + Q[7]) / (oc * n2);
+    }
+    const double in = 1.0 / std::sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    const double sg = (n0 * v0 + n1 * v1 + n2 * v2) < 0.0 ? -1.0 : 1.0;
+    phi[0] = sg * theta * n0 * in; phi[1] = sg * theta * n1 * in; phi[2] = sg * theta * n2 * in;
 }
 
 // (omega, v) of the pair (a, b): omega = log(R_a^T R_b) in the body frame of a, v = t_b - t_a in the root camera's frame
