@@ -39,7 +39,7 @@ SYMBOLS = [
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
-    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system",
+    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_covariance",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
@@ -237,6 +237,11 @@ class CSmoothReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("stop_code", C.c_int32), ("rejected_tries", C.c_int32),
                 ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_data_cost", C.c_double),
                 ("final_prior_cost", C.c_double), ("final_mu", C.c_double), ("seconds", C.c_double)]
+
+
+class CSmoothCovarianceReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("data_cost", C.c_double),
+                ("prior_cost", C.c_double), ("sigma2", C.c_double), ("launches", C.c_int32), ("seconds", C.c_double)]
 
 
 class SmoothParams:
@@ -466,6 +471,7 @@ def lib():
     L.aar_smooth_params_validate.argtypes = [C.c_int32, C.POINTER(CSmoothParams)]
     L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothReport)]
     L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_double, dp, dp, dp, dp, dp]
+    L.aar_track_smooth_covariance.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothCovarianceReport)]
     L.aar_tracker_default_params.argtypes = [C.POINTER(CTrackerParams)]
     L.aar_tracker_default_params.restype = None
     L.aar_tracker_params_validate.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerParams)]
@@ -1628,6 +1634,20 @@ class Problem:
         _check(lib().aar_track_smooth_system(self.handle, _dptr(x), C.byref(sp.c), float(mu), _dptr(diag), _dptr(off), _dptr(rhs),
                                              _dptr(delta), _dptr(cost)))
         return diag[:F], off[:max(F - 1, 0)], rhs[:6 * F], delta[:6 * F], (cost[0], cost[1])
+
+    def track_smooth_covariance(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None):
+        """aar_track_smooth_covariance: (frame_cov [F, 6, 6] = (H^-1)_ff, lag_cov [F-1, 6, 6] = (H^-1)_{f,f+1}, report dict) at x_full, H the
+        matrix of track_smooth_system at mu = 0.  Both UNSCALED: multiply by report["sigma2"]."""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp.check_lengths(F)
+        fc, lc = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6))
+        rep = CSmoothCovarianceReport()
+        rep.struct_size = C.sizeof(CSmoothCovarianceReport)
+        _check(lib().aar_track_smooth_covariance(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
+        return fc[:F], lc[:max(F - 1, 0)], report
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

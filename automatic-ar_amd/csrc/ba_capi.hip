@@ -2639,6 +2639,63 @@ int aar_track_smooth_system(aar_problem *pb, const double *x_full, const aar_smo
     return check_async("smoothing kernels");
 }
 
+// H at mu = 0 as aar_track_smooth_system assembles it, the solve's elimination, then the downward pass of
+// smooth_cov_kernels.hip over what the elimination kept
+int aar_track_smooth_covariance(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *frame_cov, double *lag_cov,
+                                aar_smooth_covariance_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_covariance: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_covariance");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCall c;
+    if ((rc = smooth_prepare(pb, sp, c))) return rc;
+    aar_smooth_covariance_report r;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
+    r.num_vars = 6 * (int64_t)F;
+    if (F > 0) {
+        // S and R of the downward pass: an allocation of their own, the carve of the solve's work area keeps its layout
+        SmoothCall sr;
+        HIP_TRY(hipMalloc((void **)&sr.base, 72 * (size_t)F * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(sr.base, 0, 72 * (size_t)F * sizeof(double), pb->stream));
+        double *S = sr.base, *R = sr.base + 36 * (size_t)F;
+        launch_smooth_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
+        r.launches = 2;
+        r.launches += launch_smooth_solve(c.w, F, 0.0, pb->stream);
+        r.launches += launch_smooth_selinv(c.w, F, S, R, pb->stream);
+        pb->launches += r.launches;
+        double res[8];
+        int32_t flag = 0;
+        if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+        if ((rc = check_async("smoothing covariance kernels"))) return rc;
+        if (flag)
+            return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_covariance: non-positive pivot in the block-tridiagonal elimination (the frames' "
+                                              "detections and the prior do not determine every pose)");
+        r.data_cost = res[0]; r.prior_cost = res[1];
+        if (frame_cov && (rc = copy_d2h(pb, frame_cov, S, 36 * (size_t)F * sizeof(double)))) return rc;
+        if (lag_cov && F > 1 && (rc = copy_d2h(pb, lag_cov, R, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+    }
+    const int64_t dof = r.num_residuals - r.num_vars;
+    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
 int aar_track_smooth(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, double *frame_err, double *pair_err,
                      aar_smooth_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth: null argument");

@@ -315,6 +315,8 @@ size_t smooth_work_doubles(int F);
 void smooth_work_carve(SmoothWork &w, double *base, int F);
 void launch_smooth_eval(const DeviceProblem &P, int which, const SmoothWork &w, int cur, bool with_j, hipStream_t st);   // two launches
 int launch_smooth_solve(const SmoothWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
+// the diagonal and lag-one blocks of H^-1 from what launch_smooth_solve(w, F, 0.0, st) left (smooth_cov_kernels.hip)
+int launch_smooth_selinv(const SmoothWork &w, int F, double *S, double *R, hipStream_t st);                               // returns its launches
 
 // live tracker (live_kernels.hip): one frame per push, the whole LM of the window in ONE launch of one workgroup
 constexpr int LIVE_MAX_W = 16;            // window frames (AAR_TRACKER_MAX_LAG + 1)

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans>] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-smooth-covariance]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -253,6 +253,9 @@ int main(int argc, char *argv[]) {
     bool smooth = false;
     double smooth_sigma[2] = {0.0, 0.0};
     int smooth_args = 0;
+    // ... -smooth-covariance (only with -smooth) also writes every frame's 6x6 pose covariance at the smoothed poses to
+    // final.smooth_covariance.yaml (MultiCamMapper::track_smooth_covariance)
+    bool smooth_covariance = false;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
     // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
@@ -300,6 +303,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-relative-sigma-deg") arg_flag = RelDeg;
         else if (a == "-relative-sigma-m") arg_flag = RelM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
+        else if (a == "-smooth-covariance") { smooth_covariance = true; arg_flag = NONE; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
@@ -397,6 +401,7 @@ int main(int argc, char *argv[]) {
         else if (arg_flag == Threshold) { threshold = stod(a); arg_flag = NONE; }
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
+    if (smooth_covariance && !smooth) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
@@ -600,6 +605,31 @@ int main(int argc, char *argv[]) {
         } catch (const exception &e) {
             cerr << "smoothing failed: " << e.what() << endl;
             return 6;
+        }
+        if (smooth_covariance) {
+            const string cov_path = folder_path + "/final.smooth_covariance.yaml";
+            try {
+                aar::MultiCamMapper::SmoothCovariance sc;
+                mcm.track_smooth_covariance(smooth_sigma[0], smooth_sigma[1], sc);
+                const size_t F = sc.frame_cov.size() / 36;
+                aar::MultiCamMapper::LiveCovariance lc;
+                lc.frame_cov = sc.frame_cov;
+                lc.sigma2.assign(F, sc.report.sigma2);
+                lc.valid.assign(F, 1);
+                if (!mcm.write_live_covariance_file(cov_path, lc)) throw runtime_error(aar_last_error());
+                double lo = 0.0, hi = 0.0;   // 1-sigma translation: sqrt(sigma2 * trace of the translation block)
+                for (size_t f = 0; f < F; f++) {
+                    const double *c = &sc.frame_cov[36 * f];
+                    const double v = sqrt(sc.report.sigma2 * (c[21] + c[28] + c[35]));
+                    if (f == 0 || v < lo) lo = v;
+                    if (f == 0 || v > hi) hi = v;
+                }
+                cout << "smooth-covariance: sigma2 " << sc.report.sigma2 << " (" << sc.report.num_residuals << " residuals, " << sc.report.num_vars
+                     << " unknowns), 1-sigma translation largest " << hi << " m, smallest " << lo << " m, written to " << cov_path << endl;
+            } catch (const exception &e) {
+                cerr << "smooth covariance failed: " << e.what() << endl;
+                return 6;
+            }
         }
     }
     const chrono::duration<double> d = chrono::system_clock::now() - start;

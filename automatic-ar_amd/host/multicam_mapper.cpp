@@ -590,6 +590,30 @@ void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans) {
     eVec2Mats(io_vec);
 }
 
+// The pose covariance of the smoothed track (aar_track_smooth_covariance) at the current poses, under track_smooth()'s model
+void MultiCamMapper::track_smooth_covariance(double sigma_rot, double sigma_trans, SmoothCovariance &out) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::track_smooth_covariance: no data set");
+    mats2eVec();
+    hubberDelta = 10;  // as track_smooth()
+    std::vector<double> x;
+    aar_problem *pb = detail::bind_problem(this, x);
+    if (aar_problem_merge_z(pb, io_vec.data(), x.data())) throw std::runtime_error(aar_last_error());
+    const int F = data_->num_frames;
+    std::vector<double> time(F);
+    for (int f = 0; f < F; f++) time[f] = (double)data_->frame_ids[f];
+    aar_smooth_params sp;
+    memset(&sp, 0, sizeof sp);
+    sp.struct_size = sizeof sp;
+    sp.sigma_rot = sigma_rot;
+    sp.sigma_trans = sigma_trans;
+    sp.frame_time = F ? time.data() : nullptr;
+    out.frame_cov.assign(36 * (size_t)F, 0.0);
+    out.lag_cov.assign(F > 1 ? 36 * (size_t)(F - 1) : 0, 0.0);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    if (aar_track_smooth_covariance(pb, x.data(), &sp, out.frame_cov.data(), out.lag_cov.data(), &out.report)) throw std::runtime_error(aar_last_error());
+}
+
 // The live loop over the data set's frames (aar_tracker_*): what apps/track.cpp does per incoming frame, with the
 // mapper's own frames as the stream.
 namespace {

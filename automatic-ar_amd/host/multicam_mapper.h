@@ -394,6 +394,15 @@ class MultiCamMapper {
     // metre per sqrt(frame id step)), all frames in one LM on the device (aar_track_smooth); the report lands in smooth_report, E_f in
     // track_errors and the pairs' prior costs in smooth_pair_errors
     void track_smooth(double sigma_rot, double sigma_trans);
+    // EXTENSION, no counterpart in the reference: the pose covariance of the smoothed track at the current poses (aar_track_smooth_covariance,
+    // DESIGN.md section 28), with track_smooth()'s prior (the frame ids as its time axis) and Huber delta.  The blocks are UNSCALED: the
+    // covariance of frame f is report.sigma2 * frame_cov[f], that of the motion from f to f + 1 follows with lag_cov[f].
+    struct SmoothCovariance {
+        std::vector<double> frame_cov;   // [num_frames][36] (H^-1)_ff, row-major over (rvec, t)
+        std::vector<double> lag_cov;     // [num_frames - 1][36] (H^-1)_{f,f+1}, the rows belong to frame f
+        aar_smooth_covariance_report report = {};
+    };
+    void track_smooth_covariance(double sigma_rot, double sigma_trans, SmoothCovariance &out);   // throws std::runtime_error on failure
     // no counterpart in the reference as a method: apps/track.cpp's loop (:102-136) over the data set's frames, one frame per push through a
     // LiveTracker (below): each frame starts from its own pose in the data set, the frame ids are the time axis; every frame ends at its lagged
     // pose, the last window at aar_tracker_window's.  smooth = false needs lag = 0.  The pushes' results land in live_results.

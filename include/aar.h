@@ -592,6 +592,29 @@ int aar_track_smooth(aar_problem *, double *x_full, const aar_lm_params *, const
  * non-positive pivot), cost = {sum_f E_f, sum_f e_f^T L_f e_f}.  Every output may be NULL. */
 int aar_track_smooth_system(aar_problem *, const double *x_full, const aar_smooth_params *, double mu, double *diag, double *off, double *rhs,
                             double *delta, double cost[2]);
+/* Pose covariance of the smoothed track: the selected inverse of the H that aar_track_smooth_system returns at mu = 0 for
+ * the same x_full and parameters (data blocks with the problem's Huber weights, prior blocks with frame_time and rel_motion).
+ *   frame_cov [num_frames][36]   = (H^-1)_ff,      row-major over (rvec, t), symmetric to the bit
+ *   lag_cov   [num_frames-1][36] = (H^-1)_{f,f+1}, row-major, the rows belong to frame f; it makes the uncertainty of a relative motion
+ *                                  computable: Cov(z_{f+1} - z_f) = S_ff + S_{f+1,f+1} - S_{f,f+1} - S_{f,f+1}^T
+ * Both are UNSCALED (the convention of aar_problem_covariance and aar_tracker_uncertainty): multiply by report->sigma2.  Computed on the
+ * device from what the solve's cyclic reduction keeps, by one pass back down its elimination tree; bit-reproducible from call to call.
+ * x_full is not modified; no LM state is left behind.  frame_cov, lag_cov and report may each be NULL.  num_frames = 0: AAR_OK, nothing
+ * written; num_frames = 1: frame_cov[0] = V_0^-1.  A frame without detections gets an ordinary finite block as long as the chain of priors
+ * ties it to an observed frame.  A non-positive pivot returns AAR_ERR_NUMERIC and writes nothing; the root pivot counts as non-positive when
+ * it is not above 64 eps times the largest diagonal entry of H_00, the rounding level of its own computation (the extreme case: no detection
+ * in any frame, the prior alone is singular).  A problem with a communicator: AAR_ERR_UNSUPPORTED on every rank. */
+typedef struct aar_smooth_covariance_report {
+    uint32_t struct_size;
+    int64_t num_residuals;       /* 8 num_obs + 6 (num_frames - 1) */
+    int64_t num_vars;            /* 6 num_frames */
+    double data_cost, prior_cost;
+    double sigma2;               /* (data_cost + prior_cost) / (num_residuals - num_vars), 0 when that is <= 0 */
+    int32_t launches;
+    double seconds;
+} aar_smooth_covariance_report;
+int aar_track_smooth_covariance(aar_problem *, const double *x_full, const aar_smooth_params *, double *frame_cov, double *lag_cov,
+                                aar_smooth_covariance_report *report);
 
 /* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
  * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are
