@@ -40,6 +40,7 @@ SYMBOLS = [
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_covariance",
+    "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
@@ -270,6 +271,39 @@ def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, 
     _check(lib().aar_smooth_params_validate(int(num_frames), C.byref(sp.c)))
 
 
+class CSmoothFitParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("rel_tol", C.c_double), ("estimate_px", C.c_int32),
+                ("estimate_rot", C.c_int32), ("estimate_trans", C.c_int32)]
+
+
+class CSmoothFitReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("stop_code", C.c_int32), ("sigma_px", C.c_double),
+                ("sigma_rot", C.c_double), ("sigma_trans", C.c_double), ("sigma_rot_eff", C.c_double), ("sigma_trans_eff", C.c_double),
+                ("last_rel_change", C.c_double), ("lm_steps", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double),
+                ("a_rot", C.c_double), ("u_rot", C.c_double), ("a_trans", C.c_double), ("u_trans", C.c_double), ("u_data", C.c_double),
+                ("data_cost", C.c_double)]
+
+
+def smooth_fit_params(struct_size=None, **over):
+    """aar_smooth_fit_default_params with the given fields replaced (max_iters, rel_tol, estimate_px, estimate_rot, estimate_trans);
+    struct_size overrides the struct's own size (versioning tests)"""
+    p = CSmoothFitParams()
+    lib().aar_smooth_fit_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in ("max_iters", "rel_tol", "estimate_px", "estimate_rot", "estimate_trans"):
+            raise TypeError("aar_smooth_fit_params has no field %r" % k)
+        setattr(p, k, float(v) if k == "rel_tol" else int(v))
+    if struct_size is not None:
+        p.struct_size = int(struct_size)
+    return p
+
+
+def smooth_fit_params_validate(struct_size=None, **over):
+    """aar_smooth_fit_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
+    p = smooth_fit_params(struct_size, **over)
+    _check(lib().aar_smooth_fit_params_validate(C.byref(p)))
+
+
 class CTrackerParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("lag", C.c_int32), ("smooth", C.c_int32), ("sigma_rot", C.c_double), ("sigma_trans", C.c_double),
                 ("with_huber", C.c_int32), ("huber_delta", C.c_float), ("max_obs_per_frame", C.c_int32), ("device_id", C.c_int32),
@@ -472,6 +506,12 @@ def lib():
     L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothReport)]
     L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_double, dp, dp, dp, dp, dp]
     L.aar_track_smooth_covariance.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothCovarianceReport)]
+    L.aar_smooth_fit_default_params.argtypes = [C.POINTER(CSmoothFitParams)]
+    L.aar_smooth_fit_default_params.restype = None
+    L.aar_smooth_fit_params_validate.argtypes = [C.POINTER(CSmoothFitParams)]
+    L.aar_track_smooth_fit.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), C.POINTER(CSmoothFitParams), dp,
+                                       C.POINTER(CSmoothFitReport)]
+    L.aar_track_smooth_fit_terms.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), dp, dp]
     L.aar_tracker_default_params.argtypes = [C.POINTER(CTrackerParams)]
     L.aar_tracker_default_params.restype = None
     L.aar_tracker_params_validate.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerParams)]
@@ -1648,6 +1688,34 @@ class Problem:
         _check(lib().aar_track_smooth_covariance(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), C.byref(rep)))
         report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
         return fc[:F], lc[:max(F - 1, 0)], report
+
+    def track_smooth_fit(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None):
+        """aar_track_smooth_fit: the pixel noise and the motion sigmas fitted to the sequence by EM, from the effective start values
+        sigma_rot, sigma_trans.  fit: None (the defaults), a dict of aar_smooth_fit_params fields, or a CSmoothFitParams.  Returns (x_full with
+        the track at the fitted values, report dict, path [iterations + 1, 3] = (sigma_px, sigma_rot, sigma_trans) per iteration).  Hand
+        report["sigma_rot_eff"], report["sigma_trans_eff"] to track_smooth / tracker_params."""
+        x = np.array(self._x(x_full), dtype=np.float64)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp.check_lengths(self.ds.num_frames)
+        fp = fit if isinstance(fit, CSmoothFitParams) else smooth_fit_params(**(fit or {}))
+        path = np.zeros((max(int(fp.max_iters), 0) + 1, 3))
+        rep = CSmoothFitReport()
+        rep.struct_size = C.sizeof(CSmoothFitReport)
+        _check(lib().aar_track_smooth_fit(self.handle, _dptr(x), C.byref(params) if params is not None else None, C.byref(sp.c), C.byref(fp),
+                                          _dptr(path), C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothFitReport._fields_ if k != "struct_size"}
+        return x, report, path[:report["iterations"] + 1]
+
+    def track_smooth_fit_terms(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None):
+        """aar_track_smooth_fit_terms: one E-step at x_full and the given effective sigmas, no smoothing.  Returns (pair_terms [F-1, 4] =
+        a_r, u_r, a_t, u_t, sums [4] = A_r, U_r, A_t, U_t)."""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp.check_lengths(F)
+        terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(4)
+        _check(lib().aar_track_smooth_fit_terms(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
+        return terms[:max(F - 1, 0)], sums
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

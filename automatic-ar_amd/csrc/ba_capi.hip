@@ -2544,6 +2544,18 @@ struct SmoothCall {
     ~SmoothCall() { if (base) (void)hipFree(base); }
 };
 
+// lambda of the pairs from the sigmas and the frame times, onto the device (F > 1)
+int smooth_upload_lambda(aar_problem *pb, const aar_smooth_params &sp, const SmoothCall &c) {
+    const int F = pb->P.F;
+    std::vector<double> lam(2 * (size_t)(F - 1));
+    for (int f = 0; f + 1 < F; f++) {
+        const double dt = sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0;
+        lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt);
+        lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt);
+    }
+    return copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double));
+}
+
 // workspace, lambda and the expected motions on the device; the frame poses of z[cur] (uploaded by the caller) into w.z[0]
 int smooth_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCall &c) {
     DeviceProblem &P = pb->P;
@@ -2554,13 +2566,7 @@ int smooth_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCall &c) 
     smooth_work_carve(c.w, c.base, F);
     int rc = AAR_OK;
     if (F > 1) {
-        std::vector<double> lam(2 * (size_t)(F - 1));
-        for (int f = 0; f + 1 < F; f++) {
-            const double dt = sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0;
-            lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt);
-            lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt);
-        }
-        if ((rc = copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double)))) return rc;
+        if ((rc = smooth_upload_lambda(pb, sp, c))) return rc;
         if (sp.rel_motion) {
             if ((rc = copy_h2d(pb, c.w.rel_buf, sp.rel_motion, 6 * (size_t)(F - 1) * sizeof(double)))) return rc;
             c.w.rel = c.w.rel_buf;
@@ -2577,6 +2583,93 @@ int smooth_entry(aar_problem *pb, const aar_smooth_params *sp_in, aar_smooth_par
     (void)smooth_params_read(sp_in, sp);
     if (pb->comm) return set_error(AAR_ERR_UNSUPPORTED, "%s: the motion prior couples frames across shard boundaries; smoothed tracking is single-GPU only", who);
     return AAR_OK;
+}
+
+// what one run of the joint LM leaves on the host; cur: in = the buffer of c.w.z the run starts from, out = the one that holds its result
+struct SmoothLm {
+    int cur = 0, iters = 0, rejected = 0, mustExit = 0;
+    double initial = 0.0, currErr = 0.0, currData = 0.0, currPrior = 0.0, mu = -1.0;
+};
+
+// aar_track_smooth's loop on a prepared SmoothCall, from c.w.z[s.cur]
+int smooth_lm_run(aar_problem *pb, const SmoothCall &c, const aar_lm_params &p, SmoothLm &s) {
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const SmoothWork &w = c.w;
+    const double rows = 8.0 * (double)P.N + 6.0 * (double)(F - 1);
+    int rc = AAR_OK;
+    int cur = s.cur, iters = 0, rejected = 0, mustExit = 0;
+    double res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double currData = 0.0, currPrior = 0.0, mu = -1.0, v = 2.0;
+    if (F > 0) {
+        // init: the first evaluation also yields the first step's system
+        launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream);
+        pb->launches += 2;
+        if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;
+        currData = res[0]; currPrior = res[1];
+    }
+    double currErr = currData + currPrior, prevErr = currErr;
+    const double initial = currErr;
+    for (int it = 0; it < p.max_iters && !mustExit && rows > 0 && F > 0; it++) {
+        if (it > 0) { launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream); pb->launches += 2; }   // H, b at curr_z (its costs are those already held)
+        if (mu < 0) mu = res[4] * p.tau;   // (first iteration: res still holds the initial evaluation's record)
+        double gain = 0.0;
+        int ntries = 0;
+        bool accepted = false;
+        do {
+            pb->launches += launch_smooth_solve(w, F, mu, pb->stream);
+            launch_smooth_eval(P, pb->cur, w, cur, false, pb->stream);   // z[1 - cur] = z[cur] + delta, its costs, |delta|^2, delta . b
+            pb->launches += 2;
+            if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;   // the try's one read-back
+            const double err = res[0] + res[1];
+            const bool bad_pivot = res[5] != 0.0;
+            const double Lq = 0.5 * (mu * res[2] - res[3]);
+            gain = (err - prevErr) / Lq;
+            if (!bad_pivot && gain > 0 && (err - prevErr) < 0) {
+                const double t = 2 * gain - 1;
+                mu = mu * std::max(0.33, 1.0 - t * t * t);
+                v = 2.0;
+                currErr = err; currData = res[0]; currPrior = res[1];
+                cur = 1 - cur;
+                accepted = true;
+            } else {
+                if (bad_pivot) gain = 0.0;   // a failed factorisation is a rejected try: more damping, and the retry rule below applies
+                mu = mu * v;
+                v = v * 5;
+                rejected++;
+            }
+        } while (gain <= 0 && ntries++ < 5 && !accepted);
+        if (currErr < p.min_error) mustExit = 1;
+        if (std::fabs(prevErr - currErr) <= p.min_step_error_diff || std::fabs((prevErr - currErr) / rows) <= p.min_average_step_error_diff || !accepted)
+            mustExit = 2;
+        if (currErr > prevErr) mustExit = 3;
+        iters++;
+        prevErr = currErr;
+    }
+    s.cur = cur; s.iters = iters; s.rejected = rejected; s.mustExit = mustExit;
+    s.initial = initial; s.currErr = currErr; s.currData = currData; s.currPrior = currPrior; s.mu = mu;
+    return AAR_OK;
+}
+
+// H at c.w.z[cur] (mu = 0) with its costs into c.w.res, the solve's elimination, the selected inverse into S, R [F][36] each (F > 0).
+// Launches only; returns their number.
+int smooth_selinv_launch(aar_problem *pb, const SmoothCall &c, int cur, double *S, double *R) {
+    const int F = pb->P.F;
+    launch_smooth_eval(pb->P, pb->cur, c.w, cur, /*with_j=*/true, pb->stream);
+    int launches = 2;
+    launches += launch_smooth_solve(c.w, F, 0.0, pb->stream);
+    launches += launch_smooth_selinv(c.w, F, S, R, pb->stream);
+    return launches;
+}
+
+// the frame poses of the problem's pose vector into x_full
+int smooth_download(aar_problem *pb, double *x_full) {
+    // only the frame poses move; download_z honours the Config flags, so force "frames on, shared off" for this call
+    PoseLayout keep = pb->L;
+    pb->L.oc = false; pb->L.om = false; pb->L.of = true;
+    int rc = download_z(pb, pb->cur, x_full);
+    pb->L = keep;
+    return rc;
 }
 
 }  // namespace
@@ -2667,10 +2760,7 @@ int aar_track_smooth_covariance(aar_problem *pb, const double *x_full, const aar
         HIP_TRY(hipMalloc((void **)&sr.base, 72 * (size_t)F * sizeof(double)));
         HIP_TRY(hipMemsetAsync(sr.base, 0, 72 * (size_t)F * sizeof(double), pb->stream));
         double *S = sr.base, *R = sr.base + 36 * (size_t)F;
-        launch_smooth_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
-        r.launches = 2;
-        r.launches += launch_smooth_solve(c.w, F, 0.0, pb->stream);
-        r.launches += launch_smooth_selinv(c.w, F, S, R, pb->stream);
+        r.launches = smooth_selinv_launch(pb, c, 0, S, R);
         pb->launches += r.launches;
         double res[8];
         int32_t flag = 0;
@@ -2715,72 +2805,210 @@ int aar_track_smooth(aar_problem *pb, double *x_full, const aar_lm_params *prm, 
     SmoothCall c;
     if ((rc = smooth_prepare(pb, sp, c))) return rc;
     const SmoothWork &w = c.w;
-    const double rows = 8.0 * (double)P.N + 6.0 * (double)(F - 1);
-    int cur = 0, iters = 0, rejected = 0, mustExit = 0;
-    double res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    double currData = 0.0, currPrior = 0.0, mu = -1.0, v = 2.0;
-    if (F > 0) {
-        // init: the first evaluation also yields the first step's system
-        launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream);
-        pb->launches += 2;
-        if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;
-        currData = res[0]; currPrior = res[1];
-    }
-    double currErr = currData + currPrior, prevErr = currErr;
-    const double initial = currErr;
-    for (int it = 0; it < p.max_iters && !mustExit && rows > 0 && F > 0; it++) {
-        if (it > 0) { launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream); pb->launches += 2; }   // H, b at curr_z (its costs are those already held)
-        if (mu < 0) mu = res[4] * p.tau;   // (first iteration: res still holds the initial evaluation's record)
-        double gain = 0.0;
-        int ntries = 0;
-        bool accepted = false;
-        do {
-            pb->launches += launch_smooth_solve(w, F, mu, pb->stream);
-            launch_smooth_eval(P, pb->cur, w, cur, false, pb->stream);   // z[1 - cur] = z[cur] + delta, its costs, |delta|^2, delta . b
-            pb->launches += 2;
-            if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;   // the try's one read-back
-            const double err = res[0] + res[1];
-            const bool bad_pivot = res[5] != 0.0;
-            const double Lq = 0.5 * (mu * res[2] - res[3]);
-            gain = (err - prevErr) / Lq;
-            if (!bad_pivot && gain > 0 && (err - prevErr) < 0) {
-                const double t = 2 * gain - 1;
-                mu = mu * std::max(0.33, 1.0 - t * t * t);
-                v = 2.0;
-                currErr = err; currData = res[0]; currPrior = res[1];
-                cur = 1 - cur;
-                accepted = true;
-            } else {
-                if (bad_pivot) gain = 0.0;   // a failed factorisation is a rejected try: more damping, and the retry rule below applies
-                mu = mu * v;
-                v = v * 5;
-                rejected++;
-            }
-        } while (gain <= 0 && ntries++ < 5 && !accepted);
-        if (currErr < p.min_error) mustExit = 1;
-        if (std::fabs(prevErr - currErr) <= p.min_step_error_diff || std::fabs((prevErr - currErr) / rows) <= p.min_average_step_error_diff || !accepted)
-            mustExit = 2;
-        if (currErr > prevErr) mustExit = 3;
-        iters++;
-        prevErr = currErr;
-    }
+    SmoothLm s;
+    if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
+    const int cur = s.cur;
     if (F) HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, w.z[cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
     if (frame_err && F && (rc = copy_d2h(pb, frame_err, w.Ef[cur], (size_t)F * sizeof(double)))) return rc;
     if (pair_err && F > 1 && (rc = copy_d2h(pb, pair_err, w.Pe[cur], (size_t)(F - 1) * sizeof(double)))) return rc;
     if ((rc = check_async("smoothing kernels"))) return rc;
-    // only the frame poses move; download_z honours the Config flags, so force "frames on, shared off" for this call
-    PoseLayout keep = pb->L;
-    pb->L.oc = false; pb->L.om = false; pb->L.of = true;
-    rc = download_z(pb, pb->cur, x_full);
-    pb->L = keep;
-    if (rc) return rc;
+    if ((rc = smooth_download(pb, x_full))) return rc;
     if (report) {
         aar_smooth_report r;
         memset(&r, 0, sizeof r);
         r.struct_size = report->struct_size;
-        r.iterations = iters; r.stop_code = mustExit; r.rejected_tries = rejected;
-        r.initial_cost = initial; r.final_cost = currErr; r.final_data_cost = currData; r.final_prior_cost = currPrior;
-        r.final_mu = mu;
+        r.iterations = s.iters; r.stop_code = s.mustExit; r.rejected_tries = s.rejected;
+        r.initial_cost = s.initial; r.final_cost = s.currErr; r.final_data_cost = s.currData; r.final_prior_cost = s.currPrior;
+        r.final_mu = s.mu;
+        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fitting the smoother's noise levels (smooth_fit_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the caller's struct read up to its struct_size, the rest at the defaults; false: too short to hold struct_size itself
+bool smooth_fit_params_read(const aar_smooth_fit_params *in, aar_smooth_fit_params *out) {
+    aar_smooth_fit_default_params(out);
+    if (in->struct_size < sizeof(uint32_t)) return false;
+    memcpy(out, in, std::min<size_t>(in->struct_size, sizeof *out));
+    out->struct_size = (uint32_t)sizeof *out;
+    return true;
+}
+
+// S, R of the downward pass, the pairs' terms and the record the host reads: one allocation
+struct SmoothFitBuf {
+    SmoothCall mem;
+    double *S = nullptr, *R = nullptr, *terms = nullptr, *rec = nullptr;
+};
+
+int smooth_fit_alloc(aar_problem *pb, SmoothFitBuf &b) {
+    const size_t F = (size_t)pb->P.F, n = 72 * F + 4 * (F - 1) + 8;
+    HIP_TRY(hipMalloc((void **)&b.mem.base, n * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(b.mem.base, 0, n * sizeof(double), pb->stream));
+    b.S = b.mem.base; b.R = b.S + 36 * F; b.terms = b.R + 36 * F; b.rec = b.terms + 4 * (F - 1);
+    return AAR_OK;
+}
+
+// the E-step at c.w.z[cur] with the lambda on the device (built with sigma_rot): launches, then the one read-back of rec [8] =
+// A_r, U_r, A_t, U_t, data cost, prior cost, pivot flag, 0
+int smooth_fit_estep(aar_problem *pb, const SmoothCall &c, int cur, double sigma_rot, const SmoothFitBuf &b, double rec[8], const char *who) {
+    const int F = pb->P.F;
+    int launches = smooth_selinv_launch(pb, c, cur, b.S, b.R);
+    launches += launch_smooth_fit_terms(c.w, cur, F, sigma_rot, b.S, b.R, b.terms, b.rec, pb->stream);
+    pb->launches += launches;
+    int rc = copy_d2h(pb, rec, b.rec, 8 * sizeof(double));
+    if (rc) return rc;
+    if (rec[6] != 0.0)
+        return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the block-tridiagonal elimination (the frames' detections and the prior do "
+                                          "not determine every pose)", who);
+    return AAR_OK;
+}
+
+// what both entries refuse, after smooth_entry
+int smooth_fit_entry(aar_problem *pb, const char *who) {
+    if (pb->with_huber)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: the problem was created with_huber; the Huber weights break the Gaussian data model the fit "
+                                              "rests on", who);
+    if (pb->L.F < 2) return set_error(AAR_ERR_INVALID, "%s: num_frames = %d, the fit needs at least one pair of frames", who, (int)pb->L.F);
+    if (pb->P.N < 1) return set_error(AAR_ERR_INVALID, "%s: the problem has no detections", who);
+    return AAR_OK;
+}
+
+}  // namespace
+
+void aar_smooth_fit_default_params(aar_smooth_fit_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof *p);
+    p->struct_size = (uint32_t)sizeof *p;
+    p->max_iters = 50;
+    p->rel_tol = 1e-3;
+    p->estimate_px = p->estimate_rot = p->estimate_trans = 1;
+}
+
+int aar_smooth_fit_params_validate(const aar_smooth_fit_params *in) {
+    if (!in) return set_error(AAR_ERR_INVALID, "aar_smooth_fit_params_validate: null argument");
+    aar_smooth_fit_params p;
+    if (!smooth_fit_params_read(in, &p))
+        return set_error(AAR_ERR_INVALID, "aar_smooth_fit_params: struct_size %u does not reach past struct_size itself", (unsigned)in->struct_size);
+    if (p.max_iters < 1) return set_error(AAR_ERR_INVALID, "aar_smooth_fit_params: max_iters = %d must be at least 1", (int)p.max_iters);
+    if (!(p.rel_tol >= 0.0) || !std::isfinite(p.rel_tol))
+        return set_error(AAR_ERR_INVALID, "aar_smooth_fit_params: rel_tol = %g must be finite and not negative", p.rel_tol);
+    const int32_t est[3] = {p.estimate_px, p.estimate_rot, p.estimate_trans};
+    const char *names[3] = {"estimate_px", "estimate_rot", "estimate_trans"};
+    for (int i = 0; i < 3; i++)
+        if (est[i] != 0 && est[i] != 1) return set_error(AAR_ERR_INVALID, "aar_smooth_fit_params: %s = %d must be 0 or 1", names[i], (int)est[i]);
+    if (!p.estimate_px && !p.estimate_rot && !p.estimate_trans)
+        return set_error(AAR_ERR_INVALID, "aar_smooth_fit_params: estimate_px, estimate_rot and estimate_trans are all 0, nothing to fit");
+    return AAR_OK;
+}
+
+int aar_track_smooth_fit_terms(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *pair_terms, double sums[4]) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit_terms: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit_terms");
+    if (rc) return rc;
+    if ((rc = smooth_fit_entry(pb, "aar_track_smooth_fit_terms"))) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCall c;
+    if ((rc = smooth_prepare(pb, sp, c))) return rc;
+    SmoothFitBuf b;
+    if ((rc = smooth_fit_alloc(pb, b))) return rc;
+    double rec[8];
+    if ((rc = smooth_fit_estep(pb, c, 0, sp.sigma_rot, b, rec, "aar_track_smooth_fit_terms"))) return rc;
+    if (pair_terms && (rc = copy_d2h(pb, pair_terms, b.terms, 4 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    if ((rc = check_async("smoothing fit kernels"))) return rc;
+    if (sums) for (int i = 0; i < 4; i++) sums[i] = rec[i];
+    return AAR_OK;
+}
+
+int aar_track_smooth_fit(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, const aar_smooth_fit_params *fp_in,
+                         double *path, aar_smooth_fit_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit");
+    if (rc) return rc;
+    aar_smooth_fit_params fp;
+    if (fp_in) {
+        if ((rc = aar_smooth_fit_params_validate(fp_in))) return rc;
+        (void)smooth_fit_params_read(fp_in, &fp);
+    } else {
+        aar_smooth_fit_default_params(&fp);
+    }
+    if ((rc = smooth_fit_entry(pb, "aar_track_smooth_fit"))) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    aar_lm_params p;
+    if (prm) p = *prm; else aar_lm_default_params(&p);
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    const int F = P.F;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t launches0 = pb->launches;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCall c;
+    if ((rc = smooth_prepare(pb, sp, c))) return rc;   // lambda at the start values
+    SmoothFitBuf b;
+    if ((rc = smooth_fit_alloc(pb, b))) return rc;
+    // the variances: q = sigma_px^2, s_r, s_t physical; the smoother runs at s / q
+    double q = 1.0, s_r = sp.sigma_rot * sp.sigma_rot, s_t = sp.sigma_trans * sp.sigma_trans;
+    aar_smooth_fit_report r;
+    memset(&r, 0, sizeof r);
+    if (path) { path[0] = 1.0; path[1] = sp.sigma_rot; path[2] = sp.sigma_trans; }
+    aar_smooth_params eff = sp;   // frame_time and rel_motion kept, the sigmas replaced
+    SmoothLm s;
+    double rec[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u_d = 0.0;
+    r.stop_code = 2;
+    for (int it = 0; it < fp.max_iters; it++) {
+        if (it > 0 && (rc = smooth_upload_lambda(pb, eff, c))) return rc;
+        if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
+        r.lm_steps += s.iters;
+        if ((rc = smooth_fit_estep(pb, c, s.cur, eff.sigma_rot, b, rec, "aar_track_smooth_fit"))) return rc;
+        const double er2 = eff.sigma_rot * eff.sigma_rot, et2 = eff.sigma_trans * eff.sigma_trans;
+        u_d = 6.0 * (double)F - rec[1] / er2 - rec[3] / et2;
+        const double n_r = fp.estimate_rot ? (rec[0] + q * rec[1]) / (3.0 * (double)(F - 1)) : s_r;
+        const double n_t = fp.estimate_trans ? (rec[2] + q * rec[3]) / (3.0 * (double)(F - 1)) : s_t;
+        const double n_q = fp.estimate_px ? (rec[4] + q * u_d) / (8.0 * (double)P.N) : q;
+        const double was[3] = {q, s_r, s_t}, now[3] = {n_q, n_r, n_t};
+        const char *names[3] = {"sigma_px", "sigma_rot", "sigma_trans"};
+        double change = 0.0;
+        for (int i = 0; i < 3; i++) {
+            if (!(now[i] > 0.0) || !std::isfinite(now[i]))
+                return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_fit: iteration %d: the M-step gives the variance %g for %s", it + 1, now[i], names[i]);
+            change = std::max(change, std::fabs(std::sqrt(now[i]) - std::sqrt(was[i])) / std::sqrt(was[i]));
+        }
+        q = n_q; s_r = n_r; s_t = n_t;
+        eff.sigma_rot = std::sqrt(s_r / q);
+        eff.sigma_trans = std::sqrt(s_t / q);
+        r.iterations = it + 1;
+        r.last_rel_change = change;
+        if (path) { double *row = path + 3 * (size_t)(it + 1); row[0] = std::sqrt(q); row[1] = std::sqrt(s_r); row[2] = std::sqrt(s_t); }
+        if (change < fp.rel_tol) { r.stop_code = 1; break; }
+    }
+    // the track at the fitted values
+    if ((rc = smooth_upload_lambda(pb, eff, c))) return rc;
+    if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
+    r.lm_steps += s.iters;
+    HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.w.z[s.cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    if ((rc = check_async("smoothing fit kernels"))) return rc;
+    if ((rc = smooth_download(pb, x_full))) return rc;
+    if (report) {
+        r.struct_size = report->struct_size;
+        r.sigma_px = std::sqrt(q); r.sigma_rot = std::sqrt(s_r); r.sigma_trans = std::sqrt(s_t);
+        r.sigma_rot_eff = eff.sigma_rot; r.sigma_trans_eff = eff.sigma_trans;
+        r.launches = (int32_t)(pb->launches - launches0);
+        r.a_rot = rec[0]; r.u_rot = rec[1]; r.a_trans = rec[2]; r.u_trans = rec[3]; r.u_data = u_d; r.data_cost = rec[4];
         r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
     }

@@ -317,6 +317,10 @@ void launch_smooth_eval(const DeviceProblem &P, int which, const SmoothWork &w, 
 int launch_smooth_solve(const SmoothWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
 // the diagonal and lag-one blocks of H^-1 from what launch_smooth_solve(w, F, 0.0, st) left (smooth_cov_kernels.hip)
 int launch_smooth_selinv(const SmoothWork &w, int F, double *S, double *R, hipStream_t st);                               // returns its launches
+// the pairs' expected sufficient statistics from S, R and z[cur] (smooth_fit_kernels.hip), F >= 2: terms [F-1][4] =
+// a_r, u_r, a_t, u_t and rec [8] = their sums, w.res[0], w.res[1], w.flag[0], 0; sigma_rot: the one w.lam was built with
+int launch_smooth_fit_terms(const SmoothWork &w, int cur, int F, double sigma_rot, const double *S, const double *R, double *terms, double *rec,
+                            hipStream_t st);                                                                              // returns its launches
 
 // live tracker (live_kernels.hip): one frame per push, the whole LM of the window in ONE launch of one workgroup
 constexpr int LIVE_MAX_W = 16;            // window frames (AAR_TRACKER_MAX_LAG + 1)

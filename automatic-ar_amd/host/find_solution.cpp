@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-smooth-covariance]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-smooth-covariance] [-fit-sigmas]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -256,6 +256,9 @@ int main(int argc, char *argv[]) {
     // ... -smooth-covariance (only with -smooth) also writes every frame's 6x6 pose covariance at the smoothed poses to
     // final.smooth_covariance.yaml (MultiCamMapper::track_smooth_covariance)
     bool smooth_covariance = false;
+    // ... -fit-sigmas (only with -smooth) first fits the corner noise and the two sigmas to the sequence, from the given values as the start
+    // (MultiCamMapper::fit_smooth_sigmas), and smooths with the fitted effective values
+    bool fit_sigmas = false;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
     // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
@@ -304,6 +307,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-relative-sigma-m") arg_flag = RelM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
         else if (a == "-smooth-covariance") { smooth_covariance = true; arg_flag = NONE; }
+        else if (a == "-fit-sigmas") { fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
@@ -402,6 +406,7 @@ int main(int argc, char *argv[]) {
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (smooth_covariance && !smooth) return print_usage(argv[0]);
+    if (fit_sigmas && (!smooth || live)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
@@ -598,6 +603,18 @@ int main(int argc, char *argv[]) {
     if (smooth) {
         try {
             mcm.track();
+            if (fit_sigmas) {
+                aar::MultiCamMapper::SmoothFit sf;
+                mcm.fit_smooth_sigmas(smooth_sigma[0], smooth_sigma[1], sf);
+                const aar_smooth_fit_report &fr = sf.report;
+                const streamsize keep = cout.precision(10);
+                cout << "smooth-fit: sigma_px " << fr.sigma_px << " sigma_rot " << fr.sigma_rot << " sigma_trans " << fr.sigma_trans << " sigma_rot_eff "
+                     << fr.sigma_rot_eff << " sigma_trans_eff " << fr.sigma_trans_eff << " after " << fr.iterations << " EM iterations (exit " << fr.stop_code
+                     << ", " << fr.lm_steps << " LM iterations) in " << fr.seconds << " s" << endl;
+                cout.precision(keep);
+                smooth_sigma[0] = fr.sigma_rot_eff;
+                smooth_sigma[1] = fr.sigma_trans_eff;
+            }
             mcm.track_smooth(smooth_sigma[0], smooth_sigma[1]);
             const aar_smooth_report &sr = mcm.smooth_report;
             cout << "smooth: " << sr.iterations << " LM iterations (" << sr.rejected_tries << " rejected tries, exit " << sr.stop_code << "), cost " << sr.initial_cost

@@ -614,6 +614,48 @@ void MultiCamMapper::track_smooth_covariance(double sigma_rot, double sigma_tran
     if (aar_track_smooth_covariance(pb, x.data(), &sp, out.frame_cov.data(), out.lag_cov.data(), &out.report)) throw std::runtime_error(aar_last_error());
 }
 
+// The pixel noise and the motion sigmas fitted to the sequence itself (aar_track_smooth_fit), under track_smooth()'s model
+// (the frame ids as the time axis).  The frame poses end as the smoothed track at the fitted values.
+void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, SmoothFit &out, const aar_smooth_fit_params *fit) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::fit_smooth_sigmas: no data set");
+    mats2eVec();
+    hubberDelta = 10;  // as track_smooth() (a mapper set_with_huber(true) is refused by the library: the fit needs the Gaussian data model)
+    std::vector<double> x;
+    aar_problem *pb = detail::bind_problem(this, x);
+    if (aar_problem_merge_z(pb, io_vec.data(), x.data())) throw std::runtime_error(aar_last_error());
+    aar_lm_params p;
+    aar_lm_default_params(&p);
+    p.max_iters = solver_params.maxIters;
+    p.min_error = solver_params.minError;
+    p.min_step_error_diff = solver_params.min_step_error_diff;
+    p.min_average_step_error_diff = solver_params.min_average_step_error_diff;
+    p.tau = solver_params.tau;
+    const int F = data_->num_frames;
+    std::vector<double> time(F);
+    for (int f = 0; f < F; f++) time[f] = (double)data_->frame_ids[f];
+    aar_smooth_params sp;
+    memset(&sp, 0, sizeof sp);
+    sp.struct_size = sizeof sp;
+    sp.sigma_rot = sigma_rot;
+    sp.sigma_trans = sigma_trans;
+    sp.frame_time = F ? time.data() : nullptr;
+    aar_smooth_fit_params fp;
+    aar_smooth_fit_default_params(&fp);
+    if (fit) {
+        if (aar_smooth_fit_params_validate(fit)) throw std::runtime_error(aar_last_error());
+        memcpy(&fp, fit, std::min<size_t>(fit->struct_size, sizeof fp));
+        fp.struct_size = sizeof fp;
+    }
+    out.path.assign(3 * ((size_t)fp.max_iters + 1), 0.0);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    if (aar_track_smooth_fit(pb, x.data(), &p, &sp, &fp, out.path.data(), &out.report)) throw std::runtime_error(aar_last_error());
+    out.path.resize(3 * ((size_t)out.report.iterations + 1));
+    if (aar_problem_extract_z(pb, x.data(), io_vec.data())) throw std::runtime_error(aar_last_error());   // (only the frame poses have moved)
+    memcpy(data_->x_full, x.data(), sizeof(double) * aar_dataset_full_len(data_));   // ... also when the Config keeps them out of z
+    eVec2Mats(io_vec);
+}
+
 // The live loop over the data set's frames (aar_tracker_*): what apps/track.cpp does per incoming frame, with the
 // mapper's own frames as the stream.
 namespace {

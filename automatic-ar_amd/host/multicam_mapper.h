@@ -403,6 +403,15 @@ class MultiCamMapper {
         aar_smooth_covariance_report report = {};
     };
     void track_smooth_covariance(double sigma_rot, double sigma_trans, SmoothCovariance &out);   // throws std::runtime_error on failure
+    // EXTENSION, no counterpart in the reference: the corner noise and track_smooth()'s two sigmas fitted to the sequence itself by EM
+    // (aar_track_smooth_fit), from the effective start values sigma_rot, sigma_trans.  The frame poses end as the smoothed
+    // track at the fitted values; report.sigma_rot_eff / sigma_trans_eff are what track_smooth() and the live tracker take.  A mapper
+    // set_with_huber(true) is refused.  fit: NULL = aar_smooth_fit_default_params.
+    struct SmoothFit {
+        aar_smooth_fit_report report = {};
+        std::vector<double> path;        // [report.iterations + 1][3] (sigma_px, sigma_rot, sigma_trans), the start values first
+    };
+    void fit_smooth_sigmas(double sigma_rot, double sigma_trans, SmoothFit &out, const aar_smooth_fit_params *fit = nullptr);   // throws std::runtime_error on failure
     // no counterpart in the reference as a method: apps/track.cpp's loop (:102-136) over the data set's frames, one frame per push through a
     // LiveTracker (below): each frame starts from its own pose in the data set, the frame ids are the time axis; every frame ends at its lagged
     // pose, the last window at aar_tracker_window's.  smooth = false needs lag = 0.  The pushes' results land in live_results.

@@ -615,6 +615,54 @@ typedef struct aar_smooth_covariance_report {
 } aar_smooth_covariance_report;
 int aar_track_smooth_covariance(aar_problem *, const double *x_full, const aar_smooth_params *, double *frame_cov, double *lag_cov,
                                 aar_smooth_covariance_report *report);
+/* Fitting the smoother's noise levels from the recorded sequence itself: expectation-maximisation over
+ *   sigma_px (the corner noise the data term fixes at 1 px), sigma_rot, sigma_trans (per sqrt(unit of frame_time)).
+ * Only the ratios sigma / sigma_px enter aar_track_smooth's estimate: it is run at the EFFECTIVE sigmas sigma_rot / sigma_px and
+ * sigma_trans / sigma_px.  One iteration: aar_track_smooth from the previous track at the current effective sigmas; H at mu = 0, its elimination
+ * and the blocks of aar_track_smooth_covariance, all kept on the device; per pair f (g = f + 1, D_f as above, phi, e_t, M_a, M_b of the
+ * between factor at the track)
+ *   a_r = |phi|^2 / D_f,  u_r = tr(M_a S_ff^ww M_a^T + M_b S_gg^ww M_b^T + M_a S_fg^ww M_b^T + M_b S_fg^ww^T M_a^T) / D_f
+ *   a_t = |e_t|^2 / D_f,  u_t = tr(S_ff^tt + S_gg^tt - S_fg^tt - S_fg^tt^T) / D_f         (^ww, ^tt: rotation / translation 3x3 sub-blocks)
+ * summed to A_r, U_r, A_t, U_t in a fixed order, U_d = 6 num_frames - U_r / sigma_rot_eff^2 - U_t / sigma_trans_eff^2 (= sum_f tr(V_f S_ff)),
+ * and with q = sigma_px^2
+ *   sigma_rot^2 <- (A_r + q U_r) / (3 (num_frames - 1)),  sigma_trans^2 <- (A_t + q U_t) / (3 (num_frames - 1)),
+ *   q <- (data_cost + q U_d) / (8 num_obs),               all three from the old q.
+ * It stops when the largest relative change of an estimated sigma is below rel_tol (stop_code 1) or after max_iters iterations (2), and ends
+ * with one aar_track_smooth at the fitted values: x_full (in/out, only the frame poses move) is the track at those.
+ * aar_smooth_params: sigma_rot, sigma_trans are the effective start values (sigma_px starts at 1); frame_time and rel_motion are kept.
+ * estimate_* = 0 holds that sigma at its start value; estimate_px = 0 fits the effective sigmas directly (sigma_px = 1 exactly).
+ * path: NULL or [max_iters + 1][3] = (sigma_px, sigma_rot, sigma_trans) at the start and after every iteration (rows beyond
+ * report->iterations are not written).  NULL aar_lm_params / aar_smooth_fit_params: the defaults.  Bit-reproducible from call to call.
+ * AAR_ERR_INVALID: num_frames < 2, no detections, all estimate_* zero, rel_tol negative or not finite, max_iters < 1.  AAR_ERR_UNSUPPORTED: a
+ * problem created with_huber (the weights break the Gaussian data model), a communicator.  AAR_ERR_NUMERIC: a non-positive pivot, an M-step
+ * that gives a variance that is not positive and finite.  On an error x_full is not modified. */
+typedef struct aar_smooth_fit_params {
+    uint32_t struct_size;
+    int32_t max_iters;           /* 50 */
+    double rel_tol;              /* 1e-3 */
+    int32_t estimate_px, estimate_rot, estimate_trans;   /* 1, 1, 1 */
+} aar_smooth_fit_params;
+typedef struct aar_smooth_fit_report {
+    uint32_t struct_size;
+    int32_t iterations;          /* EM iterations made */
+    int32_t stop_code;           /* 1 = converged, 2 = max_iters */
+    double sigma_px, sigma_rot, sigma_trans;       /* physical */
+    double sigma_rot_eff, sigma_trans_eff;         /* = physical / sigma_px: the values for aar_smooth_params and aar_tracker_params */
+    double last_rel_change;
+    int32_t lm_steps;            /* LM iterations of all smoothing runs, the final one included */
+    int32_t launches;
+    double seconds;
+    double a_rot, u_rot, a_trans, u_trans, u_data, data_cost;   /* the last iteration's A_r, U_r, A_t, U_t, U_d and data cost */
+} aar_smooth_fit_report;
+void aar_smooth_fit_default_params(aar_smooth_fit_params *);   /* struct_size set */
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming the field.  A struct_size that ends before a field leaves
+ * it at its default. */
+int aar_smooth_fit_params_validate(const aar_smooth_fit_params *);
+int aar_track_smooth_fit(aar_problem *, double *x_full, const aar_lm_params *, const aar_smooth_params *, const aar_smooth_fit_params *,
+                         double *path, aar_smooth_fit_report *report);
+/* One E-step at x_full and the given (effective) sigmas, without smoothing, for checking: pair_terms [num_frames-1][4] = a_r, u_r, a_t, u_t
+ * (may be NULL), sums = A_r, U_r, A_t, U_t.  x_full is not modified.  Errors as aar_track_smooth_fit. */
+int aar_track_smooth_fit_terms(aar_problem *, const double *x_full, const aar_smooth_params *, double *pair_terms, double sums[4]);
 
 /* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
  * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are
