@@ -41,6 +41,7 @@ SYMBOLS = [
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_covariance",
     "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms",
+    "aar_smooth_query_validate", "aar_track_smooth_query",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
@@ -245,6 +246,12 @@ class CSmoothCovarianceReport(C.Structure):
                 ("prior_cost", C.c_double), ("sigma2", C.c_double), ("launches", C.c_int32), ("seconds", C.c_double)]
 
 
+class CSmoothQueryReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("data_cost", C.c_double),
+                ("prior_cost", C.c_double), ("sigma2", C.c_double), ("num_queries", C.c_int32), ("num_inside", C.c_int32),
+                ("num_on_frame", C.c_int32), ("num_outside", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double)]
+
+
 class SmoothParams:
     """aar_smooth_params built from Python values (the arrays are kept alive with the struct)"""
 
@@ -269,6 +276,14 @@ def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, 
     sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size)
     sp.check_lengths(num_frames)
     _check(lib().aar_smooth_params_validate(int(num_frames), C.byref(sp.c)))
+
+
+def smooth_query_validate(num_frames, sigma_rot, sigma_trans, query_time, frame_time=None, rel_motion=None, struct_size=None):
+    """aar_smooth_query_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
+    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size)
+    sp.check_lengths(num_frames)
+    qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
+    _check(lib().aar_smooth_query_validate(int(num_frames), C.byref(sp.c), len(qt), _dptr(qt) if len(qt) else None))
 
 
 class CSmoothFitParams(C.Structure):
@@ -506,6 +521,9 @@ def lib():
     L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothReport)]
     L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_double, dp, dp, dp, dp, dp]
     L.aar_track_smooth_covariance.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothCovarianceReport)]
+    L.aar_smooth_query_validate.argtypes = [C.c_int32, C.POINTER(CSmoothParams), C.c_int64, dp]
+    L.aar_track_smooth_query.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_int64, dp, dp, dp, C.POINTER(C.c_int32),
+                                         C.POINTER(CSmoothQueryReport)]
     L.aar_smooth_fit_default_params.argtypes = [C.POINTER(CSmoothFitParams)]
     L.aar_smooth_fit_default_params.restype = None
     L.aar_smooth_fit_params_validate.argtypes = [C.POINTER(CSmoothFitParams)]
@@ -1716,6 +1734,23 @@ class Problem:
         terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(4)
         _check(lib().aar_track_smooth_fit_terms(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
         return terms[:max(F - 1, 0)], sums
+
+    def track_smooth_query(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True):
+        """aar_track_smooth_query: the smoothed track at the times query_time [Q] (any order, duplicates allowed).  Returns (pose [Q, 6],
+        cov [Q, 6, 6] UNSCALED -- multiply by report["sigma2"] -- or None without covariance, segment [Q], report dict)."""
+        x = self._x(x_full)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time)
+        sp.check_lengths(self.ds.num_frames)
+        qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
+        Q = len(qt)
+        pose, seg = np.zeros((max(Q, 1), 6)), np.zeros(max(Q, 1), dtype=np.int32)
+        cov = np.zeros((max(Q, 1), 6, 6)) if covariance else None
+        rep = CSmoothQueryReport()
+        rep.struct_size = C.sizeof(CSmoothQueryReport)
+        _check(lib().aar_track_smooth_query(self.handle, _dptr(x), C.byref(sp.c), Q, _dptr(qt) if Q else None, _dptr(pose),
+                                            _dptr(cov) if covariance else None, seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothQueryReport._fields_ if k != "struct_size"}
+        return pose[:Q], cov[:Q] if covariance else None, seg[:Q], report
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

@@ -3015,6 +3015,104 @@ int aar_track_smooth_fit(aar_problem *pb, double *x_full, const aar_lm_params *p
     return AAR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The smoothed track at any time (smooth_query_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+int aar_smooth_query_validate(int32_t num_frames, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time) {
+    if (!sp_in) return set_error(AAR_ERR_INVALID, "aar_smooth_query_validate: null aar_smooth_params");
+    int rc = aar_smooth_params_validate(num_frames, sp_in);
+    if (rc) return rc;
+    if (n_query < 0 || n_query > INT32_MAX)
+        return set_error(AAR_ERR_INVALID, "aar_smooth_query: n_query = %lld must lie in 0 .. %d", (long long)n_query, (int)INT32_MAX);
+    if (n_query > 0 && !query_time) return set_error(AAR_ERR_INVALID, "aar_smooth_query: query_time is NULL with n_query = %lld", (long long)n_query);
+    if (n_query > 0 && num_frames < 1)
+        return set_error(AAR_ERR_INVALID, "aar_smooth_query: num_frames = %d, a query needs at least one frame", (int)num_frames);
+    for (int64_t i = 0; i < n_query; i++)
+        if (!std::isfinite(query_time[i])) return set_error(AAR_ERR_INVALID, "aar_smooth_query: query_time[%lld] is not finite", (long long)i);
+    return AAR_OK;
+}
+
+int aar_track_smooth_query(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
+                           double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query");
+    if (rc) return rc;
+    if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
+    if (sp.rel_motion)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_query: rel_motion is set; under an expected motion the pose of an inserted frame "
+                                              "has no closed form (the split of dR does not commute)");
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const size_t Q = (size_t)n_query;
+    const auto t0 = std::chrono::steady_clock::now();
+    aar_smooth_query_report r;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
+    r.num_vars = 6 * (int64_t)F;
+    r.num_queries = (int32_t)Q;
+    if (Q > 0) {
+        // the frame times as the device searches them, and the three counts from the same search on the host
+        std::vector<double> ft((size_t)F);
+        for (int f = 0; f < F; f++) ft[f] = sp.frame_time ? sp.frame_time[f] : (double)f;
+        for (size_t i = 0; i < Q; i++) {
+            const int s = (int)(std::upper_bound(ft.begin(), ft.end(), query_time[i]) - ft.begin()) - 1;
+            if (s >= 0 && ft[s] == query_time[i]) r.num_on_frame++;
+            else if (s < 0 || s == F - 1) r.num_outside++;
+            else r.num_inside++;
+        }
+        pb->lm_ready = false;
+        pb->blocks_valid = false;
+        if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+        // one allocation: ft [F] | query times [Q] | pose [Q][6] | cov [Q][36] | S, R [F][36] each | segment [Q] and the queries' pivot flag
+        const size_t n_cov = cov ? 36 * Q + 72 * (size_t)F : 0, n_dbl = (size_t)F + 7 * Q + n_cov, n_int = Q + 2;
+        SmoothCall out, c;
+        HIP_TRY(hipMalloc((void **)&out.base, n_dbl * sizeof(double) + n_int * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(out.base, 0, n_dbl * sizeof(double) + n_int * sizeof(int32_t), pb->stream));
+        double *d_ft = out.base, *d_qt = d_ft + F, *d_pose = d_qt + Q, *d_cov = cov ? d_pose + 6 * Q : nullptr;
+        double *S = cov ? d_cov + 36 * Q : nullptr, *R = cov ? S + 36 * (size_t)F : nullptr;
+        int32_t *d_seg = reinterpret_cast<int32_t *>(out.base + n_dbl), *d_flag = d_seg + Q;
+        if ((rc = copy_h2d(pb, d_ft, ft.data(), (size_t)F * sizeof(double)))) return rc;
+        if ((rc = copy_h2d(pb, d_qt, query_time, Q * sizeof(double)))) return rc;
+        const double *z = P.z[pb->cur] + 6 * (size_t)P.A;
+        if (cov) {
+            launch_unpack(P, pb->cur, pb->stream);
+            if ((rc = smooth_prepare(pb, sp, c))) return rc;
+            r.launches = smooth_selinv_launch(pb, c, 0, S, R);
+            z = c.w.z[0];
+        }
+        r.launches += launch_smooth_query(c.w, F, z, d_ft, sp.sigma_rot, sp.sigma_trans, S, R, (int64_t)Q, d_qt, d_pose, d_cov, d_seg, d_flag, pb->stream);
+        pb->launches += r.launches;
+        if (cov) {
+            double res[8];
+            int32_t flag = 0, qflag = 0;
+            if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+            if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+            if ((rc = copy_d2h(pb, &qflag, d_flag, sizeof qflag))) return rc;
+            if ((rc = check_async("smoothing query kernels"))) return rc;
+            if (flag)
+                return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_query: non-positive pivot in the block-tridiagonal elimination (the frames' "
+                                                  "detections and the prior do not determine every pose)");
+            if (qflag) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_query: non-positive pivot in a query's 6x6 inverses");
+            r.data_cost = res[0]; r.prior_cost = res[1];
+            if ((rc = copy_d2h(pb, cov, d_cov, 36 * Q * sizeof(double)))) return rc;
+        }
+        if (pose && (rc = copy_d2h(pb, pose, d_pose, 6 * Q * sizeof(double)))) return rc;
+        if (segment && (rc = copy_d2h(pb, segment, d_seg, Q * sizeof(int32_t)))) return rc;
+        if ((rc = check_async("smoothing query kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+    }
+    const int64_t dof = r.num_residuals - r.num_vars;
+    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
 int aar_set_kernel_profiling(aar_problem *pb, int on) {
     if (!pb) return set_error(AAR_ERR_INVALID, "aar_set_kernel_profiling: null argument");
     HIP_TRY(hipSetDevice(pb->device));

@@ -317,6 +317,11 @@ void launch_smooth_eval(const DeviceProblem &P, int which, const SmoothWork &w, 
 int launch_smooth_solve(const SmoothWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
 // the diagonal and lag-one blocks of H^-1 from what launch_smooth_solve(w, F, 0.0, st) left (smooth_cov_kernels.hip)
 int launch_smooth_selinv(const SmoothWork &w, int F, double *S, double *R, hipStream_t st);                               // returns its launches
+// pose and covariance block at Q > 0 query times from z [F][6], the frame times ft [F] and S, R of launch_smooth_selinv (smooth_query_kernels.hip,
+// DESIGN.md section 30); cov == NULL: poses and segments only, w, S, R and flag unused.  All pointers on the device; flag zeroed by the caller
+int launch_smooth_query(const SmoothWork &w, int F, const double *z, const double *ft, double sigma_rot, double sigma_trans, const double *S,
+                        const double *R, int64_t Q, const double *qt, double *pose, double *cov, int32_t *seg, int32_t *flag,
+                        hipStream_t st);                                                                                  // returns its launches
 // the pairs' expected sufficient statistics from S, R and z[cur] (smooth_fit_kernels.hip), F >= 2: terms [F-1][4] =
 // a_r, u_r, a_t, u_t and rec [8] = their sums, w.res[0], w.res[1], w.flag[0], 0; sigma_rot: the one w.lam was built with
 int launch_smooth_fit_terms(const SmoothWork &w, int cur, int F, double sigma_rot, const double *S, const double *R, double *terms, double *rec,

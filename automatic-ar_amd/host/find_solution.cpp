@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-smooth-covariance] [-fit-sigmas]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -259,6 +259,10 @@ int main(int argc, char *argv[]) {
     // ... -fit-sigmas (only with -smooth) first fits the corner noise and the two sigmas to the sequence, from the given values as the start
     // (MultiCamMapper::fit_smooth_sigmas), and smooths with the fitted effective values
     bool fit_sigmas = false;
+    // ... -resample <n> (only with -smooth, n >= 2) also writes the smoothed track at n points per gap of frame ids, the frames included, with
+    // pose and 6x6 covariance to final.resampled.yaml (MultiCamMapper::track_smooth_query)
+    bool resample = false;
+    int resample_n = 0;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
     // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
@@ -282,7 +286,7 @@ int main(int argc, char *argv[]) {
     int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
     double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Live, Anchor, Gate, Motion } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Resample, Live, Anchor, Gate, Motion } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -308,6 +312,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
         else if (a == "-smooth-covariance") { smooth_covariance = true; arg_flag = NONE; }
         else if (a == "-fit-sigmas") { fit_sigmas = true; arg_flag = NONE; }
+        else if (a == "-resample") { resample = true; resample_n = 0; arg_flag = Resample; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
@@ -356,6 +361,13 @@ int main(int argc, char *argv[]) {
                 live_sigma[live_args++ - 1] = v;
                 if (live_args == 3) arg_flag = NONE;
             }
+        }
+        else if (arg_flag == Resample) {
+            char *end = nullptr;
+            const long v = strtol(a.c_str(), &end, 10);
+            if (*end != '\0' || a.empty() || v < 2 || v > 1000000) return print_usage(argv[0]);
+            resample_n = (int)v;
+            arg_flag = NONE;
         }
         else if (arg_flag == Smooth) {
             char *end = nullptr;
@@ -407,6 +419,7 @@ int main(int argc, char *argv[]) {
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (smooth_covariance && !smooth) return print_usage(argv[0]);
     if (fit_sigmas && (!smooth || live)) return print_usage(argv[0]);
+    if (resample && (!smooth || live || resample_n < 2)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
@@ -647,6 +660,38 @@ int main(int argc, char *argv[]) {
                 cerr << "smooth covariance failed: " << e.what() << endl;
                 return 6;
             }
+        }
+    }
+    if (smooth && resample) {
+        const string rs_path = folder_path + "/final.resampled.yaml";
+        try {
+            // every gap of frame ids cut into resample_n equal parts; entry k * resample_n is frame k itself
+            const aar_dataset *ds = mcm.dataset();
+            vector<double> times;
+            for (int f = 0; f < ds->num_frames; f++) {
+                const double ta = (double)ds->frame_ids[f];
+                times.push_back(ta);
+                if (f + 1 < ds->num_frames)
+                    for (int k = 1; k < resample_n; k++) times.push_back(ta + ((double)ds->frame_ids[f + 1] - ta) * ((double)k / (double)resample_n));
+            }
+            aar::MultiCamMapper::SmoothQuery q;
+            mcm.track_smooth_query(smooth_sigma[0], smooth_sigma[1], times, q);
+            FILE *fp = fopen(rs_path.c_str(), "w");
+            if (!fp) throw runtime_error("cannot write " + rs_path);
+            fprintf(fp, "%%YAML:1.0\n---\nsigma2: %.17g\nresample: %d\nresampled_poses:\n", q.report.sigma2, resample_n);
+            for (size_t k = 0; k < times.size(); k++) {
+                fprintf(fp, "   - { time: %.17g, segment:%d, pose: [", times[k], (int)q.segment[k]);
+                for (int i = 0; i < 6; i++) fprintf(fp, "%s%.17g", i ? ", " : "", q.pose[6 * k + i]);
+                fprintf(fp, "],\n       covariance: !!opencv-matrix { rows:6, cols:6, dt:d, data:[");
+                for (int i = 0; i < 36; i++) fprintf(fp, "%s%.17g", i ? ", " : "", q.report.sigma2 * q.cov[36 * k + i]);
+                fprintf(fp, "] } }\n");
+            }
+            fclose(fp);
+            cout << "resample: " << times.size() << " poses (" << q.report.num_on_frame << " on frames, " << q.report.num_inside << " between), sigma2 "
+                 << q.report.sigma2 << ", written to " << rs_path << endl;
+        } catch (const exception &e) {
+            cerr << "resampling failed: " << e.what() << endl;
+            return 6;
         }
     }
     const chrono::duration<double> d = chrono::system_clock::now() - start;

@@ -403,6 +403,17 @@ class MultiCamMapper {
         aar_smooth_covariance_report report = {};
     };
     void track_smooth_covariance(double sigma_rot, double sigma_trans, SmoothCovariance &out);   // throws std::runtime_error on failure
+    // EXTENSION, no counterpart in the reference: the smoothed track at times that need not be frame times (aar_track_smooth_query, DESIGN.md
+    // section 30), with track_smooth()'s prior (the frame ids as its time axis) and Huber delta: what the smoother would report for a frame
+    // without detections inserted at each time.  cov is UNSCALED (multiply by report.sigma2) and left empty without covariance.
+    struct SmoothQuery {
+        std::vector<double> pose;        // [n][6] (rvec, t)
+        std::vector<double> cov;         // [n][36] row-major over (rvec, t)
+        std::vector<int32_t> segment;    // [n] the frame at or before the time; -1 before the first frame
+        aar_smooth_query_report report = {};
+    };
+    void track_smooth_query(double sigma_rot, double sigma_trans, const std::vector<double> &query_time, SmoothQuery &out,
+                            bool covariance = true);                                              // throws std::runtime_error on failure
     // EXTENSION, no counterpart in the reference: the corner noise and track_smooth()'s two sigmas fitted to the sequence itself by EM
     // (aar_track_smooth_fit), from the effective start values sigma_rot, sigma_trans.  The frame poses end as the smoothed
     // track at the fitted values; report.sigma_rot_eff / sigma_trans_eff are what track_smooth() and the live tracker take.  A mapper

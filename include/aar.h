@@ -663,6 +663,41 @@ int aar_track_smooth_fit(aar_problem *, double *x_full, const aar_lm_params *, c
 /* One E-step at x_full and the given (effective) sigmas, without smoothing, for checking: pair_terms [num_frames-1][4] = a_r, u_r, a_t, u_t
  * (may be NULL), sums = A_r, U_r, A_t, U_t.  x_full is not modified.  Errors as aar_track_smooth_fit. */
 int aar_track_smooth_fit_terms(aar_problem *, const double *x_full, const aar_smooth_params *, double *pair_terms, double sums[4]);
+/* The smoothed track at any time: pose and covariance at query times that need not be frame times -- a display's vsync,
+ * an IMU sample, a camera that is not genlocked.  The answer at a time t is what the smoother would report for a frame WITHOUT detections
+ * inserted at t.  With t_0 < ... < t_{F-1} the frame times (frame_time, or 0, 1, 2, ...), z the frame poses of x_full, S_f, R_f the blocks
+ * frame_cov, lag_cov of aar_track_smooth_covariance and F(z_i, z_j, D) = J^T L J the 12x12 information of one between factor over D:
+ *   inside a gap, t_a < t < t_b (b = a + 1), alpha = (t - t_a) / (t_b - t_a):
+ *     pose  R_m = R_a Exp(alpha log(R_a^T R_b)), t_m = t_a + alpha (t_b - t_a), returned as (canonical rvec, t)
+ *     cov   the (m, m) block of the inverse of the 18x18 information over (a, b, m):  [S_a R_a; R_a^T S_b]^-1 - F(z_a, z_b, t_b - t_a) on
+ *           (a, b), F(z_a, z_m, t - t_a) on (a, m), F(z_m, z_b, t_b - t) on (m, b)
+ *   on a frame time, t == t_f exactly: z_f and S_f, bit for bit
+ *   outside, t < t_0 or t > t_{F-1} (also num_frames = 1): the pose of the end frame e; cov = the (m, m) block of the inverse of
+ *           [S_e^-1 0; 0 0] + F(., ., |t - t_e|), the factor in the order (m, e) before the start and (e, m) after the end
+ * query_time [n_query] in any order, duplicates allowed.  pose [n_query][6]; cov [n_query][36] row-major over (rvec, t), symmetric to the bit,
+ * UNSCALED (multiply by report->sigma2: an inserted frame adds six residuals and six unknowns, sigma2 is that of the problem as given);
+ * segment [n_query] = a inside a gap or on frame a, -1 before the start, num_frames - 1 after the end.  Each of the three and the report may
+ * be NULL.  cov = NULL skips the covariance chain: one launch, poses and segments only, and data_cost, prior_cost and sigma2 read 0.
+ * All on the device: the chain of aar_track_smooth_covariance, whose blocks stay there, and one thread per query on top.  A query's bits do
+ * not depend on the other queries of the call or on their order; two calls give the same bits.  x_full is not modified, no LM state is left.
+ * n_query = 0: AAR_OK, nothing written.  Problems created with_huber are accepted (the data blocks carry the weights).
+ * AAR_ERR_INVALID (naming the index): a query_time that is not finite, num_frames < 1 with n_query > 0, whatever aar_smooth_params_validate
+ * refuses.  AAR_ERR_UNSUPPORTED: rel_motion != NULL -- under an expected motion dR the inserted frame's minimiser has no closed form, because
+ * the two parts dR would have to be split into do not commute with the geodesic's steps -- and a problem with a communicator.
+ * AAR_ERR_NUMERIC, nothing written: a non-positive pivot in the elimination (as aar_track_smooth_covariance, its root tolerance included) or
+ * in any query's own 6x6 inverses. */
+typedef struct aar_smooth_query_report {
+    uint32_t struct_size;
+    int64_t num_residuals, num_vars;   /* of the problem as given, as aar_smooth_covariance_report */
+    double data_cost, prior_cost, sigma2;
+    int32_t num_queries, num_inside, num_on_frame, num_outside;
+    int32_t launches;
+    double seconds;
+} aar_smooth_query_report;
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming what aar_track_smooth_query would refuse as invalid. */
+int aar_smooth_query_validate(int32_t num_frames, const aar_smooth_params *, int64_t n_query, const double *query_time);
+int aar_track_smooth_query(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_query, const double *query_time,
+                           double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report);
 
 /* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
  * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are
