@@ -256,9 +256,7 @@ struct aar_problem {
     double spec_chol_mu = -1;
     bool spec_chol_by_cg = false;      // ... whether it was a CG solve (a speculative solve is only consumed by a try that takes the same solver)
     double spec_chol_eta = 0;          // ... and the forcing term it was solved to (inexact solvers: a speculative solve is only consumed by a try that wants the same)
-    hipStream_t stream2 = nullptr;     // pass B of the trial point runs here, beside the speculative Schur complement
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool overlap = false;              // AAR_OVERLAP=1: pass B of the trial point on a second stream beside the Schur complement
+    hipStream_t stream2 = nullptr;     // download_z(side_stream): the copy of the final poses does not wait for the main stream
     bool merge_passes = true;          // passes A and B of an evaluation in one launch (AAR_MERGE_PASSES=0: two launches)
     int64_t trial_points = 0, launches = 0;
     aar_stage_times times;
@@ -563,9 +561,7 @@ void panels_now(aar_problem *pb, int which, double mu) { if (pb->P.n_smwork > 0)
 // J^T J blocks and B at z[which] into blk[which] (whose S, rhs, g0 must be zero): the "J", "transpose", "Jt*J", "B"
 // stages of libs/sparselevmarq.h:353-367.  Pass A also leaves the per-frame sums of r^2 in err_part and, for
 // mu_pred >= 0, (V_f + mu_pred I)^-1; zero_blk >= 0 clears that block set on the way.
-// spec_schur: also subtract the Schur terms for mu_pred right away (they only need pass A's output), on the main stream,
-// while pass B accumulates the shared blocks into the same S on a second stream (both only add into S: they commute).
-int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool spec_schur = false, bool ents_ready = false) {
+int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool ents_ready = false) {
     DeviceProblem &P = pb->P;
     if (!ents_ready) launch_unpack(P, which, pb->stream);   // {R, t, J_l} rows of z[which]; after a damped try k_backsub has written them
     if (P.F == 0 && zero_blk >= 0) {  // a rank without frames launches no pass A: clear the dead block set here
@@ -575,33 +571,20 @@ int eval_blocks(aar_problem *pb, int which, double mu_pred, int zero_blk, bool s
     // pass A rewrites W of this block set: its old panels are stale; it writes new ones itself when it inverts V_f (mu_pred >= 0)
     if (pb->panels_blk == which) pb->panels_blk = -1;
     if (P.n_smwork > 0 && P.dense_from_passA && mu_pred >= 0.0 && P.F > 0) panels_now(pb, which, mu_pred);
-    const bool ready = panels_ok(pb, which, mu_pred);
     {
         StageTimer t(pb, &pb->times.jacobian_normal_eq);
         if (pb->merge_passes && launch_passAB(P, which, mu_pred, zero_blk, pb->stream)) {
             launch_prior(P, which, true, pb->stream);   // (priors: after pass B, before anything reads S)
             launch_pair_prior(P, which, true, pb->stream);
-            if (spec_schur) launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
-            pb->launches += (spec_schur ? 2 : 1) + n_prior_launches(P);
+            pb->launches += 1 + n_prior_launches(P);
             return check_async("normal-equation kernels");
         }
         launch_passA(P, which, mu_pred, zero_blk, pb->stream);
-        if (spec_schur && pb->overlap && !pb->profiling && !pb->stage_timers && n_prior_launches(P) == 0) {
-            HIP_TRY(hipEventRecord(pb->ev_fork, pb->stream));
-            HIP_TRY(hipStreamWaitEvent(pb->stream2, pb->ev_fork, 0));
-            launch_passB(P, which, pb->stream2);
-            HIP_TRY(hipEventRecord(pb->ev_join, pb->stream2));
-            launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
-            HIP_TRY(hipStreamWaitEvent(pb->stream, pb->ev_join, 0));
-        } else {
-            launch_passB(P, which, pb->stream);
-            launch_prior(P, which, true, pb->stream);
-            launch_pair_prior(P, which, true, pb->stream);
-            if (spec_schur) launch_schur(P, which, 1.0, pb->stream, 0, 0, nullptr, ready);
-        }
+        launch_passB(P, which, pb->stream);
+        launch_prior(P, which, true, pb->stream);
+        launch_pair_prior(P, which, true, pb->stream);
     }
-    if (spec_schur) panels_now(pb, which, mu_pred);
-    pb->launches += (spec_schur ? 3 : 2) + n_prior_launches(P);
+    pb->launches += 2 + n_prior_launches(P);
     return check_async("normal-equation kernels");
 }
 
@@ -777,15 +760,13 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
     }
     pb->s_reduced = false;      // the factorisation below consumes the system
     pb->trial_reduced = false;
-    bool backsub_rode = false;
     if (P.use_spcg && !pb->force_direct && pb->spcg_skip > 0) pb->spcg_skip--;   // CG on the explicit reduced system instead of the LDL^T chain (S stays as it is)
     if (!chol_done) {
         StageTimer t(pb, &pb->times.chol);
-        // (stage timers keep the frame back-substitution in its own launch, so that it has a time of its own)
-        if (by_cg) backsub_rode = launch_spcg(P, cur, mu, pb->stream, pb->stage_timers ? -1 : tr);
-        else backsub_rode = launch_chol(P, cur, mu, pb->stream, pb->stage_timers ? -1 : tr);
+        if (by_cg) launch_spcg(P, cur, mu, pb->stream);
+        else launch_chol(P, cur, mu, pb->stream);
     }
-    if (!backsub_rode) {
+    {
         StageTimer t(pb, &pb->times.backsub);
         launch_backsub(P, cur, tr, pb->stream);
     }
@@ -793,7 +774,7 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
     pb->blocks_valid = false;  // S of the current point has been eliminated in place
     if (evaluate_trial) {
         // predicted damping of the next step: every accepted step of the reference's rule with gain >= 0.94 gives 0.33 mu
-        int rc = eval_blocks(pb, tr, mu * 0.33, cur, /*spec_schur=*/false, /*ents_ready=*/true);
+        int rc = eval_blocks(pb, tr, mu * 0.33, cur, /*ents_ready=*/true);
         if (rc) return rc;
         pb->trial_points++;
     } else {
@@ -838,7 +819,7 @@ int damped_try(aar_problem *pb, double mu, bool evaluate_trial) {
             // (the solver the NEXT try is expected to take: this try's own CG count is not known yet, the previous one's is)
             const bool spec_cg = P.use_spcg && pb->spcg_skip == 0 && !cg_near_cap;
             if (spec_cg) launch_spcg(P, tr, mu * 0.33, pb->stream);
-            else (void)launch_chol(P, tr, mu * 0.33, pb->stream);
+            else launch_chol(P, tr, mu * 0.33, pb->stream);
             pb->spec_chol_by_cg = spec_cg;
             pb->spec_chol_blk = tr;
             pb->spec_chol_mu = mu * 0.33;
@@ -1088,8 +1069,6 @@ void aar_problem_destroy(aar_problem *pb) {
     if (pb->ev[0]) (void)hipEventDestroy(pb->ev[0]);
     if (pb->ev[1]) (void)hipEventDestroy(pb->ev[1]);
     for (hipEvent_t e : pb->ev_pool) (void)hipEventDestroy(e);
-    if (pb->ev_fork) (void)hipEventDestroy(pb->ev_fork);
-    if (pb->ev_join) (void)hipEventDestroy(pb->ev_join);
     if (pb->stream2) { (void)hipStreamSynchronize(pb->stream2); (void)hipStreamDestroy(pb->stream2); }
     if (pb->stream) (void)hipStreamDestroy(pb->stream);
     delete pb;
@@ -1247,7 +1226,7 @@ struct CreateEnv {
     DeviceProblem::Tuning tune;        // tuning switches of this problem (kernels.h, DeviceProblem::Tuning)
     PlanKnobs knobs;                   // the planner's part (its solver-dependent switches: choose_solver)
     bool stage_timers = false;
-    std::optional<bool> overlap, merge_passes, fused_comm, spec_chol;
+    std::optional<bool> merge_passes, fused_comm, spec_chol;
     std::optional<int> dense_from_passA, spcg_coarse, spcg_coarse_from, pcg_coarse, pcg_coarse_from, pcg_e_every, pcg_resident, spcg_spread;
     std::optional<double> pcg_eta_loose, pcg_abs_tol, pcg_eta_switch;
     std::optional<int> schur_mfma, schur_panel_mb, pcg_fused, pcg_w32, pcg_grid;
@@ -1282,15 +1261,14 @@ int read_create_options(const aar_solver_options *opts, CreateEnv &E) {
     if (so.pcg_eta < 0 || so.pcg_max_it < 0 || so.pcg_eta_loose < 0 || so.pcg_eta_switch < 0 || so.pcg_abs_tol < 0) return set_error(AAR_ERR_INVALID, "aar_solver_options: negative pcg_eta / pcg_eta_loose / pcg_eta_switch / pcg_abs_tol / pcg_max_it");
     const char *tenv = getenv("AAR_STAGE_TIMERS");
     E.stage_timers = tenv && tenv[0] == '1';
-    { const char *e = getenv("AAR_OVERLAP"); E.overlap = (e && e[0] == '1'); }  // measured slower than one stream at config 3: off by default
     { const char *e = getenv("AAR_MERGE_PASSES"); if (e) E.merge_passes = (e[0] != '0'); }
     { const char *e = getenv("AAR_FUSED_COMM"); if (e) E.fused_comm = (e[0] != '0'); }
     { const char *e = getenv("AAR_SPEC_CHOL"); if (e) E.spec_chol = (e[0] != '0'); }
     {   // tuning switches of this problem (kernels.h, DeviceProblem::Tuning)
         auto env_int = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
-        env_int("AAR_FUSED_PANEL", E.tune.fused_panel); env_int("AAR_BS_RIDES", E.tune.bs_rides); env_int("AAR_BACKSUB_RIDES", E.tune.backsub_rides);
+        env_int("AAR_FUSED_PANEL", E.tune.fused_panel); env_int("AAR_BS_RIDES", E.tune.bs_rides);
         env_int("AAR_LDL_LOOKAHEAD", E.tune.lookahead); env_int("AAR_PASSA_VARIANT", E.tune.passA_variant); env_int("AAR_PACK_SYSTEM", E.tune.pack_system);
-        env_int("AAR_INIT_HEADSTART", E.tune.init_headstart); env_int("AAR_PASSB_LEAN", E.tune.passB_lean); env_int("AAR_PASSA_WRENCH", E.tune.passA_wrench); env_int("AAR_PASSB_WRENCH_MERGED", E.tune.passB_wrench_merged); env_int("AAR_SPCG_BACKSUB_RIDES", E.tune.spcg_backsub_rides); env_int("AAR_PASSAB_OCC2", E.tune.passAB_occ2);
+        env_int("AAR_INIT_HEADSTART", E.tune.init_headstart); env_int("AAR_PASSA_WRENCH", E.tune.passA_wrench); env_int("AAR_PASSAB_OCC2", E.tune.passAB_occ2);
     }
     { const char *e = getenv("AAR_DENSE_FROM_PASSA"); if (e) E.dense_from_passA = atoi(e) != 0 ? 1 : 0; }
     if (const char *t = getenv("AAR_SPCG_COARSE")) E.spcg_coarse = atoi(t) != 0;
@@ -1354,11 +1332,8 @@ int open_streams(const aar_problem_desc *d, const CreateEnv &E, aar_problem *pb)
     if (hipStreamCreateWithFlags(&pb->stream, hipStreamNonBlocking) != hipSuccess) return set_error(AAR_ERR_HIP, "hipStreamCreate failed");
     (void)hipEventCreate(&pb->ev[0]);
     (void)hipEventCreate(&pb->ev[1]);
-    if (hipStreamCreateWithFlags(&pb->stream2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&pb->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&pb->ev_join, hipEventDisableTiming) != hipSuccess)
-        return set_error(AAR_ERR_HIP, "second stream / events could not be created");
-    if (E.overlap) pb->overlap = *E.overlap;
+    if (hipStreamCreateWithFlags(&pb->stream2, hipStreamNonBlocking) != hipSuccess)
+        return set_error(AAR_ERR_HIP, "second stream could not be created");
     if (E.merge_passes) pb->merge_passes = *E.merge_passes;
     if (E.fused_comm) pb->fused_comm = *E.fused_comm;
     if (E.spec_chol) pb->spec_chol = *E.spec_chol;
@@ -1596,12 +1571,12 @@ int alloc_workspaces(aar_problem *pb, const CreateEnv &E, int64_t sp_total) {
         P.pcg_grid = std::min(P.pcg_grid, pcg_max_grid(A, P.pcg_coarse != 0, P.n_cus));
     }
     if (P.use_spcg) {
-        AL(spcg_ws, spcg_ws_doubles(P.n_pad)); AL(spcg_iters, 8); AL(spcg_done, 2);
+        AL(spcg_ws, spcg_ws_doubles(P.n_pad)); AL(spcg_iters, 8);
         if (spcg_coarse_now(P)) AL(spcg_pre, spcg_pre_doubles(P.n_pad));   // (zeroed: the restriction rows' columns of fixed entities stay zero)
         spcg_ws_reset(P, pb->stream);
     }
     if (P.n_smwork) { AL(Wd, (size_t)F * P.Ad * 36); AL(Yd, (size_t)F * P.Ad * 36); }   // zeroed here, once: absent pairs are never written
-    AL(Dfac, (size_t)P.nT * CHOL_NB * CHOL_NB); AL(Linv16, (size_t)P.nT * (CHOL_NB / 16) * 256); AL(delta_s, P.n_pad); AL(bs_flags, (size_t)P.nT + 1);
+    AL(Dfac, (size_t)P.nT * CHOL_NB * CHOL_NB); AL(Linv16, (size_t)P.nT * (CHOL_NB / 16) * 256); AL(delta_s, P.n_pad); AL(bs_flags, (size_t)P.nT);
     AL(Lp, (size_t)P.nT * P.n_pad * CHOL_NB); AL(zf, P.n_pad);
     AL(err_part, std::max<size_t>((size_t)F, (size_t)((N + 255) / 256)) + 1);
     AL(lin_part, 2 * (size_t)(F + 1)); AL(scal, 8); AL(flags, 4);
@@ -1979,10 +1954,10 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
                  o_Dv = o_Si + (size_t)np * np, o_fr = o_Dv + np, o_db = o_fr + fr, total = o_db + 36 * (size_t)std::max(P.A, 1);
     if (!pb->cov_ws) {
         if ((rc = dev_alloc(pb, &pb->cov_ws, total))) return rc;
-        if ((rc = dev_alloc(pb, &pb->cov_iws, (size_t)np + nT2 + 1 + 4))) return rc;
+        if ((rc = dev_alloc(pb, &pb->cov_iws, (size_t)np + nT2 + 4))) return rc;
     }
     double *ws = pb->cov_ws;
-    int32_t *rowmask = pb->cov_iws, *bsf = rowmask + np, *flg = bsf + nT2 + 1;
+    int32_t *rowmask = pb->cov_iws, *bsf = rowmask + np, *flg = bsf + nT2;
     // the reduced system's diagonal and the summed sum r^2 on the host: entities no observation touches have an exactly zero diagonal
     HIP_TRY(hipMemcpy2DAsync(pb->d_diag, sizeof(double), P.blk[cur].S, (size_t)(np + 1) * sizeof(double), sizeof(double), np, hipMemcpyDeviceToDevice, pb->stream));
     std::vector<double> diag(np);
@@ -2006,12 +1981,12 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
     double *S2 = ws + o_S2;
     launch_cov_stage(P.blk[cur].S, np, S2, n2, rowmask, pb->stream);
     HIP_TRY(hipMemsetAsync(S2 + (size_t)n2 * n2, 0, (2 * (size_t)n2 + 8) * sizeof(double), pb->stream));
-    HIP_TRY(hipMemsetAsync(bsf, 0, (nT2 + 1 + 4) * sizeof(int32_t), pb->stream));
+    HIP_TRY(hipMemsetAsync(bsf, 0, (nT2 + 4) * sizeof(int32_t), pb->stream));
     DeviceProblem Q = P;
     Q.n_pad = n2; Q.nT = nT2;
     Q.blk[cur].S = S2; Q.blk[cur].rhs = S2 + (size_t)n2 * n2; Q.blk[cur].g0 = Q.blk[cur].rhs + n2; Q.blk[cur].tail = Q.blk[cur].g0 + n2;
     Q.Dfac = ws + o_D; Q.Linv16 = ws + o_Li; Q.Lp = ws + o_Lp; Q.zf = ws + o_zf; Q.delta_s = ws + o_ds; Q.bs_flags = bsf; Q.bs_epoch = 0; Q.flags = flg;
-    (void)launch_chol(Q, cur, 0.0, pb->stream, -1);
+    launch_chol(Q, cur, 0.0, pb->stream);
     launch_cov_inverse(S2, Q.Dfac, Q.Lp, np, n2, nT2, P.tune.fused_panel, ws + o_Lc, ws + o_Dv, ws + o_X, ws + o_Si, pb->stream);
     const bool frames = frame_cov && L.of && P.F > 0;
     if (frames) launch_cov_frames(P, cur, ws + o_Si, rowmask, ws + o_fr, pb->stream);
@@ -2260,7 +2235,7 @@ int aar_lm_init(aar_problem *pb, const double *x_full, const aar_lm_params *prm)
     if (P.F > 0 && P.n_chunks > 0 && !pb->comm) {
         launch_unpack(P, 0, pb->stream, /*zero_blk=*/0);
         pb->launches += 1;
-        if ((rc = eval_blocks(pb, 0, -1.0, /*zero_blk=*/1, /*spec_schur=*/false, /*ents_ready=*/true))) return rc;
+        if ((rc = eval_blocks(pb, 0, -1.0, /*zero_blk=*/1, /*ents_ready=*/true))) return rc;
     } else {
         if ((rc = zero_for_init(pb))) return rc;
         if ((rc = eval_blocks(pb, 0, -1.0, -1))) return rc;

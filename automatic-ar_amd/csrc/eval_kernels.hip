@@ -1009,15 +1009,6 @@ __global__ void __launch_bounds__(256) k_passB_det(const PassBArgs b) {
     if (WR) passB_wrench_body<true>(b, scratch, (int)blockIdx.x * 4);
     else passB_body<true>(b, scratch, (int)blockIdx.x * 4);
 }
-// experiments (AAR_PASSB_LEAN=1 / 2): the corner loop not unrolled, with / without the register cap that lets two wavefronts share a SIMD
-__global__ void __launch_bounds__(256, 2) k_passB_lean2(const PassBArgs b) {
-    __shared__ double scratch[4 * 2048];
-    passB_body<false, true>(b, scratch, (int)blockIdx.x * 4);
-}
-__global__ void __launch_bounds__(256) k_passB_lean1(const PassBArgs b) {
-    __shared__ double scratch[4 * 2048];
-    passB_body<false, true>(b, scratch, (int)blockIdx.x * 4);
-}
 
 // Pass B for the intrinsics entities (optimize_cam_intrinsics): same chunks, the 62 values of U_kk (4x4, packed lower), W_kc
 // (4x6: intrinsics x the camera's own pose), W_km (4x6: intrinsics x marker) and g_k; rows of entity k_ent0 + camera.
@@ -1159,14 +1150,13 @@ __global__ void __launch_bounds__(BLOCK) k_passA_intr(const PassAArgs a) {
     else passA_body<BLOCK, CPL, true>(a, lds, (int)blockIdx.x, (int)gridDim.x);
 }
 
-template <int BLOCK, int CPL, bool WR, bool WRB = WR>
+template <int BLOCK, int CPL, bool WR>
 __global__ void __launch_bounds__(BLOCK) k_passAB(const PassAArgs a, const PassBArgs b) {
-    extern __shared__ double lds[];   // pass A's layout; pass B uses the first (BLOCK / 64) * 2048 doubles
+    extern __shared__ double lds[];   // pass A's layout; pass B (always in row form here) uses the first (BLOCK / 64) * 2048 doubles
     if ((int)blockIdx.x < a.F) {
         if (WR) passA_wrench_body<BLOCK, CPL>(a, lds, (int)blockIdx.x, a.F);
         else passA_body<BLOCK, CPL>(a, lds, (int)blockIdx.x, a.F);
-    } else if (WRB) passB_wrench_body(b, lds, ((int)blockIdx.x - a.F) * (BLOCK / 64));
-    else passB_body(b, lds, ((int)blockIdx.x - a.F) * (BLOCK / 64));
+    } else passB_body(b, lds, ((int)blockIdx.x - a.F) * (BLOCK / 64));
 }
 // the same capped at 256 registers (two wavefronts per SIMD; pass B's corner loop not unrolled): long sequences, whose frame workgroups would otherwise take
 // more than one round of the chip's wavefront slots (AAR_PASSAB_OCC2; profiles/r05_attempts.txt section 6)
@@ -1308,14 +1298,12 @@ static void launch_passA_t(const DeviceProblem &P, const PassAArgs &a, const Pas
     } else if (P.intr) {
         if (P.tune.passA_wrench) launch_lds(k_passA_intr<B, CPL, true>, dim3(P.F), dim3(B), lds, st, a);
         else launch_lds(k_passA_intr<B, CPL, false>, dim3(P.F), dim3(B), lds, st, a);
-    } else if (pbargs && P.tune.passA_wrench && !P.tune.passB_wrench_merged &&
+    } else if (pbargs && P.tune.passA_wrench &&
                (P.tune.passAB_occ2 >= 0 ? P.tune.passAB_occ2 != 0 : P.F + nb > P.n_cus * 4 / (B / 64))) {
         // more workgroups than the chip holds at one wavefront per SIMD (388 registers): at two the frames of a long sequence run in one round instead of two
         // (config 4, 2000 frames: 36.3 -> 32.6 us; config 3's 500 frames fit anyway and keep the unrolled pass B)
         launch_lds(k_passAB_o2<B, CPL>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
-    } else if (pbargs && P.tune.passA_wrench && !P.tune.passB_wrench_merged) {   // (the default: pass A in wrench form, pass B's chunks in row form)
-        launch_lds(k_passAB<B, CPL, true, false>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
-    } else if (pbargs && P.tune.passA_wrench) {
+    } else if (pbargs && P.tune.passA_wrench) {   // (the default: pass A in wrench form, pass B's chunks in row form)
         launch_lds(k_passAB<B, CPL, true>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
     } else if (pbargs) {
         launch_lds(k_passAB<B, CPL, false>, dim3(P.F + nb), dim3(B), lds, st, a, *pbargs);
@@ -1331,14 +1319,11 @@ static void launch_passA_any(const DeviceProblem &P, const PassAArgs &a, const P
     // two wavefronts above
     const double avg = (double)P.N / (double)P.F;
     if (P.deterministic && avg > 96) return launch_passA_t<64, 4>(P, a, pbargs, st);   // ONE wavefront per frame: its LDS additions come in program order
-    const int var = P.tune.passA_variant;   // experiments (AAR_PASSA_VARIANT): 1281 / 1282 / 1284 / 2564
+    const int var = P.tune.passA_variant;   // test hook (AAR_PASSA_VARIANT): any of the four shapes below on any problem
     if (var == 641) return launch_passA_t<64, 1>(P, a, pbargs, st);
     if (var == 642) return launch_passA_t<64, 2>(P, a, pbargs, st);
     if (var == 644) return launch_passA_t<64, 4>(P, a, pbargs, st);
-    if (var == 1281) return launch_passA_t<128, 1>(P, a, pbargs, st);
-    if (var == 1282) return launch_passA_t<128, 2>(P, a, pbargs, st);
     if (var == 1284) return launch_passA_t<128, 4>(P, a, pbargs, st);
-    if (var == 2564) return launch_passA_t<256, 4>(P, a, pbargs, st);
     if (avg <= 14) launch_passA_t<64, 1>(P, a, pbargs, st);
     else if (avg <= 30) launch_passA_t<64, 2>(P, a, pbargs, st);
     else if (avg <= 96) launch_passA_t<64, 4>(P, a, pbargs, st);
@@ -1366,9 +1351,7 @@ void launch_passB(const DeviceProblem &P, int which, hipStream_t st) {
     }
     {
         HookScope _h(P, KID_PASSB);
-        if (P.tune.passB_lean == 1) hipLaunchKernelGGL(k_passB_lean2, dim3((P.n_chunks + 3) / 4), dim3(256), 0, st, passB_args(P, which));
-        else if (P.tune.passB_lean == 2) hipLaunchKernelGGL(k_passB_lean1, dim3((P.n_chunks + 3) / 4), dim3(256), 0, st, passB_args(P, which));
-        else if (P.tune.passA_wrench) hipLaunchKernelGGL(k_passB<true>, dim3((P.n_chunks + 3) / 4), dim3(256), 0, st, passB_args(P, which));
+        if (P.tune.passA_wrench) hipLaunchKernelGGL(k_passB<true>, dim3((P.n_chunks + 3) / 4), dim3(256), 0, st, passB_args(P, which));
         else hipLaunchKernelGGL(k_passB<false>, dim3((P.n_chunks + 3) / 4), dim3(256), 0, st, passB_args(P, which));
     }
     if (P.intr) { HookScope _h(P, KID_PASSB); hipLaunchKernelGGL(k_passB_intr, dim3((P.n_chunks + 3) / 4), dim3(256), 0, st, passB_args(P, which)); }

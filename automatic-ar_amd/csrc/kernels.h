@@ -14,7 +14,6 @@ namespace aar {
 constexpr int SPCG_MAX_IT = 128, SPCG_BUFS = SPCG_MAX_IT + 2, SPCG_MAX_NT = 14;
 constexpr int SPCG_MASK_WORDS = (16 * SPCG_MAX_NT + 63) / 64;   // 64-bit words of the fixed-entity mask in k_spcg's arguments (16 entities per tile)
 constexpr int SPCG_STAGE_MAX_NT = 5;  // k_spcg<NT, false> reads its rows of S in 16-byte pieces through the LDS (9 NT loads of 4 registers in flight per lane) up to this many tiles: at six the kernel starts to spill scalar registers
-constexpr int SPCG_RIDE_MAX_NT = 8;   // the back-substitution rides only while all CG wavefronts share one XCD (spcg_spread 8): at most 128 entities
 // default cap by system size: up to four tiles the direct chain (<= 120 us) is cheaper than a CG solve of more than ~64 iterations; larger systems' chains cost 200-500 us
 inline int spcg_default_cap(int nT) { return nT <= 4 ? 64 : SPCG_MAX_IT; }
 // Default forcing terms of the inexact solvers (include/aar.h: aar_solver_options.pcg_eta; DESIGN.md section 12, profiles/r05_eta_pose_sweep.txt).  Chosen for the
@@ -143,8 +142,6 @@ struct DeviceProblem {
     double *spcg_ws = nullptr;            // [2][SPCG_BUFS][spcg_stride(n_pad)] hand-over slots (sentinel-filled when idle)
     int32_t *spcg_iters = nullptr;        // [0] iterations of the last solve, [1] running total, [2] solves, [3] solves that hit the cap (flag 8)
     mutable int spcg_parity = 0;
-    int32_t *spcg_done = nullptr;         // [0] arrivals of CG workgroups, [1] flag: the frame back-substitution riding in k_spcg's launch waits for it
-    mutable int spcg_epoch = 0;
     // ... with frames sharded over ranks: this rank's set-up share [A][28] (all-reduced), Minv [A][36], x | r | p | scalars [3 n + 8],
     // this rank's partial y [n] (all-reduced per iteration), mapped host record {done, iterations, -, sequence}
     double *pcgd_setup = nullptr, *pcgd_minv = nullptr, *pcgd_state = nullptr, *pcgd_y = nullptr, *pcgd_host = nullptr;
@@ -153,15 +150,10 @@ struct DeviceProblem {
     struct Tuning {
         int fused_panel = 3;       // AAR_FUSED_PANEL: block columns with at most this many tiles below the diagonal take k_ldl_panel
         int bs_rides = 1;          // AAR_BS_RIDES=0: the back-substitution of 2-3 tile systems as its own chained launch
-        int backsub_rides = 0;     // AAR_BACKSUB_RIDES=1: the frame back-substitution rides in the last tile's launch
         int lookahead = 1;         // AAR_LDL_LOOKAHEAD=0: tall block columns launch k_ldl_update
-        int passA_variant = 0;     // AAR_PASSA_VARIANT: 641 / 642 / 644 / 1281 / 1282 / 1284 / 2564 force a pass A workgroup shape (threads, corners per lane)
+        int passA_variant = 0;     // AAR_PASSA_VARIANT (test hook): 641 / 642 / 644 / 1284 force one of pass A's four production workgroup shapes (threads, corners per lane)
         int passAB_occ2 = -1;       // AAR_PASSAB_OCC2=0 / 1: the merged observation passes capped at 256 registers (two wavefronts per SIMD); -1: when their workgroups exceed one round of the chip's slots
-        int spcg_backsub_rides = 0; // AAR_SPCG_BACKSUB_RIDES=1 (experiment, slower: profiles/r04_attempts.txt): the frame back-substitution rides in k_spcg's launch on the XCDs the CG leaves idle
         int passA_wrench = 1;      // AAR_PASSA_WRENCH=0: pass A in its row form (three Jacobian blocks per row, 100 accumulators per lane) -- the A/B reference of the wrench form
-        int passB_wrench_merged = 0;   // AAR_PASSB_WRENCH_MERGED=1: pass B in wrench form also inside the merged launch of small problems (there a lane has one observation and the
-                                       // stage after the wave sum costs more than the rows save: -1.5 % LM it/s at config 3); as a launch of its own pass B is always in pass A's form
-        int passB_lean = 0;        // AAR_PASSB_LEAN (experiment): 1 = pass B's corner loop not unrolled + two wavefronts per SIMD (28 spilled registers), 2 = not unrolled only
         int pack_system = -1;      // AAR_PACK_SYSTEM=0/1: the reduced system travels as it lies / as the packed triangle (default: by size)
         int init_headstart = 1;    // AAR_INIT_HEADSTART=0: the first step's frame inverses and Schur complement wait for the host to have read mu_0
     } tune;
@@ -256,14 +248,14 @@ void launch_frame_inv(const DeviceProblem &P, int which, double mu, hipStream_t 
 // panels_ready (MFMA path): Wd / Yd already hold this block set's panels for the damping in Vinv (pass A wrote them): no k_schur_fill
 bool launch_schur(const DeviceProblem &P, int which, double sign, hipStream_t st, unsigned long long ride_seq = 0, int ride_n_err = 0,
                   double *ride_scal = nullptr, bool panels_ready = false);   // ride_scal: the rider leaves the scalars there and does not publish
-// damping + LDL^T + both substitutions -> delta_s; trial >= 0: launch_backsub(which, trial) may ride in the last launch (true: it did)
-bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial = -1);
+// damping + LDL^T + both substitutions -> delta_s
+void launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st);
 void launch_backsub(const DeviceProblem &P, int cur, int trial, hipStream_t st);   // z[trial] = z[cur] + delta, lin_part
 void launch_pcg(const DeviceProblem &P, int which, double mu, hipStream_t st);     // AAR_SOLVER=pcg: delta_s by PCG through the frame blocks (needs Vinv, hf for mu)
 size_t pcg_lds_bytes(int A, bool coarse = false);   // coarse: with the tables of k_pcgf's coarse space
 int pcg_max_grid(int A, bool coarse, int cus);   // largest co-resident grid of the persistent PCG kernels at the dynamic LDS they are launched with
 // solver spcg: delta_s by CG on the explicit reduced system S of block set `which` (the Schur complement for mu must have been taken; S is not modified)
-bool launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial = -1);   // trial >= 0: launch_backsub(which, trial) may ride (true: it did)
+void launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st);
 int spcg_resident_per_cu(int nT, bool coarse);             // occupancy query: wavefronts of k_spcg<nT> one CU holds (0: unknown)
 inline bool spcg_coarse_now(const DeviceProblem &P) { return P.spcg_coarse && (P.spcg_root_c >= 0 || P.spcg_root_m >= 0); }   // this problem's k_spcg can carry the coarse space
 void spcg_build_fixed_mask(DeviceProblem &P, const int32_t *ent_fixed_host);   // P.spcg_fixed from the host's copy of ent_fixed [P.n / 6]

@@ -8,7 +8,6 @@
 #include <type_traits>
 #include "geom.hpp"
 #include "kernels.h"
-#include "backsub.hpp"
 
 namespace aar {
 
@@ -650,9 +649,162 @@ __device__ __forceinline__ void bs_sweep(const double *__restrict__ Ls, const do
     }
 }
 
+// Hand-over of a small vector between workgroups of one launch WITHOUT cache-maintenance fences.  A release / acquire pair at agent
+// scope costs a write-back of the XCD's L2 plus an invalidate: 4.3-5.4 us per hop from a 1024-thread workgroup, measured
+// (scripts/probe/hop_probe.hip) -- more than a kernel boundary (2.9 us).  When the payload itself travels as relaxed agent-scope
+// atomic stores / loads (sc1: written through and read past the XCD's L2) nothing needs to be flushed: the writer drains its own
+// stores (s_waitcnt) and raises the flag, the reader polls the flag and then loads: 1.1 us per hop for up to 8 KB.
+__device__ __forceinline__ void hop_publish(int32_t *flag, int value, bool leader) {   // whole wavefront; its payload stores were atomic (agent)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (leader) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ bool hop_wait(const int32_t *flag, int value) {   // one thread; false = gave up (the caller raises an error flag)
+    long spins = 0;
+    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != value) {
+        __builtin_amdgcn_s_sleep(1);
+        if (++spins > (1L << 24)) return false;
+    }
+    asm volatile("" ::: "memory");
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Frame back-substitution, one wavefront per frame: delta_f = (V_f+mu I)^-1 (g_f - sum_a W_af^T delta_a);
+// z_trial = z_cur + delta; per-frame pieces of L = 0.5 delta^T (mu delta - B) (libs/sparselevmarq.h:406).
+// The last workgroup updates the shared (camera / marker) parameters.
+// ------------------------------------------------------------------------------------------------
+struct BacksubArgs {
+    const int32_t *fslot_start, *fslot_ent;
+    const double *W, *Vinv, *gf, *g0, *delta_s, *zc;
+    const float *Wf;            // PCG with the fp32 operator: pass A's fp32 copy of W (kernels.h, Blocks::Wf) instead of W -- what the solve itself has read; nullptr otherwise
+    double *zt;
+    int A, F, n_frame_blocks;
+    double *lin_part, *ent_out;
+    int k_ent0;
+};
+
 __global__ void __launch_bounds__(256) k_backsub(const BacksubArgs b) {
     __shared__ double red[32];
-    backsub_body(b, (int)blockIdx.x, red, nullptr, 0, nullptr);
+    const int blk = (int)blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = blockDim.x >> 6;   // wave-uniform: the frame's slot range, g_f, V_f^-1 through the scalar cache
+    if (blk == b.n_frame_blocks) {  // shared part
+        double d2 = 0.0, dg = 0.0;
+        for (int i = tid; i < 6 * b.A; i += blockDim.x) {
+            const double d = b.delta_s[i];
+            b.zt[i] = b.zc[i] + d;
+            d2 += d * d;
+            dg += d * b.g0[i];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { d2 += __shfl_xor(d2, off); dg += __shfl_xor(dg, off); }
+        if (lane == 0) { red[wave] = d2; red[16 + wave] = dg; }
+        __syncthreads();
+        if (tid == 0) {
+            double s2 = 0.0, sg = 0.0;
+            for (int w = 0; w < nwaves; w++) { s2 += red[w]; sg += red[16 + w]; }
+            b.lin_part[2 * (size_t)b.F] = s2;
+            b.lin_part[2 * (size_t)b.F + 1] = sg;
+        }
+        // {R, t, J_l} rows of the shared entities at the trial point: both observation passes of the trial evaluation read
+        // them from this table (so they need not run one after the other)
+        __threadfence_block();
+        __syncthreads();
+        for (int e = tid; e < b.A; e += blockDim.x) {   // entities from k_ent0 on are intrinsics entities: their row is the camera matrix
+            if (e >= b.k_ent0) make_k_row(b.zt + 6 * (size_t)e, b.ent_out + (size_t)e * ENT_STRIDE);
+            else make_ent_row(b.zt + 6 * (size_t)e, b.ent_out + (size_t)e * ENT_STRIDE);
+        }
+        return;
+    }
+    const int f = blk * nwaves + wave;
+    const bool live = f < b.F;
+    const int s0 = live ? b.fslot_start[f] : 0, s1 = live ? b.fslot_start[f + 1] : 0;
+    // first pass of the slot list (all of it for frames with up to 64 cameras+markers)
+    const int sl = s0 + lane;
+    const bool has = sl < s1;
+    int a0 = 0;
+    double2 w0[18];
+    if (has) {
+        a0 = b.fslot_ent[sl];
+        if (b.Wf) {
+            const float4 *wf = reinterpret_cast<const float4 *>(b.Wf + (size_t)s0 * 36) + lane;
+            const int kf = s1 - s0;
+#pragma unroll
+            for (int q = 0; q < 9; q++) {
+                const float4 v = wf[(size_t)q * kf];
+                w0[2 * q] = make_double2(v.x, v.y); w0[2 * q + 1] = make_double2(v.z, v.w);
+            }
+        } else {
+            const double2 *wb = reinterpret_cast<const double2 *>(b.W + (size_t)sl * 36);
+#pragma unroll
+            for (int q = 0; q < 18; q++) w0[q] = wb[q];
+        }
+    }
+    double g[6], vrow[6], zc6 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) { g[i] = live ? b.gf[(size_t)f * 6 + i] : 0.0; vrow[i] = (live && lane < 6) ? b.Vinv[(size_t)f * 36 + lane * 6 + i] : 0.0; }
+    if (live && lane < 6) zc6 = b.zc[(size_t)6 * (b.A + f) + lane];
+    if (!live) return;
+    double c[6] = {0, 0, 0, 0, 0, 0};
+    if (has) {
+        double da[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) da[i] = b.delta_s[6 * a0 + i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            c[0] += w0[3 * i].x * da[i]; c[1] += w0[3 * i].y * da[i]; c[2] += w0[3 * i + 1].x * da[i];
+            c[3] += w0[3 * i + 1].y * da[i]; c[4] += w0[3 * i + 2].x * da[i]; c[5] += w0[3 * i + 2].y * da[i];
+        }
+    }
+    for (int s = s0 + lane + 64; s < s1; s += 64) {
+        const int a = b.fslot_ent[s];
+        double2 wt[18];
+        if (b.Wf) {
+            const float4 *wf = reinterpret_cast<const float4 *>(b.Wf + (size_t)s0 * 36) + (s - s0);
+            const int kf = s1 - s0;
+#pragma unroll
+            for (int q = 0; q < 9; q++) {
+                const float4 v = wf[(size_t)q * kf];
+                wt[2 * q] = make_double2(v.x, v.y); wt[2 * q + 1] = make_double2(v.z, v.w);
+            }
+        } else {
+            const double2 *wb = reinterpret_cast<const double2 *>(b.W + (size_t)s * 36);
+#pragma unroll
+            for (int q = 0; q < 18; q++) wt[q] = wb[q];
+        }
+        double da[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) da[i] = b.delta_s[6 * a + i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const double2 x0 = wt[3 * i], x1 = wt[3 * i + 1], x2 = wt[3 * i + 2];
+            c[0] += x0.x * da[i]; c[1] += x0.y * da[i]; c[2] += x1.x * da[i];
+            c[3] += x1.y * da[i]; c[4] += x2.x * da[i]; c[5] += x2.y * da[i];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int i = 0; i < 6; i++) c[i] += __shfl_xor(c[i], off);
+    double d = 0.0;
+    if (lane < 6) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) d += vrow[k] * (g[k] - c[k]);
+        b.zt[(size_t)6 * (b.A + f) + lane] = zc6 + d;
+    }
+    {   // the frame's own {R, t, J_l} row at the trial point (lane 0; the six new parameters come from lanes 0..5)
+        const double zn = (lane < 6) ? zc6 + d : 0.0;
+        double zv[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) zv[i] = __shfl(zn, i);
+        if (lane == 0) make_ent_row(zv, b.ent_out + (size_t)(b.A + f) * ENT_STRIDE);
+    }
+    double d2 = (lane < 6) ? d * d : 0.0;
+    double dgv = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) dgv += (lane == i) ? d * g[i] : 0.0;
+#pragma unroll
+    for (int off = 4; off > 0; off >>= 1) { d2 += __shfl_xor(d2, off); dgv += __shfl_xor(dgv, off); }
+    if (lane == 0) { b.lin_part[2 * (size_t)f] = d2; b.lin_part[2 * (size_t)f + 1] = dgv; }
 }
 
 // Back-substitution of a system of two or three tiles by ONE workgroup that rides in the launch of the LAST diagonal tile
@@ -664,7 +816,7 @@ __global__ void __launch_bounds__(256) k_backsub(const BacksubArgs b) {
 __device__ __forceinline__ void bs_small(double *__restrict__ lds, const double *__restrict__ S, const double *__restrict__ rhs,
                                          const double *__restrict__ Dfac, double *__restrict__ x, int n_pad, int nT,
                                          const int32_t *__restrict__ flag, int epoch, int32_t *__restrict__ err_flags,
-                                         const double *__restrict__ Lp, const double *__restrict__ zf, int fused_m, int32_t *__restrict__ done_flag) {
+                                         const double *__restrict__ Lp, const double *__restrict__ zf, int fused_m) {
     constexpr int LD = NB + 2, G = 10, RPT = (NB + G - 1) / G, NL = NB * NB / 1024;
     double *Ls = lds, *xs = Ls + NB * LD, *w = xs + 2 * NB, *part = w + NB;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -726,7 +878,6 @@ __device__ __forceinline__ void bs_small(double *__restrict__ lds, const double 
         bs_sweep(Ls, w, lane, b0, b1);
         __hip_atomic_store(x + s1 * NB + lane, b0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); xs[NB + lane] = b0;
         if (lane + 64 < NB) { __hip_atomic_store(x + s1 * NB + lane + 64, b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); xs[NB + lane + 64] = b1; }
-        if (nT != 3 && done_flag) hop_publish(done_flag, epoch, lane == 0);   // all of delta_s is in memory: the frame back-substitution riding in this launch may go
     }
     if (nT != 3) return;
     __syncthreads();
@@ -751,7 +902,6 @@ __device__ __forceinline__ void bs_small(double *__restrict__ lds, const double 
         bs_sweep(Ls, w, lane, b0, b1);
         __hip_atomic_store(x + lane, b0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lane + 64 < NB) __hip_atomic_store(x + lane + 64, b1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (done_flag) hop_publish(done_flag, epoch, lane == 0);
     }
 }
 
@@ -842,26 +992,20 @@ __global__ void __launch_bounds__(DG_THREADS) k_ldl_diag(const double *__restric
                                                          int32_t *__restrict__ flags, int nT, const double *__restrict__ rhs,
                                                          const double *__restrict__ g0, double *__restrict__ xout,
                                                          const double *__restrict__ Lp, const double *__restrict__ zf, int fused_m,
-                                                         int32_t *__restrict__ bs_flag, int bs_epoch, int ride_bs, int ride_backsub, const BacksubArgs bsub,
+                                                         int32_t *__restrict__ bs_flag, int bs_epoch, int ride_bs,
                                                          int upd_s, double *__restrict__ Sw, double *__restrict__ rhsw) {
     constexpr int LD = NB + 2, NBK = NB / 6, PER = NB * NB / DG_THREADS, NT16 = NB / 16, NTILE = NT16 * (NT16 + 1) / 2, NWAVE = DG_THREADS / 64, NMW = DG_ROW0 / 64;
     static_assert(NB % 16 == 0 && NB % 6 == 0 && NB * NB % DG_THREADS == 0 && NWAVE >= NSB && DG_THREADS - DG_ROW0 >= NB - 6 &&
                   NTILE <= 2 * NMW && DG_ROW0 % 64 == 0, "diag tile mapping");
     extern __shared__ __align__(16) double T[];
     TL_DECL
-    // riders of the LAST tile's launch: workgroup 1 = the back-substitution of the tiles above (two or three tiles, see bs_small);
-    // the workgroups behind it = the frame back-substitution (backsub_body), which waits for the last piece of delta_s:
-    // flag[nT] from bs_small, or flag[nT - 1] from this tile's own solve when it is the only tile
+    // rider of the LAST tile's launch: workgroup 1 = the back-substitution of the tiles above (two or three tiles, see bs_small)
     if (upd_s >= 0 && blockIdx.x > 0) {   // look-ahead: the rest of block column upd_s's trailing update rides beside this tile's factorisation
         ldl_update_rider(T, Sw, rhsw, g0, Dfac, n_pad, n, upd_s, nT, mu, ent_fixed, (int)blockIdx.x - 1);
         return;
     }
     if (ride_bs && blockIdx.x == 1) {
-        bs_small(T, S, rhs, Dfac, xout, n_pad, nT, bs_flag, bs_epoch, flags, Lp, zf, fused_m, ride_backsub ? bs_flag + nT : nullptr);
-        return;
-    }
-    if (blockIdx.x > 0) {
-        backsub_body(bsub, (int)blockIdx.x - 1 - ride_bs, T, bs_flag + (ride_bs ? nT : nT - 1), bs_epoch, flags);
+        bs_small(T, S, rhs, Dfac, xout, n_pad, nT, bs_flag, bs_epoch, flags, Lp, zf, fused_m);
         return;
     }
     double *Yn = T + NB * LD;   // [2][NB][DG_YS]: L D of block column k in buffer k & 1, columns 6, 7 zero
@@ -1614,50 +1758,39 @@ bool launch_schur(const DeviceProblem &P, int which, double sign, hipStream_t st
     return extra != 0;
 }
 
-BacksubArgs backsub_args(const DeviceProblem &P, int cur, int trial, int waves_per_block) {
+// the arguments of the back-substitution z[trial] = z[cur] + delta: four wavefronts (= frames) per workgroup
+static BacksubArgs backsub_args(const DeviceProblem &P, int cur, int trial) {
     const DeviceProblem::Blocks &b = P.blk[cur];
     BacksubArgs a;
     a.fslot_start = P.fslot_start; a.fslot_ent = P.fslot_ent; a.W = b.W; a.Vinv = b.Vinv; a.gf = b.gf; a.g0 = b.g0;
     a.Wf = P.use_pcg ? b.Wf : nullptr;   // (allocated only where the solve itself reads the fp32 blocks: ba_capi.hip)
     a.delta_s = P.delta_s; a.zc = P.z[cur]; a.zt = P.z[trial]; a.A = P.A; a.F = P.F;
-    a.n_frame_blocks = (P.F + waves_per_block - 1) / waves_per_block;
+    a.n_frame_blocks = (P.F + 3) / 4;
     a.lin_part = P.lin_part; a.ent_out = P.ent[trial]; a.k_ent0 = P.intr ? P.C + P.M : P.A;
     return a;
 }
 
-// trial >= 0: the frame back-substitution z[trial] = z[which] + delta may ride in the last tile's launch (systems of up to three
-// tiles); returns true if it did (the caller then skips launch_backsub)
-bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial) {
+void launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st) {
     const DeviceProblem::Blocks &b = P.blk[which];
     const size_t lds_diag = ((size_t)NB * (NB + 2) + 2 * NB * DG_YS + (size_t)NB * (NB / 2 + 2)) * sizeof(double);   // tile | panel | look-ahead half panel
     // block columns with at most this many tiles below the diagonal take the fused panel kernel (0: never); its redundancy grows
     // with the square of the column's height, the two-kernel path's fixed cost does not  (3: +2.6 % on a four-tile system, nothing at 14 tiles)
     const int fused_m = P.tune.fused_panel;
     const bool bs_rides = P.tune.bs_rides != 0;
-    // opt-in (AAR_BACKSUB_RIDES=1): measured on one box, it buys nothing -- 7 224 vs 7 233 LM it/s at config 3, 17 480 vs 17 780 at config 2
-    // (profiles/r03_attempts.txt): the launch then ends with the riders' work instead of a 6 us kernel, and their 1024-thread workgroups
-    // cost at dispatch what the kernel boundary did
-    const bool backsub_rides = P.tune.backsub_rides != 0;
     // Look-ahead: where trsm and update are launches of their own (tall block columns), the update is not launched: the next diagonal tile's
     // workgroup applies it to its own tile and starts factoring, riders of that launch do the other tiles (AAR_LDL_LOOKAHEAD=0: off)
     const bool lookahead = P.tune.lookahead != 0;
-    bool rode_backsub = false;
-    int upd_s = -1;   // the block column whose update the next k_ldl_diag launch carries
+    int upd_s = -1;  // the block column whose update the next k_ldl_diag launch carries
     for (int s = 0; s < P.nT; s++) {
         const int m = P.nT - s - 1;
         const bool last = s == P.nT - 1;
         const bool ride = bs_rides && last && (P.nT == 2 || P.nT == 3);   // the back-substitution rides in the last tile's launch
-        // ... and so does the frame back-substitution when the whole of delta_s comes out of that launch (one tile, or the rider above);
-        // not under per-kernel profiling (the riders would be billed to k_ldl_diag)
-        const bool ride2 = backsub_rides && last && trial >= 0 && (P.nT == 1 || ride) && !P.hook.pre;
-        BacksubArgs ba = backsub_args(P, which, trial >= 0 ? trial : which, DG_THREADS / 64);
-        if (ride || ride2) P.bs_epoch++;
-        const int grid = 1 + (ride ? 1 : 0) + (ride2 ? ba.n_frame_blocks + 1 : 0) + (upd_s >= 0 ? ldl_update_riders(P.nT - upd_s - 1) : 0);
+        if (ride) P.bs_epoch++;
+        const int grid = 1 + (ride ? 1 : 0) + (upd_s >= 0 ? ldl_update_riders(P.nT - upd_s - 1) : 0);
         { HookScope _h(P, KID_LDL_DIAG); launch_lds(k_ldl_diag, dim3(grid), dim3(DG_THREADS), lds_diag, st, b.S, P.Dfac, P.Linv16, P.n_pad, P.n, s, mu, P.ent_fixed, P.flags,
-                                                 P.nT, b.rhs, b.g0, P.delta_s, P.Lp, P.zf, fused_m, P.bs_flags, P.bs_epoch, ride ? 1 : 0, ride2 ? 1 : 0, ba,
+                                                 P.nT, b.rhs, b.g0, P.delta_s, P.Lp, P.zf, fused_m, P.bs_flags, P.bs_epoch, ride ? 1 : 0,
                                                  upd_s, b.S, b.rhs); }
         upd_s = -1;
-        rode_backsub = ride2;
         if (m > 0 && m <= fused_m) {   // short block column: panel solve and trailing update in one launch
             const int ns = NSB * m;
             HookScope _h(P, KID_LDL_PANEL);
@@ -1674,11 +1807,10 @@ bool launch_chol(const DeviceProblem &P, int which, double mu, hipStream_t st, i
         HookScope _h(P, KID_LDL_BACKSOLVE);
         launch_lds(k_ldl_backsolve, dim3(P.nT - 1), dim3(1024), lds, st, b.S, b.rhs, P.Dfac, P.delta_s, P.n_pad, P.nT, P.bs_flags, P.bs_epoch, P.flags, P.Lp, P.zf, fused_m);
     }
-    return rode_backsub;
 }
 
 void launch_backsub(const DeviceProblem &P, int cur, int trial, hipStream_t st) {
-    const BacksubArgs ba = backsub_args(P, cur, trial, 4);
+    const BacksubArgs ba = backsub_args(P, cur, trial);
     { HookScope _h(P, KID_BACKSUB); hipLaunchKernelGGL(k_backsub, dim3(ba.n_frame_blocks + 1), dim3(256), 0, st, ba); }
 }
 

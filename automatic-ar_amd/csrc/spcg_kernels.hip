@@ -31,21 +31,17 @@
 // and recurrences 560 -- and every piece of straight-line set-up code costs about one cycle per byte of instructions (the instruction cache is cold at every launch).
 //
 // Start-up.  Because once-run code costs its size, the default kernel is kept small and makes no avoidable round trip (profiles/spcg_startup.txt):
-//  * the back-substitution riders (AAR_SPCG_BACKSUB_RIDES=1, an experiment that lost) live in an instantiation of their own, k_spcg<NT, CO, true>, with their own
-//    arguments (SpcgRideArgs): the default k_spcg<NT, CO, false> carries neither backsub_body's 12.5 KB nor BacksubArgs;
 //  * which entities have identity rows arrives as bit words in the kernel arguments (SpcgArgs::fixed_mask), so the early exit, the reporting wavefront, the poll mask
 //    and the zeroed columns are scalar work and the loads of S / the assembled rows are the first memory operations a wavefront issues; the clearing of the other
 //    buffer set, whose bound is a load (iters[0]), comes behind them;
 //  * k_spcg<NT, false> up to SPCG_STAGE_MAX_NT tiles reads its rows in 16-byte pieces -- row part and column part of the lower triangle, both contiguous -- and
-//    turns them into the register layout through its own LDS; the diagonal block comes out of the same pieces.  Above that (and in the riding instantiations'
-//    larger shapes) the element-wise symmetric reads stay, with the row stride a compile-time constant (n_pad = 96 NT: the 64-bit address arithmetic was what
+//    turns them into the register layout through its own LDS; the diagonal block comes out of the same pieces.  Above that
+//    the element-wise symmetric reads stay, with the row stride a compile-time constant (n_pad = 96 NT: the 64-bit address arithmetic was what
 //    made the large instantiations spill);
 // (One copy of publish / gather / product for the start-up pass and the iterations was built too: the compiler then contracts the loop's products differently
 // and the bits change, so the start-up pass keeps its own copy.)  None of this touches the arithmetic: a solve returns the same bits for the same S (tests/test_gpu_spcg_startup.py, against the build before).
-#include <type_traits>
 #include "geom.hpp"
 #include "kernels.h"
-#include "backsub.hpp"
 #include "wave.hpp"
 
 namespace aar {
@@ -108,21 +104,11 @@ struct SpcgArgs {
     int root_c, root_m;               // the fixed entity whose slot carries the cameras' / markers' rigid-motion unknowns (-1: that group has none)
     int C, M;
 };
-// what the RIDING instantiation k_spcg<NT, CO, true> gets on top (AAR_SPCG_BACKSUB_RIDES=1, an experiment that measured slower: profiles/r05_attempts.txt section 8).
-// Riders: the workgroups of the grid that are NOT CG wavefronts do the frame back-substitution of the try (backsub.hpp) -- they fetch what does not depend
-// on delta_s (the frame's W blocks, g_f, V_f^-1) while the CG runs on the other XCD and wait for ONE flag, raised by the last CG wavefront to leave.
-// The default instantiation carries neither these arguments nor backsub_body's code.
-struct SpcgRideArgs : SpcgArgs {
-    int n_riders;
-    BacksubArgs bs;
-    int32_t *done;                    // [0] arrivals (monotonic over launches), [1] flag = done_epoch once all CG workgroups of this launch have left
-    int done_epoch;
-};
 
 typedef unsigned int sp_u32x4 __attribute__((ext_vector_type(4)));
 
-template <int NT, bool CO, bool RIDE>
-__global__ void __launch_bounds__(64) k_spcg(const std::conditional_t<RIDE, SpcgRideArgs, SpcgArgs> a) {
+template <int NT, bool CO>
+__global__ void __launch_bounds__(64) k_spcg(const SpcgArgs a) {
     // NL: 16-byte pieces of a buffer per lane (a buffer = 16 NT records of 64 bytes = 64 NT pieces); piece c = lane + 64 k belongs to record
     // c / 4 and holds its words 2 (lane % 4), 2 (lane % 4) + 1: lanes with lane % 4 < 3 gather entries of m, lanes with lane % 4 == 3 the two shares
     constexpr int NPAD = 96 * NT, NK = 6 * NT, NENT = 16 * NT, NL = NT, NEB = (NENT + 63) / 64;
@@ -135,27 +121,9 @@ __global__ void __launch_bounds__(64) k_spcg(const std::conditional_t<RIDE, Spcg
     // that all wavefronts of the solve share ONE XCD and its L2.  Whether they really do is checked at run time (every wavefront publishes its
     // XCC id in the first, placement-independent hand-over): if so, the later hand-overs keep their records in that L2 (sc0 stores; the sc1 loads
     // are L2-served) instead of sending every store out to the fabric and every poll after it -- a hand-over then costs an L2 round trip, not a memory one.
-    if (blockIdx.x % a.spread || (int)blockIdx.x >= NENT * a.spread) {
-        if constexpr (RIDE) {
-            if (blockIdx.x % 8 == 0) return;   // (position 0 mod 8 behind the CG range: the CG's XCD -- left alone)
-            __shared__ double red[32];
-            const int bx = (int)blockIdx.x, cg_range = NENT * a.spread;
-            const int rid = bx < cg_range ? bx - bx / a.spread - 1 : NENT * (a.spread - 1) + (bx - cg_range) - (bx - cg_range + 7) / 8;
-            for (int blk = rid; blk <= a.bs.n_frame_blocks; blk += a.n_riders) backsub_body(a.bs, blk, red, a.done + 1, a.done_epoch, a.flags);
-        }
-        return;
-    }
+    if (blockIdx.x % a.spread || (int)blockIdx.x >= NENT * a.spread) return;
     const int lane = threadIdx.x, e = blockIdx.x / a.spread, i = lane >> 3, g = lane & 7;
     SP_ENTRY();
-    auto leave = [&]() {   // this workgroup's entries of delta_s are on their way (agent-scope stores): drain them, arrive; the last one raises the riders' flag
-        if constexpr (RIDE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) {
-                const int old = __hip_atomic_fetch_add(a.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old + 1 == a.done_epoch * NENT) __hip_atomic_store(a.done + 1, a.done_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    };
     // identity rows: gauge / switched-off / held / padding entities (CO: a group's root carries the group's coarse unknowns -- its wavefront works, its record
     // is read like any other: the launcher has cleared its bit).  The word is picked by selects, never by an index: the mask stays in scalar registers
     auto fixed = [&](int ent) -> bool {
@@ -175,7 +143,6 @@ __global__ void __launch_bounds__(64) k_spcg(const std::conditional_t<RIDE, Spcg
     if (fixed(e)) {   // identity rows, zero right-hand side; nobody waits for this wavefront
         clear_other();
         if (lane < 6) sp_st(a.x_out + 6 * e + lane, 0.0);
-        leave();
         return;
     }
     if (e == a.test_drop) { clear_other(); return; }
@@ -542,7 +509,6 @@ __global__ void __launch_bounds__(64) k_spcg(const std::conditional_t<RIDE, Spcg
         if (pseudo) x = 0.0;
     }
     if (ra && g == 0) sp_st(a.x_out + row, x);
-    leave();
     if (lane == 0) {
         if (dead) atomicOr(a.flags, 4);
         if (status == 2 || status == 3) atomicOr(a.flags, 8);
@@ -730,8 +696,8 @@ int spcg_resident_per_cu(int nT, bool coarse) {
     int nb = 0;
     hipError_t rc = hipErrorInvalidValue;
     switch (nT) {
-#define SPCG_CASE(t) case t: { int nc = 1 << 30; if (coarse) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_spcg<t, true, false>, 64, 0); \
-                               if (!coarse || rc == hipSuccess) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_spcg<t, false, false>, 64, 0); nb = std::min(nb, nc); } break;
+#define SPCG_CASE(t) case t: { int nc = 1 << 30; if (coarse) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nc, k_spcg<t, true>, 64, 0); \
+                               if (!coarse || rc == hipSuccess) rc = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_spcg<t, false>, 64, 0); nb = std::min(nb, nc); } break;
         SPCG_CASE(1) SPCG_CASE(2) SPCG_CASE(3) SPCG_CASE(4) SPCG_CASE(5) SPCG_CASE(6) SPCG_CASE(7) SPCG_CASE(8)
         SPCG_CASE(9) SPCG_CASE(10) SPCG_CASE(11) SPCG_CASE(12) SPCG_CASE(13) SPCG_CASE(14)
 #undef SPCG_CASE
@@ -743,13 +709,10 @@ int spcg_resident_per_cu(int nT, bool coarse) {
 size_t spcg_ws_doubles(int n_pad) { return (size_t)2 * SPCG_BUFS * spcg_stride(n_pad); }
 void spcg_ws_reset(const DeviceProblem &P, hipStream_t st) {
     (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(P.spcg_ws), (int)0xFFF85EED, 2 * spcg_ws_doubles(P.n_pad), st);
-    (void)hipMemsetAsync(P.spcg_done, 0, 2 * sizeof(int32_t), st);   // the riders' arrival counter and flag start over
-    P.spcg_epoch = 0;
 }
 
 // delta_s of (S + mu I) delta_s = rhs + g0 by CG on the explicit reduced system of block set `which` (S is left as it is).
-// trial >= 0: the frame back-substitution z[trial] = z[which] + delta rides in the same launch (true is returned if it did: the caller then skips launch_backsub)
-bool launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st, int trial) {
+void launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st) {
     const DeviceProblem::Blocks &b = P.blk[which];
     SpcgArgs a;
     a.S = b.S; a.rhs = b.rhs; a.g0 = b.g0; a.n_pad = P.n_pad;
@@ -768,38 +731,15 @@ bool launch_spcg(const DeviceProblem &P, int which, double mu, hipStream_t st, i
     P.spcg_parity ^= 1;
     const int n_ent = P.n_pad / 6;
     const int grid = n_ent * a.spread;
-    // riders: only where the CG leaves seven XCDs idle anyway (which takes a system of at most SPCG_RIDE_MAX_NT tiles), and not when somebody wants the
-    // back-substitution's own time
-    const bool ride = trial >= 0 && P.tune.spcg_backsub_rides && a.spread >= 8 && P.nT <= SPCG_RIDE_MAX_NT && !P.hook.pre && P.F > 0;
     HookScope _h(P, KID_SPCG);
-    if (ride) {
-        SpcgRideArgs ar;
-        static_cast<SpcgArgs &>(ar) = a;
-        ar.bs = backsub_args(P, which, trial, 1);
-        ar.done = P.spcg_done; ar.done_epoch = ++P.spcg_epoch;
-        const int base = n_ent * (a.spread - 1), want = std::min(ar.bs.n_frame_blocks + 1, 4096);
-        int extra = 0;
-        if (base < want) extra = ((want - base) * 8 + 6) / 7;            // (every eighth block behind the CG range sits on the CG's XCD and is left alone)
-        ar.n_riders = base + extra - (extra + 7) / 8;
-        switch (P.nT) {
-#define SPCG_CASE(t) case t: if (coarse) hipLaunchKernelGGL((k_spcg<t, true, true>), dim3(grid + extra), dim3(64), 0, st, ar); \
-                             else hipLaunchKernelGGL((k_spcg<t, false, true>), dim3(grid + extra), dim3(64), 0, st, ar); break;
-            SPCG_CASE(1) SPCG_CASE(2) SPCG_CASE(3) SPCG_CASE(4) SPCG_CASE(5) SPCG_CASE(6) SPCG_CASE(7) SPCG_CASE(8)
-#undef SPCG_CASE
-            default: break;
-        }
-        static_assert(SPCG_RIDE_MAX_NT == 8, "one riding instantiation per tile count that can ride");
-        return true;
-    }
     switch (P.nT) {
-#define SPCG_CASE(t) case t: if (coarse) hipLaunchKernelGGL((k_spcg<t, true, false>), dim3(grid), dim3(64), 0, st, a); \
-                             else hipLaunchKernelGGL((k_spcg<t, false, false>), dim3(grid), dim3(64), 0, st, a); break;
+#define SPCG_CASE(t) case t: if (coarse) hipLaunchKernelGGL((k_spcg<t, true>), dim3(grid), dim3(64), 0, st, a); \
+                             else hipLaunchKernelGGL((k_spcg<t, false>), dim3(grid), dim3(64), 0, st, a); break;
         SPCG_CASE(1) SPCG_CASE(2) SPCG_CASE(3) SPCG_CASE(4) SPCG_CASE(5) SPCG_CASE(6) SPCG_CASE(7) SPCG_CASE(8)
         SPCG_CASE(9) SPCG_CASE(10) SPCG_CASE(11) SPCG_CASE(12) SPCG_CASE(13) SPCG_CASE(14)
 #undef SPCG_CASE
         default: break;   // (spcg_fits() is checked when the solver is chosen)
     }
-    return false;
 }
 
 void spcg_build_fixed_mask(DeviceProblem &P, const int32_t *ent_fixed_host) {

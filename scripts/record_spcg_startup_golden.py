@@ -34,9 +34,7 @@ def main():
         for coarse in (False, True):
             k = sc.key(name, coarse)
             mus, d, its, fb = sc.run(name, coarse, mus=old[k + "_mu"] if old else None)
-            _, dr, itr, fbr = sc.run(name, coarse, rides=True, mus=mus)
-            rides_equal = bool(np.array_equal(d.view(np.int64), dr.view(np.int64)) and np.array_equal(its, itr))
-            print("%-22s mu %.6e %.6e  iterations %s  fallbacks %d | riders: equal bits %s, fallbacks %d" % (k, mus[0], mus[1], its.tolist(), fb, rides_equal, fbr), flush=True)
+            print("%-22s mu %.6e %.6e  iterations %s  fallbacks %d" % (k, mus[0], mus[1], its.tolist(), fb), flush=True)
             if old:
                 same = np.array_equal(d.view(np.int64), old[k + "_delta"].view(np.int64)) and np.array_equal(its, old[k + "_its"])
                 print("    against the file: %s (max |diff| %.3e)" % ("equal bits" if same else "DIFFERENT", np.abs(d - old[k + "_delta"]).max()), flush=True)

@@ -164,11 +164,10 @@ def ldl_expected(nT, fused, lookahead, bs_rides):
     return dict(k_ldl_diag=nT, k_ldl_panel=panel, k_ldl_trsm=trsm, k_ldl_update=update, k_ldl_backsolve=back)
 
 
-def ldl_env(monkeypatch, fused=3, lookahead=1, bs_rides=1, backsub_rides=0):
+def ldl_env(monkeypatch, fused=3, lookahead=1, bs_rides=1):
     monkeypatch.setenv("AAR_FUSED_PANEL", str(fused))
     monkeypatch.setenv("AAR_LDL_LOOKAHEAD", str(lookahead))
     monkeypatch.setenv("AAR_BS_RIDES", str(bs_rides))
-    monkeypatch.setenv("AAR_BACKSUB_RIDES", str(backsub_rides))
 
 
 def run_ranks(world, fn):

@@ -59,11 +59,11 @@ def fixed_sets(ds, name):
     return dict(fixed_cams=[cam], fixed_markers=[marker])
 
 
-def run(name, coarse, rides=False, mus=None):
+def run(name, coarse, mus=None):
     """(mu [2], delta [2][num_vars], last_iterations [2], fallbacks) of the two one-off steps; mus: take these dampings instead of the run's own"""
     ds = dataset(name)
     # the library reads its switches when the problem is created
-    with _env(AAR_SPCG_COARSE_FROM="0" if coarse else "100000", AAR_SPCG_BACKSUB_RIDES="1" if rides else None):
+    with _env(AAR_SPCG_COARSE_FROM="0" if coarse else "100000"):
         p = aar.Problem(ds, solver="spcg", deterministic=True, **fixed_sets(ds, name))
     with p:
         assert p.solver_stats()["solver"] == "spcg"

@@ -113,7 +113,7 @@ def test_ldl_launch_structures(nT, fused, lookahead, monkeypatch):
     with _problem(ds) as p:
         _certify("ldl structures", "sweep%d" % nT, p, ds, what="fused %d lookahead %d" % (fused, lookahead))
         if (fused, lookahead) in ((2, 1), (0, 0)):
-            # premise: the intended kernels ran (profiled in a step of its own: the frame back-substitution does not ride under the profiler)
+            # premise: the intended kernels ran
             cnt = _launch_counts(p, ds, _SYS["sweep%d" % nT][1])
             want = _ldl_expected(nT, fused, lookahead, 1)
             k = cnt["k_ldl_diag"] // nT
@@ -128,14 +128,6 @@ def test_ldl_back_substitution_as_its_own_launch(nT, monkeypatch):
         _certify("ldl structures", "sweep%d" % nT, p, ds, what="AAR_BS_RIDES=0")
         cnt = _launch_counts(p, ds, _SYS["sweep%d" % nT][1])
         assert cnt["k_ldl_backsolve"] == cnt["k_ldl_diag"] // nT >= 1, cnt
-
-
-@pytest.mark.parametrize("nT", [1, 2, 3])
-def test_frame_back_substitution_riding_in_the_last_tile(nT, monkeypatch):
-    _ldl_env(monkeypatch, backsub_rides=1)
-    ds = dc.sweep_ds(nT)
-    with _problem(ds) as p:
-        _certify("ldl structures", "sweep%d" % nT, p, ds, what="AAR_BACKSUB_RIDES=1")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

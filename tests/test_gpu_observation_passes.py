@@ -14,11 +14,11 @@ mu = 1e-2 max diag(H_ref): the device's H agrees with the reference to ~1e-13 of
 <= ~1e4 turns that into <= 1e-9 of the step -- ten times inside the bar, so the step test sees the blocks and not the conditioning.
 
 Which kernel instance each combination launches (launch_passA_t<B, CPL> picks among k_passA / k_passA_intr / k_passAB / k_passAB_o2 /
-k_passAB_intr; launch_passB among k_passB<wrench> / k_passB_lean1 / k_passB_lean2 / k_passB_det + k_passB_reduce / k_passB_intr /
+k_passAB_intr; launch_passB among k_passB<wrench> / k_passB_det + k_passB_reduce / k_passB_intr /
 k_passB_intr_det) is listed in the docstring of the test that reaches it.  The launch counts of kernel_times tell a merged launch from
 separate ones; they do not tell WHICH template instance ran (all of pass A's share one counter), so a switch the launcher ignores is seen
 only through the docstrings' reading of launch_passA_any / launch_passA_t: AAR_PASSA_VARIANT is ignored in deterministic mode above 96
-observations per frame, AAR_PASSAB_OCC2 and AAR_PASSB_WRENCH_MERGED with intrinsics.
+observations per frame, AAR_PASSAB_OCC2 with intrinsics.
 
 NOT covered here: what pass A writes for the NEXT solve -- (V_f + mu I)^-1 and h_f, and with the MFMA Schur kernel the dense panels W,
 Y = W (V_f + mu I)^-1 (passA_epilogue and its wrench twin).  It is written only when the LM loop evaluates a trial point with a predicted
@@ -31,8 +31,8 @@ MEASURED on an MI355X (largest over each test's combinations; H and B relative t
   edge poses (25 data sets x 20 problems):  H 4.2e-15 (theta = 0.01 + 1e-6; elsewhere <= 1.7e-15), B 2.2e-13 (double mode), rows 4.6e-13 px,
                                             damped step 2.5e-11, scaled measure 9.5e-13 (deterministic, the -board sets; others 2.6e-13 .. 7.7e-13)
   other chart (g1_cfg2 + 2 pi):             H 6.5e-16, B 4.8e-15, rows 6.8e-13 px, step 1.0e-12, scaled 5.5e-15
-  pass A shapes (89 + 65 problems):         H 1.0e-15, B 3.6e-14, rows 4.6e-13 px, step 1.4e-11, scaled 1.03e-12 (wrench form, separate launches)
-  pass B chunks (4 modes, 24 .. 42 each):   H 9.4e-16, B 5.1e-14, rows 3.4e-13 px, step 3.3e-11 (intrinsics), scaled 9.95e-13
+  pass A shapes (51 + 41 problems):         H 1.0e-15, B 3.6e-14, rows 4.6e-13 px, step 1.4e-11, scaled 1.03e-12 (wrench form, separate launches)
+  pass B chunks (4 modes, 24 each):         H 9.4e-16, B 5.1e-14, rows 3.4e-13 px, step 3.3e-11 (intrinsics), scaled 9.95e-13
   both passes, P = 6642, chunks of 512:     H 1.6e-15, B 1.6e-14, rows 2.3e-13 px, scaled 5.2e-13
   config 5, 1.26 M observations, frames off: H 2.3e-15, B 1.4e-14, rows 1.0e-12 px, step 5.0e-14, scaled 9.9e-13
   config 5, first 200 frames:               H 2.1e-15, B 1.4e-14, rows 9.1e-13 px, step 5.9e-14, scaled 2.8e-15
@@ -53,8 +53,8 @@ pytestmark = pytest.mark.gpu
 
 H_BAR, B_BAR, ROW_BAR, STEP_BAR = 1e-12, 1e-11, 1e-9, 1e-8
 ALL, FRAMES_ONLY, SHARED_ONLY = (True, True, True), (False, False, True), (True, True, False)
-PASSA_ENV = ("AAR_PASSA_VARIANT", "AAR_PASSA_WRENCH", "AAR_MERGE_PASSES", "AAR_PASSAB_OCC2", "AAR_PASSB_WRENCH_MERGED", "AAR_SCHUR_MFMA",
-             "AAR_DENSE_FROM_PASSA", "AAR_PASSB_CHUNK", "AAR_PASSB_LEAN")
+PASSA_ENV = ("AAR_PASSA_VARIANT", "AAR_PASSA_WRENCH", "AAR_MERGE_PASSES", "AAR_PASSAB_OCC2", "AAR_SCHUR_MFMA",
+             "AAR_DENSE_FROM_PASSA", "AAR_PASSB_CHUNK")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -199,7 +199,7 @@ def test_other_chart_and_the_series_switch(monkeypatch):
 # ------------------------------------------------------------------------------------------------ b. pass A shapes
 FRAME_COUNTS = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 320]   # 320 = 8 x 40: every camera and marker in one frame
 VARIANTS = {None: "<128, 4> (100.6 observations per frame on average: above 96)", 641: "<64, 1>", 642: "<64, 2>", 644: "<64, 4>",
-            1281: "<128, 1>", 1282: "<128, 2>", 1284: "<128, 4>", 2564: "<256, 4>"}
+            1284: "<128, 4>"}
 
 
 @pytest.mark.parametrize("intrinsics", [False, True], ids=["poses", "intrinsics"])
@@ -208,18 +208,16 @@ def test_pass_a_workgroup_shapes(intrinsics, monkeypatch):
     (max_kf from 2 entities up to all 8 cameras + 40 markers in one frame; 1811 / 18 = 100.6 per frame, so the size rule itself picks
     launch_passA_t<128, 4>), under
 
-      AAR_PASSA_VARIANT unset -> <128, 4>, 641 -> <64, 1>, 642 -> <64, 2>, 644 -> <64, 4>, 1281 -> <128, 1>, 1282 -> <128, 2>, 1284 -> <128, 4>,
-      2564 -> <256, 4>                                                                       (launch_passA_any)
+      AAR_PASSA_VARIANT unset -> <128, 4>, 641 -> <64, 1>, 642 -> <64, 2>, 644 -> <64, 4>, 1284 -> <128, 4>                   (launch_passA_any)
       x AAR_PASSA_WRENCH 1 / 0                                                               (the WR template argument: wrench form / row form)
       x AAR_MERGE_PASSES 1 / 0 with all groups on:
-          merged, poses:      k_passAB<B, CPL, true, false> (wrench A, row-form B: the default), k_passAB<B, CPL, false> (row form)
+          merged, poses:      k_passAB<B, CPL, true> (wrench A, row-form B: the default), k_passAB<B, CPL, false> (row form)
           merged, intrinsics: k_passAB_intr<B, CPL, true / false>
           separate:           k_passA<B, CPL, true / false> or k_passA_intr<..>, then k_passB<true / false> (+ k_passB_intr)
         asserted from the launch counts of set_kernel_profiling / kernel_times: merged -> no k_passB launch, separate -> both
       x frames-only problems (optimize = (False, False, True)): H is exactly pass A's V_f, B its g_f
-    plus, merged and in wrench form: AAR_PASSAB_OCC2=1 -> k_passAB_o2<B, CPL>, AAR_PASSAB_OCC2=0 -> k_passAB<B, CPL, true, false>,
-    AAR_PASSB_WRENCH_MERGED=1 -> k_passAB<B, CPL, true, true> (poses only: with intrinsics all three launch the same
-    k_passAB_intr<B, CPL, true>, so they are not repeated there).
+    plus, merged and in wrench form: AAR_PASSAB_OCC2=1 -> k_passAB_o2<B, CPL>, AAR_PASSAB_OCC2=0 -> k_passAB<B, CPL, true>
+    (poses only: with intrinsics both launch the same k_passAB_intr<B, CPL, true>, so they are not repeated there).
     With AAR_SCHUR_MFMA=1 the one-off entry points run k_schur_fill + the MFMA Schur kernel behind eval_damped_step (per variant and form);
     pass A's own panel writer is not reached that way (see the module docstring)."""
     ds = pr.frame_counts_dataset(FRAME_COUNTS)
@@ -233,7 +231,7 @@ def test_pass_a_workgroup_shapes(intrinsics, monkeypatch):
                 assert nA >= 1 and (nB == 0 if merge else nB >= 1), (tag, nA, nB)      # merged: pass B's chunks rode in pass A's launch
                 if merge:       # (frames only: nothing of pass B reaches H; one launch form is enough)
                     _compare(ref, worst, tag + " frames-only", optimize=FRAMES_ONLY, intrinsics=intrinsics, rows=False)
-        for extra in (() if intrinsics else (dict(AAR_PASSAB_OCC2=1), dict(AAR_PASSAB_OCC2=0), dict(AAR_PASSB_WRENCH_MERGED=1))):
+        for extra in (() if intrinsics else (dict(AAR_PASSAB_OCC2=1), dict(AAR_PASSAB_OCC2=0))):
             _set_env(monkeypatch, AAR_PASSA_VARIANT=variant, AAR_PASSA_WRENCH=1, AAR_MERGE_PASSES=1, **extra)
             nA, nB = _compare(ref, worst, "variant=%s %s" % (variant, extra), intrinsics=intrinsics, profile=True, rows=False)
             assert nA >= 1 and nB == 0
@@ -256,10 +254,9 @@ def test_pass_b_chunks(mode, monkeypatch):
     13 (camera, marker) runs are 63, 64, 65, 127, 128, 129, 511, 512, 513, 1023, 1024, 1025 and 2049 observations long (N = 7233, 2049 frames).
     AAR_PASSB_CHUNK unset (64: N < 131 072) / 64 / 128 / 256 / 512 / 1024: 1 .. 16 observations per lane, runs that end one short of, at and
     one past a chunk's end.
-      atomic, AAR_MERGE_PASSES=0:  k_passB<true> (wrench), k_passB<false> (AAR_PASSA_WRENCH=0), AAR_PASSB_LEAN=1 -> k_passB_lean2,
-                                   AAR_PASSB_LEAN=2 -> k_passB_lean1
-      atomic, merged (default):    the chunks ride in k_passAB<64, 1, true, false> (7233 / 2049 = 3.5 observations per frame: <64, 1>);
-                                   AAR_PASSB_WRENCH_MERGED=1 -> k_passAB<64, 1, true, true>; AAR_PASSA_WRENCH=0 -> k_passAB<64, 1, false>
+      atomic, AAR_MERGE_PASSES=0:  k_passB<true> (wrench), k_passB<false> (AAR_PASSA_WRENCH=0)
+      atomic, merged (default):    the chunks ride in k_passAB<64, 1, true> (7233 / 2049 = 3.5 observations per frame: <64, 1>);
+                                   AAR_PASSA_WRENCH=0 -> k_passAB<64, 1, false>
       deterministic:               k_passB_det<true / false> + k_passB_reduce (never merged)
       intrinsics:                  separate k_passB<..> + k_passB_intr; merged k_passAB_intr<64, 1, ..>
       intrinsics_deterministic:    k_passB_det + k_passB_intr_det + k_passB_reduce
@@ -275,19 +272,13 @@ def test_pass_b_chunks(mode, monkeypatch):
                 nA, nB = _compare(ref, worst, tag, optimize=SHARED_ONLY, intrinsics=intr, det=det, profile=True, rows=(chunk is None and merge == 1 and wrench == 1))
                 merged = merge == 1 and not det
                 assert nA >= 1 and (nB == 0 if merged else nB >= 1), (tag, nA, nB)
-            if mode == "atomic":
-                extras = [dict(AAR_PASSB_WRENCH_MERGED=1)] if merge else [dict(AAR_PASSB_LEAN=1), dict(AAR_PASSB_LEAN=2)]
-                for extra in extras:
-                    _set_env(monkeypatch, AAR_PASSB_CHUNK=chunk, AAR_MERGE_PASSES=merge, AAR_PASSA_WRENCH=1, **extra)
-                    nA, nB = _compare(ref, worst, "%s chunk=%s merge=%d %s" % (mode, chunk, merge, extra), optimize=SHARED_ONLY, profile=True, rows=False)
-                    assert nB == 0 if merge else nB >= 1
     _report("pass B chunks, " + mode, worst)
 
 
 def test_passes_tied_together_at_a_long_chunk(monkeypatch):
     """All groups on, 1100 frames, runs up to 1025 observations, AAR_PASSB_CHUNK=512: P = 6642 (a dense H of 353 MB: this one case only).
     Pass A (k_passA<64, 1, true>) and pass B (k_passB<true>, up to 8 observations per lane) as launches of their own, and the same merged
-    (k_passAB<64, 1, true, false>)."""
+    (k_passAB<64, 1, true>)."""
     ds = pr.run_lengths_dataset(RUN_LENGTHS[:-1], F=1100)
     ref, worst = Ref(ds), {}
     for merge in (0, 1):

@@ -417,7 +417,7 @@ def test_gauge_rows_in_trailing_tiles_of_a_three_tile_system(opt):
 
 
 @pytest.mark.parametrize("env", [{"AAR_FUSED_PANEL": "0"}, {"AAR_BS_RIDES": "0"}, {"AAR_FUSED_PANEL": "0", "AAR_BS_RIDES": "0"}, {"AAR_FUSED_PANEL": "5"}, {"AAR_FUSED_PANEL": "2"},
-                                 {"AAR_BACKSUB_RIDES": "1"}, {"AAR_DENSE_FROM_PASSA": "0", "AAR_SCHUR_MFMA": "1"}, {"AAR_LDL_LOOKAHEAD": "0"},
+                                 {"AAR_DENSE_FROM_PASSA": "0", "AAR_SCHUR_MFMA": "1"}, {"AAR_LDL_LOOKAHEAD": "0"},
                                  {"AAR_LDL_LOOKAHEAD": "0", "AAR_FUSED_PANEL": "0"}, {"AAR_INIT_HEADSTART": "0"}])
 def test_dense_solve_path_switches(env):
     # The dense LDL^T has alternative launch structures behind environment switches that libaar reads ONCE per process (the
@@ -1238,16 +1238,15 @@ def test_observation_passes_wrench_form_equals_row_form(shape, monkeypatch):
         kw = dict(intrinsics=True)
     x_eval = None
     out = {}
-    for form in ("1", "1b", "0"):   # "1": the default (inside the merged launch of a small problem pass B's chunks stay in row form); "1b": wrench form there too
-        monkeypatch.setenv("AAR_PASSA_WRENCH", form[0])
-        monkeypatch.setenv("AAR_PASSB_WRENCH_MERGED", "1" if form == "1b" else "0")
+    for form in ("1", "0"):   # "1": the default (inside the merged launch of a small problem pass B's chunks stay in row form)
+        monkeypatch.setenv("AAR_PASSA_WRENCH", form)
         for det in (False, True):
             with Problem(ds, deterministic=det, solver="direct", **kw) as p:
                 x_eval = p.x_with_intrinsics(ds.x_full) if kw.get("intrinsics") else ds.x_full
                 H, B, ss = p.eval_normal_equations(x_eval)
                 d = p.eval_damped_step(x_eval, 1e2)
             out[form, det] = (H, B, ss, d)
-    for det, form in ((False, "1"), (True, "1"), (False, "1b"), (True, "1b")):
+    for det, form in ((False, "1"), (True, "1")):
         (H1, B1, s1, d1), (H0, B0, s0, d0) = out[form, det], out["0", det]
         assert np.abs(H1 - H0).max() / np.abs(H0).max() < 1e-13
         assert np.abs(B1 - B0).max() / np.abs(B0).max() < 1e-12
@@ -1255,7 +1254,6 @@ def test_observation_passes_wrench_form_equals_row_form(shape, monkeypatch):
         assert np.abs(d1 - d0).max() / np.abs(d0).max() < 1e-8        # (the small problem is the ill-conditioned one: 1.5e-9; the others 1e-11)
     # the deterministic mode of the wrench form gives the same bits twice
     monkeypatch.setenv("AAR_PASSA_WRENCH", "1")
-    monkeypatch.setenv("AAR_PASSB_WRENCH_MERGED", "0")
     with Problem(ds, deterministic=True, solver="direct", **kw) as p:
         H, B, ss = p.eval_normal_equations(x_eval)
     assert np.array_equal(H, out["1", True][0]) and np.array_equal(B, out["1", True][1]) and ss == out["1", True][2]

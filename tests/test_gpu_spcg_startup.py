@@ -1,5 +1,5 @@
-"""k_spcg's set-up (csrc/spcg_kernels.hip: the mask of fixed entities in the kernel arguments, the rows of S read in 16-byte pieces, the riders in an
-instantiation of their own) computes what the set-up before it computed, to the last bit.  Needs a real MI355X.
+"""k_spcg's set-up (csrc/spcg_kernels.hip: the mask of fixed entities in the kernel arguments, the rows of S read in 16-byte pieces)
+computes what the set-up before it computed, to the last bit.  Needs a real MI355X.
 
 tests/golden/spcg_startup_parent.npz was recorded by scripts/record_spcg_startup_golden.py from the build of the commit before the rework; the cases
 (tests/spcg_startup_cases.py) are the smallest shapes at which the set-up takes each of its paths, each with block-Jacobi (k_spcg<NT, false>) and with
@@ -29,16 +29,6 @@ def golden():
     return dict(np.load(os.path.join(GOLDEN, sc.GOLDEN_FILE)))
 
 
-_default = {}   # (case, coarse) -> the default path's result, computed once and shared by the two tests below
-
-
-def _default_run(name, coarse, golden):
-    k = (name, coarse)
-    if k not in _default:
-        _default[k] = sc.run(name, coarse, mus=golden[sc.key(name, coarse) + "_mu"])
-    return _default[k]
-
-
 def _bits(a):
     return np.ascontiguousarray(a).view(np.int64)
 
@@ -47,7 +37,7 @@ def _bits(a):
 @pytest.mark.parametrize("name", list(sc.CASES))
 def test_step_equals_the_parent_builds_bits(name, coarse, golden):
     k = sc.key(name, coarse)
-    mus, d, its, fb = _default_run(name, coarse, golden)
+    mus, d, its, fb = sc.run(name, coarse, mus=golden[k + "_mu"])
     g = golden[k + "_delta"]
     print("%s: iterations %s (golden %s), fall-backs %d, differing entries %d of %d, max |diff| %.3e"
           % (k, its.tolist(), golden[k + "_its"].tolist(), fb, int((_bits(d) != _bits(g)).sum()), d.size, np.abs(d - g).max()))
@@ -55,15 +45,3 @@ def test_step_equals_the_parent_builds_bits(name, coarse, golden):
     assert np.array_equal(its, golden[k + "_its"])          # (a) the same iteration counts ...
     assert d.shape == g.shape and np.array_equal(_bits(d), _bits(g))   # ... and the same bits
     assert np.abs(d).max() > 0.0
-
-
-@pytest.mark.parametrize("coarse", [False, True], ids=["block_jacobi", "coarse"])
-@pytest.mark.parametrize("name", list(sc.CASES))
-def test_riding_back_substitution_equals_the_default_path(name, coarse, golden):
-    # AAR_SPCG_BACKSUB_RIDES=1: the frame back-substitution rides in k_spcg's launch (the riding instantiation) wherever the launcher lets it
-    mus, d, its, fb = _default_run(name, coarse, golden)
-    _, dr, itr, fbr = sc.run(name, coarse, rides=True, mus=mus)
-    print("%s riders: iterations %s (default %s), fall-backs %d, differing entries %d" % (sc.key(name, coarse), itr.tolist(), its.tolist(), fbr, int((_bits(d) != _bits(dr)).sum())))
-    assert fbr == 0
-    assert np.array_equal(itr, its)
-    assert np.array_equal(_bits(dr), _bits(d))
