@@ -39,7 +39,7 @@ SYMBOLS = [
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
-    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_covariance",
+    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_system2", "aar_smooth_solve_launches", "aar_track_smooth_covariance",
     "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms",
     "aar_smooth_query_validate", "aar_track_smooth_query",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
@@ -235,6 +235,15 @@ class CSmoothParams(C.Structure):
                 ("frame_time", C.POINTER(C.c_double)), ("rel_motion", C.POINTER(C.c_double))]
 
 
+class CSmoothParamsV2(C.Structure):
+    """aar_smooth_params with the motion model (CSmoothParams stays the struct as it was before the model: a caller built against it)"""
+    _fields_ = CSmoothParams._fields_ + [("model", C.c_int32), ("sigma_rot0", C.c_double), ("sigma_trans0", C.c_double)]
+
+
+SMOOTH_MODEL_RANDOM_WALK, SMOOTH_MODEL_CONSTANT_VELOCITY = 0, 1
+_SMOOTH_MODELS = {"rw": 0, "random_walk": 0, "cv": 1, "constant_velocity": 1}
+
+
 class CSmoothReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("stop_code", C.c_int32), ("rejected_tries", C.c_int32),
                 ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_data_cost", C.c_double),
@@ -255,11 +264,18 @@ class CSmoothQueryReport(C.Structure):
 class SmoothParams:
     """aar_smooth_params built from Python values (the arrays are kept alive with the struct)"""
 
-    def __init__(self, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, struct_size=None):
+    def __init__(self, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, struct_size=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
+        """model: None = the struct without the model fields (40 bytes: the random walk); "rw" / "cv" or an AAR_SMOOTH_MODEL_* value = the
+        struct with them, sigma_rot0 / sigma_trans0 being pair 0's sigmas under "cv" """
         self._ft = None if frame_time is None else np.ascontiguousarray(frame_time, dtype=np.float64).reshape(-1)
         self._rm = None if rel_motion is None else np.ascontiguousarray(rel_motion, dtype=np.float64).reshape(-1)
-        c = CSmoothParams()
-        c.struct_size = C.sizeof(CSmoothParams) if struct_size is None else int(struct_size)
+        if model is None:
+            c = CSmoothParams()
+        else:
+            c = CSmoothParamsV2()
+            c.model = _SMOOTH_MODELS[model] if isinstance(model, str) else int(model)
+            c.sigma_rot0, c.sigma_trans0 = float(sigma_rot0), float(sigma_trans0)
+        c.struct_size = C.sizeof(c) if struct_size is None else int(struct_size)
         c.sigma_rot, c.sigma_trans = float(sigma_rot), float(sigma_trans)
         c.frame_time = None if self._ft is None else self._ft.ctypes.data_as(C.POINTER(C.c_double))
         c.rel_motion = None if self._rm is None else self._rm.ctypes.data_as(C.POINTER(C.c_double))
@@ -270,12 +286,17 @@ class SmoothParams:
         assert self._rm is None or len(self._rm) == 6 * max(num_frames - 1, 0)
 
 
-def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, struct_size=None):
+def smooth_params_validate(num_frames, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, struct_size=None, **model):
     """aar_smooth_params_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  struct_size overrides the
     struct's own size (versioning tests)."""
-    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size)
+    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size, **model)
     sp.check_lengths(num_frames)
     _check(lib().aar_smooth_params_validate(int(num_frames), C.byref(sp.c)))
+
+
+def smooth_solve_launches(num_frames, model="rw"):
+    """aar_smooth_solve_launches (host code): kernel launches of one damped solve of the smoother at this size"""
+    return int(lib().aar_smooth_solve_launches(int(num_frames), _SMOOTH_MODELS[model] if isinstance(model, str) else int(model)))
 
 
 def smooth_query_validate(num_frames, sigma_rot, sigma_trans, query_time, frame_time=None, rel_motion=None, struct_size=None):
@@ -517,19 +538,22 @@ def lib():
     L.aar_kernel_name.argtypes = [C.c_int]
     L.aar_kernel_name.restype = C.c_char_p
     L.aar_track.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(C.c_int32), dp]
-    L.aar_smooth_params_validate.argtypes = [C.c_int32, C.POINTER(CSmoothParams)]
-    L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothReport)]
-    L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_double, dp, dp, dp, dp, dp]
-    L.aar_track_smooth_covariance.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), dp, dp, C.POINTER(CSmoothCovarianceReport)]
-    L.aar_smooth_query_validate.argtypes = [C.c_int32, C.POINTER(CSmoothParams), C.c_int64, dp]
-    L.aar_track_smooth_query.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), C.c_int64, dp, dp, dp, C.POINTER(C.c_int32),
+    L.aar_smooth_params_validate.argtypes = [C.c_int32, C.c_void_p]
+    L.aar_track_smooth.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.c_void_p, dp, dp, C.POINTER(CSmoothReport)]
+    L.aar_track_smooth_system.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_double, dp, dp, dp, dp, dp]
+    L.aar_smooth_solve_launches.argtypes = [C.c_int32, C.c_int32]
+    L.aar_smooth_solve_launches.restype = C.c_int32
+    L.aar_track_smooth_system2.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_double, dp, dp, dp, dp, dp, dp]
+    L.aar_track_smooth_covariance.argtypes = [C.c_void_p, dp, C.c_void_p, dp, dp, C.POINTER(CSmoothCovarianceReport)]
+    L.aar_smooth_query_validate.argtypes = [C.c_int32, C.c_void_p, C.c_int64, dp]
+    L.aar_track_smooth_query.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, dp, dp, dp, C.POINTER(C.c_int32),
                                          C.POINTER(CSmoothQueryReport)]
     L.aar_smooth_fit_default_params.argtypes = [C.POINTER(CSmoothFitParams)]
     L.aar_smooth_fit_default_params.restype = None
     L.aar_smooth_fit_params_validate.argtypes = [C.POINTER(CSmoothFitParams)]
-    L.aar_track_smooth_fit.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.POINTER(CSmoothParams), C.POINTER(CSmoothFitParams), dp,
+    L.aar_track_smooth_fit.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.c_void_p, C.POINTER(CSmoothFitParams), dp,
                                        C.POINTER(CSmoothFitReport)]
-    L.aar_track_smooth_fit_terms.argtypes = [C.c_void_p, dp, C.POINTER(CSmoothParams), dp, dp]
+    L.aar_track_smooth_fit_terms.argtypes = [C.c_void_p, dp, C.c_void_p, dp, dp]
     L.aar_tracker_default_params.argtypes = [C.POINTER(CTrackerParams)]
     L.aar_tracker_default_params.restype = None
     L.aar_tracker_params_validate.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerParams)]
@@ -1666,12 +1690,12 @@ class Problem:
                                it.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(err)))
         return x, it, err
 
-    def track_smooth(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None):
+    def track_smooth(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth: every frame's pose with a motion prior between consecutive frames, one joint LM on the device.  Returns
         (x_full with the smoothed frame poses, report dict, frame_err [F] = E_f, pair_err [F-1] = e_f^T L_f e_f)."""
         x = np.array(self._x(x_full), dtype=np.float64)
         F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
         sp.check_lengths(F)
         fe, pe = np.zeros(max(F, 1)), np.zeros(max(F - 1, 1))
         rep = CSmoothReport()
@@ -1681,11 +1705,11 @@ class Problem:
         report = {k: getattr(rep, k) for k, _ in CSmoothReport._fields_ if k != "struct_size"}
         return x, report, fe[:F], pe[:max(F - 1, 0)]
 
-    def track_smooth_system(self, x_full, sigma_rot, sigma_trans, mu, frame_time=None, rel_motion=None):
+    def track_smooth_system(self, x_full, sigma_rot, sigma_trans, mu, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_system: (diag [F, 6, 6], off [F-1, 6, 6], rhs [6F], delta [6F], (data cost, prior cost)) of one try at x_full"""
         x = self._x(x_full)
         F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
         sp.check_lengths(F)
         diag, off = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6))
         rhs, delta, cost = np.zeros(6 * max(F, 1)), np.zeros(6 * max(F, 1)), np.zeros(2)
@@ -1693,12 +1717,25 @@ class Problem:
                                              _dptr(delta), _dptr(cost)))
         return diag[:F], off[:max(F - 1, 0)], rhs[:6 * F], delta[:6 * F], (cost[0], cost[1])
 
-    def track_smooth_covariance(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None):
+    def track_smooth_system2(self, x_full, sigma_rot, sigma_trans, mu, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_system2, either model: (diag [F, 6, 6], off [F-1, 6, 6], off2 [F-2, 6, 6], rhs [6F], delta [6F], (data cost, prior
+        cost)) of one try at x_full; off2 is zero under the random walk"""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(F)
+        diag, off, off2 = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6)), np.zeros((max(F - 2, 1), 6, 6))
+        rhs, delta, cost = np.zeros(6 * max(F, 1)), np.zeros(6 * max(F, 1)), np.zeros(2)
+        _check(lib().aar_track_smooth_system2(self.handle, _dptr(x), C.byref(sp.c), float(mu), _dptr(diag), _dptr(off), _dptr(off2), _dptr(rhs),
+                                              _dptr(delta), _dptr(cost)))
+        return diag[:F], off[:max(F - 1, 0)], off2[:max(F - 2, 0)], rhs[:6 * F], delta[:6 * F], (cost[0], cost[1])
+
+    def track_smooth_covariance(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_covariance: (frame_cov [F, 6, 6] = (H^-1)_ff, lag_cov [F-1, 6, 6] = (H^-1)_{f,f+1}, report dict) at x_full, H the
         matrix of track_smooth_system at mu = 0.  Both UNSCALED: multiply by report["sigma2"]."""
         x = self._x(x_full)
         F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
         sp.check_lengths(F)
         fc, lc = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6))
         rep = CSmoothCovarianceReport()
@@ -1707,13 +1744,13 @@ class Problem:
         report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
         return fc[:F], lc[:max(F - 1, 0)], report
 
-    def track_smooth_fit(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None):
+    def track_smooth_fit(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit: the pixel noise and the motion sigmas fitted to the sequence by EM, from the effective start values
         sigma_rot, sigma_trans.  fit: None (the defaults), a dict of aar_smooth_fit_params fields, or a CSmoothFitParams.  Returns (x_full with
         the track at the fitted values, report dict, path [iterations + 1, 3] = (sigma_px, sigma_rot, sigma_trans) per iteration).  Hand
         report["sigma_rot_eff"], report["sigma_trans_eff"] to track_smooth / tracker_params."""
         x = np.array(self._x(x_full), dtype=np.float64)
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
         sp.check_lengths(self.ds.num_frames)
         fp = fit if isinstance(fit, CSmoothFitParams) else smooth_fit_params(**(fit or {}))
         path = np.zeros((max(int(fp.max_iters), 0) + 1, 3))
@@ -1724,22 +1761,22 @@ class Problem:
         report = {k: getattr(rep, k) for k, _ in CSmoothFitReport._fields_ if k != "struct_size"}
         return x, report, path[:report["iterations"] + 1]
 
-    def track_smooth_fit_terms(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None):
+    def track_smooth_fit_terms(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit_terms: one E-step at x_full and the given effective sigmas, no smoothing.  Returns (pair_terms [F-1, 4] =
         a_r, u_r, a_t, u_t, sums [4] = A_r, U_r, A_t, U_t)."""
         x = self._x(x_full)
         F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
         sp.check_lengths(F)
         terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(4)
         _check(lib().aar_track_smooth_fit_terms(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
         return terms[:max(F - 1, 0)], sums
 
-    def track_smooth_query(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True):
+    def track_smooth_query(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_query: the smoothed track at the times query_time [Q] (any order, duplicates allowed).  Returns (pose [Q, 6],
         cov [Q, 6, 6] UNSCALED -- multiply by report["sigma2"] -- or None without covariance, segment [Q], report dict)."""
         x = self._x(x_full)
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0)
         sp.check_lengths(self.ds.num_frames)
         qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
         Q = len(qt)

@@ -2510,6 +2510,10 @@ bool smooth_params_read(const aar_smooth_params *sp, aar_smooth_params *out) {
     memset(out, 0, sizeof *out);
     if (sp->struct_size < offsetof(aar_smooth_params, sigma_trans) + sizeof(double)) return false;
     memcpy(out, sp, std::min<size_t>(sp->struct_size, sizeof *out));
+    // the fields appended for the motion model count only when the struct holds them whole
+    if (sp->struct_size < offsetof(aar_smooth_params, model) + sizeof(int32_t)) out->model = AAR_SMOOTH_MODEL_RANDOM_WALK;
+    if (sp->struct_size < offsetof(aar_smooth_params, sigma_rot0) + sizeof(double)) out->sigma_rot0 = 0.0;
+    if (sp->struct_size < offsetof(aar_smooth_params, sigma_trans0) + sizeof(double)) out->sigma_trans0 = 0.0;
     return true;
 }
 
@@ -2551,6 +2555,46 @@ int smooth_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCall &c) 
     return AAR_OK;
 }
 
+// the same for the constant-velocity prior: lambda of pair 0 (from sigma_rot0 / sigma_trans0) and of the terms 1 .. F-2, and their ratios r_f
+struct SmoothCvCall {
+    double *base = nullptr;
+    SmoothCvWork w;
+    ~SmoothCvCall() { if (base) (void)hipFree(base); }
+};
+
+int smooth_cv_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCvCall &c) {
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const size_t n = smooth_cv_work_doubles(F);
+    HIP_TRY(hipMalloc((void **)&c.base, n * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(c.base, 0, n * sizeof(double), pb->stream));
+    smooth_cv_work_carve(c.w, c.base, F);
+    int rc = AAR_OK;
+    if (F > 1) {
+        std::vector<double> lam(2 * (size_t)F, 0.0), ratio((size_t)F, 0.0);
+        auto dt = [&](int f) { return sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0; };
+        lam[0] = 1.0 / (sp.sigma_rot0 * sp.sigma_rot0 * dt(0));
+        lam[1] = 1.0 / (sp.sigma_trans0 * sp.sigma_trans0 * dt(0));
+        for (int f = 1; f + 1 < F; f++) {
+            lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt(f));
+            lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt(f));
+            ratio[f] = dt(f) / dt(f - 1);
+        }
+        if ((rc = copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double)))) return rc;
+        if ((rc = copy_h2d(pb, c.w.ratio, ratio.data(), ratio.size() * sizeof(double)))) return rc;
+    }
+    if (F) HIP_TRY(hipMemcpyAsync(c.w.z[0], P.z[pb->cur] + 6 * (size_t)P.A, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    return AAR_OK;
+}
+
+// the entries whose selected inverse is the tridiagonal one
+int smooth_rw_only(const aar_smooth_params &sp, const char *who) {
+    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY is not supported here (the selected inverse of the "
+                                              "block-pentadiagonal system is not built); use AAR_SMOOTH_MODEL_RANDOM_WALK", who);
+    return AAR_OK;
+}
+
 int smooth_entry(aar_problem *pb, const aar_smooth_params *sp_in, aar_smooth_params *sp, const char *who) {
     if (!sp_in) return set_error(AAR_ERR_INVALID, "%s: null aar_smooth_params", who);
     int rc = aar_smooth_params_validate(pb->L.F, sp_in);
@@ -2566,11 +2610,27 @@ struct SmoothLm {
     double initial = 0.0, currErr = 0.0, currData = 0.0, currPrior = 0.0, mu = -1.0;
 };
 
-// aar_track_smooth's loop on a prepared SmoothCall, from c.w.z[s.cur]
-int smooth_lm_run(aar_problem *pb, const SmoothCall &c, const aar_lm_params &p, SmoothLm &s) {
+// the launches of the two motion models behind one loop: H, b and costs (or the trial point's costs) with their record, and the damped solve
+struct SmoothRwOps {
+    aar_problem *pb;
+    const SmoothWork &w;
+    void eval(int cur, bool with_j) const { launch_smooth_eval(pb->P, pb->cur, w, cur, with_j, pb->stream); }
+    int solve(double mu) const { return launch_smooth_solve(w, pb->P.F, mu, pb->stream); }
+    const double *res() const { return w.res; }
+};
+struct SmoothCvOps {
+    aar_problem *pb;
+    const SmoothCvWork &w;
+    void eval(int cur, bool with_j) const { launch_smooth_cv_eval(pb->P, pb->cur, w, cur, with_j, pb->stream); }
+    int solve(double mu) const { return launch_smooth_cv_solve(w, pb->P.F, mu, pb->stream); }
+    const double *res() const { return w.res; }
+};
+
+// aar_track_smooth's loop on a prepared workspace, from its z[s.cur]
+extern "C++" template <class Ops>
+int smooth_lm_loop(aar_problem *pb, const Ops &o, const aar_lm_params &p, SmoothLm &s) {
     DeviceProblem &P = pb->P;
     const int F = P.F;
-    const SmoothWork &w = c.w;
     const double rows = 8.0 * (double)P.N + 6.0 * (double)(F - 1);
     int rc = AAR_OK;
     int cur = s.cur, iters = 0, rejected = 0, mustExit = 0;
@@ -2578,24 +2638,24 @@ int smooth_lm_run(aar_problem *pb, const SmoothCall &c, const aar_lm_params &p, 
     double currData = 0.0, currPrior = 0.0, mu = -1.0, v = 2.0;
     if (F > 0) {
         // init: the first evaluation also yields the first step's system
-        launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream);
+        o.eval(cur, true);
         pb->launches += 2;
-        if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;
+        if ((rc = copy_d2h(pb, res, o.res(), sizeof res))) return rc;
         currData = res[0]; currPrior = res[1];
     }
     double currErr = currData + currPrior, prevErr = currErr;
     const double initial = currErr;
     for (int it = 0; it < p.max_iters && !mustExit && rows > 0 && F > 0; it++) {
-        if (it > 0) { launch_smooth_eval(P, pb->cur, w, cur, true, pb->stream); pb->launches += 2; }   // H, b at curr_z (its costs are those already held)
+        if (it > 0) { o.eval(cur, true); pb->launches += 2; }   // H, b at curr_z (its costs are those already held)
         if (mu < 0) mu = res[4] * p.tau;   // (first iteration: res still holds the initial evaluation's record)
         double gain = 0.0;
         int ntries = 0;
         bool accepted = false;
         do {
-            pb->launches += launch_smooth_solve(w, F, mu, pb->stream);
-            launch_smooth_eval(P, pb->cur, w, cur, false, pb->stream);   // z[1 - cur] = z[cur] + delta, its costs, |delta|^2, delta . b
+            pb->launches += o.solve(mu);
+            o.eval(cur, false);   // z[1 - cur] = z[cur] + delta, its costs, |delta|^2, delta . b
             pb->launches += 2;
-            if ((rc = copy_d2h(pb, res, w.res, sizeof res))) return rc;   // the try's one read-back
+            if ((rc = copy_d2h(pb, res, o.res(), sizeof res))) return rc;   // the try's one read-back
             const double err = res[0] + res[1];
             const bool bad_pivot = res[5] != 0.0;
             const double Lq = 0.5 * (mu * res[2] - res[3]);
@@ -2626,6 +2686,10 @@ int smooth_lm_run(aar_problem *pb, const SmoothCall &c, const aar_lm_params &p, 
     return AAR_OK;
 }
 
+int smooth_lm_run(aar_problem *pb, const SmoothCall &c, const aar_lm_params &p, SmoothLm &s) {
+    return smooth_lm_loop(pb, SmoothRwOps{pb, c.w}, p, s);
+}
+
 // H at c.w.z[cur] (mu = 0) with its costs into c.w.res, the solve's elimination, the selected inverse into S, R [F][36] each (F > 0).
 // Launches only; returns their number.
 int smooth_selinv_launch(aar_problem *pb, const SmoothCall &c, int cur, double *S, double *R) {
@@ -2649,6 +2713,16 @@ int smooth_download(aar_problem *pb, double *x_full) {
 
 }  // namespace
 
+int32_t aar_smooth_solve_launches(int32_t num_frames, int32_t model) {
+    const int F = num_frames;
+    if (F <= 0) return 0;
+    if (model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return smooth_cv_solve_launches(F);
+    // smooth_kernels.hip: a level of its own while more than SMOOTH_TAIL nodes eliminate, with the damping in front and a back-substitution each
+    int n = 0;
+    for (int s = 1; s < F && (F + 2 * s - 1) / (2 * s) > SMOOTH_TAIL; s *= 2) n++;
+    return n ? 2 * n + 2 : 1;
+}
+
 int aar_smooth_params_validate(int32_t num_frames, const aar_smooth_params *sp_in) {
     if (!sp_in) return set_error(AAR_ERR_INVALID, "aar_smooth_params_validate: null argument");
     if (num_frames < 0) return set_error(AAR_ERR_INVALID, "aar_smooth_params: num_frames %d is negative", (int)num_frames);
@@ -2657,6 +2731,17 @@ int aar_smooth_params_validate(int32_t num_frames, const aar_smooth_params *sp_i
         return set_error(AAR_ERR_INVALID, "aar_smooth_params: struct_size %u does not reach sigma_rot / sigma_trans", (unsigned)sp_in->struct_size);
     if (!(sp.sigma_rot > 0.0) || !std::isfinite(sp.sigma_rot)) return set_error(AAR_ERR_INVALID, "aar_smooth_params: sigma_rot = %g must be positive and finite", sp.sigma_rot);
     if (!(sp.sigma_trans > 0.0) || !std::isfinite(sp.sigma_trans)) return set_error(AAR_ERR_INVALID, "aar_smooth_params: sigma_trans = %g must be positive and finite", sp.sigma_trans);
+    if (sp.model != AAR_SMOOTH_MODEL_RANDOM_WALK && sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+        return set_error(AAR_ERR_INVALID, "aar_smooth_params: model = %d is neither AAR_SMOOTH_MODEL_RANDOM_WALK nor AAR_SMOOTH_MODEL_CONSTANT_VELOCITY", (int)sp.model);
+    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
+        if (!(sp.sigma_rot0 > 0.0) || !std::isfinite(sp.sigma_rot0))
+            return set_error(AAR_ERR_INVALID, "aar_smooth_params: sigma_rot0 = %g must be positive and finite under AAR_SMOOTH_MODEL_CONSTANT_VELOCITY", sp.sigma_rot0);
+        if (!(sp.sigma_trans0 > 0.0) || !std::isfinite(sp.sigma_trans0))
+            return set_error(AAR_ERR_INVALID, "aar_smooth_params: sigma_trans0 = %g must be positive and finite under AAR_SMOOTH_MODEL_CONSTANT_VELOCITY", sp.sigma_trans0);
+        if (sp.rel_motion)
+            return set_error(AAR_ERR_INVALID, "aar_smooth_params: rel_motion must be NULL under AAR_SMOOTH_MODEL_CONSTANT_VELOCITY (the expected motion "
+                                              "of a term is the motion of the pair before it)");
+    }
     if (sp.frame_time)
         for (int f = 0; f < num_frames; f++) {
             if (!std::isfinite(sp.frame_time[f])) return set_error(AAR_ERR_INVALID, "aar_smooth_params: frame_time[%d] is not finite", f);
@@ -2672,6 +2757,56 @@ int aar_smooth_params_validate(int32_t num_frames, const aar_smooth_params *sp_i
     return AAR_OK;
 }
 
+namespace {
+
+// aar_track_smooth_system2 under the constant-velocity prior
+int smooth_cv_system(aar_problem *pb, const double *x_full, const aar_smooth_params &sp, double mu, double *diag, double *off, double *off2,
+                     double *rhs, double *delta, double cost[2]) {
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    int rc = AAR_OK;
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCvCall c;
+    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
+    if (cost) cost[0] = cost[1] = 0.0;
+    if (F == 0) { HIP_TRY(hipStreamSynchronize(pb->stream)); return AAR_OK; }
+    launch_smooth_cv_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
+    double res[8];
+    if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+    if (cost) { cost[0] = res[0]; cost[1] = res[1]; }
+    if (diag && (rc = copy_d2h(pb, diag, c.w.Dg, 36 * (size_t)F * sizeof(double)))) return rc;
+    if (off && F > 1 && (rc = copy_d2h(pb, off, c.w.O1, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    if (off2 && F > 2 && (rc = copy_d2h(pb, off2, c.w.O2, 36 * (size_t)(F - 2) * sizeof(double)))) return rc;
+    if (rhs && (rc = copy_d2h(pb, rhs, c.w.rhs, 6 * (size_t)F * sizeof(double)))) return rc;
+    if (delta) {
+        pb->launches += launch_smooth_cv_solve(c.w, F, mu, pb->stream);
+        int32_t flag = 0;
+        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+        if ((rc = copy_d2h(pb, delta, c.w.delta, 6 * (size_t)F * sizeof(double)))) return rc;
+        if (flag) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_system2: non-positive pivot in the block-pentadiagonal solve (mu = %g)", mu);
+    }
+    return check_async("smoothing kernels");
+}
+
+}  // namespace
+
+int aar_track_smooth_system2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double mu, double *diag, double *off, double *off2,
+                             double *rhs, double *delta, double cost[2]) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system2: null argument");
+    if (!(mu >= 0.0) || !std::isfinite(mu)) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system2: mu = %g must be finite and not negative", mu);
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_system2");
+    if (rc) return rc;
+    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return smooth_cv_system(pb, x_full, sp, mu, diag, off, off2, rhs, delta, cost);
+    if ((rc = aar_track_smooth_system(pb, x_full, sp_in, mu, diag, off, rhs, delta, cost))) return rc;
+    if (off2 && pb->P.F > 2) std::fill(off2, off2 + 36 * (size_t)(pb->P.F - 2), 0.0);
+    return AAR_OK;
+}
+
 int aar_track_smooth_system(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double mu, double *diag, double *off, double *rhs,
                             double *delta, double cost[2]) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system: null argument");
@@ -2679,6 +2814,9 @@ int aar_track_smooth_system(aar_problem *pb, const double *x_full, const aar_smo
     aar_smooth_params sp;
     int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_system");
     if (rc) return rc;
+    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_system: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY has a second off-diagonal; "
+                                              "call aar_track_smooth_system2");
     HIP_TRY(hipSetDevice(pb->device));
     DeviceProblem &P = pb->P;
     const int F = P.F;
@@ -2715,6 +2853,7 @@ int aar_track_smooth_covariance(aar_problem *pb, const double *x_full, const aar
     aar_smooth_params sp;
     int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_covariance");
     if (rc) return rc;
+    if ((rc = smooth_rw_only(sp, "aar_track_smooth_covariance"))) return rc;
     HIP_TRY(hipSetDevice(pb->device));
     DeviceProblem &P = pb->P;
     const int F = P.F;
@@ -2778,14 +2917,21 @@ int aar_track_smooth(aar_problem *pb, double *x_full, const aar_lm_params *prm, 
     if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
     launch_unpack(P, pb->cur, pb->stream);  // rows of the fixed cameras / markers (and K with intrinsics)
     SmoothCall c;
-    if ((rc = smooth_prepare(pb, sp, c))) return rc;
-    const SmoothWork &w = c.w;
+    SmoothCvCall cv;
     SmoothLm s;
-    if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
-    const int cur = s.cur;
-    if (F) HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, w.z[cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
-    if (frame_err && F && (rc = copy_d2h(pb, frame_err, w.Ef[cur], (size_t)F * sizeof(double)))) return rc;
-    if (pair_err && F > 1 && (rc = copy_d2h(pb, pair_err, w.Pe[cur], (size_t)(F - 1) * sizeof(double)))) return rc;
+    const double *zr = nullptr, *Ef = nullptr, *Pe = nullptr;   // the result's poses and costs on the device
+    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
+        if ((rc = smooth_cv_prepare(pb, sp, cv))) return rc;
+        if ((rc = smooth_lm_loop(pb, SmoothCvOps{pb, cv.w}, p, s))) return rc;
+        zr = cv.w.z[s.cur]; Ef = cv.w.Ef[s.cur]; Pe = cv.w.Pe[s.cur];
+    } else {
+        if ((rc = smooth_prepare(pb, sp, c))) return rc;
+        if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
+        zr = c.w.z[s.cur]; Ef = c.w.Ef[s.cur]; Pe = c.w.Pe[s.cur];
+    }
+    if (F) HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, zr, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    if (frame_err && F && (rc = copy_d2h(pb, frame_err, Ef, (size_t)F * sizeof(double)))) return rc;
+    if (pair_err && F > 1 && (rc = copy_d2h(pb, pair_err, Pe, (size_t)(F - 1) * sizeof(double)))) return rc;
     if ((rc = check_async("smoothing kernels"))) return rc;
     if ((rc = smooth_download(pb, x_full))) return rc;
     if (report) {
@@ -2887,6 +3033,7 @@ int aar_track_smooth_fit_terms(aar_problem *pb, const double *x_full, const aar_
     aar_smooth_params sp;
     int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit_terms");
     if (rc) return rc;
+    if ((rc = smooth_rw_only(sp, "aar_track_smooth_fit_terms"))) return rc;
     if ((rc = smooth_fit_entry(pb, "aar_track_smooth_fit_terms"))) return rc;
     HIP_TRY(hipSetDevice(pb->device));
     DeviceProblem &P = pb->P;
@@ -2913,6 +3060,7 @@ int aar_track_smooth_fit(aar_problem *pb, double *x_full, const aar_lm_params *p
     aar_smooth_params sp;
     int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit");
     if (rc) return rc;
+    if ((rc = smooth_rw_only(sp, "aar_track_smooth_fit"))) return rc;
     aar_smooth_fit_params fp;
     if (fp_in) {
         if ((rc = aar_smooth_fit_params_validate(fp_in))) return rc;
@@ -3013,6 +3161,7 @@ int aar_track_smooth_query(aar_problem *pb, const double *x_full, const aar_smoo
     aar_smooth_params sp;
     int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query");
     if (rc) return rc;
+    if ((rc = smooth_rw_only(sp, "aar_track_smooth_query"))) return rc;
     if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
     if (sp.rel_motion)
         return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_query: rel_motion is set; under an expected motion the pose of an inserted frame "

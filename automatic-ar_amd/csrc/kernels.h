@@ -318,6 +318,33 @@ int launch_smooth_query(const SmoothWork &w, int F, const double *z, const doubl
 // a_r, u_r, a_t, u_t and rec [8] = their sums, w.res[0], w.res[1], w.flag[0], 0; sigma_rot: the one w.lam was built with
 int launch_smooth_fit_terms(const SmoothWork &w, int cur, int F, double sigma_rot, const double *S, const double *R, double *terms, double *rec,
                             hipStream_t st);                                                                              // returns its launches
+// k_smooth_reduce on its own (one launch): Ef, Pe [F]; lin [F][2] or NULL; Dg [F][36] or NULL -> res [8]
+void launch_smooth_reduce(const double *Ef, const double *Pe, const double *lin, const double *Dg, const int32_t *flag, int F, double *res,
+                          hipStream_t st);
+
+// smoothed tracking under the constant-velocity prior (smooth_cv_kernels.hip): H is block pentadiagonal; the solve pairs
+// the frames into K = ceil(F / 2) supernodes (2k, 2k + 1) of 12x12 blocks, block tridiagonal again, and runs section 16's cyclic reduction on them
+constexpr int SMOOTH_CV_T = 16;    // levels with at most this many eliminating supernodes run inside the one workgroup that finishes the reduction
+struct SmoothCvWork {
+    double *z[2] = {nullptr, nullptr};     // [F][6] frame poses: the current point and the trial point
+    double *delta = nullptr;               // [2K][6] the damped step (the padded frame of an odd F: zeros)
+    double *Dg = nullptr, *O1 = nullptr, *O2 = nullptr;   // [F][36] H_ff, H_{f,f+1}, H_{f,f+2} (row-major, rows: frame f; zeros where there is none)
+    double *rhs = nullptr;                 // [F][6] b
+    double *Dw = nullptr, *Uw = nullptr, *Dinv = nullptr, *Ls = nullptr;   // [K][144] the reduction's working copy and what its back-substitution keeps
+    double *bw = nullptr;                  // [K][12]
+    double *Ef[2] = {nullptr, nullptr}, *Pe[2] = {nullptr, nullptr};   // [F] data cost per frame, prior cost per term (entry 0: pair 0, entry F-1: 0)
+    double *lin = nullptr;                 // [F][2] |delta_f|^2, delta_f . b_f
+    double *lam = nullptr;                 // [F][2] of term f (entry 0: pair 0 with sigma_rot0 / sigma_trans0): 1 / (sigma_rot^2 dt_f), 1 / (sigma_trans^2 dt_f)
+    double *ratio = nullptr;               // [F] r_f = dt_f / dt_{f-1} of term f
+    double *res = nullptr;                 // [8] as SmoothWork::res
+    int32_t *flag = nullptr;               // [1] a non-positive pivot in the last solve
+};
+inline int smooth_cv_nodes(int F) { return (F + 1) / 2; }
+size_t smooth_cv_work_doubles(int F);
+void smooth_cv_work_carve(SmoothCvWork &w, double *base, int F);
+void launch_smooth_cv_eval(const DeviceProblem &P, int which, const SmoothCvWork &w, int cur, bool with_j, hipStream_t st);   // two launches
+int launch_smooth_cv_solve(const SmoothCvWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
+int smooth_cv_solve_launches(int F);                                                                                          // ... that number, on the host
 
 // live tracker (live_kernels.hip): one frame per push, the whole LM of the window in ONE launch of one workgroup
 constexpr int LIVE_MAX_W = 16;            // window frames (AAR_TRACKER_MAX_LAG + 1)

@@ -445,6 +445,12 @@ void launch_smooth_eval(const DeviceProblem &P, int which, const SmoothWork &w, 
                        (const int32_t *)w.flag, P.F, w.res);
 }
 
+// the reduction alone, for the evaluation of another prior (smooth_cv_kernels.hip)
+void launch_smooth_reduce(const double *Ef, const double *Pe, const double *lin, const double *Dg, const int32_t *flag, int F, double *res,
+                          hipStream_t st) {
+    hipLaunchKernelGGL(k_smooth_reduce, dim3(1), dim3(256), 0, st, Ef, Pe, lin, Dg, flag, F, res);
+}
+
 // (H + mu I) delta = rhs; returns the number of launches
 int launch_smooth_solve(const SmoothWork &w, int F, double mu, hipStream_t st) {
     if (F == 0) return 0;

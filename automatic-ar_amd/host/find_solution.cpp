@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0>] [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -256,6 +256,11 @@ int main(int argc, char *argv[]) {
     // ... -smooth-covariance (only with -smooth) also writes every frame's 6x6 pose covariance at the smoothed poses to
     // final.smooth_covariance.yaml (MultiCamMapper::track_smooth_covariance)
     bool smooth_covariance = false;
+    // ... -cv <sigma_rot0> <sigma_trans0> (only with -smooth) smooths under the constant-velocity prior: the -smooth sigmas
+    // bound the deviation from constant velocity, these two the first pair's motion.  Not with -smooth-covariance, -fit-sigmas or -resample
+    bool smooth_cv = false;
+    double smooth_sigma0[2] = {0.0, 0.0};
+    int smooth_cv_args = 0;
     // ... -fit-sigmas (only with -smooth) first fits the corner noise and the two sigmas to the sequence, from the given values as the start
     // (MultiCamMapper::fit_smooth_sigmas), and smooths with the fitted effective values
     bool fit_sigmas = false;
@@ -286,7 +291,7 @@ int main(int argc, char *argv[]) {
     int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
     double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, Resample, Live, Anchor, Gate, Motion } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, Live, Anchor, Gate, Motion } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -311,6 +316,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-relative-sigma-m") arg_flag = RelM;
         else if (a == "-smooth") { smooth = true; smooth_args = 0; arg_flag = Smooth; }
         else if (a == "-smooth-covariance") { smooth_covariance = true; arg_flag = NONE; }
+        else if (a == "-cv") { smooth_cv = true; smooth_cv_args = 0; arg_flag = SmoothCv; }
         else if (a == "-fit-sigmas") { fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-resample") { resample = true; resample_n = 0; arg_flag = Resample; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
@@ -369,6 +375,13 @@ int main(int argc, char *argv[]) {
             resample_n = (int)v;
             arg_flag = NONE;
         }
+        else if (arg_flag == SmoothCv) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            smooth_sigma0[smooth_cv_args++] = v;
+            if (smooth_cv_args == 2) arg_flag = NONE;
+        }
         else if (arg_flag == Smooth) {
             char *end = nullptr;
             const double v = strtod(a.c_str(), &end);
@@ -418,6 +431,7 @@ int main(int argc, char *argv[]) {
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (smooth_covariance && !smooth) return print_usage(argv[0]);
+    if (smooth_cv && (!smooth || smooth_cv_args != 2 || smooth_covariance || fit_sigmas || resample)) return print_usage(argv[0]);
     if (fit_sigmas && (!smooth || live)) return print_usage(argv[0]);
     if (resample && (!smooth || live || resample_n < 2)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
@@ -628,9 +642,10 @@ int main(int argc, char *argv[]) {
                 smooth_sigma[0] = fr.sigma_rot_eff;
                 smooth_sigma[1] = fr.sigma_trans_eff;
             }
-            mcm.track_smooth(smooth_sigma[0], smooth_sigma[1]);
+            if (smooth_cv) mcm.track_smooth(smooth_sigma[0], smooth_sigma[1], AAR_SMOOTH_MODEL_CONSTANT_VELOCITY, smooth_sigma0[0], smooth_sigma0[1]);
+            else mcm.track_smooth(smooth_sigma[0], smooth_sigma[1]);
             const aar_smooth_report &sr = mcm.smooth_report;
-            cout << "smooth: " << sr.iterations << " LM iterations (" << sr.rejected_tries << " rejected tries, exit " << sr.stop_code << "), cost " << sr.initial_cost
+            cout << "smooth: " << (smooth_cv ? "constant velocity, " : "") << sr.iterations << " LM iterations (" << sr.rejected_tries << " rejected tries, exit " << sr.stop_code << "), cost " << sr.initial_cost
                  << " -> " << sr.final_cost << " (data " << sr.final_data_cost << ", prior " << sr.final_prior_cost << ") in " << sr.seconds << " s" << endl;
         } catch (const exception &e) {
             cerr << "smoothing failed: " << e.what() << endl;

@@ -558,6 +558,12 @@ double solve_tracking(MultiCamMapper *m, std::vector<double> &z) {
 // Smoothed tracking (aar_track_smooth): track()'s model plus a random-walk motion prior between consecutive frames, one
 // joint LM on the device.  The mapper's frame ids are the prior's time axis, so a hole in the recording is bridged more loosely than one step.
 void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans) {
+    track_smooth(sigma_rot, sigma_trans, AAR_SMOOTH_MODEL_RANDOM_WALK, 0.0, 0.0);
+}
+
+// ... under either motion model: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY makes sigma_rot / sigma_trans the deviation from
+// constant velocity and sigma_rot0 / sigma_trans0 the prior on the first pair's motion
+void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0) {
     if (!data_) throw std::runtime_error("MultiCamMapper::track_smooth: no data set");
     mats2eVec();
     hubberDelta = 10;  // as track()
@@ -580,6 +586,9 @@ void MultiCamMapper::track_smooth(double sigma_rot, double sigma_trans) {
     sp.sigma_rot = sigma_rot;
     sp.sigma_trans = sigma_trans;
     sp.frame_time = F ? time.data() : nullptr;
+    sp.model = model;
+    sp.sigma_rot0 = sigma_rot0;
+    sp.sigma_trans0 = sigma_trans0;
     memset(&smooth_report, 0, sizeof smooth_report);
     smooth_report.struct_size = sizeof smooth_report;
     track_errors.assign(F, 0.0);

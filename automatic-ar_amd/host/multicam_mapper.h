@@ -394,6 +394,9 @@ class MultiCamMapper {
     // metre per sqrt(frame id step)), all frames in one LM on the device (aar_track_smooth); the report lands in smooth_report, E_f in
     // track_errors and the pairs' prior costs in smooth_pair_errors
     void track_smooth(double sigma_rot, double sigma_trans);
+    // ... under the motion model AAR_SMOOTH_MODEL_* (DESIGN.md section 31).  Constant velocity: sigma_rot / sigma_trans bound the deviation from
+    // constant velocity, sigma_rot0 / sigma_trans0 are the sigmas of the first pair's random-walk term; smooth_pair_errors[f] is then term f's cost
+    void track_smooth(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0);
     // EXTENSION, no counterpart in the reference: the pose covariance of the smoothed track at the current poses (aar_track_smooth_covariance,
     // DESIGN.md section 28), with track_smooth()'s prior (the frame ids as its time axis) and Huber delta.  The blocks are UNSCALED: the
     // covariance of frame f is report.sigma2 * frame_cov[f], that of the motion from f to f + 1 follows with lag_cov[f].

@@ -575,7 +575,25 @@ typedef struct aar_smooth_params {
     double sigma_trans;          /* metre per sqrt(unit of frame_time), > 0 finite */
     const double *frame_time;    /* [num_frames] strictly ascending, finite; NULL = 0,1,2,... */
     const double *rel_motion;    /* [num_frames-1][6] expected (rvec, t) from f to f+1; NULL = none */
+    int32_t model;               /* AAR_SMOOTH_MODEL_*; a struct that ends before it reads as AAR_SMOOTH_MODEL_RANDOM_WALK */
+    double sigma_rot0;           /* constant velocity only: the sigmas of pair 0, the prior on the first velocity; > 0 finite */
+    double sigma_trans0;
 } aar_smooth_params;
+/* The motion model of the prior.
+ *  AAR_SMOOTH_MODEL_RANDOM_WALK: the prior above, bit for bit what a struct without the field gives.
+ *  AAR_SMOOTH_MODEL_CONSTANT_VELOCITY: a second-difference prior, the joint minimiser and not a previous pass fed back.  With
+ *  between(z_a, z_b, rel) = [ log((R_a dR)^T R_b)^v ; t_b - t_a - dt ] and L(sr, st, D) = diag(1 / (sr^2 D) x3, 1 / (st^2 D) x3):
+ *     pair 0   e_0 = between(z_0, z_1) with L(sigma_rot0, sigma_trans0, D_0): the prior on the first velocity, which makes H positive definite
+ *              exactly where the random walk's is
+ *     term f   (1 <= f <= num_frames - 2)  e_f = between(z_f, z_{f+1}, rel_f),  rel_f = r_f between(z_{f-1}, z_f),  r_f = D_f / D_{f-1}:
+ *              dR_f = Exp(r_f log(R_{f-1}^T R_f)),  dt_f = r_f (t_f - t_{f-1}),  with L(sigma_rot, sigma_trans, D_f)
+ *  so sigma_rot / sigma_trans bound the deviation from constant velocity per sqrt(unit of frame_time).  The expected motion is a function of
+ *  the unknowns and the full Jacobian is used; H is block pentadiagonal and every try solves it by the cyclic reduction on pairs of frames
+ *  (12x12 blocks).  rows = 8 num_obs + 6 (num_frames - 1) as before; pair_err[0] is pair 0, pair_err[f] term f.  rel_motion must be NULL
+ *  (AAR_ERR_INVALID).  aar_track_smooth and aar_track_smooth_system2 honour the model; aar_track_smooth_system, _covariance, _fit, _fit_terms and
+ *  _query return AAR_ERR_UNSUPPORTED under constant velocity and write nothing (their selected inverse is the tridiagonal one). */
+#define AAR_SMOOTH_MODEL_RANDOM_WALK 0
+#define AAR_SMOOTH_MODEL_CONSTANT_VELOCITY 1
 typedef struct aar_smooth_report {
     uint32_t struct_size;
     int32_t iterations, stop_code, rejected_tries;
@@ -592,6 +610,13 @@ int aar_track_smooth(aar_problem *, double *x_full, const aar_lm_params *, const
  * non-positive pivot), cost = {sum_f E_f, sum_f e_f^T L_f e_f}.  Every output may be NULL. */
 int aar_track_smooth_system(aar_problem *, const double *x_full, const aar_smooth_params *, double mu, double *diag, double *off, double *rhs,
                             double *delta, double cost[2]);
+/* The same for either model: off2 [num_frames-2][36] = H_{f,f+2} (row-major, rows: frame f), zeros under the random walk; delta by the
+ * reduction of the model in aar_smooth_params. */
+int aar_track_smooth_system2(aar_problem *, const double *x_full, const aar_smooth_params *, double mu, double *diag, double *off, double *off2,
+                             double *rhs, double *delta, double cost[2]);
+/* Host function: the kernel launches of ONE damped solve inside aar_track_smooth / aar_track_smooth_system(2) at this size under the model
+ * (AAR_SMOOTH_MODEL_*): one launch while the whole reduction fits the workgroup that finishes it, else 2 + 2 per level launched on its own. */
+int32_t aar_smooth_solve_launches(int32_t num_frames, int32_t model);
 /* Pose covariance of the smoothed track: the selected inverse of the H that aar_track_smooth_system returns at mu = 0 for
  * the same x_full and parameters (data blocks with the problem's Huber weights, prior blocks with frame_time and rel_motion).
  *   frame_cov [num_frames][36]   = (H^-1)_ff,      row-major over (rvec, t), symmetric to the bit
