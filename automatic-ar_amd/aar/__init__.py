@@ -39,7 +39,7 @@ SYMBOLS = [
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
-    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_system2", "aar_smooth_solve_launches", "aar_track_smooth_covariance",
+    "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_system2", "aar_smooth_solve_launches", "aar_track_smooth_covariance", "aar_track_smooth_covariance2",
     "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms",
     "aar_smooth_query_validate", "aar_track_smooth_query",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
@@ -545,6 +545,7 @@ def lib():
     L.aar_smooth_solve_launches.restype = C.c_int32
     L.aar_track_smooth_system2.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_double, dp, dp, dp, dp, dp, dp]
     L.aar_track_smooth_covariance.argtypes = [C.c_void_p, dp, C.c_void_p, dp, dp, C.POINTER(CSmoothCovarianceReport)]
+    L.aar_track_smooth_covariance2.argtypes = [C.c_void_p, dp, C.c_void_p, dp, dp, dp, C.POINTER(CSmoothCovarianceReport)]
     L.aar_smooth_query_validate.argtypes = [C.c_int32, C.c_void_p, C.c_int64, dp]
     L.aar_track_smooth_query.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, dp, dp, dp, C.POINTER(C.c_int32),
                                          C.POINTER(CSmoothQueryReport)]
@@ -1743,6 +1744,23 @@ class Problem:
         _check(lib().aar_track_smooth_covariance(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), C.byref(rep)))
         report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
         return fc[:F], lc[:max(F - 1, 0)], report
+
+    def track_smooth_covariance2(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0,
+                                 lag2=True):
+        """aar_track_smooth_covariance2, either model: (frame_cov [F, 6, 6] = (H^-1)_ff, lag_cov [F-1, 6, 6] = (H^-1)_{f,f+1}, lag2_cov
+        [F-2, 6, 6] = (H^-1)_{f,f+2}, report dict) at x_full, H the matrix of track_smooth_system2 at mu = 0.  All UNSCALED: multiply by
+        report["sigma2"].  lag2=False passes NULL for lag2_cov (the random walk refuses it otherwise) and returns None in its place."""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(F)
+        fc, lc, l2 = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6)), np.zeros((max(F - 2, 1), 6, 6))
+        rep = CSmoothCovarianceReport()
+        rep.struct_size = C.sizeof(CSmoothCovarianceReport)
+        _check(lib().aar_track_smooth_covariance2(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), _dptr(l2) if lag2 else None,
+                                                  C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
+        return fc[:F], lc[:max(F - 1, 0)], l2[:max(F - 2, 0)] if lag2 else None, report
 
     def track_smooth_fit(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit: the pixel noise and the motion sigmas fitted to the sequence by EM, from the effective start values

@@ -2590,8 +2590,9 @@ int smooth_cv_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCvCall
 // the entries whose selected inverse is the tridiagonal one
 int smooth_rw_only(const aar_smooth_params &sp, const char *who) {
     if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
-        return set_error(AAR_ERR_UNSUPPORTED, "%s: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY is not supported here (the selected inverse of the "
-                                              "block-pentadiagonal system is not built); use AAR_SMOOTH_MODEL_RANDOM_WALK", who);
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY is not supported here (this entry works on the selected "
+                                              "inverse of the block-tridiagonal system; the pose covariance under constant velocity is "
+                                              "aar_track_smooth_covariance2); use AAR_SMOOTH_MODEL_RANDOM_WALK", who);
     return AAR_OK;
 }
 
@@ -2887,6 +2888,71 @@ int aar_track_smooth_covariance(aar_problem *pb, const double *x_full, const aar
         r.data_cost = res[0]; r.prior_cost = res[1];
         if (frame_cov && (rc = copy_d2h(pb, frame_cov, S, 36 * (size_t)F * sizeof(double)))) return rc;
         if (lag_cov && F > 1 && (rc = copy_d2h(pb, lag_cov, R, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+    }
+    const int64_t dof = r.num_residuals - r.num_vars;
+    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
+// under constant velocity H at mu = 0 as aar_track_smooth_system2 assembles it, the supernode reduction of the solve, then
+// the downward pass of smooth_cv_cov_kernels.hip; under the random walk aar_track_smooth_covariance itself
+int aar_track_smooth_covariance2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *frame_cov, double *lag_cov,
+                                 double *lag2_cov, aar_smooth_covariance_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_covariance2: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_covariance2");
+    if (rc) return rc;
+    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
+        if (lag2_cov)
+            return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_covariance2: lag2_cov under AAR_SMOOTH_MODEL_RANDOM_WALK is not supported (the "
+                                                  "selected inverse of the block-tridiagonal system does not contain the lag-two blocks)");
+        return aar_track_smooth_covariance(pb, x_full, sp_in, frame_cov, lag_cov, report);
+    }
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCvCall c;
+    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
+    aar_smooth_covariance_report r;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
+    r.num_vars = 6 * (int64_t)F;
+    if (F > 0) {
+        // S, the two R and the unpacked blocks: an allocation of their own, the carve of the solve's work area keeps its layout
+        SmoothCvCall sel;
+        const size_t n = smooth_cv_selinv_doubles(F);
+        HIP_TRY(hipMalloc((void **)&sel.base, n * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(sel.base, 0, n * sizeof(double), pb->stream));
+        double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
+        launch_smooth_cv_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
+        r.launches = 2;
+        r.launches += launch_smooth_cv_solve(c.w, F, 0.0, pb->stream);
+        r.launches += launch_smooth_cv_selinv(c.w, F, sel.base, &fc, &lc, &l2, pb->stream);
+        pb->launches += r.launches;
+        double res[8];
+        int32_t flag = 0;
+        if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+        if ((rc = check_async("smoothing covariance kernels"))) return rc;
+        if (flag)
+            return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_covariance2: non-positive pivot in the block-pentadiagonal elimination (the frames' "
+                                              "detections and the prior do not determine every pose)");
+        r.data_cost = res[0]; r.prior_cost = res[1];
+        if (frame_cov && (rc = copy_d2h(pb, frame_cov, fc, 36 * (size_t)F * sizeof(double)))) return rc;
+        if (lag_cov && F > 1 && (rc = copy_d2h(pb, lag_cov, lc, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+        if (lag2_cov && F > 2 && (rc = copy_d2h(pb, lag2_cov, l2, 36 * (size_t)(F - 2) * sizeof(double)))) return rc;
     } else {
         HIP_TRY(hipStreamSynchronize(pb->stream));
     }

@@ -345,6 +345,11 @@ void smooth_cv_work_carve(SmoothCvWork &w, double *base, int F);
 void launch_smooth_cv_eval(const DeviceProblem &P, int which, const SmoothCvWork &w, int cur, bool with_j, hipStream_t st);   // two launches
 int launch_smooth_cv_solve(const SmoothCvWork &w, int F, double mu, hipStream_t st);                                          // returns its launches
 int smooth_cv_solve_launches(int F);                                                                                          // ... that number, on the host
+// the diagonal, lag-one and lag-two blocks of H^-1 from what launch_smooth_cv_solve(w, F, 0.0, st) left (smooth_cv_cov_kernels.hip, DESIGN.md
+// section 32): area = smooth_cv_selinv_doubles(F) zeroed doubles on the device; fc, lc, l2 [F][36] each are returned as pointers into it
+size_t smooth_cv_selinv_doubles(int F);
+int smooth_cv_selinv_launches(int F);
+int launch_smooth_cv_selinv(const SmoothCvWork &w, int F, double *area, double **fc, double **lc, double **l2, hipStream_t st);   // returns its launches
 
 // live tracker (live_kernels.hip): one frame per push, the whole LM of the window in ONE launch of one workgroup
 constexpr int LIVE_MAX_W = 16;            // window frames (AAR_TRACKER_MAX_LAG + 1)

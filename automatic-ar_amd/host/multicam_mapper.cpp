@@ -618,9 +618,43 @@ void MultiCamMapper::track_smooth_covariance(double sigma_rot, double sigma_tran
     sp.frame_time = F ? time.data() : nullptr;
     out.frame_cov.assign(36 * (size_t)F, 0.0);
     out.lag_cov.assign(F > 1 ? 36 * (size_t)(F - 1) : 0, 0.0);
+    out.lag2_cov.clear();
     memset(&out.report, 0, sizeof out.report);
     out.report.struct_size = sizeof out.report;
     if (aar_track_smooth_covariance(pb, x.data(), &sp, out.frame_cov.data(), out.lag_cov.data(), &out.report)) throw std::runtime_error(aar_last_error());
+}
+
+// ... under either motion model (aar_track_smooth_covariance2).  Constant velocity fills lag2_cov as well; the random walk
+// leaves it empty (its selected inverse does not contain that block)
+void MultiCamMapper::track_smooth_covariance(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, SmoothCovariance &out) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::track_smooth_covariance: no data set");
+    mats2eVec();
+    hubberDelta = 10;  // as track_smooth()
+    std::vector<double> x;
+    aar_problem *pb = detail::bind_problem(this, x);
+    if (aar_problem_merge_z(pb, io_vec.data(), x.data())) throw std::runtime_error(aar_last_error());
+    const int F = data_->num_frames;
+    std::vector<double> time(F);
+    for (int f = 0; f < F; f++) time[f] = (double)data_->frame_ids[f];
+    aar_smooth_params sp;
+    memset(&sp, 0, sizeof sp);
+    sp.struct_size = sizeof sp;
+    sp.sigma_rot = sigma_rot;
+    sp.sigma_trans = sigma_trans;
+    sp.frame_time = F ? time.data() : nullptr;
+    sp.model = model;
+    sp.sigma_rot0 = sigma_rot0;
+    sp.sigma_trans0 = sigma_trans0;
+    const bool cv = model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY;
+    out.frame_cov.assign(36 * (size_t)F, 0.0);
+    out.lag_cov.assign(F > 1 ? 36 * (size_t)(F - 1) : 0, 0.0);
+    out.lag2_cov.assign(cv && F > 2 ? 36 * (size_t)(F - 2) : 0, 0.0);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    // (an empty vector's data() may be anything: NULL says "not wanted", and under the random walk it must)
+    if (aar_track_smooth_covariance2(pb, x.data(), &sp, out.frame_cov.data(), out.lag_cov.empty() ? nullptr : out.lag_cov.data(),
+                                     out.lag2_cov.empty() ? nullptr : out.lag2_cov.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
 }
 
 // The smoothed track at any time (aar_track_smooth_query) from the current poses, under track_smooth()'s model

@@ -403,9 +403,14 @@ class MultiCamMapper {
     struct SmoothCovariance {
         std::vector<double> frame_cov;   // [num_frames][36] (H^-1)_ff, row-major over (rvec, t)
         std::vector<double> lag_cov;     // [num_frames - 1][36] (H^-1)_{f,f+1}, the rows belong to frame f
+        std::vector<double> lag2_cov;    // [num_frames - 2][36] (H^-1)_{f,f+2}, the rows belong to frame f; constant velocity only, else empty
         aar_smooth_covariance_report report = {};
     };
     void track_smooth_covariance(double sigma_rot, double sigma_trans, SmoothCovariance &out);   // throws std::runtime_error on failure
+    // ... under the motion model AAR_SMOOTH_MODEL_* with track_smooth()'s sigmas (aar_track_smooth_covariance2): constant
+    // velocity adds lag2_cov, with which the covariance of a second difference z_{f+2} - 2 z_{f+1} + z_f follows
+    void track_smooth_covariance(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                 SmoothCovariance &out);                                          // throws std::runtime_error on failure
     // EXTENSION, no counterpart in the reference: the smoothed track at times that need not be frame times (aar_track_smooth_query, DESIGN.md
     // section 30), with track_smooth()'s prior (the frame ids as its time axis) and Huber delta: what the smoother would report for a frame
     // without detections inserted at each time.  cov is UNSCALED (multiply by report.sigma2) and left empty without covariance.

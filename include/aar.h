@@ -590,8 +590,9 @@ typedef struct aar_smooth_params {
  *  so sigma_rot / sigma_trans bound the deviation from constant velocity per sqrt(unit of frame_time).  The expected motion is a function of
  *  the unknowns and the full Jacobian is used; H is block pentadiagonal and every try solves it by the cyclic reduction on pairs of frames
  *  (12x12 blocks).  rows = 8 num_obs + 6 (num_frames - 1) as before; pair_err[0] is pair 0, pair_err[f] term f.  rel_motion must be NULL
- *  (AAR_ERR_INVALID).  aar_track_smooth and aar_track_smooth_system2 honour the model; aar_track_smooth_system, _covariance, _fit, _fit_terms and
- *  _query return AAR_ERR_UNSUPPORTED under constant velocity and write nothing (their selected inverse is the tridiagonal one). */
+ *  (AAR_ERR_INVALID).  aar_track_smooth, aar_track_smooth_system2 and aar_track_smooth_covariance2 honour the model; aar_track_smooth_system,
+ *  _covariance, _fit, _fit_terms and _query return AAR_ERR_UNSUPPORTED under constant velocity and write nothing (their selected inverse is the
+ *  tridiagonal one). */
 #define AAR_SMOOTH_MODEL_RANDOM_WALK 0
 #define AAR_SMOOTH_MODEL_CONSTANT_VELOCITY 1
 typedef struct aar_smooth_report {
@@ -640,6 +641,21 @@ typedef struct aar_smooth_covariance_report {
 } aar_smooth_covariance_report;
 int aar_track_smooth_covariance(aar_problem *, const double *x_full, const aar_smooth_params *, double *frame_cov, double *lag_cov,
                                 aar_smooth_covariance_report *report);
+/* The same for either model, with the lag-two blocks that the block-pentadiagonal H of constant velocity brings:
+ *   lag2_cov [num_frames-2][36] = (H^-1)_{f,f+2}, row-major, the rows belong to frame f.  With it the covariance of a second difference,
+ *                                 the quantity the constant-velocity prior constrains, is computable from the three outputs.
+ * AAR_SMOOTH_MODEL_CONSTANT_VELOCITY: H is what aar_track_smooth_system2 returns at mu = 0 for the same inputs; frame_cov, lag_cov and lag2_cov
+ * are UNSCALED and the report is that of aar_track_smooth_covariance.  One pass back down the elimination tree of the solve's cyclic reduction
+ * on pairs of frames (12x12 blocks); bit-reproducible, frame_cov symmetric to the bit, x_full not modified, no LM state left behind.  Each
+ * output and the report may be NULL.  num_frames = 0: AAR_OK, nothing written; 1: frame_cov[0] = V_0^-1; 2: pair 0 alone.  AAR_ERR_NUMERIC
+ * with nothing written on a non-positive pivot; the root's pivots count as non-positive when not above 64 eps times the largest diagonal
+ * entry of H_00 and H_11 (no detection in any frame: the prior alone is singular).  Huber problems are accepted; a problem with a
+ * communicator is AAR_ERR_UNSUPPORTED.
+ * AAR_SMOOTH_MODEL_RANDOM_WALK: aar_track_smooth_covariance itself, the same bits; lag2_cov != NULL is AAR_ERR_UNSUPPORTED with nothing
+ * written (the tridiagonal selected inverse does not contain that block).
+ * aar_track_smooth_covariance, _fit, _fit_terms and _query keep returning AAR_ERR_UNSUPPORTED under constant velocity. */
+int aar_track_smooth_covariance2(aar_problem *, const double *x_full, const aar_smooth_params *, double *frame_cov, double *lag_cov,
+                                 double *lag2_cov, aar_smooth_covariance_report *report);
 /* Fitting the smoother's noise levels from the recorded sequence itself: expectation-maximisation over
  *   sigma_px (the corner noise the data term fixes at 1 px), sigma_rot, sigma_trans (per sqrt(unit of frame_time)).
  * Only the ratios sigma / sigma_px enter aar_track_smooth's estimate: it is run at the EFFECTIVE sigmas sigma_rot / sigma_px and
