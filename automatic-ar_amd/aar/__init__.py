@@ -40,7 +40,7 @@ SYMBOLS = [
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_system2", "aar_smooth_solve_launches", "aar_track_smooth_covariance", "aar_track_smooth_covariance2",
-    "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms",
+    "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms", "aar_track_smooth_fit2", "aar_track_smooth_fit_terms2",
     "aar_smooth_query_validate", "aar_track_smooth_query",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
@@ -555,6 +555,8 @@ def lib():
     L.aar_track_smooth_fit.argtypes = [C.c_void_p, dp, C.POINTER(CLmParams), C.c_void_p, C.POINTER(CSmoothFitParams), dp,
                                        C.POINTER(CSmoothFitReport)]
     L.aar_track_smooth_fit_terms.argtypes = [C.c_void_p, dp, C.c_void_p, dp, dp]
+    L.aar_track_smooth_fit2.argtypes = L.aar_track_smooth_fit.argtypes
+    L.aar_track_smooth_fit_terms2.argtypes = L.aar_track_smooth_fit_terms.argtypes
     L.aar_tracker_default_params.argtypes = [C.POINTER(CTrackerParams)]
     L.aar_tracker_default_params.restype = None
     L.aar_tracker_params_validate.argtypes = [C.POINTER(CDataset), C.POINTER(CTrackerParams)]
@@ -1788,6 +1790,34 @@ class Problem:
         sp.check_lengths(F)
         terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(4)
         _check(lib().aar_track_smooth_fit_terms(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
+        return terms[:max(F - 1, 0)], sums
+
+    def track_smooth_fit2(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_fit2, either model: track_smooth_fit's arguments and returns.  Under constant velocity sigma_rot0, sigma_trans0 are
+        physical and held; smooth afterwards with report["sigma_rot_eff"], report["sigma_trans_eff"] and sigma_rot0 / report["sigma_px"],
+        sigma_trans0 / report["sigma_px"]."""
+        x = np.array(self._x(x_full), dtype=np.float64)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(self.ds.num_frames)
+        fp = fit if isinstance(fit, CSmoothFitParams) else smooth_fit_params(**(fit or {}))
+        path = np.zeros((max(int(fp.max_iters), 0) + 1, 3))
+        rep = CSmoothFitReport()
+        rep.struct_size = C.sizeof(CSmoothFitReport)
+        _check(lib().aar_track_smooth_fit2(self.handle, _dptr(x), C.byref(params) if params is not None else None, C.byref(sp.c), C.byref(fp),
+                                           _dptr(path), C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothFitReport._fields_ if k != "struct_size"}
+        return x, report, path[:report["iterations"] + 1]
+
+    def track_smooth_fit_terms2(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_fit_terms2, either model: one E-step at x_full and the given effective sigmas, no smoothing.  Returns (pair_terms
+        [F-1, 4] = a_r, u_r, a_t, u_t with entry 0 = pair 0, sums [6] = A_r, U_r, A_t, U_t over the terms 1 .. F-2, u_0, pair 0's cost; the
+        last two are zero under the random walk, whose sums run over every pair)."""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(F)
+        terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(6)
+        _check(lib().aar_track_smooth_fit_terms2(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
         return terms[:max(F - 1, 0)], sums
 
     def track_smooth_query(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True, model=None, sigma_rot0=0.0, sigma_trans0=0.0):

@@ -2562,6 +2562,20 @@ struct SmoothCvCall {
     ~SmoothCvCall() { if (base) (void)hipFree(base); }
 };
 
+// lambda [F][2] from the sigmas and the frame times, onto the device (F > 1): entry 0 pair 0, entry f term f, entry F-1 zero
+int smooth_cv_upload_lambda(aar_problem *pb, const aar_smooth_params &sp, const SmoothCvCall &c) {
+    const int F = pb->P.F;
+    std::vector<double> lam(2 * (size_t)F, 0.0);
+    auto dt = [&](int f) { return sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0; };
+    lam[0] = 1.0 / (sp.sigma_rot0 * sp.sigma_rot0 * dt(0));
+    lam[1] = 1.0 / (sp.sigma_trans0 * sp.sigma_trans0 * dt(0));
+    for (int f = 1; f + 1 < F; f++) {
+        lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt(f));
+        lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt(f));
+    }
+    return copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double));
+}
+
 int smooth_cv_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCvCall &c) {
     DeviceProblem &P = pb->P;
     const int F = P.F;
@@ -2571,16 +2585,10 @@ int smooth_cv_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCvCall
     smooth_cv_work_carve(c.w, c.base, F);
     int rc = AAR_OK;
     if (F > 1) {
-        std::vector<double> lam(2 * (size_t)F, 0.0), ratio((size_t)F, 0.0);
+        std::vector<double> ratio((size_t)F, 0.0);
         auto dt = [&](int f) { return sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0; };
-        lam[0] = 1.0 / (sp.sigma_rot0 * sp.sigma_rot0 * dt(0));
-        lam[1] = 1.0 / (sp.sigma_trans0 * sp.sigma_trans0 * dt(0));
-        for (int f = 1; f + 1 < F; f++) {
-            lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt(f));
-            lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt(f));
-            ratio[f] = dt(f) / dt(f - 1);
-        }
-        if ((rc = copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double)))) return rc;
+        for (int f = 1; f + 1 < F; f++) ratio[f] = dt(f) / dt(f - 1);
+        if ((rc = smooth_cv_upload_lambda(pb, sp, c))) return rc;
         if ((rc = copy_h2d(pb, c.w.ratio, ratio.data(), ratio.size() * sizeof(double)))) return rc;
     }
     if (F) HIP_TRY(hipMemcpyAsync(c.w.z[0], P.z[pb->cur] + 6 * (size_t)P.A, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
@@ -2592,7 +2600,8 @@ int smooth_rw_only(const aar_smooth_params &sp, const char *who) {
     if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
         return set_error(AAR_ERR_UNSUPPORTED, "%s: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY is not supported here (this entry works on the selected "
                                               "inverse of the block-tridiagonal system; the pose covariance under constant velocity is "
-                                              "aar_track_smooth_covariance2); use AAR_SMOOTH_MODEL_RANDOM_WALK", who);
+                                              "aar_track_smooth_covariance2, the sigma fit aar_track_smooth_fit2 and aar_track_smooth_fit_terms2); "
+                                              "use AAR_SMOOTH_MODEL_RANDOM_WALK", who);
     return AAR_OK;
 }
 
@@ -2699,6 +2708,17 @@ int smooth_selinv_launch(aar_problem *pb, const SmoothCall &c, int cur, double *
     int launches = 2;
     launches += launch_smooth_solve(c.w, F, 0.0, pb->stream);
     launches += launch_smooth_selinv(c.w, F, S, R, pb->stream);
+    return launches;
+}
+
+// The same under constant velocity: H at c.w.z[cur] (mu = 0) with its costs into c.w.res, the supernode reduction, the selected inverse on
+// area (smooth_cv_selinv_doubles(F) doubles) with fc, lc, l2 [F][36] pointing into it (F > 0).  Launches only; returns their number.
+int smooth_cv_selinv_launch(aar_problem *pb, const SmoothCvCall &c, int cur, double *area, double **fc, double **lc, double **l2) {
+    const int F = pb->P.F;
+    launch_smooth_cv_eval(pb->P, pb->cur, c.w, cur, /*with_j=*/true, pb->stream);
+    int launches = 2;
+    launches += launch_smooth_cv_solve(c.w, F, 0.0, pb->stream);
+    launches += launch_smooth_cv_selinv(c.w, F, area, fc, lc, l2, pb->stream);
     return launches;
 }
 
@@ -2936,10 +2956,7 @@ int aar_track_smooth_covariance2(aar_problem *pb, const double *x_full, const aa
         HIP_TRY(hipMalloc((void **)&sel.base, n * sizeof(double)));
         HIP_TRY(hipMemsetAsync(sel.base, 0, n * sizeof(double), pb->stream));
         double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
-        launch_smooth_cv_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
-        r.launches = 2;
-        r.launches += launch_smooth_cv_solve(c.w, F, 0.0, pb->stream);
-        r.launches += launch_smooth_cv_selinv(c.w, F, sel.base, &fc, &lc, &l2, pb->stream);
+        r.launches = smooth_cv_selinv_launch(pb, c, 0, sel.base, &fc, &lc, &l2);
         pb->launches += r.launches;
         double res[8];
         int32_t flag = 0;
@@ -3192,6 +3209,182 @@ int aar_track_smooth_fit(aar_problem *pb, double *x_full, const aar_lm_params *p
     HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.w.z[s.cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
     if ((rc = check_async("smoothing fit kernels"))) return rc;
     if ((rc = smooth_download(pb, x_full))) return rc;
+    if (report) {
+        r.struct_size = report->struct_size;
+        r.sigma_px = std::sqrt(q); r.sigma_rot = std::sqrt(s_r); r.sigma_trans = std::sqrt(s_t);
+        r.sigma_rot_eff = eff.sigma_rot; r.sigma_trans_eff = eff.sigma_trans;
+        r.launches = (int32_t)(pb->launches - launches0);
+        r.a_rot = rec[0]; r.u_rot = rec[1]; r.a_trans = rec[2]; r.u_trans = rec[3]; r.u_data = u_d; r.data_cost = rec[4];
+        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same fit under the constant-velocity prior (smooth_cv_fit_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the selected inverse's area, the entries' terms and the record the host reads: one allocation
+struct SmoothCvFitBuf {
+    SmoothCvCall mem;
+    double *area = nullptr, *terms = nullptr, *rec = nullptr;
+};
+
+int smooth_cv_fit_alloc(aar_problem *pb, SmoothCvFitBuf &b) {
+    const size_t F = (size_t)pb->P.F, na = smooth_cv_selinv_doubles((int)F), n = na + 4 * (F - 1) + 8;
+    HIP_TRY(hipMalloc((void **)&b.mem.base, n * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(b.mem.base, 0, n * sizeof(double), pb->stream));
+    b.area = b.mem.base; b.terms = b.area + na; b.rec = b.terms + 4 * (F - 1);
+    return AAR_OK;
+}
+
+// the E-step at c.w.z[cur] with the lambda on the device (built with eff's sigmas): launches, then the one read-back of rec [8] =
+// A_r, U_r, A_t, U_t over the terms 1 .. F-2, data cost, prior cost, pivot flag, u_0
+int smooth_cv_fit_estep(aar_problem *pb, const SmoothCvCall &c, int cur, const aar_smooth_params &eff, const SmoothCvFitBuf &b, double rec[8],
+                        const char *who) {
+    const int F = pb->P.F;
+    double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
+    int launches = smooth_cv_selinv_launch(pb, c, cur, b.area, &fc, &lc, &l2);
+    launches += launch_smooth_cv_fit_terms(c.w, cur, F, eff.sigma_rot, eff.sigma_rot0, eff.sigma_trans0, fc, lc, l2, b.terms, b.rec, pb->stream);
+    pb->launches += launches;
+    int rc = copy_d2h(pb, rec, b.rec, 8 * sizeof(double));
+    if (rc) return rc;
+    if (rec[6] != 0.0)
+        return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the block-pentadiagonal elimination (the frames' detections and the prior do "
+                                          "not determine every pose)", who);
+    return AAR_OK;
+}
+
+// what both entries refuse under constant velocity, after smooth_entry
+int smooth_cv_fit_entry(aar_problem *pb, const char *who) {
+    if (pb->with_huber)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: the problem was created with_huber; the Huber weights break the Gaussian data model the fit "
+                                              "rests on", who);
+    if (pb->L.F < 3)
+        return set_error(AAR_ERR_INVALID, "%s: num_frames = %d, the fit under AAR_SMOOTH_MODEL_CONSTANT_VELOCITY needs at least one "
+                                          "second-difference term (three frames)", who, (int)pb->L.F);
+    if (pb->P.N < 1) return set_error(AAR_ERR_INVALID, "%s: the problem has no detections", who);
+    return AAR_OK;
+}
+
+}  // namespace
+
+int aar_track_smooth_fit_terms2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *pair_terms, double sums[6]) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit_terms2: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit_terms2");
+    if (rc) return rc;
+    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
+        if ((rc = aar_track_smooth_fit_terms(pb, x_full, sp_in, pair_terms, sums))) return rc;
+        if (sums) sums[4] = sums[5] = 0.0;
+        return AAR_OK;
+    }
+    if ((rc = smooth_cv_fit_entry(pb, "aar_track_smooth_fit_terms2"))) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCvCall c;
+    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
+    SmoothCvFitBuf b;
+    if ((rc = smooth_cv_fit_alloc(pb, b))) return rc;
+    double rec[8], pair0 = 0.0;
+    if ((rc = smooth_cv_fit_estep(pb, c, 0, sp, b, rec, "aar_track_smooth_fit_terms2"))) return rc;
+    if ((rc = copy_d2h(pb, &pair0, c.w.Pe[0], sizeof pair0))) return rc;   // the evaluation's cost of pair 0
+    if ((rc = check_async("smoothing fit kernels"))) return rc;
+    if (pair_terms && (rc = copy_d2h(pb, pair_terms, b.terms, 4 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    if (sums) {
+        for (int i = 0; i < 4; i++) sums[i] = rec[i];
+        sums[4] = rec[7];
+        sums[5] = pair0;
+    }
+    return AAR_OK;
+}
+
+int aar_track_smooth_fit2(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, const aar_smooth_fit_params *fp_in,
+                          double *path, aar_smooth_fit_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit2: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit2");
+    if (rc) return rc;
+    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return aar_track_smooth_fit(pb, x_full, prm, sp_in, fp_in, path, report);
+    aar_smooth_fit_params fp;
+    if (fp_in) {
+        if ((rc = aar_smooth_fit_params_validate(fp_in))) return rc;
+        (void)smooth_fit_params_read(fp_in, &fp);
+    } else {
+        aar_smooth_fit_default_params(&fp);
+    }
+    if ((rc = smooth_cv_fit_entry(pb, "aar_track_smooth_fit2"))) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    aar_lm_params p;
+    if (prm) p = *prm; else aar_lm_default_params(&p);
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    const int F = P.F;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t launches0 = pb->launches;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(P, pb->cur, pb->stream);
+    SmoothCvCall c;
+    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;   // lambda at the start values, the ratios once
+    SmoothCvFitBuf b;
+    if ((rc = smooth_cv_fit_alloc(pb, b))) return rc;
+    // the variances: q = sigma_px^2, s_r, s_t physical; pair 0's sigmas physical and held; the smoother runs at sigma / sqrt(q)
+    double q = 1.0, s_r = sp.sigma_rot * sp.sigma_rot, s_t = sp.sigma_trans * sp.sigma_trans;
+    aar_smooth_fit_report r;
+    memset(&r, 0, sizeof r);
+    std::vector<double> rows;   // the path, handed over only when the fit has succeeded
+    rows.insert(rows.end(), {1.0, sp.sigma_rot, sp.sigma_trans});
+    aar_smooth_params eff = sp;   // frame_time kept, the sigmas replaced
+    SmoothLm s;
+    const SmoothCvOps ops{pb, c.w};
+    const double terms_n = 3.0 * (double)(F - 2);
+    double rec[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u_d = 0.0;
+    r.stop_code = 2;
+    for (int it = 0; it < fp.max_iters; it++) {
+        if (it > 0 && (rc = smooth_cv_upload_lambda(pb, eff, c))) return rc;
+        if ((rc = smooth_lm_loop(pb, ops, p, s))) return rc;
+        r.lm_steps += s.iters;
+        if ((rc = smooth_cv_fit_estep(pb, c, s.cur, eff, b, rec, "aar_track_smooth_fit2"))) return rc;
+        const double er2 = eff.sigma_rot * eff.sigma_rot, et2 = eff.sigma_trans * eff.sigma_trans;
+        u_d = 6.0 * (double)F - rec[1] / er2 - rec[3] / et2 - rec[7];
+        const double n_r = fp.estimate_rot ? (rec[0] + q * rec[1]) / terms_n : s_r;
+        const double n_t = fp.estimate_trans ? (rec[2] + q * rec[3]) / terms_n : s_t;
+        const double n_q = fp.estimate_px ? (rec[4] + q * u_d) / (8.0 * (double)P.N) : q;
+        const double was[3] = {q, s_r, s_t}, now[3] = {n_q, n_r, n_t};
+        const char *names[3] = {"sigma_px", "sigma_rot", "sigma_trans"};
+        double change = 0.0;
+        for (int i = 0; i < 3; i++) {
+            if (!(now[i] > 0.0) || !std::isfinite(now[i]))
+                return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_fit2: iteration %d: the M-step gives the variance %g for %s", it + 1, now[i], names[i]);
+            change = std::max(change, std::fabs(std::sqrt(now[i]) - std::sqrt(was[i])) / std::sqrt(was[i]));
+        }
+        q = n_q; s_r = n_r; s_t = n_t;
+        const double sq = std::sqrt(q);
+        eff.sigma_rot = std::sqrt(s_r / q);
+        eff.sigma_trans = std::sqrt(s_t / q);
+        eff.sigma_rot0 = sp.sigma_rot0 / sq;
+        eff.sigma_trans0 = sp.sigma_trans0 / sq;
+        r.iterations = it + 1;
+        r.last_rel_change = change;
+        rows.insert(rows.end(), {sq, std::sqrt(s_r), std::sqrt(s_t)});
+        if (change < fp.rel_tol) { r.stop_code = 1; break; }
+    }
+    // the track at the fitted values
+    if ((rc = smooth_cv_upload_lambda(pb, eff, c))) return rc;
+    if ((rc = smooth_lm_loop(pb, ops, p, s))) return rc;
+    r.lm_steps += s.iters;
+    HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.w.z[s.cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    if ((rc = check_async("smoothing fit kernels"))) return rc;
+    if ((rc = smooth_download(pb, x_full))) return rc;
+    if (path) std::copy(rows.begin(), rows.end(), path);
     if (report) {
         r.struct_size = report->struct_size;
         r.sigma_px = std::sqrt(q); r.sigma_rot = std::sqrt(s_r); r.sigma_trans = std::sqrt(s_t);

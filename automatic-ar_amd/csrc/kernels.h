@@ -350,6 +350,11 @@ int smooth_cv_solve_launches(int F);                                            
 size_t smooth_cv_selinv_doubles(int F);
 int smooth_cv_selinv_launches(int F);
 int launch_smooth_cv_selinv(const SmoothCvWork &w, int F, double *area, double **fc, double **lc, double **l2, hipStream_t st);   // returns its launches
+// the terms' expected sufficient statistics from fc, lc, l2 and z[cur] (smooth_cv_fit_kernels.hip), F >= 3: terms [F-1][4]
+// = a_r, u_r, a_t, u_t (entry 0: pair 0), rec [8] = A_r, U_r, A_t, U_t over the terms 1 .. F-2, data cost, prior cost, pivot flag, u_0;
+// returns its launches
+int launch_smooth_cv_fit_terms(const SmoothCvWork &w, int cur, int F, double sigma_rot, double sigma_rot0, double sigma_trans0, const double *fc,
+                               const double *lc, const double *l2, double *terms, double *rec, hipStream_t st);
 
 // live tracker (live_kernels.hip): one frame per push, the whole LM of the window in ONE launch of one workgroup
 constexpr int LIVE_MAX_W = 16;            // window frames (AAR_TRACKER_MAX_LAG + 1)

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance]] [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas]] [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -258,10 +258,15 @@ int main(int argc, char *argv[]) {
     bool smooth_covariance = false;
     // ... -cv <sigma_rot0> <sigma_trans0> (only with -smooth) smooths under the constant-velocity prior: the -smooth sigmas
     // bound the deviation from constant velocity, these two the first pair's motion.  Not with -smooth-covariance, -fit-sigmas or -resample
+    // (the fit under this prior is -cv-fit-sigmas)
     bool smooth_cv = false;
     // ... -cv-covariance (only with -smooth and -cv) writes final.smooth_covariance.yaml under the constant-velocity prior, in -smooth-covariance's
     // format (MultiCamMapper::track_smooth_covariance with the model)
     bool cv_covariance = false;
+    // ... -cv-fit-sigmas (only with -smooth and -cv) first fits the corner noise and the two -smooth sigmas under the constant-velocity prior, the
+    // -cv sigmas held as physical values (MultiCamMapper::fit_smooth_sigmas with the model), and smooths with the fitted
+    // effective values and the -cv sigmas over the fitted corner noise
+    bool cv_fit_sigmas = false;
     double smooth_sigma0[2] = {0.0, 0.0};
     int smooth_cv_args = 0;
     // ... -fit-sigmas (only with -smooth) first fits the corner noise and the two sigmas to the sequence, from the given values as the start
@@ -321,6 +326,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-smooth-covariance") { smooth_covariance = true; arg_flag = NONE; }
         else if (a == "-cv") { smooth_cv = true; smooth_cv_args = 0; arg_flag = SmoothCv; }
         else if (a == "-cv-covariance") { cv_covariance = true; arg_flag = NONE; }
+        else if (a == "-cv-fit-sigmas") { cv_fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-fit-sigmas") { fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-resample") { resample = true; resample_n = 0; arg_flag = Resample; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
@@ -437,6 +443,7 @@ int main(int argc, char *argv[]) {
     if (smooth_covariance && !smooth) return print_usage(argv[0]);
     if (smooth_cv && (!smooth || smooth_cv_args != 2 || smooth_covariance || fit_sigmas || resample)) return print_usage(argv[0]);
     if (cv_covariance && (!smooth || !smooth_cv)) return print_usage(argv[0]);
+    if (cv_fit_sigmas && (!smooth || !smooth_cv || live)) return print_usage(argv[0]);
     if (fit_sigmas && (!smooth || live)) return print_usage(argv[0]);
     if (resample && (!smooth || live || resample_n < 2)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
@@ -646,6 +653,21 @@ int main(int argc, char *argv[]) {
                 cout.precision(keep);
                 smooth_sigma[0] = fr.sigma_rot_eff;
                 smooth_sigma[1] = fr.sigma_trans_eff;
+            }
+            if (cv_fit_sigmas) {
+                aar::MultiCamMapper::SmoothFit sf;
+                mcm.fit_smooth_sigmas(smooth_sigma[0], smooth_sigma[1], AAR_SMOOTH_MODEL_CONSTANT_VELOCITY, smooth_sigma0[0], smooth_sigma0[1], sf);
+                const aar_smooth_fit_report &fr = sf.report;
+                const streamsize keep = cout.precision(10);
+                cout << "smooth-cv-fit: sigma_px " << fr.sigma_px << " sigma_rot " << fr.sigma_rot << " sigma_trans " << fr.sigma_trans << " sigma_rot_eff "
+                     << fr.sigma_rot_eff << " sigma_trans_eff " << fr.sigma_trans_eff << " sigma_rot0_eff " << smooth_sigma0[0] / fr.sigma_px
+                     << " sigma_trans0_eff " << smooth_sigma0[1] / fr.sigma_px << " after " << fr.iterations << " EM iterations (exit " << fr.stop_code
+                     << ", " << fr.lm_steps << " LM iterations) in " << fr.seconds << " s" << endl;
+                cout.precision(keep);
+                smooth_sigma[0] = fr.sigma_rot_eff;
+                smooth_sigma[1] = fr.sigma_trans_eff;
+                smooth_sigma0[0] /= fr.sigma_px;
+                smooth_sigma0[1] /= fr.sigma_px;
             }
             if (smooth_cv) mcm.track_smooth(smooth_sigma[0], smooth_sigma[1], AAR_SMOOTH_MODEL_CONSTANT_VELOCITY, smooth_sigma0[0], smooth_sigma0[1]);
             else mcm.track_smooth(smooth_sigma[0], smooth_sigma[1]);

@@ -688,6 +688,13 @@ void MultiCamMapper::track_smooth_query(double sigma_rot, double sigma_trans, co
 // The pixel noise and the motion sigmas fitted to the sequence itself (aar_track_smooth_fit), under track_smooth()'s model
 // (the frame ids as the time axis).  The frame poses end as the smoothed track at the fitted values.
 void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, SmoothFit &out, const aar_smooth_fit_params *fit) {
+    fit_smooth_sigmas(sigma_rot, sigma_trans, AAR_SMOOTH_MODEL_RANDOM_WALK, 0.0, 0.0, out, fit);
+}
+
+// ... under the motion model AAR_SMOOTH_MODEL_* (aar_track_smooth_fit2).  Constant velocity: sigma_rot / sigma_trans are the
+// start values of the second-difference terms, sigma_rot0 / sigma_trans0 the first pair's PHYSICAL sigmas, held; the random walk is the call above
+void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, SmoothFit &out,
+                                       const aar_smooth_fit_params *fit) {
     if (!data_) throw std::runtime_error("MultiCamMapper::fit_smooth_sigmas: no data set");
     mats2eVec();
     hubberDelta = 10;  // as track_smooth() (a mapper set_with_huber(true) is refused by the library: the fit needs the Gaussian data model)
@@ -710,6 +717,9 @@ void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, Smo
     sp.sigma_rot = sigma_rot;
     sp.sigma_trans = sigma_trans;
     sp.frame_time = F ? time.data() : nullptr;
+    sp.model = model;
+    sp.sigma_rot0 = sigma_rot0;
+    sp.sigma_trans0 = sigma_trans0;
     aar_smooth_fit_params fp;
     aar_smooth_fit_default_params(&fp);
     if (fit) {
@@ -720,7 +730,7 @@ void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, Smo
     out.path.assign(3 * ((size_t)fp.max_iters + 1), 0.0);
     memset(&out.report, 0, sizeof out.report);
     out.report.struct_size = sizeof out.report;
-    if (aar_track_smooth_fit(pb, x.data(), &p, &sp, &fp, out.path.data(), &out.report)) throw std::runtime_error(aar_last_error());
+    if (aar_track_smooth_fit2(pb, x.data(), &p, &sp, &fp, out.path.data(), &out.report)) throw std::runtime_error(aar_last_error());
     out.path.resize(3 * ((size_t)out.report.iterations + 1));
     if (aar_problem_extract_z(pb, x.data(), io_vec.data())) throw std::runtime_error(aar_last_error());   // (only the frame poses have moved)
     memcpy(data_->x_full, x.data(), sizeof(double) * aar_dataset_full_len(data_));   // ... also when the Config keeps them out of z

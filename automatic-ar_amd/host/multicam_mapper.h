@@ -431,6 +431,11 @@ class MultiCamMapper {
         std::vector<double> path;        // [report.iterations + 1][3] (sigma_px, sigma_rot, sigma_trans), the start values first
     };
     void fit_smooth_sigmas(double sigma_rot, double sigma_trans, SmoothFit &out, const aar_smooth_fit_params *fit = nullptr);   // throws std::runtime_error on failure
+    // ... under the motion model AAR_SMOOTH_MODEL_* (aar_track_smooth_fit2).  Constant velocity: sigma_rot / sigma_trans start
+    // the sigmas of the second-difference terms, sigma_rot0 / sigma_trans0 are the first pair's PHYSICAL sigmas and are held: smooth afterwards
+    // with report.sigma_rot_eff / sigma_trans_eff and sigma_rot0 / report.sigma_px, sigma_trans0 / report.sigma_px
+    void fit_smooth_sigmas(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, SmoothFit &out,
+                           const aar_smooth_fit_params *fit = nullptr);                            // throws std::runtime_error on failure
     // no counterpart in the reference as a method: apps/track.cpp's loop (:102-136) over the data set's frames, one frame per push through a
     // LiveTracker (below): each frame starts from its own pose in the data set, the frame ids are the time axis; every frame ends at its lagged
     // pose, the last window at aar_tracker_window's.  smooth = false needs lag = 0.  The pushes' results land in live_results.

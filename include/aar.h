@@ -590,9 +590,9 @@ typedef struct aar_smooth_params {
  *  so sigma_rot / sigma_trans bound the deviation from constant velocity per sqrt(unit of frame_time).  The expected motion is a function of
  *  the unknowns and the full Jacobian is used; H is block pentadiagonal and every try solves it by the cyclic reduction on pairs of frames
  *  (12x12 blocks).  rows = 8 num_obs + 6 (num_frames - 1) as before; pair_err[0] is pair 0, pair_err[f] term f.  rel_motion must be NULL
- *  (AAR_ERR_INVALID).  aar_track_smooth, aar_track_smooth_system2 and aar_track_smooth_covariance2 honour the model; aar_track_smooth_system,
- *  _covariance, _fit, _fit_terms and _query return AAR_ERR_UNSUPPORTED under constant velocity and write nothing (their selected inverse is the
- *  tridiagonal one). */
+ *  (AAR_ERR_INVALID).  aar_track_smooth, aar_track_smooth_system2, aar_track_smooth_covariance2, aar_track_smooth_fit2 and
+ *  aar_track_smooth_fit_terms2 honour the model; aar_track_smooth_system, _covariance, _fit, _fit_terms and _query return AAR_ERR_UNSUPPORTED
+ *  under constant velocity and write nothing (their selected inverse is the tridiagonal one). */
 #define AAR_SMOOTH_MODEL_RANDOM_WALK 0
 #define AAR_SMOOTH_MODEL_CONSTANT_VELOCITY 1
 typedef struct aar_smooth_report {
@@ -653,7 +653,8 @@ int aar_track_smooth_covariance(aar_problem *, const double *x_full, const aar_s
  * communicator is AAR_ERR_UNSUPPORTED.
  * AAR_SMOOTH_MODEL_RANDOM_WALK: aar_track_smooth_covariance itself, the same bits; lag2_cov != NULL is AAR_ERR_UNSUPPORTED with nothing
  * written (the tridiagonal selected inverse does not contain that block).
- * aar_track_smooth_covariance, _fit, _fit_terms and _query keep returning AAR_ERR_UNSUPPORTED under constant velocity. */
+ * aar_track_smooth_covariance, _fit, _fit_terms and _query keep returning AAR_ERR_UNSUPPORTED under constant velocity (the fit under that
+ * model is aar_track_smooth_fit2). */
 int aar_track_smooth_covariance2(aar_problem *, const double *x_full, const aar_smooth_params *, double *frame_cov, double *lag_cov,
                                  double *lag2_cov, aar_smooth_covariance_report *report);
 /* Fitting the smoother's noise levels from the recorded sequence itself: expectation-maximisation over
@@ -704,6 +705,32 @@ int aar_track_smooth_fit(aar_problem *, double *x_full, const aar_lm_params *, c
 /* One E-step at x_full and the given (effective) sigmas, without smoothing, for checking: pair_terms [num_frames-1][4] = a_r, u_r, a_t, u_t
  * (may be NULL), sums = A_r, U_r, A_t, U_t.  x_full is not modified.  Errors as aar_track_smooth_fit. */
 int aar_track_smooth_fit_terms(aar_problem *, const double *x_full, const aar_smooth_params *, double *pair_terms, double sums[4]);
+/* The fit for either model.  AAR_SMOOTH_MODEL_RANDOM_WALK: aar_track_smooth_fit / aar_track_smooth_fit_terms themselves,
+ * the same bits, sums[4] = sums[5] = 0.  AAR_SMOOTH_MODEL_CONSTANT_VELOCITY: the unknowns are sigma_px and the sigma_rot, sigma_trans of the
+ * second-difference terms 1 <= f <= num_frames - 2 (the size of an acceleration per sqrt(unit of frame_time)).  Pair 0's sigma_rot0 and
+ * sigma_trans0 are NOT estimated (one pair gives three samples each): they are held at the caller's values as PHYSICAL sigmas, so every
+ * smoothing runs at sigma_rot0 / sigma_px, sigma_trans0 / sigma_px next to the effective sigma_rot / sigma_px, sigma_trans / sigma_px.
+ * One iteration: aar_track_smooth from the previous track, H at mu = 0, its reduction and the blocks of aar_track_smooth_covariance2, all kept on
+ * the device; per term f over the frames p = f-1, c = f, n = f+1, with phi, e_t and the Jacobian rows M_p, M_c, M_n (rotation) and
+ * c = (r_f, -(1 + r_f), 1) (translation) of the term at the track, S_xy the blocks of H^-1 between the frames x, y
+ *   a_r = |phi|^2 / D_f,  u_r = sum_{x,y} tr(M_x S_xy^ww M_y^T) / D_f,   a_t = |e_t|^2 / D_f,  u_t = sum_{x,y} c_x c_y tr(S_xy^tt) / D_f
+ * summed over the terms 1 .. num_frames - 2 ONLY to A_r, U_r, A_t, U_t in a fixed order; entry 0 of the term array is pair 0 in the form of
+ * aar_track_smooth_fit, its share of the trace u_0 = u_r[0] / sigma_rot0_eff^2 + u_t[0] / sigma_trans0_eff^2;
+ *   U_d = 6 num_frames - U_r / sigma_rot_eff^2 - U_t / sigma_trans_eff^2 - u_0, and with q = sigma_px^2
+ *   sigma_rot^2 <- (A_r + q U_r) / (3 (num_frames - 2)),  sigma_trans^2 <- (A_t + q U_t) / (3 (num_frames - 2)),
+ *   q <- (data_cost + q U_d) / (8 num_obs),               all three from the old q.
+ * The loop, the stop rule, the final smoothing, path, the parameters and the report are aar_track_smooth_fit's.  report->sigma_rot_eff and
+ * sigma_trans_eff are the values for aar_smooth_params.sigma_rot / sigma_trans; the matching pair-0 values are sigma_rot0 / report->sigma_px
+ * and sigma_trans0 / report->sigma_px.  Bit-reproducible from call to call.
+ * AAR_ERR_INVALID: num_frames < 3, no detections, the parameter errors of aar_track_smooth_fit.  AAR_ERR_UNSUPPORTED: with_huber, a
+ * communicator.  AAR_ERR_NUMERIC: a non-positive pivot (with the root rule of aar_track_smooth_covariance2), an M-step that gives a variance
+ * that is not positive and finite.  On an error nothing is written: x_full, path and report keep their contents. */
+int aar_track_smooth_fit2(aar_problem *, double *x_full, const aar_lm_params *, const aar_smooth_params *, const aar_smooth_fit_params *,
+                          double *path, aar_smooth_fit_report *report);
+/* One E-step at x_full and the given (effective) sigmas, without smoothing, for checking: pair_terms [num_frames-1][4] = a_r, u_r, a_t, u_t,
+ * entry 0 = pair 0 (may be NULL), sums = A_r, U_r, A_t, U_t over the terms 1 .. num_frames - 2, u_0, pair 0's cost e_0^T L_0 e_0.  x_full is
+ * not modified.  Errors as aar_track_smooth_fit2. */
+int aar_track_smooth_fit_terms2(aar_problem *, const double *x_full, const aar_smooth_params *, double *pair_terms, double sums[6]);
 /* The smoothed track at any time: pose and covariance at query times that need not be frame times -- a display's vsync,
  * an IMU sample, a camera that is not genlocked.  The answer at a time t is what the smoother would report for a frame WITHOUT detections
  * inserted at t.  With t_0 < ... < t_{F-1} the frame times (frame_time, or 0, 1, 2, ...), z the frame poses of x_full, S_f, R_f the blocks
