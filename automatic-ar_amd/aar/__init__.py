@@ -41,7 +41,7 @@ SYMBOLS = [
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_system2", "aar_smooth_solve_launches", "aar_track_smooth_covariance", "aar_track_smooth_covariance2",
     "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms", "aar_track_smooth_fit2", "aar_track_smooth_fit_terms2",
-    "aar_smooth_query_validate", "aar_track_smooth_query",
+    "aar_smooth_query_validate", "aar_track_smooth_query", "aar_track_smooth_query2", "aar_track_smooth_query2_step", "aar_track_smooth_lag3",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
@@ -299,9 +299,9 @@ def smooth_solve_launches(num_frames, model="rw"):
     return int(lib().aar_smooth_solve_launches(int(num_frames), _SMOOTH_MODELS[model] if isinstance(model, str) else int(model)))
 
 
-def smooth_query_validate(num_frames, sigma_rot, sigma_trans, query_time, frame_time=None, rel_motion=None, struct_size=None):
+def smooth_query_validate(num_frames, sigma_rot, sigma_trans, query_time, frame_time=None, rel_motion=None, struct_size=None, **model):
     """aar_smooth_query_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message"""
-    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size)
+    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size, **model)
     sp.check_lengths(num_frames)
     qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
     _check(lib().aar_smooth_query_validate(int(num_frames), C.byref(sp.c), len(qt), _dptr(qt) if len(qt) else None))
@@ -549,6 +549,9 @@ def lib():
     L.aar_smooth_query_validate.argtypes = [C.c_int32, C.c_void_p, C.c_int64, dp]
     L.aar_track_smooth_query.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, dp, dp, dp, C.POINTER(C.c_int32),
                                          C.POINTER(CSmoothQueryReport)]
+    L.aar_track_smooth_query2.argtypes = L.aar_track_smooth_query.argtypes
+    L.aar_track_smooth_query2_step.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, dp, dp, dp]
+    L.aar_track_smooth_lag3.argtypes = [C.c_void_p, dp, C.c_void_p, dp]
     L.aar_smooth_fit_default_params.argtypes = [C.POINTER(CSmoothFitParams)]
     L.aar_smooth_fit_default_params.restype = None
     L.aar_smooth_fit_params_validate.argtypes = [C.POINTER(CSmoothFitParams)]
@@ -1836,6 +1839,46 @@ class Problem:
                                             _dptr(cov) if covariance else None, seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
         report = {k: getattr(rep, k) for k, _ in CSmoothQueryReport._fields_ if k != "struct_size"}
         return pose[:Q], cov[:Q] if covariance else None, seg[:Q], report
+
+    def track_smooth_query2(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_query2, either model: track_smooth_query's arguments and returns.  Under constant velocity the answer is one
+        Gauss-Newton step of the smoother for a frame without detections inserted at the query's time; covariance=False runs the same chain and
+        saves the copy of the blocks alone."""
+        x = self._x(x_full)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(self.ds.num_frames)
+        qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
+        Q = len(qt)
+        pose, seg = np.zeros((max(Q, 1), 6)), np.zeros(max(Q, 1), dtype=np.int32)
+        cov = np.zeros((max(Q, 1), 6, 6)) if covariance else None
+        rep = CSmoothQueryReport()
+        rep.struct_size = C.sizeof(CSmoothQueryReport)
+        _check(lib().aar_track_smooth_query2(self.handle, _dptr(x), C.byref(sp.c), Q, _dptr(qt) if Q else None, _dptr(pose),
+                                             _dptr(cov) if covariance else None, seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothQueryReport._fields_ if k != "struct_size"}
+        return pose[:Q], cov[:Q] if covariance else None, seg[:Q], report
+
+    def track_smooth_query2_step(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, model="cv", sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_query2_step (constant velocity, for checking): (start_pose [Q, 6], step [Q, 6]), the two summands of
+        track_smooth_query2's pose"""
+        x = self._x(x_full)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(self.ds.num_frames)
+        qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
+        Q = len(qt)
+        start, step = np.zeros((max(Q, 1), 6)), np.zeros((max(Q, 1), 6))
+        _check(lib().aar_track_smooth_query2_step(self.handle, _dptr(x), C.byref(sp.c), Q, _dptr(qt) if Q else None, _dptr(start), _dptr(step)))
+        return start[:Q], step[:Q]
+
+    def track_smooth_lag3(self, x_full, sigma_rot, sigma_trans, frame_time=None, model="cv", sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_lag3 (constant velocity, for checking): lag3_cov [F-3, 6, 6] = (H^-1)_{f,f+3}, UNSCALED"""
+        x = self._x(x_full)
+        F = self.ds.num_frames
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(F)
+        l3 = np.zeros((max(F - 3, 1), 6, 6))
+        _check(lib().aar_track_smooth_lag3(self.handle, _dptr(x), C.byref(sp.c), _dptr(l3)))
+        return l3[:max(F - 3, 0)]
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

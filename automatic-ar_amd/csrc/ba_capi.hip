@@ -2600,7 +2600,8 @@ int smooth_rw_only(const aar_smooth_params &sp, const char *who) {
     if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
         return set_error(AAR_ERR_UNSUPPORTED, "%s: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY is not supported here (this entry works on the selected "
                                               "inverse of the block-tridiagonal system; the pose covariance under constant velocity is "
-                                              "aar_track_smooth_covariance2, the sigma fit aar_track_smooth_fit2 and aar_track_smooth_fit_terms2); "
+                                              "aar_track_smooth_covariance2, the sigma fit aar_track_smooth_fit2 and aar_track_smooth_fit_terms2, "
+                                              "the track at any time aar_track_smooth_query2); "
                                               "use AAR_SMOOTH_MODEL_RANDOM_WALK", who);
     return AAR_OK;
 }
@@ -3494,6 +3495,152 @@ int aar_track_smooth_query(aar_problem *pb, const double *x_full, const aar_smoo
         memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
     }
     return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The constant-velocity smoothed track at any time (smooth_cv_query_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the chain of aar_track_smooth_query2 under constant velocity: H at mu = 0, its reduction and selected inverse, the lag-three blocks, the
+// queries.  cov == NULL saves the copy back alone (the pose depends on the block).  start, step: the start poses and delta_m (checking)
+int smooth_cv_query(aar_problem *pb, const double *x_full, const aar_smooth_params &sp, int64_t n_query, const double *query_time, double *pose,
+                    double *cov, int32_t *segment, double *start, double *step, aar_smooth_query_report *report, const char *who) {
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const size_t Q = (size_t)n_query;
+    int rc = AAR_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    aar_smooth_query_report r;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
+    r.num_vars = 6 * (int64_t)F;
+    r.num_queries = (int32_t)Q;
+    if (Q > 0) {
+        std::vector<double> ft((size_t)F);
+        for (int f = 0; f < F; f++) ft[f] = sp.frame_time ? sp.frame_time[f] : (double)f;
+        for (size_t i = 0; i < Q; i++) {
+            const int s = (int)(std::upper_bound(ft.begin(), ft.end(), query_time[i]) - ft.begin()) - 1;
+            if (s >= 0 && ft[s] == query_time[i]) r.num_on_frame++;
+            else if (s < 0 || s == F - 1) r.num_outside++;
+            else r.num_inside++;
+        }
+        pb->lm_ready = false;
+        pb->blocks_valid = false;
+        if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+        launch_unpack(P, pb->cur, pb->stream);
+        SmoothCvCall c, sel, out;
+        if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
+        const size_t na = smooth_cv_selinv_doubles(F);
+        HIP_TRY(hipMalloc((void **)&sel.base, na * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(sel.base, 0, na * sizeof(double), pb->stream));
+        // one allocation: ft [F] | query times [Q] | pose, start, step [Q][6] each | cov [Q][36] | l3 [F-3][36] | segment [Q] and the two pivot flags
+        const size_t n3 = 36 * (size_t)std::max(F - 3, 0), n_dbl = (size_t)F + 19 * Q + (cov ? 36 * Q : 0) + n3, n_int = Q + 2;
+        HIP_TRY(hipMalloc((void **)&out.base, n_dbl * sizeof(double) + n_int * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(out.base, 0, n_dbl * sizeof(double) + n_int * sizeof(int32_t), pb->stream));
+        double *d_ft = out.base, *d_qt = d_ft + F, *d_pose = d_qt + Q, *d_start = d_pose + 6 * Q, *d_step = d_start + 6 * Q;
+        double *d_cov = cov ? d_step + 6 * Q : nullptr, *d_l3 = d_step + 6 * Q + (cov ? 36 * Q : 0);
+        int32_t *d_seg = reinterpret_cast<int32_t *>(out.base + n_dbl), *d_flag = d_seg + Q;
+        if ((rc = copy_h2d(pb, d_ft, ft.data(), (size_t)F * sizeof(double)))) return rc;
+        if ((rc = copy_h2d(pb, d_qt, query_time, Q * sizeof(double)))) return rc;
+        double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
+        r.launches = smooth_cv_selinv_launch(pb, c, 0, sel.base, &fc, &lc, &l2);
+        r.launches += launch_smooth_cv_lag3(F, sel.base, d_l3, d_flag, pb->stream);
+        r.launches += launch_smooth_cv_query(F, c.w.z[0], d_ft, sp.sigma_rot, sp.sigma_trans, sp.sigma_rot0, sp.sigma_trans0, fc, lc, l2, d_l3,
+                                             (int64_t)Q, d_qt, d_pose, d_cov, d_start, d_step, d_seg, d_flag + 1, pb->stream);
+        pb->launches += r.launches;
+        double res[8];
+        int32_t flag = 0, qflag[2] = {0, 0};
+        if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+        if ((rc = copy_d2h(pb, qflag, d_flag, sizeof qflag))) return rc;
+        if ((rc = check_async("smoothing query kernels"))) return rc;
+        if (flag)
+            return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the block-pentadiagonal elimination (the frames' detections and the prior do "
+                                              "not determine every pose)", who);
+        if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a supernode block of the lag-three blocks", who);
+        if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a query's eliminations", who);
+        r.data_cost = res[0]; r.prior_cost = res[1];
+        if (cov && (rc = copy_d2h(pb, cov, d_cov, 36 * Q * sizeof(double)))) return rc;
+        if (pose && (rc = copy_d2h(pb, pose, d_pose, 6 * Q * sizeof(double)))) return rc;
+        if (start && (rc = copy_d2h(pb, start, d_start, 6 * Q * sizeof(double)))) return rc;
+        if (step && (rc = copy_d2h(pb, step, d_step, 6 * Q * sizeof(double)))) return rc;
+        if (segment && (rc = copy_d2h(pb, segment, d_seg, Q * sizeof(int32_t)))) return rc;
+        if ((rc = check_async("smoothing query kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+    }
+    const int64_t dof = r.num_residuals - r.num_vars;
+    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
+}  // namespace
+
+int aar_track_smooth_query2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
+                            double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query2: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query2");
+    if (rc) return rc;
+    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return aar_track_smooth_query(pb, x_full, sp_in, n_query, query_time, pose, cov, segment, report);
+    if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
+    return smooth_cv_query(pb, x_full, sp, n_query, query_time, pose, cov, segment, nullptr, nullptr, report, "aar_track_smooth_query2");
+}
+
+int aar_track_smooth_query2_step(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
+                                 double *start_pose, double *step) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query2_step: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query2_step");
+    if (rc) return rc;
+    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_query2_step: model = AAR_SMOOTH_MODEL_RANDOM_WALK has no step (the pose of "
+                                              "aar_track_smooth_query is a closed form); use AAR_SMOOTH_MODEL_CONSTANT_VELOCITY");
+    if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
+    return smooth_cv_query(pb, x_full, sp, n_query, query_time, nullptr, nullptr, nullptr, start_pose, step, nullptr, "aar_track_smooth_query2_step");
+}
+
+int aar_track_smooth_lag3(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *lag3_cov) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_lag3: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_lag3");
+    if (rc) return rc;
+    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_lag3: model = AAR_SMOOTH_MODEL_RANDOM_WALK is not supported (the lag-three blocks "
+                                              "belong to the selected inverse on supernodes of the block-pentadiagonal system); use "
+                                              "AAR_SMOOTH_MODEL_CONSTANT_VELOCITY");
+    const int F = pb->P.F;
+    if (F < 4) return AAR_OK;
+    HIP_TRY(hipSetDevice(pb->device));
+    pb->lm_ready = false;
+    pb->blocks_valid = false;
+    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+    launch_unpack(pb->P, pb->cur, pb->stream);
+    SmoothCvCall c, sel;
+    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
+    const size_t na = smooth_cv_selinv_doubles(F), n3 = 36 * (size_t)(F - 3);
+    HIP_TRY(hipMalloc((void **)&sel.base, (na + n3 + 1) * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(sel.base, 0, (na + n3 + 1) * sizeof(double), pb->stream));
+    double *fc = nullptr, *lc = nullptr, *l2 = nullptr, *d_l3 = sel.base + na;
+    int32_t *d_flag = reinterpret_cast<int32_t *>(d_l3 + n3);
+    pb->launches += smooth_cv_selinv_launch(pb, c, 0, sel.base, &fc, &lc, &l2);
+    pb->launches += launch_smooth_cv_lag3(F, sel.base, d_l3, d_flag, pb->stream);
+    int32_t flag = 0, f3 = 0;
+    if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+    if ((rc = copy_d2h(pb, &f3, d_flag, sizeof f3))) return rc;
+    if ((rc = check_async("smoothing query kernels"))) return rc;
+    if (flag)
+        return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_lag3: non-positive pivot in the block-pentadiagonal elimination (the frames' detections "
+                                          "and the prior do not determine every pose)");
+    if (f3) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_lag3: non-positive pivot in a supernode block of the lag-three blocks");
+    if (lag3_cov && (rc = copy_d2h(pb, lag3_cov, d_l3, n3 * sizeof(double)))) return rc;
+    return check_async("smoothing query kernels");
 }
 
 int aar_set_kernel_profiling(aar_problem *pb, int on) {

@@ -350,6 +350,14 @@ int smooth_cv_solve_launches(int F);                                            
 size_t smooth_cv_selinv_doubles(int F);
 int smooth_cv_selinv_launches(int F);
 int launch_smooth_cv_selinv(const SmoothCvWork &w, int F, double *area, double **fc, double **lc, double **l2, hipStream_t st);   // returns its launches
+// the constant-velocity track at any time (smooth_cv_query_kernels.hip).  launch_smooth_cv_lag3: l3 [F-3][36], l3[f] =
+// (H^-1)_{f,f+3}, from the area launch_smooth_cv_selinv worked on (its S and R[0] stay there); no launch below four frames.
+// launch_smooth_cv_query: pose, covariance block and segment at Q > 0 query times from z [F][6], the frame times ft [F] and the blocks by lag;
+// cov, start (the start poses) and step (delta_m) may be NULL.  All pointers on the device; flag zeroed by the caller; both return their launches
+int launch_smooth_cv_lag3(int F, const double *area, double *l3, int32_t *flag, hipStream_t st);
+int launch_smooth_cv_query(int F, const double *z, const double *ft, double sigma_rot, double sigma_trans, double sigma_rot0, double sigma_trans0,
+                           const double *fc, const double *lc, const double *l2, const double *l3, int64_t Q, const double *qt, double *pose,
+                           double *cov, double *start, double *step, int32_t *seg, int32_t *flag, hipStream_t st);
 // the terms' expected sufficient statistics from fc, lc, l2 and z[cur] (smooth_cv_fit_kernels.hip), F >= 3: terms [F-1][4]
 // = a_r, u_r, a_t, u_t (entry 0: pair 0), rec [8] = A_r, U_r, A_t, U_t over the terms 1 .. F-2, data cost, prior cost, pivot flag, u_0;
 // returns its launches

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas]] [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -276,6 +276,9 @@ int main(int argc, char *argv[]) {
     // pose and 6x6 covariance to final.resampled.yaml (MultiCamMapper::track_smooth_query)
     bool resample = false;
     int resample_n = 0;
+    // ... -cv-resample <n> (only with -smooth and -cv, n >= 2) writes final.resampled.yaml under the constant-velocity prior, in -resample's format
+    // (MultiCamMapper::track_smooth_query with the model)
+    bool cv_resample = false;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
     // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
@@ -329,6 +332,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-cv-fit-sigmas") { cv_fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-fit-sigmas") { fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-resample") { resample = true; resample_n = 0; arg_flag = Resample; }
+        else if (a == "-cv-resample") { cv_resample = true; resample_n = 0; arg_flag = Resample; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
@@ -446,6 +450,7 @@ int main(int argc, char *argv[]) {
     if (cv_fit_sigmas && (!smooth || !smooth_cv || live)) return print_usage(argv[0]);
     if (fit_sigmas && (!smooth || live)) return print_usage(argv[0]);
     if (resample && (!smooth || live || resample_n < 2)) return print_usage(argv[0]);
+    if (cv_resample && (!smooth || !smooth_cv || live || resample || resample_n < 2)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
@@ -705,7 +710,7 @@ int main(int argc, char *argv[]) {
             }
         }
     }
-    if (smooth && resample) {
+    if (smooth && (resample || cv_resample)) {
         const string rs_path = folder_path + "/final.resampled.yaml";
         try {
             // every gap of frame ids cut into resample_n equal parts; entry k * resample_n is frame k itself
@@ -718,7 +723,10 @@ int main(int argc, char *argv[]) {
                     for (int k = 1; k < resample_n; k++) times.push_back(ta + ((double)ds->frame_ids[f + 1] - ta) * ((double)k / (double)resample_n));
             }
             aar::MultiCamMapper::SmoothQuery q;
-            mcm.track_smooth_query(smooth_sigma[0], smooth_sigma[1], times, q);
+            if (cv_resample)
+                mcm.track_smooth_query(smooth_sigma[0], smooth_sigma[1], AAR_SMOOTH_MODEL_CONSTANT_VELOCITY, smooth_sigma0[0], smooth_sigma0[1], times, q);
+            else
+                mcm.track_smooth_query(smooth_sigma[0], smooth_sigma[1], times, q);
             FILE *fp = fopen(rs_path.c_str(), "w");
             if (!fp) throw runtime_error("cannot write " + rs_path);
             fprintf(fp, "%%YAML:1.0\n---\nsigma2: %.17g\nresample: %d\nresampled_poses:\n", q.report.sigma2, resample_n);

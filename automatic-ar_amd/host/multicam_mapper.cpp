@@ -685,6 +685,39 @@ void MultiCamMapper::track_smooth_query(double sigma_rot, double sigma_trans, co
         throw std::runtime_error(aar_last_error());
 }
 
+// ... under the motion model AAR_SMOOTH_MODEL_* (aar_track_smooth_query2).  Constant velocity: one Gauss-Newton step of the
+// smoother for a frame without detections inserted at each time; the random walk is the call above
+void MultiCamMapper::track_smooth_query(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                        const std::vector<double> &query_time, SmoothQuery &out, bool covariance) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::track_smooth_query: no data set");
+    mats2eVec();
+    hubberDelta = 10;  // as track_smooth()
+    std::vector<double> x;
+    aar_problem *pb = detail::bind_problem(this, x);
+    if (aar_problem_merge_z(pb, io_vec.data(), x.data())) throw std::runtime_error(aar_last_error());
+    const int F = data_->num_frames;
+    std::vector<double> time(F);
+    for (int f = 0; f < F; f++) time[f] = (double)data_->frame_ids[f];
+    aar_smooth_params sp;
+    memset(&sp, 0, sizeof sp);
+    sp.struct_size = sizeof sp;
+    sp.sigma_rot = sigma_rot;
+    sp.sigma_trans = sigma_trans;
+    sp.frame_time = F ? time.data() : nullptr;
+    sp.model = model;
+    sp.sigma_rot0 = sigma_rot0;
+    sp.sigma_trans0 = sigma_trans0;
+    const size_t n = query_time.size();
+    out.pose.assign(6 * n, 0.0);
+    out.cov.assign(covariance ? 36 * n : 0, 0.0);
+    out.segment.assign(n, 0);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    if (aar_track_smooth_query2(pb, x.data(), &sp, (int64_t)n, query_time.data(), out.pose.data(), covariance ? out.cov.data() : nullptr,
+                                out.segment.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+}
+
 // The pixel noise and the motion sigmas fitted to the sequence itself (aar_track_smooth_fit), under track_smooth()'s model
 // (the frame ids as the time axis).  The frame poses end as the smoothed track at the fitted values.
 void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, SmoothFit &out, const aar_smooth_fit_params *fit) {

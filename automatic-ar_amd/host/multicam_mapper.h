@@ -422,6 +422,11 @@ class MultiCamMapper {
     };
     void track_smooth_query(double sigma_rot, double sigma_trans, const std::vector<double> &query_time, SmoothQuery &out,
                             bool covariance = true);                                              // throws std::runtime_error on failure
+    // ... under the motion model AAR_SMOOTH_MODEL_* with track_smooth()'s sigmas (aar_track_smooth_query2): under constant
+    // velocity the answer is one Gauss-Newton step of the smoother for the inserted frame -- extrapolated outside the recording and across
+    // gaps, not held; covariance = false saves the copy of the blocks alone
+    void track_smooth_query(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                            const std::vector<double> &query_time, SmoothQuery &out, bool covariance = true);   // throws std::runtime_error on failure
     // EXTENSION, no counterpart in the reference: the corner noise and track_smooth()'s two sigmas fitted to the sequence itself by EM
     // (aar_track_smooth_fit), from the effective start values sigma_rot, sigma_trans.  The frame poses end as the smoothed
     // track at the fitted values; report.sigma_rot_eff / sigma_trans_eff are what track_smooth() and the live tracker take.  A mapper

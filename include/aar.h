@@ -590,9 +590,9 @@ typedef struct aar_smooth_params {
  *  so sigma_rot / sigma_trans bound the deviation from constant velocity per sqrt(unit of frame_time).  The expected motion is a function of
  *  the unknowns and the full Jacobian is used; H is block pentadiagonal and every try solves it by the cyclic reduction on pairs of frames
  *  (12x12 blocks).  rows = 8 num_obs + 6 (num_frames - 1) as before; pair_err[0] is pair 0, pair_err[f] term f.  rel_motion must be NULL
- *  (AAR_ERR_INVALID).  aar_track_smooth, aar_track_smooth_system2, aar_track_smooth_covariance2, aar_track_smooth_fit2 and
- *  aar_track_smooth_fit_terms2 honour the model; aar_track_smooth_system, _covariance, _fit, _fit_terms and _query return AAR_ERR_UNSUPPORTED
- *  under constant velocity and write nothing (their selected inverse is the tridiagonal one). */
+ *  (AAR_ERR_INVALID).  aar_track_smooth, aar_track_smooth_system2, aar_track_smooth_covariance2, aar_track_smooth_fit2,
+ *  aar_track_smooth_fit_terms2 and aar_track_smooth_query2 honour the model; aar_track_smooth_system, _covariance, _fit, _fit_terms and _query
+ *  return AAR_ERR_UNSUPPORTED under constant velocity and write nothing (their selected inverse is the tridiagonal one). */
 #define AAR_SMOOTH_MODEL_RANDOM_WALK 0
 #define AAR_SMOOTH_MODEL_CONSTANT_VELOCITY 1
 typedef struct aar_smooth_report {
@@ -654,7 +654,7 @@ int aar_track_smooth_covariance(aar_problem *, const double *x_full, const aar_s
  * AAR_SMOOTH_MODEL_RANDOM_WALK: aar_track_smooth_covariance itself, the same bits; lag2_cov != NULL is AAR_ERR_UNSUPPORTED with nothing
  * written (the tridiagonal selected inverse does not contain that block).
  * aar_track_smooth_covariance, _fit, _fit_terms and _query keep returning AAR_ERR_UNSUPPORTED under constant velocity (the fit under that
- * model is aar_track_smooth_fit2). */
+ * model is aar_track_smooth_fit2, the track at any time aar_track_smooth_query2). */
 int aar_track_smooth_covariance2(aar_problem *, const double *x_full, const aar_smooth_params *, double *frame_cov, double *lag_cov,
                                  double *lag2_cov, aar_smooth_covariance_report *report);
 /* Fitting the smoother's noise levels from the recorded sequence itself: expectation-maximisation over
@@ -766,6 +766,45 @@ typedef struct aar_smooth_query_report {
 int aar_smooth_query_validate(int32_t num_frames, const aar_smooth_params *, int64_t n_query, const double *query_time);
 int aar_track_smooth_query(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_query, const double *query_time,
                            double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report);
+/* The same for either model.  AAR_SMOOTH_MODEL_RANDOM_WALK: aar_track_smooth_query itself, the same bits.
+ * AAR_SMOOTH_MODEL_CONSTANT_VELOCITY: the second-difference prior is not consistent under subdivision -- inserting a frame replaces up to two
+ * terms by up to three and the neighbours move -- so the answer at a time t is what ONE GAUSS-NEWTON STEP of the constant-velocity smoother
+ * reports for a frame m without detections inserted at t, linearised at x_full with m at a start pose z_m^0.  With H' the system of the
+ * augmented problem at mu = 0 at that point (aar_track_smooth_system2 on the augmented data set: pair 0 on its first two frames, a term on
+ * every inner frame with the ratio and L of its own times), g' its right-hand side and g the original one with zero at m:
+ *   cov  = (H'^-1)_mm, UNSCALED (report->sigma2 is that of the problem as given)
+ *   pose = z_m^0 + delta_m,  delta_m = [H'^-1 (g' - g)]_m, added as aar_track_smooth's trial point adds a step.  g' - g is the contribution
+ *          of the changed terms alone, on at most five frames: how far x_full is from converged does not enter.
+ * Translations are linear in the model, so delta_m is exactly m's component of the augmented minimiser; for rotations the error is of second
+ * order in the step.  The corrections of the other frames are not reported.  Start pose and changed terms:
+ *   inside a gap t_a < t < t_b (b = a + 1): z_m^0 the geodesic pose of aar_track_smooth_query; removed: term a (if a >= 1), term b (if
+ *     b <= num_frames - 2), pair 0 (if a = 0); added: the term on (a, m, b), on (a - 1, a, m), on (m, b, b + 1), pair 0 on (0, m) likewise
+ *   after the end (num_frames >= 2): R_m = R_e Exp(r log(R_{e-1}^T R_e)), t_m = t_e + r (t_e - t_{e-1}), e the last frame, r = (t - t_e) /
+ *     D_{e-1}; added: the term on (e - 1, e, m), zero at the start pose -- the pose is the constant-velocity extrapolation to rounding
+ *   before the start (num_frames >= 2): R_m = R_0 Exp(-r log(R_0^T R_1)), t_m = t_0 - r (t_1 - t_0), r = (t_0 - t) / D_0; removed: pair 0;
+ *     added: pair 0 on (m, 0) and the term on (m, 0, 1)
+ *   num_frames = 1, outside: aar_track_smooth_query's formula with sigma_rot0, sigma_trans0; the pose is z_0
+ *   on a frame time: z_f and frame_cov[f] of aar_track_smooth_covariance2, bit for bit
+ * Arguments, segment, the three counts and the report are aar_track_smooth_query's.  All on the device: the chain of
+ * aar_track_smooth_covariance2, whose blocks stay there, the lag-three blocks (H^-1)_{f,f+3}, and one wavefront per query.  cov = NULL still
+ * runs the whole chain -- the pose depends on the block -- and saves the copy back alone.  A query's bits depend on its time and the track
+ * alone; two calls give the same bits; blocks symmetric to the bit.  x_full is not modified, no LM state is left.  n_query = 0: AAR_OK, nothing
+ * written.  Problems created with_huber are accepted.
+ * AAR_ERR_INVALID: whatever aar_smooth_query_validate refuses.  AAR_ERR_UNSUPPORTED: a problem with a communicator.  AAR_ERR_NUMERIC, nothing
+ * written: a non-positive pivot in the elimination (with the root rule of aar_track_smooth_covariance2), in a supernode block of the lag-three
+ * blocks or in a query's own eliminations. */
+int aar_track_smooth_query2(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_query, const double *query_time,
+                            double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report);
+/* For checking, constant velocity only (the random walk is AAR_ERR_UNSUPPORTED): the two summands of aar_track_smooth_query2's pose on their
+ * own, start_pose [n_query][6] = z_m^0 and step [n_query][6] = delta_m (pose = start_pose + step to the bit; on a frame time z_f and zero).
+ * The sum rounds delta_m to eps |z_m|, so a step can only be held to its own accuracy from here.  Either may be NULL; errors as above. */
+int aar_track_smooth_query2_step(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_query, const double *query_time,
+                                 double *start_pose, double *step);
+/* For checking, constant velocity only (the random walk is AAR_ERR_UNSUPPORTED): lag3_cov [num_frames-3][36] = (H^-1)_{f,f+3}, row-major, the
+ * rows belong to frame f, UNSCALED -- the blocks aar_track_smooth_query2 takes beside those of aar_track_smooth_covariance2.  On supernodes
+ * (2k, 2k + 1) an even f is a block of the selected inverse; an odd f = 2k - 1 follows from the Gauss-Markov property of the block-tridiagonal
+ * chain, Sigma_{k-1,k+1} = Sigma_{k-1,k} Sigma_kk^-1 Sigma_{k,k+1}.  num_frames < 4: AAR_OK, nothing written.  Errors as above. */
+int aar_track_smooth_lag3(aar_problem *, const double *x_full, const aar_smooth_params *, double *lag3_cov);
 
 /* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
  * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are
