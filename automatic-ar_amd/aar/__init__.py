@@ -42,6 +42,7 @@ SYMBOLS = [
     "aar_smooth_params_validate", "aar_track_smooth", "aar_track_smooth_system", "aar_track_smooth_system2", "aar_smooth_solve_launches", "aar_track_smooth_covariance", "aar_track_smooth_covariance2",
     "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms", "aar_track_smooth_fit2", "aar_track_smooth_fit_terms2",
     "aar_smooth_query_validate", "aar_track_smooth_query", "aar_track_smooth_query2", "aar_track_smooth_query2_step", "aar_track_smooth_lag3",
+    "aar_smooth_relative_validate", "aar_track_smooth_relative",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
@@ -261,6 +262,12 @@ class CSmoothQueryReport(C.Structure):
                 ("num_on_frame", C.c_int32), ("num_outside", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double)]
 
 
+class CSmoothRelativeReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("data_cost", C.c_double),
+                ("prior_cost", C.c_double), ("sigma2", C.c_double), ("num_pairs", C.c_int32), ("num_direct", C.c_int32),
+                ("num_chained", C.c_int32), ("max_lag", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double)]
+
+
 class SmoothParams:
     """aar_smooth_params built from Python values (the arrays are kept alive with the struct)"""
 
@@ -305,6 +312,23 @@ def smooth_query_validate(num_frames, sigma_rot, sigma_trans, query_time, frame_
     sp.check_lengths(num_frames)
     qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
     _check(lib().aar_smooth_query_validate(int(num_frames), C.byref(sp.c), len(qt), _dptr(qt) if len(qt) else None))
+
+
+def _pairs(pairs):
+    """pairs [Q, 2] (or empty) as two contiguous int32 arrays"""
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    assert pr.size == 0 or (np.abs(pr).max() < 2 ** 31)
+    return np.ascontiguousarray(pr[:, 0], dtype=np.int32), np.ascontiguousarray(pr[:, 1], dtype=np.int32)
+
+
+def smooth_relative_validate(num_frames, sigma_rot, sigma_trans, pairs, frame_time=None, rel_motion=None, struct_size=None, **model):
+    """aar_smooth_relative_validate (host code): raises AarError(AAR_ERR_INVALID) with the library's message.  pairs [Q, 2] = (a, b)"""
+    sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, struct_size, **model)
+    sp.check_lengths(num_frames)
+    fa, fb = _pairs(pairs)
+    ip = C.POINTER(C.c_int32)
+    _check(lib().aar_smooth_relative_validate(int(num_frames), C.byref(sp.c), len(fa), fa.ctypes.data_as(ip) if len(fa) else None,
+                                              fb.ctypes.data_as(ip) if len(fb) else None))
 
 
 class CSmoothFitParams(C.Structure):
@@ -552,6 +576,9 @@ def lib():
     L.aar_track_smooth_query2.argtypes = L.aar_track_smooth_query.argtypes
     L.aar_track_smooth_query2_step.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, dp, dp, dp]
     L.aar_track_smooth_lag3.argtypes = [C.c_void_p, dp, C.c_void_p, dp]
+    L.aar_smooth_relative_validate.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.aar_track_smooth_relative.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, dp,
+                                            C.POINTER(CSmoothRelativeReport)]
     L.aar_smooth_fit_default_params.argtypes = [C.POINTER(CSmoothFitParams)]
     L.aar_smooth_fit_default_params.restype = None
     L.aar_smooth_fit_params_validate.argtypes = [C.POINTER(CSmoothFitParams)]
@@ -1879,6 +1906,30 @@ class Problem:
         l3 = np.zeros((max(F - 3, 1), 6, 6))
         _check(lib().aar_track_smooth_lag3(self.handle, _dptr(x), C.byref(sp.c), _dptr(l3)))
         return l3[:max(F - 3, 0)]
+
+    def track_smooth_relative(self, x_full, sigma_rot, sigma_trans, pairs, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0,
+                              sigma_trans0=0.0, cross=True, motion=True, covariance=True):
+        """aar_track_smooth_relative, either model: the covariance between any two frames and the relative motion between them.  pairs [Q, 2] =
+        (a, b), any order, duplicates allowed.  Returns (cross_cov [Q, 6, 6] = (H^-1)_ab with the rows of frame a, rel [Q, 6] =
+        [log(R_a^T R_b); t_b - t_a], rel_cov [Q, 6, 6], report dict); the covariances UNSCALED -- multiply by report["sigma2"].  A velocity over
+        the baseline is rel / (t_b - t_a) with rel_cov / (t_b - t_a)^2.  cross / motion / covariance = False pass NULL for that output and
+        return None in its place."""
+        x = self._x(x_full)
+        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
+        sp.check_lengths(self.ds.num_frames)
+        fa, fb = _pairs(pairs)
+        Q = len(fa)
+        cc = np.zeros((max(Q, 1), 6, 6)) if cross else None
+        rel = np.zeros((max(Q, 1), 6)) if motion else None
+        rc = np.zeros((max(Q, 1), 6, 6)) if covariance else None
+        rep = CSmoothRelativeReport()
+        rep.struct_size = C.sizeof(CSmoothRelativeReport)
+        ip = C.POINTER(C.c_int32)
+        _check(lib().aar_track_smooth_relative(self.handle, _dptr(x), C.byref(sp.c), Q, fa.ctypes.data_as(ip) if Q else None,
+                                               fb.ctypes.data_as(ip) if Q else None, _dptr(cc) if cross else None, _dptr(rel) if motion else None,
+                                               _dptr(rc) if covariance else None, C.byref(rep)))
+        report = {k: getattr(rep, k) for k, _ in CSmoothRelativeReport._fields_ if k != "struct_size"}
+        return cc[:Q] if cross else None, rel[:Q] if motion else None, rc[:Q] if covariance else None, report
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

@@ -3643,6 +3643,116 @@ int aar_track_smooth_lag3(aar_problem *pb, const double *x_full, const aar_smoot
     return check_async("smoothing query kernels");
 }
 
+// ------------------------------------------------------------------------------------------------
+// Covariance between any two frames, relative motion (smooth_relative_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+int aar_smooth_relative_validate(int32_t num_frames, const aar_smooth_params *sp_in, int64_t n_pairs, const int32_t *frame_a, const int32_t *frame_b) {
+    if (!sp_in) return set_error(AAR_ERR_INVALID, "aar_smooth_relative_validate: null aar_smooth_params");
+    int rc = aar_smooth_params_validate(num_frames, sp_in);
+    if (rc) return rc;
+    if (n_pairs < 0 || n_pairs > INT32_MAX)
+        return set_error(AAR_ERR_INVALID, "aar_smooth_relative: n_pairs = %lld must lie in 0 .. %d", (long long)n_pairs, (int)INT32_MAX);
+    if (n_pairs > 0 && !frame_a) return set_error(AAR_ERR_INVALID, "aar_smooth_relative: frame_a is NULL with n_pairs = %lld", (long long)n_pairs);
+    if (n_pairs > 0 && !frame_b) return set_error(AAR_ERR_INVALID, "aar_smooth_relative: frame_b is NULL with n_pairs = %lld", (long long)n_pairs);
+    for (int64_t i = 0; i < n_pairs; i++) {
+        if (frame_a[i] < 0 || frame_a[i] >= num_frames)
+            return set_error(AAR_ERR_INVALID, "aar_smooth_relative: frame_a[%lld] = %d lies outside 0 .. num_frames - 1 = %d", (long long)i,
+                             (int)frame_a[i], (int)num_frames - 1);
+        if (frame_b[i] < 0 || frame_b[i] >= num_frames)
+            return set_error(AAR_ERR_INVALID, "aar_smooth_relative: frame_b[%lld] = %d lies outside 0 .. num_frames - 1 = %d", (long long)i,
+                             (int)frame_b[i], (int)num_frames - 1);
+    }
+    return AAR_OK;
+}
+
+int aar_track_smooth_relative(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_pairs, const int32_t *frame_a,
+                              const int32_t *frame_b, double *cross_cov, double *rel, double *rel_cov, aar_smooth_relative_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_relative: null argument");
+    aar_smooth_params sp;
+    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_relative");
+    if (rc) return rc;
+    if ((rc = aar_smooth_relative_validate(pb->L.F, sp_in, n_pairs, frame_a, frame_b))) return rc;
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const size_t Q = (size_t)n_pairs;
+    const bool cv = sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY;
+    const auto t0 = std::chrono::steady_clock::now();
+    aar_smooth_relative_report r;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
+    r.num_vars = 6 * (int64_t)F;
+    r.num_pairs = (int32_t)Q;
+    if (Q > 0) {
+        const int direct_lag = cv ? 3 : 1;   // the lags the selected inverse (and the lag-three blocks) hold
+        for (size_t i = 0; i < Q; i++) {
+            const int lag = std::abs(frame_a[i] - frame_b[i]);
+            if (lag <= direct_lag) r.num_direct++; else r.num_chained++;
+            r.max_lag = std::max(r.max_lag, lag);
+        }
+        const bool chained = r.num_chained > 0;
+        pb->lm_ready = false;
+        pb->blocks_valid = false;
+        if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
+        launch_unpack(P, pb->cur, pb->stream);
+        // one allocation: cross [Q][36] | rel [Q][6] | rcov [Q][36] | the blocks and the gains of the model | the pairs [2][Q] and two pivot flags
+        const size_t K = (size_t)smooth_cv_nodes(F), n3 = 36 * (size_t)std::max(F - 3, 0);
+        const size_t n_blk = cv ? smooth_cv_selinv_doubles(F) + n3 + 144 * K : 108 * (size_t)F;
+        const size_t n_dbl = 78 * Q + n_blk, n_int = 2 * Q + 2;
+        SmoothCall out;
+        HIP_TRY(hipMalloc((void **)&out.base, n_dbl * sizeof(double) + n_int * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(out.base, 0, n_dbl * sizeof(double) + n_int * sizeof(int32_t), pb->stream));
+        double *d_cross = out.base, *d_rel = d_cross + 36 * Q, *d_rcov = d_rel + 6 * Q, *d_blk = d_rcov + 36 * Q;
+        int32_t *d_fa = reinterpret_cast<int32_t *>(out.base + n_dbl), *d_fb = d_fa + Q, *d_flag = d_fb + Q;
+        if ((rc = copy_h2d(pb, d_fa, frame_a, Q * sizeof(int32_t)))) return rc;
+        if ((rc = copy_h2d(pb, d_fb, frame_b, Q * sizeof(int32_t)))) return rc;
+        double res[8];
+        int32_t flag = 0, qflag[2] = {0, 0};
+        SmoothCall c;
+        SmoothCvCall ccv;
+        if (cv) {
+            if ((rc = smooth_cv_prepare(pb, sp, ccv))) return rc;
+            double *fc = nullptr, *lc = nullptr, *l2 = nullptr, *d_l3 = d_blk + smooth_cv_selinv_doubles(F), *d_gain = d_l3 + n3;
+            r.launches = smooth_cv_selinv_launch(pb, ccv, 0, d_blk, &fc, &lc, &l2);
+            r.launches += launch_smooth_cv_lag3(F, d_blk, d_l3, d_flag, pb->stream);
+            r.launches += launch_smooth_cv_relative(F, ccv.w.z[0], d_blk, fc, lc, l2, d_l3, d_gain, chained, (int64_t)Q, d_fa, d_fb, d_cross, d_rel,
+                                                    d_rcov, d_flag + 1, pb->stream);
+            if ((rc = copy_d2h(pb, res, ccv.w.res, sizeof res))) return rc;
+            if ((rc = copy_d2h(pb, &flag, ccv.w.flag, sizeof flag))) return rc;
+        } else {
+            if ((rc = smooth_prepare(pb, sp, c))) return rc;
+            double *S = d_blk, *R = S + 36 * (size_t)F, *d_gain = R + 36 * (size_t)F;
+            r.launches = smooth_selinv_launch(pb, c, 0, S, R);
+            r.launches += launch_smooth_relative(F, c.w.z[0], S, R, d_gain, chained, (int64_t)Q, d_fa, d_fb, d_cross, d_rel, d_rcov, d_flag + 1,
+                                                 pb->stream);
+            if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+            if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+        }
+        pb->launches += r.launches;
+        if ((rc = copy_d2h(pb, qflag, d_flag, sizeof qflag))) return rc;
+        if ((rc = check_async("smoothing relative kernels"))) return rc;
+        if (flag)
+            return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_relative: non-positive pivot in the block-%s elimination (the frames' detections and "
+                                              "the prior do not determine every pose)", cv ? "pentadiagonal" : "tridiagonal");
+        if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_relative: non-positive pivot in a supernode block of the lag-three blocks");
+        if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_relative: non-positive pivot in a covariance block that the chain inverts");
+        r.data_cost = res[0]; r.prior_cost = res[1];
+        if (cross_cov && (rc = copy_d2h(pb, cross_cov, d_cross, 36 * Q * sizeof(double)))) return rc;
+        if (rel && (rc = copy_d2h(pb, rel, d_rel, 6 * Q * sizeof(double)))) return rc;
+        if (rel_cov && (rc = copy_d2h(pb, rel_cov, d_rcov, 36 * Q * sizeof(double)))) return rc;
+        if ((rc = check_async("smoothing relative kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+    }
+    const int64_t dof = r.num_residuals - r.num_vars;
+    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
 int aar_set_kernel_profiling(aar_problem *pb, int on) {
     if (!pb) return set_error(AAR_ERR_INVALID, "aar_set_kernel_profiling: null argument");
     HIP_TRY(hipSetDevice(pb->device));

@@ -358,6 +358,16 @@ int launch_smooth_cv_lag3(int F, const double *area, double *l3, int32_t *flag, 
 int launch_smooth_cv_query(int F, const double *z, const double *ft, double sigma_rot, double sigma_trans, double sigma_rot0, double sigma_trans0,
                            const double *fc, const double *lc, const double *l2, const double *l3, int64_t Q, const double *qt, double *pose,
                            double *cov, double *start, double *step, int32_t *seg, int32_t *flag, hipStream_t st);
+// the covariance between any two frames and the relative motion with its covariance (smooth_relative_kernels.hip): the
+// answers of Q > 0 pairs (fa[q], fb[q]) into cross [Q][36], rel [Q][6], rcov [Q][36] from what the selected inverses left on the same stream
+// (S, R of launch_smooth_selinv; the area and fc, lc, l2 of launch_smooth_cv_selinv with l3 of launch_smooth_cv_lag3).  C takes the gains
+// ([F][36], [K][144]) and is written only with chained = true: some pair lies beyond the blocks that exist (lag above 1, above 3).  All
+// pointers on the device; flag zeroed by the caller, raised by a non-positive pivot of a gain; both return their launches
+int launch_smooth_relative(int F, const double *z, const double *S, const double *R, double *C, bool chained, int64_t Q, const int32_t *fa,
+                           const int32_t *fb, double *cross, double *rel, double *rcov, int32_t *flag, hipStream_t st);
+int launch_smooth_cv_relative(int F, const double *z, const double *area, const double *fc, const double *lc, const double *l2, const double *l3,
+                              double *C, bool chained, int64_t Q, const int32_t *fa, const int32_t *fb, double *cross, double *rel, double *rcov,
+                              int32_t *flag, hipStream_t st);
 // the terms' expected sufficient statistics from fc, lc, l2 and z[cur] (smooth_cv_fit_kernels.hip), F >= 3: terms [F-1][4]
 // = a_r, u_r, a_t, u_t (entry 0: pair 0), rec [8] = A_r, U_r, A_t, U_t over the terms 1 .. F-2, data cost, prior cost, pivot flag, u_0;
 // returns its launches

@@ -28,7 +28,7 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>] [-relative-to <frame_id>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
@@ -279,6 +279,11 @@ int main(int argc, char *argv[]) {
     // ... -cv-resample <n> (only with -smooth and -cv, n >= 2) writes final.resampled.yaml under the constant-velocity prior, in -resample's format
     // (MultiCamMapper::track_smooth_query with the model)
     bool cv_resample = false;
+    // ... -relative-to <frame_id> (only with -smooth; with -cv under the constant-velocity prior) also writes every frame's motion relative to
+    // that frame -- rel = [log(R_a^T R_b); t_b - t_a], its 6x6 covariance sigma2 * rel_cov and the baseline time -- to
+    // final.smooth_relative.yaml (MultiCamMapper::track_smooth_relative), at the poses of the solution file written beside it
+    bool relative_to = false, relative_set = false;
+    long relative_id = 0;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
     // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
@@ -302,7 +307,7 @@ int main(int argc, char *argv[]) {
     int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
     double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, Live, Anchor, Gate, Motion } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -333,6 +338,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-fit-sigmas") { fit_sigmas = true; arg_flag = NONE; }
         else if (a == "-resample") { resample = true; resample_n = 0; arg_flag = Resample; }
         else if (a == "-cv-resample") { cv_resample = true; resample_n = 0; arg_flag = Resample; }
+        else if (a == "-relative-to") { relative_to = true; relative_set = false; arg_flag = RelativeTo; }
         else if (a == "-live") { live = true; live_args = 0; arg_flag = Live; }
         else if (a == "-anchor") { live_anchor_set = true; arg_flag = Anchor; }
         else if (a == "-live-covariance") { live_covariance = true; arg_flag = NONE; }
@@ -387,6 +393,13 @@ int main(int argc, char *argv[]) {
             const long v = strtol(a.c_str(), &end, 10);
             if (*end != '\0' || a.empty() || v < 2 || v > 1000000) return print_usage(argv[0]);
             resample_n = (int)v;
+            arg_flag = NONE;
+        }
+        else if (arg_flag == RelativeTo) {
+            char *end = nullptr;
+            relative_id = strtol(a.c_str(), &end, 10);
+            if (*end != '\0' || a.empty()) return print_usage(argv[0]);
+            relative_set = true;
             arg_flag = NONE;
         }
         else if (arg_flag == SmoothCv) {
@@ -451,6 +464,7 @@ int main(int argc, char *argv[]) {
     if (fit_sigmas && (!smooth || live)) return print_usage(argv[0]);
     if (resample && (!smooth || live || resample_n < 2)) return print_usage(argv[0]);
     if (cv_resample && (!smooth || !smooth_cv || live || resample || resample_n < 2)) return print_usage(argv[0]);
+    if (relative_to && (!smooth || live || !relative_set)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
@@ -748,6 +762,43 @@ int main(int argc, char *argv[]) {
     const chrono::duration<double> d = chrono::system_clock::now() - start;
     mcm.write_solution_file(final_path);
     mcm.write_text_solution_file(final_path + ".yaml");
+    if (smooth && relative_to) {
+        const string rl_path = folder_path + "/final.smooth_relative.yaml";
+        try {
+            // at the poses AS THE SOLUTION FILE HOLDS THEM (its writer stores Rodrigues(matrix) of every pose: a few ulps from the driver's own
+            // vector), read back into a mapper of its own: the two files written side by side agree to the bit, and mcm stays as it is
+            aar::MultiCamMapper at_file;
+            if (!at_file.read_solution_file(final_path)) throw runtime_error("cannot read back " + final_path);
+            at_file.set_optmize_flag_cam_intrinsics(false);
+            if (with_huber) at_file.set_with_huber(true);
+            const aar_dataset *ds = at_file.dataset();
+            int base = -1;
+            for (int f = 0; f < ds->num_frames; f++)
+                if ((long)ds->frame_ids[f] == relative_id) base = f;
+            if (base < 0) throw runtime_error("-relative-to: the recording has no frame with id " + to_string(relative_id));
+            vector<pair<int32_t, int32_t>> pairs;
+            for (int f = 0; f < ds->num_frames; f++) pairs.push_back({(int32_t)base, (int32_t)f});
+            aar::MultiCamMapper::SmoothRelative q;
+            at_file.track_smooth_relative(smooth_sigma[0], smooth_sigma[1], smooth_cv ? AAR_SMOOTH_MODEL_CONSTANT_VELOCITY : AAR_SMOOTH_MODEL_RANDOM_WALK,
+                                      smooth_sigma0[0], smooth_sigma0[1], pairs, q);
+            FILE *fp = fopen(rl_path.c_str(), "w");
+            if (!fp) throw runtime_error("cannot write " + rl_path);
+            fprintf(fp, "%%YAML:1.0\n---\nsigma2: %.17g\nrelative_to: %ld\nrelative_motions:\n", q.report.sigma2, relative_id);
+            for (size_t k = 0; k < pairs.size(); k++) {
+                fprintf(fp, "   - { frame: %d, baseline: %.17g, rel: [", (int)ds->frame_ids[k], (double)ds->frame_ids[k] - (double)ds->frame_ids[base]);
+                for (int i = 0; i < 6; i++) fprintf(fp, "%s%.17g", i ? ", " : "", q.rel[6 * k + i]);
+                fprintf(fp, "],\n       covariance: !!opencv-matrix { rows:6, cols:6, dt:d, data:[");
+                for (int i = 0; i < 36; i++) fprintf(fp, "%s%.17g", i ? ", " : "", q.report.sigma2 * q.rel_cov[36 * k + i]);
+                fprintf(fp, "] } }\n");
+            }
+            fclose(fp);
+            cout << "smooth-relative: " << pairs.size() << " frames relative to frame " << relative_id << " (" << q.report.num_direct << " from the blocks, "
+                 << q.report.num_chained << " chained, longest lag " << q.report.max_lag << "), sigma2 " << q.report.sigma2 << ", written to " << rl_path << endl;
+        } catch (const exception &e) {
+            cerr << "smooth relative failed: " << e.what() << endl;
+            return 6;
+        }
+    }
     if (covariance) {
         const string cov_path = folder_path + "/final.covariance.yaml";
         try {

@@ -10,6 +10,7 @@
 #include <map>
 #include <stdexcept>
 #include <type_traits>
+#include <utility>
 #include <set>
 #include <string>
 #include <vector>
@@ -427,6 +428,18 @@ class MultiCamMapper {
     // gaps, not held; covariance = false saves the copy of the blocks alone
     void track_smooth_query(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
                             const std::vector<double> &query_time, SmoothQuery &out, bool covariance = true);   // throws std::runtime_error on failure
+    // EXTENSION, no counterpart in the reference: the covariance between ANY two frames of the smoothed track and the relative motion between
+    // them with its 6x6 covariance (aar_track_smooth_relative), with track_smooth()'s prior (the frame ids as its time axis)
+    // and Huber delta, under the motion model AAR_SMOOTH_MODEL_*.  pairs: (a, b) as frame INDICES, any order, duplicates allowed.  The
+    // covariances are UNSCALED (multiply by report.sigma2); a velocity over the baseline is rel / dt with rel_cov / dt^2.
+    struct SmoothRelative {
+        std::vector<double> cross_cov;   // [n][36] (H^-1)_ab, row-major, the rows belong to frame a
+        std::vector<double> rel;         // [n][6] [log(R_a^T R_b) ; t_b - t_a]
+        std::vector<double> rel_cov;     // [n][36]
+        aar_smooth_relative_report report = {};
+    };
+    void track_smooth_relative(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                               const std::vector<std::pair<int32_t, int32_t>> &pairs, SmoothRelative &out);   // throws std::runtime_error on failure
     // EXTENSION, no counterpart in the reference: the corner noise and track_smooth()'s two sigmas fitted to the sequence itself by EM
     // (aar_track_smooth_fit), from the effective start values sigma_rot, sigma_trans.  The frame poses end as the smoothed
     // track at the fitted values; report.sigma_rot_eff / sigma_trans_eff are what track_smooth() and the live tracker take.  A mapper

@@ -805,6 +805,41 @@ int aar_track_smooth_query2_step(aar_problem *, const double *x_full, const aar_
  * (2k, 2k + 1) an even f is a block of the selected inverse; an odd f = 2k - 1 follows from the Gauss-Markov property of the block-tridiagonal
  * chain, Sigma_{k-1,k+1} = Sigma_{k-1,k} Sigma_kk^-1 Sigma_{k,k+1}.  num_frames < 4: AAR_OK, nothing written.  Errors as above. */
 int aar_track_smooth_lag3(aar_problem *, const double *x_full, const aar_smooth_params *, double *lag3_cov);
+/* The covariance between ANY two frames of the smoothed track and the relative motion between them: how far did the
+ * object move and turn between frame a and frame b, and how sure is that?  Either model (aar_smooth_params.model).  H is the system
+ * aar_track_smooth_system2 returns at mu = 0 for the same x_full and parameters, Sigma = H^-1; everything is UNSCALED (multiply by
+ * report->sigma2), as everywhere else.  Per pair q = (a, b) = (frame_a[q], frame_b[q]), in any order, a > b and duplicates allowed:
+ *   cross_cov[q] = Sigma_ab, row-major, the rows belong to frame a.  (b, a) is the transpose of (a, b) to the bit.  a = b: frame_cov[a];
+ *                  |a - b| = 1: lag_cov; under constant velocity |a - b| = 2: lag2_cov, |a - b| = 3: the blocks of aar_track_smooth_lag3 --
+ *                  the bits those calls return.  Beyond that the Gauss-Markov chain of a block-tridiagonal H (in frames under the random walk,
+ *                  in supernodes (2k, 2k + 1) under constant velocity): Sigma_ab = Sigma_ak Sigma_kk^-1 Sigma_kb for a < k < b, one 6x6 (12x12)
+ *                  product per step of the lag, no new solve.
+ *   rel[q]       = [log(R_a^T R_b)^v ; t_b - t_a]: the smoother's own between without an expected motion (also when rel_motion is set, which
+ *                  changes H alone) -- the rotation in frame a's body frame, the translation in the root camera's frame.
+ *   rel_cov[q]   = J_a Sigma_aa J_a^T + J_b Sigma_bb J_b^T + J_a Sigma_ab J_b^T + (J_a Sigma_ab J_b^T)^T, J_a = [M_a 0; 0 -I], J_b = [M_b 0; 0 I]
+ *                  the between's Jacobians; symmetric to the bit.  With smoothing sigmas tight enough to pay off, nearby frames share most of
+ *                  their error: Sigma_aa + Sigma_bb overstates this by a large factor and only Sigma_ab corrects it.
+ *                  a = b: zeros exactly, in rel and rel_cov.
+ * A velocity over the baseline is rel / (t_b - t_a) with covariance rel_cov / (t_b - t_a)^2.
+ * Each of the three outputs and the report may be NULL.  x_full is not modified and no LM state is left behind.  n_pairs = 0: AAR_OK, no
+ * output written (the report holds the counts alone).  Problems created with Huber are accepted.  A query's bits depend on (a, b) and the
+ * track alone, not on the other queries or their order; two calls give the same bits.  The cost of a query is O(|a - b|).
+ * AAR_ERR_INVALID (naming the index): an index outside [0, num_frames), null arrays with n_pairs > 0, whatever aar_smooth_params_validate
+ * refuses.  AAR_ERR_UNSUPPORTED: a problem with a communicator.  AAR_ERR_NUMERIC, nothing written: a non-positive pivot in the elimination (with
+ * the root rules of aar_track_smooth_covariance / aar_track_smooth_covariance2), in a supernode block of the lag-three blocks, or in a Sigma_kk
+ * that the chain inverts. */
+typedef struct aar_smooth_relative_report {
+    uint32_t struct_size;
+    int64_t num_residuals, num_vars;   /* of the problem as given, as aar_smooth_covariance_report */
+    double data_cost, prior_cost, sigma2;
+    int32_t num_pairs, num_direct, num_chained, max_lag;   /* direct: answered from the blocks that exist (lag <= 1; <= 3 under constant velocity) */
+    int32_t launches;
+    double seconds;
+} aar_smooth_relative_report;
+/* Host function (no device needed): AAR_OK or AAR_ERR_INVALID with a message naming what aar_track_smooth_relative would refuse as invalid. */
+int aar_smooth_relative_validate(int32_t num_frames, const aar_smooth_params *, int64_t n_pairs, const int32_t *frame_a, const int32_t *frame_b);
+int aar_track_smooth_relative(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_pairs, const int32_t *frame_a,
+                              const int32_t *frame_b, double *cross_cov, double *rel, double *rel_cov, aar_smooth_relative_report *report);
 
 /* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
  * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are

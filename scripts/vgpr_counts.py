@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = "eval_kernels solve_kernels pcg_kernels spcg_kernels init_kernels undistort prior_kernels pair_prior_kernels smooth_cv_kernels smooth_cv_cov_kernels smooth_cv_fit_kernels smooth_cv_query_kernels ba_capi".split()
+SRC = "eval_kernels solve_kernels pcg_kernels spcg_kernels init_kernels undistort prior_kernels pair_prior_kernels smooth_cv_kernels smooth_cv_cov_kernels smooth_cv_fit_kernels smooth_cv_query_kernels smooth_relative_kernels ba_capi".split()
 PATS = (("vgpr", r"\bVGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("sgpr", r"SGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
         ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"), ("spill_v", r"VGPRs Spill: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
 
