@@ -36,6 +36,7 @@ SYMBOLS = [
     "aar_solution_read_ex", "aar_cam_configs_read_ex", "aar_set_stage_timers", "aar_problem_pcg_iterations",
     "aar_solver_default_options", "aar_problem_create_ex", "aar_problem_get_solver_stats", "aar_problem_set_test_hook",
     "aar_problem_covariance", "aar_covariance_write_yaml",
+    "aar_predict_query_validate", "aar_problem_predict_corners", "aar_problem_detection_leverage", "aar_leverage_write_yaml",
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
@@ -63,6 +64,7 @@ TRACKER_ANCHORS = {"fixed": TRACKER_ANCHOR_FIXED, "marginal": TRACKER_ANCHOR_MAR
 TRACKER_STARTS = {"vote": TRACKER_START_VOTE, "best": TRACKER_START_BEST}
 NUM_KERNELS = 18
 PRIOR_CAMERA, PRIOR_MARKER = 0, 1
+PREDICT_BEHIND, PREDICT_UNDEFINED = 1, 2
 PRIOR_KINDS = {"camera": PRIOR_CAMERA, "marker": PRIOR_MARKER}
 SOLVER_DIRECT, SOLVER_PCG, SOLVER_SPCG, SOLVER_AUTO = 0, 1, 2, 3
 TEST_HOOK_SPCG_DROP = 1
@@ -128,6 +130,12 @@ class CSolverStats(C.Structure):
 class CCovarianceReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("sum_sq", C.c_double),
                 ("sigma2", C.c_double), ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("frames_written", C.c_int32)]
+
+
+class CPredictReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("sum_sq", C.c_double),
+                ("sigma2", C.c_double), ("num_live_vars", C.c_int64), ("leverage_sum", C.c_double), ("undefined", C.c_int64),
+                ("behind", C.c_int64), ("launches", C.c_int32), ("seconds", C.c_double)]
 
 
 class COutlierRule(C.Structure):
@@ -544,6 +552,11 @@ def lib():
     L.aar_problem_covariance.argtypes = [C.c_void_p, dp, dp, dp, dp, C.POINTER(CCovarianceReport)]
     L.aar_covariance_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.c_double]
     u8p = C.POINTER(C.c_uint8)
+    ip32 = C.POINTER(C.c_int32)
+    L.aar_predict_query_validate.argtypes = [C.POINTER(CProblemDesc), C.c_int64, ip32, ip32, ip32]
+    L.aar_problem_predict_corners.argtypes = [C.c_void_p, dp, C.c_int64, ip32, ip32, ip32, dp, dp, u8p, C.POINTER(CPredictReport)]
+    L.aar_problem_detection_leverage.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(CPredictReport)]
+    L.aar_leverage_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.c_double, C.POINTER(CPredictReport)]
     L.aar_problem_residual_report.argtypes = [C.c_void_p, dp, C.POINTER(COutlierRule), dp, u8p, dp, dp, dp, C.POINTER(CResidualReport)]
     L.aar_dataset_select_observations.argtypes = [C.POINTER(CDataset), u8p, C.POINTER(C.POINTER(CDataset))]
     L.aar_residual_report_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, dp, u8p, C.POINTER(CResidualReport)]
@@ -1107,6 +1120,45 @@ def residual_report_write_yaml(path, ds, rr, det_err=True):
                                                 _u8ptr(k) if det_err else None, C.byref(r)))
 
 
+def _queries(queries):
+    """queries [Q, 3] = (camera index, marker index, frame index) -> three contiguous int32 arrays"""
+    q = np.asarray(queries, dtype=np.int64).reshape(-1, 3)
+    if len(q) and (np.abs(q) > 2 ** 31 - 1).any():
+        raise ValueError("a query index does not fit 32 bits")
+    return [np.ascontiguousarray(q[:, k], dtype=np.int32) for k in range(3)]
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if len(a) else None
+
+
+def predict_query_validate(ds, queries):
+    """aar_predict_query_validate (host code): raises AarError(AAR_ERR_INVALID) naming the first query whose index is out of range"""
+    cds = ds.as_c()
+    d = CProblemDesc()
+    lib().aar_problem_desc_from_dataset(C.byref(cds), C.byref(d))
+    qc, qm, qf = _queries(queries)
+    _check(lib().aar_predict_query_validate(C.byref(d), len(qc), _i32ptr(qc), _i32ptr(qm), _i32ptr(qf)))
+
+
+def _predict_report_dict(rep):
+    return {name: getattr(rep, name) for name, _ in CPredictReport._fields_[1:]}
+
+
+def leverage_write_yaml(path, ds, leverage, report, h_min=0.0, det_err=None):
+    """aar_leverage_write_yaml: leverage / report as Problem.detection_leverage returns them for a (single-GPU) problem created from ds;
+    det_err as Problem.residual_report(...).det_err, or None"""
+    c = ds.as_c()
+    lv = np.ascontiguousarray(leverage, dtype=np.float64)
+    e = None if det_err is None else np.ascontiguousarray(det_err, dtype=np.float64)
+    r = CPredictReport()
+    r.struct_size = C.sizeof(CPredictReport)
+    for name, _ in CPredictReport._fields_[1:]:
+        setattr(r, name, report[name])
+    _check(lib().aar_leverage_write_yaml(path.encode(), C.byref(c), _dptr(lv) if len(lv) else None, _dptr(e) if e is not None else None,
+                                         float(h_min), C.byref(r)))
+
+
 def tracker_detection_params(Ks=None, dists=None, ippe_threshold=None, min_detections=None, start_policy=None, struct_size=None):
     """(aar_tracker_detection_params, the camera array it points to) from Python values (None = the library's default; Ks / dists by camera
     INDEX, None = the solution's own); start_policy: "vote" | "best" or the number"""
@@ -1652,6 +1704,35 @@ class Problem:
                           min_pivot=rep.min_pivot, max_pivot=rep.max_pivot, frames_written=rep.frames_written,
                           entity_diag=blocks, entity_diag_flat=diag, entity_cov=ecov,
                           frames=fr.reshape(-1, 6, 6) if want_fr else None)
+
+    def predict_corners(self, x_full, queries, covariance=True):
+        """aar_problem_predict_corners at x_full for queries [Q, 3] = (camera index, marker index, frame index).  Returns (uv [Q, 4, 2],
+        cov [Q, 8, 8] UNSCALED -- None with covariance=False, which runs no covariance chain --, status [Q] (PREDICT_BEHIND | PREDICT_UNDEFINED
+        bits), report dict of the aar_predict_report fields).  A corner's a-posteriori covariance is report["sigma2"] * cov; the search
+        window of a NEW detection is report["sigma2"] * (cov + I)."""
+        x = self._x(x_full)
+        qc, qm, qf = _queries(queries)
+        n = len(qc)
+        uv = np.full((max(n, 1), 8), np.nan)
+        cov = np.full((max(n, 1), 64), np.nan) if covariance else None
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        rep = CPredictReport()
+        rep.struct_size = C.sizeof(CPredictReport)
+        _check(lib().aar_problem_predict_corners(self.handle, _dptr(x), n, _i32ptr(qc), _i32ptr(qm), _i32ptr(qf), _dptr(uv),
+                                                 _dptr(cov) if covariance else None, _u8ptr(st), C.byref(rep)))
+        return uv[:n].reshape(n, 4, 2), (cov[:n].reshape(n, 8, 8) if covariance else None), st[:n], _predict_report_dict(rep)
+
+    def detection_leverage(self, x_full, rows=False):
+        """aar_problem_detection_leverage at x_full: (leverage [local_obs] = tr(C_i) of this problem's detections in reference order,
+        row_leverage [local_obs, 8] = diag(C_i) or None, report dict)"""
+        x = self._x(x_full)
+        n = self.local_obs
+        lv = np.full(max(n, 1), np.nan)
+        rw = np.full((max(n, 1), 8), np.nan) if rows else None
+        rep = CPredictReport()
+        rep.struct_size = C.sizeof(CPredictReport)
+        _check(lib().aar_problem_detection_leverage(self.handle, _dptr(x), _dptr(lv), _dptr(rw) if rows else None, C.byref(rep)))
+        return lv[:n], (rw[:n] if rows else None), _predict_report_dict(rep)
 
     def residual_report(self, x_full, k_median=0.0, min_px=0.0, rule=None):
         """aar_problem_residual_report at x_full.  The rule's threshold is max(min_px, k_median * median) (k_median <= 0: min_px; both <= 0:

@@ -1919,11 +1919,20 @@ int aar_eval_damped_step(aar_problem *pb, const double *x_full, double mu, doubl
 
 // (J^T J)^-1 at x_full: the DIRECT chain's blocks at mu = 0, the reduced system factored by the k_ldl_* chain (one padding tile more than the
 // LM path uses, so that every real tile's factor stays in Dfac), S^-1 and the frame marginals by cov_kernels.hip.  DESIGN.md section 13.
-int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity_cov, double *entity_diag, double *frame_cov,
-                           aar_covariance_report *report) {
-    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_problem_covariance: null argument");
-    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_covariance: report->struct_size not set");
-    HIP_TRY(hipSetDevice(pb->device));
+namespace {
+// What the chain leaves behind for its callers: the row mask (PREDICT_* of kernels.h; aar_problem_covariance only asks whether a row is
+// masked), where S^-1, 1 / D, the frame blocks and the entities' diagonal blocks lie in the workspace, the summed sum r^2
+struct CovChain {
+    std::vector<int32_t> mask;
+    double *Sinv = nullptr, *Dinv = nullptr, *frame_blocks = nullptr, *diag_blocks = nullptr;
+    int32_t *rowmask = nullptr;
+    double sum_sq = 0, dmin = INFINITY, dmax = -INFINITY;
+    bool frames = false;
+};
+
+// The chain of aar_problem_covariance up to the frame blocks (want_frames) and the entities' diagonal blocks (want_diag_blocks), with its
+// pivot check: every caller fails on the same systems with the same message
+int cov_chain(aar_problem *pb, const double *x_full, bool want_frames, bool want_diag_blocks, CovChain &out) {
     DeviceProblem &P = pb->P;
     const PoseLayout &L = pb->L;
     const int cur = pb->cur, np = P.n_pad, n2 = P.n_pad + CHOL_NB, nT2 = P.nT + 1, NB = CHOL_NB;
@@ -1974,7 +1983,9 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
         bool seen = false;
         for (int i = 0; i < 6; i++) seen |= par_col(a, i) >= 0 && diag[6 * a + i] != 0.0;
         const bool held = a < L.C + L.M && pb->h_ent_fixed[a];   // (fixed by the caller: as a root)
-        for (int i = 0; i < 6; i++) mask[6 * a + i] = (seen && !held && par_col(a, i) >= 0) ? 0 : 1;
+        // a row without an unknown: a constant (no z column, or held), or -- PREDICT_UNSEEN -- a free parameter nothing determines
+        for (int i = 0; i < 6; i++)
+            mask[6 * a + i] = (seen && !held && par_col(a, i) >= 0) ? PREDICT_LIVE : ((!held && par_col(a, i) >= 0) ? PREDICT_UNSEEN : PREDICT_CONST);
     }
     if ((rc = copy_h2d(pb, rowmask, mask.data(), np * sizeof(int32_t)))) return rc;
     // factor the staged system with the LM path's own chain: a copy of the problem description pointed at the workspace
@@ -1988,9 +1999,9 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
     Q.Dfac = ws + o_D; Q.Linv16 = ws + o_Li; Q.Lp = ws + o_Lp; Q.zf = ws + o_zf; Q.delta_s = ws + o_ds; Q.bs_flags = bsf; Q.bs_epoch = 0; Q.flags = flg;
     launch_chol(Q, cur, 0.0, pb->stream);
     launch_cov_inverse(S2, Q.Dfac, Q.Lp, np, n2, nT2, P.tune.fused_panel, ws + o_Lc, ws + o_Dv, ws + o_X, ws + o_Si, pb->stream);
-    const bool frames = frame_cov && L.of && P.F > 0;
+    const bool frames = want_frames && L.of && P.F > 0;
     if (frames) launch_cov_frames(P, cur, ws + o_Si, rowmask, ws + o_fr, pb->stream);
-    if (entity_diag && !entity_cov) launch_cov_diag_blocks(ws + o_Si, np, P.A, ws + o_db, pb->stream);
+    if (want_diag_blocks) launch_cov_diag_blocks(ws + o_Si, np, P.A, ws + o_db, pb->stream);
     pb->launches += 4 + 3 * nT2 + np / 32;
     if ((rc = check_async("covariance kernels"))) return rc;
     HIP_TRY(hipStreamSynchronize(pb->stream));
@@ -2010,16 +2021,44 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
         dmin = std::min(dmin, d);
         dmax = std::max(dmax, d);
     }
+    out.mask.swap(mask);
+    out.Sinv = ws + o_Si; out.Dinv = ws + o_Dv; out.frame_blocks = ws + o_fr; out.diag_blocks = ws + o_db;
+    out.rowmask = rowmask;
+    out.sum_sq = sum_sq; out.dmin = dmin; out.dmax = dmax;
+    out.frames = frames;
+    return AAR_OK;
+}
+}  // namespace
+
+int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity_cov, double *entity_diag, double *frame_cov,
+                           aar_covariance_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_problem_covariance: null argument");
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_covariance: report->struct_size not set");
+    HIP_TRY(hipSetDevice(pb->device));
+    DeviceProblem &P = pb->P;
+    const PoseLayout &L = pb->L;
+    const int np = P.n_pad;
+    CovChain ch;
+    int rc = cov_chain(pb, x_full, frame_cov != nullptr, entity_diag && !entity_cov, ch);
+    if (rc) return rc;
+    const std::vector<int32_t> &mask = ch.mask;
+    const bool frames = ch.frames;
+    const double sum_sq = ch.sum_sq, dmin = ch.dmin, dmax = ch.dmax;
+    auto par_col = [&](int a, int i) -> int64_t {   // z column of device parameter (a, i), or -1 (as aar_eval_normal_equations)
+        if (a < L.C) { const int s = L.cam_slot(a); return (s < 0 || !L.oc) ? -1 : L.z_cam0() + 6LL * s + i; }
+        if (a < L.C + L.M) { const int s = L.mk_slot(a - L.C); return (s < 0 || !L.om) ? -1 : L.z_mk0() + 6LL * s + i; }
+        return i < 4 ? L.z_intr0() + 9LL * (a - L.C - L.M) + i : -1;
+    };
     const int64_t Pz = L.z_len(), Fz = L.of ? 6LL * L.F : 0, Pe = Pz - Fz;
     if (entity_cov || entity_diag) {
         // the whole of S^-1 for a dense output; the entities' 6x6 diagonal blocks alone otherwise (an intrinsics entity's 9x9 block is its 4x4
         // inside one 6x6 block: NaN elsewhere)
         std::vector<double> Si((size_t)np * np), db;
         if (entity_cov) {
-            if ((rc = copy_d2h(pb, Si.data(), ws + o_Si, Si.size() * sizeof(double)))) return rc;
+            if ((rc = copy_d2h(pb, Si.data(), ch.Sinv, Si.size() * sizeof(double)))) return rc;
         } else {
             db.resize(36 * (size_t)std::max(P.A, 1));
-            if ((rc = copy_d2h(pb, db.data(), ws + o_db, db.size() * sizeof(double)))) return rc;
+            if ((rc = copy_d2h(pb, db.data(), ch.diag_blocks, db.size() * sizeof(double)))) return rc;
         }
         std::vector<int> zdev((size_t)std::max<int64_t>(Pe, 1), -1);   // entity z column -> device row (-1: NaN)
         for (int a = 0; a < P.A; a++)
@@ -2048,7 +2087,7 @@ int aar_problem_covariance(aar_problem *pb, const double *x_full, double *entity
             }
         }
     }
-    if (frames && (rc = copy_d2h(pb, frame_cov + 36 * (size_t)pb->f_begin, ws + o_fr, (size_t)P.F * 36 * sizeof(double)))) return rc;
+    if (frames && (rc = copy_d2h(pb, frame_cov + 36 * (size_t)pb->f_begin, ch.frame_blocks, (size_t)P.F * 36 * sizeof(double)))) return rc;
     if (report) {
         aar_covariance_report r;
         memset(&r, 0, sizeof r);
@@ -3751,6 +3790,185 @@ int aar_track_smooth_relative(aar_problem *pb, const double *x_full, const aar_s
         memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
     }
     return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Predicted corners with covariance, detection leverages (predict_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct PredictCall {
+    void *base = nullptr;
+    ~PredictCall() { if (base) (void)hipFree(base); }
+};
+
+int predict_refuse(const aar_problem *pb, const char *who) {
+    if (pb->comm) return set_error(AAR_ERR_UNSUPPORTED, "%s: dense outputs are single-GPU only (as aar_eval_normal_equations)", who);
+    if (pb->L.oi)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: the problem optimises the camera intrinsics; its corners also depend on (fx, cx, fy, cy), whose "
+                                              "columns the corner covariance does not carry yet (that is the next step)", who);
+    return AAR_OK;
+}
+
+// The row mask without the covariance chain: what the chain reads off the diagonal of S -- an entity is determined when an observation,
+// a pose prior or a pair prior touches it -- from the host's copies of the index structure
+int predict_host_mask(aar_problem *pb, std::vector<int32_t> &mask) {
+    const DeviceProblem &P = pb->P;
+    const PoseLayout &L = pb->L;
+    std::vector<char> touched((size_t)std::max(P.A, 1), 0);
+    for (int32_t a : pb->h_fslot_ent) touched[a] = 1;
+    for (const aar_pose_prior &p : pb->priors) touched[p.kind == AAR_PRIOR_CAMERA ? p.index : L.C + p.index] = 1;
+    if (P.n_pair > 0) {
+        std::vector<int32_t> ends(4 * (size_t)P.n_pair);
+        if (int rc = copy_d2h(pb, ends.data(), P.pair_ends, ends.size() * sizeof(int32_t))) return rc;
+        for (int p = 0; p < P.n_pair; p++) touched[ends[4 * (size_t)p]] = touched[ends[4 * (size_t)p + 1]] = 1;
+    }
+    mask.assign(P.n_pad, PREDICT_CONST);
+    for (int a = 0; a < L.C + L.M; a++) {
+        const bool zcol = a < L.C ? (L.oc && L.cam_slot(a) >= 0) : (L.om && L.mk_slot(a - L.C) >= 0);
+        const int m = (!zcol || pb->h_ent_fixed[a]) ? PREDICT_CONST : (touched[a] ? PREDICT_LIVE : PREDICT_UNSEEN);
+        for (int i = 0; i < 6; i++) mask[6 * (size_t)a + i] = m;
+    }
+    return AAR_OK;
+}
+
+// mode as launch_predict_corners: 0 = uv | cov | status, 1 = uv | status without the chain, 2 = the problem's own detections
+int predict_run(aar_problem *pb, const double *x_full, int mode, int64_t n, const int32_t *q_cam, const int32_t *q_marker, const int32_t *q_frame,
+                double *uv, double *cov, uint8_t *status, double *lev, double *row_lev, aar_predict_report *report) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceProblem &P = pb->P;
+    const PoseLayout &L = pb->L;
+    const int cur = pb->cur;
+    const int64_t launches0 = pb->launches;
+    aar_predict_report r;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * pb->N_global;
+    r.num_vars = L.z_len();
+    r.sum_sq = r.sigma2 = NAN;
+    std::vector<double> h_uv, h_cov, h_lev, h_row;
+    std::vector<uint8_t> h_st;
+    if (n > 0) {
+        HIP_TRY(hipSetDevice(pb->device));
+        int rc;
+        CovChain ch;
+        std::vector<int32_t> host_mask;
+        if (mode != 1) {
+            if ((rc = cov_chain(pb, x_full, true, false, ch))) return rc;
+            r.sum_sq = ch.sum_sq;
+            r.sigma2 = r.num_residuals > r.num_vars ? ch.sum_sq / (double)(r.num_residuals - r.num_vars) : NAN;
+        } else {
+            if ((rc = upload_z(pb, x_full, cur))) return rc;
+            // whatever the LM state was, it is gone: z[cur] and its entity rows now hold x_full
+            pb->lm_ready = false;
+            pb->blocks_valid = false;
+            pb->vinv_mu = pb->schur_mu = -1;
+            pb->s_reduced = pb->trial_reduced = false;
+            pb->spec_chol_blk = -1;
+            if (pb->panels_blk == cur) pb->panels_blk = -1;
+            if ((rc = predict_host_mask(pb, host_mask))) return rc;
+        }
+        const std::vector<int32_t> &mask = mode != 1 ? ch.mask : host_mask;
+        for (int32_t m : mask) r.num_live_vars += m == PREDICT_LIVE;
+        if (L.of)
+            for (int f = 0; f < P.F; f++) r.num_live_vars += pb->h_fslot_start[f + 1] > pb->h_fslot_start[f] ? 6 : 0;
+        const bool frames_opt = L.of && P.F > 0;
+        // one allocation: gains | uv | cov | leverage | its rows, then the queries and the mask, then the status bytes
+        const size_t N = (size_t)n, n_gain = (mode != 1 && frames_opt) ? 36 * (size_t)std::max(P.total_slots, 1) : 0, n_uv = mode != 2 ? 8 * N : 0,
+                     n_cov = mode == 0 ? 64 * N : 0, n_lev = mode == 2 ? N : 0, n_row = mode == 2 ? 8 * N : 0;
+        const size_t n_dbl = n_gain + n_uv + n_cov + n_lev + n_row, n_int = (mode != 2 ? 3 * N : 0) + (mode == 1 ? (size_t)P.n_pad : 0);
+        const size_t bytes = n_dbl * sizeof(double) + n_int * sizeof(int32_t) + N;
+        PredictCall out;
+        HIP_TRY(hipMalloc(&out.base, bytes));
+        HIP_TRY(hipMemsetAsync(out.base, 0, bytes, pb->stream));
+        double *d_gain = static_cast<double *>(out.base), *d_uv = d_gain + n_gain, *d_cov = d_uv + n_uv, *d_lev = d_cov + n_cov, *d_row = d_lev + n_lev;
+        int32_t *d_qc = reinterpret_cast<int32_t *>(d_row + n_row), *d_qm = d_qc + (mode != 2 ? N : 0), *d_qf = d_qm + (mode != 2 ? N : 0),
+                *d_mask = d_qf + (mode != 2 ? N : 0);
+        uint8_t *d_st = reinterpret_cast<uint8_t *>(reinterpret_cast<int32_t *>(d_row + n_row) + n_int);
+        if (mode != 2 && ((rc = copy_h2d(pb, d_qc, q_cam, N * sizeof(int32_t))) || (rc = copy_h2d(pb, d_qm, q_marker, N * sizeof(int32_t))) ||
+                          (rc = copy_h2d(pb, d_qf, q_frame, N * sizeof(int32_t)))))
+            return rc;
+        if (mode == 1 && (rc = copy_h2d(pb, d_mask, host_mask.data(), (size_t)P.n_pad * sizeof(int32_t)))) return rc;
+        launch_unpack(P, cur, pb->stream);
+        pb->launches += 1;
+        const KTable kt = k_table(P, cur);
+        PredictArgs a;
+        memset(&a, 0, sizeof a);
+        a.ent = P.ent[cur]; a.K = kt.base; a.kstride = kt.stride; a.C = P.C; a.A = P.A; a.h = P.half_size; a.n = n;
+        a.q_cam = d_qc; a.q_marker = d_qm; a.q_frame = d_qf; a.obs = P.a_idx;
+        a.fslot_start = P.fslot_start; a.fslot_ent = P.fslot_ent; a.rowmask = mode == 1 ? d_mask : ch.rowmask;
+        a.frames_opt = frames_opt ? 1 : 0; a.n_pad = P.n_pad;
+        a.gain = d_gain; a.Sinv = ch.Sinv; a.frame_cov = ch.frame_blocks;
+        a.uv = d_uv; a.cov = d_cov; a.status = d_st; a.lev = d_lev; a.row_lev = (mode == 2 && row_lev) ? d_row : nullptr;
+        if (mode != 1 && frames_opt) {
+            launch_predict_gains(P, cur, ch.rowmask, d_gain, pb->stream);
+            pb->launches += 1;
+        }
+        launch_predict_corners(a, mode, pb->stream);
+        pb->launches += 1;
+        if ((rc = check_async("predict kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+        h_st.resize(N);
+        if ((rc = copy_d2h(pb, h_st.data(), d_st, N))) return rc;
+        if (mode != 2) { h_uv.resize(8 * N); if ((rc = copy_d2h(pb, h_uv.data(), d_uv, h_uv.size() * sizeof(double)))) return rc; }
+        if (mode == 0) { h_cov.resize(64 * N); if ((rc = copy_d2h(pb, h_cov.data(), d_cov, h_cov.size() * sizeof(double)))) return rc; }
+        if (mode == 2) { h_lev.resize(N); if ((rc = copy_d2h(pb, h_lev.data(), d_lev, N * sizeof(double)))) return rc; }
+        if (mode == 2 && row_lev) { h_row.resize(8 * N); if ((rc = copy_d2h(pb, h_row.data(), d_row, h_row.size() * sizeof(double)))) return rc; }
+        if ((rc = check_async("predict kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+        // everything succeeded: only now the caller's arrays are written
+        for (size_t i = 0; i < N; i++) {
+            r.behind += (h_st[i] & AAR_PREDICT_BEHIND) ? 1 : 0;
+            r.undefined += (h_st[i] & AAR_PREDICT_UNDEFINED) ? 1 : 0;
+            double t = NAN;
+            if (mode == 2) t = h_lev[i];
+            if (mode == 0) {
+                const double *c = &h_cov[64 * i];
+                t = ((c[0] + c[9]) + (c[18] + c[27])) + ((c[36] + c[45]) + (c[54] + c[63]));   // (the kernel's order of the trace)
+            }
+            if (std::isfinite(t)) r.leverage_sum += t;
+        }
+        if (uv) memcpy(uv, h_uv.data(), h_uv.size() * sizeof(double));
+        if (cov) memcpy(cov, h_cov.data(), h_cov.size() * sizeof(double));
+        if (status) memcpy(status, h_st.data(), N);
+        if (lev) memcpy(lev, h_lev.data(), N * sizeof(double));
+        if (row_lev) memcpy(row_lev, h_row.data(), h_row.size() * sizeof(double));
+    }
+    r.launches = (int32_t)(pb->launches - launches0);
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+}  // namespace
+
+int aar_problem_predict_corners(aar_problem *pb, const double *x_full, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker,
+                                const int32_t *q_frame, double *uv, double *cov, uint8_t *status, aar_predict_report *report) {
+    if (!pb) {   // no problem exists without a device: say which of the two it is
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_problem_predict_corners: null problem");
+    }
+    if (!x_full || (n_query > 0 && !uv)) return set_error(AAR_ERR_INVALID, "aar_problem_predict_corners: null argument");
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_predict_corners: report->struct_size not set");
+    int rc = predict_refuse(pb, "aar_problem_predict_corners");
+    if (rc) return rc;
+    aar_problem_desc d;
+    memset(&d, 0, sizeof d);
+    d.num_cams = pb->L.C; d.num_markers = pb->L.M; d.num_frames = pb->L.F;
+    if ((rc = aar_predict_query_validate(&d, n_query, q_cam, q_marker, q_frame))) return rc;
+    return predict_run(pb, x_full, cov ? 0 : 1, n_query, q_cam, q_marker, q_frame, uv, cov, status, nullptr, nullptr, report);
+}
+
+int aar_problem_detection_leverage(aar_problem *pb, const double *x_full, double *leverage, double *row_leverage, aar_predict_report *report) {
+    if (!pb) {
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_problem_detection_leverage: null problem");
+    }
+    if (!x_full || (pb->P.N > 0 && !leverage)) return set_error(AAR_ERR_INVALID, "aar_problem_detection_leverage: null argument");
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_detection_leverage: report->struct_size not set");
+    int rc = predict_refuse(pb, "aar_problem_detection_leverage");
+    if (rc) return rc;
+    return predict_run(pb, x_full, 2, pb->P.N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, leverage, row_leverage, report);
 }
 
 int aar_set_kernel_profiling(aar_problem *pb, int on) {

@@ -548,6 +548,31 @@ void launch_cov_diag_blocks(const double *Sinv, int n_pad, int A, double *out, h
 // out[f][36] = (J^T J)^-1 block of local frame f from Vinv of block set `which` (mu = 0), its W blocks and Sinv
 void launch_cov_frames(const DeviceProblem &P, int which, const double *Sinv, const int32_t *rowmask, double *out, hipStream_t st);
 
+// predicted corners with covariance, detection leverages (predict_kernels.hip).  The row mask of the covariance
+// chain with a second value: a row without an unknown is PREDICT_CONST where the parameter is a constant (root, non-optimised group,
+// fixed by the caller, padding: ZERO covariance) and PREDICT_UNSEEN where it has a z column that nothing determines (covariance undefined).
+// k_cov_stage and k_cov_frames only ask whether a row is masked at all.
+constexpr int PREDICT_LIVE = 0, PREDICT_CONST = 1, PREDICT_UNSEEN = 2;
+struct PredictArgs {
+    const double *ent, *K;                // entity rows of the point (launch_unpack), camera matrices K[kstride * camera + i]
+    int kstride, C, A;                    // cameras, shared entities (frame f's row is A + f)
+    double h;
+    int64_t n;                            // queries
+    const int32_t *q_cam, *q_marker, *q_frame;   // explicit queries: camera, marker and frame INDEX (modes 0, 1)
+    const ObsIdx *obs;                    // ... or the problem's ordering A (mode 2)
+    const int32_t *fslot_start, *fslot_ent, *rowmask;   // rowmask [n_pad]: PREDICT_*
+    int frames_opt, n_pad;                // 0: the frames are constants, gain / frame_cov are not touched
+    const double *gain, *Sinv, *frame_cov;   // launch_predict_gains' [total_slots][36], S^-1 (lower triangle), launch_cov_frames' [F][36]
+    double *uv, *cov;                     // [n][8], [n][64] (modes 0, 1; cov mode 0 only)
+    uint8_t *status;                      // [n] bit 0: a corner at non-positive depth, bit 1: covariance undefined
+    double *lev, *row_lev;                // [n], [n][8] or NULL (mode 2): trace and diagonal of C
+};
+// gain[s][36] = V_f^-1 W_s^T for every slot s (frame f's slots at fslot_start[f]), masked rows' columns zero: needs Vinv at mu = 0 and the fp64 W
+void launch_predict_gains(const DeviceProblem &P, int which, const int32_t *rowmask, double *gain, hipStream_t st);
+// mode 0: uv | cov | status of explicit queries, 1: uv | status alone (nothing of the chain is read), 2: lev | row_lev | status of the
+// problem's own detections in reference order.  One launch, one wavefront per query
+void launch_predict_corners(const PredictArgs &a, int mode, hipStream_t st);
+
 // residual report (resid_kernels.hip).  The select's state: the key bits [pshift, 63) picked so far, the rank still
 // wanted inside that bucket, done (prefix = the key), single (one key left in the bucket: the next pass fetches it), t = the threshold
 constexpr int RR_DIGIT_BITS = 11, RR_BINS = 1 << RR_DIGIT_BITS, RR_PASSES = 6;   // 63 key bits = 5 digits of 11 + one of 8

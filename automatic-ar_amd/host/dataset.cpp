@@ -1,4 +1,5 @@
 // aar_dataset lifetime, error reporting, shard planning.  Host only.
+#include <cstdint>
 #include <cstring>
 #include <string>
 
@@ -133,6 +134,27 @@ int aar_plan_shards(int32_t num_frames, const int64_t *obs_per_frame, int32_t wo
         begin[r] = f;
     }
     begin[world] = num_frames;
+    return AAR_OK;
+}
+
+// The queries of aar_problem_predict_corners against the problem they are meant for: the first index out of range is named.
+int aar_predict_query_validate(const aar_problem_desc *d, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker, const int32_t *q_frame) {
+    if (!d) return aar::set_error(AAR_ERR_INVALID, "aar_predict_query_validate: null problem description");
+    if (n_query < 0 || n_query > INT32_MAX)
+        return aar::set_error(AAR_ERR_INVALID, "aar_predict_query_validate: n_query = %lld must lie in 0 .. %d", (long long)n_query, (int)INT32_MAX);
+    if (n_query == 0) return AAR_OK;
+    if (!q_cam || !q_marker || !q_frame) return aar::set_error(AAR_ERR_INVALID, "aar_predict_query_validate: null query array with n_query = %lld", (long long)n_query);
+    for (int64_t i = 0; i < n_query; i++) {
+        if (q_cam[i] < 0 || q_cam[i] >= d->num_cams)
+            return aar::set_error(AAR_ERR_INVALID, "aar_predict_query_validate: q_cam[%lld] = %d lies outside 0 .. num_cams - 1 = %d", (long long)i, (int)q_cam[i],
+                                  (int)d->num_cams - 1);
+        if (q_marker[i] < 0 || q_marker[i] >= d->num_markers)
+            return aar::set_error(AAR_ERR_INVALID, "aar_predict_query_validate: q_marker[%lld] = %d lies outside 0 .. num_markers - 1 = %d", (long long)i,
+                                  (int)q_marker[i], (int)d->num_markers - 1);
+        if (q_frame[i] < 0 || q_frame[i] >= d->num_frames)
+            return aar::set_error(AAR_ERR_INVALID, "aar_predict_query_validate: q_frame[%lld] = %d lies outside 0 .. num_frames - 1 = %d", (long long)i,
+                                  (int)q_frame[i], (int)d->num_frames - 1);
+    }
     return AAR_OK;
 }
 

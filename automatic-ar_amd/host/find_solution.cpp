@@ -28,8 +28,9 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>] [-relative-to <frame_id>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-leverage <h_min>] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>] [-relative-to <frame_id>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
+    cout << "       -leverage <h_min>    also write final.leverage.yaml (leverage of every detection, 0 .. 8; those from h_min up are listed)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
     cout << "                            (up to 3 rounds, until a round drops nothing); final.solution keeps the remaining detections" << endl;
@@ -235,6 +236,10 @@ int main(int argc, char *argv[]) {
     const double marker_size = stod(argv[2]);
     bool use_subseqs = false, with_huber = false, set_threshold = false, from_initial = false, tracking_only = false;
     bool covariance = false;   // not an option of the reference: -covariance also writes final.covariance.yaml (aar_problem_covariance)
+    // nor this: -leverage h_min also writes final.leverage.yaml (aar_problem_detection_leverage): the detections whose
+    // leverage is at least h_min are listed with their reprojection error
+    bool leverage = false, leverage_set = false;
+    double leverage_min = 0.0;
     bool residuals = false;    // nor these: -residuals writes final.residuals.yaml; -reject-outliers k drops detections above max(min_px, k median) and solves again
     double reject_k = 0.0, reject_min_px = 0.0;
     double threshold = 2.0;
@@ -307,7 +312,7 @@ int main(int argc, char *argv[]) {
     int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
     double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion, Leverage } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -318,6 +323,7 @@ int main(int argc, char *argv[]) {
         else if (a == "-thresh") { set_threshold = true; arg_flag = Threshold; }
         else if (a == "-solver") arg_flag = Solver;
         else if (a == "-covariance") { covariance = true; arg_flag = NONE; }
+        else if (a == "-leverage") { leverage = true; arg_flag = Leverage; }
         else if (a == "-residuals") { residuals = true; arg_flag = NONE; }
         else if (a == "-reject-outliers") arg_flag = RejectK;
         else if (a == "-reject-min-px") arg_flag = RejectPx;
@@ -442,6 +448,14 @@ int main(int argc, char *argv[]) {
             (arg_flag == PriorDeg ? prior_sigma_deg : prior_sigma_m) = v;
             arg_flag = NONE;
         }
+        else if (arg_flag == Leverage) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || a.empty() || !(v >= 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            leverage_min = v;
+            leverage_set = true;
+            arg_flag = NONE;
+        }
         else if (arg_flag == RejectK || arg_flag == RejectPx) {
             const double v = stod(a);
             if (!(v > 0.0) && !(arg_flag == RejectPx && v == 0.0)) return print_usage(argv[0]);
@@ -458,6 +472,7 @@ int main(int argc, char *argv[]) {
     }
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (smooth_covariance && !smooth) return print_usage(argv[0]);
+    if (leverage && !leverage_set) return print_usage(argv[0]);
     if (smooth_cv && (!smooth || smooth_cv_args != 2 || smooth_covariance || fit_sigmas || resample)) return print_usage(argv[0]);
     if (cv_covariance && (!smooth || !smooth_cv)) return print_usage(argv[0]);
     if (cv_fit_sigmas && (!smooth || !smooth_cv || live)) return print_usage(argv[0]);
@@ -808,6 +823,21 @@ int main(int argc, char *argv[]) {
                  << cov_path << endl;
         } catch (const exception &e) {
             cerr << "covariance failed: " << e.what() << endl;
+            return 3;
+        }
+    }
+    if (leverage) {
+        const string lev_path = folder_path + "/final.leverage.yaml";
+        try {
+            const aar::MultiCamMapper::DetectionLeverage lv = mcm.detection_leverage(false);
+            const aar::MultiCamMapper::ResidualReport rr = mcm.residual_report(nullptr);
+            if (!mcm.write_leverage_file(lev_path, lv, leverage_min, rr.det_err)) throw runtime_error(aar_last_error());
+            int64_t listed = 0;
+            for (double h : lv.leverage) listed += !(h < leverage_min);
+            cout << "leverage: sum " << lv.report.leverage_sum << " over " << lv.leverage.size() << " detections (" << lv.report.num_live_vars
+                 << " live unknowns), " << listed << " at " << leverage_min << " or above, written to " << lev_path << endl;
+        } catch (const exception &e) {
+            cerr << "leverage failed: " << e.what() << endl;
             return 3;
         }
     }

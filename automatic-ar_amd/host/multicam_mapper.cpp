@@ -468,6 +468,63 @@ bool MultiCamMapper::write_residuals_file(const std::string &path, const Residua
                                           &rep.report) == AAR_OK;
 }
 
+MultiCamMapper::CornerPrediction MultiCamMapper::predict_corners(const std::vector<int> &cam_ids, const std::vector<int> &marker_ids,
+                                                                 const std::vector<int> &frame_ids, bool covariance) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::predict_corners: no data set");
+    if (cam_ids.size() != marker_ids.size() || cam_ids.size() != frame_ids.size())
+        throw std::invalid_argument("MultiCamMapper::predict_corners: the three id lists differ in length");
+    auto index_of = [](const int32_t *ids, int n, int id, const char *what) -> int32_t {
+        const int32_t *e = ids + n, *p = std::lower_bound(ids, e, id);   // (ids ascending, as constraint_indices reads them)
+        if (p == e || *p != id) throw std::invalid_argument(std::string("MultiCamMapper: no ") + what + " with id " + std::to_string(id));
+        return (int32_t)(p - ids);
+    };
+    const size_t Q = cam_ids.size();
+    std::vector<int32_t> qc(Q), qm(Q), qf(Q);
+    for (size_t i = 0; i < Q; i++) {
+        qc[i] = index_of(data_->cam_ids, data_->num_cams, cam_ids[i], "camera");
+        qm[i] = index_of(data_->marker_ids, data_->num_markers, marker_ids[i], "marker");
+        qf[i] = index_of(data_->frame_ids, data_->num_frames, frame_ids[i], "frame");
+    }
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    CornerPrediction out;
+    out.uv.assign(8 * std::max<size_t>(Q, 1), NAN);
+    if (covariance) out.cov.assign(64 * std::max<size_t>(Q, 1), NAN);
+    out.status.assign(std::max<size_t>(Q, 1), 0);
+    out.report.struct_size = (uint32_t)sizeof out.report;
+    std::vector<double> x = problem_vector();
+    if (aar_problem_predict_corners(problem_, x.data(), (int64_t)Q, qc.data(), qm.data(), qf.data(), out.uv.data(), covariance ? out.cov.data() : nullptr,
+                                    out.status.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.uv.resize(8 * Q);
+    out.status.resize(Q);
+    if (covariance) {
+        out.cov.resize(64 * Q);
+        for (double &v : out.cov) v *= out.report.sigma2;
+    }
+    return out;
+}
+
+MultiCamMapper::DetectionLeverage MultiCamMapper::detection_leverage(bool rows) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::detection_leverage: no data set");
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    const size_t N = (size_t)data_->num_obs;
+    DetectionLeverage out;
+    out.leverage.assign(std::max<size_t>(N, 1), NAN);
+    if (rows) out.row_leverage.assign(8 * std::max<size_t>(N, 1), NAN);
+    out.report.struct_size = (uint32_t)sizeof out.report;
+    std::vector<double> x = problem_vector();
+    if (aar_problem_detection_leverage(problem_, x.data(), out.leverage.data(), rows ? out.row_leverage.data() : nullptr, &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.leverage.resize(N);
+    if (rows) out.row_leverage.resize(8 * N);
+    return out;
+}
+
+bool MultiCamMapper::write_leverage_file(const std::string &path, const DetectionLeverage &lev, double h_min, const std::vector<double> &det_err) {
+    if (!data_ || lev.leverage.size() != (size_t)data_->num_obs || (!det_err.empty() && det_err.size() != lev.leverage.size())) return false;
+    return aar_leverage_write_yaml(path.c_str(), data_, lev.leverage.data(), det_err.empty() ? nullptr : det_err.data(), h_min, &lev.report) == AAR_OK;
+}
+
 void MultiCamMapper::error_function(const eVector &input, eVector &error) {
     if (probed(detail::EVAL_ERROR_FUNCTION)) return;
     if (!data_) throw std::runtime_error("MultiCamMapper::error_function: no data set");

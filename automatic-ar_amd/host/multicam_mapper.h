@@ -563,6 +563,29 @@ class MultiCamMapper {
     int64_t reject_outliers(double k_median, double min_px = 0.0, ResidualReport *out = nullptr);
     bool write_residuals_file(const std::string &path, const ResidualReport &rep);   // YAML, aar_residual_report_write_yaml
 
+    // EXTENSION, no counterpart in the reference: where the solved problem expects the four corners of a marker in a
+    // camera in a frame, and how well it knows (aar_problem_predict_corners at io_vec's poses, for the current Config).  Queries are by ID:
+    // cam_ids[i], marker_ids[i], frame_ids[i]; an unknown id throws std::invalid_argument naming it.  uv [Q][8] = u0 v0 .. u3 v3 in undistorted
+    // pixels; cov [Q][64] row-major and SCALED by sigma2 (the a-posteriori covariance of the corners; a NEW detection scatters with
+    // cov + sigma2 I); status [Q]: AAR_PREDICT_BEHIND (uv and cov NaN), AAR_PREDICT_UNDEFINED (cov NaN).  covariance = false: uv and status
+    // alone, without the covariance chain.  Throws std::runtime_error on failure.
+    struct CornerPrediction {
+        aar_predict_report report{};
+        std::vector<double> uv, cov;
+        std::vector<uint8_t> status;
+    };
+    CornerPrediction predict_corners(const std::vector<int> &cam_ids, const std::vector<int> &marker_ids, const std::vector<int> &frame_ids,
+                                     bool covariance = true);
+    // the leverage tr(C_i) (0 .. 8, UNSCALED) of every detection of the data set in its order (aar_problem_detection_leverage): a small
+    // residual means something only where the leverage is small.  rows: also diag(C_i) [N][8]
+    struct DetectionLeverage {
+        aar_predict_report report{};
+        std::vector<double> leverage, row_leverage;
+    };
+    DetectionLeverage detection_leverage(bool rows = false);
+    // YAML, aar_leverage_write_yaml: det_err as residual_report().det_err, or empty
+    bool write_leverage_file(const std::string &path, const DetectionLeverage &lev, double h_min, const std::vector<double> &det_err = {});
+
     // EXTENSION, no counterpart in the reference: per-entity fixing and pose priors (aar_problem_constraints), by ID.
     // Fixed cameras / markers stay exactly where they are; a prior pulls a camera / marker toward a 4x4 transform T (the convention of
     // get_transforms_to_root_cam / _marker) with a 6x6 information matrix over (rx ry rz tx ty tz).  They take effect when the device problem

@@ -353,6 +353,43 @@ int aar_residual_report_write_yaml(const char *path, const aar_dataset *d, const
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
 }
 
+int aar_leverage_write_yaml(const char *path, const aar_dataset *d, const double *leverage, const double *det_err, double h_min,
+                            const aar_predict_report *rep) {
+    if (!path || !d || !rep || (!leverage && d->num_obs > 0)) return set_error(AAR_ERR_INVALID, "aar_leverage_write_yaml: null argument");
+    if (std::isnan(h_min)) return set_error(AAR_ERR_INVALID, "aar_leverage_write_yaml: h_min is NaN");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "sigma2: %s\nnum_live_vars: %lld\nleverage_sum: %s\nh_min: %s\n", fs_double_nf(rep->sigma2).c_str(), (long long)rep->num_live_vars,
+            fs_double_nf(rep->leverage_sum).c_str(), fs_double_nf(h_min).c_str());
+    // per entity {detections, sum, max} over its detections with a finite leverage, in detection order
+    std::vector<double> cs(3 * (size_t)d->num_cams, 0.0), ms(3 * (size_t)d->num_markers, 0.0);
+    for (int64_t o = 0; o < d->num_obs; o++) {
+        if (!std::isfinite(leverage[o])) continue;
+        for (double *q : {cs.data() + 3LL * d->obs_cam[o], ms.data() + 3LL * d->obs_marker[o]}) {
+            q[0] += 1.0;
+            q[1] += leverage[o];
+            q[2] = leverage[o] > q[2] ? leverage[o] : q[2];
+        }
+    }
+    auto entity = [&](const char *key, int id, const double *q) {
+        fprintf(f, "   - { %s:%d, detections:%lld, mean: %s, max: %s }\n", key, id, (long long)q[0], fs_double_nf(q[0] > 0 ? q[1] / q[0] : 0.0).c_str(),
+                fs_double_nf(q[2]).c_str());
+    };
+    fprintf(f, "cameras:\n");
+    for (int c = 0; c < d->num_cams; c++) entity("cam_id", d->cam_ids[c], cs.data() + 3LL * c);
+    fprintf(f, "markers:\n");
+    for (int m = 0; m < d->num_markers; m++) entity("marker_id", d->marker_ids[m], ms.data() + 3LL * m);
+    fprintf(f, "high_leverage_detections:\n");
+    for (int64_t o = 0; o < d->num_obs; o++)
+        if (!(leverage[o] < h_min))   // (a non-finite leverage is listed)
+            fprintf(f, "   - { frame_id:%d, cam_id:%d, marker_id:%d, leverage: %s, error: %s }\n", d->frame_ids[d->obs_frame[o]], d->cam_ids[d->obs_cam[o]],
+                    d->marker_ids[d->obs_marker[o]], fs_double_nf(leverage[o]).c_str(), fs_double_nf(det_err ? det_err[o] : NAN).c_str());
+    const bool good = !ferror(f);
+    fclose(f);
+    return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
+}
+
 int aar_detections_write(const char *path, const aar_dataset *d) {
     if (!path || !d) return set_error(AAR_ERR_INVALID, "aar_detections_write: null argument");
     FILE *f = fopen(path, "wb");

@@ -423,6 +423,56 @@ int aar_dataset_select_observations(const aar_dataset *d, const uint8_t *keep, a
 int aar_residual_report_write_yaml(const char *path, const aar_dataset *d, const double *cam_stats, const double *marker_stats,
                                    const double *det_err, const uint8_t *keep, const aar_residual_report *report);
 
+/* Predicted marker corners with covariance, and the leverage of every detection (no counterpart in the reference; DESIGN.md section
+ * 36).  For a query q = (camera c, marker m, frame f), all three named by INDEX (camera and marker index as in aar_problem_desc, global
+ * frame index): u_q = the four projected corners u0 v0 .. u3 v3 at x_full, in the undistorted pixel coordinates the bundle works in,
+ * and C_q = G_q Sigma_q G_q^T (8 x 8, row-major, symmetric to the bit) with G_q = du_q / d(camera c, marker m, frame f) (8 x 18) and
+ * Sigma_q the 18 x 18 block of (J^T J)^-1 of aar_problem_covariance for that triple, its frame-camera and frame-marker cross blocks
+ * included.  C is UNSCALED like everything aar_problem_covariance returns.  HOW TO USE IT: the a-posteriori covariance of a predicted
+ * corner is sigma2 * C; the search window for a NEW detection of that marker, whose own pixel noise adds to it, is sigma2 * (C + I).
+ * A parameter that is a constant (a root, a member of a non-optimised group, an entity fixed by the caller, the frames of a problem
+ * that does not optimise them) contributes ZERO covariance.  status[q]:
+ *   bit 0 (AAR_PREDICT_BEHIND):     a corner has non-positive depth in camera c: uv and cov of the query are NaN
+ *   bit 1 (AAR_PREDICT_UNDEFINED):  the covariance is undefined: cov is NaN, uv is still written.  This is the case iff frames are optimised
+ *                                   and frame f has no observations, or camera c / marker m has a z column, is not held and nothing touches it
+ *                                   (the rows aar_problem_covariance reports as NaN because they are unseen)
+ * cov == NULL runs no covariance chain: one unpack and one launch give uv and status.  Duplicate queries are allowed; a query's outputs
+ * depend on its triple and the solution only, not on the other queries; on a deterministic problem two calls give the same bits.
+ * aar_problem_detection_leverage takes the problem's own detections as the queries (reference order, as aar_problem_residual_report):
+ * leverage[i] = tr(C_i), between 0 and 8, row_leverage[i][k] = C_i[k][k].  Without priors the leverages sum to num_live_vars and every
+ * eigenvalue of C_i lies in [0, 1]: a detection with leverage 8 is contradicted by nothing, and its residual is zero whatever was detected.
+ * Refusals, nothing written: a problem with a communicator and a problem created with optimize_cam_intrinsics (its corners also depend on
+ * fx, cx, fy, cy: the next step) are AAR_ERR_UNSUPPORTED; whatever makes aar_problem_covariance fail fails here with the same message.
+ * Both leave the problem as aar_problem_covariance does (no LM state).  n_query = 0 is AAR_OK and writes nothing but the report.
+ *   uv:      [n_query][8];  cov: [n_query][64], may be NULL;  status: [n_query], may be NULL
+ *   leverage: [aar_problem_local_obs];  row_leverage: [aar_problem_local_obs][8], may be NULL
+ *   report:  caller sets struct_size = sizeof(aar_predict_report); at most that many bytes are filled; may be NULL */
+enum { AAR_PREDICT_BEHIND = 1, AAR_PREDICT_UNDEFINED = 2 };
+typedef struct aar_predict_report {
+    uint32_t struct_size;
+    int64_t num_residuals;                    /* 8 N                                                                     */
+    int64_t num_vars;                         /* P = aar_problem_num_vars                                                */
+    double sum_sq;                            /* at x_full (NaN when no covariance chain ran)                            */
+    double sigma2;                            /* sum_sq / (num_residuals - num_vars), as aar_covariance_report           */
+    int64_t num_live_vars;                    /* unknowns with a z column that something touches and nobody holds        */
+    double leverage_sum;                      /* sum of the finite leverages in detection order (predict_corners: of tr(C_q)) */
+    int64_t undefined, behind;                /* queries with status bit 1 / bit 0                                       */
+    int32_t launches;                         /* kernel launches of the call                                             */
+    double seconds;                           /* wall time of the call                                                   */
+} aar_predict_report;
+/* Host code, no device: AAR_ERR_INVALID naming the first query whose camera, marker or frame index is out of range (or a NULL array with
+ * n_query > 0, or n_query < 0).  n_query = 0 is AAR_OK. */
+int aar_predict_query_validate(const aar_problem_desc *, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker, const int32_t *q_frame);
+int aar_problem_predict_corners(aar_problem *, const double *x_full, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker,
+                                const int32_t *q_frame, double *uv, double *cov, uint8_t *status, aar_predict_report *report);
+int aar_problem_detection_leverage(aar_problem *, const double *x_full, double *leverage, double *row_leverage, aar_predict_report *report);
+/* YAML (the dialect of aar_residual_report_write_yaml) of the leverages of a single-GPU problem created from d: sigma2, num_live_vars,
+ * leverage_sum; per camera id and marker id {detections, mean, max} of the leverages of its detections; the detections with
+ * leverage >= h_min (or a non-finite one) as (frame id, camera id, marker id, leverage, error) -- det_err [num_obs] as
+ * aar_problem_residual_report gives it, may be NULL (error: .nan).  Host code. */
+int aar_leverage_write_yaml(const char *path, const aar_dataset *d, const double *leverage, const double *det_err, double h_min,
+                            const aar_predict_report *report);
+
 /* Per-entity fixing and pose priors (no counterpart in the reference).  Cameras and markers are named by INDEX
  * (problem indices as in aar_problem_desc, not ids).
  *  Fixed entities: fixed_cams / fixed_markers are held where they are, exactly as the roots are.  The layout of z does not change
