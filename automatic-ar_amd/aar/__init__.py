@@ -1819,152 +1819,129 @@ class Problem:
         report = {k: getattr(rep, k) for k, _ in CSmoothReport._fields_ if k != "struct_size"}
         return x, report, fe[:F], pe[:max(F - 1, 0)]
 
+    # The smoother's entries come in pairs: aar_..., and aar_...2 with one more output (off2, lag2_cov, sums [6]) for either motion model.
+    # Each pair shares one helper below; fn: the C function's name, two: it is the ...2 one.  sp_args: SmoothParams' arguments.
+    def _smooth_call(self, x_full, sp_args, rep_type=None):
+        """(x, F, SmoothParams, the zeroed report or None) that every helper starts from"""
+        x = self._x(x_full)
+        sp = SmoothParams(*sp_args)
+        sp.check_lengths(self.ds.num_frames)
+        rep = None
+        if rep_type is not None:
+            rep = rep_type()
+            rep.struct_size = C.sizeof(rep_type)
+        return x, self.ds.num_frames, sp, rep
+
+    @staticmethod
+    def _report(rep):
+        return {k: getattr(rep, k) for k, _ in type(rep)._fields_ if k != "struct_size"}
+
+    def _smooth_system(self, fn, two, x_full, mu, sp_args):
+        x, F, sp, _ = self._smooth_call(x_full, sp_args)
+        diag, off, off2 = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6)), np.zeros((max(F - 2, 1), 6, 6))
+        rhs, delta, cost = np.zeros(6 * max(F, 1)), np.zeros(6 * max(F, 1)), np.zeros(2)
+        _check(getattr(lib(), fn)(self.handle, _dptr(x), C.byref(sp.c), float(mu), _dptr(diag), _dptr(off), *([_dptr(off2)] if two else []),
+                                  _dptr(rhs), _dptr(delta), _dptr(cost)))
+        return (diag[:F], off[:max(F - 1, 0)], *([off2[:max(F - 2, 0)]] if two else []), rhs[:6 * F], delta[:6 * F], (cost[0], cost[1]))
+
+    def _smooth_covariance(self, fn, two, lag2, x_full, sp_args):
+        x, F, sp, rep = self._smooth_call(x_full, sp_args, CSmoothCovarianceReport)
+        fc, lc, l2 = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6)), np.zeros((max(F - 2, 1), 6, 6))
+        _check(getattr(lib(), fn)(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), *([_dptr(l2) if lag2 else None] if two else []),
+                                  C.byref(rep)))
+        return (fc[:F], lc[:max(F - 1, 0)], *([l2[:max(F - 2, 0)] if lag2 else None] if two else []), self._report(rep))
+
+    def _smooth_fit(self, fn, x_full, params, fit, sp_args):
+        x, _, sp, rep = self._smooth_call(x_full, sp_args, CSmoothFitReport)
+        x = np.array(x, dtype=np.float64)
+        fp = fit if isinstance(fit, CSmoothFitParams) else smooth_fit_params(**(fit or {}))
+        path = np.zeros((max(int(fp.max_iters), 0) + 1, 3))
+        _check(getattr(lib(), fn)(self.handle, _dptr(x), C.byref(params) if params is not None else None, C.byref(sp.c), C.byref(fp), _dptr(path),
+                                  C.byref(rep)))
+        report = self._report(rep)
+        return x, report, path[:report["iterations"] + 1]
+
+    def _smooth_fit_terms(self, fn, two, x_full, sp_args):
+        x, F, sp, _ = self._smooth_call(x_full, sp_args)
+        terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(6 if two else 4)
+        _check(getattr(lib(), fn)(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
+        return terms[:max(F - 1, 0)], sums
+
+    def _smooth_query(self, fn, x_full, query_time, covariance, sp_args):
+        x, _, sp, rep = self._smooth_call(x_full, sp_args, CSmoothQueryReport)
+        qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
+        Q = len(qt)
+        pose, seg = np.zeros((max(Q, 1), 6)), np.zeros(max(Q, 1), dtype=np.int32)
+        cov = np.zeros((max(Q, 1), 6, 6)) if covariance else None
+        _check(getattr(lib(), fn)(self.handle, _dptr(x), C.byref(sp.c), Q, _dptr(qt) if Q else None, _dptr(pose), _dptr(cov) if covariance else None,
+                                  seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        return pose[:Q], cov[:Q] if covariance else None, seg[:Q], self._report(rep)
+
     def track_smooth_system(self, x_full, sigma_rot, sigma_trans, mu, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_system: (diag [F, 6, 6], off [F-1, 6, 6], rhs [6F], delta [6F], (data cost, prior cost)) of one try at x_full"""
-        x = self._x(x_full)
-        F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(F)
-        diag, off = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6))
-        rhs, delta, cost = np.zeros(6 * max(F, 1)), np.zeros(6 * max(F, 1)), np.zeros(2)
-        _check(lib().aar_track_smooth_system(self.handle, _dptr(x), C.byref(sp.c), float(mu), _dptr(diag), _dptr(off), _dptr(rhs),
-                                             _dptr(delta), _dptr(cost)))
-        return diag[:F], off[:max(F - 1, 0)], rhs[:6 * F], delta[:6 * F], (cost[0], cost[1])
+        return self._smooth_system("aar_track_smooth_system", False, x_full, mu,
+                                   (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_system2(self, x_full, sigma_rot, sigma_trans, mu, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_system2, either model: (diag [F, 6, 6], off [F-1, 6, 6], off2 [F-2, 6, 6], rhs [6F], delta [6F], (data cost, prior
         cost)) of one try at x_full; off2 is zero under the random walk"""
-        x = self._x(x_full)
-        F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(F)
-        diag, off, off2 = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6)), np.zeros((max(F - 2, 1), 6, 6))
-        rhs, delta, cost = np.zeros(6 * max(F, 1)), np.zeros(6 * max(F, 1)), np.zeros(2)
-        _check(lib().aar_track_smooth_system2(self.handle, _dptr(x), C.byref(sp.c), float(mu), _dptr(diag), _dptr(off), _dptr(off2), _dptr(rhs),
-                                              _dptr(delta), _dptr(cost)))
-        return diag[:F], off[:max(F - 1, 0)], off2[:max(F - 2, 0)], rhs[:6 * F], delta[:6 * F], (cost[0], cost[1])
+        return self._smooth_system("aar_track_smooth_system2", True, x_full, mu,
+                                   (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_covariance(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_covariance: (frame_cov [F, 6, 6] = (H^-1)_ff, lag_cov [F-1, 6, 6] = (H^-1)_{f,f+1}, report dict) at x_full, H the
         matrix of track_smooth_system at mu = 0.  Both UNSCALED: multiply by report["sigma2"]."""
-        x = self._x(x_full)
-        F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(F)
-        fc, lc = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6))
-        rep = CSmoothCovarianceReport()
-        rep.struct_size = C.sizeof(CSmoothCovarianceReport)
-        _check(lib().aar_track_smooth_covariance(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), C.byref(rep)))
-        report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
-        return fc[:F], lc[:max(F - 1, 0)], report
+        return self._smooth_covariance("aar_track_smooth_covariance", False, False, x_full,
+                                       (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_covariance2(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0,
                                  lag2=True):
         """aar_track_smooth_covariance2, either model: (frame_cov [F, 6, 6] = (H^-1)_ff, lag_cov [F-1, 6, 6] = (H^-1)_{f,f+1}, lag2_cov
         [F-2, 6, 6] = (H^-1)_{f,f+2}, report dict) at x_full, H the matrix of track_smooth_system2 at mu = 0.  All UNSCALED: multiply by
         report["sigma2"].  lag2=False passes NULL for lag2_cov (the random walk refuses it otherwise) and returns None in its place."""
-        x = self._x(x_full)
-        F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(F)
-        fc, lc, l2 = np.zeros((max(F, 1), 6, 6)), np.zeros((max(F - 1, 1), 6, 6)), np.zeros((max(F - 2, 1), 6, 6))
-        rep = CSmoothCovarianceReport()
-        rep.struct_size = C.sizeof(CSmoothCovarianceReport)
-        _check(lib().aar_track_smooth_covariance2(self.handle, _dptr(x), C.byref(sp.c), _dptr(fc), _dptr(lc), _dptr(l2) if lag2 else None,
-                                                  C.byref(rep)))
-        report = {k: getattr(rep, k) for k, _ in CSmoothCovarianceReport._fields_ if k != "struct_size"}
-        return fc[:F], lc[:max(F - 1, 0)], l2[:max(F - 2, 0)] if lag2 else None, report
+        return self._smooth_covariance("aar_track_smooth_covariance2", True, lag2, x_full,
+                                       (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_fit(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit: the pixel noise and the motion sigmas fitted to the sequence by EM, from the effective start values
         sigma_rot, sigma_trans.  fit: None (the defaults), a dict of aar_smooth_fit_params fields, or a CSmoothFitParams.  Returns (x_full with
         the track at the fitted values, report dict, path [iterations + 1, 3] = (sigma_px, sigma_rot, sigma_trans) per iteration).  Hand
         report["sigma_rot_eff"], report["sigma_trans_eff"] to track_smooth / tracker_params."""
-        x = np.array(self._x(x_full), dtype=np.float64)
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(self.ds.num_frames)
-        fp = fit if isinstance(fit, CSmoothFitParams) else smooth_fit_params(**(fit or {}))
-        path = np.zeros((max(int(fp.max_iters), 0) + 1, 3))
-        rep = CSmoothFitReport()
-        rep.struct_size = C.sizeof(CSmoothFitReport)
-        _check(lib().aar_track_smooth_fit(self.handle, _dptr(x), C.byref(params) if params is not None else None, C.byref(sp.c), C.byref(fp),
-                                          _dptr(path), C.byref(rep)))
-        report = {k: getattr(rep, k) for k, _ in CSmoothFitReport._fields_ if k != "struct_size"}
-        return x, report, path[:report["iterations"] + 1]
+        return self._smooth_fit("aar_track_smooth_fit", x_full, params, fit,
+                                (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_fit_terms(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit_terms: one E-step at x_full and the given effective sigmas, no smoothing.  Returns (pair_terms [F-1, 4] =
         a_r, u_r, a_t, u_t, sums [4] = A_r, U_r, A_t, U_t)."""
-        x = self._x(x_full)
-        F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(F)
-        terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(4)
-        _check(lib().aar_track_smooth_fit_terms(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
-        return terms[:max(F - 1, 0)], sums
+        return self._smooth_fit_terms("aar_track_smooth_fit_terms", False, x_full,
+                                      (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_fit2(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, params=None, fit=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit2, either model: track_smooth_fit's arguments and returns.  Under constant velocity sigma_rot0, sigma_trans0 are
         physical and held; smooth afterwards with report["sigma_rot_eff"], report["sigma_trans_eff"] and sigma_rot0 / report["sigma_px"],
         sigma_trans0 / report["sigma_px"]."""
-        x = np.array(self._x(x_full), dtype=np.float64)
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(self.ds.num_frames)
-        fp = fit if isinstance(fit, CSmoothFitParams) else smooth_fit_params(**(fit or {}))
-        path = np.zeros((max(int(fp.max_iters), 0) + 1, 3))
-        rep = CSmoothFitReport()
-        rep.struct_size = C.sizeof(CSmoothFitReport)
-        _check(lib().aar_track_smooth_fit2(self.handle, _dptr(x), C.byref(params) if params is not None else None, C.byref(sp.c), C.byref(fp),
-                                           _dptr(path), C.byref(rep)))
-        report = {k: getattr(rep, k) for k, _ in CSmoothFitReport._fields_ if k != "struct_size"}
-        return x, report, path[:report["iterations"] + 1]
+        return self._smooth_fit("aar_track_smooth_fit2", x_full, params, fit,
+                                (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_fit_terms2(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_fit_terms2, either model: one E-step at x_full and the given effective sigmas, no smoothing.  Returns (pair_terms
         [F-1, 4] = a_r, u_r, a_t, u_t with entry 0 = pair 0, sums [6] = A_r, U_r, A_t, U_t over the terms 1 .. F-2, u_0, pair 0's cost; the
         last two are zero under the random walk, whose sums run over every pair)."""
-        x = self._x(x_full)
-        F = self.ds.num_frames
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(F)
-        terms, sums = np.zeros((max(F - 1, 1), 4)), np.zeros(6)
-        _check(lib().aar_track_smooth_fit_terms2(self.handle, _dptr(x), C.byref(sp.c), _dptr(terms), _dptr(sums)))
-        return terms[:max(F - 1, 0)], sums
+        return self._smooth_fit_terms("aar_track_smooth_fit_terms2", True, x_full,
+                                      (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_query(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_query: the smoothed track at the times query_time [Q] (any order, duplicates allowed).  Returns (pose [Q, 6],
         cov [Q, 6, 6] UNSCALED -- multiply by report["sigma2"] -- or None without covariance, segment [Q], report dict)."""
-        x = self._x(x_full)
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(self.ds.num_frames)
-        qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
-        Q = len(qt)
-        pose, seg = np.zeros((max(Q, 1), 6)), np.zeros(max(Q, 1), dtype=np.int32)
-        cov = np.zeros((max(Q, 1), 6, 6)) if covariance else None
-        rep = CSmoothQueryReport()
-        rep.struct_size = C.sizeof(CSmoothQueryReport)
-        _check(lib().aar_track_smooth_query(self.handle, _dptr(x), C.byref(sp.c), Q, _dptr(qt) if Q else None, _dptr(pose),
-                                            _dptr(cov) if covariance else None, seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
-        report = {k: getattr(rep, k) for k, _ in CSmoothQueryReport._fields_ if k != "struct_size"}
-        return pose[:Q], cov[:Q] if covariance else None, seg[:Q], report
+        return self._smooth_query("aar_track_smooth_query", x_full, query_time, covariance,
+                                  (sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_query2(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, covariance=True, model=None, sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_query2, either model: track_smooth_query's arguments and returns.  Under constant velocity the answer is one
         Gauss-Newton step of the smoother for a frame without detections inserted at the query's time; covariance=False runs the same chain and
         saves the copy of the blocks alone."""
-        x = self._x(x_full)
-        sp = SmoothParams(sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0)
-        sp.check_lengths(self.ds.num_frames)
-        qt = np.ascontiguousarray(query_time, dtype=np.float64).reshape(-1)
-        Q = len(qt)
-        pose, seg = np.zeros((max(Q, 1), 6)), np.zeros(max(Q, 1), dtype=np.int32)
-        cov = np.zeros((max(Q, 1), 6, 6)) if covariance else None
-        rep = CSmoothQueryReport()
-        rep.struct_size = C.sizeof(CSmoothQueryReport)
-        _check(lib().aar_track_smooth_query2(self.handle, _dptr(x), C.byref(sp.c), Q, _dptr(qt) if Q else None, _dptr(pose),
-                                             _dptr(cov) if covariance else None, seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
-        report = {k: getattr(rep, k) for k, _ in CSmoothQueryReport._fields_ if k != "struct_size"}
-        return pose[:Q], cov[:Q] if covariance else None, seg[:Q], report
+        return self._smooth_query("aar_track_smooth_query2", x_full, query_time, covariance,
+                                  (sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0))
 
     def track_smooth_query2_step(self, x_full, sigma_rot, sigma_trans, query_time, frame_time=None, model="cv", sigma_rot0=0.0, sigma_trans0=0.0):
         """aar_track_smooth_query2_step (constant velocity, for checking): (start_pose [Q, 6], step [Q, 6]), the two summands of

@@ -2556,82 +2556,146 @@ bool smooth_params_read(const aar_smooth_params *sp, aar_smooth_params *out) {
     return true;
 }
 
-struct SmoothCall {
-    double *base = nullptr;
-    SmoothWork w;
-    ~SmoothCall() { if (base) (void)hipFree(base); }
+// device memory that one call owns: n_dbl doubles and n_int int32 behind them, zeroed on the problem's stream
+struct DevMem {
+    double *p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    int alloc(aar_problem *pb, size_t n_dbl, size_t n_int = 0) {
+        const size_t bytes = n_dbl * sizeof(double) + n_int * sizeof(int32_t);
+        HIP_TRY(hipMalloc((void **)&p, bytes));
+        HIP_TRY(hipMemsetAsync(p, 0, bytes, pb->stream));
+        return AAR_OK;
+    }
 };
 
-// lambda of the pairs from the sigmas and the frame times, onto the device (F > 1)
-int smooth_upload_lambda(aar_problem *pb, const aar_smooth_params &sp, const SmoothCall &c) {
-    const int F = pb->P.F;
-    std::vector<double> lam(2 * (size_t)(F - 1));
-    for (int f = 0; f + 1 < F; f++) {
-        const double dt = sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0;
-        lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt);
-        lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt);
-    }
-    return copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double));
-}
+// the diagonal, lag-one and lag-two blocks of H^-1 ([F][36] each, on the device; l2 under constant velocity only) and what launching them took
+struct SmoothSel {
+    double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
+    int launches = 0;
+};
 
-// workspace, lambda and the expected motions on the device; the frame poses of z[cur] (uploaded by the caller) into w.z[0]
-int smooth_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCall &c) {
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    const size_t n = smooth_work_doubles(F);
-    HIP_TRY(hipMalloc((void **)&c.base, n * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(c.base, 0, n * sizeof(double), pb->stream));
-    smooth_work_carve(c.w, c.base, F);
-    int rc = AAR_OK;
-    if (F > 1) {
-        if ((rc = smooth_upload_lambda(pb, sp, c))) return rc;
-        if (sp.rel_motion) {
-            if ((rc = copy_h2d(pb, c.w.rel_buf, sp.rel_motion, 6 * (size_t)(F - 1) * sizeof(double)))) return rc;
-            c.w.rel = c.w.rel_buf;
+// One smoother call on the host: the caller's parameters, the motion model and that model's work area.  Every entry
+// drives either model through it; the kernels of the two models stay apart behind the two-way branches below.
+struct SmoothRun {
+    aar_problem *pb = nullptr;
+    aar_smooth_params sp;
+    bool cv = false;     // AAR_SMOOTH_MODEL_CONSTANT_VELOCITY
+    SmoothWork rw;       // carved by begin() out of mem: this one under the random walk ...
+    SmoothCvWork cw;     // ... this one under constant velocity
+    DevMem mem;
+
+    double *z(int cur) const { return cv ? cw.z[cur] : rw.z[cur]; }
+    const double *Ef(int cur) const { return cv ? cw.Ef[cur] : rw.Ef[cur]; }
+    const double *Pe(int cur) const { return cv ? cw.Pe[cur] : rw.Pe[cur]; }
+    const double *res() const { return cv ? cw.res : rw.res; }
+    const int32_t *flag() const { return cv ? cw.flag : rw.flag; }
+    const char *elimination() const { return cv ? "block-pentadiagonal" : "block-tridiagonal"; }
+
+    // H, b and costs at z[cur] (with_j), or the trial point z[1 - cur] = z[cur] + delta with its costs: two launches
+    void eval(int cur, bool with_j) const {
+        if (cv) launch_smooth_cv_eval(pb->P, pb->cur, cw, cur, with_j, pb->stream);
+        else launch_smooth_eval(pb->P, pb->cur, rw, cur, with_j, pb->stream);
+    }
+    // the damped solve; returns its launches
+    int solve(double mu) const { return cv ? launch_smooth_cv_solve(cw, pb->P.F, mu, pb->stream) : launch_smooth_solve(rw, pb->P.F, mu, pb->stream); }
+
+    // lambda from the sigmas and the frame times, onto the device (F > 1).  Random walk: [F-1][2], one entry per pair.  Constant velocity:
+    // [F][2], entry 0 pair 0 (sigma_rot0 / sigma_trans0), entry f term f, entry F-1 zero
+    int upload_lambda(const aar_smooth_params &s) const {
+        const int F = pb->P.F;
+        std::vector<double> lam(2 * (size_t)(cv ? F : F - 1), 0.0);
+        for (int f = 0; f + 1 < F; f++) {
+            const double dt = s.frame_time ? s.frame_time[f + 1] - s.frame_time[f] : 1.0;
+            const double sr = cv && f == 0 ? s.sigma_rot0 : s.sigma_rot, st = cv && f == 0 ? s.sigma_trans0 : s.sigma_trans;
+            lam[2 * (size_t)f] = 1.0 / (sr * sr * dt);
+            lam[2 * (size_t)f + 1] = 1.0 / (st * st * dt);
         }
+        return copy_h2d(pb, cv ? cw.lam : rw.lam, lam.data(), lam.size() * sizeof(double));
     }
-    if (F) HIP_TRY(hipMemcpyAsync(c.w.z[0], P.z[pb->cur] + 6 * (size_t)P.A, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
-    return AAR_OK;
-}
 
-// the same for the constant-velocity prior: lambda of pair 0 (from sigma_rot0 / sigma_trans0) and of the terms 1 .. F-2, and their ratios r_f
-struct SmoothCvCall {
-    double *base = nullptr;
-    SmoothCvWork w;
-    ~SmoothCvCall() { if (base) (void)hipFree(base); }
+    // What every entry starts its device work with: x_full into the problem's pose vector and, with work, the rows of the fixed cameras and
+    // markers, the zeroed work area, lambda with the ratios r_f or the expected motions, and the frame poses in z[0].  Without work (the
+    // random-walk query that returns no covariance) the poses stay in the problem's vector and rw stays empty.
+    int begin(const double *x_full, bool work = true) {
+        HIP_TRY(hipSetDevice(pb->device));
+        DeviceProblem &P = pb->P;
+        const int F = P.F;
+        pb->lm_ready = false;
+        pb->blocks_valid = false;
+        int rc = upload_z(pb, x_full, pb->cur);
+        if (rc || !work) return rc;
+        launch_unpack(P, pb->cur, pb->stream);
+        if ((rc = mem.alloc(pb, cv ? smooth_cv_work_doubles(F) : smooth_work_doubles(F)))) return rc;
+        if (cv) smooth_cv_work_carve(cw, mem.p, F);
+        else smooth_work_carve(rw, mem.p, F);
+        if (F > 1) {
+            if ((rc = upload_lambda(sp))) return rc;
+            if (cv) {
+                std::vector<double> ratio((size_t)F, 0.0);
+                auto dt = [&](int f) { return sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0; };
+                for (int f = 1; f + 1 < F; f++) ratio[f] = dt(f) / dt(f - 1);
+                if ((rc = copy_h2d(pb, cw.ratio, ratio.data(), ratio.size() * sizeof(double)))) return rc;
+            } else if (sp.rel_motion) {
+                if ((rc = copy_h2d(pb, rw.rel_buf, sp.rel_motion, 6 * (size_t)(F - 1) * sizeof(double)))) return rc;
+                rw.rel = rw.rel_buf;
+            }
+        }
+        if (F) HIP_TRY(hipMemcpyAsync(z(0), P.z[pb->cur] + 6 * (size_t)P.A, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+        return AAR_OK;
+    }
+
+    // H at z[cur] (mu = 0) with its costs into res(), the solve's elimination, then the selected inverse on area: selinv_doubles() zeroed
+    // doubles of the caller's (F > 0).  Launches only.
+    size_t selinv_doubles() const { return cv ? smooth_cv_selinv_doubles(pb->P.F) : 72 * (size_t)pb->P.F; }
+    SmoothSel selinv(int cur, double *area) const {
+        const int F = pb->P.F;
+        SmoothSel s;
+        eval(cur, /*with_j=*/true);
+        s.launches = 2 + solve(0.0);
+        if (cv) {
+            s.launches += launch_smooth_cv_selinv(cw, F, area, &s.fc, &s.lc, &s.l2, pb->stream);
+        } else {
+            s.fc = area; s.lc = area + 36 * (size_t)F;
+            s.launches += launch_smooth_selinv(rw, F, s.fc, s.lc, pb->stream);
+        }
+        return s;
+    }
+
+    // after selinv: the record (res [8], or NULL to leave it) and the elimination's pivot flag read back, and the refusal of a raised flag
+    int read_pivot(const char *who, const char *kernels, double *res8) const {
+        int rc = AAR_OK;
+        int32_t f = 0;
+        if (res8 && (rc = copy_d2h(pb, res8, res(), 8 * sizeof(double)))) return rc;
+        if ((rc = copy_d2h(pb, &f, flag(), sizeof f))) return rc;
+        if ((rc = check_async(kernels))) return rc;
+        return f ? pivot_refusal(who) : AAR_OK;
+    }
+    int pivot_refusal(const char *who) const {
+        return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the %s elimination (the frames' detections and the prior do not determine "
+                                          "every pose)", who, elimination());
+    }
 };
 
-// lambda [F][2] from the sigmas and the frame times, onto the device (F > 1): entry 0 pair 0, entry f term f, entry F-1 zero
-int smooth_cv_upload_lambda(aar_problem *pb, const aar_smooth_params &sp, const SmoothCvCall &c) {
-    const int F = pb->P.F;
-    std::vector<double> lam(2 * (size_t)F, 0.0);
-    auto dt = [&](int f) { return sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0; };
-    lam[0] = 1.0 / (sp.sigma_rot0 * sp.sigma_rot0 * dt(0));
-    lam[1] = 1.0 / (sp.sigma_trans0 * sp.sigma_trans0 * dt(0));
-    for (int f = 1; f + 1 < F; f++) {
-        lam[2 * (size_t)f] = 1.0 / (sp.sigma_rot * sp.sigma_rot * dt(f));
-        lam[2 * (size_t)f + 1] = 1.0 / (sp.sigma_trans * sp.sigma_trans * dt(f));
-    }
-    return copy_h2d(pb, c.w.lam, lam.data(), lam.size() * sizeof(double));
+// the head of the covariance, query and relative reports, and their tail: sigma2 over the degrees of freedom, the seconds since t0, and the
+// copy bounded by the caller's struct_size
+extern "C++" template <class R>
+void smooth_report_begin(const aar_problem *pb, R &r) {
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * (int64_t)pb->P.N + 6 * (int64_t)std::max(pb->P.F - 1, 0);
+    r.num_vars = 6 * (int64_t)pb->P.F;
 }
-
-int smooth_cv_prepare(aar_problem *pb, const aar_smooth_params &sp, SmoothCvCall &c) {
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    const size_t n = smooth_cv_work_doubles(F);
-    HIP_TRY(hipMalloc((void **)&c.base, n * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(c.base, 0, n * sizeof(double), pb->stream));
-    smooth_cv_work_carve(c.w, c.base, F);
-    int rc = AAR_OK;
-    if (F > 1) {
-        std::vector<double> ratio((size_t)F, 0.0);
-        auto dt = [&](int f) { return sp.frame_time ? sp.frame_time[f + 1] - sp.frame_time[f] : 1.0; };
-        for (int f = 1; f + 1 < F; f++) ratio[f] = dt(f) / dt(f - 1);
-        if ((rc = smooth_cv_upload_lambda(pb, sp, c))) return rc;
-        if ((rc = copy_h2d(pb, c.w.ratio, ratio.data(), ratio.size() * sizeof(double)))) return rc;
-    }
-    if (F) HIP_TRY(hipMemcpyAsync(c.w.z[0], P.z[pb->cur] + 6 * (size_t)P.A, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
-    return AAR_OK;
+extern "C++" template <class R>
+void smooth_report_out(R &r, R *report, std::chrono::steady_clock::time_point t0) {
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!report) return;
+    r.struct_size = report->struct_size;
+    memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+}
+extern "C++" template <class R>
+void smooth_report_end(R &r, R *report, std::chrono::steady_clock::time_point t0) {
+    const int64_t dof = r.num_residuals - r.num_vars;
+    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
+    smooth_report_out(r, report, t0);
 }
 
 // the entries whose selected inverse is the tridiagonal one
@@ -2645,40 +2709,27 @@ int smooth_rw_only(const aar_smooth_params &sp, const char *who) {
     return AAR_OK;
 }
 
-int smooth_entry(aar_problem *pb, const aar_smooth_params *sp_in, aar_smooth_params *sp, const char *who) {
+// the checks every entry makes on its parameters; c: the record of the call, no device work yet
+int smooth_entry(aar_problem *pb, const aar_smooth_params *sp_in, SmoothRun &c, const char *who) {
     if (!sp_in) return set_error(AAR_ERR_INVALID, "%s: null aar_smooth_params", who);
     int rc = aar_smooth_params_validate(pb->L.F, sp_in);
     if (rc) return rc;
-    (void)smooth_params_read(sp_in, sp);
+    (void)smooth_params_read(sp_in, &c.sp);
+    c.pb = pb;
+    c.cv = c.sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY;
     if (pb->comm) return set_error(AAR_ERR_UNSUPPORTED, "%s: the motion prior couples frames across shard boundaries; smoothed tracking is single-GPU only", who);
     return AAR_OK;
 }
 
-// what one run of the joint LM leaves on the host; cur: in = the buffer of c.w.z the run starts from, out = the one that holds its result
+// what one run of the joint LM leaves on the host; cur: in = the buffer of c.z the run starts from, out = the one that holds its result
 struct SmoothLm {
     int cur = 0, iters = 0, rejected = 0, mustExit = 0;
     double initial = 0.0, currErr = 0.0, currData = 0.0, currPrior = 0.0, mu = -1.0;
 };
 
-// the launches of the two motion models behind one loop: H, b and costs (or the trial point's costs) with their record, and the damped solve
-struct SmoothRwOps {
-    aar_problem *pb;
-    const SmoothWork &w;
-    void eval(int cur, bool with_j) const { launch_smooth_eval(pb->P, pb->cur, w, cur, with_j, pb->stream); }
-    int solve(double mu) const { return launch_smooth_solve(w, pb->P.F, mu, pb->stream); }
-    const double *res() const { return w.res; }
-};
-struct SmoothCvOps {
-    aar_problem *pb;
-    const SmoothCvWork &w;
-    void eval(int cur, bool with_j) const { launch_smooth_cv_eval(pb->P, pb->cur, w, cur, with_j, pb->stream); }
-    int solve(double mu) const { return launch_smooth_cv_solve(w, pb->P.F, mu, pb->stream); }
-    const double *res() const { return w.res; }
-};
-
-// aar_track_smooth's loop on a prepared workspace, from its z[s.cur]
-extern "C++" template <class Ops>
-int smooth_lm_loop(aar_problem *pb, const Ops &o, const aar_lm_params &p, SmoothLm &s) {
+// aar_track_smooth's loop on a prepared record, from its z[s.cur]
+int smooth_lm(const SmoothRun &o, const aar_lm_params &p, SmoothLm &s) {
+    aar_problem *pb = o.pb;
     DeviceProblem &P = pb->P;
     const int F = P.F;
     const double rows = 8.0 * (double)P.N + 6.0 * (double)(F - 1);
@@ -2734,32 +2785,6 @@ int smooth_lm_loop(aar_problem *pb, const Ops &o, const aar_lm_params &p, Smooth
     s.cur = cur; s.iters = iters; s.rejected = rejected; s.mustExit = mustExit;
     s.initial = initial; s.currErr = currErr; s.currData = currData; s.currPrior = currPrior; s.mu = mu;
     return AAR_OK;
-}
-
-int smooth_lm_run(aar_problem *pb, const SmoothCall &c, const aar_lm_params &p, SmoothLm &s) {
-    return smooth_lm_loop(pb, SmoothRwOps{pb, c.w}, p, s);
-}
-
-// H at c.w.z[cur] (mu = 0) with its costs into c.w.res, the solve's elimination, the selected inverse into S, R [F][36] each (F > 0).
-// Launches only; returns their number.
-int smooth_selinv_launch(aar_problem *pb, const SmoothCall &c, int cur, double *S, double *R) {
-    const int F = pb->P.F;
-    launch_smooth_eval(pb->P, pb->cur, c.w, cur, /*with_j=*/true, pb->stream);
-    int launches = 2;
-    launches += launch_smooth_solve(c.w, F, 0.0, pb->stream);
-    launches += launch_smooth_selinv(c.w, F, S, R, pb->stream);
-    return launches;
-}
-
-// The same under constant velocity: H at c.w.z[cur] (mu = 0) with its costs into c.w.res, the supernode reduction, the selected inverse on
-// area (smooth_cv_selinv_doubles(F) doubles) with fc, lc, l2 [F][36] pointing into it (F > 0).  Launches only; returns their number.
-int smooth_cv_selinv_launch(aar_problem *pb, const SmoothCvCall &c, int cur, double *area, double **fc, double **lc, double **l2) {
-    const int F = pb->P.F;
-    launch_smooth_cv_eval(pb->P, pb->cur, c.w, cur, /*with_j=*/true, pb->stream);
-    int launches = 2;
-    launches += launch_smooth_cv_solve(c.w, F, 0.0, pb->stream);
-    launches += launch_smooth_cv_selinv(c.w, F, area, fc, lc, l2, pb->stream);
-    return launches;
 }
 
 // the frame poses of the problem's pose vector into x_full
@@ -2820,258 +2845,147 @@ int aar_smooth_params_validate(int32_t num_frames, const aar_smooth_params *sp_i
 
 namespace {
 
-// aar_track_smooth_system2 under the constant-velocity prior
-int smooth_cv_system(aar_problem *pb, const double *x_full, const aar_smooth_params &sp, double mu, double *diag, double *off, double *off2,
-                     double *rhs, double *delta, double cost[2]) {
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    int rc = AAR_OK;
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCvCall c;
-    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
+// aar_track_smooth_system and aar_track_smooth_system2 after their checks; off2 is written under constant velocity only
+int smooth_system(SmoothRun &c, const char *who, const double *x_full, double mu, double *diag, double *off, double *off2, double *rhs,
+                  double *delta, double cost[2]) {
+    aar_problem *pb = c.pb;
+    const int F = pb->P.F;
+    int rc = c.begin(x_full);
+    if (rc) return rc;
     if (cost) cost[0] = cost[1] = 0.0;
     if (F == 0) { HIP_TRY(hipStreamSynchronize(pb->stream)); return AAR_OK; }
-    launch_smooth_cv_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
+    c.eval(0, /*with_j=*/true);
     double res[8];
-    if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
+    if ((rc = copy_d2h(pb, res, c.res(), sizeof res))) return rc;
     if (cost) { cost[0] = res[0]; cost[1] = res[1]; }
-    if (diag && (rc = copy_d2h(pb, diag, c.w.Dg, 36 * (size_t)F * sizeof(double)))) return rc;
-    if (off && F > 1 && (rc = copy_d2h(pb, off, c.w.O1, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
-    if (off2 && F > 2 && (rc = copy_d2h(pb, off2, c.w.O2, 36 * (size_t)(F - 2) * sizeof(double)))) return rc;
-    if (rhs && (rc = copy_d2h(pb, rhs, c.w.rhs, 6 * (size_t)F * sizeof(double)))) return rc;
+    if (diag && (rc = copy_d2h(pb, diag, c.cv ? c.cw.Dg : c.rw.Dg, 36 * (size_t)F * sizeof(double)))) return rc;
+    if (off && F > 1 && (rc = copy_d2h(pb, off, c.cv ? c.cw.O1 : c.rw.Of, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+    if (c.cv && off2 && F > 2 && (rc = copy_d2h(pb, off2, c.cw.O2, 36 * (size_t)(F - 2) * sizeof(double)))) return rc;
+    if (rhs && (rc = copy_d2h(pb, rhs, c.cv ? c.cw.rhs : c.rw.rhs, 6 * (size_t)F * sizeof(double)))) return rc;
     if (delta) {
-        pb->launches += launch_smooth_cv_solve(c.w, F, mu, pb->stream);
+        pb->launches += c.solve(mu);
         int32_t flag = 0;
-        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
-        if ((rc = copy_d2h(pb, delta, c.w.delta, 6 * (size_t)F * sizeof(double)))) return rc;
-        if (flag) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_system2: non-positive pivot in the block-pentadiagonal solve (mu = %g)", mu);
+        if ((rc = copy_d2h(pb, &flag, c.flag(), sizeof flag))) return rc;
+        if ((rc = copy_d2h(pb, delta, c.cv ? c.cw.delta : c.rw.delta, 6 * (size_t)F * sizeof(double)))) return rc;
+        if (flag) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the %s solve (mu = %g)", who, c.elimination(), mu);
     }
     return check_async("smoothing kernels");
 }
 
-}  // namespace
-
-int aar_track_smooth_system2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double mu, double *diag, double *off, double *off2,
-                             double *rhs, double *delta, double cost[2]) {
-    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system2: null argument");
-    if (!(mu >= 0.0) || !std::isfinite(mu)) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system2: mu = %g must be finite and not negative", mu);
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_system2");
+// DESIGN.md sections 28 and 32: H at mu = 0 as smooth_system assembles it, the solve's elimination, then the downward pass of
+// smooth_cov_kernels.hip or smooth_cv_cov_kernels.hip over what the elimination kept; lag2_cov under constant velocity only
+int smooth_covariance(SmoothRun &c, const char *who, const double *x_full, double *frame_cov, double *lag_cov, double *lag2_cov,
+                      aar_smooth_covariance_report *report) {
+    aar_problem *pb = c.pb;
+    const int F = pb->P.F;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = c.begin(x_full);
     if (rc) return rc;
-    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return smooth_cv_system(pb, x_full, sp, mu, diag, off, off2, rhs, delta, cost);
-    if ((rc = aar_track_smooth_system(pb, x_full, sp_in, mu, diag, off, rhs, delta, cost))) return rc;
-    if (off2 && pb->P.F > 2) std::fill(off2, off2 + 36 * (size_t)(pb->P.F - 2), 0.0);
+    aar_smooth_covariance_report r;
+    smooth_report_begin(pb, r);
+    if (F > 0) {
+        // the selected inverse's area: an allocation of its own, the carve of the solve's work area keeps its layout
+        DevMem area;
+        if ((rc = area.alloc(pb, c.selinv_doubles()))) return rc;
+        const SmoothSel sel = c.selinv(0, area.p);
+        r.launches = sel.launches;
+        pb->launches += r.launches;
+        double res[8];
+        if ((rc = c.read_pivot(who, "smoothing covariance kernels", res))) return rc;
+        r.data_cost = res[0]; r.prior_cost = res[1];
+        if (frame_cov && (rc = copy_d2h(pb, frame_cov, sel.fc, 36 * (size_t)F * sizeof(double)))) return rc;
+        if (lag_cov && F > 1 && (rc = copy_d2h(pb, lag_cov, sel.lc, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
+        if (lag2_cov && F > 2 && (rc = copy_d2h(pb, lag2_cov, sel.l2, 36 * (size_t)(F - 2) * sizeof(double)))) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+    }
+    smooth_report_end(r, report, t0);
     return AAR_OK;
 }
+
+}  // namespace
 
 int aar_track_smooth_system(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double mu, double *diag, double *off, double *rhs,
                             double *delta, double cost[2]) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system: null argument");
     if (!(mu >= 0.0) || !std::isfinite(mu)) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system: mu = %g must be finite and not negative", mu);
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_system");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_system");
     if (rc) return rc;
-    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+    if (c.cv)
         return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_system: model = AAR_SMOOTH_MODEL_CONSTANT_VELOCITY has a second off-diagonal; "
                                               "call aar_track_smooth_system2");
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCall c;
-    if ((rc = smooth_prepare(pb, sp, c))) return rc;
-    if (cost) cost[0] = cost[1] = 0.0;
-    if (F == 0) { HIP_TRY(hipStreamSynchronize(pb->stream)); return AAR_OK; }
-    launch_smooth_eval(P, pb->cur, c.w, 0, /*with_j=*/true, pb->stream);
-    double res[8];
-    if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
-    if (cost) { cost[0] = res[0]; cost[1] = res[1]; }
-    if (diag && (rc = copy_d2h(pb, diag, c.w.Dg, 36 * (size_t)F * sizeof(double)))) return rc;
-    if (off && F > 1 && (rc = copy_d2h(pb, off, c.w.Of, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
-    if (rhs && (rc = copy_d2h(pb, rhs, c.w.rhs, 6 * (size_t)F * sizeof(double)))) return rc;
-    if (delta) {
-        pb->launches += launch_smooth_solve(c.w, F, mu, pb->stream);
-        int32_t flag = 0;
-        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
-        if ((rc = copy_d2h(pb, delta, c.w.delta, 6 * (size_t)F * sizeof(double)))) return rc;
-        if (flag) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_system: non-positive pivot in the block-tridiagonal solve (mu = %g)", mu);
-    }
-    return check_async("smoothing kernels");
+    return smooth_system(c, "aar_track_smooth_system", x_full, mu, diag, off, nullptr, rhs, delta, cost);
 }
 
-// H at mu = 0 as aar_track_smooth_system assembles it, the solve's elimination, then the downward pass of
-// smooth_cov_kernels.hip over what the elimination kept
+// under the random walk aar_track_smooth_system itself (its name in the messages), and off2 zero
+int aar_track_smooth_system2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double mu, double *diag, double *off, double *off2,
+                             double *rhs, double *delta, double cost[2]) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system2: null argument");
+    if (!(mu >= 0.0) || !std::isfinite(mu)) return set_error(AAR_ERR_INVALID, "aar_track_smooth_system2: mu = %g must be finite and not negative", mu);
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_system2");
+    if (rc) return rc;
+    if ((rc = smooth_system(c, c.cv ? "aar_track_smooth_system2" : "aar_track_smooth_system", x_full, mu, diag, off, off2, rhs, delta, cost))) return rc;
+    if (!c.cv && off2 && pb->P.F > 2) std::fill(off2, off2 + 36 * (size_t)(pb->P.F - 2), 0.0);
+    return AAR_OK;
+}
+
 int aar_track_smooth_covariance(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *frame_cov, double *lag_cov,
                                 aar_smooth_covariance_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_covariance: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_covariance");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_covariance");
     if (rc) return rc;
-    if ((rc = smooth_rw_only(sp, "aar_track_smooth_covariance"))) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCall c;
-    if ((rc = smooth_prepare(pb, sp, c))) return rc;
-    aar_smooth_covariance_report r;
-    memset(&r, 0, sizeof r);
-    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
-    r.num_vars = 6 * (int64_t)F;
-    if (F > 0) {
-        // S and R of the downward pass: an allocation of their own, the carve of the solve's work area keeps its layout
-        SmoothCall sr;
-        HIP_TRY(hipMalloc((void **)&sr.base, 72 * (size_t)F * sizeof(double)));
-        HIP_TRY(hipMemsetAsync(sr.base, 0, 72 * (size_t)F * sizeof(double), pb->stream));
-        double *S = sr.base, *R = sr.base + 36 * (size_t)F;
-        r.launches = smooth_selinv_launch(pb, c, 0, S, R);
-        pb->launches += r.launches;
-        double res[8];
-        int32_t flag = 0;
-        if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
-        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
-        if ((rc = check_async("smoothing covariance kernels"))) return rc;
-        if (flag)
-            return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_covariance: non-positive pivot in the block-tridiagonal elimination (the frames' "
-                                              "detections and the prior do not determine every pose)");
-        r.data_cost = res[0]; r.prior_cost = res[1];
-        if (frame_cov && (rc = copy_d2h(pb, frame_cov, S, 36 * (size_t)F * sizeof(double)))) return rc;
-        if (lag_cov && F > 1 && (rc = copy_d2h(pb, lag_cov, R, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
-    } else {
-        HIP_TRY(hipStreamSynchronize(pb->stream));
-    }
-    const int64_t dof = r.num_residuals - r.num_vars;
-    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
-    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (report) {
-        r.struct_size = report->struct_size;
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
-    return AAR_OK;
+    if ((rc = smooth_rw_only(c.sp, "aar_track_smooth_covariance"))) return rc;
+    return smooth_covariance(c, "aar_track_smooth_covariance", x_full, frame_cov, lag_cov, nullptr, report);
 }
 
-// under constant velocity H at mu = 0 as aar_track_smooth_system2 assembles it, the supernode reduction of the solve, then
-// the downward pass of smooth_cv_cov_kernels.hip; under the random walk aar_track_smooth_covariance itself
+// under the random walk aar_track_smooth_covariance itself (its name in the messages)
 int aar_track_smooth_covariance2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *frame_cov, double *lag_cov,
                                  double *lag2_cov, aar_smooth_covariance_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_covariance2: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_covariance2");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_covariance2");
     if (rc) return rc;
-    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
-        if (lag2_cov)
-            return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_covariance2: lag2_cov under AAR_SMOOTH_MODEL_RANDOM_WALK is not supported (the "
-                                                  "selected inverse of the block-tridiagonal system does not contain the lag-two blocks)");
-        return aar_track_smooth_covariance(pb, x_full, sp_in, frame_cov, lag_cov, report);
-    }
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCvCall c;
-    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
-    aar_smooth_covariance_report r;
-    memset(&r, 0, sizeof r);
-    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
-    r.num_vars = 6 * (int64_t)F;
-    if (F > 0) {
-        // S, the two R and the unpacked blocks: an allocation of their own, the carve of the solve's work area keeps its layout
-        SmoothCvCall sel;
-        const size_t n = smooth_cv_selinv_doubles(F);
-        HIP_TRY(hipMalloc((void **)&sel.base, n * sizeof(double)));
-        HIP_TRY(hipMemsetAsync(sel.base, 0, n * sizeof(double), pb->stream));
-        double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
-        r.launches = smooth_cv_selinv_launch(pb, c, 0, sel.base, &fc, &lc, &l2);
-        pb->launches += r.launches;
-        double res[8];
-        int32_t flag = 0;
-        if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
-        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
-        if ((rc = check_async("smoothing covariance kernels"))) return rc;
-        if (flag)
-            return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_covariance2: non-positive pivot in the block-pentadiagonal elimination (the frames' "
-                                              "detections and the prior do not determine every pose)");
-        r.data_cost = res[0]; r.prior_cost = res[1];
-        if (frame_cov && (rc = copy_d2h(pb, frame_cov, fc, 36 * (size_t)F * sizeof(double)))) return rc;
-        if (lag_cov && F > 1 && (rc = copy_d2h(pb, lag_cov, lc, 36 * (size_t)(F - 1) * sizeof(double)))) return rc;
-        if (lag2_cov && F > 2 && (rc = copy_d2h(pb, lag2_cov, l2, 36 * (size_t)(F - 2) * sizeof(double)))) return rc;
-    } else {
-        HIP_TRY(hipStreamSynchronize(pb->stream));
-    }
-    const int64_t dof = r.num_residuals - r.num_vars;
-    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
-    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (report) {
-        r.struct_size = report->struct_size;
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
-    return AAR_OK;
+    if (!c.cv && lag2_cov)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_covariance2: lag2_cov under AAR_SMOOTH_MODEL_RANDOM_WALK is not supported (the "
+                                              "selected inverse of the block-tridiagonal system does not contain the lag-two blocks)");
+    return smooth_covariance(c, c.cv ? "aar_track_smooth_covariance2" : "aar_track_smooth_covariance", x_full, frame_cov, lag_cov, lag2_cov, report);
 }
 
 int aar_track_smooth(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, double *frame_err, double *pair_err,
                      aar_smooth_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth");
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
     DeviceProblem &P = pb->P;
     aar_lm_params p;
     if (prm) p = *prm; else aar_lm_default_params(&p);
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
     const int F = P.F;
     const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);  // rows of the fixed cameras / markers (and K with intrinsics)
-    SmoothCall c;
-    SmoothCvCall cv;
+    if ((rc = c.begin(x_full))) return rc;
     SmoothLm s;
-    const double *zr = nullptr, *Ef = nullptr, *Pe = nullptr;   // the result's poses and costs on the device
-    if (sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
-        if ((rc = smooth_cv_prepare(pb, sp, cv))) return rc;
-        if ((rc = smooth_lm_loop(pb, SmoothCvOps{pb, cv.w}, p, s))) return rc;
-        zr = cv.w.z[s.cur]; Ef = cv.w.Ef[s.cur]; Pe = cv.w.Pe[s.cur];
-    } else {
-        if ((rc = smooth_prepare(pb, sp, c))) return rc;
-        if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
-        zr = c.w.z[s.cur]; Ef = c.w.Ef[s.cur]; Pe = c.w.Pe[s.cur];
-    }
-    if (F) HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, zr, 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
-    if (frame_err && F && (rc = copy_d2h(pb, frame_err, Ef, (size_t)F * sizeof(double)))) return rc;
-    if (pair_err && F > 1 && (rc = copy_d2h(pb, pair_err, Pe, (size_t)(F - 1) * sizeof(double)))) return rc;
+    if ((rc = smooth_lm(c, p, s))) return rc;
+    if (F) HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.z(s.cur), 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    if (frame_err && F && (rc = copy_d2h(pb, frame_err, c.Ef(s.cur), (size_t)F * sizeof(double)))) return rc;
+    if (pair_err && F > 1 && (rc = copy_d2h(pb, pair_err, c.Pe(s.cur), (size_t)(F - 1) * sizeof(double)))) return rc;
     if ((rc = check_async("smoothing kernels"))) return rc;
     if ((rc = smooth_download(pb, x_full))) return rc;
     if (report) {
         aar_smooth_report r;
         memset(&r, 0, sizeof r);
-        r.struct_size = report->struct_size;
         r.iterations = s.iters; r.stop_code = s.mustExit; r.rejected_tries = s.rejected;
         r.initial_cost = s.initial; r.final_cost = s.currErr; r.final_data_cost = s.currData; r.final_prior_cost = s.currPrior;
         r.final_mu = s.mu;
-        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+        smooth_report_out(r, report, t0);
     }
     return AAR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fitting the smoother's noise levels (smooth_fit_kernels.hip)
+// Fitting the smoother's noise levels (DESIGN.md sections 29 and 33, smooth_fit_kernels.hip and smooth_cv_fit_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -3084,42 +2998,145 @@ bool smooth_fit_params_read(const aar_smooth_fit_params *in, aar_smooth_fit_para
     return true;
 }
 
-// S, R of the downward pass, the pairs' terms and the record the host reads: one allocation
-struct SmoothFitBuf {
-    SmoothCall mem;
-    double *S = nullptr, *R = nullptr, *terms = nullptr, *rec = nullptr;
-};
-
-int smooth_fit_alloc(aar_problem *pb, SmoothFitBuf &b) {
-    const size_t F = (size_t)pb->P.F, n = 72 * F + 4 * (F - 1) + 8;
-    HIP_TRY(hipMalloc((void **)&b.mem.base, n * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(b.mem.base, 0, n * sizeof(double), pb->stream));
-    b.S = b.mem.base; b.R = b.S + 36 * F; b.terms = b.R + 36 * F; b.rec = b.terms + 4 * (F - 1);
-    return AAR_OK;
-}
-
-// the E-step at c.w.z[cur] with the lambda on the device (built with sigma_rot): launches, then the one read-back of rec [8] =
-// A_r, U_r, A_t, U_t, data cost, prior cost, pivot flag, 0
-int smooth_fit_estep(aar_problem *pb, const SmoothCall &c, int cur, double sigma_rot, const SmoothFitBuf &b, double rec[8], const char *who) {
-    const int F = pb->P.F;
-    int launches = smooth_selinv_launch(pb, c, cur, b.S, b.R);
-    launches += launch_smooth_fit_terms(c.w, cur, F, sigma_rot, b.S, b.R, b.terms, b.rec, pb->stream);
-    pb->launches += launches;
-    int rc = copy_d2h(pb, rec, b.rec, 8 * sizeof(double));
-    if (rc) return rc;
-    if (rec[6] != 0.0)
-        return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the block-tridiagonal elimination (the frames' detections and the prior do "
-                                          "not determine every pose)", who);
-    return AAR_OK;
-}
-
-// what both entries refuse, after smooth_entry
-int smooth_fit_entry(aar_problem *pb, const char *who) {
+// what the fit entries refuse, after smooth_entry and before anything is sized by F - 1
+int smooth_fit_entry(const SmoothRun &c, const char *who) {
+    const aar_problem *pb = c.pb;
     if (pb->with_huber)
         return set_error(AAR_ERR_UNSUPPORTED, "%s: the problem was created with_huber; the Huber weights break the Gaussian data model the fit "
                                               "rests on", who);
-    if (pb->L.F < 2) return set_error(AAR_ERR_INVALID, "%s: num_frames = %d, the fit needs at least one pair of frames", who, (int)pb->L.F);
+    if (!c.cv && pb->L.F < 2) return set_error(AAR_ERR_INVALID, "%s: num_frames = %d, the fit needs at least one pair of frames", who, (int)pb->L.F);
+    if (c.cv && pb->L.F < 3)
+        return set_error(AAR_ERR_INVALID, "%s: num_frames = %d, the fit under AAR_SMOOTH_MODEL_CONSTANT_VELOCITY needs at least one "
+                                          "second-difference term (three frames)", who, (int)pb->L.F);
     if (pb->P.N < 1) return set_error(AAR_ERR_INVALID, "%s: the problem has no detections", who);
+    return AAR_OK;
+}
+
+// the selected inverse's area, the terms [F-1][4] and the record the host reads: one allocation
+struct SmoothFitBuf {
+    DevMem mem;
+    double *terms = nullptr, *rec = nullptr;
+    int alloc(const SmoothRun &c) {
+        const size_t F = (size_t)c.pb->P.F, na = c.selinv_doubles();
+        int rc = mem.alloc(c.pb, na + 4 * (F - 1) + 8);
+        terms = mem.p + na; rec = terms + 4 * (F - 1);
+        return rc;
+    }
+};
+
+// the E-step at c.z(cur) with the lambda on the device (built with eff's sigmas): launches, then the one read-back of rec [8] = A_r, U_r,
+// A_t, U_t (under constant velocity over the terms 1 .. F-2), data cost, prior cost, pivot flag, and u_0 of pair 0 (zero under the random walk)
+int smooth_fit_estep(const SmoothRun &c, int cur, const aar_smooth_params &eff, const SmoothFitBuf &b, double rec[8], const char *who) {
+    aar_problem *pb = c.pb;
+    const int F = pb->P.F;
+    const SmoothSel sel = c.selinv(cur, b.mem.p);
+    int launches = sel.launches;
+    if (c.cv)
+        launches += launch_smooth_cv_fit_terms(c.cw, cur, F, eff.sigma_rot, eff.sigma_rot0, eff.sigma_trans0, sel.fc, sel.lc, sel.l2, b.terms, b.rec,
+                                               pb->stream);
+    else launches += launch_smooth_fit_terms(c.rw, cur, F, eff.sigma_rot, sel.fc, sel.lc, b.terms, b.rec, pb->stream);
+    pb->launches += launches;
+    int rc = copy_d2h(pb, rec, b.rec, 8 * sizeof(double));
+    if (rc) return rc;
+    return rec[6] != 0.0 ? c.pivot_refusal(who) : AAR_OK;
+}
+
+// aar_track_smooth_fit_terms and aar_track_smooth_fit_terms2 after their model checks; six: sums holds u_0 and pair 0's cost as well
+int smooth_fit_terms(SmoothRun &c, const char *who, const double *x_full, double *pair_terms, double *sums, bool six) {
+    aar_problem *pb = c.pb;
+    int rc = smooth_fit_entry(c, who);
+    if (rc) return rc;
+    if ((rc = c.begin(x_full))) return rc;
+    SmoothFitBuf b;
+    if ((rc = b.alloc(c))) return rc;
+    double rec[8], pair0 = 0.0;
+    if ((rc = smooth_fit_estep(c, 0, c.sp, b, rec, who))) return rc;
+    if (c.cv && (rc = copy_d2h(pb, &pair0, c.Pe(0), sizeof pair0))) return rc;   // the evaluation's cost of pair 0
+    if (pair_terms && (rc = copy_d2h(pb, pair_terms, b.terms, 4 * (size_t)(pb->P.F - 1) * sizeof(double)))) return rc;
+    if ((rc = check_async("smoothing fit kernels"))) return rc;
+    if (sums) for (int i = 0; i < 4; i++) sums[i] = rec[i];
+    if (sums && six) { sums[4] = c.cv ? rec[7] : 0.0; sums[5] = pair0; }
+    return AAR_OK;
+}
+
+// aar_track_smooth_fit and aar_track_smooth_fit2 after their model checks: EM over q = sigma_px^2 and the physical variances s_r, s_t of the
+// pairs (random walk) or of the terms 1 .. F-2 (constant velocity, pair 0's sigmas physical and held); the smoother runs at sigma / sqrt(q)
+int smooth_fit(SmoothRun &c, const char *who, double *x_full, const aar_lm_params *prm, const aar_smooth_fit_params *fp_in, double *path,
+               aar_smooth_fit_report *report) {
+    aar_problem *pb = c.pb;
+    const aar_smooth_params &sp = c.sp;
+    aar_smooth_fit_params fp;
+    int rc = AAR_OK;
+    if (fp_in) {
+        if ((rc = aar_smooth_fit_params_validate(fp_in))) return rc;
+        (void)smooth_fit_params_read(fp_in, &fp);
+    } else {
+        aar_smooth_fit_default_params(&fp);
+    }
+    if ((rc = smooth_fit_entry(c, who))) return rc;
+    DeviceProblem &P = pb->P;
+    aar_lm_params p;
+    if (prm) p = *prm; else aar_lm_default_params(&p);
+    const int F = P.F;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t launches0 = pb->launches;
+    if ((rc = c.begin(x_full))) return rc;   // lambda at the start values, the ratios once
+    SmoothFitBuf b;
+    if ((rc = b.alloc(c))) return rc;
+    double q = 1.0, s_r = sp.sigma_rot * sp.sigma_rot, s_t = sp.sigma_trans * sp.sigma_trans;
+    aar_smooth_fit_report r;
+    memset(&r, 0, sizeof r);
+    std::vector<double> rows;   // the path, handed over only when the fit has succeeded
+    rows.insert(rows.end(), {1.0, sp.sigma_rot, sp.sigma_trans});
+    aar_smooth_params eff = sp;   // frame_time and rel_motion kept, the sigmas replaced
+    SmoothLm s;
+    const double terms_n = 3.0 * (double)(c.cv ? F - 2 : F - 1);
+    double rec[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u_d = 0.0;
+    r.stop_code = 2;
+    for (int it = 0; it < fp.max_iters; it++) {
+        if (it > 0 && (rc = c.upload_lambda(eff))) return rc;
+        if ((rc = smooth_lm(c, p, s))) return rc;
+        r.lm_steps += s.iters;
+        if ((rc = smooth_fit_estep(c, s.cur, eff, b, rec, who))) return rc;
+        const double er2 = eff.sigma_rot * eff.sigma_rot, et2 = eff.sigma_trans * eff.sigma_trans;
+        u_d = 6.0 * (double)F - rec[1] / er2 - rec[3] / et2;
+        if (c.cv) u_d -= rec[7];
+        const double n_r = fp.estimate_rot ? (rec[0] + q * rec[1]) / terms_n : s_r;
+        const double n_t = fp.estimate_trans ? (rec[2] + q * rec[3]) / terms_n : s_t;
+        const double n_q = fp.estimate_px ? (rec[4] + q * u_d) / (8.0 * (double)P.N) : q;
+        const double was[3] = {q, s_r, s_t}, now[3] = {n_q, n_r, n_t};
+        const char *names[3] = {"sigma_px", "sigma_rot", "sigma_trans"};
+        double change = 0.0;
+        for (int i = 0; i < 3; i++) {
+            if (!(now[i] > 0.0) || !std::isfinite(now[i]))
+                return set_error(AAR_ERR_NUMERIC, "%s: iteration %d: the M-step gives the variance %g for %s", who, it + 1, now[i], names[i]);
+            change = std::max(change, std::fabs(std::sqrt(now[i]) - std::sqrt(was[i])) / std::sqrt(was[i]));
+        }
+        q = n_q; s_r = n_r; s_t = n_t;
+        const double sq = std::sqrt(q);
+        eff.sigma_rot = std::sqrt(s_r / q);
+        eff.sigma_trans = std::sqrt(s_t / q);
+        if (c.cv) { eff.sigma_rot0 = sp.sigma_rot0 / sq; eff.sigma_trans0 = sp.sigma_trans0 / sq; }
+        r.iterations = it + 1;
+        r.last_rel_change = change;
+        rows.insert(rows.end(), {sq, std::sqrt(s_r), std::sqrt(s_t)});
+        if (change < fp.rel_tol) { r.stop_code = 1; break; }
+    }
+    // the track at the fitted values
+    if ((rc = c.upload_lambda(eff))) return rc;
+    if ((rc = smooth_lm(c, p, s))) return rc;
+    r.lm_steps += s.iters;
+    HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.z(s.cur), 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
+    if ((rc = check_async("smoothing fit kernels"))) return rc;
+    if ((rc = smooth_download(pb, x_full))) return rc;
+    if (path) std::copy(rows.begin(), rows.end(), path);
+    if (report) {
+        r.sigma_px = std::sqrt(q); r.sigma_rot = std::sqrt(s_r); r.sigma_trans = std::sqrt(s_t);
+        r.sigma_rot_eff = eff.sigma_rot; r.sigma_trans_eff = eff.sigma_trans;
+        r.launches = (int32_t)(pb->launches - launches0);
+        r.a_rot = rec[0]; r.u_rot = rec[1]; r.a_trans = rec[2]; r.u_trans = rec[3]; r.u_data = u_d; r.data_cost = rec[4];
+        smooth_report_out(r, report, t0);
+    }
     return AAR_OK;
 }
 
@@ -3153,288 +3170,39 @@ int aar_smooth_fit_params_validate(const aar_smooth_fit_params *in) {
 
 int aar_track_smooth_fit_terms(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *pair_terms, double sums[4]) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit_terms: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit_terms");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_fit_terms");
     if (rc) return rc;
-    if ((rc = smooth_rw_only(sp, "aar_track_smooth_fit_terms"))) return rc;
-    if ((rc = smooth_fit_entry(pb, "aar_track_smooth_fit_terms"))) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCall c;
-    if ((rc = smooth_prepare(pb, sp, c))) return rc;
-    SmoothFitBuf b;
-    if ((rc = smooth_fit_alloc(pb, b))) return rc;
-    double rec[8];
-    if ((rc = smooth_fit_estep(pb, c, 0, sp.sigma_rot, b, rec, "aar_track_smooth_fit_terms"))) return rc;
-    if (pair_terms && (rc = copy_d2h(pb, pair_terms, b.terms, 4 * (size_t)(F - 1) * sizeof(double)))) return rc;
-    if ((rc = check_async("smoothing fit kernels"))) return rc;
-    if (sums) for (int i = 0; i < 4; i++) sums[i] = rec[i];
-    return AAR_OK;
+    if ((rc = smooth_rw_only(c.sp, "aar_track_smooth_fit_terms"))) return rc;
+    return smooth_fit_terms(c, "aar_track_smooth_fit_terms", x_full, pair_terms, sums, /*six=*/false);
+}
+
+// the ...2 entries: under the random walk the entry above itself (its name in the messages)
+int aar_track_smooth_fit_terms2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *pair_terms, double sums[6]) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit_terms2: null argument");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_fit_terms2");
+    if (rc) return rc;
+    return smooth_fit_terms(c, c.cv ? "aar_track_smooth_fit_terms2" : "aar_track_smooth_fit_terms", x_full, pair_terms, sums, /*six=*/true);
 }
 
 int aar_track_smooth_fit(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, const aar_smooth_fit_params *fp_in,
                          double *path, aar_smooth_fit_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_fit");
     if (rc) return rc;
-    if ((rc = smooth_rw_only(sp, "aar_track_smooth_fit"))) return rc;
-    aar_smooth_fit_params fp;
-    if (fp_in) {
-        if ((rc = aar_smooth_fit_params_validate(fp_in))) return rc;
-        (void)smooth_fit_params_read(fp_in, &fp);
-    } else {
-        aar_smooth_fit_default_params(&fp);
-    }
-    if ((rc = smooth_fit_entry(pb, "aar_track_smooth_fit"))) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    aar_lm_params p;
-    if (prm) p = *prm; else aar_lm_default_params(&p);
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    const int F = P.F;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int64_t launches0 = pb->launches;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCall c;
-    if ((rc = smooth_prepare(pb, sp, c))) return rc;   // lambda at the start values
-    SmoothFitBuf b;
-    if ((rc = smooth_fit_alloc(pb, b))) return rc;
-    // the variances: q = sigma_px^2, s_r, s_t physical; the smoother runs at s / q
-    double q = 1.0, s_r = sp.sigma_rot * sp.sigma_rot, s_t = sp.sigma_trans * sp.sigma_trans;
-    aar_smooth_fit_report r;
-    memset(&r, 0, sizeof r);
-    if (path) { path[0] = 1.0; path[1] = sp.sigma_rot; path[2] = sp.sigma_trans; }
-    aar_smooth_params eff = sp;   // frame_time and rel_motion kept, the sigmas replaced
-    SmoothLm s;
-    double rec[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u_d = 0.0;
-    r.stop_code = 2;
-    for (int it = 0; it < fp.max_iters; it++) {
-        if (it > 0 && (rc = smooth_upload_lambda(pb, eff, c))) return rc;
-        if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
-        r.lm_steps += s.iters;
-        if ((rc = smooth_fit_estep(pb, c, s.cur, eff.sigma_rot, b, rec, "aar_track_smooth_fit"))) return rc;
-        const double er2 = eff.sigma_rot * eff.sigma_rot, et2 = eff.sigma_trans * eff.sigma_trans;
-        u_d = 6.0 * (double)F - rec[1] / er2 - rec[3] / et2;
-        const double n_r = fp.estimate_rot ? (rec[0] + q * rec[1]) / (3.0 * (double)(F - 1)) : s_r;
-        const double n_t = fp.estimate_trans ? (rec[2] + q * rec[3]) / (3.0 * (double)(F - 1)) : s_t;
-        const double n_q = fp.estimate_px ? (rec[4] + q * u_d) / (8.0 * (double)P.N) : q;
-        const double was[3] = {q, s_r, s_t}, now[3] = {n_q, n_r, n_t};
-        const char *names[3] = {"sigma_px", "sigma_rot", "sigma_trans"};
-        double change = 0.0;
-        for (int i = 0; i < 3; i++) {
-            if (!(now[i] > 0.0) || !std::isfinite(now[i]))
-                return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_fit: iteration %d: the M-step gives the variance %g for %s", it + 1, now[i], names[i]);
-            change = std::max(change, std::fabs(std::sqrt(now[i]) - std::sqrt(was[i])) / std::sqrt(was[i]));
-        }
-        q = n_q; s_r = n_r; s_t = n_t;
-        eff.sigma_rot = std::sqrt(s_r / q);
-        eff.sigma_trans = std::sqrt(s_t / q);
-        r.iterations = it + 1;
-        r.last_rel_change = change;
-        if (path) { double *row = path + 3 * (size_t)(it + 1); row[0] = std::sqrt(q); row[1] = std::sqrt(s_r); row[2] = std::sqrt(s_t); }
-        if (change < fp.rel_tol) { r.stop_code = 1; break; }
-    }
-    // the track at the fitted values
-    if ((rc = smooth_upload_lambda(pb, eff, c))) return rc;
-    if ((rc = smooth_lm_run(pb, c, p, s))) return rc;
-    r.lm_steps += s.iters;
-    HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.w.z[s.cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
-    if ((rc = check_async("smoothing fit kernels"))) return rc;
-    if ((rc = smooth_download(pb, x_full))) return rc;
-    if (report) {
-        r.struct_size = report->struct_size;
-        r.sigma_px = std::sqrt(q); r.sigma_rot = std::sqrt(s_r); r.sigma_trans = std::sqrt(s_t);
-        r.sigma_rot_eff = eff.sigma_rot; r.sigma_trans_eff = eff.sigma_trans;
-        r.launches = (int32_t)(pb->launches - launches0);
-        r.a_rot = rec[0]; r.u_rot = rec[1]; r.a_trans = rec[2]; r.u_trans = rec[3]; r.u_data = u_d; r.data_cost = rec[4];
-        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
-    return AAR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same fit under the constant-velocity prior (smooth_cv_fit_kernels.hip)
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-// the selected inverse's area, the entries' terms and the record the host reads: one allocation
-struct SmoothCvFitBuf {
-    SmoothCvCall mem;
-    double *area = nullptr, *terms = nullptr, *rec = nullptr;
-};
-
-int smooth_cv_fit_alloc(aar_problem *pb, SmoothCvFitBuf &b) {
-    const size_t F = (size_t)pb->P.F, na = smooth_cv_selinv_doubles((int)F), n = na + 4 * (F - 1) + 8;
-    HIP_TRY(hipMalloc((void **)&b.mem.base, n * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(b.mem.base, 0, n * sizeof(double), pb->stream));
-    b.area = b.mem.base; b.terms = b.area + na; b.rec = b.terms + 4 * (F - 1);
-    return AAR_OK;
-}
-
-// the E-step at c.w.z[cur] with the lambda on the device (built with eff's sigmas): launches, then the one read-back of rec [8] =
-// A_r, U_r, A_t, U_t over the terms 1 .. F-2, data cost, prior cost, pivot flag, u_0
-int smooth_cv_fit_estep(aar_problem *pb, const SmoothCvCall &c, int cur, const aar_smooth_params &eff, const SmoothCvFitBuf &b, double rec[8],
-                        const char *who) {
-    const int F = pb->P.F;
-    double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
-    int launches = smooth_cv_selinv_launch(pb, c, cur, b.area, &fc, &lc, &l2);
-    launches += launch_smooth_cv_fit_terms(c.w, cur, F, eff.sigma_rot, eff.sigma_rot0, eff.sigma_trans0, fc, lc, l2, b.terms, b.rec, pb->stream);
-    pb->launches += launches;
-    int rc = copy_d2h(pb, rec, b.rec, 8 * sizeof(double));
-    if (rc) return rc;
-    if (rec[6] != 0.0)
-        return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the block-pentadiagonal elimination (the frames' detections and the prior do "
-                                          "not determine every pose)", who);
-    return AAR_OK;
-}
-
-// what both entries refuse under constant velocity, after smooth_entry
-int smooth_cv_fit_entry(aar_problem *pb, const char *who) {
-    if (pb->with_huber)
-        return set_error(AAR_ERR_UNSUPPORTED, "%s: the problem was created with_huber; the Huber weights break the Gaussian data model the fit "
-                                              "rests on", who);
-    if (pb->L.F < 3)
-        return set_error(AAR_ERR_INVALID, "%s: num_frames = %d, the fit under AAR_SMOOTH_MODEL_CONSTANT_VELOCITY needs at least one "
-                                          "second-difference term (three frames)", who, (int)pb->L.F);
-    if (pb->P.N < 1) return set_error(AAR_ERR_INVALID, "%s: the problem has no detections", who);
-    return AAR_OK;
-}
-
-}  // namespace
-
-int aar_track_smooth_fit_terms2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *pair_terms, double sums[6]) {
-    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit_terms2: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit_terms2");
-    if (rc) return rc;
-    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) {
-        if ((rc = aar_track_smooth_fit_terms(pb, x_full, sp_in, pair_terms, sums))) return rc;
-        if (sums) sums[4] = sums[5] = 0.0;
-        return AAR_OK;
-    }
-    if ((rc = smooth_cv_fit_entry(pb, "aar_track_smooth_fit_terms2"))) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCvCall c;
-    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
-    SmoothCvFitBuf b;
-    if ((rc = smooth_cv_fit_alloc(pb, b))) return rc;
-    double rec[8], pair0 = 0.0;
-    if ((rc = smooth_cv_fit_estep(pb, c, 0, sp, b, rec, "aar_track_smooth_fit_terms2"))) return rc;
-    if ((rc = copy_d2h(pb, &pair0, c.w.Pe[0], sizeof pair0))) return rc;   // the evaluation's cost of pair 0
-    if ((rc = check_async("smoothing fit kernels"))) return rc;
-    if (pair_terms && (rc = copy_d2h(pb, pair_terms, b.terms, 4 * (size_t)(F - 1) * sizeof(double)))) return rc;
-    if (sums) {
-        for (int i = 0; i < 4; i++) sums[i] = rec[i];
-        sums[4] = rec[7];
-        sums[5] = pair0;
-    }
-    return AAR_OK;
+    if ((rc = smooth_rw_only(c.sp, "aar_track_smooth_fit"))) return rc;
+    return smooth_fit(c, "aar_track_smooth_fit", x_full, prm, fp_in, path, report);
 }
 
 int aar_track_smooth_fit2(aar_problem *pb, double *x_full, const aar_lm_params *prm, const aar_smooth_params *sp_in, const aar_smooth_fit_params *fp_in,
                           double *path, aar_smooth_fit_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_fit2: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_fit2");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_fit2");
     if (rc) return rc;
-    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return aar_track_smooth_fit(pb, x_full, prm, sp_in, fp_in, path, report);
-    aar_smooth_fit_params fp;
-    if (fp_in) {
-        if ((rc = aar_smooth_fit_params_validate(fp_in))) return rc;
-        (void)smooth_fit_params_read(fp_in, &fp);
-    } else {
-        aar_smooth_fit_default_params(&fp);
-    }
-    if ((rc = smooth_cv_fit_entry(pb, "aar_track_smooth_fit2"))) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    aar_lm_params p;
-    if (prm) p = *prm; else aar_lm_default_params(&p);
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    const int F = P.F;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int64_t launches0 = pb->launches;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(P, pb->cur, pb->stream);
-    SmoothCvCall c;
-    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;   // lambda at the start values, the ratios once
-    SmoothCvFitBuf b;
-    if ((rc = smooth_cv_fit_alloc(pb, b))) return rc;
-    // the variances: q = sigma_px^2, s_r, s_t physical; pair 0's sigmas physical and held; the smoother runs at sigma / sqrt(q)
-    double q = 1.0, s_r = sp.sigma_rot * sp.sigma_rot, s_t = sp.sigma_trans * sp.sigma_trans;
-    aar_smooth_fit_report r;
-    memset(&r, 0, sizeof r);
-    std::vector<double> rows;   // the path, handed over only when the fit has succeeded
-    rows.insert(rows.end(), {1.0, sp.sigma_rot, sp.sigma_trans});
-    aar_smooth_params eff = sp;   // frame_time kept, the sigmas replaced
-    SmoothLm s;
-    const SmoothCvOps ops{pb, c.w};
-    const double terms_n = 3.0 * (double)(F - 2);
-    double rec[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u_d = 0.0;
-    r.stop_code = 2;
-    for (int it = 0; it < fp.max_iters; it++) {
-        if (it > 0 && (rc = smooth_cv_upload_lambda(pb, eff, c))) return rc;
-        if ((rc = smooth_lm_loop(pb, ops, p, s))) return rc;
-        r.lm_steps += s.iters;
-        if ((rc = smooth_cv_fit_estep(pb, c, s.cur, eff, b, rec, "aar_track_smooth_fit2"))) return rc;
-        const double er2 = eff.sigma_rot * eff.sigma_rot, et2 = eff.sigma_trans * eff.sigma_trans;
-        u_d = 6.0 * (double)F - rec[1] / er2 - rec[3] / et2 - rec[7];
-        const double n_r = fp.estimate_rot ? (rec[0] + q * rec[1]) / terms_n : s_r;
-        const double n_t = fp.estimate_trans ? (rec[2] + q * rec[3]) / terms_n : s_t;
-        const double n_q = fp.estimate_px ? (rec[4] + q * u_d) / (8.0 * (double)P.N) : q;
-        const double was[3] = {q, s_r, s_t}, now[3] = {n_q, n_r, n_t};
-        const char *names[3] = {"sigma_px", "sigma_rot", "sigma_trans"};
-        double change = 0.0;
-        for (int i = 0; i < 3; i++) {
-            if (!(now[i] > 0.0) || !std::isfinite(now[i]))
-                return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_fit2: iteration %d: the M-step gives the variance %g for %s", it + 1, now[i], names[i]);
-            change = std::max(change, std::fabs(std::sqrt(now[i]) - std::sqrt(was[i])) / std::sqrt(was[i]));
-        }
-        q = n_q; s_r = n_r; s_t = n_t;
-        const double sq = std::sqrt(q);
-        eff.sigma_rot = std::sqrt(s_r / q);
-        eff.sigma_trans = std::sqrt(s_t / q);
-        eff.sigma_rot0 = sp.sigma_rot0 / sq;
-        eff.sigma_trans0 = sp.sigma_trans0 / sq;
-        r.iterations = it + 1;
-        r.last_rel_change = change;
-        rows.insert(rows.end(), {sq, std::sqrt(s_r), std::sqrt(s_t)});
-        if (change < fp.rel_tol) { r.stop_code = 1; break; }
-    }
-    // the track at the fitted values
-    if ((rc = smooth_cv_upload_lambda(pb, eff, c))) return rc;
-    if ((rc = smooth_lm_loop(pb, ops, p, s))) return rc;
-    r.lm_steps += s.iters;
-    HIP_TRY(hipMemcpyAsync(P.z[pb->cur] + 6 * (size_t)P.A, c.w.z[s.cur], 6 * (size_t)F * sizeof(double), hipMemcpyDeviceToDevice, pb->stream));
-    if ((rc = check_async("smoothing fit kernels"))) return rc;
-    if ((rc = smooth_download(pb, x_full))) return rc;
-    if (path) std::copy(rows.begin(), rows.end(), path);
-    if (report) {
-        r.struct_size = report->struct_size;
-        r.sigma_px = std::sqrt(q); r.sigma_rot = std::sqrt(s_r); r.sigma_trans = std::sqrt(s_t);
-        r.sigma_rot_eff = eff.sigma_rot; r.sigma_trans_eff = eff.sigma_trans;
-        r.launches = (int32_t)(pb->launches - launches0);
-        r.a_rot = rec[0]; r.u_rot = rec[1]; r.a_trans = rec[2]; r.u_trans = rec[3]; r.u_data = u_d; r.data_cost = rec[4];
-        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
-    return AAR_OK;
+    return smooth_fit(c, c.cv ? "aar_track_smooth_fit2" : "aar_track_smooth_fit", x_full, prm, fp_in, path, report);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3454,229 +3222,146 @@ int aar_smooth_query_validate(int32_t num_frames, const aar_smooth_params *sp_in
     return AAR_OK;
 }
 
-int aar_track_smooth_query(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
-                           double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report) {
-    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query");
-    if (rc) return rc;
-    if ((rc = smooth_rw_only(sp, "aar_track_smooth_query"))) return rc;
-    if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
-    if (sp.rel_motion)
-        return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_query: rel_motion is set; under an expected motion the pose of an inserted frame "
-                                              "has no closed form (the split of dR does not commute)");
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
-    const size_t Q = (size_t)n_query;
-    const auto t0 = std::chrono::steady_clock::now();
-    aar_smooth_query_report r;
-    memset(&r, 0, sizeof r);
-    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
-    r.num_vars = 6 * (int64_t)F;
-    r.num_queries = (int32_t)Q;
-    if (Q > 0) {
-        // the frame times as the device searches them, and the three counts from the same search on the host
-        std::vector<double> ft((size_t)F);
-        for (int f = 0; f < F; f++) ft[f] = sp.frame_time ? sp.frame_time[f] : (double)f;
-        for (size_t i = 0; i < Q; i++) {
-            const int s = (int)(std::upper_bound(ft.begin(), ft.end(), query_time[i]) - ft.begin()) - 1;
-            if (s >= 0 && ft[s] == query_time[i]) r.num_on_frame++;
-            else if (s < 0 || s == F - 1) r.num_outside++;
-            else r.num_inside++;
-        }
-        pb->lm_ready = false;
-        pb->blocks_valid = false;
-        if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-        // one allocation: ft [F] | query times [Q] | pose [Q][6] | cov [Q][36] | S, R [F][36] each | segment [Q] and the queries' pivot flag
-        const size_t n_cov = cov ? 36 * Q + 72 * (size_t)F : 0, n_dbl = (size_t)F + 7 * Q + n_cov, n_int = Q + 2;
-        SmoothCall out, c;
-        HIP_TRY(hipMalloc((void **)&out.base, n_dbl * sizeof(double) + n_int * sizeof(int32_t)));
-        HIP_TRY(hipMemsetAsync(out.base, 0, n_dbl * sizeof(double) + n_int * sizeof(int32_t), pb->stream));
-        double *d_ft = out.base, *d_qt = d_ft + F, *d_pose = d_qt + Q, *d_cov = cov ? d_pose + 6 * Q : nullptr;
-        double *S = cov ? d_cov + 36 * Q : nullptr, *R = cov ? S + 36 * (size_t)F : nullptr;
-        int32_t *d_seg = reinterpret_cast<int32_t *>(out.base + n_dbl), *d_flag = d_seg + Q;
-        if ((rc = copy_h2d(pb, d_ft, ft.data(), (size_t)F * sizeof(double)))) return rc;
-        if ((rc = copy_h2d(pb, d_qt, query_time, Q * sizeof(double)))) return rc;
-        const double *z = P.z[pb->cur] + 6 * (size_t)P.A;
-        if (cov) {
-            launch_unpack(P, pb->cur, pb->stream);
-            if ((rc = smooth_prepare(pb, sp, c))) return rc;
-            r.launches = smooth_selinv_launch(pb, c, 0, S, R);
-            z = c.w.z[0];
-        }
-        r.launches += launch_smooth_query(c.w, F, z, d_ft, sp.sigma_rot, sp.sigma_trans, S, R, (int64_t)Q, d_qt, d_pose, d_cov, d_seg, d_flag, pb->stream);
-        pb->launches += r.launches;
-        if (cov) {
-            double res[8];
-            int32_t flag = 0, qflag = 0;
-            if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
-            if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
-            if ((rc = copy_d2h(pb, &qflag, d_flag, sizeof qflag))) return rc;
-            if ((rc = check_async("smoothing query kernels"))) return rc;
-            if (flag)
-                return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_query: non-positive pivot in the block-tridiagonal elimination (the frames' "
-                                                  "detections and the prior do not determine every pose)");
-            if (qflag) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_query: non-positive pivot in a query's 6x6 inverses");
-            r.data_cost = res[0]; r.prior_cost = res[1];
-            if ((rc = copy_d2h(pb, cov, d_cov, 36 * Q * sizeof(double)))) return rc;
-        }
-        if (pose && (rc = copy_d2h(pb, pose, d_pose, 6 * Q * sizeof(double)))) return rc;
-        if (segment && (rc = copy_d2h(pb, segment, d_seg, Q * sizeof(int32_t)))) return rc;
-        if ((rc = check_async("smoothing query kernels"))) return rc;
-        HIP_TRY(hipStreamSynchronize(pb->stream));
-    }
-    const int64_t dof = r.num_residuals - r.num_vars;
-    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
-    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (report) {
-        r.struct_size = report->struct_size;
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
-    return AAR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The constant-velocity smoothed track at any time (smooth_cv_query_kernels.hip)
-// ------------------------------------------------------------------------------------------------
 namespace {
 
-// the chain of aar_track_smooth_query2 under constant velocity: H at mu = 0, its reduction and selected inverse, the lag-three blocks, the
-// queries.  cov == NULL saves the copy back alone (the pose depends on the block).  start, step: the start poses and delta_m (checking)
-int smooth_cv_query(aar_problem *pb, const double *x_full, const aar_smooth_params &sp, int64_t n_query, const double *query_time, double *pose,
-                    double *cov, int32_t *segment, double *start, double *step, aar_smooth_query_report *report, const char *who) {
-    HIP_TRY(hipSetDevice(pb->device));
+// the frame times as the device searches them, and the report's three counts from the same search on the host
+void smooth_query_times(const aar_smooth_params &sp, int F, size_t Q, const double *query_time, std::vector<double> &ft, aar_smooth_query_report &r) {
+    ft.resize((size_t)F);
+    for (int f = 0; f < F; f++) ft[f] = sp.frame_time ? sp.frame_time[f] : (double)f;
+    for (size_t i = 0; i < Q; i++) {
+        const int s = (int)(std::upper_bound(ft.begin(), ft.end(), query_time[i]) - ft.begin()) - 1;
+        if (s >= 0 && ft[s] == query_time[i]) r.num_on_frame++;
+        else if (s < 0 || s == F - 1) r.num_outside++;
+        else r.num_inside++;
+    }
+}
+
+// The three query entries after their model checks.  Random walk: the pose is a closed form of the frame poses, the selected inverse runs
+// for cov alone.  Constant velocity: H at mu = 0, its reduction and selected inverse, the lag-three blocks, then the queries; the pose
+// depends on the blocks, so cov == NULL saves the copy back alone.  start, step: the start poses and delta_m (constant velocity, checking)
+int smooth_query(SmoothRun &c, const char *who, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
+                 double *pose, double *cov, int32_t *segment, double *start, double *step, aar_smooth_query_report *report) {
+    aar_problem *pb = c.pb;
+    const aar_smooth_params &sp = c.sp;
+    int rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time);
+    if (rc) return rc;
+    if (sp.rel_motion)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: rel_motion is set; under an expected motion the pose of an inserted frame "
+                                              "has no closed form (the split of dR does not commute)", who);
     DeviceProblem &P = pb->P;
     const int F = P.F;
     const size_t Q = (size_t)n_query;
-    int rc = AAR_OK;
+    const bool blocks = c.cv || cov;   // the selected inverse runs
     const auto t0 = std::chrono::steady_clock::now();
     aar_smooth_query_report r;
-    memset(&r, 0, sizeof r);
-    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
-    r.num_vars = 6 * (int64_t)F;
+    smooth_report_begin(pb, r);
     r.num_queries = (int32_t)Q;
     if (Q > 0) {
-        std::vector<double> ft((size_t)F);
-        for (int f = 0; f < F; f++) ft[f] = sp.frame_time ? sp.frame_time[f] : (double)f;
-        for (size_t i = 0; i < Q; i++) {
-            const int s = (int)(std::upper_bound(ft.begin(), ft.end(), query_time[i]) - ft.begin()) - 1;
-            if (s >= 0 && ft[s] == query_time[i]) r.num_on_frame++;
-            else if (s < 0 || s == F - 1) r.num_outside++;
-            else r.num_inside++;
-        }
-        pb->lm_ready = false;
-        pb->blocks_valid = false;
-        if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-        launch_unpack(P, pb->cur, pb->stream);
-        SmoothCvCall c, sel, out;
-        if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
-        const size_t na = smooth_cv_selinv_doubles(F);
-        HIP_TRY(hipMalloc((void **)&sel.base, na * sizeof(double)));
-        HIP_TRY(hipMemsetAsync(sel.base, 0, na * sizeof(double), pb->stream));
-        // one allocation: ft [F] | query times [Q] | pose, start, step [Q][6] each | cov [Q][36] | l3 [F-3][36] | segment [Q] and the two pivot flags
-        const size_t n3 = 36 * (size_t)std::max(F - 3, 0), n_dbl = (size_t)F + 19 * Q + (cov ? 36 * Q : 0) + n3, n_int = Q + 2;
-        HIP_TRY(hipMalloc((void **)&out.base, n_dbl * sizeof(double) + n_int * sizeof(int32_t)));
-        HIP_TRY(hipMemsetAsync(out.base, 0, n_dbl * sizeof(double) + n_int * sizeof(int32_t), pb->stream));
-        double *d_ft = out.base, *d_qt = d_ft + F, *d_pose = d_qt + Q, *d_start = d_pose + 6 * Q, *d_step = d_start + 6 * Q;
-        double *d_cov = cov ? d_step + 6 * Q : nullptr, *d_l3 = d_step + 6 * Q + (cov ? 36 * Q : 0);
-        int32_t *d_seg = reinterpret_cast<int32_t *>(out.base + n_dbl), *d_flag = d_seg + Q;
+        std::vector<double> ft;
+        smooth_query_times(sp, F, Q, query_time, ft, r);
+        if ((rc = c.begin(x_full, blocks))) return rc;
+        // one allocation: ft [F] | query times [Q] | pose [Q][6] | start, step [Q][6] each (constant velocity) | cov [Q][36] | the selected
+        // inverse's area | l3 [F-3][36] (constant velocity) | segment [Q] and two pivot flags: the lag-three blocks', the queries'
+        const size_t n_out = c.cv ? 18 * Q : 6 * Q, n_cov = cov ? 36 * Q : 0, n_sel = blocks ? c.selinv_doubles() : 0;
+        const size_t n_dbl = (size_t)F + Q + n_out + n_cov + n_sel + (c.cv ? 36 * (size_t)std::max(F - 3, 0) : 0);
+        DevMem out;
+        if ((rc = out.alloc(pb, n_dbl, Q + 2))) return rc;
+        double *d_ft = out.p, *d_qt = d_ft + F, *d_pose = d_qt + Q, *d_start = c.cv ? d_pose + 6 * Q : nullptr, *d_step = c.cv ? d_start + 6 * Q : nullptr;
+        double *d_cov = cov ? d_pose + n_out : nullptr, *d_area = d_pose + n_out + n_cov, *d_l3 = d_area + n_sel;
+        int32_t *d_seg = reinterpret_cast<int32_t *>(out.p + n_dbl), *d_flag = d_seg + Q;
         if ((rc = copy_h2d(pb, d_ft, ft.data(), (size_t)F * sizeof(double)))) return rc;
         if ((rc = copy_h2d(pb, d_qt, query_time, Q * sizeof(double)))) return rc;
-        double *fc = nullptr, *lc = nullptr, *l2 = nullptr;
-        r.launches = smooth_cv_selinv_launch(pb, c, 0, sel.base, &fc, &lc, &l2);
-        r.launches += launch_smooth_cv_lag3(F, sel.base, d_l3, d_flag, pb->stream);
-        r.launches += launch_smooth_cv_query(F, c.w.z[0], d_ft, sp.sigma_rot, sp.sigma_trans, sp.sigma_rot0, sp.sigma_trans0, fc, lc, l2, d_l3,
-                                             (int64_t)Q, d_qt, d_pose, d_cov, d_start, d_step, d_seg, d_flag + 1, pb->stream);
+        SmoothSel sel;
+        if (blocks) sel = c.selinv(0, d_area);
+        r.launches = sel.launches;
+        if (c.cv) {
+            r.launches += launch_smooth_cv_lag3(F, d_area, d_l3, d_flag, pb->stream);
+            r.launches += launch_smooth_cv_query(F, c.z(0), d_ft, sp.sigma_rot, sp.sigma_trans, sp.sigma_rot0, sp.sigma_trans0, sel.fc, sel.lc, sel.l2,
+                                                 d_l3, (int64_t)Q, d_qt, d_pose, d_cov, d_start, d_step, d_seg, d_flag + 1, pb->stream);
+        } else {
+            r.launches += launch_smooth_query(c.rw, F, blocks ? c.z(0) : P.z[pb->cur] + 6 * (size_t)P.A, d_ft, sp.sigma_rot, sp.sigma_trans, sel.fc,
+                                              sel.lc, (int64_t)Q, d_qt, d_pose, d_cov, d_seg, d_flag + 1, pb->stream);
+        }
         pb->launches += r.launches;
-        double res[8];
-        int32_t flag = 0, qflag[2] = {0, 0};
-        if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
-        if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
-        if ((rc = copy_d2h(pb, qflag, d_flag, sizeof qflag))) return rc;
-        if ((rc = check_async("smoothing query kernels"))) return rc;
-        if (flag)
-            return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in the block-pentadiagonal elimination (the frames' detections and the prior do "
-                                              "not determine every pose)", who);
-        if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a supernode block of the lag-three blocks", who);
-        if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a query's eliminations", who);
-        r.data_cost = res[0]; r.prior_cost = res[1];
-        if (cov && (rc = copy_d2h(pb, cov, d_cov, 36 * Q * sizeof(double)))) return rc;
+        if (blocks) {
+            double res[8];
+            int32_t qflag[2] = {0, 0};
+            if ((rc = c.read_pivot(who, "smoothing query kernels", res))) return rc;
+            if ((rc = copy_d2h(pb, qflag, d_flag, sizeof qflag))) return rc;
+            if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a supernode block of the lag-three blocks", who);
+            if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a query's %s", who, c.cv ? "eliminations" : "6x6 inverses");
+            r.data_cost = res[0]; r.prior_cost = res[1];
+            if (cov && (rc = copy_d2h(pb, cov, d_cov, 36 * Q * sizeof(double)))) return rc;
+        }
         if (pose && (rc = copy_d2h(pb, pose, d_pose, 6 * Q * sizeof(double)))) return rc;
-        if (start && (rc = copy_d2h(pb, start, d_start, 6 * Q * sizeof(double)))) return rc;
-        if (step && (rc = copy_d2h(pb, step, d_step, 6 * Q * sizeof(double)))) return rc;
+        if (start && c.cv && (rc = copy_d2h(pb, start, d_start, 6 * Q * sizeof(double)))) return rc;
+        if (step && c.cv && (rc = copy_d2h(pb, step, d_step, 6 * Q * sizeof(double)))) return rc;
         if (segment && (rc = copy_d2h(pb, segment, d_seg, Q * sizeof(int32_t)))) return rc;
         if ((rc = check_async("smoothing query kernels"))) return rc;
         HIP_TRY(hipStreamSynchronize(pb->stream));
     }
-    const int64_t dof = r.num_residuals - r.num_vars;
-    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
-    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (report) {
-        r.struct_size = report->struct_size;
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
+    smooth_report_end(r, report, t0);
     return AAR_OK;
 }
 
 }  // namespace
 
+int aar_track_smooth_query(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
+                           double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report) {
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query: null argument");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_query");
+    if (rc) return rc;
+    if ((rc = smooth_rw_only(c.sp, "aar_track_smooth_query"))) return rc;
+    return smooth_query(c, "aar_track_smooth_query", x_full, sp_in, n_query, query_time, pose, cov, segment, nullptr, nullptr, report);
+}
+
+// under the random walk aar_track_smooth_query itself (its name in the messages)
 int aar_track_smooth_query2(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
                             double *pose, double *cov, int32_t *segment, aar_smooth_query_report *report) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query2: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query2");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_query2");
     if (rc) return rc;
-    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY) return aar_track_smooth_query(pb, x_full, sp_in, n_query, query_time, pose, cov, segment, report);
-    if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
-    return smooth_cv_query(pb, x_full, sp, n_query, query_time, pose, cov, segment, nullptr, nullptr, report, "aar_track_smooth_query2");
+    return smooth_query(c, c.cv ? "aar_track_smooth_query2" : "aar_track_smooth_query", x_full, sp_in, n_query, query_time, pose, cov, segment, nullptr,
+                        nullptr, report);
 }
 
 int aar_track_smooth_query2_step(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
                                  double *start_pose, double *step) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_query2_step: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_query2_step");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_query2_step");
     if (rc) return rc;
-    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+    if (!c.cv)
         return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_query2_step: model = AAR_SMOOTH_MODEL_RANDOM_WALK has no step (the pose of "
                                               "aar_track_smooth_query is a closed form); use AAR_SMOOTH_MODEL_CONSTANT_VELOCITY");
-    if ((rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, query_time))) return rc;
-    return smooth_cv_query(pb, x_full, sp, n_query, query_time, nullptr, nullptr, nullptr, start_pose, step, nullptr, "aar_track_smooth_query2_step");
+    return smooth_query(c, "aar_track_smooth_query2_step", x_full, sp_in, n_query, query_time, nullptr, nullptr, nullptr, start_pose, step, nullptr);
 }
 
 int aar_track_smooth_lag3(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *lag3_cov) {
     if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_lag3: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_lag3");
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, "aar_track_smooth_lag3");
     if (rc) return rc;
-    if (sp.model != AAR_SMOOTH_MODEL_CONSTANT_VELOCITY)
+    if (!c.cv)
         return set_error(AAR_ERR_UNSUPPORTED, "aar_track_smooth_lag3: model = AAR_SMOOTH_MODEL_RANDOM_WALK is not supported (the lag-three blocks "
                                               "belong to the selected inverse on supernodes of the block-pentadiagonal system); use "
                                               "AAR_SMOOTH_MODEL_CONSTANT_VELOCITY");
     const int F = pb->P.F;
     if (F < 4) return AAR_OK;
-    HIP_TRY(hipSetDevice(pb->device));
-    pb->lm_ready = false;
-    pb->blocks_valid = false;
-    if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-    launch_unpack(pb->P, pb->cur, pb->stream);
-    SmoothCvCall c, sel;
-    if ((rc = smooth_cv_prepare(pb, sp, c))) return rc;
-    const size_t na = smooth_cv_selinv_doubles(F), n3 = 36 * (size_t)(F - 3);
-    HIP_TRY(hipMalloc((void **)&sel.base, (na + n3 + 1) * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(sel.base, 0, (na + n3 + 1) * sizeof(double), pb->stream));
-    double *fc = nullptr, *lc = nullptr, *l2 = nullptr, *d_l3 = sel.base + na;
+    if ((rc = c.begin(x_full))) return rc;
+    // one allocation: the selected inverse's area | l3 [F-3][36] | the lag-three blocks' pivot flag
+    const size_t na = c.selinv_doubles(), n3 = 36 * (size_t)(F - 3);
+    DevMem sel;
+    if ((rc = sel.alloc(pb, na + n3, 2))) return rc;
+    double *d_l3 = sel.p + na;
     int32_t *d_flag = reinterpret_cast<int32_t *>(d_l3 + n3);
-    pb->launches += smooth_cv_selinv_launch(pb, c, 0, sel.base, &fc, &lc, &l2);
-    pb->launches += launch_smooth_cv_lag3(F, sel.base, d_l3, d_flag, pb->stream);
-    int32_t flag = 0, f3 = 0;
-    if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
+    pb->launches += c.selinv(0, sel.p).launches;
+    pb->launches += launch_smooth_cv_lag3(F, sel.p, d_l3, d_flag, pb->stream);
+    int32_t f3 = 0;
+    if ((rc = c.read_pivot("aar_track_smooth_lag3", "smoothing query kernels", nullptr))) return rc;
     if ((rc = copy_d2h(pb, &f3, d_flag, sizeof f3))) return rc;
-    if ((rc = check_async("smoothing query kernels"))) return rc;
-    if (flag)
-        return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_lag3: non-positive pivot in the block-pentadiagonal elimination (the frames' detections "
-                                          "and the prior do not determine every pose)");
     if (f3) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_lag3: non-positive pivot in a supernode block of the lag-three blocks");
     if (lag3_cov && (rc = copy_d2h(pb, lag3_cov, d_l3, n3 * sizeof(double)))) return rc;
     return check_async("smoothing query kernels");
@@ -3706,75 +3391,54 @@ int aar_smooth_relative_validate(int32_t num_frames, const aar_smooth_params *sp
 
 int aar_track_smooth_relative(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_pairs, const int32_t *frame_a,
                               const int32_t *frame_b, double *cross_cov, double *rel, double *rel_cov, aar_smooth_relative_report *report) {
-    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "aar_track_smooth_relative: null argument");
-    aar_smooth_params sp;
-    int rc = smooth_entry(pb, sp_in, &sp, "aar_track_smooth_relative");
+    const char *who = "aar_track_smooth_relative";
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "%s: null argument", who);
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, who);
     if (rc) return rc;
     if ((rc = aar_smooth_relative_validate(pb->L.F, sp_in, n_pairs, frame_a, frame_b))) return rc;
-    HIP_TRY(hipSetDevice(pb->device));
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
+    const int F = pb->P.F;
     const size_t Q = (size_t)n_pairs;
-    const bool cv = sp.model == AAR_SMOOTH_MODEL_CONSTANT_VELOCITY;
     const auto t0 = std::chrono::steady_clock::now();
     aar_smooth_relative_report r;
-    memset(&r, 0, sizeof r);
-    r.num_residuals = 8 * (int64_t)P.N + 6 * (int64_t)std::max(F - 1, 0);
-    r.num_vars = 6 * (int64_t)F;
+    smooth_report_begin(pb, r);
     r.num_pairs = (int32_t)Q;
     if (Q > 0) {
-        const int direct_lag = cv ? 3 : 1;   // the lags the selected inverse (and the lag-three blocks) hold
+        const int direct_lag = c.cv ? 3 : 1;   // the lags the selected inverse (and the lag-three blocks) hold
         for (size_t i = 0; i < Q; i++) {
             const int lag = std::abs(frame_a[i] - frame_b[i]);
             if (lag <= direct_lag) r.num_direct++; else r.num_chained++;
             r.max_lag = std::max(r.max_lag, lag);
         }
         const bool chained = r.num_chained > 0;
-        pb->lm_ready = false;
-        pb->blocks_valid = false;
-        if ((rc = upload_z(pb, x_full, pb->cur))) return rc;
-        launch_unpack(P, pb->cur, pb->stream);
-        // one allocation: cross [Q][36] | rel [Q][6] | rcov [Q][36] | the blocks and the gains of the model | the pairs [2][Q] and two pivot flags
-        const size_t K = (size_t)smooth_cv_nodes(F), n3 = 36 * (size_t)std::max(F - 3, 0);
-        const size_t n_blk = cv ? smooth_cv_selinv_doubles(F) + n3 + 144 * K : 108 * (size_t)F;
-        const size_t n_dbl = 78 * Q + n_blk, n_int = 2 * Q + 2;
-        SmoothCall out;
-        HIP_TRY(hipMalloc((void **)&out.base, n_dbl * sizeof(double) + n_int * sizeof(int32_t)));
-        HIP_TRY(hipMemsetAsync(out.base, 0, n_dbl * sizeof(double) + n_int * sizeof(int32_t), pb->stream));
-        double *d_cross = out.base, *d_rel = d_cross + 36 * Q, *d_rcov = d_rel + 6 * Q, *d_blk = d_rcov + 36 * Q;
-        int32_t *d_fa = reinterpret_cast<int32_t *>(out.base + n_dbl), *d_fb = d_fa + Q, *d_flag = d_fb + Q;
+        if ((rc = c.begin(x_full))) return rc;
+        // one allocation: cross [Q][36] | rel [Q][6] | rcov [Q][36] | the selected inverse's area | l3 [F-3][36] (constant velocity) | the gains
+        // [K][144] or [F][36] | the pairs [2][Q] and two pivot flags: the lag-three blocks', the gains'
+        const size_t n_sel = c.selinv_doubles(), n3 = c.cv ? 36 * (size_t)std::max(F - 3, 0) : 0;
+        const size_t n_dbl = 78 * Q + n_sel + n3 + (c.cv ? 144 * (size_t)smooth_cv_nodes(F) : 36 * (size_t)F);
+        DevMem out;
+        if ((rc = out.alloc(pb, n_dbl, 2 * Q + 2))) return rc;
+        double *d_cross = out.p, *d_rel = d_cross + 36 * Q, *d_rcov = d_rel + 6 * Q, *d_area = d_rcov + 36 * Q, *d_l3 = d_area + n_sel, *d_gain = d_l3 + n3;
+        int32_t *d_fa = reinterpret_cast<int32_t *>(out.p + n_dbl), *d_fb = d_fa + Q, *d_flag = d_fb + Q;
         if ((rc = copy_h2d(pb, d_fa, frame_a, Q * sizeof(int32_t)))) return rc;
         if ((rc = copy_h2d(pb, d_fb, frame_b, Q * sizeof(int32_t)))) return rc;
-        double res[8];
-        int32_t flag = 0, qflag[2] = {0, 0};
-        SmoothCall c;
-        SmoothCvCall ccv;
-        if (cv) {
-            if ((rc = smooth_cv_prepare(pb, sp, ccv))) return rc;
-            double *fc = nullptr, *lc = nullptr, *l2 = nullptr, *d_l3 = d_blk + smooth_cv_selinv_doubles(F), *d_gain = d_l3 + n3;
-            r.launches = smooth_cv_selinv_launch(pb, ccv, 0, d_blk, &fc, &lc, &l2);
-            r.launches += launch_smooth_cv_lag3(F, d_blk, d_l3, d_flag, pb->stream);
-            r.launches += launch_smooth_cv_relative(F, ccv.w.z[0], d_blk, fc, lc, l2, d_l3, d_gain, chained, (int64_t)Q, d_fa, d_fb, d_cross, d_rel,
-                                                    d_rcov, d_flag + 1, pb->stream);
-            if ((rc = copy_d2h(pb, res, ccv.w.res, sizeof res))) return rc;
-            if ((rc = copy_d2h(pb, &flag, ccv.w.flag, sizeof flag))) return rc;
+        const SmoothSel sel = c.selinv(0, d_area);
+        r.launches = sel.launches;
+        if (c.cv) {
+            r.launches += launch_smooth_cv_lag3(F, d_area, d_l3, d_flag, pb->stream);
+            r.launches += launch_smooth_cv_relative(F, c.z(0), d_area, sel.fc, sel.lc, sel.l2, d_l3, d_gain, chained, (int64_t)Q, d_fa, d_fb, d_cross,
+                                                    d_rel, d_rcov, d_flag + 1, pb->stream);
         } else {
-            if ((rc = smooth_prepare(pb, sp, c))) return rc;
-            double *S = d_blk, *R = S + 36 * (size_t)F, *d_gain = R + 36 * (size_t)F;
-            r.launches = smooth_selinv_launch(pb, c, 0, S, R);
-            r.launches += launch_smooth_relative(F, c.w.z[0], S, R, d_gain, chained, (int64_t)Q, d_fa, d_fb, d_cross, d_rel, d_rcov, d_flag + 1,
+            r.launches += launch_smooth_relative(F, c.z(0), sel.fc, sel.lc, d_gain, chained, (int64_t)Q, d_fa, d_fb, d_cross, d_rel, d_rcov, d_flag + 1,
                                                  pb->stream);
-            if ((rc = copy_d2h(pb, res, c.w.res, sizeof res))) return rc;
-            if ((rc = copy_d2h(pb, &flag, c.w.flag, sizeof flag))) return rc;
         }
         pb->launches += r.launches;
+        double res[8];
+        int32_t qflag[2] = {0, 0};
+        if ((rc = c.read_pivot(who, "smoothing relative kernels", res))) return rc;
         if ((rc = copy_d2h(pb, qflag, d_flag, sizeof qflag))) return rc;
-        if ((rc = check_async("smoothing relative kernels"))) return rc;
-        if (flag)
-            return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_relative: non-positive pivot in the block-%s elimination (the frames' detections and "
-                                              "the prior do not determine every pose)", cv ? "pentadiagonal" : "tridiagonal");
-        if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_relative: non-positive pivot in a supernode block of the lag-three blocks");
-        if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "aar_track_smooth_relative: non-positive pivot in a covariance block that the chain inverts");
+        if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a supernode block of the lag-three blocks", who);
+        if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a covariance block that the chain inverts", who);
         r.data_cost = res[0]; r.prior_cost = res[1];
         if (cross_cov && (rc = copy_d2h(pb, cross_cov, d_cross, 36 * Q * sizeof(double)))) return rc;
         if (rel && (rc = copy_d2h(pb, rel, d_rel, 6 * Q * sizeof(double)))) return rc;
@@ -3782,13 +3446,7 @@ int aar_track_smooth_relative(aar_problem *pb, const double *x_full, const aar_s
         if ((rc = check_async("smoothing relative kernels"))) return rc;
         HIP_TRY(hipStreamSynchronize(pb->stream));
     }
-    const int64_t dof = r.num_residuals - r.num_vars;
-    r.sigma2 = dof > 0 ? (r.data_cost + r.prior_cost) / (double)dof : 0.0;
-    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (report) {
-        r.struct_size = report->struct_size;
-        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
-    }
+    smooth_report_end(r, report, t0);
     return AAR_OK;
 }
 

@@ -727,7 +727,7 @@ int aar_track_smooth_covariance2(aar_problem *, const double *x_full, const aar_
  * report->iterations are not written).  NULL aar_lm_params / aar_smooth_fit_params: the defaults.  Bit-reproducible from call to call.
  * AAR_ERR_INVALID: num_frames < 2, no detections, all estimate_* zero, rel_tol negative or not finite, max_iters < 1.  AAR_ERR_UNSUPPORTED: a
  * problem created with_huber (the weights break the Gaussian data model), a communicator.  AAR_ERR_NUMERIC: a non-positive pivot, an M-step
- * that gives a variance that is not positive and finite.  On an error x_full is not modified. */
+ * that gives a variance that is not positive and finite.  On an error nothing is written: x_full, path and report keep their contents. */
 typedef struct aar_smooth_fit_params {
     uint32_t struct_size;
     int32_t max_iters;           /* 50 */
