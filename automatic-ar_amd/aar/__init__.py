@@ -37,6 +37,7 @@ SYMBOLS = [
     "aar_solver_default_options", "aar_problem_create_ex", "aar_problem_get_solver_stats", "aar_problem_set_test_hook",
     "aar_problem_covariance", "aar_covariance_write_yaml",
     "aar_predict_query_validate", "aar_problem_predict_corners", "aar_problem_detection_leverage", "aar_leverage_write_yaml",
+    "aar_problem_detection_loo", "aar_problem_gate_detections", "aar_loo_write_yaml",
     "aar_problem_residual_report", "aar_dataset_select_observations", "aar_residual_report_write_yaml",
     "aar_problem_constraints_validate", "aar_problem_create_constrained", "aar_problem_num_priors", "aar_problem_eval_priors",
     "aar_problem_num_pair_priors", "aar_problem_eval_pair_priors", "aar_relative_pose",
@@ -65,6 +66,7 @@ TRACKER_STARTS = {"vote": TRACKER_START_VOTE, "best": TRACKER_START_BEST}
 NUM_KERNELS = 18
 PRIOR_CAMERA, PRIOR_MARKER = 0, 1
 PREDICT_BEHIND, PREDICT_UNDEFINED = 1, 2
+PREDICT_UNDETERMINED = 4
 PRIOR_KINDS = {"camera": PRIOR_CAMERA, "marker": PRIOR_MARKER}
 SOLVER_DIRECT, SOLVER_PCG, SOLVER_SPCG, SOLVER_AUTO = 0, 1, 2, 3
 TEST_HOOK_SPCG_DROP = 1
@@ -136,6 +138,15 @@ class CPredictReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("sum_sq", C.c_double),
                 ("sigma2", C.c_double), ("num_live_vars", C.c_int64), ("leverage_sum", C.c_double), ("undefined", C.c_int64),
                 ("behind", C.c_int64), ("launches", C.c_int32), ("seconds", C.c_double)]
+
+
+class CLooRule(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("f_max", C.c_double)]
+
+
+class CLooReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("predict", CPredictReport), ("dof", C.c_int64), ("undetermined", C.c_int64),
+                ("rejected", C.c_int64), ("f_max", C.c_double), ("max_f", C.c_double), ("argmax_f", C.c_int64)]
 
 
 class COutlierRule(C.Structure):
@@ -556,6 +567,10 @@ def lib():
     L.aar_predict_query_validate.argtypes = [C.POINTER(CProblemDesc), C.c_int64, ip32, ip32, ip32]
     L.aar_problem_predict_corners.argtypes = [C.c_void_p, dp, C.c_int64, ip32, ip32, ip32, dp, dp, u8p, C.POINTER(CPredictReport)]
     L.aar_problem_detection_leverage.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(CPredictReport)]
+    L.aar_problem_detection_loo.argtypes = [C.c_void_p, dp, C.POINTER(CLooRule), dp, dp, dp, dp, dp, dp, u8p, u8p, C.POINTER(CLooReport)]
+    L.aar_problem_gate_detections.argtypes = [C.c_void_p, dp, C.c_int64, ip32, ip32, ip32, C.POINTER(C.c_float), dp, dp, u8p,
+                                              C.POINTER(CPredictReport)]
+    L.aar_loo_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, dp, dp, u8p, u8p, C.POINTER(CLooReport)]
     L.aar_leverage_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, C.c_double, C.POINTER(CPredictReport)]
     L.aar_problem_residual_report.argtypes = [C.c_void_p, dp, C.POINTER(COutlierRule), dp, u8p, dp, dp, dp, C.POINTER(CResidualReport)]
     L.aar_dataset_select_observations.argtypes = [C.POINTER(CDataset), u8p, C.POINTER(C.POINTER(CDataset))]
@@ -1143,6 +1158,37 @@ def predict_query_validate(ds, queries):
 
 def _predict_report_dict(rep):
     return {name: getattr(rep, name) for name, _ in CPredictReport._fields_[1:]}
+
+
+def _loo_report_dict(rep):
+    d = {name: getattr(rep, name) for name, _ in CLooReport._fields_[2:]}
+    d["predict"] = _predict_report_dict(rep.predict)
+    return d
+
+
+class DetectionLoo:
+    """What Problem.detection_loo returns (aar_problem_detection_loo)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def loo_write_yaml(path, ds, loo, det_err=None):
+    """aar_loo_write_yaml: loo as Problem.detection_loo returns it for a (single-GPU) problem created from ds; det_err as
+    Problem.residual_report(x).det_err, or None"""
+    c = ds.as_c()
+    r = CLooReport()
+    r.struct_size = C.sizeof(CLooReport)
+    for name, _ in CLooReport._fields_[2:]:
+        setattr(r, name, loo.report[name])
+    r.predict.struct_size = C.sizeof(CPredictReport)
+    for name, _ in CPredictReport._fields_[1:]:
+        setattr(r.predict, name, loo.report["predict"][name])
+    F, q, lev = (np.ascontiguousarray(getattr(loo, k), dtype=np.float64) for k in ("F", "q", "leverage"))
+    st, keep = (np.ascontiguousarray(getattr(loo, k), dtype=np.uint8) for k in ("status", "keep"))
+    e = None if det_err is None else np.ascontiguousarray(det_err, dtype=np.float64)
+    _check(lib().aar_loo_write_yaml(path.encode(), C.byref(c), _dptr(F), _dptr(q), _dptr(lev), _dptr(e) if e is not None else None, _u8ptr(st),
+                                    _u8ptr(keep), C.byref(r)))
 
 
 def leverage_write_yaml(path, ds, leverage, report, h_min=0.0, det_err=None):
@@ -1733,6 +1779,48 @@ class Problem:
         rep.struct_size = C.sizeof(CPredictReport)
         _check(lib().aar_problem_detection_leverage(self.handle, _dptr(x), _dptr(lv), _dptr(rw) if rows else None, C.byref(rep)))
         return lv[:n], (rw[:n] if rows else None), _predict_report_dict(rep)
+
+    def detection_loo(self, x_full, f_max=None):
+        """aar_problem_detection_loo at x_full, with the rule F > f_max when f_max is given.  Returns a DetectionLoo: loo_resid [local_obs, 8],
+        q, F, cook, leverage, margin [local_obs], status, keep [local_obs] (uint8) and report: the aar_loo_report fields as a dict, its
+        "predict" entry the dict of the aar_predict_report inside.  q is UNSCALED: q / report["predict"]["sigma2"] is the chi-square."""
+        x = self._x(x_full)
+        n = self.local_obs
+        m = max(n, 1)
+        w = np.full((m, 8), np.nan)
+        q, F, cook, lev, margin = (np.full(m, np.nan) for _ in range(5))
+        st, keep = np.zeros(m, dtype=np.uint8), np.ones(m, dtype=np.uint8)
+        rule = None
+        if f_max is not None:
+            rule = CLooRule()
+            rule.struct_size = C.sizeof(CLooRule)
+            rule.f_max = float(f_max)
+        rep = CLooReport()
+        rep.struct_size = C.sizeof(CLooReport)
+        _check(lib().aar_problem_detection_loo(self.handle, _dptr(x), C.byref(rule) if rule is not None else None, _dptr(w), _dptr(q), _dptr(F),
+                                               _dptr(cook), _dptr(lev), _dptr(margin), _u8ptr(st), _u8ptr(keep), C.byref(rep)))
+        return DetectionLoo(loo_resid=w[:n], q=q[:n], F=F[:n], cook=cook[:n], leverage=lev[:n], margin=margin[:n], status=st[:n], keep=keep[:n],
+                            report=_loo_report_dict(rep))
+
+    def gate_detections(self, x_full, cams, markers, frames, uv_obs):
+        """aar_problem_gate_detections at x_full for candidate detections (camera index, marker index, frame index) with observed corners
+        uv_obs [Q, 4, 2] or [Q, 8] (undistorted pixels; stored as float32).  Returns (innovation [Q, 8] = uv_obs - predicted, m2 [Q] =
+        e^T (I + C)^-1 e UNSCALED -- m2 / report["sigma2"] is chi-square with 8 degrees of freedom --, status [Q], report dict)."""
+        x = self._x(x_full)
+        qc, qm, qf = _queries(np.stack([np.asarray(cams).reshape(-1), np.asarray(markers).reshape(-1), np.asarray(frames).reshape(-1)], axis=1))
+        n = len(qc)
+        uv = np.ascontiguousarray(np.asarray(uv_obs, dtype=np.float32).reshape(-1, 8))
+        if len(uv) != n:
+            raise ValueError("gate_detections: %d queries, %d sets of corners" % (n, len(uv)))
+        inn = np.full((max(n, 1), 8), np.nan)
+        m2 = np.full(max(n, 1), np.nan)
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        rep = CPredictReport()
+        rep.struct_size = C.sizeof(CPredictReport)
+        _check(lib().aar_problem_gate_detections(self.handle, _dptr(x), n, _i32ptr(qc), _i32ptr(qm), _i32ptr(qf),
+                                                 uv.ctypes.data_as(C.POINTER(C.c_float)) if n else None, _dptr(inn), _dptr(m2), _u8ptr(st),
+                                                 C.byref(rep)))
+        return inn[:n], m2[:n], st[:n], _predict_report_dict(rep)
 
     def residual_report(self, x_full, k_median=0.0, min_px=0.0, rule=None):
         """aar_problem_residual_report at x_full.  The rule's threshold is max(min_px, k_median * median) (k_median <= 0: min_px; both <= 0:

@@ -19,6 +19,7 @@
 #include <cstddef>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <numeric>
 #include <optional>
 #include <condition_variable>
@@ -3598,6 +3599,117 @@ int predict_run(aar_problem *pb, const double *x_full, int mode, int64_t n, cons
     }
     return AAR_OK;
 }
+
+// Leave-one-out residuals of the problem's own detections (mode 3) and the gate of candidate detections (mode 4): DESIGN.md section 37.
+// One covariance chain, one gains launch, one query launch; the scalars the F statistic needs are on the host before that launch.
+struct LooOut {
+    double *w = nullptr, *q = nullptr, *F = nullptr, *cook = nullptr, *lev = nullptr, *margin = nullptr;
+    uint8_t *status = nullptr, *keep = nullptr;
+};
+
+int loo_run(aar_problem *pb, const double *x_full, int mode, int64_t n, const int32_t *q_cam, const int32_t *q_marker, const int32_t *q_frame,
+            const float *uv_obs, double f_max, const LooOut &o, aar_predict_report &r, aar_loo_report *lr) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceProblem &P = pb->P;
+    const PoseLayout &L = pb->L;
+    const int cur = pb->cur;
+    const int64_t launches0 = pb->launches;
+    memset(&r, 0, sizeof r);
+    r.num_residuals = 8 * pb->N_global;
+    r.num_vars = L.z_len();
+    r.sum_sq = r.sigma2 = NAN;
+    const int64_t dof = r.num_residuals - r.num_vars;
+    if (lr) {
+        lr->dof = dof; lr->undetermined = lr->rejected = 0; lr->f_max = f_max > 0.0 ? f_max : INFINITY;
+        lr->max_f = NAN; lr->argmax_f = -1;
+    }
+    if (n > 0) {
+        HIP_TRY(hipSetDevice(pb->device));
+        int rc;
+        CovChain ch;
+        if ((rc = cov_chain(pb, x_full, true, false, ch))) return rc;
+        r.sum_sq = ch.sum_sq;
+        r.sigma2 = dof > 0 ? ch.sum_sq / (double)dof : NAN;
+        for (int32_t m : ch.mask) r.num_live_vars += m == PREDICT_LIVE;
+        if (L.of)
+            for (int f = 0; f < P.F; f++) r.num_live_vars += pb->h_fslot_start[f + 1] > pb->h_fslot_start[f] ? 6 : 0;
+        const bool frames_opt = L.of && P.F > 0;
+        // one allocation: gains | w | q | k | margin | F | cook | leverage, then the queries and the caller's corners, then status | keep
+        const size_t N = (size_t)n, n_gain = frames_opt ? 36 * (size_t)std::max(P.total_slots, 1) : 0, n_m3 = mode == 3 ? N : 0;
+        const size_t n_dbl = n_gain + 8 * N + 3 * N + 3 * n_m3, n_int = mode == 4 ? 3 * N : 0, n_flt = mode == 4 ? 8 * N : 0;
+        const size_t bytes = n_dbl * sizeof(double) + n_int * sizeof(int32_t) + n_flt * sizeof(float) + 2 * N;
+        PredictCall out;
+        HIP_TRY(hipMalloc(&out.base, bytes));
+        HIP_TRY(hipMemsetAsync(out.base, 0, bytes, pb->stream));
+        double *d_gain = static_cast<double *>(out.base), *d_w = d_gain + n_gain, *d_q = d_w + 8 * N, *d_k = d_q + N, *d_mg = d_k + N, *d_F = d_mg + N,
+               *d_ck = d_F + n_m3, *d_lev = d_ck + n_m3, *d_end = d_lev + n_m3;   // (k is mode 3's: its slot stays zero in mode 4)
+        int32_t *d_qc = reinterpret_cast<int32_t *>(d_end), *d_qm = d_qc + (mode == 4 ? N : 0), *d_qf = d_qm + (mode == 4 ? N : 0);
+        float *d_obs = reinterpret_cast<float *>(d_qc + n_int);
+        uint8_t *d_st = reinterpret_cast<uint8_t *>(d_obs + n_flt), *d_keep = d_st + N;
+        if (mode == 4 && ((rc = copy_h2d(pb, d_qc, q_cam, N * sizeof(int32_t))) || (rc = copy_h2d(pb, d_qm, q_marker, N * sizeof(int32_t))) ||
+                          (rc = copy_h2d(pb, d_qf, q_frame, N * sizeof(int32_t))) || (rc = copy_h2d(pb, d_obs, uv_obs, 8 * N * sizeof(float)))))
+            return rc;
+        launch_unpack(P, cur, pb->stream);
+        pb->launches += 1;
+        const KTable kt = k_table(P, cur);
+        PredictArgs a;
+        memset(&a, 0, sizeof a);
+        a.ent = P.ent[cur]; a.K = kt.base; a.kstride = kt.stride; a.C = P.C; a.A = P.A; a.h = P.half_size; a.n = n;
+        a.q_cam = d_qc; a.q_marker = d_qm; a.q_frame = d_qf; a.obs = P.a_idx;
+        a.fslot_start = P.fslot_start; a.fslot_ent = P.fslot_ent; a.rowmask = ch.rowmask;
+        a.frames_opt = frames_opt ? 1 : 0; a.n_pad = P.n_pad;
+        a.gain = d_gain; a.Sinv = ch.Sinv; a.frame_cov = ch.frame_blocks;
+        a.status = d_st; a.lev = d_lev;
+        a.obs_uv = mode == 3 ? P.a_uv : d_obs;
+        a.loo_w = d_w; a.loo_q = d_q; a.loo_k = d_k; a.loo_margin = d_mg; a.loo_F = d_F; a.loo_cook = d_ck; a.loo_keep = d_keep;
+        a.sum_sq = r.sum_sq; a.cook_den = (double)r.num_live_vars * r.sigma2; a.f_max = f_max > 0.0 ? f_max : 0.0; a.dof = dof;
+        if (frames_opt) {
+            launch_predict_gains(P, cur, ch.rowmask, d_gain, pb->stream);
+            pb->launches += 1;
+        }
+        launch_predict_corners(a, mode, pb->stream);
+        pb->launches += 1;
+        if ((rc = check_async("leave-one-out kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+        // to the host: what the report needs (status | keep, and for mode 3 F and the leverage) and what the caller asked for, nothing else,
+        // into staging that nobody has touched before (no fill pass); the caller's arrays are written below, after every copy succeeded
+        std::unique_ptr<double[]> h_d(new double[(size_t)(d_end - d_w)]);
+        std::vector<uint8_t> h_b(2 * N);
+        double *h_w = h_d.get(), *h_q = h_w + 8 * N, *h_mg = h_q + 2 * N, *h_F = h_mg + N, *h_ck = h_F + n_m3, *h_lev = h_ck + n_m3;
+        if ((rc = copy_d2h(pb, h_b.data(), d_st, 2 * N))) return rc;
+        if (o.w && (rc = copy_d2h(pb, h_w, d_w, 8 * N * sizeof(double)))) return rc;
+        if (o.q && (rc = copy_d2h(pb, h_q, d_q, N * sizeof(double)))) return rc;
+        if (o.margin && (rc = copy_d2h(pb, h_mg, d_mg, N * sizeof(double)))) return rc;
+        if (mode == 3 && ((rc = copy_d2h(pb, h_F, d_F, N * sizeof(double))) || (rc = copy_d2h(pb, h_lev, d_lev, N * sizeof(double))))) return rc;
+        if (mode == 3 && o.cook && (rc = copy_d2h(pb, h_ck, d_ck, N * sizeof(double)))) return rc;
+        if ((rc = check_async("leave-one-out kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+        // everything succeeded: only now the caller's arrays are written
+        for (size_t i = 0; i < N; i++) {
+            r.behind += (h_b[i] & AAR_PREDICT_BEHIND) ? 1 : 0;
+            r.undefined += (h_b[i] & AAR_PREDICT_UNDEFINED) ? 1 : 0;
+            if (mode == 3 && std::isfinite(h_lev[i])) r.leverage_sum += h_lev[i];
+            if (lr && mode == 3) {
+                lr->undetermined += (h_b[i] & AAR_PREDICT_UNDETERMINED) ? 1 : 0;
+                lr->rejected += h_b[N + i] ? 0 : 1;
+                if (h_F[i] > lr->max_f || (lr->argmax_f < 0 && !std::isnan(h_F[i]))) { lr->max_f = h_F[i]; lr->argmax_f = (int64_t)i; }
+            }
+        }
+        if (o.w) memcpy(o.w, h_w, 8 * N * sizeof(double));
+        if (o.q) memcpy(o.q, h_q, N * sizeof(double));
+        if (o.margin) memcpy(o.margin, h_mg, N * sizeof(double));
+        if (o.status) memcpy(o.status, h_b.data(), N);
+        if (mode == 3) {
+            if (o.F) memcpy(o.F, h_F, N * sizeof(double));
+            if (o.cook) memcpy(o.cook, h_ck, N * sizeof(double));
+            if (o.lev) memcpy(o.lev, h_lev, N * sizeof(double));
+            if (o.keep) memcpy(o.keep, h_b.data() + N, N);
+        }
+    }
+    r.launches = (int32_t)(pb->launches - launches0);
+    r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return AAR_OK;
+}
 }  // namespace
 
 int aar_problem_predict_corners(aar_problem *pb, const double *x_full, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker,
@@ -3627,6 +3739,64 @@ int aar_problem_detection_leverage(aar_problem *pb, const double *x_full, double
     int rc = predict_refuse(pb, "aar_problem_detection_leverage");
     if (rc) return rc;
     return predict_run(pb, x_full, 2, pb->P.N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, leverage, row_leverage, report);
+}
+
+int aar_problem_detection_loo(aar_problem *pb, const double *x_full, const aar_loo_rule *rule, double *loo_resid, double *q, double *F, double *cook,
+                              double *leverage, double *margin, uint8_t *status, uint8_t *keep, aar_loo_report *report) {
+    if (!pb) {
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_problem_detection_loo: null problem");
+    }
+    if (!x_full) return set_error(AAR_ERR_INVALID, "aar_problem_detection_loo: null argument");
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_detection_loo: report->struct_size not set");
+    if (rule) {
+        if (rule->struct_size < offsetof(aar_loo_rule, f_max) + sizeof(double))
+            return set_error(AAR_ERR_INVALID, "aar_problem_detection_loo: rule->struct_size %u does not reach f_max", (unsigned)rule->struct_size);
+        if (!(rule->f_max > 0.0) || !std::isfinite(rule->f_max))
+            return set_error(AAR_ERR_INVALID, "aar_problem_detection_loo: rule->f_max = %g must be positive and finite", rule->f_max);
+    }
+    int rc = predict_refuse(pb, "aar_problem_detection_loo");
+    if (rc) return rc;
+    if (pb->with_huber)
+        return set_error(AAR_ERR_UNSUPPORTED, "aar_problem_detection_loo: the problem was created with_huber; the Huber weights break the Gaussian "
+                                              "data model the statistic rests on");
+    aar_loo_report r;
+    memset(&r, 0, sizeof r);
+    LooOut o;
+    o.w = loo_resid; o.q = q; o.F = F; o.cook = cook; o.lev = leverage; o.margin = margin; o.status = status; o.keep = keep;
+    if ((rc = loo_run(pb, x_full, 3, pb->P.N, nullptr, nullptr, nullptr, nullptr, rule ? rule->f_max : 0.0, o, r.predict, &r))) return rc;
+    r.predict.struct_size = sizeof(aar_predict_report);
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
+}
+
+int aar_problem_gate_detections(aar_problem *pb, const double *x_full, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker,
+                                const int32_t *q_frame, const float *uv_obs, double *innovation, double *m2, uint8_t *status,
+                                aar_predict_report *report) {
+    if (!pb) {
+        if (int rc = ensure_device(0)) return rc;
+        return set_error(AAR_ERR_INVALID, "aar_problem_gate_detections: null problem");
+    }
+    if (!x_full || (n_query > 0 && !uv_obs)) return set_error(AAR_ERR_INVALID, "aar_problem_gate_detections: null argument");
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "aar_problem_gate_detections: report->struct_size not set");
+    int rc = predict_refuse(pb, "aar_problem_gate_detections");
+    if (rc) return rc;
+    aar_problem_desc d;
+    memset(&d, 0, sizeof d);
+    d.num_cams = pb->L.C; d.num_markers = pb->L.M; d.num_frames = pb->L.F;
+    if ((rc = aar_predict_query_validate(&d, n_query, q_cam, q_marker, q_frame))) return rc;
+    aar_predict_report r;
+    LooOut o;
+    o.w = innovation; o.q = m2; o.status = status;
+    if ((rc = loo_run(pb, x_full, 4, n_query, q_cam, q_marker, q_frame, uv_obs, 0.0, o, r, nullptr))) return rc;
+    if (report) {
+        r.struct_size = report->struct_size;
+        memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
+    }
+    return AAR_OK;
 }
 
 int aar_set_kernel_profiling(aar_problem *pb, int on) {

@@ -566,7 +566,19 @@ struct PredictArgs {
     double *uv, *cov;                     // [n][8], [n][64] (modes 0, 1; cov mode 0 only)
     uint8_t *status;                      // [n] bit 0: a corner at non-positive depth, bit 1: covariance undefined
     double *lev, *row_lev;                // [n], [n][8] or NULL (mode 2): trace and diagonal of C
+    // modes 3, 4 (leave-one-out residuals, gate of candidate detections: DESIGN.md section 37).  r = observed - u, A = I - C (3) / I + C (4)
+    const float *obs_uv;                  // observed corners [n][8]: ordering A's (mode 3), the caller's (mode 4)
+    double *loo_w, *loo_q, *loo_k, *loo_margin;   // [n][8] w = A^-1 r (mode 4: r itself), [n] r^T w, [n] w^T C w (mode 3), [n] smallest pivot
+    double *loo_F, *loo_cook;             // [n] (mode 3)
+    uint8_t *loo_keep;                    // [n] (mode 3)
+    double sum_sq, cook_den, f_max;       // (mode 3) the chain's sum r^2, num_live_vars * sigma2, the rule's bound (0: no rule)
+    int64_t dof;                          // (mode 3) nu = num_residuals - num_vars
 };
+// A pivot L_kk^2 of I - C_i at or below this (or not finite) makes the detection UNDETERMINED: nothing but itself determines some
+// direction of its corners, and a fit without it does not exist.  A stated choice: well above the absolute error measured for an
+// entry of C (<= 4e-8 on the test sets), far below any 1 - lambda at which a deleted fit still means something.
+constexpr double PREDICT_LOO_MIN_PIVOT = 1e-6;
+constexpr int PREDICT_UNDETERMINED = 4;   // status bit 2 (AAR_PREDICT_UNDETERMINED)
 // gain[s][36] = V_f^-1 W_s^T for every slot s (frame f's slots at fslot_start[f]), masked rows' columns zero: needs Vinv at mu = 0 and the fp64 W
 void launch_predict_gains(const DeviceProblem &P, int which, const int32_t *rowmask, double *gain, hipStream_t st);
 // mode 0: uv | cov | status of explicit queries, 1: uv | status alone (nothing of the chain is read), 2: lev | row_lev | status of the

@@ -32,6 +32,8 @@ static int print_usage(const char *a0) {
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -leverage <h_min>    also write final.leverage.yaml (leverage of every detection, 0 .. 8; those from h_min up are listed)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
+    cout << "       -loo <f_max>         also write final.loo.yaml (leave-one-out F of every detection; those above f_max or undetermined are listed)" << endl;
+    cout << "       -reject-loo <f_max>  after the solve, drop of every frame the detection with the largest F above f_max and solve again (not with -with-huber)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
     cout << "                            (up to 3 rounds, until a round drops nothing); final.solution keeps the remaining detections" << endl;
     cout << "       -reject-min-px px    the floor of that threshold in pixels (default 0)" << endl;
@@ -229,6 +231,33 @@ static int reject_outliers(aar::MultiCamMapper &mcm, const string &res_path, dou
     return 0;
 }
 
+// -reject-loo: report, drop, solve again from that solution -- until a round drops nothing, at most 3 rounds; a round drops of every frame
+// only the detection with the largest F above f_max
+static int reject_loo(aar::MultiCamMapper &mcm, double f_max) {
+    try {
+        for (int round = 1; round <= 3; round++) {
+            aar::MultiCamMapper::DetectionLoo loo;
+            const aar_dataset *d = mcm.dataset();
+            vector<int> fid, cid, mid;   // (ids of the detections before the drop: the data set is rebuilt by it)
+            for (int64_t o = 0; o < d->num_obs; o++) {
+                fid.push_back(d->frame_ids[d->obs_frame[o]]); cid.push_back(d->cam_ids[d->obs_cam[o]]); mid.push_back(d->marker_ids[d->obs_marker[o]]);
+            }
+            const int64_t dropped = mcm.reject_loo(f_max, &loo);
+            cout << "loo round " << round << ": largest F " << loo.report.max_f << " (f_max " << f_max << "), " << loo.report.undetermined << " undetermined, "
+                 << dropped << " of " << loo.F.size() << " detections rejected" << endl;
+            for (size_t o = 0; o < loo.keep.size(); o++)
+                if (!loo.keep[o])
+                    cout << "loo rejected: round " << round << " frame_id " << fid[o] << " cam_id " << cid[o] << " marker_id " << mid[o] << " F " << loo.F[o] << endl;
+            if (dropped == 0) break;
+            mcm.solve();
+        }
+    } catch (const exception &e) {
+        cerr << "leave-one-out rejection failed: " << e.what() << endl;
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[]) {
     if (argc >= 4 && string(argv[1]) == "--synth") return synth(atoi(argv[2]), argv[3]);
     if (argc < 3) return print_usage(argv[0]);
@@ -240,6 +269,10 @@ int main(int argc, char *argv[]) {
     // leverage is at least h_min are listed with their reprojection error
     bool leverage = false, leverage_set = false;
     double leverage_min = 0.0;
+    // nor these: -loo f_max writes final.loo.yaml (aar_problem_detection_loo); -reject-loo f_max mirrors -reject-outliers with
+    // the leave-one-out F, one detection per frame and round
+    double loo_f_max = 0.0, reject_loo_f = 0.0;
+    bool loo = false, reject_loo_on = false;
     bool residuals = false;    // nor these: -residuals writes final.residuals.yaml; -reject-outliers k drops detections above max(min_px, k median) and solves again
     double reject_k = 0.0, reject_min_px = 0.0;
     double threshold = 2.0;
@@ -312,7 +345,7 @@ int main(int argc, char *argv[]) {
     int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
     double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion, Leverage } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion, Leverage, Loo, RejectLoo } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -324,6 +357,8 @@ int main(int argc, char *argv[]) {
         else if (a == "-solver") arg_flag = Solver;
         else if (a == "-covariance") { covariance = true; arg_flag = NONE; }
         else if (a == "-leverage") { leverage = true; arg_flag = Leverage; }
+        else if (a == "-loo") { loo = true; arg_flag = Loo; }
+        else if (a == "-reject-loo") { reject_loo_on = true; arg_flag = RejectLoo; }
         else if (a == "-residuals") { residuals = true; arg_flag = NONE; }
         else if (a == "-reject-outliers") arg_flag = RejectK;
         else if (a == "-reject-min-px") arg_flag = RejectPx;
@@ -456,6 +491,13 @@ int main(int argc, char *argv[]) {
             leverage_set = true;
             arg_flag = NONE;
         }
+        else if (arg_flag == Loo || arg_flag == RejectLoo) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || a.empty() || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            (arg_flag == Loo ? loo_f_max : reject_loo_f) = v;
+            arg_flag = NONE;
+        }
         else if (arg_flag == RejectK || arg_flag == RejectPx) {
             const double v = stod(a);
             if (!(v > 0.0) && !(arg_flag == RejectPx && v == 0.0)) return print_usage(argv[0]);
@@ -473,6 +515,8 @@ int main(int argc, char *argv[]) {
     if (smooth && (!tracking_only || smooth_args != 2)) return print_usage(argv[0]);
     if (smooth_covariance && !smooth) return print_usage(argv[0]);
     if (leverage && !leverage_set) return print_usage(argv[0]);
+    if ((loo && !(loo_f_max > 0.0)) || (reject_loo_on && !(reject_loo_f > 0.0))) return print_usage(argv[0]);
+    if ((loo || reject_loo_on) && with_huber) return print_usage(argv[0]);   // (the Huber weights break the Gaussian model the statistic rests on)
     if (smooth_cv && (!smooth || smooth_cv_args != 2 || smooth_covariance || fit_sigmas || resample)) return print_usage(argv[0]);
     if (cv_covariance && (!smooth || !smooth_cv)) return print_usage(argv[0]);
     if (cv_fit_sigmas && (!smooth || !smooth_cv || live)) return print_usage(argv[0]);
@@ -673,6 +717,7 @@ int main(int argc, char *argv[]) {
             return 4;
         }
     }
+    if (reject_loo_on && reject_loo(mcm, reject_loo_f)) return 4;
     if (smooth) {
         try {
             mcm.track();
@@ -838,6 +883,19 @@ int main(int argc, char *argv[]) {
                  << " live unknowns), " << listed << " at " << leverage_min << " or above, written to " << lev_path << endl;
         } catch (const exception &e) {
             cerr << "leverage failed: " << e.what() << endl;
+            return 3;
+        }
+    }
+    if (loo) {
+        const string loo_path = folder_path + "/final.loo.yaml";
+        try {
+            const aar::MultiCamMapper::DetectionLoo lo = mcm.detection_loo(loo_f_max);
+            const aar::MultiCamMapper::ResidualReport rr = mcm.residual_report(nullptr);
+            if (!mcm.write_loo_file(loo_path, lo, rr.det_err)) throw runtime_error(aar_last_error());
+            cout << "leave-one-out: largest F " << lo.report.max_f << ", " << lo.report.rejected << " above " << loo_f_max << ", " << lo.report.undetermined
+                 << " undetermined of " << lo.F.size() << " detections, written to " << loo_path << endl;
+        } catch (const exception &e) {
+            cerr << "leave-one-out failed: " << e.what() << endl;
             return 3;
         }
     }

@@ -525,6 +525,96 @@ bool MultiCamMapper::write_leverage_file(const std::string &path, const Detectio
     return aar_leverage_write_yaml(path.c_str(), data_, lev.leverage.data(), det_err.empty() ? nullptr : det_err.data(), h_min, &lev.report) == AAR_OK;
 }
 
+MultiCamMapper::DetectionLoo MultiCamMapper::detection_loo(double f_max) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::detection_loo: no data set");
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    const size_t N = (size_t)data_->num_obs, n1 = std::max<size_t>(N, 1);
+    DetectionLoo out;
+    out.loo_resid.assign(8 * n1, NAN);
+    for (std::vector<double> *v : {&out.q, &out.F, &out.cook, &out.leverage, &out.margin}) v->assign(n1, NAN);
+    out.status.assign(n1, 0);
+    out.keep.assign(n1, 1);
+    out.report.struct_size = (uint32_t)sizeof out.report;
+    aar_loo_rule rule;
+    rule.struct_size = (uint32_t)sizeof rule;
+    rule.f_max = f_max;
+    std::vector<double> x = problem_vector();
+    if (aar_problem_detection_loo(problem_, x.data(), f_max > 0.0 ? &rule : nullptr, out.loo_resid.data(), out.q.data(), out.F.data(), out.cook.data(),
+                                  out.leverage.data(), out.margin.data(), out.status.data(), out.keep.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.loo_resid.resize(8 * N);
+    for (std::vector<double> *v : {&out.q, &out.F, &out.cook, &out.leverage, &out.margin}) v->resize(N);
+    out.status.resize(N);
+    out.keep.resize(N);
+    return out;
+}
+
+MultiCamMapper::GateResult MultiCamMapper::gate_detections(const std::vector<int> &cam_ids, const std::vector<int> &marker_ids,
+                                                           const std::vector<int> &frame_ids, const std::vector<float> &uv) {
+    if (!data_) throw std::runtime_error("MultiCamMapper::gate_detections: no data set");
+    const size_t Q = cam_ids.size();
+    if (Q != marker_ids.size() || Q != frame_ids.size() || uv.size() != 8 * Q)
+        throw std::invalid_argument("MultiCamMapper::gate_detections: the three id lists and uv / 8 differ in length");
+    auto index_of = [](const int32_t *ids, int n, int id, const char *what) -> int32_t {
+        const int32_t *e = ids + n, *p = std::lower_bound(ids, e, id);
+        if (p == e || *p != id) throw std::invalid_argument(std::string("MultiCamMapper: no ") + what + " with id " + std::to_string(id));
+        return (int32_t)(p - ids);
+    };
+    std::vector<int32_t> qc(Q), qm(Q), qf(Q);
+    for (size_t i = 0; i < Q; i++) {
+        qc[i] = index_of(data_->cam_ids, data_->num_cams, cam_ids[i], "camera");
+        qm[i] = index_of(data_->marker_ids, data_->num_markers, marker_ids[i], "marker");
+        qf[i] = index_of(data_->frame_ids, data_->num_frames, frame_ids[i], "frame");
+    }
+    if (ensure_problem()) throw std::runtime_error(aar_last_error());
+    GateResult out;
+    out.innovation.assign(8 * std::max<size_t>(Q, 1), NAN);
+    out.chi2.assign(std::max<size_t>(Q, 1), NAN);
+    out.status.assign(std::max<size_t>(Q, 1), 0);
+    out.report.struct_size = (uint32_t)sizeof out.report;
+    std::vector<double> x = problem_vector();
+    if (aar_problem_gate_detections(problem_, x.data(), (int64_t)Q, qc.data(), qm.data(), qf.data(), Q ? uv.data() : nullptr, out.innovation.data(),
+                                    out.chi2.data(), out.status.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.innovation.resize(8 * Q);
+    out.chi2.resize(Q);
+    out.status.resize(Q);
+    for (double &v : out.chi2) v /= out.report.sigma2;
+    return out;
+}
+
+int64_t MultiCamMapper::reject_loo(double f_max, DetectionLoo *out) {
+    DetectionLoo loo = detection_loo(f_max);
+    // of every frame only the detection with the largest F among those the rule rejects goes (the first of them on a tie)
+    std::vector<int64_t> worst((size_t)std::max(data_->num_frames, 1), -1);
+    for (size_t o = 0; o < loo.keep.size(); o++) {
+        if (loo.keep[o]) continue;
+        int64_t &w = worst[data_->obs_frame[o]];
+        if (w < 0 || loo.F[o] > loo.F[w]) w = (int64_t)o;
+    }
+    std::fill(loo.keep.begin(), loo.keep.end(), (uint8_t)1);
+    int64_t dropped = 0;
+    for (int64_t w : worst)
+        if (w >= 0) { loo.keep[w] = 0; dropped++; }
+    loo.report.rejected = dropped;
+    if (dropped > 0) {
+        aar_dataset *nd = nullptr;
+        if (aar_dataset_select_observations(data_, loo.keep.data(), &nd)) throw std::runtime_error(aar_last_error());
+        drop_problem();
+        aar_dataset_free(data_);
+        data_ = nd;
+        mats2eVec();
+    }
+    if (out) *out = std::move(loo);
+    return dropped;
+}
+
+bool MultiCamMapper::write_loo_file(const std::string &path, const DetectionLoo &loo, const std::vector<double> &det_err) {
+    if (!data_ || loo.F.size() != (size_t)data_->num_obs || (!det_err.empty() && det_err.size() != loo.F.size())) return false;
+    return aar_loo_write_yaml(path.c_str(), data_, loo.F.data(), loo.q.data(), loo.leverage.data(), det_err.empty() ? nullptr : det_err.data(),
+                              loo.status.data(), loo.keep.data(), &loo.report) == AAR_OK;
+}
+
 void MultiCamMapper::error_function(const eVector &input, eVector &error) {
     if (probed(detail::EVAL_ERROR_FUNCTION)) return;
     if (!data_) throw std::runtime_error("MultiCamMapper::error_function: no data set");

@@ -586,6 +586,32 @@ class MultiCamMapper {
     // YAML, aar_leverage_write_yaml: det_err as residual_report().det_err, or empty
     bool write_leverage_file(const std::string &path, const DetectionLeverage &lev, double h_min, const std::vector<double> &det_err = {});
 
+    // EXTENSION, no counterpart in the reference: the leave-one-out residual (I - C_i)^-1 r_i of every detection of the
+    // data set in its order, the cost q its deletion removes (UNSCALED), the externally studentized F, Cook's distance, leverage, margin,
+    // status (AAR_PREDICT_UNDETERMINED: NaN) and keep (0 where F > f_max; f_max <= 0: no rule) -- aar_problem_detection_loo at io_vec's poses.
+    // Throws std::runtime_error on failure (a mapper set_with_huber: the statistic rests on the Gaussian model).
+    struct DetectionLoo {
+        aar_loo_report report{};
+        std::vector<double> loo_resid, q, F, cook, leverage, margin;
+        std::vector<uint8_t> status, keep;
+    };
+    DetectionLoo detection_loo(double f_max = 0.0);
+    // candidate detections the bundle has not used, by ID as predict_corners; uv [Q][8] observed corners in undistorted pixels.  innovation
+    // [Q][8] = observed - predicted, chi2 [Q] = e^T (I + C)^-1 e / sigma2 (ALREADY divided by sigma2: chi-square with 8 degrees of freedom)
+    struct GateResult {
+        aar_predict_report report{};
+        std::vector<double> innovation, chi2;
+        std::vector<uint8_t> status;
+    };
+    GateResult gate_detections(const std::vector<int> &cam_ids, const std::vector<int> &marker_ids, const std::vector<int> &frame_ids,
+                               const std::vector<float> &uv);
+    // drops, of every frame, the ONE detection with the largest F above f_max (a single-deletion statistic licenses no more) and rebuilds the
+    // device problem with the current solution as its start, as reject_outliers does; returns how many were dropped, the report in *out
+    // with keep = what was actually dropped
+    int64_t reject_loo(double f_max, DetectionLoo *out = nullptr);
+    // YAML, aar_loo_write_yaml: det_err as residual_report().det_err, or empty
+    bool write_loo_file(const std::string &path, const DetectionLoo &loo, const std::vector<double> &det_err = {});
+
     // EXTENSION, no counterpart in the reference: per-entity fixing and pose priors (aar_problem_constraints), by ID.
     // Fixed cameras / markers stay exactly where they are; a prior pulls a camera / marker toward a 4x4 transform T (the convention of
     // get_transforms_to_root_cam / _marker) with a 6x6 information matrix over (rx ry rz tx ty tz).  They take effect when the device problem

@@ -390,6 +390,42 @@ int aar_leverage_write_yaml(const char *path, const aar_dataset *d, const double
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
 }
 
+int aar_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage, const double *det_err,
+                       const uint8_t *status, const uint8_t *keep, const aar_loo_report *rep) {
+    if (!path || !d || !rep || ((!F || !status || !keep) && d->num_obs > 0)) return set_error(AAR_ERR_INVALID, "aar_loo_write_yaml: null argument");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "sigma2: %s\ndof: %lld\nnum_live_vars: %lld\nf_max: %s\nmax_f: %s\nundetermined: %lld\nrejected: %lld\n", fs_double_nf(rep->predict.sigma2).c_str(),
+            (long long)rep->dof, (long long)rep->predict.num_live_vars, fs_double_nf(rep->f_max).c_str(), fs_double_nf(rep->max_f).c_str(),
+            (long long)rep->undetermined, (long long)rep->rejected);
+    // per entity {detections, largest F that is a number, rejected}, in detection order
+    std::vector<double> cs(3 * (size_t)d->num_cams, 0.0), ms(3 * (size_t)d->num_markers, 0.0);
+    for (int64_t o = 0; o < d->num_obs; o++)
+        for (double *e : {cs.data() + 3LL * d->obs_cam[o], ms.data() + 3LL * d->obs_marker[o]}) {
+            e[0] += 1.0;
+            if (F[o] > e[1]) e[1] = F[o];
+            if (!keep[o]) e[2] += 1.0;
+        }
+    auto entity = [&](const char *key, int id, const double *e) {
+        fprintf(f, "   - { %s:%d, detections:%lld, max_f: %s, rejected:%lld }\n", key, id, (long long)e[0], fs_double_nf(e[1]).c_str(), (long long)e[2]);
+    };
+    fprintf(f, "cameras:\n");
+    for (int c = 0; c < d->num_cams; c++) entity("cam_id", d->cam_ids[c], cs.data() + 3LL * c);
+    fprintf(f, "markers:\n");
+    for (int m = 0; m < d->num_markers; m++) entity("marker_id", d->marker_ids[m], ms.data() + 3LL * m);
+    fprintf(f, "listed_detections:\n");
+    for (int64_t o = 0; o < d->num_obs; o++)
+        if (!keep[o] || (status[o] & AAR_PREDICT_UNDETERMINED))
+            fprintf(f, "   - { frame_id:%d, cam_id:%d, marker_id:%d, F: %s, q: %s, leverage: %s, error: %s }\n", d->frame_ids[d->obs_frame[o]],
+                    d->cam_ids[d->obs_cam[o]], d->marker_ids[d->obs_marker[o]], fs_double_nf(F[o]).c_str(), fs_double_nf(q ? q[o] : NAN).c_str(),
+                    fs_double_nf(leverage ? leverage[o] : NAN).c_str(),
+                    fs_double_nf(det_err ? det_err[o] : NAN).c_str());
+    const bool good = !ferror(f);
+    fclose(f);
+    return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
+}
+
 int aar_detections_write(const char *path, const aar_dataset *d) {
     if (!path || !d) return set_error(AAR_ERR_INVALID, "aar_detections_write: null argument");
     FILE *f = fopen(path, "wb");

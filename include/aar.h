@@ -473,6 +473,60 @@ int aar_problem_detection_leverage(aar_problem *, const double *x_full, double *
 int aar_leverage_write_yaml(const char *path, const aar_dataset *d, const double *leverage, const double *det_err, double h_min,
                             const aar_predict_report *report);
 
+/* Leave-one-out residuals of every detection, and the gate of candidate detections (no counterpart in the reference; DESIGN.md section
+ * 37).  With r_i = observed - u_i (8; the stored float corners widened to double against the projection at x_full, whatever the problem's
+ * residual mode) and C_i the 8 x 8 block of aar_problem_detection_leverage, per detection in reference order:
+ *   loo_resid[i] = (I - C_i)^-1 r_i     the error detection i would show against a bundle that had not used it
+ *   q[i]         = r_i^T (I - C_i)^-1 r_i   the cost that deleting it would remove (unscaled, pixels squared)
+ *   F[i]         = (q_i / 8) / ((sum_sq - q_i) / (nu - 8))   the externally studentized statistic, F(8, nu - 8) under the Gaussian model;
+ *                  +inf where the denominator is <= 0, NaN where nu <= 8
+ *   cook[i]      = w^T C_i w / (num_live_vars sigma2), w = loo_resid[i]   Cook's distance
+ *   leverage[i]  = tr(C_i), the bits of aar_problem_detection_leverage
+ *   margin[i]    = the smallest pivot met in the Cholesky factorisation of I - C_i (in (0, 1] for a determined detection)
+ *   keep[i]      = 0 iff a rule is given, status[i] == 0 and F[i] > rule->f_max; 1 otherwise
+ * sum_sq and nu = num_residuals - num_vars are those of the report (predict.sum_sq, dof).  ON A PROBLEM WITH PRIORS sum_sq is what the
+ * covariance chain sums: the unweighted squared reprojection residuals PLUS the pose priors' and pair priors' costs, while num_residuals
+ * counts the 8 N corner coordinates only and num_vars every z column; F then is the statistic of that convention, not an exact F variate.
+ * status[i] carries the bits of aar_problem_predict_corners (NaN outputs) and
+ *   bit 2 (AAR_PREDICT_UNDETERMINED): a pivot of I - C_i is <= 1e-6 or not finite -- some direction of the detection's corners is
+ *                                     determined by nothing but itself (its frame or its marker has no other detection), so a fit
+ *                                     without it does not exist: loo_resid, q, F and cook are NaN, leverage and margin are written, keep = 1.
+ * The reading "residual against a fit without the detection" holds to first order at a converged solution (one Gauss-Newton step of the
+ * reduced problem from x_full); the quantities themselves are defined as written at any x_full.
+ * aar_problem_gate_detections asks the opposite question for CANDIDATE detections the bundle has not used: for query (c, m, f) with
+ * observed corners uv_obs (undistorted pixels), innovation = uv_obs - u_q and m2 = e^T (I + C_q)^-1 e, UNSCALED: m2 / sigma2 is chi-square
+ * with 8 degrees of freedom under the model.  status as aar_problem_predict_corners (the innovation is still written where only bit 1 is
+ * set; m2 is NaN).  The report's leverage_sum is 0.  Queries are validated by aar_predict_query_validate; uv_obs is required when n_query > 0.
+ * Both calls run the covariance chain once, leave the problem as aar_problem_covariance does, and write the caller's arrays only after
+ * everything succeeded.  Every output array may be NULL.  Refusals, nothing written: all of aar_problem_detection_leverage's;
+ * detection_loo on a problem created with_huber is AAR_ERR_UNSUPPORTED (the weights break the Gaussian model the statistic rests on); a
+ * rule whose f_max is not positive and finite is AAR_ERR_INVALID.
+ *   report.predict: as aar_problem_detection_leverage fills it;  dof = nu;  undetermined / rejected: detections with bit 2 / keep = 0;
+ *   f_max: the rule's (+inf without one);  max_f, argmax_f: the largest F that is not NaN and its detection (NaN, -1 when there is none) */
+enum { AAR_PREDICT_UNDETERMINED = 4 };
+typedef struct aar_loo_rule { uint32_t struct_size; double f_max; } aar_loo_rule;   /* f_max > 0, finite */
+typedef struct aar_loo_report {
+    uint32_t struct_size;
+    aar_predict_report predict;
+    int64_t dof;
+    int64_t undetermined, rejected;
+    double f_max, max_f;
+    int64_t argmax_f;
+} aar_loo_report;
+int aar_problem_detection_loo(aar_problem *, const double *x_full, const aar_loo_rule *rule /* may be NULL */, double *loo_resid /* [N][8] */,
+                              double *q /* [N] */, double *F /* [N] */, double *cook /* [N] */, double *leverage /* [N] */,
+                              double *margin /* [N] */, uint8_t *status /* [N] */, uint8_t *keep /* [N] */, aar_loo_report *report);
+int aar_problem_gate_detections(aar_problem *, const double *x_full, int64_t n_query, const int32_t *q_cam, const int32_t *q_marker,
+                                const int32_t *q_frame, const float *uv_obs /* [n][8] */, double *innovation /* [n][8] */,
+                                double *m2 /* [n], UNSCALED: chi2_8 = m2 / sigma2 */, uint8_t *status, aar_predict_report *report);
+/* YAML (the dialect of aar_leverage_write_yaml) of a leave-one-out report of a single-GPU problem created from d: the report's scalars
+ * (sigma2, dof, num_live_vars, f_max, max_f, undetermined, rejected); per camera id and marker id {detections, max_f, rejected} over its
+ * detections (max_f over the F that are not NaN, 0 when there is none; rejected = keep is 0); the detections with keep = 0 or an
+ * UNDETERMINED status as (frame id, camera id, marker id, F, q, leverage, error).  F, status and keep are required when d has detections;
+ * q, leverage and det_err (as aar_problem_residual_report gives it) may be NULL (.nan).  Host code. */
+int aar_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage, const double *det_err,
+                       const uint8_t *status, const uint8_t *keep, const aar_loo_report *report);
+
 /* Per-entity fixing and pose priors (no counterpart in the reference).  Cameras and markers are named by INDEX
  * (problem indices as in aar_problem_desc, not ids).
  *  Fixed entities: fixed_cams / fixed_markers are held where they are, exactly as the roots are.  The layout of z does not change
