@@ -70,24 +70,39 @@ __device__ __forceinline__ float d_ippe_error(float hf, const float *q, const do
 }
 
 // IPPERot2vec (ippe.cpp:323-345), cv::Rodrigues back to a matrix and the CV_32F conversion of getRTMatrix (:40-93)
+//
+// Guard (a departure from ippe.cpp, as in oracle/init_oracle.cpp): within delta0 = 1e-3 rad of pi the matrix -> vector -> matrix round
+// trip is skipped and R is rounded to float as it stands.  IPPERot2vec takes w = acos((trace - 1) / 2) and the axis from
+// w / (2 sin w) (R - R^T); with delta = pi - w the rounding of the trace (~4e-16) is an angle error of about pi * 4e-16 / delta^2, one
+// float ulp at delta ~ 1e-4 and garbage (often the identity) below 1e-6, and an argument rounded below -1 is a NaN.
+// IPPE_PI_GUARD_C0 = delta0^2 / 2 = 1 - cos(delta0): at delta0 the round trip's error, pi * 4e-16 / 1e-6 ~ 1.3e-9, is still 100 times below
+// a float ulp (1.2e-7), so the stored floats do not jump at the seam, and R's own departure from a rotation is ~1e-15.  The test is on the
+// trace, negated (a NaN or an argument below -1 takes the guard); no libm call decides it.
+#define IPPE_PI_GUARD_C0 5e-7
 __device__ __forceinline__ void d_store_pose(const double *R, const double *t, double *out) {
-    const double w = acos((R[0] + R[4] + R[8] - 1.0) / 2.0);
-    double rv0 = 0, rv1 = 0, rv2 = 0;
-    if (!(w < DBL_EPSILON)) {
-        const double d = 1 / (2 * sin(w)) * w;
-        rv0 = d * (R[7] - R[5]); rv1 = d * (R[2] - R[6]); rv2 = d * (R[3] - R[1]);
-    }
+    const double ca = (R[0] + R[4] + R[8] - 1.0) / 2.0;
     double M[9];
-    const double th = sqrt(rv0 * rv0 + rv1 * rv1 + rv2 * rv2);
-    if (th < DBL_EPSILON) {
+    if (!(ca > -1.0 + IPPE_PI_GUARD_C0)) {
 #pragma unroll
-        for (int i = 0; i < 9; i++) M[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        for (int i = 0; i < 9; i++) M[i] = R[i];
     } else {
-        const double c = cos(th), s = sin(th), c1 = 1. - c, ith = 1. / th;
-        const double x = rv0 * ith, y = rv1 * ith, z = rv2 * ith;
-        M[0] = c + c1 * x * x;     M[1] = c1 * x * y - s * z; M[2] = c1 * x * z + s * y;
-        M[3] = c1 * x * y + s * z; M[4] = c + c1 * y * y;     M[5] = c1 * y * z - s * x;
-        M[6] = c1 * x * z - s * y; M[7] = c1 * y * z + s * x; M[8] = c + c1 * z * z;
+        const double w = acos(ca);
+        double rv0 = 0, rv1 = 0, rv2 = 0;
+        if (!(w < DBL_EPSILON)) {
+            const double d = 1 / (2 * sin(w)) * w;
+            rv0 = d * (R[7] - R[5]); rv1 = d * (R[2] - R[6]); rv2 = d * (R[3] - R[1]);
+        }
+        const double th = sqrt(rv0 * rv0 + rv1 * rv1 + rv2 * rv2);
+        if (th < DBL_EPSILON) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) M[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        } else {
+            const double c = cos(th), s = sin(th), c1 = 1. - c, ith = 1. / th;
+            const double x = rv0 * ith, y = rv1 * ith, z = rv2 * ith;
+            M[0] = c + c1 * x * x;     M[1] = c1 * x * y - s * z; M[2] = c1 * x * z + s * y;
+            M[3] = c1 * x * y + s * z; M[4] = c + c1 * y * y;     M[5] = c1 * y * z - s * x;
+            M[6] = c1 * x * z - s * y; M[7] = c1 * y * z + s * x; M[8] = c + c1 * z * z;
+        }
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -155,7 +170,8 @@ __device__ __forceinline__ void d_ippe_square(float hf, const float *q, double *
         const double p = H[2], qq = H[5];
         const double s = sqrt(p * p + qq * qq + 1), t = sqrt(p * p + qq * qq);
         const double ct = 1 / s, st = sqrt(1 - 1 / (s * s));
-        const double kx = p / t, ky = qq / t;
+        // guard (a departure from ippe.cpp, which divides 0 / 0 here): the centre maps exactly onto the principal point, Rv = I
+        const double kx = t == 0 ? 0.0 : p / t, ky = t == 0 ? 0.0 : qq / t;
         const double Rv[9] = {(ct - 1) * kx * kx + 1, kx * ky * (ct - 1),     kx * st,
                               kx * ky * (ct - 1),     (ct - 1) * ky * ky + 1, ky * st,
                               -kx * st,               -ky * st,               (ct - 1) * (kx * kx + ky * ky) + 1};
@@ -167,8 +183,11 @@ __device__ __forceinline__ void d_ippe_square(float hf, const float *q, double *
         const double n00 = a00 * a00 + a01 * a01, n01 = a00 * a10 + a01 * a11, n11 = a10 * a10 + a11 * a11;
         const double gamma = sqrt(0.5 * (n00 + n11 + sqrt((n00 - n11) * (n00 - n11) + 4.0 * n01 * n01)));
         const double r00 = a00 / gamma, r01 = a01 / gamma, r10 = a10 / gamma, r11 = a11 / gamma;
-        const double b0 = sqrt(-r00 * r00 - r10 * r10 + 1);
-        double b1 = sqrt(-r01 * r01 - r11 * r11 + 1);
+        // guard (a departure from ippe.cpp): a column of A / gamma that is a unit vector leaves a radicand of about -1e-16, clamped at 0
+        // (a NaN stays a NaN)
+        const double g0 = -r00 * r00 - r10 * r10 + 1, g1 = -r01 * r01 - r11 * r11 + 1;
+        const double b0 = sqrt(g0 < 0 ? 0.0 : g0);
+        double b1 = sqrt(g1 < 0 ? 0.0 : g1);
         if (-r00 * r01 - r10 * r11 < 0) b1 = -b1;
         const double Qa[9] = {r00, r01, b1 * r10 - b0 * r11, r10, r11, b0 * r01 - b1 * r00, b0, b1, r00 * r11 - r01 * r10};
         const double Qb[9] = {r00, r01, b0 * r11 - b1 * r10, r10, r11, b1 * r00 - b0 * r01, -b0, -b1, r00 * r11 - r01 * r10};

@@ -112,7 +112,8 @@ void ippe_rotations(const double J[4], double p, double q, double Ra[9], double 
     // Rv: rotation that takes the optical axis onto the ray through (p,q)
     const double s = std::sqrt(p * p + q * q + 1), t = std::sqrt(p * p + q * q);
     const double ct = 1 / s, st = std::sqrt(1 - 1 / (s * s));
-    const double kx = p / t, ky = q / t;
+    // guard (departure from ippe.cpp, which divides 0 / 0 here): the centre maps exactly onto the principal point, Rv = I
+    const double kx = t == 0 ? 0.0 : p / t, ky = t == 0 ? 0.0 : q / t;
     const double Rv[9] = {(ct - 1) * kx * kx + 1, kx * ky * (ct - 1),     kx * st,
                           kx * ky * (ct - 1),     (ct - 1) * ky * ky + 1, ky * st,
                           -kx * st,               -ky * st,               (ct - 1) * (kx * kx + ky * ky) + 1};
@@ -126,8 +127,10 @@ void ippe_rotations(const double J[4], double p, double q, double Ra[9], double 
     const double n00 = a00 * a00 + a01 * a01, n01 = a00 * a10 + a01 * a11, n11 = a10 * a10 + a11 * a11;
     const double gamma = std::sqrt(0.5 * (n00 + n11 + std::sqrt((n00 - n11) * (n00 - n11) + 4.0 * n01 * n01)));
     const double r00 = a00 / gamma, r01 = a01 / gamma, r10 = a10 / gamma, r11 = a11 / gamma;
-    // third row completes unit columns; the sign of b1 makes the columns orthogonal
-    double b0 = std::sqrt(-r00 * r00 - r10 * r10 + 1), b1 = std::sqrt(-r01 * r01 - r11 * r11 + 1);
+    // third row completes unit columns; the sign of b1 makes the columns orthogonal.  guard (departure from ippe.cpp): a column of
+    // A / gamma that is a unit vector leaves a radicand of about -1e-16, clamped at 0 (a NaN stays a NaN)
+    const double g0 = -r00 * r00 - r10 * r10 + 1, g1 = -r01 * r01 - r11 * r11 + 1;
+    double b0 = std::sqrt(g0 < 0 ? 0.0 : g0), b1 = std::sqrt(g1 < 0 ? 0.0 : g1);
     if (-r00 * r01 - r10 * r11 < 0) b1 = -b1;
     for (int sol = 0; sol < 2; sol++) {
         const double c0 = sol ? -b0 : b0, c1 = sol ? -b1 : b1;
@@ -174,17 +177,26 @@ float ippe_reproj_error(const double R[9], const double t[3], const float model[
     return err;
 }
 
-// ippe.cpp:323-345 then getRTMatrix's cv::Rodrigues + CV_32F conversion (ippe.cpp:40-93)
-void rt_matrix_f32(const double R[9], const double t[3], double T[16]) {
-    const double tr = R[0] + R[4] + R[8];
-    const double w = std::acos((tr - 1.0) / 2.0);
+// IPPERot2vec + getRTMatrix's cv::Rodrigues + CV_32F conversion (ippe.cpp:40-93, :323-345)
+//
+// guard (departure from ippe.cpp): within delta0 = 1e-3 rad of pi the matrix -> vector -> matrix round trip is skipped and R is rounded
+// to float as it stands.  IPPERot2vec takes w = acos((trace - 1) / 2) and the axis from w / (2 sin w) (R - R^T); with delta = pi - w the
+// rounding of the trace (~4e-16) is an angle error of about pi * 4e-16 / delta^2, one float ulp at delta ~ 1e-4 and garbage (often the
+// identity) below 1e-6, and an argument rounded below -1 is a NaN.  PI_GUARD_C0 = delta0^2 / 2 = 1 - cos(delta0): at delta0 the round trip's
+// error, pi * 4e-16 / 1e-6 ~ 1.3e-9, is still 100 times below a float ulp (1.2e-7), so the stored floats do not jump at the seam, and R's
+// own departure from a rotation is ~1e-15.  The test is on the trace, negated (a NaN or an argument below -1 takes the guard); no libm
+// call decides it.
+const double PI_GUARD_C0 = 5e-7;
+
+// IPPERot2vec (ippe.cpp:323-345), then cv::Rodrigues back to a matrix
+void rot_round_trip(const double R[9], double ca, double M[9]) {
+    const double w = std::acos(ca);
     double rv[3] = {0, 0, 0};
     if (!(w < std::numeric_limits<double>::epsilon())) {
         const double d = 1 / (2 * std::sin(w)) * w;
         rv[0] = d * (R[7] - R[5]); rv[1] = d * (R[2] - R[6]); rv[2] = d * (R[3] - R[1]);
     }
     // cv::Rodrigues, vector -> matrix
-    double M[9];
     const double th = std::sqrt(rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2]);
     if (th < DBL_EPSILON) {
         for (int i = 0; i < 9; i++) M[i] = (i % 4 == 0) ? 1.0 : 0.0;
@@ -195,6 +207,16 @@ void rt_matrix_f32(const double R[9], const double t[3], double T[16]) {
         M[3] = c1 * x * y + s * z; M[4] = c + c1 * y * y;     M[5] = c1 * y * z - s * x;
         M[6] = c1 * x * z - s * y; M[7] = c1 * y * z + s * x; M[8] = c + c1 * z * z;
     }
+}
+
+void rt_matrix_f32(const double R[9], const double t[3], double T[16]) {
+    const double tr = R[0] + R[4] + R[8];
+    const double ca = (tr - 1.0) / 2.0;
+    double M[9];
+    if (!(ca > -1.0 + PI_GUARD_C0))
+        for (int i = 0; i < 9; i++) M[i] = R[i];
+    else
+        rot_round_trip(R, ca, M);
     for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) T[i * 4 + j] = (double)(float)M[i * 3 + j];
