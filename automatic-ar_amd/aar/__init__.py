@@ -45,6 +45,8 @@ SYMBOLS = [
     "aar_smooth_fit_default_params", "aar_smooth_fit_params_validate", "aar_track_smooth_fit", "aar_track_smooth_fit_terms", "aar_track_smooth_fit2", "aar_track_smooth_fit_terms2",
     "aar_smooth_query_validate", "aar_track_smooth_query", "aar_track_smooth_query2", "aar_track_smooth_query2_step", "aar_track_smooth_lag3",
     "aar_smooth_relative_validate", "aar_track_smooth_relative",
+    "aar_track_smooth_detection_leverage", "aar_track_smooth_detection_loo", "aar_track_smooth_predict_corners",
+    "aar_track_smooth_gate_detections", "aar_smooth_loo_write_yaml",
     "aar_tracker_default_params", "aar_tracker_params_validate", "aar_tracker_create", "aar_tracker_push", "aar_tracker_window",
     "aar_tracker_reset", "aar_tracker_destroy",
     "aar_tracker_default_detection_params", "aar_tracker_detection_params_validate", "aar_tracker_enable_detections",
@@ -285,6 +287,20 @@ class CSmoothRelativeReport(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("data_cost", C.c_double),
                 ("prior_cost", C.c_double), ("sigma2", C.c_double), ("num_pairs", C.c_int32), ("num_direct", C.c_int32),
                 ("num_chained", C.c_int32), ("max_lag", C.c_int32), ("launches", C.c_int32), ("seconds", C.c_double)]
+
+
+class CSmoothPredictReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("data_cost", C.c_double),
+                ("prior_cost", C.c_double), ("sigma2", C.c_double), ("num_queries", C.c_int64), ("behind", C.c_int64),
+                ("leverage_sum", C.c_double), ("num_inside", C.c_int32), ("num_on_frame", C.c_int32), ("num_outside", C.c_int32),
+                ("launches", C.c_int32), ("seconds", C.c_double), ("kernel_seconds", C.c_double)]
+
+
+class CSmoothLooReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("num_residuals", C.c_int64), ("num_vars", C.c_int64), ("data_cost", C.c_double),
+                ("prior_cost", C.c_double), ("sigma2", C.c_double), ("dof", C.c_int64), ("behind", C.c_int64), ("undetermined", C.c_int64),
+                ("rejected", C.c_int64), ("f_max", C.c_double), ("max_f", C.c_double), ("argmax_f", C.c_int64), ("leverage_sum", C.c_double),
+                ("launches", C.c_int32), ("seconds", C.c_double), ("kernel_seconds", C.c_double)]
 
 
 class SmoothParams:
@@ -607,6 +623,14 @@ def lib():
     L.aar_smooth_relative_validate.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.aar_track_smooth_relative.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, dp,
                                             C.POINTER(CSmoothRelativeReport)]
+    L.aar_track_smooth_detection_leverage.argtypes = [C.c_void_p, dp, C.c_void_p, dp, dp, C.POINTER(CSmoothPredictReport)]
+    L.aar_track_smooth_detection_loo.argtypes = [C.c_void_p, dp, C.c_void_p, C.POINTER(CLooRule), dp, dp, dp, dp, dp, dp, u8p, u8p,
+                                                 C.POINTER(CSmoothLooReport)]
+    L.aar_track_smooth_predict_corners.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, ip32, ip32, dp, dp, dp, u8p, ip32,
+                                                   C.POINTER(CSmoothPredictReport)]
+    L.aar_track_smooth_gate_detections.argtypes = [C.c_void_p, dp, C.c_void_p, C.c_int64, ip32, ip32, dp, C.POINTER(C.c_float), dp, dp, u8p, ip32,
+                                                   C.POINTER(CSmoothPredictReport)]
+    L.aar_smooth_loo_write_yaml.argtypes = [C.c_char_p, C.POINTER(CDataset), dp, dp, dp, dp, u8p, u8p, C.POINTER(CSmoothLooReport)]
     L.aar_smooth_fit_default_params.argtypes = [C.POINTER(CSmoothFitParams)]
     L.aar_smooth_fit_default_params.restype = None
     L.aar_smooth_fit_params_validate.argtypes = [C.POINTER(CSmoothFitParams)]
@@ -1189,6 +1213,21 @@ def loo_write_yaml(path, ds, loo, det_err=None):
     e = None if det_err is None else np.ascontiguousarray(det_err, dtype=np.float64)
     _check(lib().aar_loo_write_yaml(path.encode(), C.byref(c), _dptr(F), _dptr(q), _dptr(lev), _dptr(e) if e is not None else None, _u8ptr(st),
                                     _u8ptr(keep), C.byref(r)))
+
+
+def smooth_loo_write_yaml(path, ds, loo, det_err=None):
+    """aar_smooth_loo_write_yaml: loo as Problem.track_smooth_detection_loo returns it for a (single-GPU) problem created from ds; det_err as
+    Problem.residual_report(x).det_err, or None"""
+    c = ds.as_c()
+    r = CSmoothLooReport()
+    r.struct_size = C.sizeof(CSmoothLooReport)
+    for name, _ in CSmoothLooReport._fields_[1:]:
+        setattr(r, name, loo.report[name])
+    F, q, lev = (np.ascontiguousarray(getattr(loo, k), dtype=np.float64) for k in ("F", "q", "leverage"))
+    st, keep = (np.ascontiguousarray(getattr(loo, k), dtype=np.uint8) for k in ("status", "keep"))
+    e = None if det_err is None else np.ascontiguousarray(det_err, dtype=np.float64)
+    _check(lib().aar_smooth_loo_write_yaml(path.encode(), C.byref(c), _dptr(F), _dptr(q), _dptr(lev), _dptr(e) if e is not None else None,
+                                           _u8ptr(st), _u8ptr(keep), C.byref(r)))
 
 
 def leverage_write_yaml(path, ds, leverage, report, h_min=0.0, det_err=None):
@@ -2076,6 +2115,87 @@ class Problem:
                                                _dptr(rc) if covariance else None, C.byref(rep)))
         report = {k: getattr(rep, k) for k, _ in CSmoothRelativeReport._fields_ if k != "struct_size"}
         return cc[:Q] if cross else None, rel[:Q] if motion else None, rc[:Q] if covariance else None, report
+
+    def track_smooth_detection_leverage(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0,
+                                        sigma_trans0=0.0, rows=False):
+        """aar_track_smooth_detection_leverage, either model: (leverage [local_obs] = tr(C_i) with C_i = G_i (H^-1)_ff G_i^T of the smoothed
+        track, row_leverage [local_obs, 8] = diag(C_i) or None, report dict).  UNSCALED, reference detection order."""
+        x, _, sp, rep = self._smooth_call(x_full, (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0),
+                                          CSmoothPredictReport)
+        n = self.local_obs
+        lv = np.full(max(n, 1), np.nan)
+        rw = np.full((max(n, 1), 8), np.nan) if rows else None
+        _check(lib().aar_track_smooth_detection_leverage(self.handle, _dptr(x), C.byref(sp.c), _dptr(lv), _dptr(rw) if rows else None, C.byref(rep)))
+        return lv[:n], (rw[:n] if rows else None), self._report(rep)
+
+    def track_smooth_detection_loo(self, x_full, sigma_rot, sigma_trans, frame_time=None, rel_motion=None, model=None, sigma_rot0=0.0,
+                                   sigma_trans0=0.0, f_max=None):
+        """aar_track_smooth_detection_loo, either model, with the rule F > f_max when f_max is given.  Returns a DetectionLoo: loo_resid
+        [local_obs, 8], q, F, cook, leverage, margin [local_obs], status, keep [local_obs] (uint8) and report: the aar_smooth_loo_report
+        fields as a dict.  q is UNSCALED: q / report["sigma2"] is the chi-square."""
+        x, _, sp, rep = self._smooth_call(x_full, (sigma_rot, sigma_trans, frame_time, rel_motion, None, model, sigma_rot0, sigma_trans0),
+                                          CSmoothLooReport)
+        n = self.local_obs
+        m = max(n, 1)
+        w = np.full((m, 8), np.nan)
+        q, F, cook, lev, margin = (np.full(m, np.nan) for _ in range(5))
+        st, keep = np.zeros(m, dtype=np.uint8), np.ones(m, dtype=np.uint8)
+        rule = None
+        if f_max is not None:
+            rule = CLooRule()
+            rule.struct_size = C.sizeof(CLooRule)
+            rule.f_max = float(f_max)
+        _check(lib().aar_track_smooth_detection_loo(self.handle, _dptr(x), C.byref(sp.c), C.byref(rule) if rule is not None else None, _dptr(w),
+                                                    _dptr(q), _dptr(F), _dptr(cook), _dptr(lev), _dptr(margin), _u8ptr(st), _u8ptr(keep),
+                                                    C.byref(rep)))
+        return DetectionLoo(loo_resid=w[:n], q=q[:n], F=F[:n], cook=cook[:n], leverage=lev[:n], margin=margin[:n], status=st[:n], keep=keep[:n],
+                            report=self._report(rep))
+
+    @staticmethod
+    def _time_queries(cams, markers, times):
+        qc = np.ascontiguousarray(np.asarray(cams, dtype=np.int64).reshape(-1), dtype=np.int32)
+        qm = np.ascontiguousarray(np.asarray(markers, dtype=np.int64).reshape(-1), dtype=np.int32)
+        qt = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        if not len(qc) == len(qm) == len(qt):
+            raise ValueError("time queries: %d cameras, %d markers, %d times" % (len(qc), len(qm), len(qt)))
+        return qc, qm, qt
+
+    def track_smooth_predict_corners(self, x_full, sigma_rot, sigma_trans, cams, markers, times, frame_time=None, model=None, sigma_rot0=0.0,
+                                     sigma_trans0=0.0, covariance=True):
+        """aar_track_smooth_predict_corners, either model: the corners of (camera index, marker index) at the smoothed track's pose at a
+        TIME.  Returns (uv [Q, 4, 2], cov [Q, 8, 8] UNSCALED or None with covariance=False, status [Q], segment [Q], report dict).  A
+        corner's covariance is report["sigma2"] * cov; the search window of a new detection is report["sigma2"] * (cov + I)."""
+        x, _, sp, rep = self._smooth_call(x_full, (sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0),
+                                          CSmoothPredictReport)
+        qc, qm, qt = self._time_queries(cams, markers, times)
+        n = len(qc)
+        uv = np.full((max(n, 1), 8), np.nan)
+        cov = np.full((max(n, 1), 64), np.nan) if covariance else None
+        st, seg = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().aar_track_smooth_predict_corners(self.handle, _dptr(x), C.byref(sp.c), n, _i32ptr(qc), _i32ptr(qm), _dptr(qt) if n else None,
+                                                      _dptr(uv), _dptr(cov) if covariance else None, _u8ptr(st),
+                                                      seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        return uv[:n].reshape(n, 4, 2), (cov[:n].reshape(n, 8, 8) if covariance else None), st[:n], seg[:n], self._report(rep)
+
+    def track_smooth_gate_detections(self, x_full, sigma_rot, sigma_trans, cams, markers, times, uv_obs, frame_time=None, model=None,
+                                     sigma_rot0=0.0, sigma_trans0=0.0):
+        """aar_track_smooth_gate_detections, either model: candidate detections (camera index, marker index, time) with observed corners
+        uv_obs [Q, 4, 2] or [Q, 8] (stored as float32).  Returns (innovation [Q, 8] = uv_obs - predicted, m2 [Q] = e^T (I + C)^-1 e UNSCALED
+        -- m2 / report["sigma2"] is chi-square with 8 degrees of freedom --, status [Q], segment [Q], report dict)."""
+        x, _, sp, rep = self._smooth_call(x_full, (sigma_rot, sigma_trans, frame_time, None, None, model, sigma_rot0, sigma_trans0),
+                                          CSmoothPredictReport)
+        qc, qm, qt = self._time_queries(cams, markers, times)
+        n = len(qc)
+        uv = np.ascontiguousarray(np.asarray(uv_obs, dtype=np.float32).reshape(-1, 8))
+        if len(uv) != n:
+            raise ValueError("track_smooth_gate_detections: %d queries, %d sets of corners" % (n, len(uv)))
+        inn = np.full((max(n, 1), 8), np.nan)
+        m2 = np.full(max(n, 1), np.nan)
+        st, seg = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.int32)
+        _check(lib().aar_track_smooth_gate_detections(self.handle, _dptr(x), C.byref(sp.c), n, _i32ptr(qc), _i32ptr(qm), _dptr(qt) if n else None,
+                                                      uv.ctypes.data_as(C.POINTER(C.c_float)) if n else None, _dptr(inn), _dptr(m2), _u8ptr(st),
+                                                      seg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        return inn[:n], m2[:n], st[:n], seg[:n], self._report(rep)
 
     def set_step_callback(self, fn, want_z=True):
         """SparseLevMarq::setStepCallBackFunc: fn(z) after every step (z = numpy copy of curr_z, or None when want_z is False)."""

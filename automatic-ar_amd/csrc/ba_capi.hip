@@ -3237,9 +3237,65 @@ void smooth_query_times(const aar_smooth_params &sp, int F, size_t Q, const doub
     }
 }
 
-// The three query entries after their model checks.  Random walk: the pose is a closed form of the frame poses, the selected inverse runs
-// for cov alone.  Constant velocity: H at mu = 0, its reduction and selected inverse, the lag-three blocks, then the queries; the pose
-// depends on the blocks, so cov == NULL saves the copy back alone.  start, step: the start poses and delta_m (constant velocity, checking)
+// What a time query leaves on the device: the poses, the blocks and the segments of Q > 0 times, in one allocation
+struct SmoothQueryDev {
+    DevMem out;
+    double *pose = nullptr, *start = nullptr, *step = nullptr, *cov = nullptr;   // [Q][6] (start, step: constant velocity), [Q][36] or NULL
+    int32_t *seg = nullptr, *flag = nullptr;   // [Q]; two pivot flags: the lag-three blocks', the queries'
+    bool blocks = false;                       // the selected inverse ran
+    int launches = 0;
+};
+
+// The device work of the query entries.  Random walk: the pose is a closed form of the frame poses, the selected inverse runs for cov alone.
+// Constant velocity: H at mu = 0, its reduction and selected inverse, the lag-three blocks, then the queries; the pose depends on the
+// blocks, so want_cov = false saves the blocks of the queries alone.  Launches and copies in, nothing read back
+int smooth_query_device(SmoothRun &c, const double *x_full, size_t Q, const double *query_time, const std::vector<double> &ft, bool want_cov,
+                        SmoothQueryDev &d) {
+    aar_problem *pb = c.pb;
+    const aar_smooth_params &sp = c.sp;
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    int rc;
+    d.blocks = c.cv || want_cov;
+    if ((rc = c.begin(x_full, d.blocks))) return rc;
+    // one allocation: ft [F] | query times [Q] | pose [Q][6] | start, step [Q][6] each (constant velocity) | cov [Q][36] | the selected
+    // inverse's area | l3 [F-3][36] (constant velocity) | segment [Q] and two pivot flags: the lag-three blocks', the queries'
+    const size_t n_out = c.cv ? 18 * Q : 6 * Q, n_cov = want_cov ? 36 * Q : 0, n_sel = d.blocks ? c.selinv_doubles() : 0;
+    const size_t n_dbl = (size_t)F + Q + n_out + n_cov + n_sel + (c.cv ? 36 * (size_t)std::max(F - 3, 0) : 0);
+    if ((rc = d.out.alloc(pb, n_dbl, Q + 2))) return rc;
+    double *d_ft = d.out.p, *d_qt = d_ft + F;
+    d.pose = d_qt + Q; d.start = c.cv ? d.pose + 6 * Q : nullptr; d.step = c.cv ? d.start + 6 * Q : nullptr;
+    d.cov = want_cov ? d.pose + n_out : nullptr;
+    double *d_area = d.pose + n_out + n_cov, *d_l3 = d_area + n_sel;
+    d.seg = reinterpret_cast<int32_t *>(d.out.p + n_dbl); d.flag = d.seg + Q;
+    if ((rc = copy_h2d(pb, d_ft, ft.data(), (size_t)F * sizeof(double)))) return rc;
+    if ((rc = copy_h2d(pb, d_qt, query_time, Q * sizeof(double)))) return rc;
+    SmoothSel sel;
+    if (d.blocks) sel = c.selinv(0, d_area);
+    d.launches = sel.launches;
+    if (c.cv) {
+        d.launches += launch_smooth_cv_lag3(F, d_area, d_l3, d.flag, pb->stream);
+        d.launches += launch_smooth_cv_query(F, c.z(0), d_ft, sp.sigma_rot, sp.sigma_trans, sp.sigma_rot0, sp.sigma_trans0, sel.fc, sel.lc, sel.l2,
+                                             d_l3, (int64_t)Q, d_qt, d.pose, d.cov, d.start, d.step, d.seg, d.flag + 1, pb->stream);
+    } else {
+        d.launches += launch_smooth_query(c.rw, F, d.blocks ? c.z(0) : P.z[pb->cur] + 6 * (size_t)P.A, d_ft, sp.sigma_rot, sp.sigma_trans, sel.fc,
+                                          sel.lc, (int64_t)Q, d_qt, d.pose, d.cov, d.seg, d.flag + 1, pb->stream);
+    }
+    return AAR_OK;
+}
+
+// ... and what is read back first: the chain's record and the three pivot flags, each with its refusal (d.blocks only)
+int smooth_query_pivots(const SmoothRun &c, const char *who, const SmoothQueryDev &d, double res[8]) {
+    int rc;
+    int32_t qflag[2] = {0, 0};
+    if ((rc = c.read_pivot(who, "smoothing query kernels", res))) return rc;
+    if ((rc = copy_d2h(c.pb, qflag, d.flag, sizeof qflag))) return rc;
+    if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a supernode block of the lag-three blocks", who);
+    if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a query's %s", who, c.cv ? "eliminations" : "6x6 inverses");
+    return AAR_OK;
+}
+
+// The three query entries after their model checks.  start, step: the start poses and delta_m (constant velocity, checking)
 int smooth_query(SmoothRun &c, const char *who, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const double *query_time,
                  double *pose, double *cov, int32_t *segment, double *start, double *step, aar_smooth_query_report *report) {
     aar_problem *pb = c.pb;
@@ -3249,55 +3305,28 @@ int smooth_query(SmoothRun &c, const char *who, const double *x_full, const aar_
     if (sp.rel_motion)
         return set_error(AAR_ERR_UNSUPPORTED, "%s: rel_motion is set; under an expected motion the pose of an inserted frame "
                                               "has no closed form (the split of dR does not commute)", who);
-    DeviceProblem &P = pb->P;
-    const int F = P.F;
     const size_t Q = (size_t)n_query;
-    const bool blocks = c.cv || cov;   // the selected inverse runs
     const auto t0 = std::chrono::steady_clock::now();
     aar_smooth_query_report r;
     smooth_report_begin(pb, r);
     r.num_queries = (int32_t)Q;
     if (Q > 0) {
         std::vector<double> ft;
-        smooth_query_times(sp, F, Q, query_time, ft, r);
-        if ((rc = c.begin(x_full, blocks))) return rc;
-        // one allocation: ft [F] | query times [Q] | pose [Q][6] | start, step [Q][6] each (constant velocity) | cov [Q][36] | the selected
-        // inverse's area | l3 [F-3][36] (constant velocity) | segment [Q] and two pivot flags: the lag-three blocks', the queries'
-        const size_t n_out = c.cv ? 18 * Q : 6 * Q, n_cov = cov ? 36 * Q : 0, n_sel = blocks ? c.selinv_doubles() : 0;
-        const size_t n_dbl = (size_t)F + Q + n_out + n_cov + n_sel + (c.cv ? 36 * (size_t)std::max(F - 3, 0) : 0);
-        DevMem out;
-        if ((rc = out.alloc(pb, n_dbl, Q + 2))) return rc;
-        double *d_ft = out.p, *d_qt = d_ft + F, *d_pose = d_qt + Q, *d_start = c.cv ? d_pose + 6 * Q : nullptr, *d_step = c.cv ? d_start + 6 * Q : nullptr;
-        double *d_cov = cov ? d_pose + n_out : nullptr, *d_area = d_pose + n_out + n_cov, *d_l3 = d_area + n_sel;
-        int32_t *d_seg = reinterpret_cast<int32_t *>(out.p + n_dbl), *d_flag = d_seg + Q;
-        if ((rc = copy_h2d(pb, d_ft, ft.data(), (size_t)F * sizeof(double)))) return rc;
-        if ((rc = copy_h2d(pb, d_qt, query_time, Q * sizeof(double)))) return rc;
-        SmoothSel sel;
-        if (blocks) sel = c.selinv(0, d_area);
-        r.launches = sel.launches;
-        if (c.cv) {
-            r.launches += launch_smooth_cv_lag3(F, d_area, d_l3, d_flag, pb->stream);
-            r.launches += launch_smooth_cv_query(F, c.z(0), d_ft, sp.sigma_rot, sp.sigma_trans, sp.sigma_rot0, sp.sigma_trans0, sel.fc, sel.lc, sel.l2,
-                                                 d_l3, (int64_t)Q, d_qt, d_pose, d_cov, d_start, d_step, d_seg, d_flag + 1, pb->stream);
-        } else {
-            r.launches += launch_smooth_query(c.rw, F, blocks ? c.z(0) : P.z[pb->cur] + 6 * (size_t)P.A, d_ft, sp.sigma_rot, sp.sigma_trans, sel.fc,
-                                              sel.lc, (int64_t)Q, d_qt, d_pose, d_cov, d_seg, d_flag + 1, pb->stream);
-        }
+        smooth_query_times(sp, pb->P.F, Q, query_time, ft, r);
+        SmoothQueryDev d;
+        if ((rc = smooth_query_device(c, x_full, Q, query_time, ft, cov != nullptr, d))) return rc;
+        r.launches = d.launches;
         pb->launches += r.launches;
-        if (blocks) {
+        if (d.blocks) {
             double res[8];
-            int32_t qflag[2] = {0, 0};
-            if ((rc = c.read_pivot(who, "smoothing query kernels", res))) return rc;
-            if ((rc = copy_d2h(pb, qflag, d_flag, sizeof qflag))) return rc;
-            if (qflag[0]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a supernode block of the lag-three blocks", who);
-            if (qflag[1]) return set_error(AAR_ERR_NUMERIC, "%s: non-positive pivot in a query's %s", who, c.cv ? "eliminations" : "6x6 inverses");
+            if ((rc = smooth_query_pivots(c, who, d, res))) return rc;
             r.data_cost = res[0]; r.prior_cost = res[1];
-            if (cov && (rc = copy_d2h(pb, cov, d_cov, 36 * Q * sizeof(double)))) return rc;
+            if (cov && (rc = copy_d2h(pb, cov, d.cov, 36 * Q * sizeof(double)))) return rc;
         }
-        if (pose && (rc = copy_d2h(pb, pose, d_pose, 6 * Q * sizeof(double)))) return rc;
-        if (start && c.cv && (rc = copy_d2h(pb, start, d_start, 6 * Q * sizeof(double)))) return rc;
-        if (step && c.cv && (rc = copy_d2h(pb, step, d_step, 6 * Q * sizeof(double)))) return rc;
-        if (segment && (rc = copy_d2h(pb, segment, d_seg, Q * sizeof(int32_t)))) return rc;
+        if (pose && (rc = copy_d2h(pb, pose, d.pose, 6 * Q * sizeof(double)))) return rc;
+        if (start && c.cv && (rc = copy_d2h(pb, start, d.start, 6 * Q * sizeof(double)))) return rc;
+        if (step && c.cv && (rc = copy_d2h(pb, step, d.step, 6 * Q * sizeof(double)))) return rc;
+        if (segment && (rc = copy_d2h(pb, segment, d.seg, Q * sizeof(int32_t)))) return rc;
         if ((rc = check_async("smoothing query kernels"))) return rc;
         HIP_TRY(hipStreamSynchronize(pb->stream));
     }
@@ -3797,6 +3826,299 @@ int aar_problem_gate_detections(aar_problem *pb, const double *x_full, int64_t n
         memcpy(report, &r, std::min<size_t>(report->struct_size, sizeof r));
     }
     return AAR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same per-detection layer on a smoothed track (smooth_predict_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// the launch of k_smooth_corners between two events when the problem's kernel profiling is on (aar_set_kernel_profiling): its own time for
+// the reports' kernel_seconds, read after the call's last synchronisation; 0 otherwise
+struct SmoothCornersTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~SmoothCornersTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    void launch(const aar_problem *pb, const SmoothCornersArgs &a, int mode) {
+        const bool on = pb->profiling && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+        if (on) (void)hipEventRecord(e0, pb->stream);
+        launch_smooth_corners(a, mode, pb->stream);
+        if (on) (void)hipEventRecord(e1, pb->stream);
+        else if (e0) { (void)hipEventDestroy(e0); e0 = nullptr; }
+    }
+    double seconds() const {
+        float ms = 0.f;
+        return e0 && e1 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess ? 1e-3 * (double)ms : 0.0;
+    }
+};
+
+// what the kernel reads of the problem itself
+SmoothCornersArgs smooth_corners_args(const aar_problem *pb, int64_t n) {
+    const DeviceProblem &P = pb->P;
+    const KTable kt = k_table(P, pb->cur);
+    SmoothCornersArgs a;
+    memset(&a, 0, sizeof a);
+    a.ent = P.ent[pb->cur]; a.K = kt.base; a.kstride = kt.stride; a.C = P.C; a.h = P.half_size; a.n = n;
+    a.obs = P.a_idx;
+    return a;
+}
+
+// aar_track_smooth_detection_leverage (mode 2) and aar_track_smooth_detection_loo (mode 3) after their checks: the chain of
+// aar_track_smooth_covariance2, whose diagonal blocks stay on the device, and one launch over the problem's detections behind it.  r: the
+// report's head (costs, launches); hb: status | keep of every detection, hF, hlev: what the report's counts need (mode 3)
+extern "C++" template <class R>
+int smooth_detections(SmoothRun &c, const char *who, const double *x_full, int mode, double f_max, const LooOut &o, double *row_lev, R &r,
+                      std::vector<uint8_t> &h_b, std::vector<double> &h_F, std::vector<double> &h_lev) {
+    aar_problem *pb = c.pb;
+    DeviceProblem &P = pb->P;
+    const int F = P.F;
+    const size_t N = (size_t)P.N;
+    int rc = c.begin(x_full);
+    if (rc) return rc;
+    if (F == 0) { HIP_TRY(hipStreamSynchronize(pb->stream)); return AAR_OK; }
+    // one allocation: the selected inverse's area | w [N][8] (mode 3) or the rows [N][8] (mode 2) | q | margin | F | cook | leverage, then
+    // status | keep
+    const size_t n_sel = c.selinv_doubles(), n_m3 = mode == 3 ? N : 0;
+    const size_t n_dbl = n_sel + 8 * N + 2 * n_m3 + 2 * n_m3 + N, n_bytes = 2 * N;
+    DevMem out;
+    if ((rc = out.alloc(pb, n_dbl, (n_bytes + 3) / 4))) return rc;
+    double *d_w = out.p + n_sel, *d_q = d_w + 8 * N, *d_mg = d_q + n_m3, *d_F = d_mg + n_m3, *d_ck = d_F + n_m3, *d_lev = d_ck + n_m3;
+    uint8_t *d_st = reinterpret_cast<uint8_t *>(out.p + n_dbl), *d_keep = d_st + N;
+    const SmoothSel sel = c.selinv(0, out.p);
+    r.launches = sel.launches;
+    SmoothCornersTimer timer;
+    if (N > 0) {
+        SmoothCornersArgs a = smooth_corners_args(pb, (int64_t)N);
+        a.pose = c.z(0); a.block = sel.fc;
+        a.status = d_st; a.lev = d_lev; a.row_lev = (mode == 2 && row_lev) ? d_w : nullptr;
+        a.obs_uv = P.a_uv;
+        a.loo_w = d_w; a.loo_q = d_q; a.loo_margin = d_mg; a.loo_F = d_F; a.loo_cook = d_ck; a.loo_keep = d_keep;
+        a.res = c.res(); a.f_max = f_max > 0.0 ? f_max : 0.0; a.num_vars = (double)r.num_vars; a.dof = r.num_residuals - r.num_vars;
+        timer.launch(pb, a, mode);
+        r.launches += 1;
+    }
+    pb->launches += r.launches;
+    double res[8];
+    if ((rc = c.read_pivot(who, "smoothing covariance kernels", res))) return rc;
+    r.data_cost = res[0]; r.prior_cost = res[1];
+    if (N == 0) return AAR_OK;
+    // to the host, into staging: what the report needs and what the caller asked for; the caller's arrays are written after every copy succeeded
+    std::unique_ptr<double[]> h_w, h_q, h_mg, h_ck;
+    h_b.resize(2 * N);
+    h_lev.resize(N);
+    if ((rc = copy_d2h(pb, h_b.data(), d_st, 2 * N))) return rc;
+    if ((rc = copy_d2h(pb, h_lev.data(), d_lev, N * sizeof(double)))) return rc;
+    if (mode == 2 ? row_lev != nullptr : o.w != nullptr) {
+        h_w.reset(new double[8 * N]);
+        if ((rc = copy_d2h(pb, h_w.get(), d_w, 8 * N * sizeof(double)))) return rc;
+    }
+    if (mode == 3) {
+        h_F.resize(N);
+        if ((rc = copy_d2h(pb, h_F.data(), d_F, N * sizeof(double)))) return rc;
+        if (o.q) { h_q.reset(new double[N]); if ((rc = copy_d2h(pb, h_q.get(), d_q, N * sizeof(double)))) return rc; }
+        if (o.margin) { h_mg.reset(new double[N]); if ((rc = copy_d2h(pb, h_mg.get(), d_mg, N * sizeof(double)))) return rc; }
+        if (o.cook) { h_ck.reset(new double[N]); if ((rc = copy_d2h(pb, h_ck.get(), d_ck, N * sizeof(double)))) return rc; }
+    }
+    if ((rc = check_async("smoothing detection kernels"))) return rc;
+    HIP_TRY(hipStreamSynchronize(pb->stream));
+    r.kernel_seconds = timer.seconds();
+    // everything succeeded: only now the caller's arrays are written
+    if (o.lev) memcpy(o.lev, h_lev.data(), N * sizeof(double));
+    if (mode == 2 && row_lev) memcpy(row_lev, h_w.get(), 8 * N * sizeof(double));
+    if (mode == 3) {
+        if (o.w) memcpy(o.w, h_w.get(), 8 * N * sizeof(double));
+        if (o.q) memcpy(o.q, h_q.get(), N * sizeof(double));
+        if (o.margin) memcpy(o.margin, h_mg.get(), N * sizeof(double));
+        if (o.cook) memcpy(o.cook, h_ck.get(), N * sizeof(double));
+        if (o.F) memcpy(o.F, h_F.data(), N * sizeof(double));
+        if (o.status) memcpy(o.status, h_b.data(), N);
+        if (o.keep) memcpy(o.keep, h_b.data() + N, N);
+    }
+    return AAR_OK;
+}
+
+// aar_track_smooth_predict_corners (mode 0, or 1 without cov) and aar_track_smooth_gate_detections (mode 4) after smooth_entry: the checks,
+// the query chain of aar_track_smooth_query2, whose poses and blocks stay on the device, and one launch over the queries behind it
+int smooth_time_queries(SmoothRun &c, const char *who, const double *x_full, const aar_smooth_params *sp_in, int mode, int64_t n_query,
+                        const int32_t *q_cam, const int32_t *q_marker, const double *q_time, const float *uv_obs, double *uv, double *cov,
+                        double *m2, uint8_t *status, int32_t *segment, aar_smooth_predict_report *report) {
+    aar_problem *pb = c.pb;
+    int rc = aar_smooth_query_validate(pb->L.F, sp_in, n_query, q_time);
+    if (rc) return rc;
+    if (n_query > 0 && (!q_cam || !q_marker)) return set_error(AAR_ERR_INVALID, "%s: null query array with n_query = %lld", who, (long long)n_query);
+    for (int64_t i = 0; i < n_query; i++) {
+        if (q_cam[i] < 0 || q_cam[i] >= pb->L.C)
+            return set_error(AAR_ERR_INVALID, "%s: q_cam[%lld] = %d lies outside 0 .. num_cams - 1 = %d", who, (long long)i, (int)q_cam[i], pb->L.C - 1);
+        if (q_marker[i] < 0 || q_marker[i] >= pb->L.M)
+            return set_error(AAR_ERR_INVALID, "%s: q_marker[%lld] = %d lies outside 0 .. num_markers - 1 = %d", who, (long long)i, (int)q_marker[i],
+                             pb->L.M - 1);
+    }
+    if (c.sp.rel_motion)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: rel_motion is set; under an expected motion the pose of an inserted frame "
+                                              "has no closed form (the split of dR does not commute)", who);
+    const size_t Q = (size_t)n_query;
+    const auto t0 = std::chrono::steady_clock::now();
+    aar_smooth_predict_report r;
+    smooth_report_begin(pb, r);
+    r.num_queries = (int64_t)Q;
+    if (Q > 0) {
+        DeviceProblem &P = pb->P;
+        aar_smooth_query_report counts;
+        memset(&counts, 0, sizeof counts);
+        std::vector<double> ft;
+        smooth_query_times(c.sp, P.F, Q, q_time, ft, counts);
+        r.num_inside = counts.num_inside; r.num_on_frame = counts.num_on_frame; r.num_outside = counts.num_outside;
+        SmoothQueryDev d;
+        if ((rc = smooth_query_device(c, x_full, Q, q_time, ft, mode != 1, d))) return rc;
+        r.launches = d.launches;
+        if (!d.blocks) {   // (no work area, and nobody has made the rows of the cameras and markers yet)
+            launch_unpack(P, pb->cur, pb->stream);
+            r.launches += 1;
+        }
+        // one allocation: uv [Q][8] (the gate: the innovation) | cov [Q][64] (mode 0) | m2, margin [Q] (mode 4), then the caller's corners
+        // (mode 4), the queries' cameras and markers, the status bytes
+        const size_t n_cov = mode == 0 ? 64 * Q : 0, n_m4 = mode == 4 ? Q : 0, n_dbl = 8 * Q + n_cov + 2 * n_m4;
+        DevMem out;
+        if ((rc = out.alloc(pb, n_dbl, 8 * n_m4 + 2 * Q + (Q + 3) / 4))) return rc;
+        double *d_uv = out.p, *d_cov = d_uv + 8 * Q, *d_m2 = d_cov + n_cov, *d_mg = d_m2 + n_m4;
+        float *d_obs = reinterpret_cast<float *>(out.p + n_dbl);
+        int32_t *d_qc = reinterpret_cast<int32_t *>(d_obs + 8 * n_m4), *d_qm = d_qc + Q;
+        uint8_t *d_st = reinterpret_cast<uint8_t *>(d_qm + Q);
+        if ((rc = copy_h2d(pb, d_qc, q_cam, Q * sizeof(int32_t))) || (rc = copy_h2d(pb, d_qm, q_marker, Q * sizeof(int32_t)))) return rc;
+        if (mode == 4 && (rc = copy_h2d(pb, d_obs, uv_obs, 8 * Q * sizeof(float)))) return rc;
+        SmoothCornersArgs a = smooth_corners_args(pb, (int64_t)Q);
+        a.q_cam = d_qc; a.q_marker = d_qm; a.pose = d.pose; a.block = d.cov;
+        a.uv = d_uv; a.cov = d_cov; a.status = d_st;
+        a.obs_uv = d_obs; a.loo_w = d_uv; a.loo_q = d_m2; a.loo_margin = d_mg;
+        SmoothCornersTimer timer;
+        timer.launch(pb, a, mode);
+        r.launches += 1;
+        pb->launches += r.launches;
+        if (d.blocks) {
+            double res[8];
+            if ((rc = smooth_query_pivots(c, who, d, res))) return rc;
+            r.data_cost = res[0]; r.prior_cost = res[1];
+        }
+        std::vector<uint8_t> h_st(Q);
+        std::vector<int32_t> h_seg(Q);
+        std::unique_ptr<double[]> h_uv(new double[8 * Q]), h_cov, h_m2;
+        if ((rc = copy_d2h(pb, h_st.data(), d_st, Q))) return rc;
+        if ((rc = copy_d2h(pb, h_seg.data(), d.seg, Q * sizeof(int32_t)))) return rc;
+        if ((rc = copy_d2h(pb, h_uv.get(), d_uv, 8 * Q * sizeof(double)))) return rc;
+        if (mode == 0) { h_cov.reset(new double[64 * Q]); if ((rc = copy_d2h(pb, h_cov.get(), d_cov, 64 * Q * sizeof(double)))) return rc; }
+        if (mode == 4) { h_m2.reset(new double[Q]); if ((rc = copy_d2h(pb, h_m2.get(), d_m2, Q * sizeof(double)))) return rc; }
+        if ((rc = check_async("smoothing detection kernels"))) return rc;
+        HIP_TRY(hipStreamSynchronize(pb->stream));
+        r.kernel_seconds = timer.seconds();
+        // everything succeeded: only now the caller's arrays are written
+        for (size_t i = 0; i < Q; i++) {
+            r.behind += (h_st[i] & AAR_PREDICT_BEHIND) ? 1 : 0;
+            if (mode == 0) {
+                const double *cc = &h_cov[64 * i];
+                const double t = ((cc[0] + cc[9]) + (cc[18] + cc[27])) + ((cc[36] + cc[45]) + (cc[54] + cc[63]));   // (the kernel's order of the trace)
+                if (std::isfinite(t)) r.leverage_sum += t;
+            }
+        }
+        if (uv) memcpy(uv, h_uv.get(), 8 * Q * sizeof(double));
+        if (cov) memcpy(cov, h_cov.get(), 64 * Q * sizeof(double));
+        if (m2) memcpy(m2, h_m2.get(), Q * sizeof(double));
+        if (status) memcpy(status, h_st.data(), Q);
+        if (segment) memcpy(segment, h_seg.data(), Q * sizeof(int32_t));
+    }
+    smooth_report_end(r, report, t0);
+    return AAR_OK;
+}
+
+}  // namespace
+
+int aar_track_smooth_detection_leverage(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, double *leverage, double *row_leverage,
+                                        aar_smooth_predict_report *report) {
+    const char *who = "aar_track_smooth_detection_leverage";
+    if (!pb || !x_full || (pb->P.N > 0 && !leverage)) return set_error(AAR_ERR_INVALID, "%s: null argument", who);
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "%s: report->struct_size not set", who);
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, who);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    aar_smooth_predict_report r;
+    smooth_report_begin(pb, r);
+    r.num_queries = pb->P.N;
+    LooOut o;
+    o.lev = leverage;
+    std::vector<uint8_t> h_b;
+    std::vector<double> h_F, h_lev;
+    if ((rc = smooth_detections(c, who, x_full, 2, 0.0, o, row_leverage, r, h_b, h_F, h_lev))) return rc;
+    for (size_t i = 0; i < h_lev.size(); i++) {
+        r.behind += (h_b[i] & AAR_PREDICT_BEHIND) ? 1 : 0;
+        if (std::isfinite(h_lev[i])) r.leverage_sum += h_lev[i];
+    }
+    smooth_report_end(r, report, t0);
+    return AAR_OK;
+}
+
+int aar_track_smooth_detection_loo(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, const aar_loo_rule *rule, double *loo_resid,
+                                   double *q, double *F, double *cook, double *leverage, double *margin, uint8_t *status, uint8_t *keep,
+                                   aar_smooth_loo_report *report) {
+    const char *who = "aar_track_smooth_detection_loo";
+    if (!pb || !x_full) return set_error(AAR_ERR_INVALID, "%s: null argument", who);
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "%s: report->struct_size not set", who);
+    if (rule) {
+        if (rule->struct_size < offsetof(aar_loo_rule, f_max) + sizeof(double))
+            return set_error(AAR_ERR_INVALID, "%s: rule->struct_size %u does not reach f_max", who, (unsigned)rule->struct_size);
+        if (!(rule->f_max > 0.0) || !std::isfinite(rule->f_max))
+            return set_error(AAR_ERR_INVALID, "%s: rule->f_max = %g must be positive and finite", who, rule->f_max);
+    }
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, who);
+    if (rc) return rc;
+    if (pb->with_huber)
+        return set_error(AAR_ERR_UNSUPPORTED, "%s: the problem was created with_huber; the Huber weights break the Gaussian data model the "
+                                              "statistic rests on", who);
+    const auto t0 = std::chrono::steady_clock::now();
+    aar_smooth_loo_report r;
+    smooth_report_begin(pb, r);
+    r.dof = r.num_residuals - r.num_vars;
+    r.f_max = rule ? rule->f_max : INFINITY;
+    r.max_f = NAN;
+    r.argmax_f = -1;
+    LooOut o;
+    o.w = loo_resid; o.q = q; o.F = F; o.cook = cook; o.lev = leverage; o.margin = margin; o.status = status; o.keep = keep;
+    std::vector<uint8_t> h_b;
+    std::vector<double> h_F, h_lev;
+    if ((rc = smooth_detections(c, who, x_full, 3, rule ? rule->f_max : 0.0, o, nullptr, r, h_b, h_F, h_lev))) return rc;
+    const size_t N = h_lev.size();
+    for (size_t i = 0; i < N; i++) {
+        r.behind += (h_b[i] & AAR_PREDICT_BEHIND) ? 1 : 0;
+        r.undetermined += (h_b[i] & AAR_PREDICT_UNDETERMINED) ? 1 : 0;
+        r.rejected += h_b[N + i] ? 0 : 1;
+        if (std::isfinite(h_lev[i])) r.leverage_sum += h_lev[i];
+        if (h_F[i] > r.max_f || (r.argmax_f < 0 && !std::isnan(h_F[i]))) { r.max_f = h_F[i]; r.argmax_f = (int64_t)i; }
+    }
+    smooth_report_end(r, report, t0);
+    return AAR_OK;
+}
+
+int aar_track_smooth_predict_corners(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const int32_t *q_cam,
+                                     const int32_t *q_marker, const double *q_time, double *uv, double *cov, uint8_t *status, int32_t *segment,
+                                     aar_smooth_predict_report *report) {
+    const char *who = "aar_track_smooth_predict_corners";
+    if (!pb || !x_full || (n_query > 0 && !uv)) return set_error(AAR_ERR_INVALID, "%s: null argument", who);
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "%s: report->struct_size not set", who);
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, who);
+    if (rc) return rc;
+    return smooth_time_queries(c, who, x_full, sp_in, cov ? 0 : 1, n_query, q_cam, q_marker, q_time, nullptr, uv, cov, nullptr, status, segment, report);
+}
+
+int aar_track_smooth_gate_detections(aar_problem *pb, const double *x_full, const aar_smooth_params *sp_in, int64_t n_query, const int32_t *q_cam,
+                                     const int32_t *q_marker, const double *q_time, const float *uv_obs, double *innovation, double *m2,
+                                     uint8_t *status, int32_t *segment, aar_smooth_predict_report *report) {
+    const char *who = "aar_track_smooth_gate_detections";
+    if (!pb || !x_full || (n_query > 0 && !uv_obs)) return set_error(AAR_ERR_INVALID, "%s: null argument", who);
+    if (report && report->struct_size < sizeof(uint32_t)) return set_error(AAR_ERR_INVALID, "%s: report->struct_size not set", who);
+    SmoothRun c;
+    int rc = smooth_entry(pb, sp_in, c, who);
+    if (rc) return rc;
+    return smooth_time_queries(c, who, x_full, sp_in, 4, n_query, q_cam, q_marker, q_time, uv_obs, innovation, nullptr, m2, status, segment, report);
 }
 
 int aar_set_kernel_profiling(aar_problem *pb, int on) {

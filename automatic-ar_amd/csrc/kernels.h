@@ -585,6 +585,31 @@ void launch_predict_gains(const DeviceProblem &P, int which, const int32_t *rowm
 // problem's own detections in reference order.  One launch, one wavefront per query
 void launch_predict_corners(const PredictArgs &a, int mode, hipStream_t st);
 
+// the same quantities on a smoothed track (smooth_predict_kernels.hip): Sigma is one 6 x 6 block of the smoother's H^-1,
+// G the frame Jacobian alone.  The problem's detections (modes 2, 3) read pose[frame] and block[frame]: z [F][6] and SmoothSel.fc.  Explicit
+// queries (modes 0, 1, 4) read pose[q] and block[q]: the poses and blocks the query chain left for the queries' times.  Mode 1 reads no block
+struct SmoothCornersArgs {
+    const double *ent, *K;                // entity rows of the cameras and markers (launch_unpack), camera matrices K[kstride * camera + i]
+    int kstride, C;
+    double h;
+    int64_t n;                            // queries
+    const ObsIdx *obs;                    // ordering A (modes 2, 3) ...
+    const int32_t *q_cam, *q_marker;      // ... or camera and marker INDEX per query (modes 0, 1, 4)
+    const double *pose, *block;           // [.][6], [.][36]
+    double *uv, *cov;                     // [n][8], [n][64] (modes 0, 1; cov mode 0 only)
+    uint8_t *status;                      // [n] bit 0: a corner at non-positive depth, bit 2 (modes 3, 4): PREDICT_UNDETERMINED
+    double *lev, *row_lev;                // [n], [n][8] or NULL (mode 2; lev also mode 3)
+    const float *obs_uv;                  // observed corners [n][8]: ordering A's (mode 3), the caller's (mode 4)
+    double *loo_w, *loo_q, *loo_margin;   // [n][8] w = A^-1 r (mode 4: r itself), [n] r^T w, [n] smallest pivot
+    double *loo_F, *loo_cook;             // [n] (mode 3)
+    uint8_t *loo_keep;                    // [n] (mode 3)
+    const double *res;                    // (mode 3) the chain's record ON THE DEVICE: data cost, prior cost
+    double f_max, num_vars;               // (mode 3) the rule's bound (0: no rule), 6 F
+    int64_t dof;                          // (mode 3) nu = num_residuals - num_vars
+};
+// one launch, eight lanes per query
+void launch_smooth_corners(const SmoothCornersArgs &a, int mode, hipStream_t st);
+
 // residual report (resid_kernels.hip).  The select's state: the key bits [pshift, 63) picked so far, the rank still
 // wanted inside that bucket, done (prefix = the key), single (one key left in the bucket: the next pass fetches it), t = the threshold
 constexpr int RR_DIGIT_BITS = 11, RR_BINS = 1 << RR_DIGIT_BITS, RR_PASSES = 6;   // 63 key bits = 5 digits of 11 + one of 8

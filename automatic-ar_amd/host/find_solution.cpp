@@ -28,12 +28,14 @@
 using namespace std;
 
 static int print_usage(const char *a0) {
-    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-leverage <h_min>] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>] [-relative-to <frame_id>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
+    cout << "Usage: " << a0 << " <data_folder_path> <marker_size> [ignored] [-subseqs] [-exclude-cams <cam_id> ...] [-with-huber] [-thresh <t>] [-from-initial] [-solver direct|spcg|pcg|auto] [-covariance] [-leverage <h_min>] [-residuals] [-reject-outliers <k> [-reject-min-px <px>]] [-fix-cams <id>[,<id>...]] [-fix-markers <id>[,<id>...]] [-prior-solution <file> [-prior-sigma-deg <d>] [-prior-sigma-m <m>]] [-relative-prior-solution <file> [-relative-kinds cams|markers|both] [-relative-sigma-deg <d>] [-relative-sigma-m <m>]] [-tracking-only -smooth <sigma_rot> <sigma_trans> [-cv <sigma_rot0> <sigma_trans0> [-cv-covariance] [-cv-fit-sigmas] [-cv-resample <n>]] [-smooth-covariance] [-fit-sigmas] [-resample <n>] [-relative-to <frame_id>] [-smooth-loo <f_max>] [-smooth-reject-loo <f_max>]] [-tracking-only -live <lag> [<sigma_rot> <sigma_trans>] [-from-detections [vote|best]] [-anchor fixed|marginal] [-live-covariance] [-gate <k_median> <min_px>] [-motion cv|rw [<max_dt>]]]" << endl;
     cout << "       -covariance          also write final.covariance.yaml (pose covariance of the final solution)" << endl;
     cout << "       -leverage <h_min>    also write final.leverage.yaml (leverage of every detection, 0 .. 8; those from h_min up are listed)" << endl;
     cout << "       -residuals           also write final.residuals.yaml (reprojection errors per camera and marker)" << endl;
     cout << "       -loo <f_max>         also write final.loo.yaml (leave-one-out F of every detection; those above f_max or undetermined are listed)" << endl;
     cout << "       -reject-loo <f_max>  after the solve, drop of every frame the detection with the largest F above f_max and solve again (not with -with-huber)" << endl;
+    cout << "       -smooth-loo <f_max>  (needs -smooth) also write final.smooth_loo.yaml (leave-one-out F of every detection against the smoothed track)" << endl;
+    cout << "       -smooth-reject-loo <f_max>   (needs -smooth) drop of every frame the detection with the largest F above f_max and smooth again (up to 3 rounds)" << endl;
     cout << "       -reject-outliers k   after the solve, drop the detections whose error exceeds max(px, k * median) and solve again" << endl;
     cout << "                            (up to 3 rounds, until a round drops nothing); final.solution keeps the remaining detections" << endl;
     cout << "       -reject-min-px px    the floor of that threshold in pixels (default 0)" << endl;
@@ -322,6 +324,11 @@ int main(int argc, char *argv[]) {
     // final.smooth_relative.yaml (MultiCamMapper::track_smooth_relative), at the poses of the solution file written beside it
     bool relative_to = false, relative_set = false;
     long relative_id = 0;
+    // ... -smooth-loo <f_max> (only with -smooth; with -cv under the constant-velocity prior) writes the smoothed track's leave-one-out report to
+    // final.smooth_loo.yaml (MultiCamMapper::track_smooth_detection_loo); -smooth-reject-loo <f_max> drops of every frame the
+    // detection with the largest F above f_max and smooths again, at most 3 rounds: -reject-loo on the smoothed track
+    double smooth_loo_f = 0.0, smooth_reject_loo_f = 0.0;
+    bool smooth_loo = false, smooth_reject_loo = false;
     // nor this: -live <lag> [sigma_rot sigma_trans] (only with -tracking-only) takes the cameras and markers as they are and feeds the frames one at a
     // time through the live tracker (MultiCamMapper::track_live) instead of solving; without sigmas there is no prior and the lag must be 0
     // ... with -from-detections [vote|best] the frames are fed the RAW detections of aruco.detections (calib.* for the lenses) and start from their
@@ -345,7 +352,7 @@ int main(int argc, char *argv[]) {
     int motion_args = 0, motion_model = AAR_TRACKER_MOTION_RANDOM_WALK;
     double motion_max_dt = 0.0;
     int solver = AAR_SOLVER_AUTO;   // not an option of the reference: how the damped systems are solved (aar_solver_options); `-solver direct` = the reference's every step
-    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion, Leverage, Loo, RejectLoo } arg_flag = NONE;
+    enum ArgFlag { NONE, ExcludeCams, Threshold, Solver, RejectK, RejectPx, FixCams, FixMarkers, PriorPath, PriorDeg, PriorM, RelPath, RelKinds, RelDeg, RelM, Smooth, SmoothCv, Resample, RelativeTo, Live, Anchor, Gate, Motion, Leverage, Loo, RejectLoo, SmoothLoo, SmoothRejectLoo } arg_flag = NONE;
     for (int i = 4; i < argc; i++) {  // sic: the reference starts at argv[4] (apps/find_solution.cpp:47)
         const string a = argv[i];
         if (a == "-subseqs") use_subseqs = true;
@@ -359,6 +366,8 @@ int main(int argc, char *argv[]) {
         else if (a == "-leverage") { leverage = true; arg_flag = Leverage; }
         else if (a == "-loo") { loo = true; arg_flag = Loo; }
         else if (a == "-reject-loo") { reject_loo_on = true; arg_flag = RejectLoo; }
+        else if (a == "-smooth-loo") { smooth_loo = true; arg_flag = SmoothLoo; }
+        else if (a == "-smooth-reject-loo") { smooth_reject_loo = true; arg_flag = SmoothRejectLoo; }
         else if (a == "-residuals") { residuals = true; arg_flag = NONE; }
         else if (a == "-reject-outliers") arg_flag = RejectK;
         else if (a == "-reject-min-px") arg_flag = RejectPx;
@@ -498,6 +507,13 @@ int main(int argc, char *argv[]) {
             (arg_flag == Loo ? loo_f_max : reject_loo_f) = v;
             arg_flag = NONE;
         }
+        else if (arg_flag == SmoothLoo || arg_flag == SmoothRejectLoo) {
+            char *end = nullptr;
+            const double v = strtod(a.c_str(), &end);
+            if (*end != '\0' || a.empty() || !(v > 0.0) || !std::isfinite(v)) return print_usage(argv[0]);
+            (arg_flag == SmoothLoo ? smooth_loo_f : smooth_reject_loo_f) = v;
+            arg_flag = NONE;
+        }
         else if (arg_flag == RejectK || arg_flag == RejectPx) {
             const double v = stod(a);
             if (!(v > 0.0) && !(arg_flag == RejectPx && v == 0.0)) return print_usage(argv[0]);
@@ -524,6 +540,8 @@ int main(int argc, char *argv[]) {
     if (resample && (!smooth || live || resample_n < 2)) return print_usage(argv[0]);
     if (cv_resample && (!smooth || !smooth_cv || live || resample || resample_n < 2)) return print_usage(argv[0]);
     if (relative_to && (!smooth || live || !relative_set)) return print_usage(argv[0]);
+    if ((smooth_loo && !(smooth_loo_f > 0.0)) || (smooth_reject_loo && !(smooth_reject_loo_f > 0.0))) return print_usage(argv[0]);
+    if ((smooth_loo || smooth_reject_loo) && (!smooth || live || with_huber)) return print_usage(argv[0]);
     if (live && (!tracking_only || smooth || (live_args != 1 && live_args != 3) || (live_args == 1 && live_lag != 0))) return print_usage(argv[0]);
     if ((live_anchor_set || live_covariance) && (!live || arg_flag == Anchor)) return print_usage(argv[0]);
     if (live_anchor == AAR_TRACKER_ANCHOR_MARGINAL && (live_args != 3 || live_lag < 1)) return print_usage(argv[0]);
@@ -753,6 +771,29 @@ int main(int argc, char *argv[]) {
             const aar_smooth_report &sr = mcm.smooth_report;
             cout << "smooth: " << (smooth_cv ? "constant velocity, " : "") << sr.iterations << " LM iterations (" << sr.rejected_tries << " rejected tries, exit " << sr.stop_code << "), cost " << sr.initial_cost
                  << " -> " << sr.final_cost << " (data " << sr.final_data_cost << ", prior " << sr.final_prior_cost << ") in " << sr.seconds << " s" << endl;
+            const int model = smooth_cv ? AAR_SMOOTH_MODEL_CONSTANT_VELOCITY : AAR_SMOOTH_MODEL_RANDOM_WALK;
+            if (smooth_reject_loo) {
+                int64_t total = 0;
+                for (int round = 1; round <= 3; round++) {
+                    aar::MultiCamMapper::SmoothLoo lo;
+                    const int64_t dropped = mcm.smooth_reject_loo(smooth_sigma[0], smooth_sigma[1], model, smooth_sigma0[0], smooth_sigma0[1], smooth_reject_loo_f, &lo);
+                    cout << "smooth-reject-loo round " << round << ": largest F " << lo.report.max_f << ", " << dropped << " detections dropped" << endl;
+                    if (dropped == 0) break;
+                    total += dropped;
+                    mcm.track_smooth(smooth_sigma[0], smooth_sigma[1], model, smooth_sigma0[0], smooth_sigma0[1]);
+                }
+                cout << "smooth-reject-loo: " << total << " detections dropped, " << mcm.dataset()->num_obs << " left, cost " << mcm.smooth_report.final_cost << endl;
+            }
+            if (smooth_loo) {
+                const string lo_path = folder_path + "/final.smooth_loo.yaml";
+                aar::MultiCamMapper::SmoothLoo lo;
+                mcm.track_smooth_detection_loo(smooth_sigma[0], smooth_sigma[1], model, smooth_sigma0[0], smooth_sigma0[1], smooth_loo_f, lo);
+                if (aar_smooth_loo_write_yaml(lo_path.c_str(), mcm.dataset(), lo.F.data(), lo.q.data(), lo.leverage.data(), nullptr, lo.status.data(),
+                                              lo.keep.data(), &lo.report))
+                    throw runtime_error(aar_last_error());
+                cout << "smooth-loo: largest F " << lo.report.max_f << ", " << lo.report.rejected << " above " << smooth_loo_f << ", " << lo.report.undetermined
+                     << " undetermined, sigma2 " << lo.report.sigma2 << ", written to " << lo_path << endl;
+            }
         } catch (const exception &e) {
             cerr << "smoothing failed: " << e.what() << endl;
             return 6;

@@ -900,6 +900,159 @@ void MultiCamMapper::track_smooth_relative(double sigma_rot, double sigma_trans,
         throw std::runtime_error(aar_last_error());
 }
 
+// The per-detection layer of the smoothed track from the current poses, under track_smooth()'s prior
+namespace {
+struct SmoothBound {   // what every entry of the layer starts from: the bound problem, its pose vector, the frame ids as times, the parameters
+    aar_problem *pb = nullptr;
+    std::vector<double> x, time;
+    aar_smooth_params sp;
+};
+int32_t index_of_id(const int32_t *ids, int n, int id, const char *what) {
+    const int32_t *e = ids + n, *p = std::lower_bound(ids, e, id);
+    if (p == e || *p != id) throw std::invalid_argument(std::string("MultiCamMapper: no ") + what + " with id " + std::to_string(id));
+    return (int32_t)(p - ids);
+}
+}  // namespace
+
+#define AAR_SMOOTH_BOUND(b, who)                                                                                        \
+    if (!data_) throw std::runtime_error("MultiCamMapper::" who ": no data set");                                       \
+    mats2eVec();                                                                                                        \
+    hubberDelta = 10; /* as track_smooth() */                                                                           \
+    SmoothBound b;                                                                                                      \
+    b.pb = detail::bind_problem(this, b.x);                                                                             \
+    if (aar_problem_merge_z(b.pb, io_vec.data(), b.x.data())) throw std::runtime_error(aar_last_error());               \
+    b.time.resize(data_->num_frames);                                                                                   \
+    for (int f = 0; f < data_->num_frames; f++) b.time[f] = (double)data_->frame_ids[f];                                \
+    memset(&b.sp, 0, sizeof b.sp);                                                                                      \
+    b.sp.struct_size = sizeof b.sp;                                                                                     \
+    b.sp.sigma_rot = sigma_rot;                                                                                         \
+    b.sp.sigma_trans = sigma_trans;                                                                                     \
+    b.sp.frame_time = data_->num_frames ? b.time.data() : nullptr;                                                      \
+    b.sp.model = model;                                                                                                 \
+    b.sp.sigma_rot0 = sigma_rot0;                                                                                       \
+    b.sp.sigma_trans0 = sigma_trans0
+
+void MultiCamMapper::track_smooth_detection_leverage(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                                     SmoothLeverage &out) {
+    AAR_SMOOTH_BOUND(b, "track_smooth_detection_leverage");
+    const size_t N = (size_t)data_->num_obs, n1 = std::max<size_t>(N, 1);
+    out.leverage.assign(n1, NAN);
+    out.row_leverage.assign(8 * n1, NAN);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    if (aar_track_smooth_detection_leverage(b.pb, b.x.data(), &b.sp, out.leverage.data(), out.row_leverage.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.leverage.resize(N);
+    out.row_leverage.resize(8 * N);
+}
+
+void MultiCamMapper::track_smooth_detection_loo(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, double f_max,
+                                                SmoothLoo &out) {
+    AAR_SMOOTH_BOUND(b, "track_smooth_detection_loo");
+    const size_t N = (size_t)data_->num_obs, n1 = std::max<size_t>(N, 1);
+    out.loo_resid.assign(8 * n1, NAN);
+    for (std::vector<double> *v : {&out.q, &out.F, &out.cook, &out.leverage, &out.margin}) v->assign(n1, NAN);
+    out.status.assign(n1, 0);
+    out.keep.assign(n1, 1);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    aar_loo_rule rule;
+    rule.struct_size = (uint32_t)sizeof rule;
+    rule.f_max = f_max;
+    if (aar_track_smooth_detection_loo(b.pb, b.x.data(), &b.sp, f_max > 0.0 ? &rule : nullptr, out.loo_resid.data(), out.q.data(), out.F.data(),
+                                       out.cook.data(), out.leverage.data(), out.margin.data(), out.status.data(), out.keep.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.loo_resid.resize(8 * N);
+    for (std::vector<double> *v : {&out.q, &out.F, &out.cook, &out.leverage, &out.margin}) v->resize(N);
+    out.status.resize(N);
+    out.keep.resize(N);
+}
+
+void MultiCamMapper::track_smooth_predict_corners(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                                  const std::vector<int> &cam_ids, const std::vector<int> &marker_ids,
+                                                  const std::vector<double> &times, SmoothCorners &out, bool covariance) {
+    const size_t Q = cam_ids.size(), q1 = std::max<size_t>(Q, 1);
+    if (Q != marker_ids.size() || Q != times.size())
+        throw std::invalid_argument("MultiCamMapper::track_smooth_predict_corners: the id lists and the times differ in length");
+    AAR_SMOOTH_BOUND(b, "track_smooth_predict_corners");
+    std::vector<int32_t> qc(Q), qm(Q);
+    for (size_t i = 0; i < Q; i++) {
+        qc[i] = index_of_id(data_->cam_ids, data_->num_cams, cam_ids[i], "camera");
+        qm[i] = index_of_id(data_->marker_ids, data_->num_markers, marker_ids[i], "marker");
+    }
+    out.uv.assign(8 * q1, NAN);
+    out.cov.assign(covariance ? 64 * q1 : 0, NAN);
+    out.m2.clear();
+    out.status.assign(q1, 0);
+    out.segment.assign(q1, 0);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    if (aar_track_smooth_predict_corners(b.pb, b.x.data(), &b.sp, (int64_t)Q, qc.data(), qm.data(), times.data(), out.uv.data(),
+                                         covariance ? out.cov.data() : nullptr, out.status.data(), out.segment.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.uv.resize(8 * Q);
+    if (covariance) out.cov.resize(64 * Q);
+    out.status.resize(Q);
+    out.segment.resize(Q);
+}
+
+void MultiCamMapper::track_smooth_gate_detections(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                                  const std::vector<int> &cam_ids, const std::vector<int> &marker_ids,
+                                                  const std::vector<double> &times, const std::vector<float> &uv_obs, SmoothCorners &out) {
+    const size_t Q = cam_ids.size(), q1 = std::max<size_t>(Q, 1);
+    if (Q != marker_ids.size() || Q != times.size() || uv_obs.size() != 8 * Q)
+        throw std::invalid_argument("MultiCamMapper::track_smooth_gate_detections: the id lists, the times and uv / 8 differ in length");
+    AAR_SMOOTH_BOUND(b, "track_smooth_gate_detections");
+    std::vector<int32_t> qc(Q), qm(Q);
+    for (size_t i = 0; i < Q; i++) {
+        qc[i] = index_of_id(data_->cam_ids, data_->num_cams, cam_ids[i], "camera");
+        qm[i] = index_of_id(data_->marker_ids, data_->num_markers, marker_ids[i], "marker");
+    }
+    out.uv.assign(8 * q1, NAN);
+    out.cov.clear();
+    out.m2.assign(q1, NAN);
+    out.status.assign(q1, 0);
+    out.segment.assign(q1, 0);
+    memset(&out.report, 0, sizeof out.report);
+    out.report.struct_size = sizeof out.report;
+    if (aar_track_smooth_gate_detections(b.pb, b.x.data(), &b.sp, (int64_t)Q, qc.data(), qm.data(), times.data(), Q ? uv_obs.data() : nullptr,
+                                         out.uv.data(), out.m2.data(), out.status.data(), out.segment.data(), &out.report))
+        throw std::runtime_error(aar_last_error());
+    out.uv.resize(8 * Q);
+    out.m2.resize(Q);
+    out.status.resize(Q);
+    out.segment.resize(Q);
+}
+
+int64_t MultiCamMapper::smooth_reject_loo(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, double f_max,
+                                          SmoothLoo *out) {
+    SmoothLoo loo;
+    track_smooth_detection_loo(sigma_rot, sigma_trans, model, sigma_rot0, sigma_trans0, f_max, loo);
+    // of every frame only the detection with the largest F among those the rule rejects goes (the first of them on a tie), as reject_loo
+    std::vector<int64_t> worst((size_t)std::max(data_->num_frames, 1), -1);
+    for (size_t o = 0; o < loo.keep.size(); o++) {
+        if (loo.keep[o]) continue;
+        int64_t &w = worst[data_->obs_frame[o]];
+        if (w < 0 || loo.F[o] > loo.F[w]) w = (int64_t)o;
+    }
+    std::fill(loo.keep.begin(), loo.keep.end(), (uint8_t)1);
+    int64_t dropped = 0;
+    for (int64_t w : worst)
+        if (w >= 0) { loo.keep[w] = 0; dropped++; }
+    loo.report.rejected = dropped;
+    if (dropped > 0) {
+        aar_dataset *nd = nullptr;
+        if (aar_dataset_select_observations(data_, loo.keep.data(), &nd)) throw std::runtime_error(aar_last_error());
+        drop_problem();
+        aar_dataset_free(data_);
+        data_ = nd;
+        mats2eVec();
+    }
+    if (out) *out = std::move(loo);
+    return dropped;
+}
+#undef AAR_SMOOTH_BOUND
+
 // The pixel noise and the motion sigmas fitted to the sequence itself (aar_track_smooth_fit), under track_smooth()'s model
 // (the frame ids as the time axis).  The frame poses end as the smoothed track at the fitted values.
 void MultiCamMapper::fit_smooth_sigmas(double sigma_rot, double sigma_trans, SmoothFit &out, const aar_smooth_fit_params *fit) {

@@ -440,6 +440,40 @@ class MultiCamMapper {
     };
     void track_smooth_relative(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
                                const std::vector<std::pair<int32_t, int32_t>> &pairs, SmoothRelative &out);   // throws std::runtime_error on failure
+    // EXTENSION, no counterpart in the reference: the per-detection layer of the smoothed track at the current poses, with
+    // track_smooth()'s prior (the frame ids as its time axis), under the motion model AAR_SMOOTH_MODEL_*.  Everything is UNSCALED (multiply by
+    // report.sigma2).  Cameras and markers are named by ID, times are on the frame ids' axis.  All four throw std::runtime_error on failure
+    // (std::invalid_argument for an id that does not exist); track_smooth_detection_loo refuses a mapper set_with_huber(true).
+    struct SmoothLeverage {
+        std::vector<double> leverage, row_leverage;   // [num_obs], [num_obs][8]: trace and diagonal of C_i = G_i (H^-1)_ff G_i^T
+        aar_smooth_predict_report report = {};
+    };
+    void track_smooth_detection_leverage(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, SmoothLeverage &out);
+    struct SmoothLoo {
+        std::vector<double> loo_resid;                // [num_obs][8]
+        std::vector<double> q, F, cook, leverage, margin;   // [num_obs]
+        std::vector<uint8_t> status, keep;            // [num_obs]; keep = 0 where F > f_max (f_max <= 0: no rule)
+        aar_smooth_loo_report report = {};
+    };
+    void track_smooth_detection_loo(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, double f_max,
+                                    SmoothLoo &out);
+    struct SmoothCorners {
+        std::vector<double> uv, cov;                  // [n][8], [n][64] (empty without covariance); the gate: uv = the innovation
+        std::vector<double> m2;                       // [n] the gate's e^T (I + C)^-1 e, UNSCALED
+        std::vector<uint8_t> status;
+        std::vector<int32_t> segment;
+        aar_smooth_predict_report report = {};
+    };
+    void track_smooth_predict_corners(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                      const std::vector<int> &cam_ids, const std::vector<int> &marker_ids, const std::vector<double> &times,
+                                      SmoothCorners &out, bool covariance = true);
+    void track_smooth_gate_detections(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0,
+                                      const std::vector<int> &cam_ids, const std::vector<int> &marker_ids, const std::vector<double> &times,
+                                      const std::vector<float> &uv_obs, SmoothCorners &out);
+    // ... and the round of -smooth-reject-loo: of every frame the detection with the largest F above f_max is dropped from the data set (the
+    // problem is rebuilt on the next use).  Returns the number dropped; out (may be NULL): the report of the call, rejected = that number
+    int64_t smooth_reject_loo(double sigma_rot, double sigma_trans, int model, double sigma_rot0, double sigma_trans0, double f_max,
+                              SmoothLoo *out = nullptr);
     // EXTENSION, no counterpart in the reference: the corner noise and track_smooth()'s two sigmas fitted to the sequence itself by EM
     // (aar_track_smooth_fit), from the effective start values sigma_rot, sigma_trans.  The frame poses end as the smoothed
     // track at the fitted values; report.sigma_rot_eff / sigma_trans_eff are what track_smooth() and the live tracker take.  A mapper

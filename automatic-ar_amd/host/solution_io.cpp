@@ -390,16 +390,10 @@ int aar_leverage_write_yaml(const char *path, const aar_dataset *d, const double
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
 }
 
-int aar_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage, const double *det_err,
-                       const uint8_t *status, const uint8_t *keep, const aar_loo_report *rep) {
-    if (!path || !d || !rep || ((!F || !status || !keep) && d->num_obs > 0)) return set_error(AAR_ERR_INVALID, "aar_loo_write_yaml: null argument");
-    FILE *f = fopen(path, "w");
-    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
-    fprintf(f, "%%YAML:1.0\n---\n");
-    fprintf(f, "sigma2: %s\ndof: %lld\nnum_live_vars: %lld\nf_max: %s\nmax_f: %s\nundetermined: %lld\nrejected: %lld\n", fs_double_nf(rep->predict.sigma2).c_str(),
-            (long long)rep->dof, (long long)rep->predict.num_live_vars, fs_double_nf(rep->f_max).c_str(), fs_double_nf(rep->max_f).c_str(),
-            (long long)rep->undetermined, (long long)rep->rejected);
-    // per entity {detections, largest F that is a number, rejected}, in detection order
+// what the two leave-one-out reports share behind their scalars: per entity {detections, largest F that is a number, rejected} in detection
+// order, then the detections with keep = 0 or an UNDETERMINED status; closes f
+static int loo_yaml_body(FILE *f, const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage, const double *det_err,
+                         const uint8_t *status, const uint8_t *keep) {
     std::vector<double> cs(3 * (size_t)d->num_cams, 0.0), ms(3 * (size_t)d->num_markers, 0.0);
     for (int64_t o = 0; o < d->num_obs; o++)
         for (double *e : {cs.data() + 3LL * d->obs_cam[o], ms.data() + 3LL * d->obs_marker[o]}) {
@@ -424,6 +418,31 @@ int aar_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, 
     const bool good = !ferror(f);
     fclose(f);
     return good ? AAR_OK : set_error(AAR_ERR_IO, "write error on %s", path);
+}
+
+int aar_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage, const double *det_err,
+                       const uint8_t *status, const uint8_t *keep, const aar_loo_report *rep) {
+    if (!path || !d || !rep || ((!F || !status || !keep) && d->num_obs > 0)) return set_error(AAR_ERR_INVALID, "aar_loo_write_yaml: null argument");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "sigma2: %s\ndof: %lld\nnum_live_vars: %lld\nf_max: %s\nmax_f: %s\nundetermined: %lld\nrejected: %lld\n", fs_double_nf(rep->predict.sigma2).c_str(),
+            (long long)rep->dof, (long long)rep->predict.num_live_vars, fs_double_nf(rep->f_max).c_str(), fs_double_nf(rep->max_f).c_str(),
+            (long long)rep->undetermined, (long long)rep->rejected);
+    return loo_yaml_body(f, path, d, F, q, leverage, det_err, status, keep);
+}
+
+int aar_smooth_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage, const double *det_err,
+                              const uint8_t *status, const uint8_t *keep, const aar_smooth_loo_report *rep) {
+    if (!path || !d || !rep || ((!F || !status || !keep) && d->num_obs > 0)) return set_error(AAR_ERR_INVALID, "aar_smooth_loo_write_yaml: null argument");
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(AAR_ERR_IO, "Could not open a file in: %s for writing.", path);
+    fprintf(f, "%%YAML:1.0\n---\n");
+    fprintf(f, "sigma2: %s\ndata_cost: %s\nprior_cost: %s\ndof: %lld\nf_max: %s\nmax_f: %s\nundetermined: %lld\nrejected: %lld\nleverage_sum: %s\n",
+            fs_double_nf(rep->sigma2).c_str(), fs_double_nf(rep->data_cost).c_str(), fs_double_nf(rep->prior_cost).c_str(), (long long)rep->dof,
+            fs_double_nf(rep->f_max).c_str(), fs_double_nf(rep->max_f).c_str(), (long long)rep->undetermined, (long long)rep->rejected,
+            fs_double_nf(rep->leverage_sum).c_str());
+    return loo_yaml_body(f, path, d, F, q, leverage, det_err, status, keep);
 }
 
 int aar_detections_write(const char *path, const aar_dataset *d) {

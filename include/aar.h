@@ -944,6 +944,81 @@ typedef struct aar_smooth_relative_report {
 int aar_smooth_relative_validate(int32_t num_frames, const aar_smooth_params *, int64_t n_pairs, const int32_t *frame_a, const int32_t *frame_b);
 int aar_track_smooth_relative(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_pairs, const int32_t *frame_a,
                               const int32_t *frame_b, double *cross_cov, double *rel, double *rel_cov, aar_smooth_relative_report *report);
+/* Per-detection diagnostics of a SMOOTHED track: what aar_problem_predict_corners, _detection_leverage,
+ * _detection_loo and _gate_detections are to the bundle, with the smoother's own covariance.  Either model.  With z_f the frame poses of
+ * x_full, H the system aar_track_smooth_system2 returns at mu = 0 for the same arguments (the cameras and markers are constants, the motion
+ * prior is in), Sigma = H^-1 UNSCALED, cost = data_cost + prior_cost, nu = num_residuals - num_vars = 8 N - 6 and sigma2 = cost / nu as
+ * aar_smooth_covariance_report has them: for a detection i of frame f, u_i its four projected corners, G_i = du_i / dz_f (8 x 6, the
+ * smoother's own frame Jacobian, without the Huber weights) and C_i = G_i Sigma_ff G_i^T (8 x 8, symmetric to the bit).
+ * aar_track_smooth_detection_leverage, the problem's detections in reference order:
+ *   leverage[i] = tr(C_i), row_leverage[i][k] = C_i[k][k].  Without Huber  sum_i leverage_i = 6 F - tr(Sigma H_prior),  H_prior = H minus the
+ *   frames' data blocks (a frame without detections contributes nothing to the sum): what the prior determines is not the detections' to
+ *   determine.  With Huber the call is allowed and the identity is not claimed: Sigma carries the weights and G does not, as in the bundle.
+ * aar_track_smooth_detection_loo: the quantities of aar_problem_detection_loo with this C_i, this cost and this nu --
+ *   r_i = observed - u_i, loo_resid = (I - C_i)^-1 r_i, q = r_i^T (I - C_i)^-1 r_i, F = (q / 8) / ((cost - q) / (nu - 8)) (+inf where the
+ *   denominator is <= 0, NaN where nu <= 8), cook = w^T C_i w / (6 F sigma2), margin = the smallest pivot met, keep = 0 iff a rule is
+ *   given, status == 0 and F > f_max.  status bit 0 (AAR_PREDICT_BEHIND): outputs NaN, keep = 1.  Bit 2 (AAR_PREDICT_UNDETERMINED): a pivot
+ *   of I - C_i is <= 1e-6 or not finite; leverage and margin are written, the rest is NaN, keep = 1 -- the detection alone carries some
+ *   direction of its frame's pose: its frame has no other detection and no neighbour reaches it through the prior (one frame with one
+ *   detection).  Bit 1 is never set: a smoothed track whose chain succeeded has a block for every frame.  Every array may be NULL.
+ *   A problem created with_huber is AAR_ERR_UNSUPPORTED (the weights break the Gaussian data model the statistic rests on); a rule whose
+ *   f_max is not positive and finite is AAR_ERR_INVALID.
+ * aar_track_smooth_predict_corners: for any camera index, marker index and TIME the four corners at the pose aar_track_smooth_query2
+ *   reports for that time and C = G Sigma_t G^T with Sigma_t that query's 6 x 6 block.  sigma2 C is the corners' covariance and
+ *   sigma2 (C + I) the search window of a new detection at that time: the next frame, a camera that is not genlocked, a vsync.  At
+ *   (cam_i, marker_i, frame_time[f_i]) of the problem's own detections the diagonal of cov is row_leverage to the bit.  cov == NULL under
+ *   the random walk runs no selected inverse.  Duplicates are allowed; a query's bits depend on its triple and the track only.  Camera and
+ *   marker indices are checked as aar_predict_query_validate checks them, times as aar_smooth_query_validate; rel_motion != NULL is
+ *   AAR_ERR_UNSUPPORTED as in aar_track_smooth_query.  status bit 0: uv and cov NaN.
+ * aar_track_smooth_gate_detections: the same queries with observed corners uv_obs; innovation = uv_obs - u, m2 = e^T (I + C)^-1 e,
+ *   UNSCALED (m2 / sigma2 is chi-square with 8 degrees of freedom under the model); status as above.
+ * All four validate as every smoother entry does, are AAR_ERR_UNSUPPORTED behind a communicator, leave no LM state, do not modify x_full
+ * and write the caller's arrays only after everything succeeded; a non-positive pivot of the chain is AAR_ERR_NUMERIC with the chain's
+ * own message.  Two calls give the same bits.  The reports are size-versioned: the caller sets struct_size, at most that many bytes are
+ * filled; they may be NULL. */
+typedef struct aar_smooth_predict_report {
+    uint32_t struct_size;
+    int64_t num_residuals, num_vars;   /* of the problem as given, as aar_smooth_covariance_report */
+    double data_cost, prior_cost, sigma2;   /* 0 where no selected inverse ran */
+    int64_t num_queries, behind;       /* queries (the problem's detections for detection_leverage), those with status bit 0 */
+    double leverage_sum;               /* sum of the finite tr(C) in query order (gate_detections: 0) */
+    int32_t num_inside, num_on_frame, num_outside;   /* time queries, as aar_smooth_query_report */
+    int32_t launches;
+    double seconds;
+    double kernel_seconds;             /* the query kernel's own time between two events; 0 unless aar_set_kernel_profiling is on */
+} aar_smooth_predict_report;
+typedef struct aar_smooth_loo_report {
+    uint32_t struct_size;
+    int64_t num_residuals, num_vars;
+    double data_cost, prior_cost, sigma2;
+    int64_t dof;                       /* nu = num_residuals - num_vars */
+    int64_t behind, undetermined, rejected;   /* detections with status bit 0 / bit 2 / keep = 0 */
+    double f_max, max_f;               /* the rule's (+inf without one); the largest F that is not NaN (NaN when there is none) ... */
+    int64_t argmax_f;                  /* ... and its detection (-1) */
+    double leverage_sum;               /* sum of the finite leverages in detection order */
+    int32_t launches;
+    double seconds;
+    double kernel_seconds;             /* as aar_smooth_predict_report */
+} aar_smooth_loo_report;
+int aar_track_smooth_detection_leverage(aar_problem *, const double *x_full, const aar_smooth_params *, double *leverage /* [N] */,
+                                        double *row_leverage /* [N][8], may be NULL */, aar_smooth_predict_report *report);
+int aar_track_smooth_detection_loo(aar_problem *, const double *x_full, const aar_smooth_params *, const aar_loo_rule *rule /* may be NULL */,
+                                   double *loo_resid /* [N][8] */, double *q, double *F, double *cook, double *leverage, double *margin /* [N] */,
+                                   uint8_t *status, uint8_t *keep /* [N] */, aar_smooth_loo_report *report);
+int aar_track_smooth_predict_corners(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_query, const int32_t *q_cam,
+                                     const int32_t *q_marker, const double *q_time, double *uv /* [n][8] */, double *cov /* [n][64] or NULL */,
+                                     uint8_t *status, int32_t *segment /* [n] or NULL, as aar_track_smooth_query */,
+                                     aar_smooth_predict_report *report);
+int aar_track_smooth_gate_detections(aar_problem *, const double *x_full, const aar_smooth_params *, int64_t n_query, const int32_t *q_cam,
+                                     const int32_t *q_marker, const double *q_time, const float *uv_obs /* [n][8] */,
+                                     double *innovation /* [n][8] */, double *m2 /* [n] */, uint8_t *status, int32_t *segment,
+                                     aar_smooth_predict_report *report);
+/* YAML (the dialect of aar_loo_write_yaml) of a smoothed track's leave-one-out report, of a single-GPU problem created from d: the report's
+ * scalars (sigma2, data_cost, prior_cost, dof, f_max, max_f, undetermined, rejected, leverage_sum); per camera id and marker id
+ * {detections, max_f, rejected}; the detections with keep = 0 or an UNDETERMINED status as (frame id, camera id, marker id, F, q, leverage,
+ * error).  F, status and keep are required when d has detections; q, leverage and det_err may be NULL (.nan).  Host code. */
+int aar_smooth_loo_write_yaml(const char *path, const aar_dataset *d, const double *F, const double *q, const double *leverage,
+                              const double *det_err, const uint8_t *status, const uint8_t *keep, const aar_smooth_loo_report *report);
 
 /* Live tracker (no counterpart in the reference as one object: it is the body of apps/track.cpp's loop, :102-136, kept on the device; DESIGN.md
  * section 17).  Created from a solution -- cameras, markers, cam_mats, marker_size and the roots; the solution's own frames and detections are
